@@ -13,10 +13,15 @@ Weights are seeded random tensors of the reference architectures (no checkpoints
 Frames shard by image: each rank runs its own frames (weak scaling), weights are broadcast from
 rank 0 over RCCL at start-up and the per-frame result records are all-gathered at the end.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (conv FLOPs of the timed region over its wall clock = the
-in-situ figure, plus the dominant kernel alone with HIP events), "latency_ms" (per-frame p50 / p95 with all frames in
-flight and strictly one at a time), "h2d_inclusive" (the same run with every frame uploaded from pinned host memory
-inside the timed region -- never `value`), "rccl" (N > 1) and "cpu_baseline" (oracle on the host cores, N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, runs the W warm-up steps, times the K steps and reports them
+("latency_ms" = per-frame p50 / p95 with all frames in flight, "rccl" for N > 1).  With --full the line also carries:
+"repeats" / "value_settled" (more K-step regions back to back), "roofline" (conv FLOPs of the timed region over its wall
+clock = the in-situ figure, plus the dominant kernel alone with HIP events), one-frame-at-a-time latency, clocks under load,
+"h2d_inclusive" (the same run with every frame uploaded from pinned host memory inside the timed region -- never `value`),
+the other precisions and served configurations, the flip rate and "cpu_baseline" (oracle on the host cores); all N = 1 only
+except "repeats" and "roofline".
+
+--dump-outputs DIR writes what the timed path returned for the LAST timed step (rank 0's frames) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -58,12 +63,17 @@ def parse_args():
     ap.add_argument("--no-side-runs", action="store_true", help="skip the one-frame-at-a-time and H2D-inclusive runs")
     ap.add_argument("--no-flip-rate", action="store_true", help="skip the planted-margin flip-rate object")
     ap.add_argument("--no-served-legs", action="store_true", help="skip the configs[2] leg (fp16, 28 frames per launch x 3 streams) and the other_configs lines")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="K-step timed regions run back to back: `value` is the FIRST (the contract's region), \"repeats\" "
-                         "reports p50 / min / max over all of them")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="--full: K-step timed regions run back to back (default 5): `value` is the FIRST (the contract's region), "
+                         "\"repeats\" reports p50 / min / max over all of them")
     ap.add_argument("--insitu", default="", metavar="PATH",
-                    help="N=1: after the timed regions, time every convolution WHILE the frames are in flight (s_memtime "
+                    help="--full, N=1: after the timed regions, time every convolution WHILE the frames are in flight (s_memtime "
                          "stamps written by the kernels themselves) and write the per-layer table to PATH")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every other measurement of the line (repeats, side runs, roofline, other "
+                         "precisions, served legs, flip rate, CPU baseline; each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the arrays the timed path returned in its last timed step as DIR/<name>.npy")
     ap.add_argument("--partition", type=int, default=0,
                     help="give each of the --streams frames in flight its own 1/PARTITION slice of the CUs of every "
                          "XCD (hipExtStreamCreateWithCUMask); 0 = ordinary streams sharing the chip")
@@ -79,7 +89,14 @@ def parse_args():
     ap.add_argument("--precision", choices=["f32", "f16", "f16r", "bf16x3"], default="bf16x3",
                     help="matrix-core operand precision: bf16x3 = fp32-accurate 3-way bf16 operand split (default, parity-grade); f32 = fp32 MFMA; f16 = fp16 "
                          "MFMA operands with fp32 accumulation (BASELINE configs[2])")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not a.full and ((a.repeats or 1) > 1 or a.insitu):
+        ap.error("--repeats > 1 and --insitu are measurements beyond the headline: add --full")
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    return a
 
 
 def cpu_baseline(seconds: float, kp3d, cam_K):
@@ -692,6 +709,37 @@ def served_leg(ys, ks, local, batch, streams, precision, steps, kp3d, cam_K, lab
     return res, gflop, alg_bytes
 
 
+def dump_outputs(path, recs, outs):
+    """--dump-outputs: what a caller of the timed path receives for the frames of one step, as float32 / float64 .npy files.
+    `recs` [batch, 316] are the device records; their int32 fields (detector index, key-point arg-max pixel) are written as
+    their integer values in float64, not as the bits.  `outs` are finish_record's dicts; NaN where a frame has no detection
+    or no pose."""
+    os.makedirs(path, exist_ok=True)
+    recs = np.ascontiguousarray(recs, dtype=np.float32)
+    r64 = recs.astype(np.float64)
+    ints = [0] + list(range(16, recs.shape[1], 6))
+    r64[:, ints] = recs[:, ints].view(np.int32)
+    n = len(outs)
+    arrays = {"records": r64, "boxes": np.full((n, 4), np.nan, np.float32), "box_scores": np.full((n,), np.nan, np.float32),
+              "keypoints": np.full((n, 50, 2), np.nan, np.float32), "kp_scores": np.full((n, 50), np.nan, np.float32),
+              "proposal_scores": np.full((n,), np.nan, np.float32),
+              "cam_R": np.full((n, 3, 3), np.nan, np.float64), "cam_t": np.full((n, 3), np.nan, np.float64)}
+    for b, o in enumerate(outs):
+        if o.get("boxes") is not None:
+            arrays["boxes"][b] = np.asarray(o["boxes"]).reshape(4)
+            arrays["box_scores"][b] = np.asarray(o["scores"]).reshape(-1)[0]
+        if o["result"]:
+            r = o["result"][0]
+            arrays["keypoints"][b] = np.asarray(r["keypoints"]).reshape(50, 2)
+            arrays["kp_scores"][b] = np.asarray(r["kp_score"]).reshape(50)
+            arrays["proposal_scores"][b] = np.asarray(r["proposal_score"]).reshape(-1)[0]
+        if len(o["cam_R"]):
+            arrays["cam_R"][b] = np.asarray(o["cam_R"]).reshape(3, 3)
+            arrays["cam_t"][b] = np.asarray(o["cam_t"]).reshape(3)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     a = parse_args()
     import torch
@@ -763,6 +811,7 @@ def main():
     pinned = [torch.empty((a.batch, pipe.results.shape[1]), dtype=torch.float32).pin_memory() for _ in range(NS)]
     events = [torch.cuda.Event() for _ in range(NS)]
     records = np.zeros((a.steps, a.batch, pipe.results.shape[1]), np.float32)
+    last_outs = []                 # finish_record's dicts of the last timed step (--dump-outputs)
     stats = {"det": 0, "pose": 0}
     t_issue = np.zeros(max(a.steps, 1))
     lat = {"on": False, "ms": []}
@@ -789,6 +838,8 @@ def main():
             if keep:
                 stats["det"] += out.get("boxes") is not None
                 stats["pose"] += len(out["result"]) > 0
+                if i == a.steps - 1:
+                    last_outs.append(out)
         if keep:
             records[i] = rec
 
@@ -826,6 +877,8 @@ def main():
     lat_flight = np.array(lat["ms"]) if lat["ms"] else np.zeros(1)
     rank_fps = bpd.gather_floats(a.steps * a.batch / t_own)
     rank_cpu_ms = bpd.gather_floats(cpu_own / (a.steps * a.batch) * 1e3)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, records[-1], last_outs)
 
     # ---- more K-step regions, back to back, each bracketed like the first (barrier + synchronize both sides, max over
     # ranks): a single 20-step region is a 20 ms window
@@ -850,7 +903,7 @@ def main():
     # ---- side measurements on the same pipelines (never `value`): strictly one frame at a time, and the same
     # multi-frame run with every frame uploaded from pinned host memory inside the timed region
     side = {}
-    if world == 1 and not a.no_side_runs:
+    if a.full and world == 1 and not a.no_side_runs:
         n1 = min(a.steps, 100)
 
         def one_at_a_time(prefetch):
@@ -917,9 +970,8 @@ def main():
             "protocol_version": 2,
             "value_definition": "K timed steps right behind exactly W warm-up steps, frames RESIDENT IN HBM when the timed region starts (the "
                                 "bench contract of this tier: the PCIe-inclusive rate is never `value`; SURVEY 8(d)'s upload-inclusive figure is "
-                                "`h2d_inclusive` beside it, within noise of `value`); compare across rounds on `value_settled`",
+                                "`h2d_inclusive` beside it under --full, within noise of `value`); compare across rounds on `value_settled` (--full)",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "warmup_steps_run": warmup_run, "ms_per_step": round(el / a.steps * 1e3, 4),
-            "value_settled": round(float(np.percentile([v for v, fb in zip(region_fps, frames_before) if fb >= 60] or region_fps, 50)), 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": {"f32": "f32", "f16": "f16 MFMA operands, f32 accumulate and activations",
                       "f16r": "f16 MFMA operands, f32 accumulate, fp16 skip connections (residuals read from the fp16 operand planes)",
@@ -939,19 +991,21 @@ def main():
                            "definition": "frame handed to the stream -> its record (post-processing input) on the host",
                            **({"one_frame_at_a_time": side["single"]} if "single" in side else {})},
             **({"clocks_under_load": side["clocks"]} if "clocks" in side else {}),
-            "repeats": {"regions": len(region_fps), "steps_each": a.steps, "fps": [round(v, 2) for v in region_fps],
-                        "p50": round(float(np.percentile(region_fps, 50)), 2), "min": round(min(region_fps), 2),
-                        "max": round(max(region_fps), 2), "frames_run_before_each": frames_before,
-                        "note": "`value` is region 0 (right behind the commanded warm-up); `value_settled` = p50 of the regions that started after >= 60 frames"},
             "detections": stats["det"], "poses": stats["pose"],
             "host_cpu_ms_per_frame": round(rank_cpu_ms[0], 3),
             "records_gathered": int((gathered[:, 0].view(np.int32) >= -1).sum()) if gathered is not None else 0,
         }
         assert gathered.shape == (frames_total, records.shape[-1])
-        t1 = time.perf_counter()
-        for _ in range(200):
-            finish_record(records[0, 0], "x.png", kp3d, cam_K)
-        out["host_post_ms_per_frame"] = round((time.perf_counter() - t1) / 200 * 1e3, 4)
+        if a.full:
+            out["value_settled"] = round(float(np.percentile([v for v, fb in zip(region_fps, frames_before) if fb >= 60] or region_fps, 50)), 2)
+            out["repeats"] = {"regions": len(region_fps), "steps_each": a.steps, "fps": [round(v, 2) for v in region_fps],
+                              "p50": round(float(np.percentile(region_fps, 50)), 2), "min": round(min(region_fps), 2),
+                              "max": round(max(region_fps), 2), "frames_run_before_each": frames_before,
+                              "note": "`value` is region 0 (right behind the commanded warm-up); `value_settled` = p50 of the regions that started after >= 60 frames"}
+            t1 = time.perf_counter()
+            for _ in range(200):
+                finish_record(records[0, 0], "x.png", kp3d, cam_K)
+            out["host_post_ms_per_frame"] = round((time.perf_counter() - t1) / 200 * 1e3, 4)
         if "h2d" in side:
             out["h2d_inclusive"] = side["h2d"]
         if world > 1:
@@ -962,7 +1016,7 @@ def main():
                            "host_cores": os.cpu_count(),
                            "collectives": "broadcast of 2 fp32 weight streams (246 + 239 MB) at start-up, all_gather of "
                                           "316-float records, barriers around the timed region"}
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         rf = roofline(det, pose, a.batch)
         # IN-SITU figure = the convolution FLOPs of the timed steps over the wall clock of the timed region (all frames
         # in flight, per GPU): kernel time per step <= ms_per_step holds by construction
@@ -981,7 +1035,7 @@ def main():
         out["roofline"]["hbm"] = hbm_block(rf["algorithmic_bytes_per_step"], out["value"] / world, a.batch, a.precision)
     if rank == 0 and world == 1 and a.insitu:
         out.setdefault("roofline", {})["insitu"] = insitu_layers(dets, poses, run, S, a.batch, a.insitu, a.precision)
-    if rank == 0 and world == 1 and a.other_modes:
+    if a.full and rank == 0 and world == 1 and a.other_modes:
         # the opt-in precisions on the same workload, for the record: 4 frames in flight, same
         # graph pipeline (re-captured on the precision change), a short timed run each
         other = {}
@@ -1003,7 +1057,7 @@ def main():
         other["note"] = ("bf16x3 = fp32-accurate (exact 3-way bf16 operand split, passes the whole parity suite); "
                          "f16 = fp16 operands (stated-tolerance mode, BASELINE configs[2])")
         out["other_precisions"] = other
-    if rank == 0 and world == 1 and not a.no_served_legs and len(streams) >= 4 and not a.partition:
+    if a.full and rank == 0 and world == 1 and not a.no_served_legs and len(streams) >= 4 and not a.partition:
         # BASELINE configs[2] on the driver's clock: fp16 MFMA operands, 28 crops / frames per launch, 3 streams
         c2, gf, ab = served_leg(ys, ks, local, 28, streams[:3], "f16", max(30, min(a.steps, 60)), kp3d, cam_K,
                                 "BASELINE configs[2]: batched inference, 28 frames per launch x 3 streams, fp16 MFMA conv path "
@@ -1036,11 +1090,11 @@ def main():
             r_["roofline_frac"] = round(gf_ * r_["value"] / 1e3 / {"f32": PEAK_FP32_MFMA_TFLOPS, "bf16x3": PEAK_BF16X3_TFLOPS}.get(a.precision, PEAK_F16_MFMA_TFLOPS), 4)
             oc.append(r_)
         out["other_configs"] = oc
-    if rank == 0 and world == 1 and not a.no_flip_rate:
+    if a.full and rank == 0 and world == 1 and not a.no_flip_rate:
         # low-margin flip rate of the arg-max stages per arithmetic (betapose_amd/fliprate.py; asserted in tests/test_gpu_flip_rate.py)
         from betapose_amd import fliprate
         out["flip_rate"] = fliprate.measure(device="cuda:%d" % local, trials=2)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_seconds, kp3d, cam_K)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -144,10 +144,9 @@ def test_golden_frame_keypoints_product_equals_oracle():
 
 def test_designated_keypoints_from_reference_assets():
     """The only real data fixtures of the reference: 1_keypoint_designator/assets/sifts/*.ply (50 3-D key points in
-    mm).  Build-container only -- the GPU box has no /root/reference."""
-    ply = "/root/reference/1_keypoint_designator/assets/sifts/1.ply"
-    if not os.path.exists(ply):
-        pytest.skip("reference assets not present")
+    mm); object 1's file is stored as tests/golden/sifts_1.ply."""
+    import helpers
+    ply = os.path.join(helpers.GOLD, "sifts_1.ply")
     lines = open(ply).read().split("\n")
     start = lines.index("end_header") + 1
     pts = np.array([[float(v) for v in ln.split()[:3]] for ln in lines[start:start + 50] if ln.strip()]) * 0.001

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round-5 verdict item 6 as a per-layer plan: the small 3x3 / stride-1 layers of the bf16x3 mode on operand planes their producers write (BP_B3_MIX =
 # largest map, pixels per image, that takes the plane path), A/B on one box against the default plan: frames/s, clock, joules per frame
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 2"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 2"
 val() { python -c "
 import sys, json
 for l in sys.stdin:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of an environment switch in the whole pipeline: tools/ab_env.sh reps VAR   (alternates VAR unset / VAR=1)
 reps=$1; var=$2
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-side-runs --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 3"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-side-runs --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 3"
 for rep in $(seq $reps); do
 for on in 0 1; do
   if [ $on = 1 ]; then export $var=1; else unset $var; fi

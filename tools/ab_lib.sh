@@ -2,7 +2,7 @@
 # A/B of two builds of the library on the configs[2] shape (28 frames per launch x 3 streams), one box: tools/ab_lib.sh <other .so> [reps] [precisions]
 # alternates BP_LIB=<other .so> with the product library; frames/s, clock, socket power, joules per frame
 LIB=$1; reps=${2:-2}; shift; shift
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
 val() { python -c "
 import sys, json
 for l in sys.stdin:

@@ -4,7 +4,7 @@
 # a timing experiment with wrong results: the detector sees an unwritten input).   tools/ab_resize.sh [reps]
 reps=${1:-3}
 export BP_LIB=betapose_amd/libbetapose_hip_exp.so
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-side-runs --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 3"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-side-runs --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 3"
 for rep in $(seq $reps); do
 for on in 0 1; do
   if [ $on = 1 ]; then export BP_ABLATE_RESIZE=1; else unset BP_ABLATE_RESIZE; fi

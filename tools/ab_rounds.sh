@@ -6,7 +6,8 @@ reps=${1:-2}
 B="--no-cpu-baseline --no-flip-rate --no-side-runs --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 3"
 for rep in $(seq $reps); do
 for tree in tools/_r04_tree .; do
-  python $tree/bench.py $B 2>/dev/null | python -c "
+  # (--full: this tree's bench runs the repeats and the served legs only behind it; older trees have no such option)
+  python $tree/bench.py $B $(grep -q -- '"--full"' $tree/bench.py && echo --full) 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

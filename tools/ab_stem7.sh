@@ -1,6 +1,6 @@
 #!/bin/bash
 # the fp16 7x7 stem in the configs[2] pipeline, A/B on one box (BP_NO_STEM7=1: the fp32 MFMA kernel as before): frames/s, clock, joules per frame
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
 val() { python -c "
 import sys, json
 for l in sys.stdin:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # configs[2] (28 frames per launch x 3 streams): clocks / socket power / limiter / joules per frame with and without the round-6 kernels, one box
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --batch 28 --streams 3 --steps 60 --warmup 10 --repeats 2"
 val() { python -c "
 import sys, json
 for l in sys.stdin:

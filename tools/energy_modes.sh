@@ -1,6 +1,6 @@
 #!/bin/bash
 # clocks / power / throttle reason / joules per frame per mode (bench.py clocks_under_load), one box
-B="python bench.py --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 2"
+B="python bench.py --full --no-cpu-baseline --no-served-legs --no-flip-rate --no-roofline --other-modes= --steps 200 --warmup 60 --repeats 2"
 val() { python -c "
 import sys, json
 for l in sys.stdin:
