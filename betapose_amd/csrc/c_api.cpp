@@ -19,6 +19,10 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
                      double confidence, double* R, double* t, unsigned char* inlier_mask);
 int pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, const float* scores, int n, int K,
              int* out_pick, float* out_pose, float* out_score, float* out_prop);
+// pose_metrics.hip
+int pose_error_blocks(int n);
+void launch_pose_errors(const double* model, int n, const double* gt, const double* est, int P, const double* K,
+                        int want, double* partial, double* out, hipStream_t s);
 }
 
 static thread_local std::string g_err;
@@ -482,6 +486,23 @@ int bp_resize_bicubic(const uint8_t* d_in, int batch, int H, int W, int oh, int 
     bp::launch_resize_bicubic(d_in, batch, H, W, tmp, d_out_nhwc, d_out_u8, oh, ow, t, swap_rb, s);
     BP_HIP(hipGetLastError());
     BP_HIP(hipStreamSynchronize(s));   // tables live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* K, int want,
+                   double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_gt && d_est && d_out, "null argument");
+    BP_CHECK(n > 0 && P > 0, "n and P must be positive");
+    BP_CHECK(want >= 1 && want <= 7, "want must be a non-empty mask of 1 (ADD), 2 (ADD-S), 4 (2-D)");
+    BP_CHECK(K || !(want & 4), "K is required for the 2-D projection error");
+    hipStream_t s = (hipStream_t)stream;
+    bp::Arena a;
+    double* partial = (double*)a.alloc_bytes((size_t)P * bp::pose_error_blocks(n) * 3 * sizeof(double));
+    bp::launch_pose_errors(d_model, n, d_gt, d_est, P, K, want, partial, d_out, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // partials live in a local arena
     return 0;
     BP_CATCH
 }

@@ -1,4 +1,4 @@
-"""Evaluation metrics and ground-truth helpers of the harness (utils/metrics.py:10-22,77-127;
+"""Evaluation metrics and ground-truth helpers of the harness (utils/metrics.py:10-33,77-127;
 utils/model.py:29-46,79-85; utils/sixd.py:60-111), numpy f64."""
 from __future__ import annotations
 
@@ -20,6 +20,73 @@ def projection_error_2d(gt_pose, est_pose, model, cam):
     e = cam @ est_pose[:3] @ m.T
     g, e = g / g[2], e / e[2]
     return float(np.mean(np.linalg.norm(g[:2].T - e[:2].T, axis=1)))
+
+
+def add_s_err(gt_pose, est_pose, model):
+    """ADD-S, the LineMod score of symmetric objects: the mean over the ground-truth model points of the distance to
+    the CLOSEST estimated model point, mean_i min_j |T_g x_i - T_e x_j|.  The reference has it only as the debug loop
+    it keeps commented out in add_err (utils/metrics.py:23-33), which stops after the first five ground-truth vertices
+    (``if idx_A > 4: break``); that truncation is not followed here -- every vertex is a query and every vertex a
+    candidate.  Brute force in the camera frame over chunks of queries so memory stays bounded (``est == gt`` gives
+    exactly 0).  ``bp_pose_errors`` computes the same on the GPU, in the ground-truth object frame."""
+    model = np.asarray(model, dtype=np.float64)
+    gt_pose, est_pose = np.asarray(gt_pose, dtype=np.float64), np.asarray(est_pose, dtype=np.float64)
+    qry = model @ gt_pose[:3, :3].T + gt_pose[:3, 3]
+    cand = model @ est_pose[:3, :3].T + est_pose[:3, 3]
+    n = len(model)
+    step = max(1, (1 << 16) // max(n, 1))       # ~64 Ki distances (512 KB, cache-resident) per chunk
+    best = np.empty(n)
+    for s in range(0, n, step):
+        q = qry[s:s + step]
+        d = np.square(q[:, 0:1] - cand[None, :, 0])
+        d += np.square(q[:, 1:2] - cand[None, :, 1])
+        d += np.square(q[:, 2:3] - cand[None, :, 2])
+        best[s:s + step] = d.min(axis=1)
+    return float(np.mean(np.sqrt(best)))
+
+
+WANT_ADD, WANT_ADDS, WANT_2D = 1, 2, 4      # bp_pose_errors' `want` bits
+
+
+def pose_errors(gt_poses, est_poses, model, cam, device=None, want=WANT_ADD | WANT_ADDS | WANT_2D):
+    """(ADD, ADD-S, 2-D projection error) of P pose pairs of one model as three float64 arrays [P] (metres, metres,
+    pixels).  Poses are [P, 4, 4] or [P, 3, 4]; ``cam`` the 3x3 K of the 2-D error.  ``device=None``: the host numpy
+    functions pair by pair; a torch device: one ``bp_pose_errors`` call on it.  ``want`` selects the columns
+    (WANT_* bits); the others are NaN."""
+    gt = np.asarray(gt_poses, dtype=np.float64).reshape(-1, *np.shape(gt_poses)[-2:])[:, :3, :4]
+    est = np.asarray(est_poses, dtype=np.float64).reshape(-1, *np.shape(est_poses)[-2:])[:, :3, :4]
+    if gt.shape != est.shape:
+        raise ValueError("gt_poses and est_poses differ in shape: %s vs %s" % (gt.shape, est.shape))
+    model = np.ascontiguousarray(model, dtype=np.float64).reshape(-1, 3)
+    P = len(gt)
+    out = np.full((P, 3), np.nan)
+    if P == 0:
+        return out[:, 0], out[:, 1], out[:, 2]
+    if device is None:
+        for p in range(P):
+            g, e = np.vstack((gt[p], [0, 0, 0, 1])), np.vstack((est[p], [0, 0, 0, 1]))
+            if want & WANT_ADD:
+                out[p, 0] = add_err(g, e, model)
+            if want & WANT_ADDS:
+                out[p, 1] = add_s_err(g, e, model)
+            if want & WANT_2D:
+                out[p, 2] = projection_error_2d(g, e, model, cam)
+        return out[:, 0], out[:, 1], out[:, 2]
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    dev = torch.device(device)
+    K = np.ascontiguousarray(cam, dtype=np.float64).reshape(9) if want & WANT_2D else None
+    with torch.cuda.device(dev):
+        d_model = torch.from_numpy(model).to(dev)
+        d_gt = torch.from_numpy(np.ascontiguousarray(gt.reshape(P, 12))).to(dev)
+        d_est = torch.from_numpy(np.ascontiguousarray(est.reshape(P, 12))).to(dev)
+        d_out = torch.from_numpy(out).to(dev)
+        _lib.check(_lib.lib().bp_pose_errors(_lib.ptr(d_model), len(model), _lib.ptr(d_gt), _lib.ptr(d_est), P,
+                                             _lib.ptr(K), int(want), _lib.ptr(d_out),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+        out = d_out.cpu().numpy()
+    return out[:, 0], out[:, 1], out[:, 2]
 
 
 def rot_error(gt_pose, est_pose):
@@ -124,11 +191,14 @@ def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
 
 
 def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model_vertices, cam_K, diameter_mm,
-                     pixel_thresh: float = 5.0):
+                     pixel_thresh: float = 5.0, symmetric: bool = False, device=None):
     """The metric loop of betapose_evaluate.py:204-266.  ``gt_frames[nr]`` = list of ``{'pose': 4x4, 'bbox': [x, y, w, h]}`` (one per ground-truth
     annotation compared; a bare dict is accepted for one).
-    Returns dict(mean_add, mean_2d_acc, mean_iou, n)."""
-    add_errs, adds, proj, ious = [], [], [], []
+    Returns dict(mean_add, mean_2d_acc, mean_iou, mean_add_err_mm, n).  ``symmetric``: also ADD-S (add_s_err) --
+    ``mean_adds``, the fraction under diameter / 10 (the ADD rule of betapose_evaluate.py:246-249), and
+    ``mean_adds_err_mm``.  ``device``: every scored pair's errors in one bp_pose_errors call on that torch device
+    instead of numpy."""
+    ious, gts, ests = [], [], []
     for f in final_result:
         nr = int(os.path.basename(f["imgname"])[0:-4])
         if nr not in gt_frames:
@@ -148,14 +218,25 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
             pose[:3, :3] = f["cam_R"]
             pose[:3, 3] = np.asarray(f["cam_t"])[:, 0]
             if i >= 0.5:
-                a = add_err(gt["pose"], pose, model_vertices) * 1000
-                add_errs.append(a)
-                adds.append(a < diameter_mm / 10)
-                proj.append(projection_error_2d(gt["pose"], pose, model_vertices, cam_K))
-    return {"mean_add": float(np.mean(adds)) if adds else float("nan"),
-            "mean_2d_acc": float(np.mean(np.array(proj) < pixel_thresh)) if proj else float("nan"),
-            "mean_iou": float(np.mean(np.array(ious) > 0.5)) if ious else float("nan"),
-            "mean_add_err_mm": float(np.mean(add_errs)) if add_errs else float("nan"), "n": len(ious)}
+                gts.append(gt["pose"])
+                ests.append(pose)
+    if device is None:
+        add_errs = [add_err(g, e, model_vertices) * 1000 for g, e in zip(gts, ests)]
+        proj = [projection_error_2d(g, e, model_vertices, cam_K) for g, e in zip(gts, ests)]
+        adds_errs = [add_s_err(g, e, model_vertices) * 1000 for g, e in zip(gts, ests)] if symmetric else []
+    else:
+        a, s, pr = pose_errors(np.reshape(gts, (-1, 4, 4)), np.reshape(ests, (-1, 4, 4)), model_vertices, cam_K, device,
+                               WANT_ADD | WANT_2D | (WANT_ADDS if symmetric else 0))
+        add_errs, proj, adds_errs = list(a * 1000), list(pr), list(s * 1000) if symmetric else []
+    adds = [a < diameter_mm / 10 for a in add_errs]
+    m = {"mean_add": float(np.mean(adds)) if adds else float("nan"),
+         "mean_2d_acc": float(np.mean(np.array(proj) < pixel_thresh)) if proj else float("nan"),
+         "mean_iou": float(np.mean(np.array(ious) > 0.5)) if ious else float("nan"),
+         "mean_add_err_mm": float(np.mean(add_errs)) if add_errs else float("nan"), "n": len(ious)}
+    if symmetric:
+        m["mean_adds"] = float(np.mean([a < diameter_mm / 10 for a in adds_errs])) if adds_errs else float("nan")
+        m["mean_adds_err_mm"] = float(np.mean(adds_errs)) if adds_errs else float("nan")
+    return m
 
 
 class Model3D:

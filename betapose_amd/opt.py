@@ -39,6 +39,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='occlusion_evaluate.py: comma-separated object ids evaluated in ONE run, e.g. 1,5,6,8,9,10,11,12 -- '
                         'units of work are (frame, object) pairs, every object keeps its weights resident, frames are '
                         'decoded once')
+    p.add_argument('--symmetric_ids', default='', type=str,
+                   help='comma-separated object ids scored with ADD-S as well (LineMod\'s symmetric objects are 10, eggbox, '
+                        'and 11, glue): one more line per such object, "Mean add-s accuracy for seq XX is: ...", computed '
+                        'on the run\'s GPU (metrics.pose_errors)')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
     p.add_argument('--synthetic', type=int, default=0, help='run on N seeded synthetic frames / weights')
     p.add_argument('--synth_weights', default=False, action='store_true',
@@ -83,6 +87,11 @@ _COMPAT_FLAGS = [
 
 opt = build_parser().parse_args([])
 opt.num_classes = 80            # opt.py:150
+
+
+def id_list(text: str):
+    """'10, 11' -> [10, 11] (--obj_ids, --symmetric_ids)."""
+    return [int(v) for v in text.split(",") if v.strip()]
 
 
 def parse_args(argv=None):

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from betapose_amd import dist as bpd, metrics, synth  # noqa: E402
-from betapose_amd.opt import parse_args  # noqa: E402
+from betapose_amd.opt import id_list, parse_args  # noqa: E402
 
 
 def load_sixd_gt(base, obj_id, seq_id=None):
@@ -64,6 +64,7 @@ def load_sixd_gt(base, obj_id, seq_id=None):
 
 def main():
     args = parse_args()
+    import torch
     from betapose_amd import _lib
     from betapose_amd.darknet import Darknet
     from betapose_amd.kpd import ALLPATHS, FastPoseHIP
@@ -182,8 +183,12 @@ def main():
             len(im_names), sum(len(f['result']) > 0 for f in final_result), time.time() - t0))
         write_json(final_result, args.outputpath)
         if gt_frames is not None:
-            m = metrics.evaluate_results(final_result, gt_frames, model_vertices, metric_cam, diameter, pixel_thresh)
+            sym = obj_id in id_list(args.symmetric_ids)
+            m = metrics.evaluate_results(final_result, gt_frames, model_vertices, metric_cam, diameter, pixel_thresh,
+                                         symmetric=sym, device=torch.device("cuda", local) if sym else None)
             print("Mean add accuracy for seq %02d is: %.3f" % (obj_id, m["mean_add"]))
+            if sym:
+                print("Mean add-s accuracy for seq %02d is: %.3f" % (obj_id, m["mean_adds"]))
             print("2d reprojection accuracy for seq %02d is: %.3f" % (obj_id, m["mean_2d_acc"]))
             print("Mean IoU for seq %02d is: %.3f" % (obj_id, m["mean_iou"]))
     bpd.finalize()

@@ -25,6 +25,8 @@
  *   bp_solve_pnp           pnp (cv2.solvePnP + cv2.Rodrigues)                 utils/utils.py:17-41
  *   bp_solve_pnp_ransac    the commented-out cv2.solvePnPRansac variant       utils/utils.py:32-36
  *   bp_pose_nms            pose_nms                                           pPose_nms.py:24-122
+ *   bp_pose_errors         add_err / projection_error_2d + the commented-out   utils/metrics.py:10-33,99-127
+ *                          closest-point (ADD-S) loop, over every vertex
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
@@ -177,6 +179,12 @@ int bp_resize_bicubic(const uint8_t* d_in, int batch, int H, int W, int oh, int 
  * -> d_kp [batch][C][6] = (flat arg-max index as int bits -- first maximum wins --, max, left, right, up, down; the four
  * neighbours are 0 when the maximum lies on the border) */
 int bp_heatmap_argmax(const float* d_hm, int batch, int C, int H, int W, float* d_kp, void* stream);
+/* add_err / projection_error_2d (utils/metrics.py:10-22,99-127) and ADD-S (the closest-point form the reference
+ * keeps commented out, :23-33), f64, for P pose pairs of one model.  d_model [n][3] object frame; d_gt, d_est
+ * [P][12] row-major [R|t]; K host 3x3 (may be NULL when (want & 4) == 0); want: 1 ADD, 2 ADD-S, 4 2-D;
+ * d_out [P][3] = (ADD, ADD-S, 2-D px), unrequested columns untouched.  Synchronises `stream`. */
+int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P,
+                   const double* K, int want, double* d_out, void* stream);
 /* one fused convolution on device tensors (unit tests / kernel benchmarks).  h_w: host OIHW filter, h_bias host or NULL.
  * d_in NHWC [N,H,W,Cin]; d_out per store_mode (0 NHWC, 1 nearest-x2 NHWC, 2 PixelShuffle(2) NHWC, 3 NCHW);
  * act 0 linear / 1 leaky(0.1) / 2 relu; d_res NHWC residual or NULL; splits 0 auto; tile -1 auto, else a kernel id

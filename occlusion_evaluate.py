@@ -32,11 +32,12 @@ import evaluate  # noqa: E402
 def main():
     if "--occlusion" not in sys.argv:
         sys.argv.append("--occlusion")
-    from betapose_amd.opt import parse_args
+    from betapose_amd.opt import id_list, parse_args
     args = parse_args()
     if not args.obj_ids:
         return evaluate.main()          # the reference's own protocol: one object per run
 
+    import torch
     from betapose_amd import _lib, dist as bpd, metrics, synth
     from betapose_amd.darknet import Darknet
     from betapose_amd.frame_loader import FrameLoader
@@ -48,7 +49,8 @@ def main():
     _lib.require_gpu()
     bpd.limit_host_threads()
     rank, world, local = bpd.init_from_env()
-    obj_ids = [int(v) for v in args.obj_ids.split(",") if v.strip()]
+    obj_ids = id_list(args.obj_ids)
+    symmetric = set(id_list(args.symmetric_ids))
     assert len(obj_ids) == len(set(obj_ids)) and obj_ids, "--obj_ids: distinct object ids"
     K = len(obj_ids)
     left_number = args.left_keypoints
@@ -128,8 +130,12 @@ def main():
             odir = os.path.join(args.outputpath, "obj_%02d" % o)
             os.makedirs(odir, exist_ok=True)
             write_json(final_result, odir)
-            m = metrics.evaluate_results(final_result, frames_gt, model, cam, diameter, 20.0)
+            sym = o in symmetric
+            m = metrics.evaluate_results(final_result, frames_gt, model, cam, diameter, 20.0, symmetric=sym,
+                                         device=torch.device("cuda", local) if sym else None)
             print("Mean add accuracy for seq %02d is: %.3f" % (o, m["mean_add"]))
+            if sym:
+                print("Mean add-s accuracy for seq %02d is: %.3f" % (o, m["mean_adds"]))
             print("2d reprojection accuracy with leftkeypoints %d for seq %02d is: %.3f" % (left_number, o, m["mean_2d_acc"]))
             print("Mean IoU for seq %02d is: %.3f" % (o, m["mean_iou"]))
     bpd.finalize()
