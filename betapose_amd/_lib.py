@@ -89,6 +89,10 @@ PROTOTYPES = {
     "bp_pipeline_latency_faults": (C.c_int, [vp]),
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
+    "bp_pipeline_poses": (vp, [vp]),
+    "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "bp_solve_pnp_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "bp_solve_pnp": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "bp_solve_pnp_refined": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "bp_solve_pnp_ransac": (C.c_int, [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
@@ -119,6 +123,8 @@ PROTOTYPES = {
 }
 
 RESULT_FLOATS = 316
+POSE_DOUBLES = 166          # include/betapose_hip.h BP_POSE_DOUBLES
+PNP_MAX_POINTS = 64
 
 
 class BetaposeHipError(RuntimeError):

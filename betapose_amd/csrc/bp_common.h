@@ -48,6 +48,13 @@ inline void allow_big_lds(const void* kernel) {
 // XCDs differ by seconds, so a layer's first-entry -> last-store span cannot be taken from it.)
 __device__ __forceinline__ unsigned long long bp_clock() { return __builtin_amdgcn_s_memrealtime(); }
 
+// camera and damping table of the device PnP (pose_tail.hip): lam[lg + 16] = 10^lg for lg = -16 .. 16, computed on the
+// host with the host solver's own expression so that both minimisers damp by the same numbers
+struct PnpCam {
+    double fx, fy, cx, cy;
+    double lam[33];
+};
+
 enum Act : int { ACT_LINEAR = 0, ACT_LEAKY = 1, ACT_RELU = 2 };
 
 // where the epilogue puts element (m = (b,oy,ox), n = out channel)

@@ -2,6 +2,7 @@
 #include "../../include/betapose_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -23,6 +24,20 @@ int pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, 
 int pose_error_blocks(int n);
 void launch_pose_errors(const double* model, int n, const double* gt, const double* est, int P, const double* K,
                         int want, double* partial, double* out, hipStream_t s);
+// pose_tail.hip
+void launch_solve_pnp_batch(const double* pts3d, int shared_3d, const double* pts2d, int n, int P, const PnpCam& cam,
+                            double* Rt, int* status, hipStream_t s);
+void launch_pose_tail(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
+                      double* poses, hipStream_t s);
+}
+
+// the device PnP's camera: K (host, 3x3 row-major) and the minimiser's damping table 10^lg, lg = -16 .. 16, computed with
+// the expression the host solver uses (host_post.cpp solve_pnp_iterative, step())
+static bp::PnpCam make_pnp_cam(const double* K) {
+    bp::PnpCam c;
+    c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
+    for (int lg = -16; lg <= 16; ++lg) c.lam[lg + 16] = std::exp(lg * std::log(10.0));
+    return c;
 }
 
 static thread_local std::string g_err;
@@ -68,6 +83,13 @@ struct bp_pipeline {
     hipStream_t cap_stream = nullptr;
     unsigned ver_y = 0, ver_k = 0;   // engine plan versions the graph was captured with
     int latency_faults = 0;          // frames re-run because the latency mode's placement check failed (bp_pipeline_latency_faults)
+    // device pose tail (bp_pipeline_set_pose_solver): on while pose_on; kp3d [50][3] and poses [batch][166] in the arena
+    bool pose_on = false;
+    double* kp3d = nullptr;
+    double* poses = nullptr;
+    double* own_poses = nullptr;
+    bp::PnpCam cam{};
+    int left_number = 50;
     ~bp_pipeline() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -722,6 +744,8 @@ static void pipeline_enqueue(bp_pipeline* p, hipStream_t s) {
                     p->use_fixed ? p->fixed_box : nullptr, kn.input_nhwc(), nullptr, p->results + 8, kn.in_h(), kn.in_w(), s, R, R);
     // a8-a9: KPD + heat-map arg-max
     kn.forward(kn.input_nhwc(), true, p->batch, p->hm, p->results + 16, s, R);
+    // a10 (opt-in): decode, pPose-NMS, pruning and PnP on the records just written (pose_tail.hip)
+    if (p->pose_on) bp::launch_pose_tail(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->poses, s);
     BP_HIP(hipGetLastError());
 }
 
@@ -780,6 +804,61 @@ int bp_pipeline_set_fixed_box(bp_pipeline* p, const float* box) {
         for (int b = 0; b < p->batch; ++b) std::memcpy(&h[b * 4], box, 4 * sizeof(float));
         BP_HIP(hipMemcpy(p->fixed_box, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    return 0;
+    BP_CATCH
+}
+
+int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, const double* K, int left_number,
+                                double* d_poses) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    drop_graph(p);
+    if (!kp3d) {
+        p->pose_on = false;
+        return 0;
+    }
+    BP_CHECK(K, "null camera matrix");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    BP_HIP(hipSetDevice(p->y->device));
+    if (!p->kp3d) p->kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
+    if (!d_poses && !p->own_poses) {
+        p->own_poses = (double*)p->arena.alloc_bytes((size_t)p->batch * BP_POSE_DOUBLES * sizeof(double));
+        BP_HIP(hipMemset(p->own_poses, 0, (size_t)p->batch * BP_POSE_DOUBLES * sizeof(double)));
+    }
+    p->poses = d_poses ? d_poses : p->own_poses;
+    BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
+    p->cam = make_pnp_cam(K);
+    p->left_number = left_number;
+    p->pose_on = true;
+    return 0;
+    BP_CATCH
+}
+double* bp_pipeline_poses(bp_pipeline* p) { return p ? p->poses : nullptr; }
+
+int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
+                         int left_number, double* d_poses, void* stream) {
+    BP_TRY
+    BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
+    BP_CHECK(batch >= 0, "batch must be >= 0");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    if (batch == 0) return 0;
+    bp::launch_pose_tail(d_records, batch, d_kp3d, make_pnp_cam(K), left_number, d_poses, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
+                       double* d_Rt, int* d_status, void* stream) {
+    BP_TRY
+    BP_CHECK(d_pts3d && d_pts2d && K && d_Rt && d_status, "null argument");
+    BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_batch: n must be in [0, 64] points per problem");
+    BP_CHECK(P >= 0, "P must be >= 0");
+    if (P == 0) return 0;
+    bp::launch_solve_pnp_batch(d_pts3d, shared_3d, d_pts2d, n, P, make_pnp_cam(K), d_Rt, d_status, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
 }

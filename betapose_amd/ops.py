@@ -113,6 +113,42 @@ def solve_pnp(points_3d, points_2d, K, method: str = "iterative"):
     return R, t.reshape(3, 1)
 
 
+def solve_pnp_batch(points_3d, points_2d, K):
+    """``solve_pnp`` over P independent problems in one device launch (bp_solve_pnp_batch, one wave per problem).
+    ``points_3d``: [n,3] shared by every problem or [P,n,3]; ``points_2d``: [P,n,2]; numpy or torch, n <= 64.  Returns
+    (R [P,3,3], t [P,3,1], status [P] int32) as cuda torch tensors: status 0 = solved, -1 too few points, -2 degenerate
+    (R, t NaN there), the codes of the host solver."""
+    import torch
+    _lib.require_gpu()
+    p2 = torch.as_tensor(points_2d, dtype=torch.float64).cuda().contiguous()
+    assert p2.dim() == 3 and p2.shape[2] >= 2, "points_2d must be [P, n, 2]"
+    p2 = p2[:, :, :2].contiguous()
+    P, n = p2.shape[0], p2.shape[1]
+    p3 = torch.as_tensor(points_3d, dtype=torch.float64).to(p2.device).contiguous()
+    shared = p3.dim() == 2
+    assert p3.shape[-2:] == (n, 3) and (shared or p3.shape[0] == P), "points 3D and points 2D must have same number of vertices"
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    Rt = torch.empty((P, 3, 4), dtype=torch.float64, device=p2.device)
+    st = torch.empty(P, dtype=torch.int32, device=p2.device)
+    _lib.check(_lib.lib().bp_solve_pnp_batch(p3.data_ptr(), int(shared), p2.data_ptr(), n, P, Kc.ctypes.data,
+                                             Rt.data_ptr(), st.data_ptr(), _lib.current_stream()))
+    return Rt[:, :, :3].contiguous(), Rt[:, :, 3:].contiguous(), st
+
+
+def pose_from_records(records, kp3d, K, left_number: int = 50):
+    """The device pose tail on records made any way (bp_pose_from_records): cuda f32 [B,316] -> cuda f64 [B,166]."""
+    import torch
+    _lib.require_gpu()
+    rec = records.contiguous()
+    assert rec.dtype == torch.float32 and rec.dim() == 2 and rec.shape[1] == _lib.RESULT_FLOATS
+    k3 = torch.as_tensor(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3), device=rec.device).contiguous()
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    out = torch.empty((rec.shape[0], _lib.POSE_DOUBLES), dtype=torch.float64, device=rec.device)
+    _lib.check(_lib.lib().bp_pose_from_records(rec.data_ptr(), rec.shape[0], k3.data_ptr(), k3.shape[0], Kc.ctypes.data,
+                                               int(left_number), out.data_ptr(), _lib.current_stream()))
+    return out
+
+
 def solve_pnp_ransac(points_3d, points_2d, K, reprojection_error: float = 12.0, iterations: int = 100,
                      confidence: float = 0.99):
     """The variant utils/utils.py:32-36 keeps commented out (cv2.solvePnPRansac, reprojectionError=12.0): returns

@@ -44,6 +44,9 @@ def build_parser() -> argparse.ArgumentParser:
                         'and 11, glue): one more line per such object, "Mean add-s accuracy for seq XX is: ...", computed '
                         'on the run\'s GPU (metrics.pose_errors)')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
+    p.add_argument('--device_pnp', default=False, action='store_true',
+                   help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '
+                        'graph (the device pose tail, DESIGN.md 3.5); rank 0 only builds the result dicts')
     p.add_argument('--synthetic', type=int, default=0, help='run on N seeded synthetic frames / weights')
     p.add_argument('--synth_weights', default=False, action='store_true',
                    help='seeded synthetic weights with real frames / ground truth (plumbing runs without checkpoints)')

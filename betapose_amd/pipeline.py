@@ -3,7 +3,8 @@
 Device part (one hipGraph, ``bp_pipeline_run``): Pillow-exact bicubic stretch ->
 YOLOv3 -> decode + arg-max objectness -> box rescale + crop -> FastPose -> heat-map
 arg-max; 316 floats per frame come back.  Host part (``finish_record``): key-point
-decoding, pPose-NMS (n = 1), key-point pruning, PnP.  Together they replace
+decoding, pPose-NMS (n = 1), key-point pruning, PnP.  Opt-in (``set_pose_solver``): the same
+tail as one more launch at the end of the graph, 166 doubles per frame (``finish_pose_record``).  Together they replace
 ``DetectionLoader.update`` -> ``DetectionProcessor.update`` -> the KPD main loop ->
 ``DataWriter.update`` of the reference (dataloader.py:330-401,438-457,678-741;
 betapose_evaluate.py:145-176) for the evaluation stream.
@@ -21,6 +22,8 @@ from .ops import solve_pnp
 from .pPose_nms import pose_nms
 
 RESULT_FLOATS = _lib.RESULT_FLOATS
+POSE_DOUBLES = _lib.POSE_DOUBLES
+PNP_FAILED = "solve_pnp failed (need >= 6 non-degenerate points, or >= 4 coplanar ones)"   # bp_solve_pnp's error text
 
 
 class FramePipeline:
@@ -48,6 +51,7 @@ class FramePipeline:
                                                  self.heatmaps.data_ptr() if keep_heatmaps else None, C.byref(h)))
         self._h = h
         self._faults_seen = 0
+        self.poses = None          # torch f64 [B, POSE_DOUBLES] once set_pose_solver was called
 
     def __del__(self):
         try:
@@ -64,6 +68,23 @@ class FramePipeline:
         else:
             b = np.ascontiguousarray(box_xyxy, dtype=np.float32)
             _lib.check(_lib.lib().bp_pipeline_set_fixed_box(self._h, b.ctypes.data))
+
+    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50):
+        """Opt-in device pose tail: every run then also writes ``self.poses`` [B, 166] f64, the frame's pose record
+        (include/betapose_hip.h BP_POSE_DOUBLES; ``finish_pose_record`` turns it into ``finish_record``'s dict).
+        ``kp3d`` [50, 3]: the 3-D key points; ``cam_K`` [3, 3]; ``left_number``: --left_keypoints.  None switches it off."""
+        import torch
+        if kp3d is None:
+            _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, None, 0, None, 0, None))
+            return self
+        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
+        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
+        if self.poses is None:
+            self.poses = torch.zeros((self.batch, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
+            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
+        _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, k3.ctypes.data, k3.shape[0], Kc.ctypes.data,
+                                                          int(left_number), self.poses.data_ptr()))
+        return self
 
     def enqueue(self, stream: Optional[int] = None):
         """Launch the device part on ``stream`` (default: torch's current stream).  ``self.frames`` must
@@ -119,8 +140,11 @@ class StreamedRunner:
     overlapping on the chip is where the throughput comes from."""
 
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, streams: int = 4,
-                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, batch: int = 1):
-        """``batch`` frames per launch and stream (the reference's ``--detbatch``, dataloader.py:284-289): the engines
+                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, batch: int = 1,
+                 pose_solver=None):
+        """``pose_solver``: ``(kp3d, cam_K, left_number)`` turns the device pose tail on in every stream's pipeline; the
+        pose rows then come back with the records and ``on_record`` gets ``(index, rec, pose_row)``.
+        ``batch`` frames per launch and stream (the reference's ``--detbatch``, dataloader.py:284-289): the engines
         must have been created with ``max_batch >= batch``.  More frames per launch mean fewer launches, K slices and
         hand-offs per frame: 1 -> 2 -> 4 frames per launch run 945 -> 1 100 -> 1 290 frames/s."""
         import torch
@@ -136,10 +160,16 @@ class StreamedRunner:
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
         self._pinned = [torch.empty((B, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
         self._events = [torch.cuda.Event() for _ in range(2 * S)]
+        self._pinned_pose = None
+        if pose_solver is not None:
+            for fp in self.pipes:
+                fp.set_pose_solver(*pose_solver)
+            self._pinned_pose = [torch.empty((B, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
 
     def run(self, source, on_record) -> int:
         """``source`` yields ``(index, frame[H,W,3] u8 BGR, host_address)`` and has ``release(index)`` (FrameLoader);
-        ``on_record(index, rec[316])`` is called in source order once the frame's record is on the host.
+        ``on_record(index, rec[316])`` -- ``(index, rec[316], pose_row[166])`` with a pose solver -- is called in source
+        order once the frame's record is on the host.
         Returns the number of frames processed."""
         import torch
         L = _lib.lib()
@@ -151,10 +181,14 @@ class StreamedRunner:
             j, idxs = inflight.pop(0)
             self._events[j % NS].synchronize()
             recs = self._pinned[j % NS].numpy().copy()
+            poses = self._pinned_pose[j % NS].numpy().copy() if self._pinned_pose is not None else None
             for b, idx in enumerate(idxs):
                 source.release(idx)
             for b, idx in enumerate(idxs):
-                on_record(idx, recs[b])
+                if poses is None:
+                    on_record(idx, recs[b])
+                else:
+                    on_record(idx, recs[b], poses[b])
 
         def launch(j):
             k = j % S
@@ -162,6 +196,8 @@ class StreamedRunner:
             with torch.cuda.stream(st):
                 self.pipes[k].enqueue(st.cuda_stream)
                 self._pinned[j % NS].copy_(self.pipes[k].results, non_blocking=True)
+                if self._pinned_pose is not None:
+                    self._pinned_pose[j % NS].copy_(self.pipes[k].poses, non_blocking=True)
                 self._events[j % NS].record(st)
             inflight.append((j, list(pending)))
             pending.clear()
@@ -212,10 +248,12 @@ class MultiObjectRunner:
     flight; unit u = frame_position * n_objects + object_position, and only the units in ``owned`` are run (the caller
     shards them ``u % world``).
 
-    ``engines``: {obj_id: (Darknet, FastPoseHIP)} for the objects this rank owns units of."""
+    ``engines``: {obj_id: (Darknet, FastPoseHIP)} for the objects this rank owns units of.  ``pose_solvers``:
+    {obj_id: (kp3d, cam_K, left_number)} turns the device pose tail on (every object in ``engines`` needs one); then
+    ``on_record`` gets ``(u, rec, pose_row)``."""
 
     def __init__(self, engines: dict, obj_ids: List[int], frame_h: int = 480, frame_w: int = 640, streams: int = 4,
-                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True):
+                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, pose_solvers: Optional[dict] = None):
         import torch
         self.obj_ids = list(obj_ids)
         S = max(1, int(streams))
@@ -230,6 +268,8 @@ class MultiObjectRunner:
                 d, p_ = (det, pose) if k == 0 else (det.clone(), pose.clone())
                 fp = FramePipeline(d, p_, frame_h, frame_w, batch=1, confidence=confidence, num_classes=num_classes,
                                    use_graph=use_graph, frames=buf)
+                if pose_solvers is not None:
+                    fp.set_pose_solver(*pose_solvers[oid])
                 buf = fp.frames
                 dev = buf.device
                 self.pipes[(k, oid)] = fp
@@ -237,6 +277,9 @@ class MultiObjectRunner:
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)] if dev is not None else []
         self._pinned = [torch.empty((1, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
         self._events = [torch.cuda.Event() for _ in range(2 * S)]
+        self._pinned_pose = None
+        if pose_solvers is not None:
+            self._pinned_pose = [torch.empty((1, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
 
     def run(self, source, frame_positions: List[int], owned, on_record) -> int:
         """``source``: FrameLoader over the frames this rank touches (in ``frame_positions`` order: position of each
@@ -252,11 +295,15 @@ class MultiObjectRunner:
             j, u, idx = inflight.pop(0)
             self._events[j % NS].synchronize()
             rec = self._pinned[j % NS].numpy()[0].copy()
+            pose = self._pinned_pose[j % NS].numpy()[0].copy() if self._pinned_pose is not None else None
             pending[idx] -= 1
             if pending[idx] == 0:
                 del pending[idx]
                 source.release(idx)
-            on_record(u, rec)
+            if pose is None:
+                on_record(u, rec)
+            else:
+                on_record(u, rec, pose)
 
         j = 0
         try:
@@ -276,8 +323,11 @@ class MultiObjectRunner:
                     # (same stream: in order)
                     with torch.cuda.stream(st):
                         _lib.check(L.bp_upload(self.frame_bufs[k].data_ptr(), addr, nbytes, st.cuda_stream))
-                        self.pipes[(k, self.obj_ids[u % K])].enqueue(st.cuda_stream)
-                        self._pinned[j % NS].copy_(self.pipes[(k, self.obj_ids[u % K])].results, non_blocking=True)
+                        fp = self.pipes[(k, self.obj_ids[u % K])]
+                        fp.enqueue(st.cuda_stream)
+                        self._pinned[j % NS].copy_(fp.results, non_blocking=True)
+                        if self._pinned_pose is not None:
+                            self._pinned_pose[j % NS].copy_(fp.poses, non_blocking=True)
                         self._events[j % NS].record(st)
                     inflight.append((j, u, idx))
                     j += 1
@@ -325,4 +375,33 @@ def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.nd
         out.update({"cam_R": R, "cam_t": t})
     else:
         out.update({"cam_R": [], "cam_t": []})
+    return out
+
+
+def finish_pose_record(rec: np.ndarray, pose_row: np.ndarray, imgname: str) -> dict:
+    """Device-tail twin of ``finish_record``: the frame's 316-float record and its 166-double pose record (device pose
+    tail, ``FramePipeline.set_pose_solver`` / ``bp_pose_from_records``) -> the same dict ``finish_record`` returns for
+    the solver's kp3d / cam_K / left_number.  Raises ``BetaposeHipError`` where the host path raises."""
+    rec = np.ascontiguousarray(rec, dtype=np.float32)
+    row = np.asarray(pose_row, dtype=np.float64).reshape(POSE_DOUBLES)
+    idx = int(rec[:1].view(np.int32)[0])
+    status = int(row[0])
+    if (idx < 0) != (status == 1):
+        raise ValueError("pose record (status %d) does not belong to this frame record (index %d)" % (status, idx))
+    if idx < 0:
+        return {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+    if status < 0:
+        raise _lib.BetaposeHipError(PNP_FAILED)
+    boxes = rec[12:16].reshape(1, 4).copy()
+    scores = rec[5:6].reshape(1, 1).copy()
+    out = {"imgname": imgname, "boxes": boxes, "scores": scores, "yolo_index": idx}
+    if status == 2:
+        out.update({"result": [], "cam_R": [], "cam_t": []})
+        return out
+    kp = row[16:].reshape(50, 3).astype(np.float32)
+    out["result"] = [{"bbox": boxes[0].copy(),
+                      "keypoints": kp[:, :2].copy(),
+                      "kp_score": kp[:, 2:3].copy(),
+                      "proposal_score": np.array([row[14]], dtype=np.float32)}]
+    out.update({"cam_R": row[2:11].reshape(3, 3).copy(), "cam_t": row[11:14].reshape(3, 1).copy()})
     return out

@@ -126,12 +126,15 @@ def main():
     t0 = time.time()
     if args.fused:
         from betapose_amd.frame_loader import FrameLoader
-        from betapose_amd.pipeline import StreamedRunner, finish_record
+        from betapose_amd.pipeline import POSE_DOUBLES, StreamedRunner, finish_pose_record, finish_record
         mine = bpd.shard_indices(len(im_names), rank, world)
         recs = np.zeros((len(mine), 316), np.float32)
+        poses = np.zeros((len(mine), POSE_DOUBLES), np.float64) if args.device_pnp else None
 
-        def keep(j, rec):
+        def keep(j, rec, pose=None):
             recs[j] = rec
+            if pose is not None:
+                poses[j] = pose
         t_dev = time.time()
         if len(mine):   # a rank beyond the frame count has nothing to load (its share of the gather is empty)
             # decode threads are a per-GPU budget: ranks of one node share the host cores
@@ -139,21 +142,28 @@ def main():
             loader = FrameLoader([os.path.join(args.inputpath, im_names[i]) for i in mine], threads=threads,
                                  depth=max(16, 2 * args.streams * max(1, args.detbatch) + threads))
             runner = StreamedRunner(det, pose_model, loader.height, loader.width, streams=args.streams,
-                                    confidence=args.confidence, num_classes=args.num_classes, batch=args.detbatch)
+                                    confidence=args.confidence, num_classes=args.num_classes, batch=args.detbatch,
+                                    pose_solver=(kp3d, cam_K, left_number) if args.device_pnp else None)
             runner.run(loader, keep)
             loader.close()
         t_dev = time.time() - t_dev
         print("rank %d: %d frames, files -> records %.1f frames/sec (%d launches of %d frame(s) in flight, %d decode threads)" % (
             rank, len(mine), len(mine) / max(t_dev, 1e-9), args.streams, max(1, args.detbatch), args.load_threads))
         allrec = bpd.gather_records(recs, mine, len(im_names))
+        # the pose rows travel through the same gather, each f64 as a pair of f32 bit patterns
+        allpose = bpd.gather_records(poses.view(np.float32), mine, len(im_names)) if args.device_pnp else None
         final_result = []
         if rank == 0:
             for i, name in enumerate(im_names):
-                out = finish_record(allrec[i], name, kp3d, cam_K, left_number)
+                if allpose is not None:
+                    out = finish_pose_record(allrec[i], np.ascontiguousarray(allpose[i]).view(np.float64), name)
+                else:
+                    out = finish_record(allrec[i], name, kp3d, cam_K, left_number)
                 if out["boxes"] is not None:
                     final_result.append(out)
     else:
         assert world == 1, "the staged pipeline is single-GPU; use --fused to shard frames over ranks"
+        assert not args.device_pnp, "--device_pnp needs --fused (the device pose tail ends the fused frame graph)"
         from betapose_amd.dataloader import DataWriter, DetectionLoader, DetectionProcessor, ImageLoader
         data_loader = ImageLoader(im_names, batchSize=args.detbatch, format='yolo', reso=int(args.inp_dim)).start()
         det_loader = DetectionLoader(data_loader, obj_id, batchSize=args.detbatch, det_model=det).start()

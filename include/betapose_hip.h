@@ -25,6 +25,11 @@
  *   bp_solve_pnp           pnp (cv2.solvePnP + cv2.Rodrigues)                 utils/utils.py:17-41
  *   bp_solve_pnp_ransac    the commented-out cv2.solvePnPRansac variant       utils/utils.py:32-36
  *   bp_pose_nms            pose_nms                                           pPose_nms.py:24-122
+ *   bp_pipeline_set_pose_solver, bp_pipeline_poses, bp_pose_from_records
+ *                          DataWriter.update's per-frame tail on device: key-point   dataloader.py:704-727
+ *                          decode (getPrediction), pPose-NMS at n = 1, pruning to   KPD/src/utils/eval.py:113-147
+ *                          --left_keypoints, pnp                                     pPose_nms.py:24-122, utils/utils.py:17-41
+ *   bp_solve_pnp_batch     pnp over P independent problems on device            utils/utils.py:17-41
  *   bp_pose_errors         add_err / projection_error_2d + the commented-out   utils/metrics.py:10-33,99-127
  *                          closest-point (ADD-S) loop, over every vertex
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
@@ -65,6 +70,16 @@ typedef struct bp_pipeline bp_pipeline;
 #define BP_RESULT_FLOATS 316
 #define BP_KP_FLOATS 6
 #define BP_SEL_FLOATS 8
+
+/* doubles per frame in the pose record of the device pose tail (bp_pipeline_set_pose_solver, bp_pose_from_records):
+ *   [0]        status: 0 ok, 1 no detection, 2 dropped by pPose-NMS, < 0 the solver's status as bp_solve_pnp reports it
+ *              (-1 too few points, -2 degenerate or non-finite)
+ *   [1]        key points used by the PnP (after the left_number pruning)
+ *   [2..10]    R row-major, [11..13] t -- NaN unless status 0
+ *   [14]       proposal score, [15] 0
+ *   [16..165]  50 x (x, y, score) after pPose-NMS (the - 0.3 applied; f32 values held exactly), zero for status 1 and 2 */
+#define BP_POSE_DOUBLES 166
+#define BP_PNP_MAX_POINTS 64
 
 const char* bp_last_error(void);
 int bp_version(void);
@@ -220,6 +235,25 @@ int bp_pipeline_latency_faults(const bp_pipeline* p);
  * (It creates the pipeline's capture stream: call it AFTER the caller's own streams have launched something -- HIP binds streams to
  * its four hardware queues as they are first used, and two pipelines prepared first were seen to share one queue.) */
 int bp_pipeline_prepare(bp_pipeline* p);
+
+/* ---- device pose tail (opt-in): what pipeline.finish_record does on the host, per frame on the GPU ----
+ * Key-point decode and pPose-NMS in f32 and the pruning bit-identical to the host tail; the PnP is bp_solve_pnp's algorithm
+ * in f64 in the host's operation order (agrees with it to rounding).  kp3d [50][3] f64 = the 3-D key points, K [9] host,
+ * left_number >= 0 = key points kept (--left_keypoints).
+ * bp_pipeline_set_pose_solver: kp3d host; NULL switches the tail off.  Either way the captured graph is dropped (as
+ * bp_pipeline_set_fixed_box does); while it is on, every run ends with one more launch that writes the pose records into
+ * d_poses [batch][BP_POSE_DOUBLES] (device; NULL: the pipeline's own buffer, as bp_pipeline_create's d_results). */
+int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, const double* K, int left_number,
+                                double* d_poses);
+double* bp_pipeline_poses(bp_pipeline* p);      /* device [batch][BP_POSE_DOUBLES]; NULL while no solver was ever set */
+/* the tail alone, on records made any way: d_records [batch][BP_RESULT_FLOATS], d_kp3d device, d_poses [batch][166] */
+int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K, int left_number,
+                         double* d_poses, void* stream);
+/* bp_solve_pnp over P independent problems of n <= BP_PNP_MAX_POINTS points, one wave each: d_pts3d [n][3] shared by all
+ * (shared_3d = 1) or [P][n][3], d_pts2d [P][n][2], K [9] host -> d_Rt [P][12] ([R | t] row-major, NaN unless the status is
+ * 0), d_status [P] (bp_solve_pnp's codes: 0, -1 too few points, -2 degenerate).  Asynchronous on `stream`. */
+int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
+                       double* d_Rt, int* d_status, void* stream);
 
 /* ---- host post-processing (no device work) ---- */
 /* pnp (utils/utils.py:17-41): a restatement of cv2.solvePnP's default SOLVEPNP_ITERATIVE (planar / DLT initialisation,

@@ -42,7 +42,7 @@ def main():
     from betapose_amd.darknet import Darknet
     from betapose_amd.frame_loader import FrameLoader
     from betapose_amd.kpd import ALLPATHS, FastPoseHIP
-    from betapose_amd.pipeline import MultiObjectRunner, finish_record
+    from betapose_amd.pipeline import POSE_DOUBLES, MultiObjectRunner, finish_pose_record, finish_record
     from betapose_amd.pPose_nms import write_json
     from betapose_amd.weights import fastpose_stream_from_state_dict, load_kpd_pkl, read_darknet_weights
 
@@ -101,16 +101,29 @@ def main():
         del ys, ks
     print("rank %d: %d object engine pairs resident (%s), %.1f s" % (rank, len(engines), sorted(engines), time.time() - t0))
 
+    # ---- --device_pnp: every rank solves its own units, so it needs the 3-D key points of the objects it runs
+    solvers = None
+    if args.device_pnp:
+        solvers = {}
+        for o in my_objs:
+            kp3d = gt[o][2] if o in gt else evaluate.load_sixd_gt(args.sixd_base, o, 2)[2]
+            solvers[o] = (metrics.refine_keypoints(kp3d, 50) if len(kp3d) > 50 else kp3d, synth.CAM_K, left_number)
+
     # ---- run this rank's units
-    recs = {}
+    recs, poses = {}, {}
+
+    def keep(u, rec, pose=None):
+        recs[u] = rec
+        if pose is not None:
+            poses[u] = pose
     t_dev = time.time()
     if my_frames:
         threads = max(1, min(args.load_threads, (os.cpu_count() or 8) // max(1, world)))
         loader = FrameLoader([os.path.join(args.inputpath, im_names[f]) for f in my_frames], threads=threads,
                              depth=max(16, 2 * args.streams + threads))
         runner = MultiObjectRunner(engines, obj_ids, loader.height, loader.width, streams=args.streams,
-                                   confidence=args.confidence, num_classes=args.num_classes)
-        runner.run(loader, my_frames, owned, lambda u, rec: recs.__setitem__(u, rec))
+                                   confidence=args.confidence, num_classes=args.num_classes, pose_solvers=solvers)
+        runner.run(loader, my_frames, owned, keep)
         loader.close()
     t_dev = time.time() - t_dev
     mine = sorted(recs)
@@ -118,13 +131,20 @@ def main():
         rank, len(mine), len(my_frames), len(mine) / max(t_dev, 1e-9), args.streams))
     mine_recs = np.stack([recs[u] for u in mine]) if mine else np.zeros((0, 316), np.float32)
     allrec = bpd.gather_records(mine_recs, mine, n_units)
+    allpose = None
+    if args.device_pnp:   # the pose rows ride the same gather, each f64 as a pair of f32 bit patterns
+        mine_poses = np.stack([poses[u] for u in mine]) if mine else np.zeros((0, POSE_DOUBLES), np.float64)
+        allpose = bpd.gather_records(mine_poses.view(np.float32), mine, n_units)
 
     if rank == 0:
         for oi, o in enumerate(obj_ids):
             frames_gt, model, kp3d, diameter, cam = gt[o]
             final_result = []
             for f, name in enumerate(im_names):
-                out = finish_record(allrec[f * K + oi], name, kp3d, synth.CAM_K, left_number)
+                if allpose is not None:
+                    out = finish_pose_record(allrec[f * K + oi], np.ascontiguousarray(allpose[f * K + oi]).view(np.float64), name)
+                else:
+                    out = finish_record(allrec[f * K + oi], name, kp3d, synth.CAM_K, left_number)
                 if out["boxes"] is not None:
                     final_result.append(out)
             odir = os.path.join(args.outputpath, "obj_%02d" % o)
