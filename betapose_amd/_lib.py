@@ -93,6 +93,15 @@ PROTOTYPES = {
     "bp_pipeline_poses": (vp, [vp]),
     "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_solve_pnp_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "bp_pnp_ransac_samples": (C.c_int, [C.c_int, C.c_int, vp]),
+    "bp_pnp_ransac_trials_needed": (C.c_int, [C.c_int, C.c_double, vp]),
+    "bp_pnp_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bp_solve_pnp_ransac_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp,
+                                            vp, C.c_size_t, vp]),
+    "bp_pipeline_set_pose_ransac": (C.c_int, [vp, C.c_double, C.c_int, C.c_double]),
+    "bp_pose_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bp_pose_from_records_ransac": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp,
+                                              C.c_size_t, vp]),
     "bp_solve_pnp": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "bp_solve_pnp_refined": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "bp_solve_pnp_ransac": (C.c_int, [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp]),

@@ -18,6 +18,8 @@ int solve_pnp(const double* P, const double* U, int n, const double* K, double* 
 int solve_pnp_refined(const double* P, const double* U, int n, const double* K, double* R, double* t);
 int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, double reproj_err, int max_trials,
                      double confidence, double* R, double* t, unsigned char* inlier_mask);
+void pnp_ransac_samples(int n, int max_trials, int* idx);
+void pnp_ransac_trials_needed(int n, double confidence, int* need);
 int pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, const float* scores, int n, int K,
              int* out_pick, float* out_pose, float* out_score, float* out_prop);
 // pose_metrics.hip
@@ -29,6 +31,13 @@ void launch_solve_pnp_batch(const double* pts3d, int shared_3d, const double* pt
                             double* Rt, int* status, hipStream_t s);
 void launch_pose_tail(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
                       double* poses, hipStream_t s);
+void launch_pose_tail_prepare(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
+                              double* poses, double* ws3d, double* ws2d, int* active, hipStream_t s);
+// pnp_ransac.hip
+size_t pnp_ransac_workspace_bytes(int P, int max_trials);
+void launch_pnp_ransac(const double* pts3d, size_t stride3d, const double* pts2d, size_t stride2d, const int* active, int n,
+                       int P, const PnpCam& cam, double reproj_err, int max_trials, const int* samples, const int* need,
+                       void* workspace, double* Rt, int* status, unsigned char* inliers, double* poses, hipStream_t s);
 }
 
 // the device PnP's camera: K (host, 3x3 row-major) and the minimiser's damping table 10^lg, lg = -16 .. 16, computed with
@@ -38,6 +47,34 @@ static bp::PnpCam make_pnp_cam(const double* K) {
     c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
     for (int lg = -16; lg <= 16; ++lg) c.lam[lg + 16] = std::exp(lg * std::log(10.0));
     return c;
+}
+
+// The RANSAC pose tail: workspace = kept 3-D points [batch][64][3] f64 | kept 2-D points [batch][64][2] f64 | the
+// hypotheses' masks and counts (pnp_ransac_workspace_bytes) | active [batch] i32.  Three launches: prepare (decode, NMS,
+// pruning; the pose row but for the solver's slots), hypotheses, select-and-refit.
+static size_t pose_ransac_ws_bytes(int batch, int max_trials) {
+    return (size_t)batch * 64 * 5 * sizeof(double) + bp::pnp_ransac_workspace_bytes(batch, max_trials) + (size_t)batch * sizeof(int);
+}
+static void pose_tail_ransac(const float* records, int batch, const double* kp3d, const bp::PnpCam& cam, int left_number,
+                             double reproj_err, int max_trials, const int* samples, const int* need, double* poses, void* ws,
+                             hipStream_t s) {
+    double* ws3d = (double*)ws;
+    double* ws2d = ws3d + (size_t)batch * 64 * 3;
+    char* hyp = (char*)(ws2d + (size_t)batch * 64 * 2);
+    int* active = (int*)(hyp + bp::pnp_ransac_workspace_bytes(batch, max_trials));
+    const int n = left_number < 50 ? left_number : 50;     // points the pruning keeps, the same for every frame
+    bp::launch_pose_tail_prepare(records, batch, kp3d, cam, left_number, poses, ws3d, ws2d, active, s);
+    bp::launch_pnp_ransac(ws3d, 64 * 3, ws2d, 64 * 2, active, n, batch, cam, reproj_err, max_trials, samples, need, hyp, nullptr,
+                          nullptr, nullptr, poses, s);
+}
+// the host's tables for n points (n > 6: below that the device code reads neither)
+static void ransac_tables(int n, int max_trials, double confidence, std::vector<int>& samples, std::vector<int>& need) {
+    samples.assign((size_t)max_trials * 6, 0);
+    need.assign((size_t)(n > 0 ? n : 0) + 1, 0x7fffffff);
+    if (n > 6) {
+        bp::pnp_ransac_samples(n, max_trials, samples.data());
+        bp::pnp_ransac_trials_needed(n, confidence, need.data());
+    }
 }
 
 static thread_local std::string g_err;
@@ -90,6 +127,13 @@ struct bp_pipeline {
     double* own_poses = nullptr;
     bp::PnpCam cam{};
     int left_number = 50;
+    // RANSAC in place of the plain PnP (bp_pipeline_set_pose_ransac): on while ransac_trials > 0; the sampler's and the
+    // early stop's tables are the host's, for n = min(50, left_number) points
+    int ransac_trials = 0;
+    double ransac_err = 0, ransac_conf = 0;
+    std::vector<int> ransac_samples, ransac_need;
+    void* ransac_ws = nullptr;
+    size_t ransac_ws_bytes = 0;
     ~bp_pipeline() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -745,7 +789,10 @@ static void pipeline_enqueue(bp_pipeline* p, hipStream_t s) {
     // a8-a9: KPD + heat-map arg-max
     kn.forward(kn.input_nhwc(), true, p->batch, p->hm, p->results + 16, s, R);
     // a10 (opt-in): decode, pPose-NMS, pruning and PnP on the records just written (pose_tail.hip)
-    if (p->pose_on) bp::launch_pose_tail(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->poses, s);
+    if (p->pose_on && p->ransac_trials > 0) pose_tail_ransac(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->ransac_err,
+                                                             p->ransac_trials, p->ransac_samples.data(), p->ransac_need.data(),
+                                                             p->poses, p->ransac_ws, s);
+    else if (p->pose_on) bp::launch_pose_tail(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->poses, s);
     BP_HIP(hipGetLastError());
 }
 
@@ -831,6 +878,8 @@ int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, co
     p->cam = make_pnp_cam(K);
     p->left_number = left_number;
     p->pose_on = true;
+    if (p->ransac_trials > 0)   // the RANSAC setting stays; its tables are per point count
+        ransac_tables(left_number < 50 ? left_number : 50, p->ransac_trials, p->ransac_conf, p->ransac_samples, p->ransac_need);
     return 0;
     BP_CATCH
 }
@@ -858,6 +907,100 @@ int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts
     BP_CHECK(P >= 0, "P must be >= 0");
     if (P == 0) return 0;
     bp::launch_solve_pnp_batch(d_pts3d, shared_3d, d_pts2d, n, P, make_pnp_cam(K), d_Rt, d_status, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_pnp_ransac_samples(int n, int max_trials, int* idx) {
+    BP_TRY
+    BP_CHECK(idx, "null argument");
+    BP_CHECK(n >= 6 && max_trials >= 1, "bp_pnp_ransac_samples: needs n >= 6 points and max_trials >= 1");
+    bp::pnp_ransac_samples(n, max_trials, idx);
+    return 0;
+    BP_CATCH
+}
+
+int bp_pnp_ransac_trials_needed(int n, double confidence, int* need) {
+    BP_TRY
+    BP_CHECK(need, "null argument");
+    BP_CHECK(n >= 1 && confidence > 0 && confidence < 1, "bp_pnp_ransac_trials_needed: needs n >= 1 and a confidence in (0, 1)");
+    bp::pnp_ransac_trials_needed(n, confidence, need);
+    return 0;
+    BP_CATCH
+}
+
+size_t bp_pnp_ransac_workspace_bytes(int P, int max_trials) {
+    return P > 0 && max_trials > 0 ? bp::pnp_ransac_workspace_bytes(P, max_trials) : 0;
+}
+
+int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
+                              double reproj_err, int max_trials, double confidence, double* d_Rt, int* d_status,
+                              unsigned char* d_inliers, void* d_workspace, size_t workspace_bytes, void* stream) {
+    BP_TRY
+    BP_CHECK(d_pts3d && d_pts2d && K && d_Rt && d_status, "null argument");
+    BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_ransac_batch: n must be in [0, 64] points per problem");
+    BP_CHECK(P >= 0, "P must be >= 0");
+    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    if (P == 0) return 0;
+    BP_CHECK(d_workspace && workspace_bytes >= bp::pnp_ransac_workspace_bytes(P, max_trials),
+             "bp_solve_pnp_ransac_batch: workspace smaller than bp_pnp_ransac_workspace_bytes(P, max_trials)");
+    BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_solve_pnp_ransac_batch: workspace must be 8-byte aligned");
+    std::vector<int> samples, need;
+    ransac_tables(n, max_trials, confidence, samples, need);
+    bp::launch_pnp_ransac(d_pts3d, shared_3d ? 0 : (size_t)n * 3, d_pts2d, (size_t)n * 2, nullptr, n, P, make_pnp_cam(K), reproj_err,
+                          max_trials, samples.data(), need.data(), d_workspace, d_Rt, d_status, d_inliers, nullptr,
+                          (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_pipeline_set_pose_ransac(bp_pipeline* p, double reproj_err, int max_trials, double confidence) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    drop_graph(p);
+    if (max_trials == 0) {
+        p->ransac_trials = 0;
+        return 0;
+    }
+    BP_CHECK(p->pose_on, "bp_pipeline_set_pose_ransac: set a pose solver first (bp_pipeline_set_pose_solver)");
+    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    BP_HIP(hipSetDevice(p->y->device));
+    const size_t bytes = pose_ransac_ws_bytes(p->batch, max_trials);
+    if (bytes > p->ransac_ws_bytes) {
+        p->ransac_ws = p->arena.alloc_bytes(bytes);
+        p->ransac_ws_bytes = bytes;
+    }
+    p->ransac_err = reproj_err;
+    p->ransac_conf = confidence;
+    ransac_tables(p->left_number < 50 ? p->left_number : 50, max_trials, confidence, p->ransac_samples, p->ransac_need);
+    p->ransac_trials = max_trials;
+    return 0;
+    BP_CATCH
+}
+
+size_t bp_pose_ransac_workspace_bytes(int batch, int max_trials) {
+    return batch > 0 && max_trials > 0 ? pose_ransac_ws_bytes(batch, max_trials) : 0;
+}
+
+int bp_pose_from_records_ransac(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
+                                int left_number, double reproj_err, int max_trials, double confidence, double* d_poses,
+                                void* d_workspace, size_t workspace_bytes, void* stream) {
+    BP_TRY
+    BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
+    BP_CHECK(batch >= 0, "batch must be >= 0");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    if (batch == 0) return 0;
+    BP_CHECK(d_workspace && workspace_bytes >= pose_ransac_ws_bytes(batch, max_trials),
+             "bp_pose_from_records_ransac: workspace smaller than bp_pose_ransac_workspace_bytes(batch, max_trials)");
+    BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_pose_from_records_ransac: workspace must be 8-byte aligned");
+    std::vector<int> samples, need;
+    ransac_tables(left_number < 50 ? left_number : 50, max_trials, confidence, samples, need);
+    pose_tail_ransac(d_records, batch, d_kp3d, make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
+                     d_poses, d_workspace, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH

@@ -29,6 +29,7 @@
 // ---- pose_nms (pPose_nms.py:24-122): the greedy cluster / merge over n candidate poses, f32 like the reference.
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -566,6 +567,43 @@ int solve_pnp(const double* P, const double* U, int n, const double* K, double* 
     return solve_pnp_iterative(P, U, n, K, Rout, tout);
 }
 
+// The RANSAC sampler: max_trials rows of six distinct indices below n, drawn with a 64-bit LCG from a fixed seed (so a
+// run is reproducible), duplicates rejected, the state carried from trial to trial.  The sequence depends on
+// (n, max_trials) alone; the host loop below and the device kernels (pnp_ransac.hip) read the same table.
+void pnp_ransac_samples(int n, int max_trials, int* idx) {
+    const int MS = 6;
+    unsigned long long state = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&](int m) {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        return (int)((state >> 33) % (unsigned long long)m);
+    };
+    for (int it = 0; it < max_trials; ++it) {
+        int* row = idx + (size_t)it * MS;
+        for (int k = 0; k < MS;) {
+            const int c = rnd(n);
+            bool dup = false;
+            for (int j = 0; j < k; ++j) dup |= row[j] == c;
+            if (!dup) row[k++] = c;
+        }
+    }
+}
+
+// RANSACUpdateNumIters as a table: need[cnt], cnt = 0 .. n, is the number of trials needed to draw one all-inlier
+// sample at the requested confidence when cnt of n points are inliers, INT_MAX where the estimate is unusable or does
+// not fit an int.  The trial loop applies it as `if (need < trials) trials = max(it + 1, need)`, which is the update
+// `if (den < 0 && num / den < trials) trials = max(it + 1, (int)ceil(num / den))` (for num / den < trials the ceiling
+// is <= trials, and equal to it only where the assignment changes nothing).  log / pow / ceil are evaluated here, on
+// the host, for the device kernels too: another libm could round across an integer and flip the ceiling.
+void pnp_ransac_trials_needed(int n, double confidence, int* need) {
+    const int MS = 6;
+    const double num = std::log(std::max(1.0 - confidence, DBL_MIN));
+    for (int cnt = 0; cnt <= n; ++cnt) {
+        const double ep = 1.0 - (double)cnt / n;
+        const double den = std::log(std::max(1.0 - std::pow(1.0 - ep, MS), DBL_MIN));
+        need[cnt] = (den < 0 && num / den < (double)INT_MAX) ? (int)std::ceil(num / den) : INT_MAX;
+    }
+}
+
 int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, double reproj_err, int max_trials,
                      double confidence, double* Rout, double* tout, unsigned char* inlier_mask) {
     const int MS = 6;                                   // sample size: the DLT initialiser needs 6 points
@@ -574,23 +612,15 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
         if (inlier_mask) std::memset(inlier_mask, 1, n);
         return solve_pnp_iterative(P, U, n, K, Rout, tout);
     }
-    unsigned long long state = 0x9E3779B97F4A7C15ull;  // fixed seed: reproducible
-    auto rnd = [&](int m) {
-        state = state * 6364136223846793005ull + 1442695040888963407ull;
-        return (int)((state >> 33) % (unsigned long long)m);
-    };
     std::vector<unsigned char> best(n, 0), cur(n);
     int best_cnt = 0, trials = std::max(1, max_trials);
+    std::vector<int> samples((size_t)trials * MS), need(n + 1);
+    pnp_ransac_samples(n, trials, samples.data());
+    pnp_ransac_trials_needed(n, confidence, need.data());
     std::vector<double> sp(3 * MS), su(2 * MS), err(2 * n);
     double R[9], t[3], prm[6];
     for (int it = 0; it < trials; ++it) {
-        int idx[MS];
-        for (int k = 0; k < MS;) {
-            const int c = rnd(n);
-            bool dup = false;
-            for (int j = 0; j < k; ++j) dup |= idx[j] == c;
-            if (!dup) idx[k++] = c;
-        }
+        const int* idx = &samples[(size_t)it * MS];
         for (int k = 0; k < MS; ++k) {
             std::memcpy(&sp[3 * k], P + 3 * idx[k], 3 * sizeof(double));
             std::memcpy(&su[2 * k], U + 2 * idx[k], 2 * sizeof(double));
@@ -607,11 +637,7 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
         if (cnt > best_cnt) {
             best_cnt = cnt;
             best = cur;
-            // RANSACUpdateNumIters: trials needed to draw one all-inlier sample at the requested confidence
-            const double ep = 1.0 - (double)cnt / n;
-            const double num = std::log(std::max(1.0 - confidence, DBL_MIN));
-            const double den = std::log(std::max(1.0 - std::pow(1.0 - ep, MS), DBL_MIN));
-            if (den < 0 && num / den < trials) trials = std::max(it + 1, (int)std::ceil(num / den));
+            if (need[cnt] < trials) trials = std::max(it + 1, need[cnt]);
         }
     }
     if (best_cnt < MS) return -2;

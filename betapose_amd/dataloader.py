@@ -13,7 +13,7 @@ import numpy as np
 from .darknet import Darknet
 from .eval import getPrediction
 from .img import crop_from_dets, crop_from_dets_frame, load_frame_bgr  # noqa: F401  (crop_from_dets: reference name)
-from .ops import solve_pnp
+from .ops import solve_pnp, solve_pnp_ransac
 from .opt import opt
 from .pPose_nms import pose_nms
 from .yolo_util import dynamic_write_results
@@ -217,7 +217,7 @@ class DataWriter(_Stage):
     """dataloader.py:649-763: heat-maps -> key points -> pPose-NMS -> key-point pruning -> PnP."""
 
     def __init__(self, cam_K, left_number, kp_model_vertices, save_video=False, savepath='examples/res/1.avi',
-                 fourcc=0, fps=25, frameSize=(640, 480), queueSize=1024):
+                 fourcc=0, fps=25, frameSize=(640, 480), queueSize=1024, ransac=None):
         # same positional signature as the reference (dataloader.py:650-653).  save_video: the annotated frames go to a
         # Motion-JPEG .avi (video.MJPEGWriter stands in for cv2.VideoWriter; `fourcc` is accepted and ignored)
         super().__init__(queueSize)
@@ -230,6 +230,7 @@ class DataWriter(_Stage):
         self.kp_3d = kp_model_vertices
         self.cam_K = cam_K
         self.left_number = left_number
+        self.ransac = ransac              # (reproj_err, max_trials, confidence): --pnp_ransac; None: the reference's pnp
         self._pending = 0                 # items handed to save() and not yet fully processed by the writer thread
         self._pending_lock = Lock()
         self._thread = None
@@ -250,7 +251,10 @@ class DataWriter(_Stage):
             best = poses[0]
             kp_2d, _, kp_3d = keep_best_keypoints(best['keypoints'], np.asarray(best['kp_score'])[:, 0], self.kp_3d,
                                                   self.left_number)
-            result['cam_R'], result['cam_t'] = solve_pnp(kp_3d, kp_2d, self.cam_K)
+            if self.ransac is not None:
+                result['cam_R'], result['cam_t'], result['pnp_inliers'] = solve_pnp_ransac(kp_3d, kp_2d, self.cam_K, *self.ransac)
+            else:
+                result['cam_R'], result['cam_t'] = solve_pnp(kp_3d, kp_2d, self.cam_K)
         return result
 
     def update(self):

@@ -166,6 +166,71 @@ def solve_pnp_ransac(points_3d, points_2d, K, reprojection_error: float = 12.0, 
     return R, t.reshape(3, 1), inl.astype(bool)
 
 
+def pnp_ransac_samples(n: int, max_trials: int = 100):
+    """The draws of ``solve_pnp_ransac``'s sampler (bp_pnp_ransac_samples): int32 [max_trials, 6], six distinct indices
+    below ``n`` per trial.  They depend on (n, max_trials) alone; host and device solver read this one table."""
+    idx = np.empty((int(max_trials), 6), np.int32)
+    _lib.check(_lib.lib().bp_pnp_ransac_samples(int(n), int(max_trials), idx.ctypes.data))
+    return idx
+
+
+def pnp_ransac_trials_needed(n: int, confidence: float = 0.99):
+    """The early stop of ``solve_pnp_ransac`` as a table (bp_pnp_ransac_trials_needed): int32 [n + 1], the trial limit
+    after a hypothesis with ``cnt`` inliers (INT_MAX: none)."""
+    need = np.empty(int(n) + 1, np.int32)
+    _lib.check(_lib.lib().bp_pnp_ransac_trials_needed(int(n), float(confidence), need.ctypes.data))
+    return need
+
+
+def solve_pnp_ransac_batch(points_3d, points_2d, K, reprojection_error: float = 12.0, iterations: int = 100,
+                           confidence: float = 0.99, workspace=None):
+    """``solve_pnp_ransac`` over P independent problems on the device (bp_solve_pnp_ransac_batch): every hypothesis of
+    every problem is one wave, then one wave per problem replays the host's trial loop and refits on the inliers -- the
+    result is the host loop's.  Arguments as ``solve_pnp_batch``.  Returns (Rt [P,3,4] f64, status [P] int32, inliers
+    [P,n] bool) as cuda tensors: status 0 solved, -1 fewer than six points, -2 no six-point consensus or a degenerate
+    refit (Rt NaN there).  ``workspace``: a cuda uint8 tensor to reuse between calls (default: allocated here)."""
+    import torch
+    _lib.require_gpu()
+    p2 = torch.as_tensor(points_2d, dtype=torch.float64).cuda().contiguous()
+    assert p2.dim() == 3 and p2.shape[2] >= 2, "points_2d must be [P, n, 2]"
+    p2 = p2[:, :, :2].contiguous()
+    P, n = p2.shape[0], p2.shape[1]
+    p3 = torch.as_tensor(points_3d, dtype=torch.float64).to(p2.device).contiguous()
+    shared = p3.dim() == 2
+    assert p3.shape[-2:] == (n, 3) and (shared or p3.shape[0] == P), "points 3D and points 2D must have same number of vertices"
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    Rt = torch.empty((P, 3, 4), dtype=torch.float64, device=p2.device)
+    st = torch.empty(P, dtype=torch.int32, device=p2.device)
+    inl = torch.empty((P, n), dtype=torch.uint8, device=p2.device)
+    if workspace is None:
+        nbytes = int(_lib.lib().bp_pnp_ransac_workspace_bytes(P, max(int(iterations), 1)))
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=p2.device)
+    _lib.check(_lib.lib().bp_solve_pnp_ransac_batch(p3.data_ptr(), int(shared), p2.data_ptr(), n, P, Kc.ctypes.data,
+                                                    float(reprojection_error), int(iterations), float(confidence),
+                                                    Rt.data_ptr(), st.data_ptr(), inl.data_ptr(), workspace.data_ptr(),
+                                                    workspace.numel(), _lib.current_stream()))
+    return Rt, st, inl.bool()
+
+
+def pose_from_records_ransac(records, kp3d, K, left_number: int = 50, reprojection_error: float = 12.0,
+                             iterations: int = 100, confidence: float = 0.99):
+    """``pose_from_records`` with the RANSAC solver (bp_pose_from_records_ransac): slot 15 of a row is the inlier set."""
+    import torch
+    _lib.require_gpu()
+    rec = records.contiguous()
+    assert rec.dtype == torch.float32 and rec.dim() == 2 and rec.shape[1] == _lib.RESULT_FLOATS
+    k3 = torch.as_tensor(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3), device=rec.device).contiguous()
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    out = torch.empty((rec.shape[0], _lib.POSE_DOUBLES), dtype=torch.float64, device=rec.device)
+    nbytes = int(_lib.lib().bp_pose_ransac_workspace_bytes(rec.shape[0], max(int(iterations), 1)))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=rec.device)
+    _lib.check(_lib.lib().bp_pose_from_records_ransac(rec.data_ptr(), rec.shape[0], k3.data_ptr(), k3.shape[0], Kc.ctypes.data,
+                                                      int(left_number), float(reprojection_error), int(iterations),
+                                                      float(confidence), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _lib.current_stream()))
+    return out
+
+
 def heatmap_argmax(hm):
     """Device arg-max records of a heat-map tensor: cuda f32 [B,K,H,W] -> [B,K,6] (idx as int bits, max, l, r, u, d)."""
     import torch

@@ -47,6 +47,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--device_pnp', default=False, action='store_true',
                    help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '
                         'graph (the device pose tail, DESIGN.md 3.5); rank 0 only builds the result dicts')
+    p.add_argument('--pnp_ransac', nargs='?', type=float, default=None, const=12.0, metavar='PX',
+                   help='solve the pose with the RANSAC variant the reference keeps commented out (utils/utils.py:32-36): '
+                        'reprojection error in pixels (default 12.0), 100 trials, confidence 0.99; in the host tail and, '
+                        'with --device_pnp, on the GPU with the hypotheses in parallel (DESIGN.md 3.5)')
     p.add_argument('--synthetic', type=int, default=0, help='run on N seeded synthetic frames / weights')
     p.add_argument('--synth_weights', default=False, action='store_true',
                    help='seeded synthetic weights with real frames / ground truth (plumbing runs without checkpoints)')

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from .eval import decode_keypoints
-from .ops import solve_pnp
+from .ops import solve_pnp, solve_pnp_ransac
 from .pPose_nms import pose_nms
 
 RESULT_FLOATS = _lib.RESULT_FLOATS
@@ -69,12 +69,15 @@ class FramePipeline:
             b = np.ascontiguousarray(box_xyxy, dtype=np.float32)
             _lib.check(_lib.lib().bp_pipeline_set_fixed_box(self._h, b.ctypes.data))
 
-    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50):
+    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50, ransac=None):
         """Opt-in device pose tail: every run then also writes ``self.poses`` [B, 166] f64, the frame's pose record
         (include/betapose_hip.h BP_POSE_DOUBLES; ``finish_pose_record`` turns it into ``finish_record``'s dict).
-        ``kp3d`` [50, 3]: the 3-D key points; ``cam_K`` [3, 3]; ``left_number``: --left_keypoints.  None switches it off."""
+        ``kp3d`` [50, 3]: the 3-D key points; ``cam_K`` [3, 3]; ``left_number``: --left_keypoints.  None switches it off.
+        ``ransac``: ``(reproj_err, max_trials, confidence)`` solves with the device RANSAC (``set_pose_ransac``) instead
+        of the plain iterative PnP; None: the iterative tail."""
         import torch
         if kp3d is None:
+            _lib.check(_lib.lib().bp_pipeline_set_pose_ransac(self._h, 0.0, 0, 0.0))
             _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, None, 0, None, 0, None))
             return self
         k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
@@ -84,6 +87,14 @@ class FramePipeline:
             torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
         _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, k3.ctypes.data, k3.shape[0], Kc.ctypes.data,
                                                           int(left_number), self.poses.data_ptr()))
+        return self.set_pose_ransac(ransac)
+
+    def set_pose_ransac(self, ransac=None):
+        """``(reproj_err, max_trials, confidence)``: the device pose tail (which must be on) solves with RANSAC, the
+        hypotheses in parallel (bp_pipeline_set_pose_ransac) -- the host solver's result, its inlier set in slot 15 of
+        the pose row.  None (or ``max_trials`` 0): back to the iterative tail."""
+        err, trials, conf = (0.0, 0, 0.0) if ransac is None else ransac
+        _lib.check(_lib.lib().bp_pipeline_set_pose_ransac(self._h, float(err), int(trials), float(conf)))
         return self
 
     def enqueue(self, stream: Optional[int] = None):
@@ -142,7 +153,7 @@ class StreamedRunner:
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, streams: int = 4,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, batch: int = 1,
                  pose_solver=None):
-        """``pose_solver``: ``(kp3d, cam_K, left_number)`` turns the device pose tail on in every stream's pipeline; the
+        """``pose_solver``: ``(kp3d, cam_K, left_number)`` or ``(kp3d, cam_K, left_number, ransac)`` turns the device pose tail on in every stream's pipeline; the
         pose rows then come back with the records and ``on_record`` gets ``(index, rec, pose_row)``.
         ``batch`` frames per launch and stream (the reference's ``--detbatch``, dataloader.py:284-289): the engines
         must have been created with ``max_batch >= batch``.  More frames per launch mean fewer launches, K slices and
@@ -249,7 +260,7 @@ class MultiObjectRunner:
     shards them ``u % world``).
 
     ``engines``: {obj_id: (Darknet, FastPoseHIP)} for the objects this rank owns units of.  ``pose_solvers``:
-    {obj_id: (kp3d, cam_K, left_number)} turns the device pose tail on (every object in ``engines`` needs one); then
+    {obj_id: (kp3d, cam_K, left_number[, ransac])} turns the device pose tail on (every object in ``engines`` needs one); then
     ``on_record`` gets ``(u, rec, pose_row)``."""
 
     def __init__(self, engines: dict, obj_ids: List[int], frame_h: int = 480, frame_w: int = 640, streams: int = 4,
@@ -348,9 +359,12 @@ class MultiObjectRunner:
         return j
 
 
-def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray, left_number: int = 50) -> dict:
+def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray, left_number: int = 50,
+                  ransac=None) -> dict:
     """Host tail for one frame: 316-float record -> the dict ``DataWriter.update`` appends to
-    ``final_result`` (dataloader.py:704-727): {'imgname', 'result', 'cam_R', 'cam_t'} (+ the raw boxes)."""
+    ``final_result`` (dataloader.py:704-727): {'imgname', 'result', 'cam_R', 'cam_t'} (+ the raw boxes).
+    ``ransac``: ``(reproj_err, max_trials, confidence)`` solves the pruned points with ``ops.solve_pnp_ransac`` (the
+    variant utils/utils.py:32-36 keeps commented out) and adds 'pnp_inliers', a bool array over the kept points."""
     rec = np.ascontiguousarray(rec, dtype=np.float32)
     idx = int(rec[:1].view(np.int32)[0])
     if idx < 0:     # no detection: the reference forwards the frame with boxes=None and records nothing
@@ -371,7 +385,11 @@ def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.nd
             kp_score = np.delete(kp_score, d)
             kp_2d = np.delete(kp_2d, d, axis=0)
             k3 = np.delete(k3, d, axis=0)
-        R, t = solve_pnp(k3, kp_2d, cam_K)
+        if ransac is not None:
+            R, t, inl = solve_pnp_ransac(k3, kp_2d, cam_K, ransac[0], ransac[1], ransac[2])
+            out["pnp_inliers"] = inl
+        else:
+            R, t = solve_pnp(k3, kp_2d, cam_K)
         out.update({"cam_R": R, "cam_t": t})
     else:
         out.update({"cam_R": [], "cam_t": []})
@@ -403,5 +421,7 @@ def finish_pose_record(rec: np.ndarray, pose_row: np.ndarray, imgname: str) -> d
                       "keypoints": kp[:, :2].copy(),
                       "kp_score": kp[:, 2:3].copy(),
                       "proposal_score": np.array([row[14]], dtype=np.float32)}]
+    if row[15] != 0:      # RANSAC tail: bit j of the integer-valued slot is the j-th point handed to the PnP
+        out["pnp_inliers"] = ((int(row[15]) >> np.arange(int(row[1]), dtype=np.int64)) & 1).astype(bool)
     out.update({"cam_R": row[2:11].reshape(3, 3).copy(), "cam_t": row[11:14].reshape(3, 1).copy()})
     return out

@@ -77,6 +77,8 @@ def main():
     obj_id = args.obj_id
     # key points handed to PnP: all 50 on LineMod (betapose_evaluate.py:139), the --left_keypoints best on Occlusion
     left_number = args.left_keypoints if args.occlusion else 50
+    # --pnp_ransac [PX]: the RANSAC variant (100 trials, confidence 0.99: ops.solve_pnp_ransac's defaults) in either tail
+    ransac = (float(args.pnp_ransac), 100, 0.99) if args.pnp_ransac is not None else None
     pixel_thresh = 20.0 if args.occlusion else 5.0          # occlusion_betapose_evaluate.py:255 vs betapose_evaluate.py:257
     print("Betapose begin running now.  Test object", obj_id, "| key points for PnP:", left_number)
     os.makedirs(args.outputpath, exist_ok=True)
@@ -143,7 +145,7 @@ def main():
                                  depth=max(16, 2 * args.streams * max(1, args.detbatch) + threads))
             runner = StreamedRunner(det, pose_model, loader.height, loader.width, streams=args.streams,
                                     confidence=args.confidence, num_classes=args.num_classes, batch=args.detbatch,
-                                    pose_solver=(kp3d, cam_K, left_number) if args.device_pnp else None)
+                                    pose_solver=(kp3d, cam_K, left_number, ransac) if args.device_pnp else None)
             runner.run(loader, keep)
             loader.close()
         t_dev = time.time() - t_dev
@@ -158,7 +160,7 @@ def main():
                 if allpose is not None:
                     out = finish_pose_record(allrec[i], np.ascontiguousarray(allpose[i]).view(np.float64), name)
                 else:
-                    out = finish_record(allrec[i], name, kp3d, cam_K, left_number)
+                    out = finish_record(allrec[i], name, kp3d, cam_K, left_number, ransac=ransac)
                 if out["boxes"] is not None:
                     final_result.append(out)
     else:
@@ -168,7 +170,7 @@ def main():
         data_loader = ImageLoader(im_names, batchSize=args.detbatch, format='yolo', reso=int(args.inp_dim)).start()
         det_loader = DetectionLoader(data_loader, obj_id, batchSize=args.detbatch, det_model=det).start()
         det_processor = DetectionProcessor(det_loader).start()
-        writer = DataWriter(cam_K, left_number, kp3d).start()
+        writer = DataWriter(cam_K, left_number, kp3d, ransac=ransac).start()
         prof = {'dt': [], 'pt': [], 'pn': []}
         for i in range(data_loader.length()):
             t_s = time.time()

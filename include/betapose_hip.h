@@ -30,6 +30,8 @@
  *                          decode (getPrediction), pPose-NMS at n = 1, pruning to   KPD/src/utils/eval.py:113-147
  *                          --left_keypoints, pnp                                     pPose_nms.py:24-122, utils/utils.py:17-41
  *   bp_solve_pnp_batch     pnp over P independent problems on device            utils/utils.py:17-41
+ *   bp_solve_pnp_ransac_batch, bp_pipeline_set_pose_ransac, bp_pose_from_records_ransac
+ *                          the solvePnPRansac variant on device, hypotheses in parallel   utils/utils.py:32-36
  *   bp_pose_errors         add_err / projection_error_2d + the commented-out   utils/metrics.py:10-33,99-127
  *                          closest-point (ADD-S) loop, over every vertex
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
@@ -73,10 +75,14 @@ typedef struct bp_pipeline bp_pipeline;
 
 /* doubles per frame in the pose record of the device pose tail (bp_pipeline_set_pose_solver, bp_pose_from_records):
  *   [0]        status: 0 ok, 1 no detection, 2 dropped by pPose-NMS, < 0 the solver's status as bp_solve_pnp reports it
- *              (-1 too few points, -2 degenerate or non-finite)
- *   [1]        key points used by the PnP (after the left_number pruning)
+ *              (-1 too few points, -2 degenerate or non-finite; with RANSAC on: -1 fewer than six points, -2 no
+ *              six-point consensus, else the status of the refit on the inliers)
+ *   [1]        key points handed to the PnP (after the left_number pruning)
  *   [2..10]    R row-major, [11..13] t -- NaN unless status 0
- *   [14]       proposal score, [15] 0
+ *   [14]       proposal score
+ *   [15]       0; with RANSAC on (bp_pipeline_set_pose_ransac, bp_pose_from_records_ransac) the inlier set: an
+ *              integer-valued double whose bit j is the j-th point handed to the PnP (at most 50 bits, exact in f64);
+ *              0 for status 1, 2, -1 and -2
  *   [16..165]  50 x (x, y, score) after pPose-NMS (the - 0.3 applied; f32 values held exactly), zero for status 1 and 2 */
 #define BP_POSE_DOUBLES 166
 #define BP_PNP_MAX_POINTS 64
@@ -254,6 +260,37 @@ int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d
  * 0), d_status [P] (bp_solve_pnp's codes: 0, -1 too few points, -2 degenerate).  Asynchronous on `stream`. */
 int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
                        double* d_Rt, int* d_status, void* stream);
+
+/* ---- RANSAC PnP on device (the solvePnPRansac variant, utils/utils.py:32-36) ----
+ * The device result is the result of bp_solve_pnp_ransac's sequential loop: same samples, same inlier test, same early
+ * stop, the refit by bp_solve_pnp_batch's solver on the same inlier set -- R, t agree with the host to the rounding that
+ * solver's contract leaves, masks and statuses are equal unless a point's reprojection error sits within that rounding
+ * of the threshold.  All max_trials hypotheses run in parallel (one wave each), then one wave per problem replays the
+ * host's loop over their inlier counts and refits.
+ *
+ * bp_pnp_ransac_samples: the sampler's draws, idx [max_trials][6] -- six distinct indices below n per trial; depends on
+ * (n, max_trials) only.  bp_pnp_ransac_trials_needed: need [n + 1], the trial limit after a hypothesis with cnt inliers
+ * (INT_MAX: no limit), applied as `if (need[cnt] < trials) trials = max(it + 1, need[cnt])`.  Host only, no device work. */
+int bp_pnp_ransac_samples(int n, int max_trials, int* idx);
+int bp_pnp_ransac_trials_needed(int n, double confidence, int* need);
+size_t bp_pnp_ransac_workspace_bytes(int P, int max_trials);
+/* P problems of n <= BP_PNP_MAX_POINTS points (layout as bp_solve_pnp_batch).  d_Rt [P][12], NaN unless the status is 0;
+ * d_status [P]: 0, -1 (n < 6), -2 (no six-point consensus) or the refit's status; d_inliers [P][n] u8 or NULL, all zero
+ * for status -1 / -2.  d_workspace: bp_pnp_ransac_workspace_bytes(P, max_trials) bytes, 8-byte aligned, the caller's,
+ * in use until the stream has passed the call.  Asynchronous on `stream`, no allocation, capturable. */
+int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
+                              double reproj_err, int max_trials, double confidence, double* d_Rt, int* d_status,
+                              unsigned char* d_inliers, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The device pose tail with RANSAC in place of the plain PnP: needs a pose solver set (bp_pipeline_set_pose_solver keeps
+ * the setting); max_trials = 0 switches back to the iterative tail.  Drops the captured graph.  While on, the tail is
+ * three launches (prepare: decode / NMS / pruning; hypotheses; select-and-refit) instead of one and slot [15] of the
+ * pose record carries the inlier set.  The workspace is the pipeline's. */
+int bp_pipeline_set_pose_ransac(bp_pipeline* p, double reproj_err, int max_trials, double confidence);
+size_t bp_pose_ransac_workspace_bytes(int batch, int max_trials);
+/* bp_pose_from_records with the RANSAC solver; d_workspace: bp_pose_ransac_workspace_bytes(batch, max_trials) bytes */
+int bp_pose_from_records_ransac(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
+                                int left_number, double reproj_err, int max_trials, double confidence, double* d_poses,
+                                void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- host post-processing (no device work) ---- */
 /* pnp (utils/utils.py:17-41): a restatement of cv2.solvePnP's default SOLVEPNP_ITERATIVE (planar / DLT initialisation,

@@ -54,6 +54,8 @@ def main():
     assert len(obj_ids) == len(set(obj_ids)) and obj_ids, "--obj_ids: distinct object ids"
     K = len(obj_ids)
     left_number = args.left_keypoints
+    # --pnp_ransac [PX]: the RANSAC variant (100 trials, confidence 0.99: ops.solve_pnp_ransac's defaults) in either tail
+    ransac = (float(args.pnp_ransac), 100, 0.99) if args.pnp_ransac is not None else None
     os.makedirs(args.outputpath, exist_ok=True)
     if len(args.inputlist):
         im_names = [l.strip() for l in open(args.inputlist)]
@@ -107,7 +109,7 @@ def main():
         solvers = {}
         for o in my_objs:
             kp3d = gt[o][2] if o in gt else evaluate.load_sixd_gt(args.sixd_base, o, 2)[2]
-            solvers[o] = (metrics.refine_keypoints(kp3d, 50) if len(kp3d) > 50 else kp3d, synth.CAM_K, left_number)
+            solvers[o] = (metrics.refine_keypoints(kp3d, 50) if len(kp3d) > 50 else kp3d, synth.CAM_K, left_number, ransac)
 
     # ---- run this rank's units
     recs, poses = {}, {}
@@ -144,7 +146,7 @@ def main():
                 if allpose is not None:
                     out = finish_pose_record(allrec[f * K + oi], np.ascontiguousarray(allpose[f * K + oi]).view(np.float64), name)
                 else:
-                    out = finish_record(allrec[f * K + oi], name, kp3d, synth.CAM_K, left_number)
+                    out = finish_record(allrec[f * K + oi], name, kp3d, synth.CAM_K, left_number, ransac=ransac)
                 if out["boxes"] is not None:
                     final_result.append(out)
             odir = os.path.join(args.outputpath, "obj_%02d" % o)
