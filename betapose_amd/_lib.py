@@ -37,6 +37,7 @@ PROTOTYPES = {
     "bp_yolo_attrs": (C.c_int, [vp]),
     "bp_yolo_forward": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "bp_yolo_forward_select": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
+    "bp_yolo_forward_select_classes": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp]),
     "bp_yolo_select": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]),
     "bp_yolo_tap_count": (C.c_int, [vp]),
     "bp_yolo_tap_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, c_int_p, c_int_p, c_int_p]),
@@ -87,6 +88,15 @@ PROTOTYPES = {
     "bp_pipeline_run": (C.c_int, [vp, C.c_int, vp]),
     "bp_pipeline_prepare": (C.c_int, [vp]),
     "bp_pipeline_latency_faults": (C.c_int, [vp]),
+    "bp_scene_create": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.POINTER(vp)]),
+    "bp_scene_destroy": (None, [vp]),
+    "bp_scene_results": (vp, [vp]),
+    "bp_scene_poses": (vp, [vp]),
+    "bp_scene_set_pose_solver": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
+    "bp_scene_set_pose_ransac": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_double]),
+    "bp_scene_prepare": (C.c_int, [vp]),
+    "bp_scene_run": (C.c_int, [vp, C.c_int, vp]),
+    "bp_scene_kernel_count": (C.c_int, [vp]),
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
@@ -134,6 +144,7 @@ PROTOTYPES = {
 RESULT_FLOATS = 316
 POSE_DOUBLES = 166          # include/betapose_hip.h BP_POSE_DOUBLES
 PNP_MAX_POINTS = 64
+MAX_SCENE_CLASSES = 16      # include/betapose_hip.h BP_MAX_SCENE_CLASSES
 
 
 class BetaposeHipError(RuntimeError):

@@ -466,6 +466,160 @@ void launch_yolo_decode_select(const YoloHead* heads, int nheads, int N, int res
     hipLaunchKernelGGL(yolo_decode_select_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, sel, sel_ld);
 }
 
+// ---------------------------------------------------------------- per-class select (shared multi-class detector)
+// write_results(nms=False) with the class filter generalised: the row's arg-max class (first maximum wins) is looked up in
+// a list of up to BP_MAX_SCENE_CLASSES class ids, and the row competes for that list slot only.  ONE pass over the rows: every
+// thread keeps a (objectness, row) pair per slot in registers (constant indices: the slot loops are unrolled), the slots
+// are reduced wave by wave with shuffles and across waves through LDS, and thread k writes slot k's record.  Row sources:
+// the decoded [rows][attrs] tensor (PredRows) or the head tensors (HeadRows), with the float operations of
+// yolo_select_kernel / yolo_decode_select_kernel -- with the list {0} the record is theirs bit for bit.
+struct PredRows {
+    const float* P;   // this image's [rows][attrs]
+    int attrs;
+    __device__ __forceinline__ const float* row(int r) const { return P + (long long)r * attrs; }
+    __device__ __forceinline__ float attr(const float* q, int k) const { return q[k]; }   // k >= 4: objectness, class scores
+    __device__ __forceinline__ void box(int, const float* q, float* b) const { b[0] = q[0]; b[1] = q[1]; b[2] = q[2]; b[3] = q[3]; }
+};
+struct HeadRows {
+    const YoloHeads* hs;
+    int n, attrs, reso;
+    __device__ __forceinline__ int head_of(int r) const {
+        int hi = 0;
+        for (int k = 1; k < hs->n; ++k)
+            if (r >= hs->h[k].row_off) hi = k;
+        return hi;
+    }
+    __device__ __forceinline__ const float* row(int r) const {
+        const YoloHead& H = hs->h[head_of(r)];
+        const int g = H.g, rr = r - H.row_off;
+        const int a = rr / (g * g);
+        const int cell = rr - a * g * g;
+        return H.t + ((long long)n * g * g + cell) * (3 * attrs) + a * attrs;
+    }
+    __device__ __forceinline__ float attr(const float* t, int k) const { return sigmoidf_(t[k]); }
+    __device__ __forceinline__ void box(int r, const float* t, float* b) const {
+        const YoloHead& H = hs->h[head_of(r)];
+        const int g = H.g, rr = r - H.row_off;
+        const int a = rr / (g * g);
+        const int cell = rr - a * g * g;
+        const int gy = cell / g, gx = cell - gy * g;
+        const float stride = (float)(reso / g);
+        b[0] = (sigmoidf_(t[0]) + (float)gx) * stride;
+        b[1] = (sigmoidf_(t[1]) + (float)gy) * stride;
+        b[2] = (expf(t[2]) * (H.aw[a] / stride)) * stride;
+        b[3] = (expf(t[3]) * (H.ah[a] / stride)) * stride;
+    }
+};
+template <class Rows>
+__device__ __forceinline__ void select_classes(const Rows& src, int rows, float conf, int ncls, const YoloClassList& cl,
+                                               float* __restrict__ out, int ld_slot, float (*sv)[16], int (*si)[16]) {
+    constexpr int S = BP_MAX_SCENE_CLASSES;
+    float best[S];
+    int bi[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) { best[k] = -1.f; bi[k] = 0x7fffffff; }
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        const float* q = src.row(r);
+        const float obj = src.attr(q, 4);
+        if (!(obj > conf)) continue;
+        int cls = 0;
+        float cm = src.attr(q, 5);
+        for (int k = 1; k < ncls; ++k) {
+            const float v = src.attr(q, 5 + k);
+            if (v > cm) { cm = v; cls = k; }
+        }
+#pragma unroll
+        for (int k = 0; k < S; ++k)
+            if (k < cl.n && cl.id[k] == cls && (obj > best[k] || (obj == best[k] && r < bi[k]))) { best[k] = obj; bi[k] = r; }
+    }
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        if (k < cl.n) {   // uniform
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ov = __shfl_down(best[k], off, 64);
+                const int oi = __shfl_down(bi[k], off, 64);
+                if (ov > best[k] || (ov == best[k] && oi < bi[k])) { best[k] = ov; bi[k] = oi; }
+            }
+            if ((threadIdx.x & 63) == 0) { sv[k][w] = best[k]; si[k][w] = bi[k]; }
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cl.n) {
+        const int k = threadIdx.x;
+        int id = 0;
+#pragma unroll
+        for (int j = 0; j < S; ++j)
+            if (j == k) id = cl.id[j];
+        float b = sv[k][0];
+        int i = si[k][0];
+        for (int j = 1; j < (int)(blockDim.x >> 6); ++j)
+            if (sv[k][j] > b || (sv[k][j] == b && si[k][j] < i)) { b = sv[k][j]; i = si[k][j]; }
+        float* o = out + (long long)k * ld_slot;
+        if (b < 0.f) {
+            o[0] = __int_as_float(-1);
+            for (int j = 1; j < 8; ++j) o[j] = 0.f;
+        } else {
+            const float* q = src.row(i);
+            float x[4];
+            src.box(i, q, x);
+            o[0] = __int_as_float(i);
+            o[1] = x[0] - x[2] / 2;
+            o[2] = x[1] - x[3] / 2;
+            o[3] = x[0] + x[2] / 2;
+            o[4] = x[1] + x[3] / 2;
+            o[5] = src.attr(q, 4);
+            o[6] = src.attr(q, 5 + id);
+            o[7] = (float)id;
+        }
+    }
+}
+__global__ __launch_bounds__(1024) void yolo_select_classes_kernel(const float* __restrict__ pred, int rows, int attrs, float conf,
+                                                                    int num_classes, YoloClassList cl, float* __restrict__ sel,
+                                                                    int ld_image, int ld_slot) {
+    __shared__ float sv[BP_MAX_SCENE_CLASSES][16];
+    __shared__ int si[BP_MAX_SCENE_CLASSES][16];
+    const PredRows src{pred + (long long)blockIdx.x * rows * attrs, attrs};
+    select_classes(src, rows, conf, min(num_classes, attrs - 5), cl, sel + (long long)blockIdx.x * ld_image, ld_slot, sv, si);
+}
+__global__ __launch_bounds__(1024) void yolo_decode_select_classes_kernel(YoloHeads hs, int reso, int attrs, int rows, float conf,
+                                                                           int num_classes, YoloClassList cl, float* __restrict__ sel,
+                                                                           int ld_image, int ld_slot) {
+    __shared__ float sv[BP_MAX_SCENE_CLASSES][16];
+    __shared__ int si[BP_MAX_SCENE_CLASSES][16];
+    const HeadRows src{&hs, (int)blockIdx.x, attrs, reso};
+    select_classes(src, rows, conf, min(num_classes, attrs - 5), cl, sel + (long long)blockIdx.x * ld_image, ld_slot, sv, si);
+}
+YoloClassList make_class_list(const int* class_ids, int K, int num_classes, int attrs) {
+    BP_CHECK(K >= 1 && K <= BP_MAX_SCENE_CLASSES, "class list: 1 to 16 class ids (BP_MAX_SCENE_CLASSES)");
+    BP_CHECK(class_ids, "class list: null class ids");
+    const int ncls = num_classes < attrs - 5 ? num_classes : attrs - 5;
+    YoloClassList cl{};
+    cl.n = K;
+    for (int k = 0; k < K; ++k) {
+        if (class_ids[k] < 0 || class_ids[k] >= ncls)
+            throw Error("class list: class id " + std::to_string(class_ids[k]) + " is not below the detector's class count " + std::to_string(ncls));
+        for (int j = 0; j < k; ++j)
+            if (class_ids[j] == class_ids[k]) throw Error("class list: duplicate class id " + std::to_string(class_ids[k]));
+        cl.id[k] = class_ids[k];
+    }
+    return cl;
+}
+void launch_yolo_select_classes(const float* pred, int N, int rows, int attrs, float conf, int num_classes, const YoloClassList& cl,
+                                float* sel, hipStream_t s, int ld_image, int ld_slot) {
+    hipLaunchKernelGGL(yolo_select_classes_kernel, dim3(N), dim3(1024), 0, s, pred, rows, attrs, conf, num_classes, cl, sel, ld_image, ld_slot);
+}
+void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
+                                       const YoloClassList& cl, float* sel, hipStream_t s, int ld_image, int ld_slot) {
+    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
+    YoloHeads hs;
+    hs.n = nheads;
+    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
+    hipLaunchKernelGGL(yolo_decode_select_classes_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, cl, sel,
+                       ld_image, ld_slot);
+}
+
 // ---------------------------------------------------------------- heat-map arg-max (+4 neighbours), eval.py:113-147
 __global__ __launch_bounds__(256) void heatmap_argmax_kernel(const float* __restrict__ hm, int H, int W,
                                                               float* __restrict__ out, int C, int out_ld) {

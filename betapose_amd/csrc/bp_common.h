@@ -305,6 +305,22 @@ void launch_yolo_select(const float* pred, int N, int rows, int attrs, float con
 // both in one launch, for callers that read the select record only (no [rows][attrs] tensor is written): same records
 void launch_yolo_decode_select(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
                                float* sel, hipStream_t s, int sel_ld = 8);
+// Per-class select for a shared multi-class detector: K <= BP_MAX_SCENE_CLASSES class ids travel BY VALUE in the launch
+// arguments (nothing is uploaded, the launch captures into a graph as it is).  A row with objectness > conf is a candidate
+// for the list slot that holds its arg-max class; per slot the arg-max objectness row wins (lower row on ties).
+// sel + n * ld_image + k * ld_slot: the record of image n, slot k -- launch_yolo_select's, with [6] = the winning class's
+// score and [7] = the class id; index -1 and zeros when the class has no row.  Both forms write identical records.
+#define BP_MAX_SCENE_CLASSES 16
+struct YoloClassList {
+    int n;
+    int id[BP_MAX_SCENE_CLASSES];
+};
+// checks the list (1..16 ids, distinct, each below min(num_classes, attrs - 5)) and packs it; throws Error otherwise
+YoloClassList make_class_list(const int* class_ids, int K, int num_classes, int attrs);
+void launch_yolo_select_classes(const float* pred, int N, int rows, int attrs, float conf, int num_classes, const YoloClassList& cl,
+                                float* sel, hipStream_t s, int ld_image, int ld_slot);
+void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf,
+                                       int num_classes, const YoloClassList& cl, float* sel, hipStream_t s, int ld_image, int ld_slot);
 // hm NCHW [N][C][H*W] -> out [N][C][6] = (idx as int bits, max, left, right, up, down)
 // out_ld: floats between consecutive images' [C][6] blocks (0 = dense C*6)
 void launch_heatmap_argmax(const float* hm, int N, int C, int H, int W, float* out, hipStream_t s, int out_ld = 0);

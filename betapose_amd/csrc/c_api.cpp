@@ -141,6 +141,48 @@ struct bp_pipeline {
     }
 };
 
+// One shared multi-class detector pass per frame feeding K objects' pose chains (bp_scene_*): slot k = class_ids[k], its
+// key-point engine, result row k and (opt-in) its pose tail.
+struct bp_scene_slot {
+    bp_kpd* k = nullptr;
+    unsigned ver_k = 0;
+    bool pose_on = false;
+    double* kp3d = nullptr;
+    double* poses = nullptr;
+    bp::PnpCam cam{};
+    int left_number = 50;
+    int ransac_trials = 0;
+    double ransac_err = 0, ransac_conf = 0;
+    std::vector<int> ransac_samples, ransac_need;
+    void* ransac_ws = nullptr;
+    size_t ransac_ws_bytes = 0;
+};
+struct bp_scene {
+    bp_yolo* y;
+    std::vector<bp_scene_slot> slots;
+    std::vector<int> class_ids;
+    int H, W;
+    float conf;
+    int num_classes;
+    bp::Arena arena;
+    uint8_t* frames = nullptr;
+    uint8_t* tmp = nullptr;
+    float* results = nullptr;    // [K][316], row k = slot k's record
+    double* own_poses = nullptr; // [K][166], rows of the slots whose solver was set without a buffer
+    int *hb = nullptr, *hk = nullptr, *vb = nullptr, *vk = nullptr;
+    int ksh = 0, ksv = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipStream_t cap_stream = nullptr;
+    unsigned ver_y = 0;
+    int latency_faults = 0;
+    ~bp_scene() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+    }
+};
+
 static std::string read_text(const char* path) {
     std::ifstream f(path);
     if (!f) throw bp::Error(std::string("cannot open ") + path);
@@ -306,6 +348,16 @@ int bp_yolo_forward_select(bp_yolo* y, const float* d_img, int batch, float conf
     BP_TRY
     BP_CHECK(y && d_img && d_sel, "null argument");
     y->net->forward(d_img, false, batch, d_pred, conf, num_classes, d_sel, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_forward_select_classes(bp_yolo* y, const float* d_img, int batch, float conf, int num_classes, const int* class_ids,
+                                   int K, float* d_pred, float* d_sel, void* stream) {
+    BP_TRY
+    BP_CHECK(K >= 1 && K <= BP_MAX_SCENE_CLASSES, "class list: 1 to 16 class ids (BP_MAX_SCENE_CLASSES)");
+    BP_CHECK(y && d_img && class_ids && d_sel, "null argument");
+    y->net->forward_classes(d_img, false, batch, d_pred, conf, num_classes, class_ids, K, d_sel, (hipStream_t)stream);
     return 0;
     BP_CATCH
 }
@@ -1073,6 +1125,202 @@ int bp_pipeline_run(bp_pipeline* p, int use_graph, void* stream) {
     BP_CATCH
 }
 int bp_pipeline_latency_faults(const bp_pipeline* p) { return p ? p->latency_faults : -1; }
+
+// ------------------------------------------------------------------ scene: one detector pass, K objects' pose chains
+// Everything on ONE stream in sequence (no parallel branches in the captured graph): resize once, the shared detector with
+// the per-class select writing sel[8] of all K rows, then per slot crop -> KPD -> arg-max -> (opt-in) pose tail -- the
+// launches pipeline_enqueue makes for that object, reading row k's own select record.
+static void scene_enqueue(bp_scene* p, hipStream_t s) {
+    bp::YoloNet& yn = *p->y->net;
+    const int reso = yn.reso(), R = BP_RESULT_FLOATS, K = (int)p->slots.size();
+    bp::ResizeTables t{p->hb, p->hk, p->ksh, p->vb, p->vk, p->ksv};
+    bp::launch_resize_bicubic(p->frames, 1, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    yn.forward_classes(yn.input_nhwc(), true, 1, nullptr, p->conf, p->num_classes, p->class_ids.data(), K, p->results, s, K * R, R);
+    for (int k = 0; k < K; ++k) {
+        bp_scene_slot& sl = p->slots[k];
+        bp::KpdNet& kn = *sl.k->net;
+        float* row = p->results + (size_t)k * R;
+        bp::launch_crop(p->frames, 1, p->H, p->W, row, reso, nullptr, kn.input_nhwc(), nullptr, row + 8, kn.in_h(), kn.in_w(), s, R, R);
+        kn.forward(kn.input_nhwc(), true, 1, nullptr, row + 16, s, R);
+        if (sl.pose_on && sl.ransac_trials > 0)
+            pose_tail_ransac(row, 1, sl.kp3d, sl.cam, sl.left_number, sl.ransac_err, sl.ransac_trials, sl.ransac_samples.data(),
+                             sl.ransac_need.data(), sl.poses, sl.ransac_ws, s);
+        else if (sl.pose_on) bp::launch_pose_tail(row, 1, sl.kp3d, sl.cam, sl.left_number, sl.poses, s);
+    }
+    BP_HIP(hipGetLastError());
+}
+
+int bp_scene_create(bp_yolo* y, bp_kpd* const* kpds, const int* class_ids, int K, int frame_h, int frame_w, float conf,
+                    int num_classes, uint8_t* d_frames, float* d_results, bp_scene** out) {
+    BP_TRY
+    BP_CHECK(K >= 1 && K <= BP_MAX_SCENE_CLASSES, "class list: 1 to 16 class ids (BP_MAX_SCENE_CLASSES)");
+    BP_CHECK(y && kpds && class_ids && out, "null argument");
+    BP_CHECK(frame_h >= 1 && frame_w >= 1, "frame size");
+    (void)bp::make_class_list(class_ids, K, num_classes, y->net->attrs());
+    std::unique_ptr<bp_scene> p(new bp_scene);
+    p->y = y; p->H = frame_h; p->W = frame_w; p->conf = conf; p->num_classes = num_classes;
+    p->class_ids.assign(class_ids, class_ids + K);
+    p->slots.resize(K);
+    for (int k = 0; k < K; ++k) {
+        BP_CHECK(kpds[k], "null key-point engine");
+        BP_CHECK(kpds[k]->net->out_c() == 50, "scene expects 50 key points");
+        BP_CHECK(kpds[k]->device == y->device, "scene: every engine on the detector's device");
+        for (int j = 0; j < k; ++j) BP_CHECK(kpds[j] != kpds[k], "scene: one key-point engine per object (its activations are the slot's)");
+        p->slots[k].k = kpds[k];
+    }
+    BP_HIP(hipSetDevice(y->device));
+    const int reso = y->net->reso();
+    p->frames = d_frames ? d_frames : (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * frame_w * 3);
+    p->tmp = (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * reso * 3);
+    p->results = d_results ? d_results : p->arena.alloc((size_t)K * BP_RESULT_FLOATS);
+    const bp::ResizePlan ph = bp::make_bicubic_plan(frame_w, reso), pv = bp::make_bicubic_plan(frame_h, reso);
+    p->ksh = ph.ksize; p->ksv = pv.ksize;
+    p->hb = (int*)p->arena.alloc_bytes(ph.bounds.size() * 4);
+    p->hk = (int*)p->arena.alloc_bytes(ph.coeffs.size() * 4);
+    p->vb = (int*)p->arena.alloc_bytes(pv.bounds.size() * 4);
+    p->vk = (int*)p->arena.alloc_bytes(pv.coeffs.size() * 4);
+    BP_HIP(hipMemcpy(p->hb, ph.bounds.data(), ph.bounds.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->hk, ph.coeffs.data(), ph.coeffs.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->vb, pv.bounds.data(), pv.bounds.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->vk, pv.coeffs.data(), pv.coeffs.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemset(p->results, 0, (size_t)K * BP_RESULT_FLOATS * sizeof(float)));
+    *out = p.release();
+    return 0;
+    BP_CATCH
+}
+void bp_scene_destroy(bp_scene* s) { delete s; }
+float* bp_scene_results(bp_scene* s) { return s ? s->results : nullptr; }
+double* bp_scene_poses(bp_scene* s) { return s ? s->own_poses : nullptr; }
+int bp_scene_kernel_count(bp_scene* s) {
+    if (!s || !s->graph) return -1;
+    size_t n = 0;
+    if (hipGraphGetNodes(s->graph, nullptr, &n) != hipSuccess) return -1;
+    return (int)n;
+}
+static void scene_drop_graph(bp_scene* p) {
+    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
+}
+
+int bp_scene_set_pose_solver(bp_scene* p, int k, const double* kp3d, int n_kp, const double* K, int left_number, double* d_poses_row) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    BP_CHECK(k >= 0 && k < (int)p->slots.size(), "scene: slot out of range");
+    bp_scene_slot& sl = p->slots[k];
+    scene_drop_graph(p);
+    if (!kp3d) {
+        sl.pose_on = false;
+        return 0;
+    }
+    BP_CHECK(K, "null camera matrix");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    BP_HIP(hipSetDevice(p->y->device));
+    if (!sl.kp3d) sl.kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
+    if (!d_poses_row && !p->own_poses) {
+        const size_t bytes = p->slots.size() * BP_POSE_DOUBLES * sizeof(double);
+        p->own_poses = (double*)p->arena.alloc_bytes(bytes);
+        BP_HIP(hipMemset(p->own_poses, 0, bytes));
+    }
+    sl.poses = d_poses_row ? d_poses_row : p->own_poses + (size_t)k * BP_POSE_DOUBLES;
+    BP_HIP(hipMemcpy(sl.kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
+    sl.cam = make_pnp_cam(K);
+    sl.left_number = left_number;
+    sl.pose_on = true;
+    if (sl.ransac_trials > 0)
+        ransac_tables(left_number < 50 ? left_number : 50, sl.ransac_trials, sl.ransac_conf, sl.ransac_samples, sl.ransac_need);
+    return 0;
+    BP_CATCH
+}
+
+int bp_scene_set_pose_ransac(bp_scene* p, int k, double reproj_err, int max_trials, double confidence) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    BP_CHECK(k >= 0 && k < (int)p->slots.size(), "scene: slot out of range");
+    bp_scene_slot& sl = p->slots[k];
+    scene_drop_graph(p);
+    if (max_trials == 0) {
+        sl.ransac_trials = 0;
+        return 0;
+    }
+    BP_CHECK(sl.pose_on, "bp_scene_set_pose_ransac: set the slot's pose solver first (bp_scene_set_pose_solver)");
+    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    BP_HIP(hipSetDevice(p->y->device));
+    const size_t bytes = pose_ransac_ws_bytes(1, max_trials);
+    if (bytes > sl.ransac_ws_bytes) {
+        sl.ransac_ws = p->arena.alloc_bytes(bytes);
+        sl.ransac_ws_bytes = bytes;
+    }
+    sl.ransac_err = reproj_err;
+    sl.ransac_conf = confidence;
+    ransac_tables(sl.left_number < 50 ? sl.left_number : 50, max_trials, confidence, sl.ransac_samples, sl.ransac_need);
+    sl.ransac_trials = max_trials;
+    return 0;
+    BP_CATCH
+}
+
+// bp_pipeline's rule, for the detector and every key-point engine: a plan that changed since the capture makes the graph stale
+static void scene_capture(bp_scene* p) {
+    bool stale = p->ver_y != p->y->net->plan_version();
+    for (const bp_scene_slot& sl : p->slots) stale = stale || sl.ver_k != sl.k->net->plan_version();
+    if (p->exec && stale) scene_drop_graph(p);
+    if (!p->exec) {
+        p->ver_y = p->y->net->plan_version();
+        for (bp_scene_slot& sl : p->slots) sl.ver_k = sl.k->net->plan_version();
+        if (!p->cap_stream) BP_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
+        BP_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
+        try {
+            scene_enqueue(p, p->cap_stream);
+        } catch (...) {
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(p->cap_stream, &g);
+            if (g) (void)hipGraphDestroy(g);
+            throw;
+        }
+        BP_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
+        BP_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
+    }
+}
+
+int bp_scene_prepare(bp_scene* p) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    scene_capture(p);
+    return 0;
+    BP_CATCH
+}
+
+static void scene_launch(bp_scene* p, int use_graph, hipStream_t s) {
+    if (!use_graph) {
+        scene_enqueue(p, s);
+        return;
+    }
+    scene_capture(p);
+    BP_HIP(hipGraphLaunch(p->exec, s));
+}
+
+int bp_scene_run(bp_scene* p, int use_graph, void* stream) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    scene_launch(p, use_graph, s);
+    // lone-frame latency mode: bp_pipeline_run's rule over every engine of the scene
+    bool latency = p->y->net->prefetch();
+    for (const bp_scene_slot& sl : p->slots) latency = latency || sl.k->net->prefetch();
+    if (latency) {
+        BP_HIP(hipSetDevice(p->y->device));
+        int bad = p->y->net->take_xcd_errors(s);
+        for (bp_scene_slot& sl : p->slots) bad += sl.k->net->take_xcd_errors(s);
+        if (bad) {
+            ++p->latency_faults;
+            p->y->net->set_prefetch(false);
+            for (bp_scene_slot& sl : p->slots) sl.k->net->set_prefetch(false);
+            scene_launch(p, use_graph, s);
+        }
+    }
+    return 0;
+    BP_CATCH
+}
 
 // ------------------------------------------------------------------ xcd mode (mega.inc): prototype entry point, experimental library only
 #ifdef BP_EXPERIMENTAL

@@ -1604,8 +1604,7 @@ YoloNet::YoloNet(const std::string& cfg_text, const float* stream, size_t n_floa
     finalize();
 }
 
-void YoloNet::forward(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
-                      float* d_sel, hipStream_t s, int sel_ld) {
+void YoloNet::run_net(const float* d_img, bool nhwc_input, int batch, hipStream_t s) {
     BP_CHECK(batch >= 1 && batch <= max_batch_, "batch out of range");
     if (nhwc_input) {
         if (d_img != in_nhwc_)
@@ -1615,6 +1614,11 @@ void YoloNet::forward(const float* d_img, bool nhwc_input, int batch, float* d_p
         launch_nchw_to_nhwc(d_img, in_nhwc_, batch, 3, reso_, reso_, s);
     }
     run_ops(batch, s);
+}
+
+void YoloNet::forward(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
+                      float* d_sel, hipStream_t s, int sel_ld) {
+    run_net(d_img, nhwc_input, batch, s);
     // heads hold per-image strides for max_batch_ == layout of batch b (contiguous by image), so decode as is
     static const bool two_kernels = std::getenv("BP_NO_DECODE_FUSION") != nullptr;   // A/B runs, tests
     if (d_sel && !d_pred && !two_kernels) {
@@ -1624,6 +1628,23 @@ void YoloNet::forward(const float* d_img, bool nhwc_input, int batch, float* d_p
         float* pred = d_pred ? d_pred : pred_;
         launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, pred, s);
         if (d_sel) launch_yolo_select(pred, batch, rows_, attrs_, conf, num_classes, d_sel, s, sel_ld);
+    }
+    BP_HIP(hipGetLastError());
+}
+
+void YoloNet::forward_classes(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
+                              const int* class_ids, int K, float* d_sel, hipStream_t s, int ld_image, int ld_slot) {
+    const YoloClassList cl = make_class_list(class_ids, K, num_classes, attrs_);
+    BP_CHECK(d_sel, "null select buffer");
+    if (ld_image <= 0) ld_image = K * ld_slot;
+    run_net(d_img, nhwc_input, batch, s);
+    if (!d_pred) {
+        // the scene graph: nobody reads the prediction tensor, the K records come straight from the head tensors
+        launch_yolo_decode_select_classes(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, conf, num_classes, cl, d_sel, s,
+                                          ld_image, ld_slot);
+    } else {
+        launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, d_pred, s);
+        launch_yolo_select_classes(d_pred, batch, rows_, attrs_, conf, num_classes, cl, d_sel, s, ld_image, ld_slot);
     }
     BP_HIP(hipGetLastError());
 }

@@ -187,9 +187,15 @@ public:
     // img: NCHW f32 [B,3,reso,reso] RGB 0..1 (or NHWC when nhwc_input); pred [B,rows,attrs] (may be null when sel given)
     void forward(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
                  float* d_sel, hipStream_t s, int sel_ld = 8);
+    // the same pass for a multi-class detector shared by K <= BP_MAX_SCENE_CLASSES objects: d_sel + n * ld_image + k * ld_slot
+    // receives the best box whose arg-max class is class_ids[k] (launch_yolo_select_classes; ld_image 0 = K * ld_slot).
+    // With d_pred the prediction tensor is written too; without it the records are decoded straight from the heads.
+    void forward_classes(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
+                         const int* class_ids, int K, float* d_sel, hipStream_t s, int ld_image = 0, int ld_slot = 8);
     float* input_nhwc() { return in_nhwc_; }
     float* pred_buffer() { return pred_; }
 private:
+    void run_net(const float* d_img, bool nhwc_input, int batch, hipStream_t s);   // input layout + every layer up to the heads
     std::string cfg_text_;
     size_t n_floats_ = 0;
     int reso_, rows_ = 0, attrs_ = 0;

@@ -35,6 +35,23 @@ def _cfg_text(blocks) -> str:
     return "\n".join(out)
 
 
+def check_class_ids(class_ids, n_classes: int, num_classes: int = 80):
+    """The class list of one shared detector pass (``forward_select_classes``, ``ScenePipeline``): 1 to
+    ``_lib.MAX_SCENE_CLASSES`` distinct ids, each below the class count the select compares over,
+    ``min(num_classes, n_classes)`` (``n_classes``: the cfg's).  Returns the ids as a list of ints; raises ``ValueError``
+    otherwise -- the library refuses the same lists (csrc/aux_kernels.hip make_class_list)."""
+    ids = [int(c) for c in class_ids]
+    if not 1 <= len(ids) <= _lib.MAX_SCENE_CLASSES:
+        raise ValueError("class list: %d class ids, one detector pass selects for 1 to %d" % (len(ids), _lib.MAX_SCENE_CLASSES))
+    if len(set(ids)) != len(ids):
+        raise ValueError("class list: duplicate class ids in %s" % ids)
+    top = min(int(num_classes), int(n_classes))
+    for c in ids:
+        if not 0 <= c < top:
+            raise ValueError("class list: class id %d is not below the detector's class count %d" % (c, top))
+    return ids
+
+
 class Darknet:
     def __init__(self, cfgfile: str, reso: int = 416, max_batch: int = 1, device: Optional[int] = None):
         self.blocks = parse_cfg(cfgfile)
@@ -47,6 +64,11 @@ class Darknet:
         self.header = None
         self.seen = 0
         self.training = False
+
+    @property
+    def n_classes(self) -> int:
+        """Classes per anchor of the cfg's [yolo] layers (attrs - 5); known without an engine."""
+        return int(next(b for b in self.blocks if b["type"] == "yolo")["classes"])
 
     # ---- nn.Module-like surface used by the reference callers
     def load_weights(self, path: str, cutoff=None):
@@ -142,6 +164,25 @@ class Darknet:
         _lib.check(_lib.lib().bp_yolo_forward_select(self._h, x.data_ptr(), x.shape[0], float(confidence), int(num_classes),
                                                      pred.data_ptr() if want_pred else None, sel.data_ptr(),
                                                      _lib.current_stream()))
+        return (sel, pred) if want_pred else sel
+
+    def forward_select_classes(self, x, class_ids, confidence: float = 0.01, num_classes: int = 80, want_pred: bool = False):
+        """One pass of a multi-class detector, the best box of every class in ``class_ids`` (at most 16, distinct):
+        ``write_results``' rule with the class filter generalised -- a row with objectness > confidence belongs to its
+        arg-max class, per class the highest objectness wins.  Returns ``sel`` f32[B,K,8] in list order:
+        ``forward_select``'s record with [6] = the class's score and [7] = the class id, idx = -1 for a class without a
+        row.  ``want_pred``: also the prediction tensor (the records are then selected from it instead of decoded from
+        the heads; same records)."""
+        import torch
+        ids = check_class_ids(class_ids, self.n_classes, num_classes)
+        x = self._prep(x)
+        K = len(ids)
+        sel = torch.empty((x.shape[0], K, 8), device=x.device, dtype=torch.float32)
+        pred = torch.empty((x.shape[0], self.rows, self.attrs), device=x.device, dtype=torch.float32) if want_pred else None
+        arr = (C.c_int * K)(*ids)
+        _lib.check(_lib.lib().bp_yolo_forward_select_classes(self._h, x.data_ptr(), x.shape[0], float(confidence), int(num_classes),
+                                                             C.cast(arr, C.c_void_p), K, pred.data_ptr() if want_pred else None,
+                                                             sel.data_ptr(), _lib.current_stream()))
         return (sel, pred) if want_pred else sel
 
     # ---- inspection hooks (tests)

@@ -126,9 +126,12 @@ def broadcast_stream(stream: Optional[np.ndarray], src: int = 0, device=None) ->
     return t.cpu().numpy()
 
 
-def gather_records(local_records: np.ndarray, local_indices: Sequence[int], n_total: int, dst: int = 0, device=None):
+def gather_records(local_records: np.ndarray, local_indices: Sequence[int], n_total: int, dst: int = 0, device=None,
+                   max_local: Optional[int] = None):
     """Gather per-frame records [n_local, R] to ``dst`` and put them back in global frame order.
-    Returns [n_total, R] on ``dst`` (None elsewhere)."""
+    Returns [n_total, R] on ``dst`` (None elsewhere).  ``max_local``: the largest record count any rank holds, the same
+    on every rank; default ceil(n_total / world), which fits the round-robin ``i % world`` sharding -- a sharding in
+    larger groups (whole frames of several units) must pass its own."""
     import torch
     dist = _dist()
     local_records = np.ascontiguousarray(local_records, dtype=np.float32)
@@ -139,7 +142,9 @@ def gather_records(local_records: np.ndarray, local_indices: Sequence[int], n_to
     world, rank = dist.get_world_size(), dist.get_rank()
     dev = device if device is not None else ("cuda" if dist.get_backend() == "nccl" else "cpu")
     R = local_records.shape[1]
-    per = (n_total + world - 1) // world           # pad every rank to the same count
+    per = (n_total + world - 1) // world if max_local is None else int(max_local)   # pad every rank to the same count
+    if len(local_indices) > per:
+        raise ValueError("gather_records: %d local records, at most %d per rank expected" % (len(local_indices), per))
     # column R carries (global index + 1) as INT32 BITS inside the fp32 buffer (0 = padding row): exact for every index a
     # 32-bit count can name, where the fp32 VALUE round 2 sent was exact only below 2^24 frames
     buf = torch.zeros((per, R + 1), dtype=torch.float32, device=dev)

@@ -43,6 +43,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help='comma-separated object ids scored with ADD-S as well (LineMod\'s symmetric objects are 10, eggbox, '
                         'and 11, glue): one more line per such object, "Mean add-s accuracy for seq XX is: ...", computed '
                         'on the run\'s GPU (metrics.pose_errors)')
+    p.add_argument('--shared_detector', default='', type=str, metavar='CFG[,WEIGHTS]',
+                   help='occlusion_evaluate.py --obj_ids: ONE multi-class detector (Darknet cfg, .weights file) serves every '
+                        'object -- one resize and one detector pass per frame, the best box of each object\'s class, then each '
+                        'object\'s key-point chain in the same graph (DESIGN.md 3.6).  With --synth_weights the weights are '
+                        'seeded synthetic ones and only CFG is read.  Frames, not units, are sharded over the ranks')
+    p.add_argument('--class_map', default='', type=str, metavar='OBJ:CLASS,...',
+                   help='--shared_detector: detector class of each object id, e.g. 1:0,5:1,6:2; default: the position of the '
+                        'id in LineMod\'s sorted id list 1..15 (class = id - 1, as the reference\'s 15-class labels are written)')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
     p.add_argument('--device_pnp', default=False, action='store_true',
                    help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '
@@ -99,6 +107,46 @@ opt.num_classes = 80            # opt.py:150
 def id_list(text: str):
     """'10, 11' -> [10, 11] (--obj_ids, --symmetric_ids)."""
     return [int(v) for v in text.split(",") if v.strip()]
+
+
+LINEMOD_IDS = list(range(1, 16))     # the 15 LineMod objects; the reference's multi-object labels use obj_id - 1
+
+
+def shared_detector_arg(text: str):
+    """'CFG' or 'CFG,WEIGHTS' (--shared_detector) -> (cfg path, weights path or None)."""
+    parts = [v.strip() for v in text.split(",")]
+    if not 1 <= len(parts) <= 2 or not all(parts):
+        raise ValueError("--shared_detector takes CFG or CFG,WEIGHTS, not %r" % text)
+    return parts[0], (parts[1] if len(parts) == 2 else None)
+
+
+def class_map(text: str, obj_ids):
+    """--class_map 'OBJ:CLASS,...' -> {obj_id: class id} for ``obj_ids``.  Empty text: the position of each id in the
+    sorted LineMod id list.  Every object needs a class, and no two objects may share one."""
+    if text.strip():
+        m = {}
+        for item in text.split(","):
+            if not item.strip():
+                continue
+            try:
+                o, c = item.split(":")
+                o, c = int(o), int(c)
+            except ValueError:
+                raise ValueError("--class_map: %r is not OBJ:CLASS" % item.strip())
+            if o in m:
+                raise ValueError("--class_map: object %d listed twice" % o)
+            m[o] = c
+    else:
+        m = {o: LINEMOD_IDS.index(o) for o in obj_ids if o in LINEMOD_IDS}
+    missing = [o for o in obj_ids if o not in m]
+    if missing:
+        raise ValueError("--class_map: no detector class for objects %s" % missing)
+    out = {o: m[o] for o in obj_ids}
+    if len(set(out.values())) != len(out):
+        raise ValueError("--class_map: two objects share a detector class in %s" % out)
+    if min(out.values()) < 0:
+        raise ValueError("--class_map: negative class id in %s" % out)
+    return out
 
 
 def parse_args(argv=None):

@@ -144,6 +144,110 @@ class FramePipeline:
         return True
 
 
+class ScenePipeline:
+    """A frame with several objects behind ONE multi-class detector pass (``bp_scene_*``): bicubic resize once, the shared
+    detector once with the per-class select, then per object crop -> its key-point net -> arg-max -> (opt-in) its pose
+    tail, all on one stream in one hipGraph.  ``pose_models``: {obj_id: FastPoseHIP}; ``class_of``: {obj_id: class id of
+    the detector}.  ``results`` [K, 316] and ``poses`` [K, 166] hold one row per object in the order of ``obj_ids`` (the
+    order of ``pose_models``); a row is the record ``FramePipeline`` writes for that object, select slots [6], [7] = class
+    score, class id.  A class without a detection leaves index -1 in its row (``finish_record`` -> ``boxes`` None)."""
+
+    def __init__(self, det_model, pose_models: dict, class_of: dict, frame_h: int = 480, frame_w: int = 640,
+                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, frames=None):
+        import torch
+        from .darknet import check_class_ids
+        self.obj_ids = list(pose_models)
+        if not self.obj_ids:
+            raise ValueError("ScenePipeline: no objects")
+        missing = [o for o in self.obj_ids if o not in class_of]
+        if missing:
+            raise ValueError("ScenePipeline: no detector class for objects %s" % missing)
+        self.class_ids = check_class_ids([class_of[o] for o in self.obj_ids], det_model.n_classes, num_classes)
+        _lib.require_gpu()
+        self.det = det_model
+        self.poses_nets = [getattr(pose_models[o], "pyranet", pose_models[o]) for o in self.obj_ids]
+        self.H, self.W, self.K = int(frame_h), int(frame_w), len(self.obj_ids)
+        self.use_graph = bool(use_graph)
+        self.det.cuda()
+        for m in self.poses_nets:
+            m.cuda()
+        dev = "cuda:%d" % self.det._device
+        self.frames = frames if frames is not None else torch.zeros((1, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        assert tuple(self.frames.shape) == (1, self.H, self.W, 3) and self.frames.dtype == torch.uint8
+        self.results = torch.zeros((self.K, RESULT_FLOATS), dtype=torch.float32, device=dev)
+        self.poses = None          # torch f64 [K, POSE_DOUBLES] once set_pose_solver was called
+        kpds = (C.c_void_p * self.K)(*[m.handle for m in self.poses_nets])
+        ids = (C.c_int * self.K)(*self.class_ids)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp_scene_create(self.det.handle, C.cast(kpds, C.c_void_p), C.cast(ids, C.c_void_p), self.K, self.H,
+                                              self.W, float(confidence), int(num_classes), self.frames.data_ptr(),
+                                              self.results.data_ptr(), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                _lib.lib().bp_scene_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def set_pose_solver(self, obj_id, kp3d=None, cam_K=None, left_number: int = 50, ransac=None):
+        """``FramePipeline.set_pose_solver`` for one object of the scene: its runs then also write row
+        ``obj_ids.index(obj_id)`` of ``self.poses``.  ``kp3d`` None switches that object's tail off."""
+        import torch
+        k = self.obj_ids.index(obj_id)
+        L = _lib.lib()
+        if kp3d is None:
+            _lib.check(L.bp_scene_set_pose_ransac(self._h, k, 0.0, 0, 0.0))
+            _lib.check(L.bp_scene_set_pose_solver(self._h, k, None, 0, None, 0, None))
+            return self
+        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
+        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
+        if self.poses is None:
+            self.poses = torch.zeros((self.K, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
+            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
+        _lib.check(L.bp_scene_set_pose_solver(self._h, k, k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number),
+                                              self.poses.data_ptr() + k * POSE_DOUBLES * 8))
+        err, trials, conf = (0.0, 0, 0.0) if ransac is None else ransac
+        _lib.check(L.bp_scene_set_pose_ransac(self._h, k, float(err), int(trials), float(conf)))
+        return self
+
+    def enqueue(self, stream: Optional[int] = None):
+        """Launch the frame on ``stream`` (default: torch's current stream).  ``self.frames`` must already hold it;
+        ``self.results`` (and ``self.poses``) are valid once the stream reaches this point."""
+        _lib.check(_lib.lib().bp_scene_run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
+
+    def prepare(self):
+        """Build the scene's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
+        if self.use_graph:
+            _lib.check(_lib.lib().bp_scene_prepare(self._h))
+        return self
+
+    def kernel_count(self) -> int:
+        return _lib.lib().bp_scene_kernel_count(self._h)
+
+    def run(self, frame_bgr_u8) -> np.ndarray:
+        """Convenience: upload one frame (numpy [H,W,3] u8 or cuda tensor), run, return the rows [K,316] (host)."""
+        import torch
+        f = frame_bgr_u8 if hasattr(frame_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frame_bgr_u8))
+        if f.dim() == 3:
+            f = f.unsqueeze(0)
+        self.frames.copy_(f, non_blocking=True)
+        self.enqueue()
+        return self.results.cpu().numpy()
+
+
+def frame_sharded_owner(n_objects: int, world: int):
+    """Ownership of (frame, object) units when a shared detector serves all objects of a frame: the whole frame --
+    units ``f * n_objects .. f * n_objects + n_objects - 1`` -- belongs to rank ``f % world``.  Returns ``owner(u)``."""
+    K, world = int(n_objects), int(world)
+
+    def owner(u: int) -> int:
+        return (int(u) // K) % world
+    return owner
+
+
 class StreamedRunner:
     """Keeps ``streams`` frames in flight: one engine clone + one hipGraph per HIP stream over shared filters, frame
     uploads straight from the loader's pinned slots, records copied back into a ring of pinned buffers.  At batch 1
@@ -261,17 +365,52 @@ class MultiObjectRunner:
 
     ``engines``: {obj_id: (Darknet, FastPoseHIP)} for the objects this rank owns units of.  ``pose_solvers``:
     {obj_id: (kp3d, cam_K, left_number[, ransac])} turns the device pose tail on (every object in ``engines`` needs one); then
-    ``on_record`` gets ``(u, rec, pose_row)``."""
+    ``on_record`` gets ``(u, rec, pose_row)``.
+
+    ``shared_detector``: ``(Darknet, {obj_id: class id})`` -- one multi-class detector serves every object.  ``engines``
+    is then {obj_id: FastPoseHIP} for ALL of ``obj_ids``, each stream owns one ``ScenePipeline`` (clones over shared
+    filters), and the unit of scheduling is the frame: the K units of a frame run in one graph on one stream, so
+    ``owned`` must give a frame's units to one rank (``frame_sharded_owner``).  ``on_record`` is still called once per
+    unit, with that object's row."""
 
     def __init__(self, engines: dict, obj_ids: List[int], frame_h: int = 480, frame_w: int = 640, streams: int = 4,
-                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, pose_solvers: Optional[dict] = None):
+                 confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, pose_solvers: Optional[dict] = None,
+                 shared_detector=None):
         import torch
         self.obj_ids = list(obj_ids)
         S = max(1, int(streams))
         self.S, self.H, self.W = S, int(frame_h), int(frame_w)
         self.pipes = {}            # (stream, obj_id) -> FramePipeline over the stream's shared frame buffer
+        self.scenes = None         # shared_detector: one ScenePipeline per stream
         dev = None
         self.frame_bufs = []
+        if shared_detector is not None:
+            det, class_of = shared_detector
+            missing = [o for o in self.obj_ids if o not in engines]
+            if missing:
+                raise ValueError("shared detector: no key-point engine for objects %s" % missing)
+            K = len(self.obj_ids)
+            self.scenes = []
+            for k in range(S):
+                poses = {o: getattr(engines[o], "pyranet", engines[o]) for o in self.obj_ids}
+                d = det if k == 0 else det.clone()
+                if k:
+                    poses = {o: m.clone() for o, m in poses.items()}
+                sp = ScenePipeline(d, poses, class_of, frame_h, frame_w, confidence=confidence, num_classes=num_classes,
+                                   use_graph=use_graph)
+                if pose_solvers is not None:
+                    for o in self.obj_ids:
+                        sp.set_pose_solver(o, *pose_solvers[o])
+                self.scenes.append(sp)
+                self.frame_bufs.append(sp.frames)
+            dev = self.frame_bufs[0].device
+            self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
+            self._pinned = [torch.empty((K, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
+            self._events = [torch.cuda.Event() for _ in range(2 * S)]
+            self._pinned_pose = None
+            if pose_solvers is not None:
+                self._pinned_pose = [torch.empty((K, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
+            return
         for k in range(S):
             buf = None
             for oid, (det, pose) in engines.items():
@@ -297,6 +436,8 @@ class MultiObjectRunner:
         in the global frame list); ``owned(u)`` tells whether unit u belongs to this rank;
         ``on_record(u, rec[316])`` receives every owned unit's record.  Returns the number of units run."""
         import torch
+        if self.scenes is not None:
+            return self._run_shared(source, frame_positions, owned, on_record)
         L = _lib.lib()
         S, NS, nbytes, K = self.S, 2 * self.S, self.H * self.W * 3, len(self.obj_ids)
         inflight = []              # (sequence number, unit, loader index or None when this is not the frame's last unit)
@@ -357,6 +498,69 @@ class MultiObjectRunner:
                         pass
                 inflight.clear()
         return j
+
+
+    def _run_shared(self, source, frame_positions, owned, on_record) -> int:
+        """``run`` behind a shared detector: a frame is the unit in flight (``streams`` of them), its K rows come back
+        together and are handed out unit by unit."""
+        import torch
+        L = _lib.lib()
+        S, NS, nbytes, K = self.S, 2 * self.S, self.H * self.W * 3, len(self.obj_ids)
+        inflight = []              # (sequence number, frame position, loader index)
+
+        def finish():
+            j, f, idx = inflight.pop(0)
+            self._events[j % NS].synchronize()
+            recs = self._pinned[j % NS].numpy().copy()
+            poses = self._pinned_pose[j % NS].numpy().copy() if self._pinned_pose is not None else None
+            source.release(idx)
+            for oi in range(K):
+                if poses is None:
+                    on_record(f * K + oi, recs[oi])
+                else:
+                    on_record(f * K + oi, recs[oi], poses[oi])
+
+        j = 0
+        try:
+            for idx, frame, addr in source:
+                if frame.shape != (self.H, self.W, 3):
+                    source.release(idx)
+                    raise ValueError("frame %d is %s, pipeline was built for %s" % (idx, frame.shape, (self.H, self.W, 3)))
+                f = frame_positions[idx]
+                mine = [owned(f * K + oi) for oi in range(K)]
+                if not any(mine):
+                    source.release(idx)
+                    continue
+                if not all(mine):
+                    source.release(idx)
+                    raise ValueError("shared detector: the units of frame %d are split over ranks (shard by frame)" % f)
+                k = j % S
+                st = self.streams[k]
+                with torch.cuda.stream(st):
+                    _lib.check(L.bp_upload(self.frame_bufs[k].data_ptr(), addr, nbytes, st.cuda_stream))
+                    sp = self.scenes[k]
+                    sp.enqueue(st.cuda_stream)
+                    self._pinned[j % NS].copy_(sp.results, non_blocking=True)
+                    if self._pinned_pose is not None:
+                        self._pinned_pose[j % NS].copy_(sp.poses, non_blocking=True)
+                    self._events[j % NS].record(st)
+                inflight.append((j, f, idx))
+                j += 1
+                if len(inflight) > S:
+                    finish()
+            while inflight:
+                finish()
+        finally:
+            if inflight:
+                for st in self.streams:
+                    st.synchronize()
+                for _, _, idx in inflight:
+                    try:
+                        source.release(idx)
+                    except Exception:
+                        pass
+                inflight.clear()
+        return j * K
 
 
 def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray, left_number: int = 50,

@@ -22,6 +22,9 @@
  *   bp_resize_bicubic      transforms.Resize((416,416), 3) + ToTensor      dataloader.py:94-99,162
  *   bp_pipeline_*          DetectionLoader.update -> DetectionProcessor.update -> main loop
  *                          (dataloader.py:330-401,438-457; betapose_evaluate.py:145-176) fused on device
+ *   bp_yolo_forward_select_classes, bp_scene_*
+ *                          the same chain for K objects of one frame behind ONE multi-class detector pass
+ *                          (write_results' class filter generalised; the reference runs one process per object)
  *   bp_solve_pnp           pnp (cv2.solvePnP + cv2.Rodrigues)                 utils/utils.py:17-41
  *   bp_solve_pnp_ransac    the commented-out cv2.solvePnPRansac variant       utils/utils.py:32-36
  *   bp_pose_nms            pose_nms                                           pPose_nms.py:24-122
@@ -64,6 +67,7 @@ extern "C" {
 typedef struct bp_yolo bp_yolo;
 typedef struct bp_kpd bp_kpd;
 typedef struct bp_pipeline bp_pipeline;
+typedef struct bp_scene bp_scene;
 
 /* floats per frame in the pipeline result record:
  *   [0..7]   select: idx (int bits; -1 = no detection), x1,y1,x2,y2 (YOLO-input pixels), obj, cls_conf, cls_idx
@@ -72,6 +76,8 @@ typedef struct bp_pipeline bp_pipeline;
 #define BP_RESULT_FLOATS 316
 #define BP_KP_FLOATS 6
 #define BP_SEL_FLOATS 8
+/* class ids one shared detector pass can select for (bp_yolo_forward_select_classes, bp_scene_create) */
+#define BP_MAX_SCENE_CLASSES 16
 
 /* doubles per frame in the pose record of the device pose tail (bp_pipeline_set_pose_solver, bp_pose_from_records):
  *   [0]        status: 0 ok, 1 no detection, 2 dropped by pPose-NMS, < 0 the solver's status as bp_solve_pnp reports it
@@ -105,6 +111,15 @@ int bp_yolo_forward(bp_yolo* y, const float* d_img_nchw, int batch, float* d_pre
 /* d_pred may be NULL; d_sel: [batch][8] */
 int bp_yolo_forward_select(bp_yolo* y, const float* d_img_nchw, int batch, float conf, int num_classes, float* d_pred,
                            float* d_sel, void* stream);
+/* One pass of a MULTI-class detector, the best box of each of K <= BP_MAX_SCENE_CLASSES classes: a row with objectness > conf
+ * whose arg-max class (first maximum, over min(num_classes, attrs - 5) scores) is class_ids[k] is a candidate of slot k, and
+ * the candidate with the highest objectness wins (lower row on ties) -- write_results' rule (yolo/util.py:118-223, NMS off)
+ * with `class 0` generalised.  class_ids: host, distinct, each below the class count.  d_sel [batch][K][8]: bp_yolo_forward_select's
+ * record with [6] = the winning class's score and [7] = the class id; index -1 and zeros for a class without a row.  With
+ * class_ids = {0} it is bp_yolo_forward_select's record bit for bit.  d_pred may be NULL (the records are then decoded
+ * straight from the head tensors; same records). */
+int bp_yolo_forward_select_classes(bp_yolo* y, const float* d_img_nchw, int batch, float conf, int num_classes,
+                                   const int* class_ids, int K, float* d_pred, float* d_sel, void* stream);
 /* dynamic_write_results on an existing prediction tensor (yolo/util.py:104-223, NMS hard-wired off):
  * d_pred [batch][rows][attrs] -> d_sel [batch][8] */
 int bp_yolo_select(const float* d_pred, int batch, int rows, int attrs, float conf, int num_classes, float* d_sel,
@@ -291,6 +306,28 @@ size_t bp_pose_ransac_workspace_bytes(int batch, int max_trials);
 int bp_pose_from_records_ransac(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
                                 int left_number, double reproj_err, int max_trials, double confidence, double* d_poses,
                                 void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- scene: ONE multi-class detector pass per frame feeding K objects' pose chains (opt-in; bp_pipeline_* is unchanged) ----
+ * Multi-object scenes run one detector per object with bp_pipeline: K resizes and K detector passes per frame.  A scene
+ * resizes the frame once, runs the shared detector `y` once with the per-class select (class_ids[k] = object k's class),
+ * then per object k: crop from row k's box -> kpds[k] -> arg-max -> (opt-in) that object's pose tail.  One stream, one
+ * hipGraph, the launches in that order; one frame per scene (frames in flight = scenes on separate streams over engine
+ * clones).  d_frames [H][W][3] u8 BGR and d_results [K][BP_RESULT_FLOATS] are the caller's (NULL: the scene's own);
+ * row k is the record bp_pipeline writes for that object, select slots [6], [7] = class score, class id.  A class
+ * without a detection leaves its row as bp_pipeline leaves a frame without a box (index -1).  kpds: K distinct engines. */
+int bp_scene_create(bp_yolo* y, bp_kpd* const* kpds, const int* class_ids, int K, int frame_h, int frame_w, float conf,
+                    int num_classes, uint8_t* d_frames, float* d_results, bp_scene** out);
+void bp_scene_destroy(bp_scene* s);
+float* bp_scene_results(bp_scene* s);           /* device [K][BP_RESULT_FLOATS] */
+/* slot k's device pose tail, as bp_pipeline_set_pose_solver / bp_pipeline_set_pose_ransac: d_poses_row = that object's
+ * [BP_POSE_DOUBLES] row (NULL: row k of the scene's own [K][BP_POSE_DOUBLES] buffer, bp_scene_poses).  Drops the graph. */
+int bp_scene_set_pose_solver(bp_scene* s, int k, const double* kp3d, int n_kp, const double* K, int left_number,
+                             double* d_poses_row);
+int bp_scene_set_pose_ransac(bp_scene* s, int k, double reproj_err, int max_trials, double confidence);
+double* bp_scene_poses(bp_scene* s);            /* NULL until a solver was set without a buffer */
+int bp_scene_prepare(bp_scene* s);              /* capture + instantiate now; re-captures after a plan change of any engine */
+int bp_scene_run(bp_scene* s, int use_graph, void* stream);
+int bp_scene_kernel_count(bp_scene* s);         /* graph nodes per run (after the first capture), -1 before */
 
 /* ---- host post-processing (no device work) ---- */
 /* pnp (utils/utils.py:17-41): a restatement of cv2.solvePnP's default SOLVEPNP_ITERATIVE (planar / DLT initialisation,

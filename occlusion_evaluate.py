@@ -5,6 +5,7 @@
     python occlusion_evaluate.py --indir <seq02/rgb> --outdir <out> --obj_id 5            # one object, as the reference
     python occlusion_evaluate.py --indir <seq02/rgb> --outdir <out> --obj_ids 1,5,6,8,9,10,11,12
     python -m torch.distributed.run --nproc-per-node 8 occlusion_evaluate.py --obj_ids ...   # units sharded over GPUs
+    python occlusion_evaluate.py ... --obj_ids 1,5,6 --shared_detector yolo-linemod.cfg,linemod.weights   # one detector pass per frame
 
 The reference evaluates ONE object per process: eight runs over the same 1214 frames of sequence 02, each decoding
 every frame again and loading one detector + one key-point net (occlusion_betapose_evaluate.py:89-90,131-139).  With
@@ -14,6 +15,11 @@ HBM (8 x 1.2 GB of 288 GB), a frame is decoded once and handed to every object's
 prints the reference's three numbers per object -- ADD accuracy, 2-D reprojection accuracy at 20 px with the
 ``--left_keypoints`` best key points, IoU (occlusion_betapose_evaluate.py:204-260) -- and writes one
 ``obj_XX/Betapose-results.json`` per object.  Per object the results equal a single-object run of that object.
+
+``--shared_detector CFG[,WEIGHTS]`` replaces the per-object detectors by ONE multi-class detector: a frame is resized
+and detected once, the best box of each object's class (``--class_map``) feeds that object's key-point chain in the same
+graph (``pipeline.ScenePipeline``).  Whole frames are then sharded ``f % world``; units, records, gather and output are
+the same.
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ import evaluate  # noqa: E402
 def main():
     if "--occlusion" not in sys.argv:
         sys.argv.append("--occlusion")
-    from betapose_amd.opt import id_list, parse_args
+    from betapose_amd.opt import class_map, id_list, parse_args, shared_detector_arg
     args = parse_args()
     if not args.obj_ids:
         return evaluate.main()          # the reference's own protocol: one object per run
@@ -67,9 +73,19 @@ def main():
     print("Betapose begin running now.  Occlusion objects", obj_ids, "| %d frames -> %d (frame, object) units | "
           "key points for PnP: %d" % (len(im_names), n_units, left_number))
 
+    shared = shared_detector_arg(args.shared_detector) if args.shared_detector else None
+    if shared:
+        from betapose_amd.cfg import parse_cfg
+        from betapose_amd.pipeline import frame_sharded_owner
+        class_of = class_map(args.class_map, obj_ids)
+        frame_owner = frame_sharded_owner(K, world)
+        print("shared detector %s | object -> class %s" % (shared[0], class_of))
+
     def owned(u):
-        return bpd.owner_of(u, world) == rank
+        return (frame_owner(u) if shared else bpd.owner_of(u, world)) == rank
     my_objs = [o for oi, o in enumerate(obj_ids) if any(owned(f * K + oi) for f in range(min(len(im_names), world)))]
+    if shared and my_objs:
+        my_objs = list(obj_ids)        # a rank that owns a frame runs all of its objects
     my_frames = [f for f in range(len(im_names)) if any(owned(f * K + oi) for oi in range(K))]
 
     # ---- ground truth / models per object (rank 0 evaluates)
@@ -82,18 +98,39 @@ def main():
     # ---- weights: rank 0 reads every object's two streams, all ranks receive them, each builds the engines it needs
     engines = {}
     t0 = time.time()
+    shared_det = None
+    if shared:
+        ys = None
+        if rank == 0:
+            if args.synth_weights:      # seeded synthetic weights for that cfg (the fixtures' detector seed)
+                ys = synth.synth_yolo_stream(1, [b for b in parse_cfg(shared[0]) if b["type"] != "net"])
+            elif shared[1] is None:
+                raise IOError("--shared_detector %s: give CFG,WEIGHTS (or --synth_weights)" % shared[0])
+            else:
+                ys = read_darknet_weights(shared[1])[2]
+        ys = bpd.broadcast_stream(ys)
+        if my_objs:
+            shared_det = Darknet(shared[0], reso=int(args.inp_dim), max_batch=1, device=local)
+            shared_det.load_stream(ys).cuda()
+            shared_det.set_precision(args.precision)
+        del ys
     for o in obj_ids:
         ys = ks = None
         if rank == 0:
             if args.synth_weights and not args.yolo_weights:
                 sy, sk = synth.object_seeds(o)
-                ys = synth.synth_yolo_stream(sy)
+                ys = None if shared else synth.synth_yolo_stream(sy)
                 ks = fastpose_stream_from_state_dict(synth.synth_fastpose_state_dict(sk, args.nClasses), args.nClasses)
             else:
-                ys = read_darknet_weights('models/yolo/{:02d}.weights'.format(o))[2]
+                ys = None if shared else read_darknet_weights('models/yolo/{:02d}.weights'.format(o))[2]
                 ks = fastpose_stream_from_state_dict(load_kpd_pkl('./exp/final_model/' + ALLPATHS[o] + '.pkl'), args.nClasses)
-        ys, ks = bpd.broadcast_stream(ys), bpd.broadcast_stream(ks)
-        if o in my_objs:
+        ys, ks = (None if shared else bpd.broadcast_stream(ys)), bpd.broadcast_stream(ks)
+        if shared:
+            if o in my_objs:
+                pose = FastPoseHIP.from_stream(ks, n_classes=args.nClasses, max_batch=1, device=local).cuda()
+                pose.set_precision(args.precision)
+                engines[o] = pose
+        elif o in my_objs:
             det = Darknet("yolo/cfg/yolov3-single.cfg", reso=int(args.inp_dim), max_batch=1, device=local)
             det.load_stream(ys).cuda()
             pose = FastPoseHIP.from_stream(ks, n_classes=args.nClasses, max_batch=1, device=local).cuda()
@@ -124,7 +161,8 @@ def main():
         loader = FrameLoader([os.path.join(args.inputpath, im_names[f]) for f in my_frames], threads=threads,
                              depth=max(16, 2 * args.streams + threads))
         runner = MultiObjectRunner(engines, obj_ids, loader.height, loader.width, streams=args.streams,
-                                   confidence=args.confidence, num_classes=args.num_classes, pose_solvers=solvers)
+                                   confidence=args.confidence, num_classes=args.num_classes, pose_solvers=solvers,
+                                   shared_detector=(shared_det, class_of) if shared else None)
         runner.run(loader, my_frames, owned, keep)
         loader.close()
     t_dev = time.time() - t_dev
@@ -132,11 +170,13 @@ def main():
     print("rank %d: %d units over %d decoded frames, %.1f units/sec (%d in flight)" % (
         rank, len(mine), len(my_frames), len(mine) / max(t_dev, 1e-9), args.streams))
     mine_recs = np.stack([recs[u] for u in mine]) if mine else np.zeros((0, 316), np.float32)
-    allrec = bpd.gather_records(mine_recs, mine, n_units)
+    # whole frames per rank (shared detector): rank 0 holds the most, ceil(frames / world) frames of K units
+    most = -(-len(im_names) // world) * K if shared else None
+    allrec = bpd.gather_records(mine_recs, mine, n_units, max_local=most)
     allpose = None
     if args.device_pnp:   # the pose rows ride the same gather, each f64 as a pair of f32 bit patterns
         mine_poses = np.stack([poses[u] for u in mine]) if mine else np.zeros((0, POSE_DOUBLES), np.float64)
-        allpose = bpd.gather_records(mine_poses.view(np.float32), mine, n_units)
+        allpose = bpd.gather_records(mine_poses.view(np.float32), mine, n_units, max_local=most)
 
     if rank == 0:
         for oi, o in enumerate(obj_ids):
