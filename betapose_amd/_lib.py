@@ -46,6 +46,7 @@ PROTOTYPES = {
     "bp_kpd_destroy": (None, [vp]),
     "bp_kpd_forward": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "bp_kpd_forward_argmax": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "bp_kpd_launch_count": (C.c_int, [vp, C.c_int]),
     "bp_kpd_tap_count": (C.c_int, [vp]),
     "bp_kpd_tap_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, c_int_p, c_int_p, c_int_p]),
     "bp_kpd_tap_copy": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
@@ -97,6 +98,21 @@ PROTOTYPES = {
     "bp_scene_prepare": (C.c_int, [vp]),
     "bp_scene_run": (C.c_int, [vp, C.c_int, vp]),
     "bp_scene_kernel_count": (C.c_int, [vp]),
+    "bp_yolo_select_nms": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
+    "bp_yolo_forward_select_nms": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp]),
+    "bp_crop_candidates": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "bp_cands_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, vp, vp, C.POINTER(vp)]),
+    "bp_cands_destroy": (None, [vp]),
+    "bp_cands_results": (vp, [vp]),
+    "bp_cands_counts": (vp, [vp]),
+    "bp_cands_prepare": (C.c_int, [vp]),
+    "bp_cands_run": (C.c_int, [vp, C.c_int, vp]),
+    "bp_cands_kernel_count": (C.c_int, [vp]),
+    "bp_cands_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
+    "bp_cands_pose": (vp, [vp]),
+    "bp_cands_merged": (vp, [vp]),
+    "bp_cands_info": (vp, [vp]),
+    "bp_pose_from_candidate_records": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
@@ -145,6 +161,8 @@ RESULT_FLOATS = 316
 POSE_DOUBLES = 166          # include/betapose_hip.h BP_POSE_DOUBLES
 PNP_MAX_POINTS = 64
 MAX_SCENE_CLASSES = 16      # include/betapose_hip.h BP_MAX_SCENE_CLASSES
+MAX_CANDIDATES = 8          # include/betapose_hip.h BP_MAX_CANDIDATES
+MERGED_FLOATS = 152         # include/betapose_hip.h BP_MERGED_FLOATS
 
 
 class BetaposeHipError(RuntimeError):

@@ -620,6 +620,167 @@ void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N,
                        ld_image, ld_slot);
 }
 
+// ---------------------------------------------------------------- select with box NMS (candidate boxes per frame)
+// write_results with its NMS branch live and the final arg-max removed (yolo/util.py:176-196, bbox_iou yolo/bbox.py:51-77):
+// the rows with objectness > conf whose first-max class is class_id, visited by descending objectness (lower row on ties);
+// each visited survivor is kept and removes every later row whose IoU with it is NOT < nms_conf (a NaN IoU removes); stop
+// after C <= BP_MAX_CANDIDATES survivors.  IoU in f32 on corner boxes in detector-input pixels, with the reference's + 1 on
+// widths and heights.  dynamic_write_results' second pass at nms_conf - 0.05 when more than 100 boxes survive is not
+// reproduced: at most 8 survivors are ever kept, so it is moot.
+// One block of 1 024 threads per image: a thread owns rows tid, tid + 1024, ... (at most NMS_RPT; 11 at 10 647 rows), their
+// liveness as a bit mask and their corners in registers.  C rounds of: block arg-max over the live rows (wave shuffles, 16
+// partials through LDS), the winner's box broadcast through LDS, every thread clears the rows that fail the IoU test.  A
+// round without a live row ends the loop, uniformly.  No atomics, nothing uploaded: the launch captures as it is.  No FMA
+// contraction: +, -, x, max / min and one correctly rounded division, bit-identical to an f32 host restatement.
+constexpr int NMS_RPT = 12;   // rows per thread: rows <= 12 288
+__device__ __forceinline__ float nms_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a >= b ? a : b)); }   // torch.max
+__device__ __forceinline__ float nms_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a <= b ? a : b)); }   // torch.min
+// bbox_iou(box1 = the kept box w, box2 = a later row b)
+__device__ __forceinline__ float nms_iou(const float* w, const float* b) {
+#pragma clang fp contract(off)
+    const float ix1 = nms_max(w[0], b[0]), iy1 = nms_max(w[1], b[1]);
+    const float ix2 = nms_min(w[2], b[2]), iy2 = nms_min(w[3], b[3]);
+    const float inter = nms_max(ix2 - ix1 + 1.f, 0.f) * nms_max(iy2 - iy1 + 1.f, 0.f);
+    const float a1 = (w[2] - w[0] + 1.f) * (w[3] - w[1] + 1.f);
+    const float a2 = (b[2] - b[0] + 1.f) * (b[3] - b[1] + 1.f);
+    return inter / (a1 + a2 - inter);
+}
+template <class Rows>
+__device__ __forceinline__ void select_nms(const Rows& src, int rows, float conf, int ncls, int class_id, float nms_conf, int C,
+                                           float* __restrict__ out, int ld_slot, int* __restrict__ count, float* sv, int* si,
+                                           float* sbox) {
+#pragma clang fp contract(off)
+    float bx[NMS_RPT][4], ob[NMS_RPT];
+    unsigned live = 0;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < NMS_RPT; ++j) {
+        const int r = tid + j * 1024;
+        ob[j] = -1.f;
+        bx[j][0] = bx[j][1] = bx[j][2] = bx[j][3] = 0.f;
+        if (r < rows) {
+            const float* q = src.row(r);
+            const float obj = src.attr(q, 4);
+            if (obj > conf) {
+                int cls = 0;
+                float cm = src.attr(q, 5);
+                for (int k = 1; k < ncls; ++k) {
+                    const float v = src.attr(q, 5 + k);
+                    if (v > cm) { cm = v; cls = k; }
+                }
+                if (cls == class_id) {
+                    float x[4];
+                    src.box(r, q, x);
+                    bx[j][0] = x[0] - x[2] / 2;
+                    bx[j][1] = x[1] - x[3] / 2;
+                    bx[j][2] = x[0] + x[2] / 2;
+                    bx[j][3] = x[1] + x[3] / 2;
+                    ob[j] = obj;
+                    live |= 1u << j;
+                }
+            }
+        }
+    }
+    const int w = tid >> 6;
+    int kept = 0;
+    for (int c = 0; c < C; ++c) {
+        float best = -1.f;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < NMS_RPT; ++j)   // ascending rows: the first maximum stays
+            if (((live >> j) & 1u) && ob[j] > best) { best = ob[j]; bi = tid + j * 1024; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_down(best, off, 64);
+            const int oi = __shfl_down(bi, off, 64);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
+        if ((tid & 63) == 0) { sv[w] = best; si[w] = bi; }
+        __syncthreads();
+        best = sv[0];
+        bi = si[0];
+        for (int k = 1; k < 16; ++k)
+            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+        if (best < 0.f) break;   // no live row left: the same on every thread
+        if ((bi & 1023) == tid) {   // the winner's owner: broadcast its box, write its record, retire it
+            const int jw = bi >> 10;
+            float wb[4] = {0.f, 0.f, 0.f, 0.f}, wo = 0.f;
+#pragma unroll
+            for (int j = 0; j < NMS_RPT; ++j)
+                if (j == jw) { wb[0] = bx[j][0]; wb[1] = bx[j][1]; wb[2] = bx[j][2]; wb[3] = bx[j][3]; wo = ob[j]; }
+            sbox[0] = wb[0]; sbox[1] = wb[1]; sbox[2] = wb[2]; sbox[3] = wb[3];
+            float* o = out + (long long)c * ld_slot;
+            o[0] = __int_as_float(bi);
+            o[1] = wb[0]; o[2] = wb[1]; o[3] = wb[2]; o[4] = wb[3];
+            o[5] = wo;
+            o[6] = src.attr(src.row(bi), 5 + class_id);
+            o[7] = (float)class_id;
+            live &= ~(1u << jw);
+        }
+        __syncthreads();   // (also: every thread has read sv / si before the next round rewrites them)
+        const float wb[4] = {sbox[0], sbox[1], sbox[2], sbox[3]};
+#pragma unroll
+        for (int j = 0; j < NMS_RPT; ++j)
+            if ((live >> j) & 1u) {
+                const float iou = nms_iou(wb, bx[j]);
+                if (!(iou < nms_conf)) live &= ~(1u << j);
+            }
+        ++kept;
+        __syncthreads();   // sbox is read before the next winner overwrites it
+    }
+    if (tid < C && tid >= kept) {   // unused slots: the "no detection" record
+        float* o = out + (long long)tid * ld_slot;
+        o[0] = __int_as_float(-1);
+        for (int k = 1; k < 8; ++k) o[k] = 0.f;
+    }
+    if (tid == 0) *count = kept;
+}
+__global__ __launch_bounds__(1024) void yolo_select_nms_kernel(const float* __restrict__ pred, int rows, int attrs, float conf,
+                                                                int num_classes, int class_id, float nms_conf, int C,
+                                                                float* __restrict__ sel, int* __restrict__ count, int ld_image,
+                                                                int ld_slot) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float sbox[4];
+    const PredRows src{pred + (long long)blockIdx.x * rows * attrs, attrs};
+    select_nms(src, rows, conf, min(num_classes, attrs - 5), class_id, nms_conf, C, sel + (long long)blockIdx.x * ld_image, ld_slot,
+               count + blockIdx.x, sv, si, sbox);
+}
+__global__ __launch_bounds__(1024) void yolo_decode_select_nms_kernel(YoloHeads hs, int reso, int attrs, int rows, float conf,
+                                                                       int num_classes, int class_id, float nms_conf, int C,
+                                                                       float* __restrict__ sel, int* __restrict__ count,
+                                                                       int ld_image, int ld_slot) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float sbox[4];
+    const HeadRows src{&hs, (int)blockIdx.x, attrs, reso};
+    select_nms(src, rows, conf, min(num_classes, attrs - 5), class_id, nms_conf, C, sel + (long long)blockIdx.x * ld_image, ld_slot,
+               count + blockIdx.x, sv, si, sbox);
+}
+static void check_select_nms(int rows, int attrs, int num_classes, int class_id, int C) {
+    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "select with NMS: 1 to 8 candidates (BP_MAX_CANDIDATES)");
+    BP_CHECK(rows >= 1 && rows <= NMS_RPT * 1024, "select with NMS: at most 12 288 rows per image");
+    const int ncls = num_classes < attrs - 5 ? num_classes : attrs - 5;
+    BP_CHECK(class_id >= 0 && class_id < ncls, "select with NMS: class id is not below the detector's class count");
+}
+void launch_yolo_select_nms(const float* pred, int N, int rows, int attrs, float conf, int num_classes, int class_id, float nms_conf,
+                            int C, float* sel, int* count, hipStream_t s, int ld_image, int ld_slot) {
+    check_select_nms(rows, attrs, num_classes, class_id, C);
+    hipLaunchKernelGGL(yolo_select_nms_kernel, dim3(N), dim3(1024), 0, s, pred, rows, attrs, conf, num_classes, class_id, nms_conf, C,
+                       sel, count, ld_image, ld_slot);
+}
+void launch_yolo_decode_select_nms(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
+                                   int class_id, float nms_conf, int C, float* sel, int* count, hipStream_t s, int ld_image,
+                                   int ld_slot) {
+    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
+    check_select_nms(rows, attrs, num_classes, class_id, C);
+    YoloHeads hs;
+    hs.n = nheads;
+    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
+    hipLaunchKernelGGL(yolo_decode_select_nms_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, class_id,
+                       nms_conf, C, sel, count, ld_image, ld_slot);
+}
+
 // ---------------------------------------------------------------- heat-map arg-max (+4 neighbours), eval.py:113-147
 __global__ __launch_bounds__(256) void heatmap_argmax_kernel(const float* __restrict__ hm, int H, int W,
                                                               float* __restrict__ out, int C, int out_ld) {
@@ -709,9 +870,9 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* __restrict__ f
                                                     const float* __restrict__ sel, int reso,
                                                     const float* __restrict__ box_override, float* __restrict__ out_nhwc,
                                                     float* __restrict__ out_nchw, float* __restrict__ pts, int oh, int ow,
-                                                    int sel_ld, int pts_ld) {
-    const int img = blockIdx.y;
-    frame += (long long)img * H * W * 3;
+                                                    int sel_ld, int pts_ld, int per_frame) {
+    const int img = blockIdx.y;   // crop img reads frame img / per_frame (candidate boxes of one frame) with box img
+    frame += (long long)(img / per_frame) * H * W * 3;
     if (sel) sel += (long long)img * sel_ld;
     if (box_override) box_override += img * 4;
     if (out_nhwc) out_nhwc += (long long)img * oh * ow * 3;
@@ -751,9 +912,10 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* __restrict__ f
     }
 }
 void launch_crop(const uint8_t* frames, int batch, int H, int W, const float* sel, int reso, const float* boxes,
-                 float* out_nhwc, float* out_nchw, float* pts, int oh, int ow, hipStream_t s, int sel_ld, int pts_ld) {
+                 float* out_nhwc, float* out_nchw, float* pts, int oh, int ow, hipStream_t s, int sel_ld, int pts_ld, int per_frame) {
+    BP_CHECK(per_frame >= 1, "crop: crops per frame must be >= 1");
     hipLaunchKernelGGL(crop_kernel, dim3(grid_for((long long)oh * ow, 256, 1024), batch), dim3(256), 0, s, frames, H, W,
-                       sel, reso, boxes, out_nhwc, out_nchw, pts, oh, ow, sel_ld, pts_ld);
+                       sel, reso, boxes, out_nhwc, out_nchw, pts, oh, ow, sel_ld, pts_ld, per_frame);
 }
 
 // ---------------------------------------------------------------- Pillow-exact bicubic resize (u8, two passes)

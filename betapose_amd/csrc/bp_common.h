@@ -321,6 +321,15 @@ void launch_yolo_select_classes(const float* pred, int N, int rows, int attrs, f
                                 float* sel, hipStream_t s, int ld_image, int ld_slot);
 void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf,
                                        int num_classes, const YoloClassList& cl, float* sel, hipStream_t s, int ld_image, int ld_slot);
+// Select with box NMS (write_results' NMS branch live, its final arg-max removed): up to C <= BP_MAX_CANDIDATES survivors of
+// class class_id per image, in survivor order, at sel + n * ld_image + c * ld_slot (launch_yolo_select's record, [6] = the class's
+// score, [7] = the class id; unused slots index -1 and zeros); count[n] = survivors.  Parameters by value: the launch captures.
+#define BP_MAX_CANDIDATES 8
+void launch_yolo_select_nms(const float* pred, int N, int rows, int attrs, float conf, int num_classes, int class_id, float nms_conf,
+                            int C, float* sel, int* count, hipStream_t s, int ld_image, int ld_slot);
+void launch_yolo_decode_select_nms(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
+                                   int class_id, float nms_conf, int C, float* sel, int* count, hipStream_t s, int ld_image,
+                                   int ld_slot);
 // hm NCHW [N][C][H*W] -> out [N][C][6] = (idx as int bits, max, left, right, up, down)
 // out_ld: floats between consecutive images' [C][6] blocks (0 = dense C*6)
 void launch_heatmap_argmax(const float* hm, int N, int C, int H, int W, float* out, hipStream_t s, int out_ld = 0);
@@ -336,7 +345,8 @@ void launch_spin_ticks(long long ticks, hipStream_t s);   // one thread spinning
 //  frames: BGR u8 [batch][H][W][3]; sel: [batch][8] select records (box in YOLO-input pixels) or boxes [batch][4];
 //  out_nhwc [oh][ow][3] (engine input) and/or out_nchw [3][oh][ow]; pts: (ul.x, ul.y, br.x, br.y)
 void launch_crop(const uint8_t* frames, int batch, int H, int W, const float* sel, int reso, const float* boxes,
-                 float* out_nhwc, float* out_nchw, float* pts, int oh, int ow, hipStream_t s, int sel_ld = 8, int pts_ld = 8);
+                 float* out_nhwc, float* out_nchw, float* pts, int oh, int ow, hipStream_t s, int sel_ld = 8, int pts_ld = 8,
+                 int per_frame = 1);   // per_frame: crops per frame -- crop n reads frame n / per_frame with box n
 
 // Pillow-exact antialiased bicubic resize of a u8 HWC frame (two passes, 22-bit fixed point);
 // coefficient tables are built on the host (engine.cpp).

@@ -33,6 +33,9 @@ void launch_pose_tail(const float* records, int batch, const double* kp3d, const
                       double* poses, hipStream_t s);
 void launch_pose_tail_prepare(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
                               double* poses, double* ws3d, double* ws2d, int* active, hipStream_t s);
+// pose_tail_cands.hip
+void launch_pose_tail_cands(const float* records, const int* counts, int frames, int C, const double* kp3d, const PnpCam& cam,
+                            int left_number, double* poses, float* merged, int* info, hipStream_t s);
 // pnp_ransac.hip
 size_t pnp_ransac_workspace_bytes(int P, int max_trials);
 void launch_pnp_ransac(const double* pts3d, size_t stride3d, const double* pts2d, size_t stride2d, const int* active, int n,
@@ -177,6 +180,41 @@ struct bp_scene {
     unsigned ver_y = 0;
     int latency_faults = 0;
     ~bp_scene() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+    }
+};
+
+// Candidate boxes per frame (bp_cands_*): one frame, up to C NMS survivors of the detector through ONE key-point pass at
+// batch C; rows [C][316], their number in counts[0]; (opt-in) the candidate pose tail over them.
+struct bp_cands {
+    bp_yolo* y;
+    bp_kpd* k;
+    int C, H, W;
+    float conf, nms_conf;
+    int num_classes, class_id;
+    bp::Arena arena;
+    uint8_t* frames = nullptr;
+    uint8_t* tmp = nullptr;
+    float* results = nullptr;    // [C][316]
+    int* counts = nullptr;       // [1]
+    int *hb = nullptr, *hk = nullptr, *vb = nullptr, *vk = nullptr;
+    int ksh = 0, ksv = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipStream_t cap_stream = nullptr;
+    unsigned ver_y = 0, ver_k = 0;
+    int latency_faults = 0;
+    bool pose_on = false;
+    double* kp3d = nullptr;
+    double* pose = nullptr;      // [166]
+    double* own_pose = nullptr;
+    float* merged = nullptr;     // [C][152]
+    int* info = nullptr;         // [4]
+    bp::PnpCam cam{};
+    int left_number = 50;
+    ~bp_cands() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
@@ -372,6 +410,27 @@ int bp_yolo_select(const float* d_pred, int batch, int rows, int attrs, float co
     BP_CATCH
 }
 
+int bp_yolo_select_nms(const float* d_pred, int batch, int rows, int attrs, float conf, int num_classes, int class_id,
+                       float nms_conf, int max_candidates, float* d_sel, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(d_pred && d_sel && d_counts && batch >= 1 && rows >= 1 && attrs >= 6, "bad argument");
+    bp::launch_yolo_select_nms(d_pred, batch, rows, attrs, conf, num_classes, class_id, nms_conf, max_candidates, d_sel, d_counts,
+                               (hipStream_t)stream, max_candidates * BP_SEL_FLOATS, BP_SEL_FLOATS);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_forward_select_nms(bp_yolo* y, const float* d_img, int batch, float conf, int num_classes, int class_id,
+                               float nms_conf, int max_candidates, float* d_pred, float* d_sel, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(y && d_img && d_sel && d_counts, "null argument");
+    y->net->forward_nms(d_img, false, batch, d_pred, conf, num_classes, class_id, nms_conf, max_candidates, d_sel, d_counts,
+                        (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
 static int tap_info(const bp::Net& n, int i, char* name, int cap, int* C, int* H, int* W) {
     if (i < 0 || i >= n.tap_count()) { g_err = "tap index"; return -1; }
     if (name && cap > 0) std::snprintf(name, cap, "%s", n.tap_name(i));
@@ -430,6 +489,36 @@ int bp_kpd_forward_argmax(bp_kpd* k, const float* d_inps, int batch, float* d_hm
     BP_CHECK(k && d_inps && d_kp, "null argument");
     k->net->forward(d_inps, false, batch, d_hm, d_kp, (hipStream_t)stream);
     return 0;
+    BP_CATCH
+}
+int bp_kpd_launch_count(bp_kpd* k, int batch) {
+    BP_TRY
+    BP_CHECK(k, "null argument");
+    BP_CHECK(batch >= 1 && batch <= k->net->max_batch(), "batch out of range");
+    BP_HIP(hipSetDevice(k->device));
+    // record one forward + arg-max pass at this batch into a throw-away graph (nothing executes) and count its nodes
+    hipStream_t cs = nullptr;
+    BP_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    hipGraph_t g = nullptr;
+    size_t n = 0;
+    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        float* kp = k->net->input_nhwc();   // never written: the launches are only recorded
+        try {
+            k->net->forward(k->net->input_nhwc(), true, batch, nullptr, kp, cs);
+        } catch (...) {
+            (void)hipStreamEndCapture(cs, &g);
+            if (g) (void)hipGraphDestroy(g);
+            (void)hipStreamDestroy(cs);
+            throw;
+        }
+        e = hipStreamEndCapture(cs, &g);
+    }
+    if (e == hipSuccess) e = hipGraphGetNodes(g, nullptr, &n);
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipStreamDestroy(cs);
+    BP_HIP(e);
+    return (int)n;
     BP_CATCH
 }
 int bp_kpd_tap_count(const bp_kpd* k) { return k ? k->net->tap_count() : -1; }
@@ -579,6 +668,17 @@ int bp_crop(const uint8_t* d_frames, int batch, int H, int W, const float* d_sel
     BP_TRY
     BP_CHECK(d_frames && (d_sel || d_boxes) && (d_out_nchw || d_out_nhwc), "null argument");
     bp::launch_crop(d_frames, batch, H, W, d_sel, reso, d_boxes, d_out_nhwc, d_out_nchw, d_pts, oh, ow, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_crop_candidates(const uint8_t* d_frames, int frames, int C, int H, int W, const float* d_sel, int reso, const float* d_boxes,
+                       float* d_out_nchw, float* d_out_nhwc, float* d_pts, int oh, int ow, void* stream) {
+    BP_TRY
+    BP_CHECK(d_frames && (d_sel || d_boxes) && (d_out_nchw || d_out_nhwc), "null argument");
+    BP_CHECK(frames >= 1 && C >= 1, "bp_crop_candidates: frames and crops per frame must be >= 1");
+    bp::launch_crop(d_frames, frames * C, H, W, d_sel, reso, d_boxes, d_out_nhwc, d_out_nchw, d_pts, oh, ow, (hipStream_t)stream, 8, 8, C);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
@@ -951,6 +1051,22 @@ int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d
     BP_CATCH
 }
 
+int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, int frames, int C, const double* d_kp3d, int n_kp,
+                                   const double* K, int left_number, double* d_poses, float* d_merged, int* d_info, void* stream) {
+    BP_TRY
+    BP_CHECK(d_records && d_counts && d_kp3d && K && d_poses && d_merged && d_info, "null argument");
+    BP_CHECK(frames >= 0, "frames must be >= 0");
+    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    if (frames == 0) return 0;
+    bp::launch_pose_tail_cands(d_records, d_counts, frames, C, d_kp3d, make_pnp_cam(K), left_number, d_poses, d_merged, d_info,
+                               (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
 int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
                        double* d_Rt, int* d_status, void* stream) {
     BP_TRY
@@ -1316,6 +1432,169 @@ int bp_scene_run(bp_scene* p, int use_graph, void* stream) {
             p->y->net->set_prefetch(false);
             for (bp_scene_slot& sl : p->slots) sl.k->net->set_prefetch(false);
             scene_launch(p, use_graph, s);
+        }
+    }
+    return 0;
+    BP_CATCH
+}
+
+// ------------------------------------------------------------------ candidates: NMS survivors of one frame, one key-point pass at batch C
+// One stream, one hipGraph: resize -> detector -> select with box NMS (C records + count) -> one crop launch over the C
+// boxes -> key-point net at batch C -> arg-max -> (opt-in) the candidate pose tail.  The graph always runs at batch C:
+// a slot without a box crops as a frame without a detection does, and the tail reads the count.
+static void cands_enqueue(bp_cands* p, hipStream_t s) {
+    bp::YoloNet& yn = *p->y->net;
+    bp::KpdNet& kn = *p->k->net;
+    const int reso = yn.reso(), R = BP_RESULT_FLOATS, C = p->C;
+    bp::ResizeTables t{p->hb, p->hk, p->ksh, p->vb, p->vk, p->ksv};
+    bp::launch_resize_bicubic(p->frames, 1, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    yn.forward_nms(yn.input_nhwc(), true, 1, nullptr, p->conf, p->num_classes, p->class_id, p->nms_conf, C, p->results, p->counts, s,
+                   C * R, R);
+    bp::launch_crop(p->frames, C, p->H, p->W, p->results, reso, nullptr, kn.input_nhwc(), nullptr, p->results + 8, kn.in_h(), kn.in_w(),
+                    s, R, R, C);
+    kn.forward(kn.input_nhwc(), true, C, nullptr, p->results + 16, s, R);
+    if (p->pose_on)
+        bp::launch_pose_tail_cands(p->results, p->counts, 1, C, p->kp3d, p->cam, p->left_number, p->pose, p->merged, p->info, s);
+    BP_HIP(hipGetLastError());
+}
+
+int bp_cands_create(bp_yolo* y, bp_kpd* k, int max_candidates, int frame_h, int frame_w, float conf, int num_classes, int class_id,
+                    float nms_conf, uint8_t* d_frame, float* d_results, bp_cands** out) {
+    BP_TRY
+    BP_CHECK(y && k && out, "null argument");
+    const int C = max_candidates;
+    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "bp_cands_create: 1 to 8 candidates (BP_MAX_CANDIDATES)");
+    BP_CHECK(C <= k->net->max_batch(), "bp_cands_create: the key-point engine's max_batch is below the candidate count");
+    BP_CHECK(k->net->out_c() == 50, "candidate pipeline expects 50 key points");
+    BP_CHECK(k->device == y->device, "candidate pipeline: both engines on one device");
+    BP_CHECK(frame_h >= 1 && frame_w >= 1, "frame size");
+    const int ncls = num_classes < y->net->attrs() - 5 ? num_classes : y->net->attrs() - 5;
+    BP_CHECK(class_id >= 0 && class_id < ncls, "bp_cands_create: class id is not below the detector's class count");
+    BP_HIP(hipSetDevice(y->device));
+    std::unique_ptr<bp_cands> p(new bp_cands);
+    p->y = y; p->k = k; p->C = C; p->H = frame_h; p->W = frame_w; p->conf = conf; p->nms_conf = nms_conf;
+    p->num_classes = num_classes; p->class_id = class_id;
+    const int reso = y->net->reso();
+    p->frames = d_frame ? d_frame : (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * frame_w * 3);
+    p->tmp = (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * reso * 3);
+    p->results = d_results ? d_results : p->arena.alloc((size_t)C * BP_RESULT_FLOATS);
+    p->counts = (int*)p->arena.alloc_bytes(sizeof(int));
+    const bp::ResizePlan ph = bp::make_bicubic_plan(frame_w, reso), pv = bp::make_bicubic_plan(frame_h, reso);
+    p->ksh = ph.ksize; p->ksv = pv.ksize;
+    p->hb = (int*)p->arena.alloc_bytes(ph.bounds.size() * 4);
+    p->hk = (int*)p->arena.alloc_bytes(ph.coeffs.size() * 4);
+    p->vb = (int*)p->arena.alloc_bytes(pv.bounds.size() * 4);
+    p->vk = (int*)p->arena.alloc_bytes(pv.coeffs.size() * 4);
+    BP_HIP(hipMemcpy(p->hb, ph.bounds.data(), ph.bounds.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->hk, ph.coeffs.data(), ph.coeffs.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->vb, pv.bounds.data(), pv.bounds.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemcpy(p->vk, pv.coeffs.data(), pv.coeffs.size() * 4, hipMemcpyHostToDevice));
+    BP_HIP(hipMemset(p->results, 0, (size_t)C * BP_RESULT_FLOATS * sizeof(float)));
+    BP_HIP(hipMemset(p->counts, 0, sizeof(int)));
+    *out = p.release();
+    return 0;
+    BP_CATCH
+}
+void bp_cands_destroy(bp_cands* s) { delete s; }
+float* bp_cands_results(bp_cands* s) { return s ? s->results : nullptr; }
+int* bp_cands_counts(bp_cands* s) { return s ? s->counts : nullptr; }
+double* bp_cands_pose(bp_cands* s) { return s ? s->pose : nullptr; }
+float* bp_cands_merged(bp_cands* s) { return s ? s->merged : nullptr; }
+int* bp_cands_info(bp_cands* s) { return s ? s->info : nullptr; }
+int bp_cands_kernel_count(bp_cands* s) {
+    if (!s || !s->graph) return -1;
+    size_t n = 0;
+    if (hipGraphGetNodes(s->graph, nullptr, &n) != hipSuccess) return -1;
+    return (int)n;
+}
+static void cands_drop_graph(bp_cands* p) {
+    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
+}
+
+int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const double* K, int left_number, double* d_pose) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    cands_drop_graph(p);
+    if (!kp3d) {
+        p->pose_on = false;
+        return 0;
+    }
+    BP_CHECK(K, "null camera matrix");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    BP_HIP(hipSetDevice(p->y->device));
+    if (!p->kp3d) {
+        p->kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
+        p->merged = p->arena.alloc((size_t)p->C * 152);
+        p->info = (int*)p->arena.alloc_bytes(4 * sizeof(int));
+        BP_HIP(hipMemset(p->merged, 0, (size_t)p->C * 152 * sizeof(float)));
+        BP_HIP(hipMemset(p->info, 0, 4 * sizeof(int)));
+    }
+    if (!d_pose && !p->own_pose) {
+        p->own_pose = (double*)p->arena.alloc_bytes(BP_POSE_DOUBLES * sizeof(double));
+        BP_HIP(hipMemset(p->own_pose, 0, BP_POSE_DOUBLES * sizeof(double)));
+    }
+    p->pose = d_pose ? d_pose : p->own_pose;
+    BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
+    p->cam = make_pnp_cam(K);
+    p->left_number = left_number;
+    p->pose_on = true;
+    return 0;
+    BP_CATCH
+}
+
+static void cands_capture(bp_cands* p) {
+    if (p->exec && (p->ver_y != p->y->net->plan_version() || p->ver_k != p->k->net->plan_version())) cands_drop_graph(p);
+    if (!p->exec) {
+        p->ver_y = p->y->net->plan_version();
+        p->ver_k = p->k->net->plan_version();
+        if (!p->cap_stream) BP_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
+        BP_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
+        try {
+            cands_enqueue(p, p->cap_stream);
+        } catch (...) {
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(p->cap_stream, &g);
+            if (g) (void)hipGraphDestroy(g);
+            throw;
+        }
+        BP_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
+        BP_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
+    }
+}
+
+int bp_cands_prepare(bp_cands* p) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    cands_capture(p);
+    return 0;
+    BP_CATCH
+}
+
+static void cands_launch(bp_cands* p, int use_graph, hipStream_t s) {
+    if (!use_graph) {
+        cands_enqueue(p, s);
+        return;
+    }
+    cands_capture(p);
+    BP_HIP(hipGraphLaunch(p->exec, s));
+}
+
+int bp_cands_run(bp_cands* p, int use_graph, void* stream) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    cands_launch(p, use_graph, s);
+    // lone-frame latency mode: bp_pipeline_run's rule
+    if (p->y->net->prefetch() || p->k->net->prefetch()) {
+        BP_HIP(hipSetDevice(p->y->device));
+        const int bad = p->y->net->take_xcd_errors(s) + p->k->net->take_xcd_errors(s);
+        if (bad) {
+            ++p->latency_faults;
+            p->y->net->set_prefetch(false);
+            p->k->net->set_prefetch(false);
+            cands_launch(p, use_graph, s);
         }
     }
     return 0;

@@ -1649,6 +1649,22 @@ void YoloNet::forward_classes(const float* d_img, bool nhwc_input, int batch, fl
     BP_HIP(hipGetLastError());
 }
 
+void YoloNet::forward_nms(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes, int class_id,
+                          float nms_conf, int C, float* d_sel, int* d_count, hipStream_t s, int ld_image, int ld_slot) {
+    BP_CHECK(d_sel && d_count, "null select buffer");
+    if (ld_image <= 0) ld_image = C * ld_slot;
+    run_net(d_img, nhwc_input, batch, s);
+    if (!d_pred) {
+        // the candidate graph: nobody reads the prediction tensor, the records come straight from the head tensors
+        launch_yolo_decode_select_nms(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, conf, num_classes, class_id, nms_conf,
+                                      C, d_sel, d_count, s, ld_image, ld_slot);
+    } else {
+        launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, d_pred, s);
+        launch_yolo_select_nms(d_pred, batch, rows_, attrs_, conf, num_classes, class_id, nms_conf, C, d_sel, d_count, s, ld_image, ld_slot);
+    }
+    BP_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------ KpdNet (FastPose)
 KpdNet::KpdNet(const float* stream, size_t n_floats, int n_classes, int max_batch, int inH, int inW,
                std::shared_ptr<WeightStore> store)

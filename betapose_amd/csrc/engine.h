@@ -192,6 +192,10 @@ public:
     // With d_pred the prediction tensor is written too; without it the records are decoded straight from the heads.
     void forward_classes(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
                          const int* class_ids, int K, float* d_sel, hipStream_t s, int ld_image = 0, int ld_slot = 8);
+    // the same pass with box NMS in the select: up to C <= BP_MAX_CANDIDATES survivors of class class_id per image at
+    // d_sel + n * ld_image + c * ld_slot, their number in d_count[n] (launch_yolo_select_nms; ld_image 0 = C * ld_slot)
+    void forward_nms(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes, int class_id,
+                     float nms_conf, int C, float* d_sel, int* d_count, hipStream_t s, int ld_image = 0, int ld_slot = 8);
     float* input_nhwc() { return in_nhwc_; }
     float* pred_buffer() { return pred_; }
 private:

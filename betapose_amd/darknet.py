@@ -185,6 +185,26 @@ class Darknet:
                                                              sel.data_ptr(), _lib.current_stream()))
         return (sel, pred) if want_pred else sel
 
+    def forward_select_nms(self, x, max_candidates: int, nms_conf: float, class_id: int = 0, confidence: float = 0.01,
+                           num_classes: int = 80, want_pred: bool = False):
+        """Fused forward + ``write_results`` with its NMS branch live and the final arg-max removed (yolo/util.py:176-196):
+        up to ``max_candidates`` (at most 8) NMS survivors of class ``class_id`` per image, by descending objectness.
+        Returns ``(sel f32[B,C,8], counts int32[B])``: ``forward_select``'s record per survivor ([6] = the class's score,
+        [7] = the class id), unused slots idx = -1; candidate 0 is ``forward_select``'s record.  ``want_pred``: also
+        the prediction tensor (the records are then selected from it; same records)."""
+        import torch
+        Cn = int(max_candidates)
+        if not 1 <= Cn <= _lib.MAX_CANDIDATES:
+            raise ValueError("max_candidates must be 1 to %d, not %d" % (_lib.MAX_CANDIDATES, Cn))
+        x = self._prep(x)
+        sel = torch.empty((x.shape[0], Cn, 8), device=x.device, dtype=torch.float32)
+        counts = torch.empty((x.shape[0],), device=x.device, dtype=torch.int32)
+        pred = torch.empty((x.shape[0], self.rows, self.attrs), device=x.device, dtype=torch.float32) if want_pred else None
+        _lib.check(_lib.lib().bp_yolo_forward_select_nms(self._h, x.data_ptr(), x.shape[0], float(confidence), int(num_classes),
+                                                         int(class_id), float(nms_conf), Cn, pred.data_ptr() if want_pred else None,
+                                                         sel.data_ptr(), counts.data_ptr(), _lib.current_stream()))
+        return (sel, counts, pred) if want_pred else (sel, counts)
+
     # ---- inspection hooks (tests)
     def taps(self):
         self._ensure()

@@ -80,6 +80,65 @@ def crop(frames_bgr_u8, sel=None, boxes=None, reso: int = 416, oh: int = 320, ow
     return out, pts
 
 
+def crop_candidates(frames_bgr_u8, candidates: int, sel=None, boxes=None, reso: int = 416, oh: int = 320, ow: int = 256,
+                    nchw: bool = True):
+    """``crop`` over ``candidates`` boxes per frame (bp_crop_candidates): ``frames`` cuda u8 [F,H,W,3]; ``sel`` [F*C,8] or
+    ``boxes`` [F*C,4]; crop n reads frame n // C with box n.  Returns (inps [F*C,...], pts [F*C,8])."""
+    import torch
+    _lib.require_gpu()
+    f = frames_bgr_u8.contiguous()
+    F, H, W, _ = f.shape
+    Cn = int(candidates)
+    B = F * Cn
+    src = sel if sel is not None else boxes
+    src = src.contiguous().reshape(B, -1)
+    assert src.shape[1] == (8 if sel is not None else 4)
+    out = torch.empty((B, 3, oh, ow) if nchw else (B, oh, ow, 3), device=f.device, dtype=torch.float32)
+    pts = torch.empty((B, 8), device=f.device, dtype=torch.float32)
+    _lib.check(_lib.lib().bp_crop_candidates(f.data_ptr(), F, Cn, H, W, src.data_ptr() if sel is not None else None, reso,
+                                             src.data_ptr() if sel is None else None,
+                                             out.data_ptr() if nchw else None, None if nchw else out.data_ptr(), pts.data_ptr(),
+                                             oh, ow, _lib.current_stream()))
+    return out, pts
+
+
+def select_nms(pred, max_candidates: int, nms_conf: float, class_id: int = 0, confidence: float = 0.01, num_classes: int = 80):
+    """Select with box NMS on an existing prediction tensor (bp_yolo_select_nms): cuda f32 [B,rows,attrs] ->
+    (sel f32 [B,C,8], counts int32 [B]); see ``Darknet.forward_select_nms``."""
+    import torch
+    _lib.require_gpu()
+    p = pred.contiguous()
+    assert p.dtype == torch.float32 and p.dim() == 3
+    B, rows, attrs = p.shape
+    Cn = int(max_candidates)
+    sel = torch.empty((B, Cn, 8), device=p.device, dtype=torch.float32)
+    counts = torch.empty((B,), device=p.device, dtype=torch.int32)
+    _lib.check(_lib.lib().bp_yolo_select_nms(p.data_ptr(), B, rows, attrs, float(confidence), int(num_classes), int(class_id),
+                                             float(nms_conf), Cn, sel.data_ptr(), counts.data_ptr(), _lib.current_stream()))
+    return sel, counts
+
+
+def pose_from_candidate_records(records, counts, kp3d, K, left_number: int = 50):
+    """The candidate pose tail on records made any way (bp_pose_from_candidate_records): cuda f32 [F,C,316] and int32 [F]
+    -> (poses f64 [F,166], merged f32 [F,C,152], info int32 [F,4]); layouts: include/betapose_hip.h."""
+    import torch
+    _lib.require_gpu()
+    rec = records.contiguous()
+    assert rec.dtype == torch.float32 and rec.dim() == 3 and rec.shape[2] == _lib.RESULT_FLOATS
+    F, Cn = rec.shape[0], rec.shape[1]
+    cnt = counts.to(device=rec.device, dtype=torch.int32).contiguous()
+    assert cnt.shape == (F,)
+    k3 = torch.as_tensor(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3), device=rec.device).contiguous()
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    poses = torch.empty((F, _lib.POSE_DOUBLES), dtype=torch.float64, device=rec.device)
+    merged = torch.zeros((F, Cn, _lib.MERGED_FLOATS), dtype=torch.float32, device=rec.device)
+    info = torch.zeros((F, 4), dtype=torch.int32, device=rec.device)
+    _lib.check(_lib.lib().bp_pose_from_candidate_records(rec.data_ptr(), cnt.data_ptr(), F, Cn, k3.data_ptr(), k3.shape[0],
+                                                         Kc.ctypes.data, int(left_number), poses.data_ptr(), merged.data_ptr(),
+                                                         info.data_ptr(), _lib.current_stream()))
+    return poses, merged, info
+
+
 def resize_bicubic(frames_u8, oh: int = 416, ow: int = 416, swap_rb: bool = True, want: str = "f32"):
     """Pillow-exact antialiased bicubic (dataloader.py:94-99).  ``frames``: cuda u8 [B,H,W,3].
     ``want`` 'u8' -> u8 [B,oh,ow,3]; 'f32' -> f32 NHWC /255."""

@@ -51,6 +51,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--class_map', default='', type=str, metavar='OBJ:CLASS,...',
                    help='--shared_detector: detector class of each object id, e.g. 1:0,5:1,6:2; default: the position of the '
                         'id in LineMod\'s sorted id list 1..15 (class = id - 1, as the reference\'s 15-class labels are written)')
+    p.add_argument('--candidates', type=int, default=0, metavar='C',
+                   help='--fused: up to C (1..8) box-NMS survivors per frame (--nms is the IoU threshold) go through one '
+                        'key-point pass at batch C and are merged by pPose-NMS; PnP on result[0] (DESIGN.md 3.7).  Alone '
+                        'or with --device_pnp; not with --pnp_ransac or --shared_detector')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
     p.add_argument('--device_pnp', default=False, action='store_true',
                    help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '

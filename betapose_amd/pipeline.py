@@ -238,6 +238,143 @@ class ScenePipeline:
         return self.results.cpu().numpy()
 
 
+class CandidatePipeline:
+    """A frame through several NMS survivors of the detector (``bp_cands_*``): bicubic resize, the detector, the select
+    with box NMS (``write_results``' NMS branch live, up to ``candidates`` boxes), ONE crop launch and ONE key-point pass
+    at batch ``candidates``, arg-max, (opt-in) the candidate pose tail -- pPose-NMS merges the candidates' key points and
+    the PnP runs on ``result[0]``.  ``results`` [C, 316] holds one ``FramePipeline`` record per candidate in survivor
+    order, ``counts`` [1] their number; unused rows carry index -1.  ``pose_model`` needs ``max_batch >= candidates``.
+    With ``candidates=1`` the row (and the pose row) is ``FramePipeline``'s, bit for bit."""
+
+    def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, candidates: int = 4,
+                 nms_conf: float = 0.6, confidence: float = 0.01, num_classes: int = 80, class_id: int = 0,
+                 use_graph: bool = True, frames=None):
+        import torch
+        Cn = int(candidates)
+        if not 1 <= Cn <= _lib.MAX_CANDIDATES:
+            raise ValueError("candidates must be 1 to %d, not %d" % (_lib.MAX_CANDIDATES, Cn))
+        _lib.require_gpu()
+        self.det, self.pose = det_model, getattr(pose_model, "pyranet", pose_model)
+        self.H, self.W, self.C = int(frame_h), int(frame_w), Cn
+        self.use_graph = bool(use_graph)
+        self.det.cuda()
+        self.pose.cuda()
+        dev = "cuda:%d" % self.det._device
+        self.frames = frames if frames is not None else torch.zeros((1, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        assert tuple(self.frames.shape) == (1, self.H, self.W, 3) and self.frames.dtype == torch.uint8
+        self.results = torch.zeros((Cn, RESULT_FLOATS), dtype=torch.float32, device=dev)
+        self.poses = None          # torch f64 [1, POSE_DOUBLES] once set_pose_solver was called
+        self.merged = None         # torch f32 [C, MERGED_FLOATS]: device copies of the tail's merged poses ...
+        self.info = None           # ... and int32 [4]: n, m, index of result[0], mask of the candidates merged into it
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp_cands_create(self.det.handle, self.pose.handle, Cn, self.H, self.W, float(confidence),
+                                              int(num_classes), int(class_id), float(nms_conf), self.frames.data_ptr(),
+                                              self.results.data_ptr(), C.byref(h)))
+        self._h = h
+        self.counts = _device_view(_lib.lib().bp_cands_counts(self._h), (1,), torch.int32, self.results.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                _lib.lib().bp_cands_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50):
+        """Opt-in candidate pose tail: every run then also writes ``self.poses`` [1, 166] f64 (``FramePipeline``'s pose
+        record for ``result[0]``), ``self.merged`` [C, 152] and ``self.info`` [4]; ``finish_candidate_pose_record`` turns
+        them into ``finish_candidate_records``' dict.  None switches it off.  (No RANSAC variant yet.)"""
+        import torch
+        L = _lib.lib()
+        if kp3d is None:
+            _lib.check(L.bp_cands_set_pose_solver(self._h, None, 0, None, 0, None))
+            return self
+        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
+        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
+        if self.poses is None:
+            self.poses = torch.zeros((1, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
+            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
+        _lib.check(L.bp_cands_set_pose_solver(self._h, k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number),
+                                              self.poses.data_ptr()))
+        dev = self.results.device
+        self.merged = _device_view(L.bp_cands_merged(self._h), (self.C, _lib.MERGED_FLOATS), torch.float32, dev)
+        self.info = _device_view(L.bp_cands_info(self._h), (4,), torch.int32, dev)
+        return self
+
+    def enqueue(self, stream: Optional[int] = None):
+        """Launch the frame on ``stream`` (default: torch's current stream).  ``self.frames`` must already hold it."""
+        _lib.check(_lib.lib().bp_cands_run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
+
+    def prepare(self):
+        """Build the frame's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
+        if self.use_graph:
+            _lib.check(_lib.lib().bp_cands_prepare(self._h))
+        return self
+
+    def kernel_count(self) -> int:
+        return _lib.lib().bp_cands_kernel_count(self._h)
+
+    def run(self, frame_bgr_u8):
+        """Convenience: upload one frame (numpy [H,W,3] u8 or cuda tensor), run, return (rows [C,316], count) (host)."""
+        import torch
+        f = frame_bgr_u8 if hasattr(frame_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frame_bgr_u8))
+        if f.dim() == 3:
+            f = f.unsqueeze(0)
+        self.frames.copy_(f, non_blocking=True)
+        self.enqueue()
+        return self.results.cpu().numpy(), int(self.counts.cpu()[0])
+
+
+# A frame's candidate results as ONE f32 row (StreamedRunner(candidates=C), the harness' gather): the pose row first (f64,
+# so its offset stays 8-byte aligned), then the C records, the merged poses, the count and the info words (int bits).
+def candidate_row_floats(C_: int, with_pose: bool) -> int:
+    return C_ * RESULT_FLOATS + 1 + ((2 * POSE_DOUBLES + C_ * _lib.MERGED_FLOATS + 4) if with_pose else 0)
+
+
+def _candidate_row_parts(row, C_: int, with_pose: bool):
+    """Views (pose f32-pairs, recs, merged, count, info) into a packed row (torch or numpy, f32 [W])."""
+    a = 2 * POSE_DOUBLES if with_pose else 0
+    b = a + C_ * RESULT_FLOATS
+    c = b + (C_ * _lib.MERGED_FLOATS if with_pose else 0)
+    return row[:a], row[a:b], row[b:c], row[c:c + 1], row[c + 1:c + 1 + (4 if with_pose else 0)]
+
+
+def _pack_candidate_row(pinned, cp, with_pose: bool):
+    import torch
+    pose, recs, merged, count, info = _candidate_row_parts(pinned, cp.C, with_pose)
+    recs.view(cp.C, RESULT_FLOATS).copy_(cp.results, non_blocking=True)
+    count.view(torch.int32).copy_(cp.counts, non_blocking=True)
+    if with_pose:
+        pose.view(torch.float64).copy_(cp.poses[0], non_blocking=True)
+        merged.view(cp.C, _lib.MERGED_FLOATS).copy_(cp.merged, non_blocking=True)
+        info.view(torch.int32).copy_(cp.info, non_blocking=True)
+
+
+def unpack_candidate_row(row, candidates: int, with_pose: bool):
+    """A packed candidate row (numpy f32) -> (recs [C,316], count, pose_row [166] f64 or None, merged [C,152] or None,
+    info [4] int32 or None)."""
+    row = np.ascontiguousarray(row, dtype=np.float32)
+    pose, recs, merged, count, info = _candidate_row_parts(row, int(candidates), with_pose)
+    n = int(count.view(np.int32)[0])
+    recs = recs.reshape(int(candidates), RESULT_FLOATS)
+    if not with_pose:
+        return recs, n, None, None, None
+    return (recs, n, np.ascontiguousarray(pose).view(np.float64), merged.reshape(int(candidates), _lib.MERGED_FLOATS),
+            np.ascontiguousarray(info).view(np.int32))
+
+
+def _device_view(ptr, shape, dtype, device):
+    """A torch tensor over library-owned device memory (alive as long as the owning handle)."""
+    import torch
+    n = int(np.prod(shape))
+    size = n * torch.empty((), dtype=dtype).element_size()
+
+    class _Mem:
+        __cuda_array_interface__ = {"shape": (size,), "typestr": "|u1", "data": (int(ptr), False), "version": 3}
+    return torch.as_tensor(_Mem(), device=device).view(dtype).reshape(shape)
+
+
 def frame_sharded_owner(n_objects: int, world: int):
     """Ownership of (frame, object) units when a shared detector serves all objects of a frame: the whole frame --
     units ``f * n_objects .. f * n_objects + n_objects - 1`` -- belongs to rank ``f % world``.  Returns ``owner(u)``."""
@@ -256,8 +393,12 @@ class StreamedRunner:
 
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, streams: int = 4,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, batch: int = 1,
-                 pose_solver=None):
-        """``pose_solver``: ``(kp3d, cam_K, left_number)`` or ``(kp3d, cam_K, left_number, ransac)`` turns the device pose tail on in every stream's pipeline; the
+                 pose_solver=None, candidates: Optional[int] = None, nms_conf: float = 0.6):
+        """``candidates`` = C: every stream owns one ``CandidatePipeline`` (up to C NMS survivors per frame at box-NMS
+        threshold ``nms_conf``, one frame per launch; ``pose_model`` needs ``max_batch >= C``) and ``on_record`` gets
+        ``(index, row)`` with the frame's packed candidate row (``unpack_candidate_row``); ``pose_solver`` is then
+        ``(kp3d, cam_K, left_number)`` -- the candidate tail has no RANSAC variant.
+        ``pose_solver``: ``(kp3d, cam_K, left_number)`` or ``(kp3d, cam_K, left_number, ransac)`` turns the device pose tail on in every stream's pipeline; the
         pose rows then come back with the records and ``on_record`` gets ``(index, rec, pose_row)``.
         ``batch`` frames per launch and stream (the reference's ``--detbatch``, dataloader.py:284-289): the engines
         must have been created with ``max_batch >= batch``.  More frames per launch mean fewer launches, K slices and
@@ -268,11 +409,30 @@ class StreamedRunner:
         pose = getattr(pose_model, "pyranet", pose_model)
         dets = [det_model] + [det_model.clone() for _ in range(S - 1)]
         poses = [pose] + [pose.clone() for _ in range(S - 1)]
-        self.pipes = [FramePipeline(dets[k], poses[k], frame_h, frame_w, batch=B, confidence=confidence,
-                                    num_classes=num_classes, use_graph=use_graph) for k in range(S)]
+        self.C = None if candidates is None else int(candidates)
+        if self.C is not None:
+            if B != 1:
+                raise ValueError("StreamedRunner: candidates run one frame per launch (batch=1), not batch=%d" % B)
+            if pose_solver is not None and len(pose_solver) > 3 and pose_solver[3] is not None:
+                raise ValueError("StreamedRunner: the candidate pose tail has no RANSAC variant")
+            self.pipes = [CandidatePipeline(dets[k], poses[k], frame_h, frame_w, candidates=self.C, nms_conf=nms_conf,
+                                            confidence=confidence, num_classes=num_classes, use_graph=use_graph) for k in range(S)]
+        else:
+            self.pipes = [FramePipeline(dets[k], poses[k], frame_h, frame_w, batch=B, confidence=confidence,
+                                        num_classes=num_classes, use_graph=use_graph) for k in range(S)]
         dev = self.pipes[0].frames.device
         self.S, self.B, self.H, self.W = S, B, int(frame_h), int(frame_w)
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
+        if self.C is not None:
+            self._with_pose = pose_solver is not None
+            if self._with_pose:
+                for cp in self.pipes:
+                    cp.set_pose_solver(*pose_solver[:3])
+            W_ = candidate_row_floats(self.C, self._with_pose)
+            self._pinned = [torch.empty((W_,), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
+            self._events = [torch.cuda.Event() for _ in range(2 * S)]
+            self._pinned_pose = None
+            return
         self._pinned = [torch.empty((B, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
         self._events = [torch.cuda.Event() for _ in range(2 * S)]
         self._pinned_pose = None
@@ -299,6 +459,9 @@ class StreamedRunner:
             poses = self._pinned_pose[j % NS].numpy().copy() if self._pinned_pose is not None else None
             for b, idx in enumerate(idxs):
                 source.release(idx)
+            if self.C is not None:
+                on_record(idxs[0], recs)
+                return
             for b, idx in enumerate(idxs):
                 if poses is None:
                     on_record(idx, recs[b])
@@ -310,7 +473,10 @@ class StreamedRunner:
             st = self.streams[k]
             with torch.cuda.stream(st):
                 self.pipes[k].enqueue(st.cuda_stream)
-                self._pinned[j % NS].copy_(self.pipes[k].results, non_blocking=True)
+                if self.C is not None:
+                    _pack_candidate_row(self._pinned[j % NS], self.pipes[k], self._with_pose)
+                else:
+                    self._pinned[j % NS].copy_(self.pipes[k].results, non_blocking=True)
                 if self._pinned_pose is not None:
                     self._pinned_pose[j % NS].copy_(self.pipes[k].poses, non_blocking=True)
                 self._events[j % NS].record(st)
@@ -597,6 +763,81 @@ def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.nd
         out.update({"cam_R": R, "cam_t": t})
     else:
         out.update({"cam_R": [], "cam_t": []})
+    return out
+
+
+def finish_candidate_records(recs: np.ndarray, count: int, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray,
+                             left_number: int = 50) -> dict:
+    """Host tail over the frame's ``count`` candidates (``CandidatePipeline`` rows [C, 316]): every candidate's key
+    points are decoded, ``pose_nms`` clusters and merges them (pPose_nms.py:24-122 with n rows, what ``DataWriter.update``
+    does with several boxes), and the PnP runs on ``result[0]`` after the ``left_number`` pruning.  With ``count`` 1 it is
+    ``finish_record``'s dict."""
+    recs = np.ascontiguousarray(recs, dtype=np.float32).reshape(-1, RESULT_FLOATS)
+    n = int(count)
+    if n <= 0:
+        return {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+    if n == 1:
+        return finish_record(recs[0], imgname, kp_3d, cam_K, left_number)
+    recs = recs[:n]
+    idx = recs[:, :1].copy().view(np.int32)[:, 0]
+    boxes = recs[:, 12:16].copy()
+    scores = recs[:, 5:6].copy()
+    kp = recs[:, 16:].reshape(n, 50, 6)
+    _, preds_img, preds_scores = decode_keypoints(kp, recs[:, 8:10], recs[:, 10:12])
+    result = pose_nms(boxes, scores, preds_img, preds_scores)
+    out = {"imgname": imgname, "result": result, "boxes": boxes, "scores": scores, "yolo_index": int(idx[0]),
+           "yolo_indices": idx}
+    if result:
+        kp_score = np.array(result[0]["kp_score"][:, 0])
+        kp_2d = np.array(result[0]["keypoints"])
+        k3 = np.array(kp_3d)
+        while len(kp_2d) > left_number:          # dataloader.py:718-722
+            d = int(np.argmin(kp_score, axis=0))
+            kp_score = np.delete(kp_score, d)
+            kp_2d = np.delete(kp_2d, d, axis=0)
+            k3 = np.delete(k3, d, axis=0)
+        R, t = solve_pnp(k3, kp_2d, cam_K)
+        out.update({"cam_R": R, "cam_t": t})
+    else:
+        out.update({"cam_R": [], "cam_t": []})
+    return out
+
+
+def finish_candidate_pose_record(recs: np.ndarray, count: int, pose_row: np.ndarray, merged: np.ndarray, info: np.ndarray,
+                                 imgname: str) -> dict:
+    """Device-tail twin of ``finish_candidate_records``: the rows [C, 316], their count, the pose row [166], the merged
+    poses [C, 152] and the info words [4] of the candidate pose tail -> the same dict, no arithmetic redone."""
+    recs = np.ascontiguousarray(recs, dtype=np.float32).reshape(-1, RESULT_FLOATS)
+    n = int(count)
+    info = np.asarray(info, dtype=np.int32).reshape(4)
+    if n == 1:
+        return finish_pose_record(recs[0], pose_row, imgname)
+    row = np.asarray(pose_row, dtype=np.float64).reshape(POSE_DOUBLES)
+    status = int(row[0])
+    if (n <= 0) != (status == 1) or (n > 0 and int(info[0]) != n):
+        raise ValueError("pose record (status %d, %d candidates) does not belong to these %d candidate records" % (status, int(info[0]), n))
+    if n <= 0:
+        return {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+    if status < 0:
+        raise _lib.BetaposeHipError(PNP_FAILED)
+    recs = recs[:n]
+    idx = recs[:, :1].copy().view(np.int32)[:, 0]
+    boxes = recs[:, 12:16].copy()
+    scores = recs[:, 5:6].copy()
+    mg = np.ascontiguousarray(merged, dtype=np.float32).reshape(-1, _lib.MERGED_FLOATS)
+    out = {"imgname": imgname, "boxes": boxes, "scores": scores, "yolo_index": int(idx[0]), "yolo_indices": idx}
+    result = []
+    for j in range(int(info[1])):
+        kp = mg[j, 2:].reshape(50, 3)
+        result.append({"bbox": boxes[0].copy(),                          # always the first box (pPose_nms.py:116)
+                       "keypoints": kp[:, :2].copy(),
+                       "kp_score": kp[:, 2:3].copy(),
+                       "proposal_score": mg[j, 1:2].copy()})
+    out["result"] = result
+    if status == 2:
+        out.update({"cam_R": [], "cam_t": []})
+        return out
+    out.update({"cam_R": row[2:11].reshape(3, 3).copy(), "cam_t": row[11:14].reshape(3, 1).copy()})
     return out
 
 

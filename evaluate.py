@@ -80,6 +80,18 @@ def main():
     # --pnp_ransac [PX]: the RANSAC variant (100 trials, confidence 0.99: ops.solve_pnp_ransac's defaults) in either tail
     ransac = (float(args.pnp_ransac), 100, 0.99) if args.pnp_ransac is not None else None
     pixel_thresh = 20.0 if args.occlusion else 5.0          # occlusion_betapose_evaluate.py:255 vs betapose_evaluate.py:257
+    C_ = int(args.candidates)
+    if C_:
+        from betapose_amd._lib import MAX_CANDIDATES
+        if not 1 <= C_ <= MAX_CANDIDATES:
+            raise SystemExit("--candidates takes 1 to %d candidate boxes per frame, not %d" % (MAX_CANDIDATES, C_))
+        if ransac is not None:
+            raise SystemExit("--candidates cannot be combined with --pnp_ransac: the candidate pose tail has no RANSAC variant yet")
+        if getattr(args, "shared_detector", ""):
+            raise SystemExit("--candidates cannot be combined with --shared_detector: candidates are boxes of ONE object's detector")
+        args.fused = True   # the candidate chain exists in the fused frame graph only
+        if max(1, args.detbatch) != 1:
+            raise SystemExit("--candidates runs one frame per launch: leave --detbatch at 1")
     print("Betapose begin running now.  Test object", obj_id, "| key points for PnP:", left_number)
     os.makedirs(args.outputpath, exist_ok=True)
 
@@ -120,7 +132,7 @@ def main():
     ys, ks = bpd.broadcast_stream(ys), bpd.broadcast_stream(ks)
     det = Darknet("yolo/cfg/yolov3-single.cfg", reso=int(args.inp_dim), max_batch=max(1, args.detbatch), device=local)
     det.load_stream(ys).cuda()
-    pose_model = FastPoseHIP.from_stream(ks, n_classes=args.nClasses, max_batch=max(1, args.detbatch) if args.fused else 1,
+    pose_model = FastPoseHIP.from_stream(ks, n_classes=args.nClasses, max_batch=max(1, args.detbatch, C_) if args.fused else 1,
                                         device=local).cuda()
     det.set_precision(args.precision)
     pose_model.set_precision(args.precision)
@@ -128,10 +140,12 @@ def main():
     t0 = time.time()
     if args.fused:
         from betapose_amd.frame_loader import FrameLoader
-        from betapose_amd.pipeline import POSE_DOUBLES, StreamedRunner, finish_pose_record, finish_record
+        from betapose_amd.pipeline import (POSE_DOUBLES, StreamedRunner, candidate_row_floats, finish_candidate_pose_record,
+                                           finish_candidate_records, finish_pose_record, finish_record, unpack_candidate_row)
         mine = bpd.shard_indices(len(im_names), rank, world)
-        recs = np.zeros((len(mine), 316), np.float32)
-        poses = np.zeros((len(mine), POSE_DOUBLES), np.float64) if args.device_pnp else None
+        # --candidates: a frame's record is its packed candidate row (C records, count and, with --device_pnp, the tail's outputs)
+        recs = np.zeros((len(mine), candidate_row_floats(C_, args.device_pnp) if C_ else 316), np.float32)
+        poses = np.zeros((len(mine), POSE_DOUBLES), np.float64) if args.device_pnp and not C_ else None
 
         def keep(j, rec, pose=None):
             recs[j] = rec
@@ -145,7 +159,8 @@ def main():
                                  depth=max(16, 2 * args.streams * max(1, args.detbatch) + threads))
             runner = StreamedRunner(det, pose_model, loader.height, loader.width, streams=args.streams,
                                     confidence=args.confidence, num_classes=args.num_classes, batch=args.detbatch,
-                                    pose_solver=(kp3d, cam_K, left_number, ransac) if args.device_pnp else None)
+                                    pose_solver=(kp3d, cam_K, left_number, ransac) if args.device_pnp else None,
+                                    candidates=C_ or None, nms_conf=args.nms_thesh)
             runner.run(loader, keep)
             loader.close()
         t_dev = time.time() - t_dev
@@ -153,11 +168,17 @@ def main():
             rank, len(mine), len(mine) / max(t_dev, 1e-9), args.streams, max(1, args.detbatch), args.load_threads))
         allrec = bpd.gather_records(recs, mine, len(im_names))
         # the pose rows travel through the same gather, each f64 as a pair of f32 bit patterns
-        allpose = bpd.gather_records(poses.view(np.float32), mine, len(im_names)) if args.device_pnp else None
+        allpose = bpd.gather_records(poses.view(np.float32), mine, len(im_names)) if poses is not None else None
         final_result = []
         if rank == 0:
             for i, name in enumerate(im_names):
-                if allpose is not None:
+                if C_:
+                    rows, n, prow, merged, info = unpack_candidate_row(allrec[i], C_, args.device_pnp)
+                    if args.device_pnp:
+                        out = finish_candidate_pose_record(rows, n, prow, merged, info, name)
+                    else:
+                        out = finish_candidate_records(rows, n, name, kp3d, cam_K, left_number)
+                elif allpose is not None:
                     out = finish_pose_record(allrec[i], np.ascontiguousarray(allpose[i]).view(np.float64), name)
                 else:
                     out = finish_record(allrec[i], name, kp3d, cam_K, left_number, ransac=ransac)

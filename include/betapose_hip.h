@@ -25,6 +25,9 @@
  *   bp_yolo_forward_select_classes, bp_scene_*
  *                          the same chain for K objects of one frame behind ONE multi-class detector pass
  *                          (write_results' class filter generalised; the reference runs one process per object)
+ *   bp_yolo_select_nms, bp_yolo_forward_select_nms, bp_crop_candidates, bp_cands_*, bp_pose_from_candidate_records
+ *                          write_results with its NMS branch live (yolo/util.py:180-196, hard-coded off in the reference)
+ *                          feeding pose_nms several candidates per frame (pPose_nms.py:24-122), PnP on result[0]
  *   bp_solve_pnp           pnp (cv2.solvePnP + cv2.Rodrigues)                 utils/utils.py:17-41
  *   bp_solve_pnp_ransac    the commented-out cv2.solvePnPRansac variant       utils/utils.py:32-36
  *   bp_pose_nms            pose_nms                                           pPose_nms.py:24-122
@@ -68,6 +71,7 @@ typedef struct bp_yolo bp_yolo;
 typedef struct bp_kpd bp_kpd;
 typedef struct bp_pipeline bp_pipeline;
 typedef struct bp_scene bp_scene;
+typedef struct bp_cands bp_cands;
 
 /* floats per frame in the pipeline result record:
  *   [0..7]   select: idx (int bits; -1 = no detection), x1,y1,x2,y2 (YOLO-input pixels), obj, cls_conf, cls_idx
@@ -78,6 +82,10 @@ typedef struct bp_scene bp_scene;
 #define BP_SEL_FLOATS 8
 /* class ids one shared detector pass can select for (bp_yolo_forward_select_classes, bp_scene_create) */
 #define BP_MAX_SCENE_CLASSES 16
+/* candidate boxes one frame can yield (bp_yolo_select_nms, bp_cands_create) */
+#define BP_MAX_CANDIDATES 8
+/* floats per merged pose of the candidate pose tail: pick (int bits), proposal score, 50 x (x, y, score) */
+#define BP_MERGED_FLOATS 152
 
 /* doubles per frame in the pose record of the device pose tail (bp_pipeline_set_pose_solver, bp_pose_from_records):
  *   [0]        status: 0 ok, 1 no detection, 2 dropped by pPose-NMS, < 0 the solver's status as bp_solve_pnp reports it
@@ -124,6 +132,20 @@ int bp_yolo_forward_select_classes(bp_yolo* y, const float* d_img_nchw, int batc
  * d_pred [batch][rows][attrs] -> d_sel [batch][8] */
 int bp_yolo_select(const float* d_pred, int batch, int rows, int attrs, float conf, int num_classes, float* d_sel,
                    void* stream);
+/* Select with box NMS: write_results with its NMS branch live and the final arg-max removed (yolo/util.py:176-196).  A row is
+ * live if objectness > conf and its first-max class is class_id; live rows are visited by descending objectness (lower row
+ * on ties); each visited survivor is kept and removes every later row whose IoU with it is not < nms_conf (bbox_iou,
+ * yolo/bbox.py:51-77, f32, + 1 on widths and heights, corner boxes in detector-input pixels; a NaN IoU removes); stop after
+ * max_candidates <= BP_MAX_CANDIDATES survivors.  dynamic_write_results' second pass at nms_conf - 0.05 when more than 100
+ * boxes survive is not reproduced: with at most 8 survivors kept it is moot.  d_sel [batch][max_candidates][8]: the select
+ * record of each survivor in survivor order ([6] = the class's score, [7] = the class id), unused slots index -1 and zeros;
+ * d_counts [batch]: survivors.  Candidate 0 is bp_yolo_select's / bp_yolo_forward_select's record bit for bit (class 0).
+ * The forward form decodes straight from the head tensors when d_pred is NULL; both forms write identical records.
+ * At most 12 288 rows per image. */
+int bp_yolo_select_nms(const float* d_pred, int batch, int rows, int attrs, float conf, int num_classes, int class_id,
+                       float nms_conf, int max_candidates, float* d_sel, int* d_counts, void* stream);
+int bp_yolo_forward_select_nms(bp_yolo* y, const float* d_img_nchw, int batch, float conf, int num_classes, int class_id,
+                               float nms_conf, int max_candidates, float* d_pred, float* d_sel, int* d_counts, void* stream);
 /* test/inspection hooks: intermediate layer outputs (dense NCHW copies) */
 int bp_yolo_tap_count(const bp_yolo* y);
 int bp_yolo_tap_info(const bp_yolo* y, int i, char* name, int cap, int* C, int* H, int* W);
@@ -136,6 +158,9 @@ void bp_kpd_destroy(bp_kpd* k);
 int bp_kpd_forward(bp_kpd* k, const float* d_inps_nchw, int batch, float* d_hm, void* stream);
 /* d_hm may be NULL; d_kp: [batch][50][6] */
 int bp_kpd_forward_argmax(bp_kpd* k, const float* d_inps_nchw, int batch, float* d_hm, float* d_kp, void* stream);
+/* launches one bp_kpd_forward_argmax pass makes at this batch under the current plan (recorded into a throw-away graph,
+ * nothing executes); < 0 on error.  bp_cands_kernel_count = bp_pipeline_kernel_count at batch 1 - this at 1 + this at C. */
+int bp_kpd_launch_count(bp_kpd* k, int batch);
 int bp_kpd_tap_count(const bp_kpd* k);
 int bp_kpd_tap_info(const bp_kpd* k, int i, char* name, int cap, int* C, int* H, int* W);
 int bp_kpd_tap_copy(bp_kpd* k, int i, int batch, float* d_out_nchw, void* stream);
@@ -207,6 +232,11 @@ size_t bp_kpd_device_bytes(const bp_kpd* k);
  * d_out_nhwc [batch][oh][ow][3]; d_pts [batch][8]. */
 int bp_crop(const uint8_t* d_frames, int batch, int H, int W, const float* d_sel, int reso, const float* d_boxes,
             float* d_out_nchw, float* d_out_nhwc, float* d_pts, int oh, int ow, void* stream);
+/* bp_crop over C candidate boxes per frame: d_frames [frames][H][W][3], d_sel [frames * C][8] or d_boxes [frames * C][4];
+ * crop n reads frame n / C with box n; outputs as bp_crop's at batch frames * C.  A slot without a box (index -1, zeros)
+ * crops as a frame without a detection does. */
+int bp_crop_candidates(const uint8_t* d_frames, int frames, int C, int H, int W, const float* d_sel, int reso,
+                       const float* d_boxes, float* d_out_nchw, float* d_out_nhwc, float* d_pts, int oh, int ow, void* stream);
 /* Pillow-exact antialiased bicubic: d_in [batch][H][W][3] u8 -> d_out_u8 [batch][oh][ow][3] (nullable) and/or
  * d_out_nhwc f32 /255 (nullable).  swap_rb: read BGR, write RGB. */
 int bp_resize_bicubic(const uint8_t* d_in, int batch, int H, int W, int oh, int ow, int swap_rb, uint8_t* d_out_u8,
@@ -328,6 +358,41 @@ double* bp_scene_poses(bp_scene* s);            /* NULL until a solver was set w
 int bp_scene_prepare(bp_scene* s);              /* capture + instantiate now; re-captures after a plan change of any engine */
 int bp_scene_run(bp_scene* s, int use_graph, void* stream);
 int bp_scene_kernel_count(bp_scene* s);         /* graph nodes per run (after the first capture), -1 before */
+
+/* ---- candidates: several NMS survivors per frame, merged by pPose-NMS (opt-in; bp_pipeline_* and bp_scene_* are unchanged) ----
+ * One frame per object, one stream, one hipGraph: resize -> detector -> select with box NMS -> one crop launch over the C
+ * boxes -> key-point net at batch C -> arg-max -> (opt-in) the candidate pose tail.  k's max_batch must be >= C.  d_frame
+ * [H][W][3] u8 BGR and d_results [C][BP_RESULT_FLOATS] are the caller's (NULL: the object's own); row c is the record
+ * bp_pipeline writes for candidate c; bp_cands_counts: device int [1], the survivors.  The graph always runs at batch C:
+ * unused slots are carried (index -1) and ignored by the tail.  With C = 1 the row is bp_pipeline's, bit for bit. */
+int bp_cands_create(bp_yolo* y, bp_kpd* k, int max_candidates, int frame_h, int frame_w, float conf, int num_classes,
+                    int class_id, float nms_conf, uint8_t* d_frame, float* d_results, bp_cands** out);
+void bp_cands_destroy(bp_cands* s);
+float* bp_cands_results(bp_cands* s);           /* device [C][BP_RESULT_FLOATS] */
+int* bp_cands_counts(bp_cands* s);              /* device [1] */
+int bp_cands_prepare(bp_cands* s);
+int bp_cands_run(bp_cands* s, int use_graph, void* stream);
+int bp_cands_kernel_count(bp_cands* s);         /* graph nodes per run (after the first capture), -1 before */
+/* The candidate pose tail, one wave64 workgroup per frame: decode of the n = count valid candidates (f32, bit-identical to
+ * the host), the full pPose-NMS over them as bp_pose_nms (pick, merged x / y / score and proposal score bit-identical; only
+ * tanhf / expf may round differently from the host's libm, and they feed the comparison simi > gamma alone), result[0] = the
+ * first merged pose that survives the filters, the left_number pruning, the iterative PnP.
+ *   d_pose [BP_POSE_DOUBLES]: the frame's row for result[0], today's layout; status 2 = every merged pose was filtered
+ *     out, 1 = no candidate
+ *   merged [C][BP_MERGED_FLOATS] f32: for each merged pose j < m the pick (int bits), the proposal score, 50 x (x, y, score)
+ *   info [4] int: n, m, index of result[0] among the merged poses (-1: none), bit mask of the candidates merged into it
+ * bp_cands_set_pose_solver: kp3d host [50][3]; NULL switches the tail off; drops the graph; d_pose NULL: the object's own
+ * row (bp_cands_pose).  bp_cands_merged / bp_cands_info: device, NULL until a solver was set.  A RANSAC variant does not
+ * exist yet. */
+int bp_cands_set_pose_solver(bp_cands* s, const double* kp3d, int n_kp, const double* K, int left_number, double* d_pose);
+double* bp_cands_pose(bp_cands* s);
+float* bp_cands_merged(bp_cands* s);
+int* bp_cands_info(bp_cands* s);
+/* the tail alone: d_records [frames][C][BP_RESULT_FLOATS], d_counts [frames], d_kp3d device [50][3] -> d_poses [frames][166],
+ * d_merged [frames][C][152], d_info [frames][4] */
+int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, int frames, int C, const double* d_kp3d,
+                                   int n_kp, const double* K, int left_number, double* d_poses, float* d_merged, int* d_info,
+                                   void* stream);
 
 /* ---- host post-processing (no device work) ---- */
 /* pnp (utils/utils.py:17-41): a restatement of cv2.solvePnP's default SOLVEPNP_ITERATIVE (planar / DLT initialisation,

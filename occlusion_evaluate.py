@@ -41,7 +41,14 @@ def main():
     from betapose_amd.opt import class_map, id_list, parse_args, shared_detector_arg
     args = parse_args()
     if not args.obj_ids:
-        return evaluate.main()          # the reference's own protocol: one object per run
+        return evaluate.main()          # the reference's own protocol: one object per run (--candidates works there)
+    if int(args.candidates):
+        if args.pnp_ransac is not None:
+            raise SystemExit("--candidates cannot be combined with --pnp_ransac: the candidate pose tail has no RANSAC variant yet")
+        if args.shared_detector:
+            raise SystemExit("--candidates cannot be combined with --shared_detector: candidates are boxes of ONE object's detector")
+        raise SystemExit("--candidates: the multi-object runner of this harness has no candidate mode yet; "
+                         "run one object at a time (--obj_id N instead of --obj_ids)")
 
     import torch
     from betapose_amd import _lib, dist as bpd, metrics, synth
