@@ -115,6 +115,7 @@ PROTOTYPES = {
     "bp_pose_from_candidate_records": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "bp_pose_errors_sym": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
     "bp_pipeline_poses": (vp, [vp]),
     "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),

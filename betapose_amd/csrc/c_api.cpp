@@ -26,6 +26,9 @@ int pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, 
 int pose_error_blocks(int n);
 void launch_pose_errors(const double* model, int n, const double* gt, const double* est, int P, const double* K,
                         int want, double* partial, double* out, hipStream_t s);
+size_t pose_errors_sym_scratch_bytes(int n, int P, int S);
+void launch_pose_errors_sym(const double* model, int n, const double* gt, const double* est, int P, const double* sym,
+                            int S, const double* K, int want, double* scratch, double* out, hipStream_t s);
 // pose_tail.hip
 void launch_solve_pnp_batch(const double* pts3d, int shared_3d, const double* pts2d, int n, int P, const PnpCam& cam,
                             double* Rt, int* status, hipStream_t s);
@@ -721,6 +724,23 @@ int bp_pose_errors(const double* d_model, int n, const double* d_gt, const doubl
     bp::launch_pose_errors(d_model, n, d_gt, d_est, P, K, want, partial, d_out, s);
     BP_HIP(hipGetLastError());
     BP_HIP(hipStreamSynchronize(s));   // partials live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym,
+                       int S, const double* K, int want, double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_gt && d_est && d_sym && d_out, "null argument");
+    BP_CHECK(n > 0 && P > 0 && S > 0, "n, P and S must be positive");
+    BP_CHECK(want >= 1 && want <= 3, "want must be a non-empty mask of 1 (MSSD), 2 (MSPD)");
+    BP_CHECK(K || !(want & 2), "K is required for the projection distance (MSPD)");
+    hipStream_t s = (hipStream_t)stream;
+    bp::Arena a;
+    double* scratch = (double*)a.alloc_bytes(bp::pose_errors_sym_scratch_bytes(n, P, S));
+    bp::launch_pose_errors_sym(d_model, n, d_gt, d_est, P, d_sym, S, K, want, scratch, d_out, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the per-symmetry maxima live in a local arena
     return 0;
     BP_CATCH
 }

@@ -89,6 +89,150 @@ def pose_errors(gt_poses, est_poses, model, cam, device=None, want=WANT_ADD | WA
     return out[:, 0], out[:, 1], out[:, 2]
 
 
+def symmetry_transforms(info_entry, max_sym_disc_step=0.01, obj_id=None):
+    """The symmetry set of one object as float64 [S, 3, 4] rows [R|t] in metres, from its ``models_info.yml`` entry
+    (the BOP field names, translations in the file's millimetres): ``symmetries_discrete``, a list of 16-number
+    row-major 4x4 transforms, and ``symmetries_continuous``, a list of ``{axis: [3], offset: [3]}``.  D = [I] + the
+    discrete entries in file order; a continuous entry becomes the N = ceil(pi / max_sym_disc_step) rotations by
+    i * 2 pi / N (i = 0 .. N - 1, so the identity is one of them) about the normalised axis through ``offset``; the set
+    is {c o d}, d outer and c inner, further continuous entries composed on in file order.  No field: [I].  A zero axis
+    or a discrete block further than 1e-6 from orthonormal raises ValueError naming ``obj_id``."""
+    entry = info_entry or {}
+    who = "object %s" % obj_id if obj_id is not None else "object"
+    sym = [np.eye(4)]
+    for k, flat in enumerate(entry.get("symmetries_discrete") or []):
+        T = np.asarray(flat, dtype=np.float64).reshape(4, 4).copy()
+        if np.abs(T[:3, :3] @ T[:3, :3].T - np.eye(3)).max() > 1e-6:
+            raise ValueError("%s: symmetries_discrete[%d] is not orthonormal" % (who, k))
+        T[:3, 3] /= 1000.0
+        T[3] = [0.0, 0.0, 0.0, 1.0]
+        sym.append(T)
+    for k, c in enumerate(entry.get("symmetries_continuous") or []):
+        axis = np.asarray(c["axis"], dtype=np.float64).reshape(3)
+        offset = np.asarray(c.get("offset", [0.0, 0.0, 0.0]), dtype=np.float64).reshape(3) / 1000.0
+        norm = float(np.linalg.norm(axis))
+        if not norm > 0.0:
+            raise ValueError("%s: symmetries_continuous[%d] has a zero axis" % (who, k))
+        a = axis / norm
+        A = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        N = int(np.ceil(np.pi / max_sym_disc_step))
+        turns = []
+        for i in range(N):
+            th = i * 2.0 * np.pi / N
+            T = np.eye(4)
+            T[:3, :3] = np.eye(3) + np.sin(th) * A + (1.0 - np.cos(th)) * (A @ A)     # Rodrigues
+            T[:3, 3] = offset - T[:3, :3] @ offset
+            turns.append(T)
+        sym = [c_ @ d for d in sym for c_ in turns]
+    return np.stack(sym)[:, :3, :4].copy()
+
+
+def load_symmetries(base, obj_id, max_sym_disc_step=0.01):
+    """``symmetry_transforms`` of object ``obj_id``'s entry in ``<base>/models/models_info.yml``."""
+    import yaml
+    with open(os.path.join(base, "models", "models_info.yml")) as f:
+        info = yaml.safe_load(f)
+    return symmetry_transforms(info[obj_id], max_sym_disc_step, obj_id=obj_id)
+
+
+def load_image_width(base, default=640):
+    """``width`` of ``<base>/camera.yml`` (the r = width / 640 of the MSPD thresholds), ``default`` without one."""
+    import yaml
+    path = os.path.join(base, "camera.yml")
+    if not os.path.exists(path):
+        return default
+    with open(path) as f:
+        return int((yaml.safe_load(f) or {}).get("width", default))
+
+
+def _sym44(syms):
+    s = np.asarray(syms, dtype=np.float64).reshape(-1, *np.shape(syms)[-2:])[:, :3, :4]
+    out = np.tile(np.eye(4), (len(s), 1, 1))
+    out[:, :3, :4] = s
+    return out
+
+
+def mssd_err(gt_pose, est_pose, model, syms):
+    """BOP's maximum symmetry-aware surface distance, min_S max_x |E x - G S x| in metres: in the camera frame, one
+    symmetry at a time.  ``syms`` [S, 3, 4] or [S, 4, 4] (symmetry_transforms).  ``bp_pose_errors_sym`` computes the
+    same on the GPU with the symmetries folded into per-lane matrices."""
+    model = np.asarray(model, dtype=np.float64).reshape(-1, 3)
+    g, e = np.asarray(gt_pose, dtype=np.float64), np.asarray(est_pose, dtype=np.float64)
+    pe = model @ e[:3, :3].T + e[:3, 3]
+    best = np.inf
+    for S in _sym44(syms):
+        ms = model @ S[:3, :3].T + S[:3, 3]
+        pg = ms @ g[:3, :3].T + g[:3, 3]
+        best = min(best, float(np.linalg.norm(pe - pg, axis=1).max()))
+    return best
+
+
+def mspd_err(gt_pose, est_pose, model, cam, syms):
+    """BOP's maximum symmetry-aware projection distance, min_S max_x |proj(E x) - proj(G S x)| in pixels, with
+    proj(X) = (K X)[:2] / (K X)[2]; one symmetry at a time, as mssd_err."""
+    model = np.asarray(model, dtype=np.float64).reshape(-1, 3)
+    g, e = np.asarray(gt_pose, dtype=np.float64), np.asarray(est_pose, dtype=np.float64)
+    cam = np.asarray(cam, dtype=np.float64)
+
+    def proj(X):
+        u = X @ cam.T
+        return u[:, :2] / u[:, 2:3]
+    pe = proj(model @ e[:3, :3].T + e[:3, 3])
+    best = np.inf
+    for S in _sym44(syms):
+        ms = model @ S[:3, :3].T + S[:3, 3]
+        pg = proj(ms @ g[:3, :3].T + g[:3, 3])
+        best = min(best, float(np.linalg.norm(pe - pg, axis=1).max()))
+    return best
+
+
+WANT_MSSD, WANT_MSPD = 1, 2                 # bp_pose_errors_sym's `want` bits
+BOP_MSSD_THETAS = tuple(0.05 * k for k in range(1, 11))     # fractions of the object diameter
+BOP_MSPD_THETAS = tuple(5.0 * k for k in range(1, 11))      # pixels at a 640-wide image
+
+
+def pose_errors_sym(gt_poses, est_poses, model, cam, syms, device=None, want=WANT_MSSD | WANT_MSPD):
+    """(MSSD, MSPD) of P pose pairs of one model over its symmetry set as two float64 arrays [P] (metres, pixels).
+    Poses are [P, 4, 4] or [P, 3, 4], ``syms`` [S, 3, 4] or [S, 4, 4]; ``cam`` the 3x3 K of MSPD.  ``device=None``:
+    mssd_err / mspd_err pair by pair; a torch device: one ``bp_pose_errors_sym`` call on it.  ``want`` selects the
+    columns (WANT_MSSD, WANT_MSPD); the others are NaN."""
+    gt = np.asarray(gt_poses, dtype=np.float64).reshape(-1, *np.shape(gt_poses)[-2:])[:, :3, :4]
+    est = np.asarray(est_poses, dtype=np.float64).reshape(-1, *np.shape(est_poses)[-2:])[:, :3, :4]
+    if gt.shape != est.shape:
+        raise ValueError("gt_poses and est_poses differ in shape: %s vs %s" % (gt.shape, est.shape))
+    model = np.ascontiguousarray(model, dtype=np.float64).reshape(-1, 3)
+    sym = np.ascontiguousarray(_sym44(syms)[:, :3, :4])
+    if len(sym) < 1:
+        raise ValueError("the symmetry set is empty (it holds at least the identity)")
+    P = len(gt)
+    out = np.full((P, 2), np.nan)
+    if P == 0:
+        return out[:, 0], out[:, 1]
+    if device is None:
+        for p in range(P):
+            if want & WANT_MSSD:
+                out[p, 0] = mssd_err(gt[p], est[p], model, sym)
+            if want & WANT_MSPD:
+                out[p, 1] = mspd_err(gt[p], est[p], model, cam, sym)
+        return out[:, 0], out[:, 1]
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    dev = torch.device(device)
+    K = np.ascontiguousarray(cam, dtype=np.float64).reshape(9) if want & WANT_MSPD else None
+    with torch.cuda.device(dev):
+        d_model = torch.from_numpy(model).to(dev)
+        d_gt = torch.from_numpy(np.ascontiguousarray(gt.reshape(P, 12))).to(dev)
+        d_est = torch.from_numpy(np.ascontiguousarray(est.reshape(P, 12))).to(dev)
+        d_sym = torch.from_numpy(sym.reshape(len(sym), 12)).to(dev)
+        d_out = torch.from_numpy(out).to(dev)
+        _lib.check(_lib.lib().bp_pose_errors_sym(_lib.ptr(d_model), len(model), _lib.ptr(d_gt), _lib.ptr(d_est), P,
+                                                 _lib.ptr(d_sym), len(sym), _lib.ptr(K), int(want), _lib.ptr(d_out),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        out = d_out.cpu().numpy()
+    return out[:, 0], out[:, 1]
+
+
 def rot_error(gt_pose, est_pose):
     """Angle of the relative rotation in degrees, 0..180 (utils/metrics.py:35-67 computes the same angle through
     quaternions)."""
@@ -191,13 +335,17 @@ def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
 
 
 def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model_vertices, cam_K, diameter_mm,
-                     pixel_thresh: float = 5.0, symmetric: bool = False, device=None):
+                     pixel_thresh: float = 5.0, symmetric: bool = False, device=None, symmetries=None,
+                     image_width: int = 640):
     """The metric loop of betapose_evaluate.py:204-266.  ``gt_frames[nr]`` = list of ``{'pose': 4x4, 'bbox': [x, y, w, h]}`` (one per ground-truth
     annotation compared; a bare dict is accepted for one).
     Returns dict(mean_add, mean_2d_acc, mean_iou, mean_add_err_mm, n).  ``symmetric``: also ADD-S (add_s_err) --
     ``mean_adds``, the fraction under diameter / 10 (the ADD rule of betapose_evaluate.py:246-249), and
     ``mean_adds_err_mm``.  ``device``: every scored pair's errors in one bp_pose_errors call on that torch device
-    instead of numpy."""
+    instead of numpy.  ``symmetries`` (symmetry_transforms): also BOP's MSSD and MSPD over that set on the same scored
+    pairs (pose_errors_sym, on ``device`` when one is given) -- ``ar_mssd``, the mean over theta = 0.05 .. 0.50 of the
+    fraction with MSSD < theta * diameter, ``ar_mspd``, the mean over theta = 5 .. 50 of the fraction with
+    MSPD < theta * image_width / 640, ``mean_mssd_err_mm`` and ``mean_mspd_err_px``."""
     ious, gts, ests = [], [], []
     for f in final_result:
         nr = int(os.path.basename(f["imgname"])[0:-4])
@@ -236,6 +384,15 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
     if symmetric:
         m["mean_adds"] = float(np.mean([a < diameter_mm / 10 for a in adds_errs])) if adds_errs else float("nan")
         m["mean_adds_err_mm"] = float(np.mean(adds_errs)) if adds_errs else float("nan")
+    if symmetries is not None:
+        mssd, mspd = pose_errors_sym(np.reshape(gts, (-1, 4, 4)), np.reshape(ests, (-1, 4, 4)), model_vertices, cam_K,
+                                     symmetries, device)
+        mssd_mm, r = mssd * 1000, image_width / 640.0
+        nan = float("nan")
+        m["ar_mssd"] = float(np.mean([np.mean(mssd_mm < th * diameter_mm) for th in BOP_MSSD_THETAS])) if len(gts) else nan
+        m["ar_mspd"] = float(np.mean([np.mean(mspd < th * r) for th in BOP_MSPD_THETAS])) if len(gts) else nan
+        m["mean_mssd_err_mm"] = float(np.mean(mssd_mm)) if len(gts) else nan
+        m["mean_mspd_err_px"] = float(np.mean(mspd)) if len(gts) else nan
     return m
 
 

@@ -43,6 +43,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help='comma-separated object ids scored with ADD-S as well (LineMod\'s symmetric objects are 10, eggbox, '
                         'and 11, glue): one more line per such object, "Mean add-s accuracy for seq XX is: ...", computed '
                         'on the run\'s GPU (metrics.pose_errors)')
+    p.add_argument('--bop_metrics', default=False, action='store_true',
+                   help='also score every evaluated object with the BOP symmetry-aware errors MSSD and MSPD, over the '
+                        'symmetry set its models_info.yml entry declares (symmetries_discrete / symmetries_continuous; '
+                        'none: the identity), as average recall over the ten BOP thresholds: two more lines per object, '
+                        '"Mean mssd recall for seq XX is: ..." and "Mean mspd recall for seq XX is: ...", computed on the '
+                        'run\'s GPU (metrics.pose_errors_sym)')
     p.add_argument('--shared_detector', default='', type=str, metavar='CFG[,WEIGHTS]',
                    help='occlusion_evaluate.py --obj_ids: ONE multi-class detector (Darknet cfg, .weights file) serves every '
                         'object -- one resize and one detector pass per frame, the best box of each object\'s class, then each '

@@ -145,11 +145,23 @@ def _write_ply(path: str, pts: np.ndarray) -> None:
             f.write("%.6f %.6f %.6f\n" % (x, y, z))
 
 
+def _plain_yaml(v):
+    """Nested dicts / lists / arrays of numbers as plain Python dicts, lists and floats (what yaml.safe_dump takes)."""
+    if isinstance(v, dict):
+        return {k: _plain_yaml(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple, np.ndarray)):
+        return [_plain_yaml(x) for x in (v.reshape(-1) if isinstance(v, np.ndarray) else v)]
+    return float(v)
+
+
 def write_sixd_tree(base: str, seq: int, gt_by_frame: Dict[int, list], models_mm: Dict[int, np.ndarray],
-                    kpmodels_mm: Dict[int, np.ndarray], diameters_mm: Dict[int, float], cam_K=None) -> None:
+                    kpmodels_mm: Dict[int, np.ndarray], diameters_mm: Dict[int, float], cam_K=None,
+                    symmetries: Dict[int, dict] = None) -> None:
     """Lay out a SIXD-format ground-truth tree the harness reads (utils/sixd.py:60-111; betapose_evaluate.py:60-75):
     ``camera.yml``, ``models/models_info.yml``, ``models/obj_XX.ply``, ``kpmodels/obj_XX.ply`` (millimetres) and
-    ``test/<seq>/{gt.yml, info.yml}``.  ``gt_by_frame[nr]`` = list of ``(obj_id, R[3,3], t_mm[3], bbox[x,y,w,h])``."""
+    ``test/<seq>/{gt.yml, info.yml}``.  ``gt_by_frame[nr]`` = list of ``(obj_id, R[3,3], t_mm[3], bbox[x,y,w,h])``.
+    ``symmetries[obj_id]`` = ``{'symmetries_discrete': [...], 'symmetries_continuous': [...]}`` (either; the BOP fields
+    metrics.symmetry_transforms reads, millimetres) is merged into that object's ``models_info.yml`` entry."""
     import os
     import yaml
     K = CAM_K if cam_K is None else np.asarray(cam_K, dtype=np.float64)
@@ -161,7 +173,10 @@ def write_sixd_tree(base: str, seq: int, gt_by_frame: Dict[int, list], models_mm
         yaml.safe_dump({"fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
                         "depth_scale": 1.0, "width": 640, "height": 480}, f)
     with open(os.path.join(base, "models", "models_info.yml"), "w") as f:
-        yaml.safe_dump({int(k): {"diameter": float(v)} for k, v in sorted(diameters_mm.items())}, f)
+        info = {int(k): {"diameter": float(v)} for k, v in sorted(diameters_mm.items())}
+        for k, fields in sorted((symmetries or {}).items()):
+            info[int(k)].update(_plain_yaml(fields))
+        yaml.safe_dump(info, f)
     for oid, pts in models_mm.items():
         _write_ply(os.path.join(base, "models", "obj_%02d.ply" % oid), np.asarray(pts))
     for oid, pts in kpmodels_mm.items():

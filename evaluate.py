@@ -62,6 +62,16 @@ def load_sixd_gt(base, obj_id, seq_id=None):
     return frames, model, kp, float(info[obj_id]["diameter"]), cam
 
 
+def print_bop_metrics(base, obj_id, final_result, gt_frames, model_vertices, cam, diameter, device):
+    """--bop_metrics: the object's symmetry set from models_info.yml, MSSD / MSPD of the scored pairs on ``device``, and
+    the two average-recall lines (the lines before them are computed as without the flag)."""
+    m = metrics.evaluate_results(final_result, gt_frames, model_vertices, cam, diameter, device=device,
+                                 symmetries=metrics.load_symmetries(base, obj_id),
+                                 image_width=metrics.load_image_width(base))
+    print("Mean mssd recall for seq %02d is: %.3f" % (obj_id, m["ar_mssd"]))
+    print("Mean mspd recall for seq %02d is: %.3f" % (obj_id, m["ar_mspd"]))
+
+
 def main():
     args = parse_args()
     import torch
@@ -224,6 +234,9 @@ def main():
                 print("Mean add-s accuracy for seq %02d is: %.3f" % (obj_id, m["mean_adds"]))
             print("2d reprojection accuracy for seq %02d is: %.3f" % (obj_id, m["mean_2d_acc"]))
             print("Mean IoU for seq %02d is: %.3f" % (obj_id, m["mean_iou"]))
+            if args.bop_metrics:
+                print_bop_metrics(args.sixd_base, obj_id, final_result, gt_frames, model_vertices, metric_cam, diameter,
+                                  torch.device("cuda", local))
     bpd.finalize()
 
 

@@ -40,6 +40,7 @@
  *                          the solvePnPRansac variant on device, hypotheses in parallel   utils/utils.py:32-36
  *   bp_pose_errors         add_err / projection_error_2d + the commented-out   utils/metrics.py:10-33,99-127
  *                          closest-point (ADD-S) loop, over every vertex
+ *   bp_pose_errors_sym     no reference counterpart: the BOP errors MSSD and MSPD over an object's symmetry set
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
@@ -251,6 +252,13 @@ int bp_heatmap_argmax(const float* d_hm, int batch, int C, int H, int W, float* 
  * d_out [P][3] = (ADD, ADD-S, 2-D px), unrequested columns untouched.  Synchronises `stream`. */
 int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P,
                    const double* K, int want, double* d_out, void* stream);
+/* The BOP symmetry-aware errors, f64, for P pose pairs of one model: MSSD = min_S max_x |E x - G S x| (metres) and
+ * MSPD = min_S max_x |proj(E x) - proj(G S x)| (pixels), E the estimate, G the ground truth, S over the symmetry set.
+ * d_model [n][3] object frame; d_gt, d_est [P][12] and d_sym [S][12] row-major [R|t] (the set should hold the
+ * identity); K host 3x3 (may be NULL when (want & 2) == 0); want: 1 MSSD, 2 MSPD; d_out [P][2] = (MSSD, MSPD),
+ * unrequested columns untouched.  Bit-identical from run to run.  Synchronises `stream`. */
+int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym,
+                       int S, const double* K, int want, double* d_out, void* stream);
 /* one fused convolution on device tensors (unit tests / kernel benchmarks).  h_w: host OIHW filter, h_bias host or NULL.
  * d_in NHWC [N,H,W,Cin]; d_out per store_mode (0 NHWC, 1 nearest-x2 NHWC, 2 PixelShuffle(2) NHWC, 3 NCHW);
  * act 0 linear / 1 leaky(0.1) / 2 relu; d_res NHWC residual or NULL; splits 0 auto; tile -1 auto, else a kernel id

@@ -207,6 +207,9 @@ def main():
                 print("Mean add-s accuracy for seq %02d is: %.3f" % (o, m["mean_adds"]))
             print("2d reprojection accuracy with leftkeypoints %d for seq %02d is: %.3f" % (left_number, o, m["mean_2d_acc"]))
             print("Mean IoU for seq %02d is: %.3f" % (o, m["mean_iou"]))
+            if args.bop_metrics:
+                evaluate.print_bop_metrics(args.sixd_base, o, final_result, frames_gt, model, cam, diameter,
+                                           torch.device("cuda", local))
     bpd.finalize()
 
 
