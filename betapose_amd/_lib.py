@@ -113,6 +113,9 @@ PROTOTYPES = {
     "bp_cands_merged": (vp, [vp]),
     "bp_cands_info": (vp, [vp]),
     "bp_pose_from_candidate_records": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    "bp_cands_set_instance_poses": (C.c_int, [vp, C.c_int, vp]),
+    "bp_cands_instance_poses": (vp, [vp]),
+    "bp_pose_instances_from_merged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_pose_errors_sym": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
@@ -130,6 +133,7 @@ PROTOTYPES = {
     "bp_pose_from_records_ransac": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp,
                                               C.c_size_t, vp]),
     "bp_solve_pnp": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "bp_solve_pnp_status": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
     "bp_solve_pnp_refined": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "bp_solve_pnp_ransac": (C.c_int, [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
     "bp_pose_nms": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),

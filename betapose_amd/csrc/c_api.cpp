@@ -39,6 +39,9 @@ void launch_pose_tail_prepare(const float* records, int batch, const double* kp3
 // pose_tail_cands.hip
 void launch_pose_tail_cands(const float* records, const int* counts, int frames, int C, const double* kp3d, const PnpCam& cam,
                             int left_number, double* poses, float* merged, int* info, hipStream_t s);
+// pose_tail_inst.hip
+void launch_pose_instances(const float* merged, const int* info, const double* poses, int frames, int C, const double* kp3d,
+                           const PnpCam& cam, int left_number, double* inst_poses, hipStream_t s);
 // pnp_ransac.hip
 size_t pnp_ransac_workspace_bytes(int P, int max_trials);
 void launch_pnp_ransac(const double* pts3d, size_t stride3d, const double* pts2d, size_t stride2d, const int* active, int n,
@@ -217,6 +220,9 @@ struct bp_cands {
     int* info = nullptr;         // [4]
     bp::PnpCam cam{};
     int left_number = 50;
+    bool inst_on = false;
+    double* inst = nullptr;      // [C][166]: a pose per merged candidate (opt-in)
+    double* own_inst = nullptr;
     ~bp_cands() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -1087,6 +1093,23 @@ int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, 
     BP_CATCH
 }
 
+int bp_pose_instances_from_merged(const float* d_merged, const int* d_info, const double* d_poses, int frames, int C,
+                                  const double* d_kp3d, int n_kp, const double* K, int left_number, double* d_inst_poses,
+                                  void* stream) {
+    BP_TRY
+    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
+    BP_CHECK(d_merged && d_info && d_poses && d_kp3d && K && d_inst_poses, "null argument");
+    BP_CHECK(frames >= 0 && frames <= 65535, "frames must be in [0, 65535]");
+    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
+    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    if (frames == 0) return 0;
+    bp::launch_pose_instances(d_merged, d_info, d_poses, frames, C, d_kp3d, make_pnp_cam(K), left_number, d_inst_poses,
+                              (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
 int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
                        double* d_Rt, int* d_status, void* stream) {
     BP_TRY
@@ -1475,6 +1498,8 @@ static void cands_enqueue(bp_cands* p, hipStream_t s) {
     kn.forward(kn.input_nhwc(), true, C, nullptr, p->results + 16, s, R);
     if (p->pose_on)
         bp::launch_pose_tail_cands(p->results, p->counts, 1, C, p->kp3d, p->cam, p->left_number, p->pose, p->merged, p->info, s);
+    if (p->pose_on && p->inst_on)
+        bp::launch_pose_instances(p->merged, p->info, p->pose, 1, C, p->kp3d, p->cam, p->left_number, p->inst, s);
     BP_HIP(hipGetLastError());
 }
 
@@ -1521,6 +1546,7 @@ int* bp_cands_counts(bp_cands* s) { return s ? s->counts : nullptr; }
 double* bp_cands_pose(bp_cands* s) { return s ? s->pose : nullptr; }
 float* bp_cands_merged(bp_cands* s) { return s ? s->merged : nullptr; }
 int* bp_cands_info(bp_cands* s) { return s ? s->info : nullptr; }
+double* bp_cands_instance_poses(bp_cands* s) { return s && s->inst_on ? s->inst : nullptr; }
 int bp_cands_kernel_count(bp_cands* s) {
     if (!s || !s->graph) return -1;
     size_t n = 0;
@@ -1538,6 +1564,7 @@ int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const do
     cands_drop_graph(p);
     if (!kp3d) {
         p->pose_on = false;
+        p->inst_on = false;          // the instance poses read the tail's outputs
         return 0;
     }
     BP_CHECK(K, "null camera matrix");
@@ -1560,6 +1587,27 @@ int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const do
     p->cam = make_pnp_cam(K);
     p->left_number = left_number;
     p->pose_on = true;
+    return 0;
+    BP_CATCH
+}
+
+int bp_cands_set_instance_poses(bp_cands* p, int on, double* d_inst_poses) {
+    BP_TRY
+    BP_CHECK(p, "null argument");
+    BP_CHECK(p->pose_on, "bp_cands_set_instance_poses: set a pose solver first (bp_cands_set_pose_solver)");
+    cands_drop_graph(p);
+    if (!on) {
+        p->inst_on = false;
+        return 0;
+    }
+    BP_HIP(hipSetDevice(p->y->device));
+    const size_t bytes = (size_t)p->C * BP_POSE_DOUBLES * sizeof(double);
+    if (!d_inst_poses && !p->own_inst) {
+        p->own_inst = (double*)p->arena.alloc_bytes(bytes);
+        BP_HIP(hipMemset(p->own_inst, 0, bytes));
+    }
+    p->inst = d_inst_poses ? d_inst_poses : p->own_inst;
+    p->inst_on = true;
     return 0;
     BP_CATCH
 }
@@ -1710,6 +1758,14 @@ int bp_solve_pnp(const double* pts3d, const double* pts2d, int n, const double* 
     BP_CHECK(pts3d && pts2d && K && R && t, "null argument");
     const int rc = bp::solve_pnp(pts3d, pts2d, n, K, R, t);
     if (rc != 0) throw bp::Error("solve_pnp failed (need >= 6 non-degenerate points, or >= 4 coplanar ones)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_solve_pnp_status(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t, int* status) {
+    BP_TRY
+    BP_CHECK(pts3d && pts2d && K && R && t && status, "null argument");
+    *status = bp::solve_pnp(pts3d, pts2d, n, K, R, t);
     return 0;
     BP_CATCH
 }

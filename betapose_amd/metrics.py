@@ -336,7 +336,7 @@ def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
 
 def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model_vertices, cam_K, diameter_mm,
                      pixel_thresh: float = 5.0, symmetric: bool = False, device=None, symmetries=None,
-                     image_width: int = 640):
+                     image_width: int = 640, match_instances: bool = False):
     """The metric loop of betapose_evaluate.py:204-266.  ``gt_frames[nr]`` = list of ``{'pose': 4x4, 'bbox': [x, y, w, h]}`` (one per ground-truth
     annotation compared; a bare dict is accepted for one).
     Returns dict(mean_add, mean_2d_acc, mean_iou, mean_add_err_mm, n).  ``symmetric``: also ADD-S (add_s_err) --
@@ -345,7 +345,12 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
     instead of numpy.  ``symmetries`` (symmetry_transforms): also BOP's MSSD and MSPD over that set on the same scored
     pairs (pose_errors_sym, on ``device`` when one is given) -- ``ar_mssd``, the mean over theta = 0.05 .. 0.50 of the
     fraction with MSSD < theta * diameter, ``ar_mspd``, the mean over theta = 5 .. 50 of the fraction with
-    MSPD < theta * image_width / 640, ``mean_mssd_err_mm`` and ``mean_mspd_err_px``."""
+    MSPD < theta * image_width / 640, ``mean_mssd_err_mm`` and ``mean_mspd_err_px``.
+    ``match_instances``: a frame whose dict has ``"instances"`` (pipeline.finish_candidate_records, all_instances) is
+    scored instance by instance instead of ``result[0]`` against every annotation: each ground-truth entry, in list
+    order, takes the still unmatched solved instance whose ``bbox`` has the highest IoU with its box (ties: the lower j);
+    the pair is scored at IoU >= 0.5, and an entry without such an instance counts in ``n`` and ``mean_iou`` as a miss
+    (with the best IoU left, 0 when no instance is).  A frame without any result is skipped, as it is without the flag."""
     ious, gts, ests = [], [], []
     for f in final_result:
         nr = int(os.path.basename(f["imgname"])[0:-4])
@@ -354,6 +359,28 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
         entries = gt_frames[nr]
         if isinstance(entries, dict):
             entries = [entries]
+        if match_instances and "instances" in f:
+            if len(f["result"]) < 1:
+                continue
+            free = [j for j, s in enumerate(f["instances"]) if int(s["status"]) == 0 and len(s["cam_R"]) > 0]
+            for gt in entries:
+                x, y, w, h = gt["bbox"]
+                gt_box = [x, y, x + w, y + h]
+                best, bi = -1, 0.0
+                for j in free:                                   # ascending j: the first maximum is the lower j
+                    i = iou(gt_box, np.asarray(f["instances"][j]["bbox"]).tolist())
+                    if best < 0 or i > bi:
+                        best, bi = j, i
+                ious.append(bi)
+                if best >= 0 and bi >= 0.5:
+                    free.remove(best)
+                    s = f["instances"][best]
+                    pose = np.eye(4)
+                    pose[:3, :3] = s["cam_R"]
+                    pose[:3, 3] = np.asarray(s["cam_t"])[:, 0]
+                    gts.append(gt["pose"])
+                    ests.append(pose)
+            continue
         for gt in entries:
             if len(f["result"]) < 1 or len(f["result"][0]) < 1:
                 continue

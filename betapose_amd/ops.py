@@ -139,6 +139,27 @@ def pose_from_candidate_records(records, counts, kp3d, K, left_number: int = 50)
     return poses, merged, info
 
 
+def pose_instances(merged, info, poses, kp3d, K, left_number: int = 50):
+    """A pose for every merged candidate (bp_pose_instances_from_merged) on ``pose_from_candidate_records``' outputs: cuda
+    merged f32 [F,C,152], info int32 [F,4], poses f64 [F,166] -> f64 [F,C,166]: row 0 is the frame's pose row, row
+    0 < j < m the pruned PnP of merged pose j, every other row status 1; layouts: include/betapose_hip.h."""
+    import torch
+    _lib.require_gpu()
+    mg = merged.contiguous()
+    assert mg.dtype == torch.float32 and mg.dim() == 3 and mg.shape[2] == _lib.MERGED_FLOATS
+    F, Cn = mg.shape[0], mg.shape[1]
+    inf = info.to(device=mg.device, dtype=torch.int32).contiguous()
+    ps = poses.to(device=mg.device, dtype=torch.float64).contiguous()
+    assert inf.shape == (F, 4) and ps.shape == (F, _lib.POSE_DOUBLES)
+    k3 = torch.as_tensor(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3), device=mg.device).contiguous()
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    inst = torch.empty((F, Cn, _lib.POSE_DOUBLES), dtype=torch.float64, device=mg.device)
+    _lib.check(_lib.lib().bp_pose_instances_from_merged(mg.data_ptr(), inf.data_ptr(), ps.data_ptr(), F, Cn, k3.data_ptr(),
+                                                        k3.shape[0], Kc.ctypes.data, int(left_number), inst.data_ptr(),
+                                                        _lib.current_stream()))
+    return inst
+
+
 def resize_bicubic(frames_u8, oh: int = 416, ow: int = 416, swap_rb: bool = True, want: str = "f32"):
     """Pillow-exact antialiased bicubic (dataloader.py:94-99).  ``frames``: cuda u8 [B,H,W,3].
     ``want`` 'u8' -> u8 [B,oh,ow,3]; 'f32' -> f32 NHWC /255."""
@@ -170,6 +191,23 @@ def solve_pnp(points_3d, points_2d, K, method: str = "iterative"):
     fn = {"iterative": _lib.lib().bp_solve_pnp, "refined": _lib.lib().bp_solve_pnp_refined}[method]
     _lib.check(fn(p3.ctypes.data, p2.ctypes.data, p3.shape[0], Kc.ctypes.data, R.ctypes.data, t.ctypes.data))
     return R, t.reshape(3, 1)
+
+
+def solve_pnp_status(points_3d, points_2d, K):
+    """``solve_pnp`` with a failure reported instead of raised (bp_solve_pnp_status): returns (R, t, status); status 0 =
+    solved, else the solver's code (-1 too few points, -2 degenerate) and R, t are empty lists."""
+    p3 = np.ascontiguousarray(points_3d, dtype=np.float64)
+    p2 = np.ascontiguousarray(np.asarray(points_2d)[:, :2], dtype=np.float64)
+    assert p3.shape[0] == p2.shape[0], "points 3D and points 2D must have same number of vertices"
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    R = np.empty((3, 3), np.float64)
+    t = np.empty(3, np.float64)
+    st = C.c_int(0)
+    _lib.check(_lib.lib().bp_solve_pnp_status(p3.ctypes.data, p2.ctypes.data, p3.shape[0], Kc.ctypes.data, R.ctypes.data,
+                                              t.ctypes.data, C.addressof(st)))
+    if st.value != 0:
+        return [], [], int(st.value)
+    return R, t.reshape(3, 1), 0
 
 
 def solve_pnp_batch(points_3d, points_2d, K):

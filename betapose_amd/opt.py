@@ -61,6 +61,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='--fused: up to C (1..8) box-NMS survivors per frame (--nms is the IoU threshold) go through one '
                         'key-point pass at batch C and are merged by pPose-NMS; PnP on result[0] (DESIGN.md 3.7).  Alone '
                         'or with --device_pnp; not with --pnp_ransac or --shared_detector')
+    p.add_argument('--all_instances', default=False, action='store_true',
+                   help='--candidates C: a pose for EVERY merged pose pPose-NMS leaves, not result[0] alone -- each JSON entry '
+                        'carries its own cam_R / cam_t and the scoring matches ground-truth entries to instances by box IoU '
+                        '(DESIGN.md 3.7).  Alone or with --device_pnp (one more launch at the end of the frame graph)')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
     p.add_argument('--device_pnp', default=False, action='store_true',
                    help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '

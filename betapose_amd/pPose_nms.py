@@ -27,6 +27,11 @@ def pose_nms(bboxes, bbox_scores, pose_preds, pose_scores):
     """bboxes [n,4], bbox_scores [n,1], pose_preds [n,K,2], pose_scores [n,K,1] -> list of dicts with
     numpy arrays: 'bbox' [4], 'keypoints' [K,2], 'kp_score' [K,1], 'proposal_score' (1-elem array).
     The greedy cluster / merge runs in ``bp_pose_nms`` (csrc/host_post.cpp, f32) for every n."""
+    return pose_nms_picks(bboxes, bbox_scores, pose_preds, pose_scores)[0]
+
+
+def pose_nms_picks(bboxes, bbox_scores, pose_preds, pose_scores):
+    """``pose_nms`` plus, as a second value, the int32 [m] candidate each merged pose was built around."""
     import ctypes as C
     from . import _lib
     bboxes = np.ascontiguousarray(_np(bboxes), dtype=F32).reshape(-1, 4)
@@ -45,14 +50,17 @@ def pose_nms(bboxes, bbox_scores, pose_preds, pose_scores):
     return [{"bbox": bboxes[0].copy(),                                   # always the first box (pPose_nms.py:116)
              "keypoints": out_pose[j].copy(),
              "kp_score": out_score[j].reshape(K, 1).copy(),
-             "proposal_score": out_prop[j:j + 1].copy()} for j in range(m)]
+             "proposal_score": out_prop[j:j + 1].copy()} for j in range(m)], pick[:m].copy()
 
 
 def results_to_json_list(all_results, for_eval=False):
     out = []
     for im_res in all_results:
         im_name, cam_R, cam_t = im_res["imgname"], im_res["cam_R"], im_res["cam_t"]
-        for human in im_res["result"]:
+        instances = im_res.get("instances")      # a pose per merged candidate (pipeline.finish_candidate_records)
+        for j, human in enumerate(im_res["result"]):
+            if instances is not None:            # entry j carries its own pose, none when its PnP failed
+                cam_R, cam_t = instances[j]["cam_R"], instances[j]["cam_t"]
             r = {}
             if for_eval:
                 r["image_id"] = int(im_name.split('/')[-1].split('.')[0].split('_')[-1])

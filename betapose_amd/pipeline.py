@@ -18,8 +18,8 @@ import numpy as np
 
 from . import _lib
 from .eval import decode_keypoints
-from .ops import solve_pnp, solve_pnp_ransac
-from .pPose_nms import pose_nms
+from .ops import solve_pnp, solve_pnp_ransac, solve_pnp_status
+from .pPose_nms import pose_nms, pose_nms_picks
 
 RESULT_FLOATS = _lib.RESULT_FLOATS
 POSE_DOUBLES = _lib.POSE_DOUBLES
@@ -266,6 +266,7 @@ class CandidatePipeline:
         self.poses = None          # torch f64 [1, POSE_DOUBLES] once set_pose_solver was called
         self.merged = None         # torch f32 [C, MERGED_FLOATS]: device copies of the tail's merged poses ...
         self.info = None           # ... and int32 [4]: n, m, index of result[0], mask of the candidates merged into it
+        self.inst_poses = None     # torch f64 [C, POSE_DOUBLES] with set_pose_solver(..., all_instances=True)
         h = C.c_void_p()
         _lib.check(_lib.lib().bp_cands_create(self.det.handle, self.pose.handle, Cn, self.H, self.W, float(confidence),
                                               int(num_classes), int(class_id), float(nms_conf), self.frames.data_ptr(),
@@ -281,14 +282,17 @@ class CandidatePipeline:
         except Exception:
             pass
 
-    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50):
+    def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50, all_instances: bool = False):
         """Opt-in candidate pose tail: every run then also writes ``self.poses`` [1, 166] f64 (``FramePipeline``'s pose
         record for ``result[0]``), ``self.merged`` [C, 152] and ``self.info`` [4]; ``finish_candidate_pose_record`` turns
-        them into ``finish_candidate_records``' dict.  None switches it off.  (No RANSAC variant yet.)"""
+        them into ``finish_candidate_records``' dict.  None switches it off.  (No RANSAC variant yet.)
+        ``all_instances``: one more launch solves EVERY merged pose, not ``result[0]`` alone: ``self.inst_poses`` [C, 166]
+        f64, row j the pose row of merged pose j (row 0 = ``self.poses[0]``, rows past the last merged pose status 1)."""
         import torch
         L = _lib.lib()
         if kp3d is None:
             _lib.check(L.bp_cands_set_pose_solver(self._h, None, 0, None, 0, None))
+            self.inst_poses = None
             return self
         k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
         Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
@@ -300,6 +304,14 @@ class CandidatePipeline:
         dev = self.results.device
         self.merged = _device_view(L.bp_cands_merged(self._h), (self.C, _lib.MERGED_FLOATS), torch.float32, dev)
         self.info = _device_view(L.bp_cands_info(self._h), (4,), torch.int32, dev)
+        if all_instances:
+            if self.inst_poses is None:
+                self.inst_poses = torch.zeros((self.C, POSE_DOUBLES), dtype=torch.float64, device=dev)
+                torch.cuda.current_stream(dev).synchronize()
+            _lib.check(L.bp_cands_set_instance_poses(self._h, 1, self.inst_poses.data_ptr()))
+        elif self.inst_poses is not None:
+            _lib.check(L.bp_cands_set_instance_poses(self._h, 0, None))
+            self.inst_poses = None
         return self
 
     def enqueue(self, stream: Optional[int] = None):
@@ -327,9 +339,23 @@ class CandidatePipeline:
 
 
 # A frame's candidate results as ONE f32 row (StreamedRunner(candidates=C), the harness' gather): the pose row first (f64,
-# so its offset stays 8-byte aligned), then the C records, the merged poses, the count and the info words (int bits).
-def candidate_row_floats(C_: int, with_pose: bool) -> int:
-    return C_ * RESULT_FLOATS + 1 + ((2 * POSE_DOUBLES + C_ * _lib.MERGED_FLOATS + 4) if with_pose else 0)
+# so its offset stays 8-byte aligned), then the C records, the merged poses, the count and the info words (int bits);
+# with ``instances`` the C instance pose rows (f64) follow everything else, after a pad word where they would otherwise
+# start on an odd float.
+def candidate_row_floats(C_: int, with_pose: bool, instances: bool = False) -> int:
+    base = C_ * RESULT_FLOATS + 1 + ((2 * POSE_DOUBLES + C_ * _lib.MERGED_FLOATS + 4) if with_pose else 0)
+    if not instances:
+        return base
+    if not with_pose:
+        raise ValueError("instance rows need the pose tail (with_pose)")
+    return base + (base & 1) + 2 * POSE_DOUBLES * C_
+
+
+def _candidate_row_instances(row, C_: int):
+    """View of the instance rows (f32 pairs, [2 * 166 * C]) at the end of a packed row that carries them."""
+    base = candidate_row_floats(C_, True)
+    a = base + (base & 1)
+    return row[a:a + 2 * POSE_DOUBLES * C_]
 
 
 def _candidate_row_parts(row, C_: int, with_pose: bool):
@@ -340,8 +366,10 @@ def _candidate_row_parts(row, C_: int, with_pose: bool):
     return row[:a], row[a:b], row[b:c], row[c:c + 1], row[c + 1:c + 1 + (4 if with_pose else 0)]
 
 
-def _pack_candidate_row(pinned, cp, with_pose: bool):
+def _pack_candidate_row(pinned, cp, with_pose: bool, instances: bool = False):
     import torch
+    if instances:
+        _candidate_row_instances(pinned, cp.C).view(torch.float64).view(cp.C, POSE_DOUBLES).copy_(cp.inst_poses, non_blocking=True)
     pose, recs, merged, count, info = _candidate_row_parts(pinned, cp.C, with_pose)
     recs.view(cp.C, RESULT_FLOATS).copy_(cp.results, non_blocking=True)
     count.view(torch.int32).copy_(cp.counts, non_blocking=True)
@@ -351,10 +379,13 @@ def _pack_candidate_row(pinned, cp, with_pose: bool):
         info.view(torch.int32).copy_(cp.info, non_blocking=True)
 
 
-def unpack_candidate_row(row, candidates: int, with_pose: bool):
+def unpack_candidate_row(row, candidates: int, with_pose: bool, instances: bool = False):
     """A packed candidate row (numpy f32) -> (recs [C,316], count, pose_row [166] f64 or None, merged [C,152] or None,
-    info [4] int32 or None)."""
+    info [4] int32 or None); with ``instances`` a sixth value, the instance pose rows [C,166] f64."""
     row = np.ascontiguousarray(row, dtype=np.float32)
+    if instances:
+        inst = np.ascontiguousarray(_candidate_row_instances(row, int(candidates))).view(np.float64)
+        return unpack_candidate_row(row, candidates, with_pose) + (inst.reshape(int(candidates), POSE_DOUBLES),)
     pose, recs, merged, count, info = _candidate_row_parts(row, int(candidates), with_pose)
     n = int(count.view(np.int32)[0])
     recs = recs.reshape(int(candidates), RESULT_FLOATS)
@@ -393,8 +424,10 @@ class StreamedRunner:
 
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, streams: int = 4,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, batch: int = 1,
-                 pose_solver=None, candidates: Optional[int] = None, nms_conf: float = 0.6):
-        """``candidates`` = C: every stream owns one ``CandidatePipeline`` (up to C NMS survivors per frame at box-NMS
+                 pose_solver=None, candidates: Optional[int] = None, nms_conf: float = 0.6, all_instances: bool = False):
+        """``all_instances`` (with ``candidates`` and a ``pose_solver``): every stream's tail solves every merged pose and
+        the packed row carries the instance rows (``unpack_candidate_row(..., instances=True)``).
+        ``candidates`` = C: every stream owns one ``CandidatePipeline`` (up to C NMS survivors per frame at box-NMS
         threshold ``nms_conf``, one frame per launch; ``pose_model`` needs ``max_batch >= C``) and ``on_record`` gets
         ``(index, row)`` with the frame's packed candidate row (``unpack_candidate_row``); ``pose_solver`` is then
         ``(kp3d, cam_K, left_number)`` -- the candidate tail has no RANSAC variant.
@@ -410,6 +443,9 @@ class StreamedRunner:
         dets = [det_model] + [det_model.clone() for _ in range(S - 1)]
         poses = [pose] + [pose.clone() for _ in range(S - 1)]
         self.C = None if candidates is None else int(candidates)
+        self._instances = bool(all_instances)
+        if self._instances and (self.C is None or pose_solver is None):
+            raise ValueError("StreamedRunner: all_instances needs candidates=C and a pose_solver")
         if self.C is not None:
             if B != 1:
                 raise ValueError("StreamedRunner: candidates run one frame per launch (batch=1), not batch=%d" % B)
@@ -427,8 +463,8 @@ class StreamedRunner:
             self._with_pose = pose_solver is not None
             if self._with_pose:
                 for cp in self.pipes:
-                    cp.set_pose_solver(*pose_solver[:3])
-            W_ = candidate_row_floats(self.C, self._with_pose)
+                    cp.set_pose_solver(*pose_solver[:3], all_instances=self._instances)
+            W_ = candidate_row_floats(self.C, self._with_pose, self._instances)
             self._pinned = [torch.empty((W_,), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
             self._events = [torch.cuda.Event() for _ in range(2 * S)]
             self._pinned_pose = None
@@ -474,7 +510,7 @@ class StreamedRunner:
             with torch.cuda.stream(st):
                 self.pipes[k].enqueue(st.cuda_stream)
                 if self.C is not None:
-                    _pack_candidate_row(self._pinned[j % NS], self.pipes[k], self._with_pose)
+                    _pack_candidate_row(self._pinned[j % NS], self.pipes[k], self._with_pose, self._instances)
                 else:
                     self._pinned[j % NS].copy_(self.pipes[k].results, non_blocking=True)
                 if self._pinned_pose is not None:
@@ -766,58 +802,118 @@ def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.nd
     return out
 
 
+def _prune_keypoints(human: dict, kp_3d: np.ndarray, left_number: int):
+    """dataloader.py:718-722 on one merged pose: drop the lowest score until ``left_number`` remain -> (kp_3d, kp_2d)."""
+    kp_score = np.array(human["kp_score"][:, 0])
+    kp_2d = np.array(human["keypoints"])
+    k3 = np.array(kp_3d)
+    while len(kp_2d) > left_number:
+        d = int(np.argmin(kp_score, axis=0))
+        kp_score = np.delete(kp_score, d)
+        kp_2d = np.delete(kp_2d, d, axis=0)
+        k3 = np.delete(k3, d, axis=0)
+    return k3, kp_2d
+
+
+def _host_instances(out: dict, picks, kp_3d: np.ndarray, cam_K: np.ndarray, left_number: int) -> list:
+    """The ``"instances"`` list for a host dict whose ``result[0]`` is already solved: entry 0 carries the frame's pose,
+    every other merged pose goes through the same pruning and ``solve_pnp``; its failure is recorded, not raised."""
+    inst = []
+    for j, human in enumerate(out["result"]):
+        pk = int(picks[j])
+        if j == 0:
+            R, t, st = out["cam_R"], out["cam_t"], 0
+            npts = min(len(human["keypoints"]), max(int(left_number), 0))
+        else:
+            k3, kp_2d = _prune_keypoints(human, kp_3d, left_number)
+            R, t, st = solve_pnp_status(k3, kp_2d, cam_K)
+            npts = len(kp_2d)
+        inst.append({"cam_R": R, "cam_t": t, "status": st, "points": npts, "pick": pk, "bbox": out["boxes"][pk].copy()})
+    return inst
+
+
 def finish_candidate_records(recs: np.ndarray, count: int, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray,
-                             left_number: int = 50) -> dict:
+                             left_number: int = 50, all_instances: bool = False) -> dict:
     """Host tail over the frame's ``count`` candidates (``CandidatePipeline`` rows [C, 316]): every candidate's key
     points are decoded, ``pose_nms`` clusters and merges them (pPose_nms.py:24-122 with n rows, what ``DataWriter.update``
     does with several boxes), and the PnP runs on ``result[0]`` after the ``left_number`` pruning.  With ``count`` 1 it is
-    ``finish_record``'s dict."""
+    ``finish_record``'s dict.
+    ``all_instances``: the dict gains ``"instances"``, a list parallel to ``"result"``: {"cam_R", "cam_t", "status",
+    "points", "pick", "bbox"} per merged pose -- its own pruned PnP (entry 0: the frame's ``cam_R`` / ``cam_t``), the
+    solver's code and the points it used, the candidate the pose was built around and that candidate's box
+    (``result[j]["bbox"]`` stays the first box, pPose_nms.py:116).  A failed PnP of an entry j > 0 is recorded (empty
+    ``cam_R`` / ``cam_t``, ``status`` < 0), not raised."""
     recs = np.ascontiguousarray(recs, dtype=np.float32).reshape(-1, RESULT_FLOATS)
     n = int(count)
     if n <= 0:
-        return {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+        out = {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+        if all_instances:
+            out["instances"] = []
+        return out
     if n == 1:
-        return finish_record(recs[0], imgname, kp_3d, cam_K, left_number)
+        out = finish_record(recs[0], imgname, kp_3d, cam_K, left_number)
+        if all_instances:
+            out["instances"] = _host_instances(out, [0] * len(out["result"]), kp_3d, cam_K, left_number)
+        return out
     recs = recs[:n]
     idx = recs[:, :1].copy().view(np.int32)[:, 0]
     boxes = recs[:, 12:16].copy()
     scores = recs[:, 5:6].copy()
     kp = recs[:, 16:].reshape(n, 50, 6)
     _, preds_img, preds_scores = decode_keypoints(kp, recs[:, 8:10], recs[:, 10:12])
-    result = pose_nms(boxes, scores, preds_img, preds_scores)
+    result, picks = pose_nms_picks(boxes, scores, preds_img, preds_scores)
     out = {"imgname": imgname, "result": result, "boxes": boxes, "scores": scores, "yolo_index": int(idx[0]),
            "yolo_indices": idx}
     if result:
-        kp_score = np.array(result[0]["kp_score"][:, 0])
-        kp_2d = np.array(result[0]["keypoints"])
-        k3 = np.array(kp_3d)
-        while len(kp_2d) > left_number:          # dataloader.py:718-722
-            d = int(np.argmin(kp_score, axis=0))
-            kp_score = np.delete(kp_score, d)
-            kp_2d = np.delete(kp_2d, d, axis=0)
-            k3 = np.delete(k3, d, axis=0)
+        k3, kp_2d = _prune_keypoints(result[0], kp_3d, left_number)
         R, t = solve_pnp(k3, kp_2d, cam_K)
         out.update({"cam_R": R, "cam_t": t})
     else:
         out.update({"cam_R": [], "cam_t": []})
+    if all_instances:
+        out["instances"] = _host_instances(out, picks, kp_3d, cam_K, left_number)
     return out
 
 
+def _device_instances(out: dict, picks, inst_poses: np.ndarray) -> list:
+    """The ``"instances"`` list from the device's instance rows [C, 166]: ``_host_instances``' entries, nothing redone."""
+    rows = np.asarray(inst_poses, dtype=np.float64).reshape(-1, POSE_DOUBLES)
+    inst = []
+    for j in range(len(out["result"])):
+        r = rows[j]
+        st, pk = int(r[0]), int(picks[j])
+        if j == 0:
+            R, t = out["cam_R"], out["cam_t"]
+        elif st == 0:
+            R, t = r[2:11].reshape(3, 3).copy(), r[11:14].reshape(3, 1).copy()
+        else:
+            R, t = [], []
+        inst.append({"cam_R": R, "cam_t": t, "status": st, "points": int(r[1]), "pick": pk, "bbox": out["boxes"][pk].copy()})
+    return inst
+
+
 def finish_candidate_pose_record(recs: np.ndarray, count: int, pose_row: np.ndarray, merged: np.ndarray, info: np.ndarray,
-                                 imgname: str) -> dict:
+                                 imgname: str, inst_poses: Optional[np.ndarray] = None) -> dict:
     """Device-tail twin of ``finish_candidate_records``: the rows [C, 316], their count, the pose row [166], the merged
-    poses [C, 152] and the info words [4] of the candidate pose tail -> the same dict, no arithmetic redone."""
+    poses [C, 152] and the info words [4] of the candidate pose tail -> the same dict, no arithmetic redone.
+    ``inst_poses`` [C, 166] (``CandidatePipeline.inst_poses``): the dict of ``all_instances=True``."""
     recs = np.ascontiguousarray(recs, dtype=np.float32).reshape(-1, RESULT_FLOATS)
     n = int(count)
     info = np.asarray(info, dtype=np.int32).reshape(4)
     if n == 1:
-        return finish_pose_record(recs[0], pose_row, imgname)
+        out = finish_pose_record(recs[0], pose_row, imgname)
+        if inst_poses is not None:
+            out["instances"] = _device_instances(out, [0] * len(out["result"]), inst_poses)
+        return out
     row = np.asarray(pose_row, dtype=np.float64).reshape(POSE_DOUBLES)
     status = int(row[0])
     if (n <= 0) != (status == 1) or (n > 0 and int(info[0]) != n):
         raise ValueError("pose record (status %d, %d candidates) does not belong to these %d candidate records" % (status, int(info[0]), n))
     if n <= 0:
-        return {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+        out = {"imgname": imgname, "result": [], "cam_R": [], "cam_t": [], "boxes": None}
+        if inst_poses is not None:
+            out["instances"] = []
+        return out
     if status < 0:
         raise _lib.BetaposeHipError(PNP_FAILED)
     recs = recs[:n]
@@ -836,8 +932,10 @@ def finish_candidate_pose_record(recs: np.ndarray, count: int, pose_row: np.ndar
     out["result"] = result
     if status == 2:
         out.update({"cam_R": [], "cam_t": []})
-        return out
-    out.update({"cam_R": row[2:11].reshape(3, 3).copy(), "cam_t": row[11:14].reshape(3, 1).copy()})
+    else:
+        out.update({"cam_R": row[2:11].reshape(3, 3).copy(), "cam_t": row[11:14].reshape(3, 1).copy()})
+    if inst_poses is not None:
+        out["instances"] = _device_instances(out, mg[:len(result), :1].copy().view(np.int32)[:, 0], inst_poses)
     return out
 
 

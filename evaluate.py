@@ -62,12 +62,12 @@ def load_sixd_gt(base, obj_id, seq_id=None):
     return frames, model, kp, float(info[obj_id]["diameter"]), cam
 
 
-def print_bop_metrics(base, obj_id, final_result, gt_frames, model_vertices, cam, diameter, device):
+def print_bop_metrics(base, obj_id, final_result, gt_frames, model_vertices, cam, diameter, device, match_instances=False):
     """--bop_metrics: the object's symmetry set from models_info.yml, MSSD / MSPD of the scored pairs on ``device``, and
     the two average-recall lines (the lines before them are computed as without the flag)."""
     m = metrics.evaluate_results(final_result, gt_frames, model_vertices, cam, diameter, device=device,
                                  symmetries=metrics.load_symmetries(base, obj_id),
-                                 image_width=metrics.load_image_width(base))
+                                 image_width=metrics.load_image_width(base), match_instances=match_instances)
     print("Mean mssd recall for seq %02d is: %.3f" % (obj_id, m["ar_mssd"]))
     print("Mean mspd recall for seq %02d is: %.3f" % (obj_id, m["ar_mspd"]))
 
@@ -91,6 +91,8 @@ def main():
     ransac = (float(args.pnp_ransac), 100, 0.99) if args.pnp_ransac is not None else None
     pixel_thresh = 20.0 if args.occlusion else 5.0          # occlusion_betapose_evaluate.py:255 vs betapose_evaluate.py:257
     C_ = int(args.candidates)
+    if args.all_instances and not C_:
+        raise SystemExit("--all_instances needs --candidates C: the instances are the merged poses of a frame's candidate boxes")
     if C_:
         from betapose_amd._lib import MAX_CANDIDATES
         if not 1 <= C_ <= MAX_CANDIDATES:
@@ -154,7 +156,9 @@ def main():
                                            finish_candidate_records, finish_pose_record, finish_record, unpack_candidate_row)
         mine = bpd.shard_indices(len(im_names), rank, world)
         # --candidates: a frame's record is its packed candidate row (C records, count and, with --device_pnp, the tail's outputs)
-        recs = np.zeros((len(mine), candidate_row_floats(C_, args.device_pnp) if C_ else 316), np.float32)
+        # (and, with --all_instances on top, the instance pose rows)
+        inst_dev = bool(C_ and args.device_pnp and args.all_instances)
+        recs = np.zeros((len(mine), candidate_row_floats(C_, args.device_pnp, inst_dev) if C_ else 316), np.float32)
         poses = np.zeros((len(mine), POSE_DOUBLES), np.float64) if args.device_pnp and not C_ else None
 
         def keep(j, rec, pose=None):
@@ -170,7 +174,7 @@ def main():
             runner = StreamedRunner(det, pose_model, loader.height, loader.width, streams=args.streams,
                                     confidence=args.confidence, num_classes=args.num_classes, batch=args.detbatch,
                                     pose_solver=(kp3d, cam_K, left_number, ransac) if args.device_pnp else None,
-                                    candidates=C_ or None, nms_conf=args.nms_thesh)
+                                    candidates=C_ or None, nms_conf=args.nms_thesh, all_instances=inst_dev)
             runner.run(loader, keep)
             loader.close()
         t_dev = time.time() - t_dev
@@ -184,10 +188,13 @@ def main():
             for i, name in enumerate(im_names):
                 if C_:
                     rows, n, prow, merged, info = unpack_candidate_row(allrec[i], C_, args.device_pnp)
-                    if args.device_pnp:
+                    if inst_dev:
+                        inst = unpack_candidate_row(allrec[i], C_, True, instances=True)[5]
+                        out = finish_candidate_pose_record(rows, n, prow, merged, info, name, inst_poses=inst)
+                    elif args.device_pnp:
                         out = finish_candidate_pose_record(rows, n, prow, merged, info, name)
                     else:
-                        out = finish_candidate_records(rows, n, name, kp3d, cam_K, left_number)
+                        out = finish_candidate_records(rows, n, name, kp3d, cam_K, left_number, all_instances=args.all_instances)
                 elif allpose is not None:
                     out = finish_pose_record(allrec[i], np.ascontiguousarray(allpose[i]).view(np.float64), name)
                 else:
@@ -228,7 +235,8 @@ def main():
         if gt_frames is not None:
             sym = obj_id in id_list(args.symmetric_ids)
             m = metrics.evaluate_results(final_result, gt_frames, model_vertices, metric_cam, diameter, pixel_thresh,
-                                         symmetric=sym, device=torch.device("cuda", local) if sym else None)
+                                         symmetric=sym, device=torch.device("cuda", local) if sym else None,
+                                         match_instances=args.all_instances)
             print("Mean add accuracy for seq %02d is: %.3f" % (obj_id, m["mean_add"]))
             if sym:
                 print("Mean add-s accuracy for seq %02d is: %.3f" % (obj_id, m["mean_adds"]))
@@ -236,7 +244,7 @@ def main():
             print("Mean IoU for seq %02d is: %.3f" % (obj_id, m["mean_iou"]))
             if args.bop_metrics:
                 print_bop_metrics(args.sixd_base, obj_id, final_result, gt_frames, model_vertices, metric_cam, diameter,
-                                  torch.device("cuda", local))
+                                  torch.device("cuda", local), match_instances=args.all_instances)
     bpd.finalize()
 
 

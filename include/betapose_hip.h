@@ -25,7 +25,8 @@
  *   bp_yolo_forward_select_classes, bp_scene_*
  *                          the same chain for K objects of one frame behind ONE multi-class detector pass
  *                          (write_results' class filter generalised; the reference runs one process per object)
- *   bp_yolo_select_nms, bp_yolo_forward_select_nms, bp_crop_candidates, bp_cands_*, bp_pose_from_candidate_records
+ *   bp_yolo_select_nms, bp_yolo_forward_select_nms, bp_crop_candidates, bp_cands_*, bp_pose_from_candidate_records,
+ *   bp_pose_instances_from_merged
  *                          write_results with its NMS branch live (yolo/util.py:180-196, hard-coded off in the reference)
  *                          feeding pose_nms several candidates per frame (pPose_nms.py:24-122), PnP on result[0]
  *   bp_solve_pnp           pnp (cv2.solvePnP + cv2.Rodrigues)                 utils/utils.py:17-41
@@ -401,12 +402,33 @@ int* bp_cands_info(bp_cands* s);
 int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, int frames, int C, const double* d_kp3d,
                                    int n_kp, const double* K, int left_number, double* d_poses, float* d_merged, int* d_info,
                                    void* stream);
+/* A pose for EVERY merged candidate (opt-in; the tail above solves result[0] alone), one wave64 workgroup per (frame, slot):
+ *   inst_poses [C][BP_POSE_DOUBLES] f64, row j in the pose row's layout: status, points used, R [9], t [3], proposal
+ *     score, slot 15 = 0, 50 x (x, y, score)
+ *   j = 0            the frame's existing pose row (d_pose), all 166 doubles, whatever its status (0, 1 = no candidate,
+ *                    2 = everything filtered, < 0 = PnP failed); the PnP of result[0] is not repeated
+ *   0 < j < m        merged pose j through the same left_number pruning and iterative PnP: status = the solver's code,
+ *                    R and t NaN when it is non-zero, proposal score = merged[j][1], the 50 unpruned key points
+ *   j >= max(m, 1)   status 1, NaN in R and t, zeros elsewhere (the "no candidate" row)
+ * bp_cands_set_instance_poses: needs a pose solver (error otherwise; switching the solver off switches this off); drops
+ * the graph; on: the frame graph ends in one more launch (bp_cands_kernel_count + 1); d_inst_poses NULL: the object's own
+ * buffer.  bp_cands_instance_poses: device, NULL until switched on. */
+int bp_cands_set_instance_poses(bp_cands* s, int on, double* d_inst_poses);
+double* bp_cands_instance_poses(bp_cands* s);
+/* the instance launch alone, on the outputs of bp_pose_from_candidate_records: d_merged [frames][C][152], d_info [frames][4],
+ * d_poses [frames][166], d_kp3d device [50][3] -> d_inst_poses [frames][C][166]; frames <= 65535 */
+int bp_pose_instances_from_merged(const float* d_merged, const int* d_info, const double* d_poses, int frames, int C,
+                                  const double* d_kp3d, int n_kp, const double* K, int left_number, double* d_inst_poses,
+                                  void* stream);
 
 /* ---- host post-processing (no device work) ---- */
 /* pnp (utils/utils.py:17-41): a restatement of cv2.solvePnP's default SOLVEPNP_ITERATIVE (planar / DLT initialisation,
  * CvLevMarq on (Rodrigues vector, t): <= 20 steps, FLT_EPSILON) followed by cv2.Rodrigues; f64.
  * pts3d [n][3], pts2d [n][2], K [9] row-major; outputs R [9] row-major, t [3].  n >= 6 (>= 4 for a planar model). */
 int bp_solve_pnp(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t);
+/* ... a failed solve reported, not raised: *status = the solver's code (0 solved, -1 too few points, -2 degenerate; R and
+ * t are then not to be read), the codes bp_solve_pnp_batch and the pose rows carry */
+int bp_solve_pnp_status(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t, int* status);
 /* opt-in, NOT what the reference calls: Hartley-conditioned DLT + the same reprojection objective minimised to
  * convergence -- for callers who want the optimum where the raw-DLT start of SOLVEPNP_ITERATIVE lands in a wrong basin
  * (small distant objects).  n >= 6, non-planar. */

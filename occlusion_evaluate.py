@@ -42,6 +42,8 @@ def main():
     args = parse_args()
     if not args.obj_ids:
         return evaluate.main()          # the reference's own protocol: one object per run (--candidates works there)
+    if args.all_instances and not int(args.candidates):
+        raise SystemExit("--all_instances needs --candidates C: the instances are the merged poses of a frame's candidate boxes")
     if int(args.candidates):
         if args.pnp_ransac is not None:
             raise SystemExit("--candidates cannot be combined with --pnp_ransac: the candidate pose tail has no RANSAC variant yet")
@@ -201,7 +203,8 @@ def main():
             write_json(final_result, odir)
             sym = o in symmetric
             m = metrics.evaluate_results(final_result, frames_gt, model, cam, diameter, 20.0, symmetric=sym,
-                                         device=torch.device("cuda", local) if sym else None)
+                                         device=torch.device("cuda", local) if sym else None,
+                                         match_instances=args.all_instances)
             print("Mean add accuracy for seq %02d is: %.3f" % (o, m["mean_add"]))
             if sym:
                 print("Mean add-s accuracy for seq %02d is: %.3f" % (o, m["mean_adds"]))
@@ -209,7 +212,7 @@ def main():
             print("Mean IoU for seq %02d is: %.3f" % (o, m["mean_iou"]))
             if args.bop_metrics:
                 evaluate.print_bop_metrics(args.sixd_base, o, final_result, frames_gt, model, cam, diameter,
-                                           torch.device("cuda", local))
+                                           torch.device("cuda", local), match_instances=args.all_instances)
     bpd.finalize()
 
 
