@@ -48,24 +48,6 @@ inline void allow_big_lds(const void* kernel) {
 // XCDs differ by seconds, so a layer's first-entry -> last-store span cannot be taken from it.)
 __device__ __forceinline__ unsigned long long bp_clock() { return __builtin_amdgcn_s_memrealtime(); }
 
-// camera and damping table of the device PnP (pose_tail.hip): lam[lg + 16] = 10^lg for lg = -16 .. 16, computed on the
-// host with the host solver's own expression so that both minimisers damp by the same numbers
-struct PnpCam {
-    double fx, fy, cx, cy;
-    double lam[33];
-};
-
-// launch arguments of the device RANSAC (pnp_ransac.hip), both filled on the host: the sample indices of up to TRIALS
-// consecutive trials (host_post.cpp pnp_ransac_samples; below 64, so a byte each) and the trials-needed table
-// (pnp_ransac_trials_needed), passed by value so that a launch needs no upload and can be captured in a graph
-struct RansacSamples {
-    static constexpr int TRIALS = 256;
-    unsigned char idx[TRIALS * 6];
-};
-struct RansacNeed {
-    int need[65];
-};
-
 enum Act : int { ACT_LINEAR = 0, ACT_LEAKY = 1, ACT_RELU = 2 };
 
 // where the epilogue puts element (m = (b,oy,ox), n = out channel)

@@ -12,51 +12,7 @@
 
 #include "engine.h"
 #include "frame_io.h"
-
-namespace bp {   // host_post.cpp
-int solve_pnp(const double* P, const double* U, int n, const double* K, double* R, double* t);
-int solve_pnp_refined(const double* P, const double* U, int n, const double* K, double* R, double* t);
-int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, double reproj_err, int max_trials,
-                     double confidence, double* R, double* t, unsigned char* inlier_mask);
-void pnp_ransac_samples(int n, int max_trials, int* idx);
-void pnp_ransac_trials_needed(int n, double confidence, int* need);
-int pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, const float* scores, int n, int K,
-             int* out_pick, float* out_pose, float* out_score, float* out_prop);
-// pose_metrics.hip
-int pose_error_blocks(int n);
-void launch_pose_errors(const double* model, int n, const double* gt, const double* est, int P, const double* K,
-                        int want, double* partial, double* out, hipStream_t s);
-size_t pose_errors_sym_scratch_bytes(int n, int P, int S);
-void launch_pose_errors_sym(const double* model, int n, const double* gt, const double* est, int P, const double* sym,
-                            int S, const double* K, int want, double* scratch, double* out, hipStream_t s);
-// pose_tail.hip
-void launch_solve_pnp_batch(const double* pts3d, int shared_3d, const double* pts2d, int n, int P, const PnpCam& cam,
-                            double* Rt, int* status, hipStream_t s);
-void launch_pose_tail(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
-                      double* poses, hipStream_t s);
-void launch_pose_tail_prepare(const float* records, int batch, const double* kp3d, const PnpCam& cam, int left_number,
-                              double* poses, double* ws3d, double* ws2d, int* active, hipStream_t s);
-// pose_tail_cands.hip
-void launch_pose_tail_cands(const float* records, const int* counts, int frames, int C, const double* kp3d, const PnpCam& cam,
-                            int left_number, double* poses, float* merged, int* info, hipStream_t s);
-// pose_tail_inst.hip
-void launch_pose_instances(const float* merged, const int* info, const double* poses, int frames, int C, const double* kp3d,
-                           const PnpCam& cam, int left_number, double* inst_poses, hipStream_t s);
-// pnp_ransac.hip
-size_t pnp_ransac_workspace_bytes(int P, int max_trials);
-void launch_pnp_ransac(const double* pts3d, size_t stride3d, const double* pts2d, size_t stride2d, const int* active, int n,
-                       int P, const PnpCam& cam, double reproj_err, int max_trials, const int* samples, const int* need,
-                       void* workspace, double* Rt, int* status, unsigned char* inliers, double* poses, hipStream_t s);
-}
-
-// the device PnP's camera: K (host, 3x3 row-major) and the minimiser's damping table 10^lg, lg = -16 .. 16, computed with
-// the expression the host solver uses (host_post.cpp solve_pnp_iterative, step())
-static bp::PnpCam make_pnp_cam(const double* K) {
-    bp::PnpCam c;
-    c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
-    for (int lg = -16; lg <= 16; ++lg) c.lam[lg + 16] = std::exp(lg * std::log(10.0));
-    return c;
-}
+#include "pose_tail.h"
 
 // The RANSAC pose tail: workspace = kept 3-D points [batch][64][3] f64 | kept 2-D points [batch][64][2] f64 | the
 // hypotheses' masks and counts (pnp_ransac_workspace_bytes) | active [batch] i32.  Three launches: prepare (decode, NMS,
@@ -1053,7 +1009,7 @@ int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, co
     }
     p->poses = d_poses ? d_poses : p->own_poses;
     BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    p->cam = make_pnp_cam(K);
+    p->cam = bp::make_pnp_cam(K);
     p->left_number = left_number;
     p->pose_on = true;
     if (p->ransac_trials > 0)   // the RANSAC setting stays; its tables are per point count
@@ -1071,7 +1027,7 @@ int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d
     BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
     BP_CHECK(left_number >= 0, "left_number must be >= 0");
     if (batch == 0) return 0;
-    bp::launch_pose_tail(d_records, batch, d_kp3d, make_pnp_cam(K), left_number, d_poses, (hipStream_t)stream);
+    bp::launch_pose_tail(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
@@ -1086,7 +1042,7 @@ int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, 
     BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
     BP_CHECK(left_number >= 0, "left_number must be >= 0");
     if (frames == 0) return 0;
-    bp::launch_pose_tail_cands(d_records, d_counts, frames, C, d_kp3d, make_pnp_cam(K), left_number, d_poses, d_merged, d_info,
+    bp::launch_pose_tail_cands(d_records, d_counts, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, d_merged, d_info,
                                (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
@@ -1103,7 +1059,7 @@ int bp_pose_instances_from_merged(const float* d_merged, const int* d_info, cons
     BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
     BP_CHECK(left_number >= 0, "left_number must be >= 0");
     if (frames == 0) return 0;
-    bp::launch_pose_instances(d_merged, d_info, d_poses, frames, C, d_kp3d, make_pnp_cam(K), left_number, d_inst_poses,
+    bp::launch_pose_instances(d_merged, d_info, d_poses, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_inst_poses,
                               (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
@@ -1117,7 +1073,7 @@ int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts
     BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_batch: n must be in [0, 64] points per problem");
     BP_CHECK(P >= 0, "P must be >= 0");
     if (P == 0) return 0;
-    bp::launch_solve_pnp_batch(d_pts3d, shared_3d, d_pts2d, n, P, make_pnp_cam(K), d_Rt, d_status, (hipStream_t)stream);
+    bp::launch_solve_pnp_batch(d_pts3d, shared_3d, d_pts2d, n, P, bp::make_pnp_cam(K), d_Rt, d_status, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
@@ -1159,7 +1115,7 @@ int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double
     BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_solve_pnp_ransac_batch: workspace must be 8-byte aligned");
     std::vector<int> samples, need;
     ransac_tables(n, max_trials, confidence, samples, need);
-    bp::launch_pnp_ransac(d_pts3d, shared_3d ? 0 : (size_t)n * 3, d_pts2d, (size_t)n * 2, nullptr, n, P, make_pnp_cam(K), reproj_err,
+    bp::launch_pnp_ransac(d_pts3d, shared_3d ? 0 : (size_t)n * 3, d_pts2d, (size_t)n * 2, nullptr, n, P, bp::make_pnp_cam(K), reproj_err,
                           max_trials, samples.data(), need.data(), d_workspace, d_Rt, d_status, d_inliers, nullptr,
                           (hipStream_t)stream);
     BP_HIP(hipGetLastError());
@@ -1210,7 +1166,7 @@ int bp_pose_from_records_ransac(const float* d_records, int batch, const double*
     BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_pose_from_records_ransac: workspace must be 8-byte aligned");
     std::vector<int> samples, need;
     ransac_tables(left_number < 50 ? left_number : 50, max_trials, confidence, samples, need);
-    pose_tail_ransac(d_records, batch, d_kp3d, make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
+    pose_tail_ransac(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
                      d_poses, d_workspace, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
@@ -1383,7 +1339,7 @@ int bp_scene_set_pose_solver(bp_scene* p, int k, const double* kp3d, int n_kp, c
     }
     sl.poses = d_poses_row ? d_poses_row : p->own_poses + (size_t)k * BP_POSE_DOUBLES;
     BP_HIP(hipMemcpy(sl.kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    sl.cam = make_pnp_cam(K);
+    sl.cam = bp::make_pnp_cam(K);
     sl.left_number = left_number;
     sl.pose_on = true;
     if (sl.ransac_trials > 0)
@@ -1584,7 +1540,7 @@ int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const do
     }
     p->pose = d_pose ? d_pose : p->own_pose;
     BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    p->cam = make_pnp_cam(K);
+    p->cam = bp::make_pnp_cam(K);
     p->left_number = left_number;
     p->pose_on = true;
     return 0;

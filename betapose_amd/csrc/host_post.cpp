@@ -27,6 +27,9 @@
 // restated; the sampler is a fixed-seed LCG so results are reproducible.
 //
 // ---- pose_nms (pPose_nms.py:24-122): the greedy cluster / merge over n candidate poses, f32 like the reference.
+// The arithmetic of O(1) size (Jacobi rotations, polar factor, Rodrigues, the 6x6 solve, one point's projection, the closed
+// forms of the initialisation, the LM step and its tests) is pnp_math.inc, the text the device solver compiles too
+// (pnp_wave.inc); what is here is the loops over the points.  FP contraction is off, as in the device units.
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -34,10 +37,18 @@
 #include <cstring>
 #include <vector>
 
+#include "pose_tail.h"
+
+#pragma clang fp contract(off)
+
 namespace bp {
 
+namespace {
+
+#include "pnp_math.inc"
+
 // cyclic Jacobi for a symmetric n x n matrix (row-major, destroyed); V columns = eigenvectors
-static void jacobi_eig(double* A, int n, double* V, double* w) {
+void jacobi_eig(double* A, int n, double* V, double* w) {
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 100; ++sweep) {
@@ -49,170 +60,29 @@ static void jacobi_eig(double* A, int n, double* V, double* w) {
             for (int q = p + 1; q < n; ++q) {
                 const double apq = A[p * n + q];
                 if (std::fabs(apq) < 1e-300) continue;
-                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[k * n + p], akq = A[k * n + q];
-                    A[k * n + p] = c * akp - s * akq;
-                    A[k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[p * n + k], aqk = A[q * n + k];
-                    A[p * n + k] = c * apk - s * aqk;
-                    A[q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[k * n + p], vkq = V[k * n + q];
-                    V[k * n + p] = c * vkp - s * vkq;
-                    V[k * n + q] = s * vkp + c * vkq;
-                }
+                double c, s;
+                jacobi_rotation(A[p * n + p], A[q * n + q], apq, &c, &s);
+                for (int k = 0; k < n; ++k) jacobi_apply(c, s, &A[k * n + p], &A[k * n + q]);
+                for (int k = 0; k < n; ++k) jacobi_apply(c, s, &A[p * n + k], &A[q * n + k]);
+                for (int k = 0; k < n; ++k) jacobi_apply(c, s, &V[k * n + p], &V[k * n + q]);
             }
     }
     for (int i = 0; i < n; ++i) w[i] = A[i * n + i];
 }
 
-static double det3(const double* M) {
-    return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-}
-static void mul33(const double* A, const double* B, double* C) {
-    double T[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) T[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-    std::memcpy(C, T, sizeof(T));
-}
-
-// U V^T of M's SVD = the orthogonal polar factor M (M^T M)^(-1/2), through the eigen-decomposition of M^T M
-// (det(M) > 0 on every path that calls this, so the factor is a rotation)
-static void polar_rotation(const double* M, double* R) {
-    double MtM[9], V[9], w[3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) MtM[i * 3 + j] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
-    jacobi_eig(MtM, 3, V, w);
-    double S[9] = {0};
-    for (int i = 0; i < 3; ++i) {
-        const double s = std::sqrt(std::max(w[i], 1e-300));
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) S[r * 3 + c] += V[r * 3 + i] * V[c * 3 + i] / s;
-    }
-    mul33(M, S, R);
-}
-
-// Rodrigues vector -> matrix (cvRodrigues2, vector input)
-static void rodrigues_exp(const double* w, double* R) {
-    const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double a, b;
-    if (th < 1e-8) { a = 1.0 - th * th / 6.0; b = 0.5 - th * th / 24.0; }
-    else { a = std::sin(th) / th; b = (1.0 - std::cos(th)) / (th * th); }
-    const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-    double K2[9];
-    mul33(K, K, K2);
-    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * K[i] + b * K2[i];
-}
-
-// rotation matrix -> Rodrigues vector (cvRodrigues2, matrix input; angle in [0, pi])
-static void rodrigues_log(const double* R, double* r) {
-    const double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    const double s = 0.5 * std::sqrt(rx * rx + ry * ry + rz * rz);
-    double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    const double th = std::acos(c);
-    if (s < 1e-5) {
-        if (c > 0) { r[0] = r[1] = r[2] = 0.0; return; }
-        // angle pi: the axis from the diagonal, signs from the off-diagonal sums
-        double t = (R[0] + 1) * 0.5;
-        r[0] = std::sqrt(std::max(t, 0.0));
-        t = (R[4] + 1) * 0.5;
-        r[1] = std::sqrt(std::max(t, 0.0)) * (R[1] < 0 ? -1.0 : 1.0);
-        t = (R[8] + 1) * 0.5;
-        r[2] = std::sqrt(std::max(t, 0.0)) * (R[2] < 0 ? -1.0 : 1.0);
-        if (std::fabs(r[0]) < std::fabs(r[1]) && std::fabs(r[0]) < std::fabs(r[2]) && (R[5] > 0) != (r[1] * r[2] > 0)) r[2] = -r[2];
-        const double nr = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-        for (int i = 0; i < 3; ++i) r[i] *= th / std::max(nr, 1e-300);
-        return;
-    }
-    const double k = th / (2.0 * s);
-    r[0] = rx * k; r[1] = ry * k; r[2] = rz * k;
-}
-
-static bool solve_n(double* A, double* b, int n) {   // Gaussian elimination with partial pivoting, in place
-    for (int c = 0; c < n; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < n; ++r)
-            if (std::fabs(A[r * n + c]) > std::fabs(A[piv * n + c])) piv = r;
-        if (std::fabs(A[piv * n + c]) < 1e-300) return false;
-        if (piv != c) {
-            for (int k = 0; k < n; ++k) std::swap(A[c * n + k], A[piv * n + k]);
-            std::swap(b[c], b[piv]);
-        }
-        for (int r = c + 1; r < n; ++r) {
-            const double f = A[r * n + c] / A[c * n + c];
-            for (int k = c; k < n; ++k) A[r * n + k] -= f * A[c * n + k];
-            b[r] -= f * b[c];
-        }
-    }
-    for (int r = n - 1; r >= 0; --r) {
-        double s = b[r];
-        for (int k = r + 1; k < n; ++k) s -= A[r * n + k] * b[k];
-        b[r] = s / A[r * n + r];
-    }
-    return true;
-}
-
 // cvProjectPoints2 with zero distortion: pixel residuals err = proj - observed and, when J != null, the 2N x 6
-// Jacobian [dp/dr | dp/dt] (r = Rodrigues vector; d(R X)/dr = -R [X]x Jr(r), Jr = right Jacobian of SO(3))
-static void project_residuals(const double* P, const double* U, int n, const double* K, const double* prm, double* err,
-                              double* J) {
-    double R[9];
+// Jacobian [dp/dr | dp/dt] (r = Rodrigues vector)
+void project_residuals(const double* P, const double* U, int n, const PnpCam& cam, const double* prm, double* err, double* J) {
+    double R[9], Jr[9];
     rodrigues_exp(prm, R);
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    double Jr[9];
-    if (J) {
-        const double* w = prm;
-        const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-        double a, b;
-        if (th < 1e-6) { a = 0.5 - th * th / 24.0; b = 1.0 / 6.0 - th * th / 120.0; }
-        else { a = (1.0 - std::cos(th)) / (th * th); b = (th - std::sin(th)) / (th * th * th); }
-        const double Kx[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        double K2[9];
-        mul33(Kx, Kx, K2);
-        for (int i = 0; i < 9; ++i) Jr[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * Kx[i] + b * K2[i];
-    }
-    for (int i = 0; i < n; ++i) {
-        const double* X = P + 3 * i;
-        const double Y0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + prm[3];
-        const double Y1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + prm[4];
-        const double Y2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + prm[5];
-        const double iz = Y2 != 0.0 ? 1.0 / Y2 : 1.0;                      // as OpenCV: z = z ? 1./z : 1
-        err[2 * i] = fx * Y0 * iz + cx - U[2 * i];
-        err[2 * i + 1] = fy * Y1 * iz + cy - U[2 * i + 1];
-        if (!J) continue;
-        // dY/dr = -R [X]x Jr
-        const double Xx[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
-        double T[9], D[9];
-        mul33(R, Xx, T);
-        mul33(T, Jr, D);
-        const double du[3] = {fx * iz, 0, -fx * Y0 * iz * iz};
-        const double dv[3] = {0, fy * iz, -fy * Y1 * iz * iz};
-        double* Ju = J + (2 * i) * 6;
-        double* Jv = J + (2 * i + 1) * 6;
-        for (int c = 0; c < 3; ++c) {
-            Ju[c] = -(du[0] * D[c] + du[1] * D[3 + c] + du[2] * D[6 + c]);
-            Jv[c] = -(dv[0] * D[c] + dv[1] * D[3 + c] + dv[2] * D[6 + c]);
-            Ju[3 + c] = du[c];
-            Jv[3 + c] = dv[c];
-        }
-    }
-}
-
-static double norm_l2(const double* v, int n) {
-    double s = 0;
-    for (int i = 0; i < n; ++i) s += v[i] * v[i];
-    return std::sqrt(s);
+    if (J) right_jacobian(prm, Jr);
+    for (int i = 0; i < n; ++i)
+        project_point(cam, R, Jr, prm, P + 3 * i, U + 2 * i, err + 2 * i, J != nullptr, J ? J + (size_t)(2 * i) * 6 : nullptr,
+                      J ? J + (size_t)(2 * i + 1) * 6 : nullptr);
 }
 
 // homography  m ~ H (x, y, 1)  by the normalised DLT (9x9 normal matrix, smallest eigenvector)
-static bool homography_dlt(const double* xy, const double* m, int n, double* H) {
+bool homography_dlt(const double* xy, const double* m, int n, double* H) {
     double c0[2] = {0, 0}, c1[2] = {0, 0};
     for (int i = 0; i < n; ++i) { c0[0] += xy[2 * i] / n; c0[1] += xy[2 * i + 1] / n; c1[0] += m[2 * i] / n; c1[1] += m[2 * i + 1] / n; }
     double d0 = 0, d1 = 0;
@@ -247,11 +117,10 @@ static bool homography_dlt(const double* xy, const double* m, int n, double* H) 
     return true;
 }
 
-int solve_pnp_iterative(const double* P, const double* U, int n, const double* K, double* Rout, double* tout) {
+int solve_pnp_iterative(const double* P, const double* U, int n, const PnpCam& cam, double* Rout, double* tout) {
     if (n < 4) return -1;
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     std::vector<double> mn(2 * n);
-    for (int i = 0; i < n; ++i) { mn[2 * i] = (U[2 * i] - cx) / fx; mn[2 * i + 1] = (U[2 * i + 1] - cy) / fy; }
+    for (int i = 0; i < n; ++i) { mn[2 * i] = (U[2 * i] - cam.cx) / cam.fx; mn[2 * i + 1] = (U[2 * i + 1] - cam.cy) / cam.fy; }
     // ---- step 2: spread of the model
     double Mc[3] = {0, 0, 0};
     for (int i = 0; i < n; ++i)
@@ -261,51 +130,24 @@ int solve_pnp_iterative(const double* P, const double* U, int n, const double* K
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) MM[a * 3 + b] += (P[3 * i + a] - Mc[a]) * (P[3 * i + b] - Mc[b]);
     double Vm[9], Wm[3];
-    jacobi_eig(MM, 3, Vm, Wm);
-    int ord[3] = {0, 1, 2};
-    std::sort(ord, ord + 3, [&](int a, int b) { return Wm[a] > Wm[b]; });
-    double prm[6];
-    double R[9], t[3];
+    jacobi_small<3>(MM, Vm, Wm);
+    int ord[3];
+    order3_desc(Wm, ord);
+    double prm[6], R[9], t[3];
     if (!(Wm[ord[0]] > 0)) return -2;
-    if (Wm[ord[2]] / std::max(Wm[ord[1]], 1e-300) < 1e-3) {
+    if (Wm[ord[2]] / dmax(Wm[ord[1]], 1e-300) < 1e-3) {
         // ---- planar model: R_transform = V^T (rows = principal directions, the plane normal last)
-        if (n < 4) return -1;
-        double Rt[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Rt[r * 3 + c] = Vm[c * 3 + ord[r]];
-        if (Rt[6] * Rt[6] + Rt[7] * Rt[7] < 1e-10) {
-            const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            std::memcpy(Rt, I, sizeof(I));
-        }
-        if (det3(Rt) < 0)
-            for (int i = 0; i < 9; ++i) Rt[i] = -Rt[i];
-        double Tt[3];
-        for (int r = 0; r < 3; ++r) Tt[r] = -(Rt[r * 3] * Mc[0] + Rt[r * 3 + 1] * Mc[1] + Rt[r * 3 + 2] * Mc[2]);
+        double Rt[9], Tt[3];
+        plane_frame(Vm, ord, Mc, Rt, Tt);
         std::vector<double> xy(2 * n);
         for (int i = 0; i < n; ++i)
             for (int r = 0; r < 2; ++r)
                 xy[2 * i + r] = Rt[r * 3] * P[3 * i] + Rt[r * 3 + 1] * P[3 * i + 1] + Rt[r * 3 + 2] * P[3 * i + 2] + Tt[r];
         double H[9];
         if (homography_dlt(xy.data(), mn.data(), n, H)) {
-            double h1[3] = {H[0], H[3], H[6]}, h2[3] = {H[1], H[4], H[7]}, h3[3] = {H[2], H[5], H[8]};
-            // a homography is defined up to sign: keep the plane in front of the camera
-            const double zc = h3[2];
-            if (zc < 0)
-                for (int k = 0; k < 3; ++k) { h1[k] = -h1[k]; h2[k] = -h2[k]; h3[k] = -h3[k]; }
-            const double n1 = norm_l2(h1, 3), n2 = norm_l2(h2, 3);
-            if (!(n1 > 0) || !(n2 > 0)) return -2;
-            for (int k = 0; k < 3; ++k) { h1[k] /= n1; h2[k] /= n2; t[k] = h3[k] * 2.0 / (n1 + n2); }
-            const double hx[3] = {h1[1] * h2[2] - h1[2] * h2[1], h1[2] * h2[0] - h1[0] * h2[2], h1[0] * h2[1] - h1[1] * h2[0]};
-            double Hm[9] = {h1[0], h2[0], hx[0], h1[1], h2[1], hx[1], h1[2], h2[2], hx[2]};
-            double rv[3], Hp[9];
-            polar_rotation(Hm, Hp);          // cvRodrigues2 orthonormalises a matrix input through its SVD
-            rodrigues_log(Hp, rv);
-            rodrigues_exp(rv, Hm);
-            for (int r = 0; r < 3; ++r) t[r] += Hm[r * 3] * Tt[0] + Hm[r * 3 + 1] * Tt[1] + Hm[r * 3 + 2] * Tt[2];
-            mul33(Hm, Rt, R);
+            if (!homography_pose(H, Rt, Tt, R, t)) return -2;
         } else {
-            const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            std::memcpy(R, I, sizeof(I));
+            identity33(R);
             t[0] = t[1] = t[2] = 0;
         }
     } else {
@@ -325,22 +167,9 @@ int solve_pnp_iterative(const double* P, const double* U, int n, const double* K
         int m = 0;
         for (int i = 1; i < 12; ++i)
             if (w[i] < w[m]) m = i;
-        double RR[9], tt[3];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) RR[r * 3 + c] = V[(r * 4 + c) * 12 + m];
-            tt[r] = V[(r * 4 + 3) * 12 + m];
-        }
-        if (det3(RR) < 0) {
-            for (int i = 0; i < 9; ++i) RR[i] = -RR[i];
-            for (int i = 0; i < 3; ++i) tt[i] = -tt[i];
-        }
-        const double sc = norm_l2(RR, 9);
-        if (!(sc > 0)) return -2;
-        polar_rotation(RR, R);
-        for (int i = 0; i < 3; ++i) t[i] = tt[i] * (std::sqrt(3.0) / sc);
+        if (!dlt_pose(V + m, R, t)) return -2;
     }
-    rodrigues_log(R, prm);
-    prm[3] = t[0]; prm[4] = t[1]; prm[5] = t[2];
+    pose_to_params(R, t, prm);
 
     // ---- CvLevMarq
     const int ne = 2 * n;
@@ -348,18 +177,9 @@ int solve_pnp_iterative(const double* P, const double* U, int n, const double* K
     double prev[6], JtJ[36], JtErr[6];
     int lambdaLg10 = -3, iters = 0;
     double prevErrNorm = 0;
-    auto step = [&]() {
-        const double lambda = std::exp(lambdaLg10 * std::log(10.0));
-        double A[36], d[6];
-        std::memcpy(A, JtJ, sizeof(A));
-        std::memcpy(d, JtErr, sizeof(d));
-        for (int i = 0; i < 6; ++i) A[i * 6 + i] *= 1.0 + lambda;
-        if (!solve_n(A, d, 6)) std::memset(d, 0, sizeof(d));
-        for (int i = 0; i < 6; ++i) prm[i] = prev[i] - d[i];
-    };
     for (;;) {
         // CALC_J at the current parameters
-        project_residuals(P, U, n, K, prm, err.data(), J.data());
+        project_residuals(P, U, n, cam, prm, err.data(), J.data());
         std::memset(JtJ, 0, sizeof(JtJ));
         std::memset(JtErr, 0, sizeof(JtErr));
         for (int e = 0; e < ne; ++e)
@@ -369,57 +189,30 @@ int solve_pnp_iterative(const double* P, const double* U, int n, const double* K
             }
         std::memcpy(prev, prm, sizeof(prev));
         if (iters == 0) prevErrNorm = norm_l2(err.data(), ne);
-        step();
         // CHECK_ERR
         double errNorm;
-        for (;;) {
-            project_residuals(P, U, n, K, prm, err.data(), nullptr);
+        do {
+            lm_step(JtJ, JtErr, cam.lam[lambdaLg10 + 16], prev, prm);
+            project_residuals(P, U, n, cam, prm, err.data(), nullptr);
             errNorm = norm_l2(err.data(), ne);
-            if (errNorm > prevErrNorm && ++lambdaLg10 <= 16) { step(); continue; }
-            break;
-        }
-        lambdaLg10 = std::max(lambdaLg10 - 1, -16);
-        double dn = 0;
-        for (int i = 0; i < 6; ++i) dn += (prm[i] - prev[i]) * (prm[i] - prev[i]);
-        const double rel = std::sqrt(dn) / std::max(norm_l2(prev, 6), DBL_MIN);
-        if (++iters >= 20 || rel < (double)FLT_EPSILON) break;
+        } while (lm_retry(errNorm, prevErrNorm, &lambdaLg10));
+        lambdaLg10 = lm_relax(lambdaLg10);
+        if (++iters >= 20 || lm_converged(prm, prev)) break;
         prevErrNorm = errNorm;
     }
-    rodrigues_exp(prm, Rout);          // cv2.Rodrigues(R_exp)
-    tout[0] = prm[3]; tout[1] = prm[4]; tout[2] = prm[5];
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(Rout[i])) return -2;
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(tout[i])) return -2;
-    return 0;
+    return params_to_pose(prm, Rout, tout);
 }
 
-// nearest rotation to M (polar decomposition through the eigen-decomposition of M^T M)
-static void nearest_rotation(const double* M, double* R) {
-    double MtM[9], V[9], w[3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) MtM[i * 3 + j] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
-    jacobi_eig(MtM, 3, V, w);
-    // U = M V S^-1 ; R = U V^T = M V S^-1 V^T
-    double S[9] = {0};
-    for (int i = 0; i < 3; ++i) {
-        const double s = std::sqrt(std::max(w[i], 1e-300));
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) S[r * 3 + c] += V[r * 3 + i] * V[c * 3 + i] / s;
-    }
-    mul33(M, S, R);
+// nearest rotation to M: the polar factor, with the direction of least stretch flipped when that factor is a reflection
+void nearest_rotation(const double* M, double* R) {
+    double V[9], w[3];
+    polar_eig(M, V, w);
+    polar_factor(M, V, w, -1, R);
     if (det3(R) < 0) {
-        // flip the direction of least stretch
         int m = 0;
         for (int i = 1; i < 3; ++i)
             if (w[i] < w[m]) m = i;
-        double S2[9] = {0};
-        for (int i = 0; i < 3; ++i) {
-            const double s = std::sqrt(std::max(w[i], 1e-300)) * (i == m ? -1.0 : 1.0);
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) S2[r * 3 + c] += V[r * 3 + i] * V[c * 3 + i] / s;
-        }
-        mul33(M, S2, R);
+        polar_factor(M, V, w, m, R);
     }
 }
 
@@ -428,7 +221,7 @@ static void nearest_rotation(const double* M, double* R) {
 // reprojection objective minimised to convergence (left-multiplicative LM).  Not what the reference calls; offered
 // because the raw-DLT initialisation of SOLVEPNP_ITERATIVE lands in a wrong basin on a measurable share of noisy
 // inputs.
-static double reproj_cost(const double* P, const double* U, int n, const double* K, const double* R, const double* t,
+double reproj_cost(const double* P, const double* U, int n, const double* K, const double* R, const double* t,
                           double* res) {
     double c = 0;
     for (int i = 0; i < n; ++i) {
@@ -444,6 +237,8 @@ static double reproj_cost(const double* P, const double* U, int n, const double*
     }
     return c;
 }
+
+}  // namespace
 
 int solve_pnp_refined(const double* P, const double* U, int n, const double* K, double* Rout, double* tout) {
     if (n < 6) return -1;
@@ -531,7 +326,7 @@ int solve_pnp_refined(const double* P, const double* U, int n, const double* K, 
             double A[36], d[6];
             for (int i = 0; i < 36; ++i) A[i] = JtJ[i];
             for (int i = 0; i < 6; ++i) { A[i * 6 + i] *= (1.0 + lambda); d[i] = -Jtr[i]; }
-            if (!solve_n(A, d, 6)) { lambda *= 10; continue; }
+            if (!solve6(A, d)) { lambda *= 10; continue; }
             double dR[9], Rn[9], tn[3];
             rodrigues_exp(d, dR);
             mul33(dR, R, Rn);
@@ -564,7 +359,7 @@ int solve_pnp_refined(const double* P, const double* U, int n, const double* K, 
 
 // kept name of the C-ABI's worker
 int solve_pnp(const double* P, const double* U, int n, const double* K, double* Rout, double* tout) {
-    return solve_pnp_iterative(P, U, n, K, Rout, tout);
+    return solve_pnp_iterative(P, U, n, make_pnp_cam(K), Rout, tout);
 }
 
 // The RANSAC sampler: max_trials rows of six distinct indices below n, drawn with a 64-bit LCG from a fixed seed (so a
@@ -608,9 +403,10 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
                      double confidence, double* Rout, double* tout, unsigned char* inlier_mask) {
     const int MS = 6;                                   // sample size: the DLT initialiser needs 6 points
     if (n < MS) return -1;
+    const PnpCam cam = make_pnp_cam(K);
     if (n == MS) {
         if (inlier_mask) std::memset(inlier_mask, 1, n);
-        return solve_pnp_iterative(P, U, n, K, Rout, tout);
+        return solve_pnp_iterative(P, U, n, cam, Rout, tout);
     }
     std::vector<unsigned char> best(n, 0), cur(n);
     int best_cnt = 0, trials = std::max(1, max_trials);
@@ -625,10 +421,9 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
             std::memcpy(&sp[3 * k], P + 3 * idx[k], 3 * sizeof(double));
             std::memcpy(&su[2 * k], U + 2 * idx[k], 2 * sizeof(double));
         }
-        if (solve_pnp_iterative(sp.data(), su.data(), MS, K, R, t) != 0) continue;
-        rodrigues_log(R, prm);
-        prm[3] = t[0]; prm[4] = t[1]; prm[5] = t[2];
-        project_residuals(P, U, n, K, prm, err.data(), nullptr);
+        if (solve_pnp_iterative(sp.data(), su.data(), MS, cam, R, t) != 0) continue;
+        pose_to_params(R, t, prm);
+        project_residuals(P, U, n, cam, prm, err.data(), nullptr);
         int cnt = 0;
         for (int i = 0; i < n; ++i) {
             cur[i] = err[2 * i] * err[2 * i] + err[2 * i + 1] * err[2 * i + 1] <= reproj_err * reproj_err;
@@ -648,7 +443,7 @@ int solve_pnp_ransac(const double* P, const double* U, int n, const double* K, d
             iu.insert(iu.end(), U + 2 * i, U + 2 * i + 2);
         }
     if (inlier_mask) std::memcpy(inlier_mask, best.data(), n);
-    return solve_pnp_iterative(ip.data(), iu.data(), best_cnt, K, Rout, tout);
+    return solve_pnp_iterative(ip.data(), iu.data(), best_cnt, cam, Rout, tout);
 }
 
 // ------------------------------------------------------------------------------------------------ pose NMS (f32)

@@ -15,6 +15,7 @@
 // pnp_wave's and project_residuals', in the host's operation order without FMA contraction; the inlier test is written
 // as the host writes it.  No atomics: each (problem, trial) owns its workspace slot.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -61,8 +62,7 @@ __global__ __launch_bounds__(64) void pnp_ransac_hypothesis_kernel(const double*
     const int rc = pnp_wave(sh, RS_MS, cam, R, t);
     unsigned long long mask = 0;
     if (rc == 0) {                         // (a failed hypothesis counts as no inliers: the host's `continue`)
-        rodrigues_log(R, prm);
-        prm[3] = t[0]; prm[4] = t[1]; prm[5] = t[2];
+        pose_to_params(R, t, prm);
         wsync();
         if (lane < n) {
 #pragma unroll
@@ -87,7 +87,8 @@ __global__ __launch_bounds__(64) void pnp_ransac_hypothesis_kernel(const double*
 
 // ---- 2. the host's loop over the counts, then the refit on the winner's inliers.
 // Rt [P][12] / status [P] / inliers [P][n] (may be null): the batch form.  poses (non-null): the pose-tail form, which
-// writes slots 0, 2..13 and 15 of the frame's pose row instead (the prepare launch wrote the others).
+// writes slots 0 (status), 2..13 (R, t) and 15 (inlier set) of the frame's pose row instead: a partial write of the layout
+// that write_pose_row (pose_decode.inc) documents; the prepare launch wrote the whole row through it.
 __global__ __launch_bounds__(64) void pnp_ransac_select_kernel(const double* __restrict__ pts3d, size_t stride3d,
                                                                 const double* __restrict__ pts2d, size_t stride2d,
                                                                 const int* __restrict__ active, int n, PnpCam cam,

@@ -1,13 +1,11 @@
-// The wave64 PnP shared by the device pose tail (pose_tail.hip) and the device RANSAC (pnp_ransac.hip): pnp_wave, the
-// twin of solve_pnp_iterative of host_post.cpp in the host's operation order, with its helpers (project_residuals,
-// rodrigues_exp / rodrigues_log, the cyclic Jacobi solvers).  Included inside `namespace bp { namespace {` of a unit
-// that has `#pragma clang fp contract(off)` in force; the numerical contract and the wave layout are described at the
-// top of pose_tail.hip.
+// The wave64 PnP shared by the device pose tails (pose_tail.hip, pose_tail_cands.hip, pose_tail_inst.hip) and the device
+// RANSAC (pnp_ransac.hip): pnp_wave, which is solve_pnp_iterative of host_post.cpp with the loops over the points spread
+// over the lanes.  Everything of O(1) size is pnp_math.inc, the same text the host compiles; what is here is what differs
+// by nature: the LDS arrays, the lane-per-accumulator sums in the host's order and the wave-parallel Jacobi.  Included
+// inside `namespace bp { namespace {` of a unit that includes pose_tail.h and has `#pragma clang fp contract(off)` in
+// force; the numerical contract and the wave layout are described at the top of pose_tail.hip.
 
-constexpr int PT_MAXN = 64;            // points per problem (one per lane)
-constexpr int PT_K = 50;               // key points per frame record
-constexpr int PT_REC = 316;            // BP_RESULT_FLOATS
-constexpr int PT_POSE = 166;           // BP_POSE_DOUBLES
+#include "pnp_math.inc"
 
 struct PnpShared {
     double P[PT_MAXN * 3], U[PT_MAXN * 2], mn[PT_MAXN * 2], xy[PT_MAXN * 2];
@@ -17,170 +15,8 @@ struct PnpShared {
 };
 
 __device__ __forceinline__ void wsync() { __syncthreads(); }   // the workgroup is one wave
-__device__ __forceinline__ double dmax(double a, double b) { return a < b ? b : a; }   // std::max
 __device__ __forceinline__ float fmaxs(float a, float b) { return a < b ? b : a; }      // std::max
 __device__ __forceinline__ float fmins(float a, float b) { return b < a ? b : a; }      // std::min
-
-// ---------------------------------------------------------------- O(1) pieces, every lane redundantly (registers)
-template <int N>
-__device__ void jacobi_small(double* A, double* V, double* w) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) V[i * N + j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0.0;
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-#pragma unroll
-            for (int j = i + 1; j < N; ++j) off += A[i * N + j] * A[i * N + j];
-        if (off < 1e-300) break;
-#pragma unroll
-        for (int p = 0; p < N; ++p)
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = A[p * N + q];
-                if (fabs(apq) < 1e-300) continue;
-                const double theta = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-                    const double akp = A[k * N + p], akq = A[k * N + q];
-                    A[k * N + p] = c * akp - s * akq;
-                    A[k * N + q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-                    const double apk = A[p * N + k], aqk = A[q * N + k];
-                    A[p * N + k] = c * apk - s * aqk;
-                    A[q * N + k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-                    const double vkp = V[k * N + p], vkq = V[k * N + q];
-                    V[k * N + p] = c * vkp - s * vkq;
-                    V[k * N + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) w[i] = A[i * N + i];
-}
-
-__device__ __forceinline__ double det3(const double* M) {
-    return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-}
-__device__ __forceinline__ void mul33(const double* A, const double* B, double* C) {
-    double T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) T[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) C[i] = T[i];
-}
-
-__device__ void polar_rotation(const double* M, double* R) {
-    double MtM[9], V[9], w[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) MtM[i * 3 + j] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
-    jacobi_small<3>(MtM, V, w);
-    double S[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) S[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double s = sqrt(dmax(w[i], 1e-300));
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) S[r * 3 + c] += V[r * 3 + i] * V[c * 3 + i] / s;
-    }
-    mul33(M, S, R);
-}
-
-__device__ void rodrigues_exp(const double* w, double* R) {
-    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double a, b;
-    if (th < 1e-8) { a = 1.0 - th * th / 6.0; b = 0.5 - th * th / 24.0; }
-    else { a = sin(th) / th; b = (1.0 - cos(th)) / (th * th); }
-    const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-    double K2[9];
-    mul33(K, K, K2);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * K[i] + b * K2[i];
-}
-
-__device__ void rodrigues_log(const double* R, double* r) {
-    const double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    const double s = 0.5 * sqrt(rx * rx + ry * ry + rz * rz);
-    double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    const double th = acos(c);
-    if (s < 1e-5) {
-        if (c > 0) { r[0] = r[1] = r[2] = 0.0; return; }
-        double t = (R[0] + 1) * 0.5;
-        r[0] = sqrt(dmax(t, 0.0));
-        t = (R[4] + 1) * 0.5;
-        r[1] = sqrt(dmax(t, 0.0)) * (R[1] < 0 ? -1.0 : 1.0);
-        t = (R[8] + 1) * 0.5;
-        r[2] = sqrt(dmax(t, 0.0)) * (R[2] < 0 ? -1.0 : 1.0);
-        if (fabs(r[0]) < fabs(r[1]) && fabs(r[0]) < fabs(r[2]) && (R[5] > 0) != (r[1] * r[2] > 0)) r[2] = -r[2];
-        const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) r[i] *= th / dmax(nr, 1e-300);
-        return;
-    }
-    const double k = th / (2.0 * s);
-    r[0] = rx * k; r[1] = ry * k; r[2] = rz * k;
-}
-
-// Gaussian elimination with partial pivoting on the 6x6 damped system (host solve_n); the row swap is written as
-// selects so that the arrays stay in registers
-__device__ bool solve6(double* A, double* b) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        int piv = c;
-        double best = fabs(A[c * 6 + c]);
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            const double v = fabs(A[r * 6 + c]);
-            if (v > best) { piv = r; best = v; }
-        }
-        if (best < 1e-300) return false;
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            if (r != piv) continue;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) { const double x = A[c * 6 + k]; A[c * 6 + k] = A[r * 6 + k]; A[r * 6 + k] = x; }
-            const double x = b[c]; b[c] = b[r]; b[r] = x;
-        }
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            const double f = A[r * 6 + c] / A[c * 6 + c];
-#pragma unroll
-            for (int k = c; k < 6; ++k) A[r * 6 + k] -= f * A[c * 6 + k];
-            b[r] -= f * b[c];
-        }
-    }
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {
-        double s = b[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; ++k) s -= A[r * 6 + k] * b[k];
-        b[r] = s / A[r * 6 + r];
-    }
-    return true;
-}
-
-__device__ double norm_l2_lds(const double* v, int n) {
-    double s = 0;
-    for (int i = 0; i < n; ++i) s += v[i] * v[i];
-    return sqrt(s);
-}
 
 // ---------------------------------------------------------------- wave-parallel pieces (LDS)
 // cyclic Jacobi of the symmetric n x n matrix sh.A (n <= 12), eigenvectors in the columns of sh.V, eigenvalues in w
@@ -198,28 +34,13 @@ __device__ void jacobi_wave(PnpShared& sh, int n, double* w) {
             for (int q = p + 1; q < n; ++q) {
                 const double apq = sh.A[p * n + q];
                 if (fabs(apq) < 1e-300) continue;
-                const double theta = (sh.A[q * n + q] - sh.A[p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                double c, s;
+                jacobi_rotation(sh.A[p * n + p], sh.A[q * n + q], apq, &c, &s);
                 wsync();
-                if (lane < n) {                       // columns p, q of row k
-                    const int k = lane;
-                    const double akp = sh.A[k * n + p], akq = sh.A[k * n + q];
-                    sh.A[k * n + p] = c * akp - s * akq;
-                    sh.A[k * n + q] = s * akp + c * akq;
-                } else if (lane >= 32 && lane - 32 < n) {   // eigenvector columns p, q of row k
-                    const int k = lane - 32;
-                    const double vkp = sh.V[k * n + p], vkq = sh.V[k * n + q];
-                    sh.V[k * n + p] = c * vkp - s * vkq;
-                    sh.V[k * n + q] = s * vkp + c * vkq;
-                }
+                if (lane < n) jacobi_apply(c, s, &sh.A[lane * n + p], &sh.A[lane * n + q]);                 // columns p, q of row k
+                else if (lane >= 32 && lane - 32 < n) jacobi_apply(c, s, &sh.V[(lane - 32) * n + p], &sh.V[(lane - 32) * n + q]);
                 wsync();
-                if (lane < n) {                       // rows p, q of column k
-                    const int k = lane;
-                    const double apk = sh.A[p * n + k], aqk = sh.A[q * n + k];
-                    sh.A[p * n + k] = c * apk - s * aqk;
-                    sh.A[q * n + k] = s * apk + c * aqk;
-                }
+                if (lane < n) jacobi_apply(c, s, &sh.A[p * n + lane], &sh.A[q * n + lane]);                 // rows p, q of column k
                 wsync();
             }
     }
@@ -229,48 +50,11 @@ __device__ void jacobi_wave(PnpShared& sh, int n, double* w) {
 // cvProjectPoints2, zero distortion: err = proj - observed (sh.err); with_j: the 2n x 6 Jacobian (sh.J).  Lane i = point i.
 __device__ void project_residuals(PnpShared& sh, int n, const PnpCam& cam, const double* prm, bool with_j) {
     const int i = threadIdx.x;
-    double R[9];
+    double R[9], Jr[9];
     rodrigues_exp(prm, R);
-    const double fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
-    double Jr[9];
-    if (with_j) {
-        const double* w = prm;
-        const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-        double a, b;
-        if (th < 1e-6) { a = 0.5 - th * th / 24.0; b = 1.0 / 6.0 - th * th / 120.0; }
-        else { a = (1.0 - cos(th)) / (th * th); b = (th - sin(th)) / (th * th * th); }
-        const double Kx[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        double K2[9];
-        mul33(Kx, Kx, K2);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Jr[e] = (e % 4 == 0 ? 1.0 : 0.0) - a * Kx[e] + b * K2[e];
-    }
-    if (i < n) {
-        const double X[3] = {sh.P[3 * i], sh.P[3 * i + 1], sh.P[3 * i + 2]};
-        const double Y0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + prm[3];
-        const double Y1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + prm[4];
-        const double Y2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + prm[5];
-        const double iz = Y2 != 0.0 ? 1.0 / Y2 : 1.0;
-        sh.err[2 * i] = fx * Y0 * iz + cx - sh.U[2 * i];
-        sh.err[2 * i + 1] = fy * Y1 * iz + cy - sh.U[2 * i + 1];
-        if (with_j) {
-            const double Xx[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
-            double T[9], D[9];
-            mul33(R, Xx, T);
-            mul33(T, Jr, D);
-            const double du[3] = {fx * iz, 0, -fx * Y0 * iz * iz};
-            const double dv[3] = {0, fy * iz, -fy * Y1 * iz * iz};
-            double* Ju = sh.J + (2 * i) * 6;
-            double* Jv = sh.J + (2 * i + 1) * 6;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                Ju[c] = -(du[0] * D[c] + du[1] * D[3 + c] + du[2] * D[6 + c]);
-                Jv[c] = -(dv[0] * D[c] + dv[1] * D[3 + c] + dv[2] * D[6 + c]);
-                Ju[3 + c] = du[c];
-                Jv[3 + c] = dv[c];
-            }
-        }
-    }
+    if (with_j) right_jacobian(prm, Jr);
+    if (i < n)
+        project_point(cam, R, Jr, prm, sh.P + 3 * i, sh.U + 2 * i, sh.err + 2 * i, with_j, sh.J + (2 * i) * 6, sh.J + (2 * i + 1) * 6);
     wsync();
 }
 
@@ -356,31 +140,15 @@ __device__ int pnp_wave(PnpShared& sh, int n, const PnpCam& cam, double* Rout, d
 #pragma unroll
     for (int e = 0; e < 9; ++e) MM[e] = sh.A[e];
     jacobi_small<3>(MM, Vm, Wm);
-    int ord[3] = {0, 1, 2};           // std::sort of three: insertion sort, descending
-    for (int i = 1; i < 3; ++i) {
-        const int v = ord[i];
-        int j = i;
-        while (j > 0 && Wm[v] > Wm[ord[j - 1]]) { ord[j] = ord[j - 1]; --j; }
-        ord[j] = v;
-    }
+    int ord[3];
+    order3_desc(Wm, ord);
     double prm[6], R[9], t[3];
     if (!(Wm[ord[0]] > 0)) return -2;
     wsync();                           // sh.A is rewritten below
     if (Wm[ord[2]] / dmax(Wm[ord[1]], 1e-300) < 1e-3) {
         // ---- planar model
-        double Rt[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Rt[r * 3 + c] = Vm[c * 3 + ord[r]];
-        if (Rt[6] * Rt[6] + Rt[7] * Rt[7] < 1e-10) {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) Rt[e] = e % 4 == 0 ? 1.0 : 0.0;
-        }
-        if (det3(Rt) < 0)
-#pragma unroll
-            for (int e = 0; e < 9; ++e) Rt[e] = -Rt[e];
-        double Tt[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) Tt[r] = -(Rt[r * 3] * Mc[0] + Rt[r * 3 + 1] * Mc[1] + Rt[r * 3 + 2] * Mc[2]);
+        double Rt[9], Tt[3];
+        plane_frame(Vm, ord, Mc, Rt, Tt);
         if (lane < n)
 #pragma unroll
             for (int r = 0; r < 2; ++r)
@@ -389,28 +157,9 @@ __device__ int pnp_wave(PnpShared& sh, int n, const PnpCam& cam, double* Rout, d
         wsync();
         double H[9];
         if (homography_dlt(sh, n, H)) {
-            double h1[3] = {H[0], H[3], H[6]}, h2[3] = {H[1], H[4], H[7]}, h3[3] = {H[2], H[5], H[8]};
-            const double zc = h3[2];
-            if (zc < 0)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { h1[k] = -h1[k]; h2[k] = -h2[k]; h3[k] = -h3[k]; }
-            const double n1 = sqrt(h1[0] * h1[0] + h1[1] * h1[1] + h1[2] * h1[2]);
-            const double n2 = sqrt(h2[0] * h2[0] + h2[1] * h2[1] + h2[2] * h2[2]);
-            if (!(n1 > 0) || !(n2 > 0)) return -2;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { h1[k] /= n1; h2[k] /= n2; t[k] = h3[k] * 2.0 / (n1 + n2); }
-            const double hx[3] = {h1[1] * h2[2] - h1[2] * h2[1], h1[2] * h2[0] - h1[0] * h2[2], h1[0] * h2[1] - h1[1] * h2[0]};
-            double Hm[9] = {h1[0], h2[0], hx[0], h1[1], h2[1], hx[1], h1[2], h2[2], hx[2]};
-            double rv[3], Hp[9];
-            polar_rotation(Hm, Hp);
-            rodrigues_log(Hp, rv);
-            rodrigues_exp(rv, Hm);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) t[r] += Hm[r * 3] * Tt[0] + Hm[r * 3 + 1] * Tt[1] + Hm[r * 3 + 2] * Tt[2];
-            mul33(Hm, Rt, R);
+            if (!homography_pose(H, Rt, Tt, R, t)) return -2;
         } else {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) R[e] = e % 4 == 0 ? 1.0 : 0.0;
+            identity33(R);
             t[0] = t[1] = t[2] = 0;
         }
     } else {
@@ -432,28 +181,9 @@ __device__ int pnp_wave(PnpShared& sh, int n, const PnpCam& cam, double* Rout, d
         int m = 0;
         for (int i = 1; i < 12; ++i)
             if (w[i] < w[m]) m = i;
-        double RR[9], tt[3];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) RR[r * 3 + c] = sh.V[(r * 4 + c) * 12 + m];
-            tt[r] = sh.V[(r * 4 + 3) * 12 + m];
-        }
-        if (det3(RR) < 0) {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) RR[e] = -RR[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) tt[e] = -tt[e];
-        }
-        double sc = 0;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) sc += RR[e] * RR[e];
-        sc = sqrt(sc);
-        if (!(sc > 0)) return -2;
-        polar_rotation(RR, R);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) t[e] = tt[e] * (sqrt(3.0) / sc);
+        if (!dlt_pose(sh.V + m, R, t)) return -2;
     }
-    rodrigues_log(R, prm);
-    prm[3] = t[0]; prm[4] = t[1]; prm[5] = t[2];
+    pose_to_params(R, t, prm);
 
     // ---- CvLevMarq
     const int ne = 2 * n;
@@ -475,46 +205,19 @@ __device__ int pnp_wave(PnpShared& sh, int n, const PnpCam& cam, double* Rout, d
         wsync();
 #pragma unroll
         for (int i = 0; i < 6; ++i) prev[i] = prm[i];
-        if (iters == 0) prevErrNorm = norm_l2_lds(sh.err, ne);
+        if (iters == 0) prevErrNorm = norm_l2(sh.err, ne);
         double errNorm;
-        for (;;) {
-            // step(): (JtJ with its diagonal scaled by 1 + lambda) d = JtErr, param = previous - d
-            const double lambda = cam.lam[lambdaLg10 + 16];
-            double A[36], d[6];
-#pragma unroll
-            for (int e = 0; e < 36; ++e) A[e] = sh.JtJ[e];
-#pragma unroll
-            for (int e = 0; e < 6; ++e) d[e] = sh.JtErr[e];
-#pragma unroll
-            for (int e = 0; e < 6; ++e) A[e * 6 + e] *= 1.0 + lambda;
-            if (!solve6(A, d))
-#pragma unroll
-                for (int e = 0; e < 6; ++e) d[e] = 0.0;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) prm[e] = prev[e] - d[e];
+        do {
+            lm_step(sh.JtJ, sh.JtErr, cam.lam[lambdaLg10 + 16], prev, prm);
             wsync();                     // sh.err is rewritten
             project_residuals(sh, n, cam, prm, false);
-            errNorm = norm_l2_lds(sh.err, ne);
-            if (errNorm > prevErrNorm && ++lambdaLg10 <= 16) continue;
-            break;
-        }
-        lambdaLg10 = lambdaLg10 - 1 < -16 ? -16 : lambdaLg10 - 1;
-        double dn = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dn += (prm[i] - prev[i]) * (prm[i] - prev[i]);
-        double pn = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) pn += prev[i] * prev[i];
-        const double rel = sqrt(dn) / dmax(sqrt(pn), 2.2250738585072014e-308);
+            errNorm = norm_l2(sh.err, ne);
+        } while (lm_retry(errNorm, prevErrNorm, &lambdaLg10));
+        lambdaLg10 = lm_relax(lambdaLg10);
+        const bool stop = lm_converged(prm, prev);
         wsync();                         // sh.J / sh.err / sh.JtJ are rewritten by the next iteration
-        if (++iters >= 20 || rel < (double)1.19209290e-07F) break;
+        if (++iters >= 20 || stop) break;
         prevErrNorm = errNorm;
     }
-    rodrigues_exp(prm, Rout);
-    tout[0] = prm[3]; tout[1] = prm[4]; tout[2] = prm[5];
-    for (int i = 0; i < 9; ++i)
-        if (!isfinite(Rout[i])) return -2;
-    for (int i = 0; i < 3; ++i)
-        if (!isfinite(tout[i])) return -2;
-    return 0;
+    return params_to_pose(prm, Rout, tout);
 }

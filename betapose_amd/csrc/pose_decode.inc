@@ -1,6 +1,6 @@
-// Pieces of the device pose tail shared by pose_tail.hip (one candidate per frame) and pose_tail_cands.hip (several):
-// the key-point decode and the left_number pruning.  Included inside `namespace bp { namespace {` after pnp_wave.inc, in a
-// unit that has `#pragma clang fp contract(off)` in force.
+// Pieces shared by the device pose tails (pose_tail.hip, pose_tail_cands.hip, pose_tail_inst.hip): the key-point decode,
+// the scan and filters of a merged pose, the left_number pruning and the writers of the pose row.  Included inside
+// `namespace bp { namespace {` after pnp_wave.inc, in a unit that has `#pragma clang fp contract(off)` in force.
 
 __device__ __forceinline__ float sign_np(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : (v == 0.f ? 0.f : v)); }
 __device__ __forceinline__ float max_np(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a >= b ? a : b)); }
@@ -69,4 +69,47 @@ __device__ __forceinline__ int prune_and_compact(PnpShared& sh, const float* kx,
     }
     wsync();
     return cnt;
+}
+
+// the end of pose_nms for one merged pose x / y / s [PT_K] (host_post.cpp, pPose_nms.py:85-110): max and sum of the scores,
+// bounding box, the score and area filters; the same sequential scan on every lane.  false: the pose is dropped.
+__device__ __forceinline__ bool merged_pose_scan(const float* x, const float* y, const float* s, float* ssum_out, float* smax_out) {
+    float smax = -HUGE_VALF, ssum = 0.f, xmin = HUGE_VALF, xmax = -HUGE_VALF, ymin = HUGE_VALF, ymax = -HUGE_VALF;
+    for (int k = 0; k < PT_K; ++k) {
+        smax = fmaxs(smax, s[k]); ssum += s[k];
+        xmin = fmins(xmin, x[k]); xmax = fmaxs(xmax, x[k]);
+        ymin = fmins(ymin, y[k]); ymax = fmaxs(ymax, y[k]);
+    }
+    *ssum_out = ssum;
+    *smax_out = smax;
+    return !(smax < 0.3f) && !(1.5f * 1.5f * (xmax - xmin) * (ymax - ymin) < 0.f);
+}
+__device__ __forceinline__ float proposal_score(float ssum, float smax, float box_score) {
+    return ssum / (float)PT_K + box_score + 1.25f * smax;
+}
+
+// ---- the pose row [PT_POSE] f64 (include/betapose_hip.h BP_POSE_DOUBLES): 0 status, 1 points kept, 2..10 R, 11..13 t
+// (NaN unless status 0), 14 proposal score, 15 RANSAC inlier set (0 here), 16.. the 50 key points (x, y, score).
+// pnp_ransac.hip's select kernel rewrites slots 0, 2..13 and 15 of a row that the prepare launch wrote through here.
+__device__ __forceinline__ void write_pose_row(double* __restrict__ out, int lane, int rc, int cnt, const double* R, const double* t,
+                                               float prop, const float* kx, const float* ky, const float* ks) {
+    const double qnan = __builtin_nan("");
+    for (int e = lane; e < PT_POSE; e += 64) {
+        double v;
+        if (e == 0) v = rc;
+        else if (e == 1) v = cnt;
+        else if (e < 11) v = rc == 0 ? R[e - 2] : qnan;
+        else if (e < 14) v = rc == 0 ? t[e - 11] : qnan;
+        else if (e == 14) v = prop;
+        else if (e == 15) v = 0.0;
+        else {
+            const int k = (e - 16) / 3, c = (e - 16) % 3;
+            v = c == 0 ? kx[k] : (c == 1 ? ky[k] : ks[k]);
+        }
+        out[e] = v;
+    }
+}
+// a row without a pose: status 1 (no detection / no candidate) or 2 (dropped by pPose-NMS), NaN in R and t, zeros elsewhere
+__device__ __forceinline__ void write_status_row(double* __restrict__ out, int lane, int status) {
+    for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? (double)status : ((e >= 2 && e < 14) ? __builtin_nan("") : 0.0);
 }

@@ -11,6 +11,7 @@
 // query.  ADD and 2-D ride along (O(n) per pose).  Sums are deterministic: per thread in query order, wave tree, waves
 // in order, one partial per (pose, block); pose_errors_finish adds a pose's partials in block order.  No atomics.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 namespace bp {
 

@@ -22,6 +22,7 @@
 // Pads: tile slots past n hold vertex 0 (a real vertex cannot change the maximum it is already part of); lanes past S
 // compute symmetry 0 and write nothing; a wave whose 64 symmetries all lie past S only helps staging the tiles.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 namespace bp {
 

@@ -4,19 +4,21 @@
 //   a. key-point decode, f32 -- eval.decode_keypoints (KPD/src/utils/eval.py:113-147, img.py:216-239) op for op
 //   b. pPose-NMS at n = 1, f32 -- the n == 1 path of bp::pose_nms (host_post.cpp, pPose_nms.py:24-122)
 //   c. pruning to left_number key points: the first minimum goes each time (np.argmin + np.delete, dataloader.py:718-722)
-//   d. PnP, f64 -- solve_pnp_iterative of host_post.cpp in the host's operation order (utils/utils.py:17-41)
+//   d. PnP, f64 -- solve_pnp_iterative of host_post.cpp (utils/utils.py:17-41): its O(1) arithmetic is the very text the
+//      host compiles (pnp_math.inc), its sums over the points run in the host's order (pnp_wave.inc)
 //
-// Numerical contract: no FMA contraction (the x86 host has none), every sum accumulates in the host's order, and the
-// eigen-solvers are the host's cyclic Jacobi with the same rotation order.  Only the transcendental functions (sin, cos,
-// acos, hypot) may round differently from the host's libm; lambda = 10^lg of the minimiser comes from a table the host
-// computes with the host solver's own expression.  So decode / NMS / pruning are bit-identical to the host and R, t
-// agree to the rounding that the minimiser's FLT_EPSILON stop leaves.
+// Numerical contract: no FMA contraction (fp contract(off) on both sides), every sum accumulates in the host's order, and
+// the eigen-solvers are the host's cyclic Jacobi with the same rotation order.  Only the transcendental functions (sin, cos,
+// acos, hypot) may round differently from the host's libm; lambda = 10^lg of the minimiser comes from the one table both
+// sides read (pose_tail.h make_pnp_cam).  So decode / NMS / pruning are bit-identical to the host and R, t agree to the
+// rounding that the minimiser's FLT_EPSILON stop leaves.
 //
 // Wave layout: one lane per accumulator (a normal-matrix entry, a JtJ / JtErr entry), looping over the points in host
 // order; one lane per point for the residuals and Jacobian rows (J in LDS); each Jacobi rotation's three k-loops spread
 // over lanes; everything of O(1) size (3x3 polar factors, Rodrigues, the damped 6x6 solve, error norms) computed by
 // every lane redundantly on the same LDS inputs, which keeps control flow uniform.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__
     const double qnan = __builtin_nan("");
     const int det = __float_as_int(rec[0]);
     if (det < 0) {                     // no detection
-        for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? 1.0 : ((e >= 2 && e < 14) ? qnan : 0.0);
+        write_status_row(out, lane, 1);
         if (PREP && lane == 0) active[blockIdx.x] = 0;
         return;
     }
@@ -86,20 +88,14 @@ __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__
     // ---- b. pPose-NMS, n = 1 (host pose_nms): the same sequential scans on every lane
     float mx = -HUGE_VALF;
     for (int k = 0; k < PT_K; ++k) mx = fmaxs(mx, ks[k]);
-    bool keep = !(mx < 0.3f);
-    float smax = -HUGE_VALF, ssum = 0.f, xmin = HUGE_VALF, xmax = -HUGE_VALF, ymin = HUGE_VALF, ymax = -HUGE_VALF;
-    for (int k = 0; k < PT_K; ++k) {
-        smax = fmaxs(smax, ks[k]); ssum += ks[k];
-        xmin = fmins(xmin, kx[k]); xmax = fmaxs(xmax, kx[k]);
-        ymin = fmins(ymin, ky[k]); ymax = fmaxs(ymax, ky[k]);
-    }
-    keep = keep && !(smax < 0.3f) && !(1.5f * 1.5f * (xmax - xmin) * (ymax - ymin) < 0.f);
+    float ssum, smax;
+    const bool keep = merged_pose_scan(kx, ky, ks, &ssum, &smax) && !(mx < 0.3f);
     if (!keep) {                       // dropped by pPose-NMS
-        for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? 2.0 : ((e >= 2 && e < 14) ? qnan : 0.0);
+        write_status_row(out, lane, 2);
         if (PREP && lane == 0) active[blockIdx.x] = 0;
         return;
     }
-    const float prop = ssum / (float)PT_K + rec[5] + 1.25f * smax;
+    const float prop = proposal_score(ssum, smax, rec[5]);
     if (lane < PT_K) {
         kx[lane] = kx[lane] - 0.3f;
         ky[lane] = ky[lane] - 0.3f;
@@ -127,20 +123,7 @@ __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__
     } else {
         rc = pnp_wave(sh, cnt, cam, R, t);
     }
-    for (int e = lane; e < PT_POSE; e += 64) {
-        double v;
-        if (e == 0) v = rc;
-        else if (e == 1) v = cnt;
-        else if (e < 11) v = rc == 0 ? R[e - 2] : qnan;
-        else if (e < 14) v = rc == 0 ? t[e - 11] : qnan;
-        else if (e == 14) v = prop;
-        else if (e == 15) v = 0.0;
-        else {
-            const int k = (e - 16) / 3, c = (e - 16) % 3;
-            v = c == 0 ? kx[k] : (c == 1 ? ky[k] : ks[k]);
-        }
-        out[e] = v;
-    }
+    write_pose_row(out, lane, rc, cnt, R, t, prop, kx, ky, ks);
 }
 
 }  // namespace

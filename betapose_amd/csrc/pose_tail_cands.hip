@@ -14,6 +14,7 @@
 // ever loses entries, so it stays sorted).  Pick, merged x / y / score and proposal score are bit-identical to bp_pose_nms.
 // Only tanhf and expf may round differently from the host's libm, and they feed the comparison simi > gamma alone.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -24,16 +25,13 @@ namespace {
 #include "pnp_wave.inc"
 #include "pose_decode.inc"
 
-constexpr int PC_MAXC = BP_MAX_CANDIDATES;
-constexpr int PC_MERGED = 152;         // floats per merged pose: pick (int bits), proposal score, 50 x (x, y, score)
-
 // records [frames][C][316] f32, counts [frames] -> poses [frames][166] f64, merged [frames][C][152] f32, info [frames][4] i32
 __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __restrict__ records, const int* __restrict__ counts, int C,
                                                              const double* __restrict__ kp3d, PnpCam cam, int left_number,
                                                              double* __restrict__ poses, float* __restrict__ merged,
                                                              int* __restrict__ info) {
     __shared__ PnpShared sh;
-    __shared__ float cx[PC_MAXC][PT_K], cy[PC_MAXC][PT_K], cs[PC_MAXC][PT_K];
+    __shared__ float cx[PT_MAXC][PT_K], cy[PT_MAXC][PT_K], cs[PT_MAXC][PT_K];
     __shared__ float kx[PT_K], ky[PT_K], ks[PT_K];        // result[0]
     __shared__ float mx_[PT_K], my_[PT_K], ms_[PT_K];     // the merged pose being built
     __shared__ float t_sd[PT_K], t_ex[PT_K];
@@ -42,13 +40,12 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
     const int lane = threadIdx.x;
     const float* recs = records + (size_t)blockIdx.x * C * PT_REC;
     double* out = poses + (size_t)blockIdx.x * PT_POSE;
-    float* mrg = merged + (size_t)blockIdx.x * C * PC_MERGED;
+    float* mrg = merged + (size_t)blockIdx.x * C * PT_MERGED;
     int* inf = info + (size_t)blockIdx.x * 4;
-    const double qnan = __builtin_nan("");
     int n = counts[blockIdx.x];
     n = n < 0 ? 0 : (n > C ? C : n);
     if (n == 0) {                      // no candidate
-        for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? 1.0 : ((e >= 2 && e < 14) ? qnan : 0.0);
+        write_status_row(out, lane, 1);
         if (lane < 4) inf[lane] = lane == 2 ? -1 : 0;
         return;
     }
@@ -57,9 +54,9 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
         for (int c = 0; c < n; ++c) decode_kp(recs + (size_t)c * PT_REC, lane, &cx[c][lane], &cy[c][lane], &cs[c][lane]);
     wsync();
     // ---- b. pPose-NMS: the same sequential scans on every lane (uniform control flow)
-    float ref_dists[PC_MAXC], human[PC_MAXC];
+    float ref_dists[PT_MAXC], human[PT_MAXC];
 #pragma unroll
-    for (int c = 0; c < PC_MAXC; ++c) {
+    for (int c = 0; c < PT_MAXC; ++c) {
         ref_dists[c] = 0.f;
         human[c] = 0.f;
         if (c < n) {
@@ -72,9 +69,9 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
         }
     }
     // greedy clustering: `ids` as a bit mask (ascending index = the host's list order)
-    int pick[PC_MAXC], cluster[PC_MAXC], npick = 0;
+    int pick[PT_MAXC], cluster[PT_MAXC], npick = 0;
 #pragma unroll
-    for (int j = 0; j < PC_MAXC; ++j) { pick[j] = 0; cluster[j] = 0; }
+    for (int j = 0; j < PT_MAXC; ++j) { pick[j] = 0; cluster[j] = 0; }
     if (n == 1) {
         pick[0] = 0; cluster[0] = 1; npick = 1;
     } else {
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
             int ref = -1;
             float hbest = 0.f, rd = 0.f;
 #pragma unroll
-            for (int c = 0; c < PC_MAXC; ++c)       // first maximum (a NaN never wins, as the host's >)
+            for (int c = 0; c < PT_MAXC; ++c)       // first maximum (a NaN never wins, as the host's >)
                 if (((ids >> c) & 1u) && (ref < 0 || human[c] > hbest)) { hbest = human[c]; ref = c; rd = ref_dists[c]; }
             const float mlim = fmins(rd, 7.f);
             unsigned dele = 0;
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
             }
             if (!dele) dele = 1u << ref;                                    // pPose_nms.py:63-64
 #pragma unroll
-            for (int j = 0; j < PC_MAXC; ++j)
+            for (int j = 0; j < PT_MAXC; ++j)
                 if (j == npick) { pick[j] = ref; cluster[j] = (int)dele; }
             ++npick;
             ids &= ~dele;
@@ -123,11 +120,11 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
     for (int j = 0; j < npick; ++j) {
         int pk = 0, mid = 0;
 #pragma unroll
-        for (int q = 0; q < PC_MAXC; ++q)
+        for (int q = 0; q < PT_MAXC; ++q)
             if (q == j) { pk = pick[q]; mid = cluster[q]; }
         float rd = 0.f;
 #pragma unroll
-        for (int c = 0; c < PC_MAXC; ++c)
+        for (int c = 0; c < PT_MAXC; ++c)
             if (c == pk) rd = ref_dists[c];
         float mx = -HUGE_VALF;
         for (int k = 0; k < PT_K; ++k) mx = fmaxs(mx, cs[pk][k]);
@@ -158,16 +155,10 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
             }
         }
         wsync();
-        float smax = -HUGE_VALF, ssum = 0.f, xmin = HUGE_VALF, xmax = -HUGE_VALF, ymin = HUGE_VALF, ymax = -HUGE_VALF;
-        for (int k = 0; k < PT_K; ++k) {
-            smax = fmaxs(smax, ms_[k]); ssum += ms_[k];
-            xmin = fmins(xmin, mx_[k]); xmax = fmaxs(xmax, mx_[k]);
-            ymin = fmins(ymin, my_[k]); ymax = fmaxs(ymax, my_[k]);
-        }
-        if (smax < 0.3f) continue;
-        if (1.5f * 1.5f * (xmax - xmin) * (ymax - ymin) < 0.f) continue;
-        const float prop = ssum / (float)PT_K + recs[(size_t)pk * PT_REC + 5] + 1.25f * smax;
-        float* o = mrg + (size_t)m * PC_MERGED;
+        float ssum, smax;
+        if (!merged_pose_scan(mx_, my_, ms_, &ssum, &smax)) continue;
+        const float prop = proposal_score(ssum, smax, recs[(size_t)pk * PT_REC + 5]);
+        float* o = mrg + (size_t)m * PT_MERGED;
         if (lane == 0) { o[0] = __int_as_float(pk); o[1] = prop; }
         if (lane < PT_K) {
             const float x = mx_[lane] - 0.3f, y = my_[lane] - 0.3f;
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
     }
     if (lane == 0) { inf[0] = n; inf[1] = m; inf[2] = m > 0 ? 0 : -1; inf[3] = mask0; }
     if (m == 0) {                      // every merged pose was filtered out
-        for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? 2.0 : ((e >= 2 && e < 14) ? qnan : 0.0);
+        write_status_row(out, lane, 2);
         return;
     }
     wsync();
@@ -187,27 +178,14 @@ __global__ __launch_bounds__(64) void pose_tail_cands_kernel(const float* __rest
     const int cnt = prune_and_compact(sh, kx, ky, ks, kept, kp3d, left_number, lane);
     double R[9], t[3];
     const int rc = pnp_wave(sh, cnt, cam, R, t);
-    for (int e = lane; e < PT_POSE; e += 64) {
-        double v;
-        if (e == 0) v = rc;
-        else if (e == 1) v = cnt;
-        else if (e < 11) v = rc == 0 ? R[e - 2] : qnan;
-        else if (e < 14) v = rc == 0 ? t[e - 11] : qnan;
-        else if (e == 14) v = prop0;
-        else if (e == 15) v = 0.0;
-        else {
-            const int k = (e - 16) / 3, c = (e - 16) % 3;
-            v = c == 0 ? kx[k] : (c == 1 ? ky[k] : ks[k]);
-        }
-        out[e] = v;
-    }
+    write_pose_row(out, lane, rc, cnt, R, t, prop0, kx, ky, ks);
 }
 
 }  // namespace
 
 void launch_pose_tail_cands(const float* records, const int* counts, int frames, int C, const double* kp3d, const PnpCam& cam,
                             int left_number, double* poses, float* merged, int* info, hipStream_t s) {
-    BP_CHECK(C >= 1 && C <= PC_MAXC, "candidate pose tail: 1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
+    BP_CHECK(C >= 1 && C <= PT_MAXC, "candidate pose tail: 1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
     hipLaunchKernelGGL(pose_tail_cands_kernel, dim3(frames), dim3(64), 0, s, records, counts, C, kp3d, cam, left_number, poses, merged,
                        info);
 }

@@ -10,6 +10,7 @@
 // contraction; the same prune_and_compact and pnp_wave as the tail that produced `merged`, so an instance's R and t are
 // what bp_solve_pnp_batch gives on its pruned points, bit for bit.
 #include "bp_common.h"
+#include "pose_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -19,9 +20,6 @@ namespace {
 
 #include "pnp_wave.inc"
 #include "pose_decode.inc"
-
-constexpr int PI_MAXC = BP_MAX_CANDIDATES;
-constexpr int PI_MERGED = 152;         // BP_MERGED_FLOATS
 
 // merged [frames][C][152] f32, info [frames][4] i32, poses [frames][166] f64 -> inst [frames][C][166] f64
 __global__ __launch_bounds__(64) void pose_instances_kernel(const float* __restrict__ merged, const int* __restrict__ info,
@@ -34,7 +32,6 @@ __global__ __launch_bounds__(64) void pose_instances_kernel(const float* __restr
     const int lane = threadIdx.x;
     const int j = blockIdx.x, f = blockIdx.y;
     double* out = inst + ((size_t)f * C + j) * PT_POSE;
-    const double qnan = __builtin_nan("");
     int m = info[(size_t)f * 4 + 1];
     m = m < 0 ? 0 : (m > C ? C : m);
     if (j == 0) {
@@ -43,10 +40,10 @@ __global__ __launch_bounds__(64) void pose_instances_kernel(const float* __restr
         return;
     }
     if (j >= m) {                      // no merged pose in this slot
-        for (int e = lane; e < PT_POSE; e += 64) out[e] = e == 0 ? 1.0 : ((e >= 2 && e < 14) ? qnan : 0.0);
+        write_status_row(out, lane, 1);
         return;
     }
-    const float* mg = merged + ((size_t)f * C + j) * PI_MERGED;
+    const float* mg = merged + ((size_t)f * C + j) * PT_MERGED;
     if (lane < PT_K) {
         kx[lane] = mg[2 + 3 * lane]; ky[lane] = mg[3 + 3 * lane]; ks[lane] = mg[4 + 3 * lane];
         kept[lane] = 1;
@@ -55,28 +52,14 @@ __global__ __launch_bounds__(64) void pose_instances_kernel(const float* __restr
     const int cnt = prune_and_compact(sh, kx, ky, ks, kept, kp3d, left_number, lane);
     double R[9], t[3];
     const int rc = pnp_wave(sh, cnt, cam, R, t);
-    const float prop = mg[1];
-    for (int e = lane; e < PT_POSE; e += 64) {
-        double v;
-        if (e == 0) v = rc;
-        else if (e == 1) v = cnt;
-        else if (e < 11) v = rc == 0 ? R[e - 2] : qnan;
-        else if (e < 14) v = rc == 0 ? t[e - 11] : qnan;
-        else if (e == 14) v = prop;
-        else if (e == 15) v = 0.0;
-        else {
-            const int k = (e - 16) / 3, c = (e - 16) % 3;
-            v = c == 0 ? kx[k] : (c == 1 ? ky[k] : ks[k]);
-        }
-        out[e] = v;
-    }
+    write_pose_row(out, lane, rc, cnt, R, t, mg[1], kx, ky, ks);
 }
 
 }  // namespace
 
 void launch_pose_instances(const float* merged, const int* info, const double* poses, int frames, int C, const double* kp3d,
                            const PnpCam& cam, int left_number, double* inst_poses, hipStream_t s) {
-    BP_CHECK(C >= 1 && C <= PI_MAXC, "instance poses: 1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
+    BP_CHECK(C >= 1 && C <= PT_MAXC, "instance poses: 1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
     hipLaunchKernelGGL(pose_instances_kernel, dim3(C, frames), dim3(64), 0, s, merged, info, poses, C, kp3d, cam, left_number,
                        inst_poses);
 }
