@@ -119,6 +119,12 @@ PROTOTYPES = {
     "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "bp_pose_errors_sym": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "bp_render_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp,
+                                  vp]),
+    "bp_render_depth_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp,
+                                       vp]),
+    "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
     "bp_pipeline_poses": (vp, [vp]),
     "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),

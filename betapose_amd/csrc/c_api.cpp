@@ -13,6 +13,7 @@
 #include "engine.h"
 #include "frame_io.h"
 #include "pose_tail.h"
+#include "raster.h"
 
 // The RANSAC pose tail: workspace = kept 3-D points [batch][64][3] f64 | kept 2-D points [batch][64][2] f64 | the
 // hypotheses' masks and counts (pnp_ransac_workspace_bytes) | active [batch] i32.  Three launches: prepare (decode, NMS,
@@ -703,6 +704,91 @@ int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const d
     bp::launch_pose_errors_sym(d_model, n, d_gt, d_est, P, d_sym, S, K, want, scratch, d_out, s);
     BP_HIP(hipGetLastError());
     BP_HIP(hipStreamSynchronize(s));   // the per-symmetry maxima live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+// what the three rasteriser calls check alike
+static void raster_check_sizes(int n, int F, int P, int H, int W, double near_z) {
+    BP_CHECK(n > 0 && F > 0 && P > 0 && H > 0 && W > 0, "n, F, P, H and W must be positive");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+}
+constexpr size_t RASTER_WS_BYTES = (size_t)256 << 20;      // what the chunked calls keep their workspaces under
+
+int bp_render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         int H, int W, double pixel_center, double near_z, float* depth, int* skipped) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth && skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(bp::render_depth_host(poses, P, vertices, n, faces, F, K, H, W, pixel_center, near_z, depth, skipped) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    int H, int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth && d_skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    size_t chunk = RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1);
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)P));
+    bp::Arena a;
+    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)chunk));
+    BP_HIP(hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)P * HW, s));   // +inf
+    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
+        const int c = (int)std::min(chunk, (size_t)P - p0);
+        bp::launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, c, nullptr, 0, K, H, W, pixel_center, near_z, ws,
+                          (uint32_t*)d_depth + p0 * HW, d_skipped + p0, s);
+    }
+    bp::launch_raster_finish((uint32_t*)d_depth, (size_t)P * HW, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the vertex workspace lives in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
+                  const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                  const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
+                  double near_z, int chunk, double* d_err, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_gt && d_est && K && d_depth_test && d_test_index && taus && d_err && d_counts,
+             "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(T > 0, "T must be positive");
+    BP_CHECK(n_tau >= 1 && n_tau <= bp::VSD_MAX_TAUS, "n_tau must lie in 1 .. 16");
+    BP_CHECK(diameter > 0.0 && depth_scale > 0.0 && chunk >= 0, "diameter and depth_scale must be positive, chunk >= 0");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    size_t c = (size_t)chunk;
+    if (c == 0)   // both workspaces (2 c z-buffers, 2 c posed meshes) under RASTER_WS_BYTES
+        c = std::min(RASTER_WS_BYTES / (2 * HW * sizeof(float)), RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 2));
+    c = std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+    bp::VsdTaus tv{};
+    for (int k = 0; k < n_tau; ++k) tv.tau[k] = taus[k];
+    bp::Arena a;
+    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(2 * c * HW * sizeof(uint32_t));
+    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)(2 * c)));
+    int* skipped = (int*)a.alloc_bytes(2 * c * sizeof(int));
+    int* acc = (int*)a.alloc_bytes((size_t)P * bp::VSD_ACC * sizeof(int));
+    BP_HIP(hipMemsetAsync(acc, 0, (size_t)P * bp::VSD_ACC * sizeof(int), s));
+    BP_HIP(hipMemsetAsync(skipped, 0, 2 * c * sizeof(int), s));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, 2 * (size_t)m * HW, s));   // +inf
+        bp::launch_raster(d_model, n, d_faces, F, d_gt + p0 * 12, m, d_est + p0 * 12, m, K, H, W, pixel_center, near_z, ws, zbuf,
+                          skipped, s);
+        bp::launch_vsd_reduce(zbuf, m, d_depth_test, T, d_test_index + p0, H, W, K, pixel_center, depth_scale, delta, tv, n_tau,
+                              diameter, acc + p0 * bp::VSD_ACC, s);
+    }
+    bp::launch_vsd_finish(acc, d_test_index, T, P, n_tau, d_err, d_counts, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders live in a local arena
     return 0;
     BP_CATCH
 }

@@ -317,6 +317,266 @@ def load_ply_vertices(path: str) -> np.ndarray:
         return np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float64)
 
 
+def load_ply_mesh(path: str):
+    """``(vertices [n, 3] float64, faces [F, 3] int32)`` of a .ply file: the x, y, z of its vertex element as
+    ``load_ply_vertices`` reads them (same formats, same units: the file's own, nothing is scaled) and the
+    ``vertex_indices`` / ``vertex_index`` list of its face element.  A polygon of more than three vertices is
+    fan-triangulated about its first vertex, (v0, v1, v2), (v0, v2, v3), ...; one of fewer than three is dropped."""
+    with open(path, "rb") as f:
+        head = b""
+        while not head.rstrip().endswith(b"end_header"):
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            head += line
+        lines = [ln.strip() for ln in head.decode("ascii", "replace").split("\n") if ln.strip()]
+        if not lines or lines[0] != "ply":
+            raise ValueError("%s: not a PLY file" % path)
+        fmt, elems = None, []                   # elems: [name, count, [(property name, type) | (name, count type, item type)]]
+        for ln in lines[1:]:
+            tok = ln.split()
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elems.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property" and elems:
+                types = tok[2:4] if tok[1] == "list" else tok[1:2]
+                for t in types:
+                    if t not in _PLY_TYPES:
+                        raise ValueError("%s: unknown property type %s" % (path, t))
+                elems[-1][2].append((tok[-1],) + tuple(_PLY_TYPES[t] for t in types))
+        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+            raise ValueError("%s: unknown PLY format %s" % (path, fmt))
+        end = ">" if fmt == "binary_big_endian" else "<"
+        vertices, faces = None, None
+        for name, count, props in elems:
+            has_list = any(len(p_) == 3 for p_ in props)
+            names = [p_[0] for p_ in props]
+            if name == "vertex":
+                if has_list or not all(a in names for a in ("x", "y", "z")):
+                    raise ValueError("%s: the vertex element needs scalar x, y, z" % path)
+            want = None
+            if name == "face":
+                want = next((i for i, p_ in enumerate(props) if len(p_) == 3 and p_[0] in ("vertex_indices", "vertex_index")), None)
+                if want is None:
+                    raise ValueError("%s: face element without a vertex_indices list" % path)
+            rows = []
+            if fmt != "ascii" and not has_list:
+                dt = np.dtype([(nm, end + t) for nm, t in props])
+                buf = f.read(count * dt.itemsize)
+                if len(buf) < count * dt.itemsize:
+                    raise ValueError("%s: truncated %s data" % (path, name))
+                if name == "vertex":
+                    v = np.frombuffer(buf, dtype=dt, count=count)
+                    vertices = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float64)
+                continue
+            for _ in range(count):
+                vals = []
+                if fmt == "ascii":
+                    tok = f.readline().split()
+                    k = 0
+                    for p_ in props:
+                        m = 1
+                        if len(p_) == 3:
+                            m = int(tok[k]) if k < len(tok) else 0
+                            k += 1
+                        if k + m > len(tok):
+                            raise ValueError("%s: truncated %s list" % (path, name))
+                        vals.append([float(t) for t in tok[k:k + m]])
+                        k += m
+                else:
+                    for p_ in props:
+                        m = 1
+                        if len(p_) == 3:
+                            ct = np.dtype(end + p_[1])
+                            raw = f.read(ct.itemsize)
+                            if len(raw) < ct.itemsize:
+                                raise ValueError("%s: truncated %s data" % (path, name))
+                            m = int(np.frombuffer(raw, dtype=ct)[0])
+                        it = np.dtype(end + p_[-1])
+                        raw = f.read(m * it.itemsize)
+                        if len(raw) < m * it.itemsize:
+                            raise ValueError("%s: truncated %s data" % (path, name))
+                        vals.append(np.frombuffer(raw, dtype=it, count=m).tolist())
+                rows.append(vals)
+            if name == "vertex":
+                ix = [names.index(a) for a in ("x", "y", "z")]
+                vertices = np.array([[r[i][0] for i in ix] for r in rows], dtype=np.float64).reshape(count, 3)
+            elif name == "face":
+                tris = []
+                for r in rows:
+                    poly = [int(i) for i in r[want]]
+                    tris.extend((poly[0], poly[k], poly[k + 1]) for k in range(1, len(poly) - 1))
+                faces = np.array(tris, dtype=np.int32).reshape(-1, 3)
+        if vertices is None or faces is None:
+            raise ValueError("%s: needs a vertex and a face element" % path)
+        return vertices, faces
+
+
+BOP_VSD_TAUS = tuple(0.05 * k for k in range(1, 11))        # misalignment tolerances, fractions of the object diameter
+BOP_VSD_THETAS = tuple(0.05 * k for k in range(1, 11))      # thresholds of correctness on the VSD error
+BOP_VSD_DELTA = 0.015                                       # visibility tolerance in metres
+VSD_MAX_TAUS = 16                                           # csrc/raster.h VSD_MAX_TAUS
+
+
+def _poses34(poses):
+    return np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, *np.shape(poses)[-2:])[:, :3, :4])
+
+
+def _mesh_args(vertices, faces):
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    if len(vertices) < 1 or len(faces) < 1:
+        raise ValueError("the mesh needs at least one vertex and one face")
+    if faces.min() < 0 or faces.max() >= len(vertices):
+        raise ValueError("a face index lies outside [0, %d)" % len(vertices))
+    return vertices, faces
+
+
+def render_depth(poses, vertices, faces, K, size, device=None, pixel_center=0.0, near=0.01):
+    """Depth images of a triangle mesh at P poses: ``(depth [P, H, W] float32, skipped [P] int32)``, ``size = (H, W)``.
+    ``poses`` [P, 3, 4] or [P, 4, 4] model-to-camera, ``vertices`` [n, 3] and ``faces`` [F, 3] (load_ply_mesh), ``K`` 3x3,
+    all float64 in the units of the poses; the depth is the camera-space z in those units, 0 where nothing was drawn.
+    The centre of pixel (x, y) lies at image coordinates (x + pixel_center, y + pixel_center): 0.0 is BOP's convention
+    and the one projection_error_2d and the key points are expressed in, 0.5 the reference renderer's.  Coverage is
+    exact integer arithmetic (vertices snapped to 1/256 px, top-left rule, both windings), the depth of a covered pixel
+    the intersection of its ray with the triangle's plane.  There is NO near-plane clipping: a triangle
+    with a vertex nearer than ``near`` (or projecting beyond +-2^14 px) is dropped whole and counted in ``skipped``.
+    ``device=None``: the host renderer (bp_render_depth_host, no GPU needed); a torch device: bp_render_depth on it.
+    The two images are bit-identical."""
+    from . import _lib
+    poses = _poses34(poses)
+    vertices, faces = _mesh_args(vertices, faces)
+    H, W = int(size[0]), int(size[1])
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    P = len(poses)
+    if P == 0:
+        return np.zeros((0, H, W), np.float32), np.zeros(0, np.int32)
+    if device is None:
+        depth, skipped = np.empty((P, H, W), np.float32), np.empty(P, np.int32)
+        _lib.check(_lib.lib().bp_render_depth_host(_lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces),
+                                                   len(faces), _lib.ptr(Kf), H, W, float(pixel_center), float(near),
+                                                   _lib.ptr(depth), _lib.ptr(skipped)))
+        return depth, skipped
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_depth = torch.empty((P, H, W), dtype=torch.float32, device=dev)
+        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().bp_render_depth(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces),
+                                              _lib.ptr(d_poses), P, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
+                                              _lib.ptr(d_depth), _lib.ptr(d_skipped),
+                                              torch.cuda.current_stream(dev).cuda_stream))
+        return d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+
+
+def vsd_masks(depth_test, depth_gt, depth_est, K, delta, pixel_center=0.0):
+    """The per-pixel quantities of vsd_err as a dict: the distance images ``dist_test``, ``dist_gt``, ``dist_est``
+    (depth z times the length of the pixel's ray ((x + c - cx) / fx, (y + c - cy) / fy, 1); 0 stays 0) and the boolean
+    masks ``visib_gt``, ``visib_est``, ``inter``, ``union`` of visibility mode bop19."""
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    H, W = np.shape(depth_gt)
+    x = np.arange(W, dtype=np.float64)[None, :]
+    y = np.arange(H, dtype=np.float64)[:, None]
+    a = (x + pixel_center - K[0, 2]) / K[0, 0]
+    b = (y + pixel_center - K[1, 2]) / K[1, 1]
+    ray = np.sqrt(a * a + b * b + 1.0)
+    dt = np.asarray(depth_test, dtype=np.float64) * ray
+    dg = np.asarray(depth_gt, dtype=np.float64) * ray
+    de = np.asarray(depth_est, dtype=np.float64) * ray
+    vg = (dg > 0) & ((dg - dt <= delta) | (dt == 0))
+    ve = ((de > 0) & ((de - dt <= delta) | (dt == 0))) | (vg & (de > 0))
+    return {"dist_test": dt, "dist_gt": dg, "dist_est": de, "visib_gt": vg, "visib_est": ve, "inter": vg & ve,
+            "union": vg | ve}
+
+
+def vsd_err(depth_test, depth_gt, depth_est, K, delta, taus, diameter, pixel_center=0.0):
+    """BOP's Visible Surface Discrepancy of one pose pair from three depth images [H, W] in one unit -- the test image
+    and the renders of the ground-truth and the estimated pose, 0 = nothing / missing -- as float64 [len(taus)]: the
+    toolkit's ``vsd`` with ``cost_type='step'``, ``normalized_by_diameter=True`` and visibility mode ``bop19``.
+    Depths become distances from the camera centre (vsd_masks); the ground truth is visible where it is rendered and
+    not more than ``delta`` behind the test surface (or the test depth is missing); the estimate likewise, and also
+    wherever the ground truth is visible and the estimate is rendered.  With inter / union the pixel counts of the two
+    masks' intersection and union, e(tau) = (#{p in inter: |dist_gt - dist_est| / diameter >= tau} + union - inter)
+    / union, and 1.0 when the union is empty.
+    This restates the published description of the metric; the BOP toolkit itself was not available to check against.
+    ``bp_vsd_errors`` computes the same on the GPU from renders it makes itself."""
+    m = vsd_masks(depth_test, depth_gt, depth_est, K, delta, pixel_center)
+    inter, union = int(m["inter"].sum()), int(m["union"].sum())
+    out = np.ones(len(taus), dtype=np.float64)
+    if union == 0:
+        return out
+    rel = np.abs(m["dist_gt"] - m["dist_est"])[m["inter"]] / diameter
+    for k, tau in enumerate(taus):
+        out[k] = (int((rel >= tau).sum()) + (union - inter)) / union
+    return out
+
+
+def pose_errors_vsd(gt_poses, est_poses, vertices, faces, K, depth_test_u16, test_index, diameter, depth_scale=0.001,
+                    delta=BOP_VSD_DELTA, taus=BOP_VSD_TAUS, device=None, chunk=0, pixel_center=0.0, near=0.01):
+    """VSD of P pose pairs of one mesh: ``(err [P, n_tau] float64, counts [P, 4] int32)``.  Both poses of a pair are
+    rendered (render_depth) and compared with test image ``test_index[p]`` of ``depth_test_u16`` [T, H, W] uint16,
+    whose depth is ``raw * depth_scale`` in the units of the poses (0.001 for LineMod's millimetre PNGs with poses in
+    metres; 0 = missing).  ``counts[p]`` = (rendered ground-truth pixels, visible ground-truth pixels, intersection,
+    union), so ``counts[:, 1] / counts[:, 0]`` is BOP's visible fraction (``visib_fract``) of each annotation.
+    ``device=None``: host renders and vsd_err pair by pair; a torch device: one bp_vsd_errors call on it, ``chunk``
+    pairs at a time (0: a default that keeps the workspace under 256 MB).  The device results are bit-identical from
+    call to call and across chunk sizes, and equal the host's."""
+    gt, est = _poses34(gt_poses), _poses34(est_poses)
+    if gt.shape != est.shape:
+        raise ValueError("gt_poses and est_poses differ in shape: %s vs %s" % (gt.shape, est.shape))
+    vertices, faces = _mesh_args(vertices, faces)
+    dtest = np.ascontiguousarray(depth_test_u16)
+    if dtest.dtype != np.uint16 or dtest.ndim != 3:
+        raise ValueError("depth_test_u16 must be a uint16 array [T, H, W]")
+    T, H, W = dtest.shape
+    idx = np.ascontiguousarray(test_index, dtype=np.int32).reshape(-1)
+    taus = np.ascontiguousarray(taus, dtype=np.float64).reshape(-1)
+    P = len(gt)
+    if len(idx) != P:
+        raise ValueError("test_index needs one entry per pose pair")
+    if P and (idx.min() < 0 or idx.max() >= T):
+        raise ValueError("a test index lies outside [0, %d)" % T)
+    if not 1 <= len(taus) <= VSD_MAX_TAUS:
+        raise ValueError("between 1 and %d taus" % VSD_MAX_TAUS)
+    err, counts = np.ones((P, len(taus)), np.float64), np.zeros((P, 4), np.int32)
+    if P == 0:
+        return err, counts
+    if device is None:
+        step = max(1, (1 << 24) // (H * W))
+        for s in range(0, P, step):
+            dg = render_depth(gt[s:s + step], vertices, faces, K, (H, W), None, pixel_center, near)[0]
+            de = render_depth(est[s:s + step], vertices, faces, K, (H, W), None, pixel_center, near)[0]
+            for j in range(len(dg)):
+                p = s + j
+                test = dtest[idx[p]].astype(np.float64) * depth_scale
+                err[p] = vsd_err(test, dg[j], de[j], K, delta, taus, diameter, pixel_center)
+                m = vsd_masks(test, dg[j], de[j], K, delta, pixel_center)
+                counts[p] = (int((dg[j] > 0).sum()), int(m["visib_gt"].sum()), int(m["inter"].sum()), int(m["union"].sum()))
+        return err, counts
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    dev = torch.device(device)
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    with torch.cuda.device(dev):
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_gt, d_est = torch.from_numpy(gt.reshape(P, 12)).to(dev), torch.from_numpy(est.reshape(P, 12)).to(dev)
+        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
+        d_idx = torch.from_numpy(idx).to(dev)
+        d_err = torch.empty((P, len(taus)), dtype=torch.float64, device=dev)
+        d_counts = torch.empty((P, 4), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().bp_vsd_errors(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_gt),
+                                            _lib.ptr(d_est), P, _lib.ptr(Kf), _lib.ptr(d_test), T, H, W, float(depth_scale),
+                                            _lib.ptr(d_idx), float(delta), _lib.ptr(taus), len(taus), float(diameter),
+                                            float(pixel_center), float(near), int(chunk), _lib.ptr(d_err), _lib.ptr(d_counts),
+                                            torch.cuda.current_stream(dev).cuda_stream))
+        return d_err.cpu().numpy(), d_counts.cpu().numpy()
+
+
 def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
     """``Model3D.refine`` (utils/model.py:29-46): ``len - keep`` times, delete the first point (in row-major pair
     order) of the closest pair.  Two quirks of the reference are kept: the running minimum of a round starts at the
@@ -336,7 +596,8 @@ def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
 
 def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model_vertices, cam_K, diameter_mm,
                      pixel_thresh: float = 5.0, symmetric: bool = False, device=None, symmetries=None,
-                     image_width: int = 640, match_instances: bool = False):
+                     image_width: int = 640, match_instances: bool = False, faces=None, depth_frames=None,
+                     depth_scale: float = 0.001):
     """The metric loop of betapose_evaluate.py:204-266.  ``gt_frames[nr]`` = list of ``{'pose': 4x4, 'bbox': [x, y, w, h]}`` (one per ground-truth
     annotation compared; a bare dict is accepted for one).
     Returns dict(mean_add, mean_2d_acc, mean_iou, mean_add_err_mm, n).  ``symmetric``: also ADD-S (add_s_err) --
@@ -350,8 +611,15 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
     scored instance by instance instead of ``result[0]`` against every annotation: each ground-truth entry, in list
     order, takes the still unmatched solved instance whose ``bbox`` has the highest IoU with its box (ties: the lower j);
     the pair is scored at IoU >= 0.5, and an entry without such an instance counts in ``n`` and ``mean_iou`` as a miss
-    (with the best IoU left, 0 when no instance is).  A frame without any result is skipped, as it is without the flag."""
-    ious, gts, ests = [], [], []
+    (with the best IoU left, 0 when no instance is).  A frame without any result is skipped, as it is without the flag.
+    ``faces`` [F, 3] (load_ply_mesh, indices into ``model_vertices``) and ``depth_frames`` (frame number -> uint16 [H, W]
+    test depth image, ``depth_scale`` metres per count), both given: also BOP's VSD on the same scored pairs
+    (pose_errors_vsd, on ``device`` when one is given, with ``cam_K``, BOP_VSD_DELTA and BOP_VSD_TAUS) -- ``ar_vsd``, the
+    mean over (tau, theta) in BOP_VSD_TAUS x BOP_VSD_THETAS of the fraction of pairs with err(tau) < theta,
+    ``mean_vsd_err``, the mean over pairs and taus, and ``mean_visib_fract``, the mean visible fraction of the scored
+    ground-truth annotations (those that render at least one pixel).  A scored frame without a depth image raises
+    KeyError."""
+    ious, gts, ests, nrs = [], [], [], []
     for f in final_result:
         nr = int(os.path.basename(f["imgname"])[0:-4])
         if nr not in gt_frames:
@@ -380,6 +648,7 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
                     pose[:3, 3] = np.asarray(s["cam_t"])[:, 0]
                     gts.append(gt["pose"])
                     ests.append(pose)
+                    nrs.append(nr)
             continue
         for gt in entries:
             if len(f["result"]) < 1 or len(f["result"][0]) < 1:
@@ -395,6 +664,7 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
             if i >= 0.5:
                 gts.append(gt["pose"])
                 ests.append(pose)
+                nrs.append(nr)
     if device is None:
         add_errs = [add_err(g, e, model_vertices) * 1000 for g, e in zip(gts, ests)]
         proj = [projection_error_2d(g, e, model_vertices, cam_K) for g, e in zip(gts, ests)]
@@ -420,6 +690,23 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
         m["ar_mspd"] = float(np.mean([np.mean(mspd < th * r) for th in BOP_MSPD_THETAS])) if len(gts) else nan
         m["mean_mssd_err_mm"] = float(np.mean(mssd_mm)) if len(gts) else nan
         m["mean_mspd_err_px"] = float(np.mean(mspd)) if len(gts) else nan
+    if faces is not None and depth_frames is not None:
+        nan = float("nan")
+        m["ar_vsd"] = m["mean_vsd_err"] = m["mean_visib_fract"] = nan
+        if len(gts):
+            used = sorted(set(nrs))
+            for nr in used:
+                if nr not in depth_frames:
+                    raise KeyError("no depth image for frame %d" % nr)
+            test = np.stack([np.asarray(depth_frames[nr]) for nr in used])
+            index = np.array([used.index(nr) for nr in nrs], dtype=np.int32)
+            err, counts = pose_errors_vsd(np.reshape(gts, (-1, 4, 4)), np.reshape(ests, (-1, 4, 4)), model_vertices, faces,
+                                          cam_K, test, index, diameter_mm / 1000.0, depth_scale, device=device)
+            m["ar_vsd"] = float(np.mean([[np.mean(err[:, k] < th) for th in BOP_VSD_THETAS] for k in range(err.shape[1])]))
+            m["mean_vsd_err"] = float(np.mean(err))
+            seen = counts[:, 0] > 0
+            if seen.any():
+                m["mean_visib_fract"] = float(np.mean(counts[seen, 1] / counts[seen, 0]))
     return m
 
 

@@ -49,6 +49,13 @@ def build_parser() -> argparse.ArgumentParser:
                         'none: the identity), as average recall over the ten BOP thresholds: two more lines per object, '
                         '"Mean mssd recall for seq XX is: ..." and "Mean mspd recall for seq XX is: ...", computed on the '
                         'run\'s GPU (metrics.pose_errors_sym)')
+    p.add_argument('--vsd', default=False, action='store_true',
+                   help='also score every evaluated object with BOP\'s Visible Surface Discrepancy: reads the faces of '
+                        'models/obj_XX.ply and the 16-bit depth images <sequence>/depth/NNNN.png, renders the ground-truth '
+                        'and the estimated pose of every scored pair on the run\'s GPU (metrics.pose_errors_vsd) and prints '
+                        'one more line per object, "Mean vsd recall for seq XX is: ...", the average recall over the BOP '
+                        'taus and thresholds.  With --synthetic the run scores its own poses against depth images rendered '
+                        'from them (a closed loop that only exercises the path)')
     p.add_argument('--shared_detector', default='', type=str, metavar='CFG[,WEIGHTS]',
                    help='occlusion_evaluate.py --obj_ids: ONE multi-class detector (Darknet cfg, .weights file) serves every '
                         'object -- one resize and one detector pass per frame, the best box of each object\'s class, then each '

@@ -1,7 +1,8 @@
 """SIXD benchmark reader with the reference's structure (utils/sixd.py:43-111): ``load_sixd(base_path, seq, nr_frames)``
 returns a ``Benchmark`` whose ``frames[i].gt`` is a list of ``(obj_id, pose 4x4 in metres, [x, y, w, h])``, ``cam`` the
 3x3 intrinsics from ``camera.yml`` (identity without it) and ``diameter`` a list indexed by object id (entry 0 is a
-placeholder, as in the reference).  Images and meshes are not loaded (the reference has those lines commented out)."""
+placeholder, as in the reference).  Images and meshes are not loaded (the reference has those lines commented out);
+``load_depth=True`` fills ``frames[i].depth`` with the 16-bit depth image of ``<seq>/depth/NNNN.png`` (what VSD reads)."""
 from __future__ import annotations
 
 import os
@@ -52,6 +53,18 @@ def _gt_tuple(entry, to_metres):
     return entry["obj_id"], T, entry["obj_bb"]
 
 
+def read_depth_png(path):
+    """A 16-bit depth PNG as uint16 [H, W] (raw counts; LineMod's are millimetres)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im)
+    if a.ndim != 2 or a.dtype.itemsize < 2:
+        raise ValueError("%s: not a 16-bit single-channel image" % path)
+    if a.min() < 0 or a.max() > 65535:
+        raise ValueError("%s: values outside 16 bits" % path)
+    return np.ascontiguousarray(a.astype(np.uint16))
+
+
 def _frame(seq_dir, nr, gt_entries, info, to_metres):
     fr = Frame()
     fr.nr, fr.path = nr, "%srgb/%04d.png" % (seq_dir, nr)
@@ -61,8 +74,9 @@ def _frame(seq_dir, nr, gt_entries, info, to_metres):
     return fr
 
 
-def load_sixd(base_path, seq, nr_frames=0, load_mesh=True):
-    """``seq`` None: intrinsics and diameters only.  ``nr_frames`` 0: every frame of the sequence."""
+def load_sixd(base_path, seq, nr_frames=0, load_mesh=True, load_depth=False):
+    """``seq`` None: intrinsics and diameters only.  ``nr_frames`` 0: every frame of the sequence.  ``load_depth``: also
+    each frame's depth image (read_depth_png) into ``Frame.depth``."""
     bench = Benchmark()
     bench.cam = _intrinsics(base_path)
     # diameters indexed by object id; ids start at 1, so slot 0 holds the reference's placeholder (utils/sixd.py:73)
@@ -72,4 +86,7 @@ def load_sixd(base_path, seq, nr_frames=0, load_mesh=True):
         infos, gts = _yaml(seq_dir, "info.yml"), _yaml(seq_dir, "gt.yml")
         count = nr_frames if nr_frames > 0 else len(infos)
         bench.frames = [_frame(seq_dir, i, gts[i], infos[i], bench.scale_to_meters) for i in range(count)]
+        if load_depth:
+            for fr in bench.frames:
+                fr.depth = read_depth_png("%sdepth/%04d.png" % (seq_dir, fr.nr))
     return bench

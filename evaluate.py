@@ -72,6 +72,49 @@ def print_bop_metrics(base, obj_id, final_result, gt_frames, model_vertices, cam
     print("Mean mspd recall for seq %02d is: %.3f" % (obj_id, m["ar_mspd"]))
 
 
+def print_vsd_metrics(base, obj_id, seq_id, final_result, gt_frames, model_vertices, cam, diameter, device,
+                      match_instances=False):
+    """--vsd: the faces of the object's mesh, the depth images of the scored frames, VSD of the scored pairs on ``device``
+    and the average-recall line.  The camera is camera.yml's when the dataset has one, else the LineMod K PnP uses."""
+    from betapose_amd import sixd
+    _, faces = metrics.load_ply_mesh(os.path.join(base, "models", "obj_%02d.ply" % obj_id))
+    seq = os.path.join(base, "test", "%02d" % (obj_id if seq_id is None else seq_id))
+    depth_frames = {}
+    for f in final_result:
+        nr = int(os.path.basename(f["imgname"])[0:-4])
+        if nr in gt_frames and nr not in depth_frames:
+            depth_frames[nr] = sixd.read_depth_png(os.path.join(seq, "depth", "%04d.png" % nr))
+    K = cam if os.path.exists(os.path.join(base, "camera.yml")) else synth.CAM_K
+    m = metrics.evaluate_results(final_result, gt_frames, model_vertices, K, diameter, device=device, faces=faces,
+                                 depth_frames=depth_frames, match_instances=match_instances)
+    print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m["ar_vsd"]))
+
+
+def print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, size, device):
+    """--synthetic --vsd: a closed loop that only shows the path runs.  The mesh is the bounding box of the synthetic key
+    points, the ground truth is each frame's own estimated pose and its depth image is rendered from that pose, so a
+    frame whose pose puts the box in front of the camera scores 0 error and any other renders nothing and scores 1."""
+    lo, hi = np.min(kp3d, axis=0), np.max(kp3d, axis=0)
+    v = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=np.float64)
+    faces = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
+                      [1, 5, 7], [1, 7, 3]], dtype=np.int32)
+    gt_frames, depth_frames = {}, {}
+    for f in final_result:
+        if len(f["result"]) < 1:
+            continue
+        nr = int(os.path.basename(f["imgname"])[0:-4])
+        pose = np.eye(4)
+        pose[:3, :3], pose[:3, 3] = f["cam_R"], np.asarray(f["cam_t"])[:, 0]
+        x1, y1, x2, y2 = np.asarray(f["result"][0]["bbox"]).tolist()
+        gt_frames[nr] = [{"pose": pose, "bbox": [x1, y1, x2 - x1, y2 - y1]}]
+        depth = metrics.render_depth(pose[None], v, faces, cam_K, size, device)[0][0]
+        depth_frames[nr] = np.clip(np.round(depth.astype(np.float64) * 1000.0), 0, 65535).astype(np.uint16)
+    diameter = float(np.linalg.norm(hi - lo)) * 1000.0
+    m = metrics.evaluate_results(final_result, gt_frames, v, cam_K, diameter, device=device, faces=faces,
+                                 depth_frames=depth_frames)
+    print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m["ar_vsd"]))
+
+
 def main():
     args = parse_args()
     import torch
@@ -118,6 +161,7 @@ def main():
                 name = "%04d.png" % i
                 Image.fromarray(fr[:, :, ::-1].copy()).save(os.path.join(args.inputpath, name))
                 im_names.append(name)
+                synth_size = fr.shape[:2]
         cam_K, kp3d = synth.CAM_K, synth.synth_kp3d(50)
     else:
         if len(args.inputlist):
@@ -245,6 +289,12 @@ def main():
             if args.bop_metrics:
                 print_bop_metrics(args.sixd_base, obj_id, final_result, gt_frames, model_vertices, metric_cam, diameter,
                                   torch.device("cuda", local), match_instances=args.all_instances)
+            if args.vsd:
+                print_vsd_metrics(args.sixd_base, obj_id, 2 if args.occlusion else None, final_result, gt_frames,
+                                  model_vertices, metric_cam, diameter, torch.device("cuda", local),
+                                  match_instances=args.all_instances)
+        elif args.vsd and args.synthetic:
+            print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, synth_size, torch.device("cuda", local))
     bpd.finalize()
 
 

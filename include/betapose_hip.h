@@ -42,6 +42,9 @@
  *   bp_pose_errors         add_err / projection_error_2d + the commented-out   utils/metrics.py:10-33,99-127
  *                          closest-point (ADD-S) loop, over every vertex
  *   bp_pose_errors_sym     no reference counterpart: the BOP errors MSSD and MSPD over an object's symmetry set
+ *   bp_render_depth, bp_render_depth_host
+ *                          Renderer.render's depth image (OpenGL through vispy)   utils/renderer.py
+ *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
@@ -260,6 +263,30 @@ int bp_pose_errors(const double* d_model, int n, const double* d_gt, const doubl
  * unrequested columns untouched.  Bit-identical from run to run.  Synchronises `stream`. */
 int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym,
                        int S, const double* K, int want, double* d_out, void* stream);
+/* Depth images of a triangle mesh at P poses.  d_model [n][3] f64 object frame, d_faces [F][3] int32, d_poses [P][12]
+ * row-major [R|t] f64, K host 3x3; the centre of pixel (x, y) lies at image coordinates (x + pixel_center,
+ * y + pixel_center) (0 BOP's convention, 0.5 the reference renderer's).  Coverage: vertices snapped to 1/256 px, int64
+ * edge functions, top-left rule, both windings; depth: the pixel ray's f64 intersection with the triangle's camera-space
+ * plane, clamped to the triangle's depth range, rounded to f32; z-buffer: minimum.  d_depth [P][H][W] f32, 0 where
+ * nothing was drawn.  A triangle with a vertex at z < near_z (> 0) or projecting beyond +-2^14 px, or with a face index
+ * outside [0, n), is skipped whole (no near-plane clipping) and counted in d_skipped [P].  H * W <= 2^24.
+ * bp_render_depth_host is the same on host memory, without a GPU, bit-identical to the device image; it refuses a face
+ * index outside [0, n).  bp_render_depth synchronises `stream`. */
+int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    int H, int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, void* stream);
+int bp_render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         int H, int W, double pixel_center, double near_z, float* depth, int* skipped);
+/* BOP's Visible Surface Discrepancy (step cost, normalised by the diameter, visibility mode bop19) of P pose pairs of
+ * one mesh: both poses of a pair are rendered as bp_render_depth does and compared with the test depth image
+ * d_test_index[p] of d_depth_test [T][H][W] uint16 (depth = raw * depth_scale in pose units, 0 = missing).  taus: host,
+ * n_tau <= 16.  d_err [P][n_tau] f64; d_counts [P][4] int32 = (rendered ground-truth pixels, visible ground-truth
+ * pixels, intersection, union) -- counts[1] / counts[0] is BOP's visible fraction.  Pairs are processed `chunk` at a
+ * time (0: as many as keep the workspaces under 256 MB); the results do not depend on it and are bit-identical from run
+ * to run.  A pair whose test index lies outside [0, T) gets NaN errors and counts of -1.  Synchronises `stream`. */
+int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
+                  const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                  const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
+                  double near_z, int chunk, double* d_err, int* d_counts, void* stream);
 /* one fused convolution on device tensors (unit tests / kernel benchmarks).  h_w: host OIHW filter, h_bias host or NULL.
  * d_in NHWC [N,H,W,Cin]; d_out per store_mode (0 NHWC, 1 nearest-x2 NHWC, 2 PixelShuffle(2) NHWC, 3 NCHW);
  * act 0 linear / 1 leaky(0.1) / 2 relu; d_res NHWC residual or NULL; splits 0 auto; tile -1 auto, else a kernel id

@@ -213,6 +213,9 @@ def main():
             if args.bop_metrics:
                 evaluate.print_bop_metrics(args.sixd_base, o, final_result, frames_gt, model, cam, diameter,
                                            torch.device("cuda", local), match_instances=args.all_instances)
+            if args.vsd:
+                evaluate.print_vsd_metrics(args.sixd_base, o, 2, final_result, frames_gt, model, cam, diameter,
+                                           torch.device("cuda", local), match_instances=args.all_instances)
     bpd.finalize()
 
 
