@@ -11,37 +11,10 @@
 #include <vector>
 
 #include "engine.h"
+#include "frame_chain.h"
 #include "frame_io.h"
 #include "pose_tail.h"
 #include "raster.h"
-
-// The RANSAC pose tail: workspace = kept 3-D points [batch][64][3] f64 | kept 2-D points [batch][64][2] f64 | the
-// hypotheses' masks and counts (pnp_ransac_workspace_bytes) | active [batch] i32.  Three launches: prepare (decode, NMS,
-// pruning; the pose row but for the solver's slots), hypotheses, select-and-refit.
-static size_t pose_ransac_ws_bytes(int batch, int max_trials) {
-    return (size_t)batch * 64 * 5 * sizeof(double) + bp::pnp_ransac_workspace_bytes(batch, max_trials) + (size_t)batch * sizeof(int);
-}
-static void pose_tail_ransac(const float* records, int batch, const double* kp3d, const bp::PnpCam& cam, int left_number,
-                             double reproj_err, int max_trials, const int* samples, const int* need, double* poses, void* ws,
-                             hipStream_t s) {
-    double* ws3d = (double*)ws;
-    double* ws2d = ws3d + (size_t)batch * 64 * 3;
-    char* hyp = (char*)(ws2d + (size_t)batch * 64 * 2);
-    int* active = (int*)(hyp + bp::pnp_ransac_workspace_bytes(batch, max_trials));
-    const int n = left_number < 50 ? left_number : 50;     // points the pruning keeps, the same for every frame
-    bp::launch_pose_tail_prepare(records, batch, kp3d, cam, left_number, poses, ws3d, ws2d, active, s);
-    bp::launch_pnp_ransac(ws3d, 64 * 3, ws2d, 64 * 2, active, n, batch, cam, reproj_err, max_trials, samples, need, hyp, nullptr,
-                          nullptr, nullptr, poses, s);
-}
-// the host's tables for n points (n > 6: below that the device code reads neither)
-static void ransac_tables(int n, int max_trials, double confidence, std::vector<int>& samples, std::vector<int>& need) {
-    samples.assign((size_t)max_trials * 6, 0);
-    need.assign((size_t)(n > 0 ? n : 0) + 1, 0x7fffffff);
-    if (n > 6) {
-        bp::pnp_ransac_samples(n, max_trials, samples.data());
-        bp::pnp_ransac_trials_needed(n, confidence, need.data());
-    }
-}
 
 static thread_local std::string g_err;
 
@@ -66,6 +39,8 @@ struct bp_kpd {
     int device;
 };
 
+// The per-frame device chains.  What they share -- the frame's graph, the latency mode's re-run, the resize stage and the
+// pose solver -- is frame_chain.h; `engines` lists the detector, then the key-point engine(s).
 struct bp_pipeline {
     bp_yolo* y;
     bp_kpd* k;
@@ -73,55 +48,23 @@ struct bp_pipeline {
     float conf;
     int num_classes;
     bp::Arena arena;
-    uint8_t* frames = nullptr;
-    uint8_t* tmp = nullptr;
+    bp::ResizeStage resize;
     float* results = nullptr;    // [batch][316] = sel[8] | pts[8] | kp[50][6], each written by its producer
     float* hm = nullptr;
     float* fixed_box = nullptr;  // [batch][4] or null
     bool use_fixed = false;
-    int *hb = nullptr, *hk = nullptr, *vb = nullptr, *vk = nullptr;
-    int ksh = 0, ksv = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    unsigned ver_y = 0, ver_k = 0;   // engine plan versions the graph was captured with
+    bp::EngineList engines;
+    bp::FrameGraph graph;
     int latency_faults = 0;          // frames re-run because the latency mode's placement check failed (bp_pipeline_latency_faults)
-    // device pose tail (bp_pipeline_set_pose_solver): on while pose_on; kp3d [50][3] and poses [batch][166] in the arena
-    bool pose_on = false;
-    double* kp3d = nullptr;
-    double* poses = nullptr;
+    bp::PoseSolver pose;             // bp_pipeline_set_pose_solver / _ransac: rows [batch][166]
     double* own_poses = nullptr;
-    bp::PnpCam cam{};
-    int left_number = 50;
-    // RANSAC in place of the plain PnP (bp_pipeline_set_pose_ransac): on while ransac_trials > 0; the sampler's and the
-    // early stop's tables are the host's, for n = min(50, left_number) points
-    int ransac_trials = 0;
-    double ransac_err = 0, ransac_conf = 0;
-    std::vector<int> ransac_samples, ransac_need;
-    void* ransac_ws = nullptr;
-    size_t ransac_ws_bytes = 0;
-    ~bp_pipeline() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    }
 };
 
 // One shared multi-class detector pass per frame feeding K objects' pose chains (bp_scene_*): slot k = class_ids[k], its
-// key-point engine, result row k and (opt-in) its pose tail.
+// key-point engine (engines[1 + k]), result row k and (opt-in) its pose tail.
 struct bp_scene_slot {
     bp_kpd* k = nullptr;
-    unsigned ver_k = 0;
-    bool pose_on = false;
-    double* kp3d = nullptr;
-    double* poses = nullptr;
-    bp::PnpCam cam{};
-    int left_number = 50;
-    int ransac_trials = 0;
-    double ransac_err = 0, ransac_conf = 0;
-    std::vector<int> ransac_samples, ransac_need;
-    void* ransac_ws = nullptr;
-    size_t ransac_ws_bytes = 0;
+    bp::PoseSolver pose;
 };
 struct bp_scene {
     bp_yolo* y;
@@ -131,22 +74,12 @@ struct bp_scene {
     float conf;
     int num_classes;
     bp::Arena arena;
-    uint8_t* frames = nullptr;
-    uint8_t* tmp = nullptr;
+    bp::ResizeStage resize;
     float* results = nullptr;    // [K][316], row k = slot k's record
     double* own_poses = nullptr; // [K][166], rows of the slots whose solver was set without a buffer
-    int *hb = nullptr, *hk = nullptr, *vb = nullptr, *vk = nullptr;
-    int ksh = 0, ksv = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    unsigned ver_y = 0;
+    bp::EngineList engines;
+    bp::FrameGraph graph;
     int latency_faults = 0;
-    ~bp_scene() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    }
 };
 
 // Candidate boxes per frame (bp_cands_*): one frame, up to C NMS survivors of the detector through ONE key-point pass at
@@ -158,33 +91,19 @@ struct bp_cands {
     float conf, nms_conf;
     int num_classes, class_id;
     bp::Arena arena;
-    uint8_t* frames = nullptr;
-    uint8_t* tmp = nullptr;
+    bp::ResizeStage resize;
     float* results = nullptr;    // [C][316]
     int* counts = nullptr;       // [1]
-    int *hb = nullptr, *hk = nullptr, *vb = nullptr, *vk = nullptr;
-    int ksh = 0, ksv = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    unsigned ver_y = 0, ver_k = 0;
+    bp::EngineList engines;
+    bp::FrameGraph graph;
     int latency_faults = 0;
-    bool pose_on = false;
-    double* kp3d = nullptr;
-    double* pose = nullptr;      // [166]
+    bp::PoseSolver pose;         // the candidate tail: row [166]; its RANSAC part stays unused
     double* own_pose = nullptr;
     float* merged = nullptr;     // [C][152]
     int* info = nullptr;         // [4]
-    bp::PnpCam cam{};
-    int left_number = 50;
     bool inst_on = false;
     double* inst = nullptr;      // [C][166]: a pose per merged candidate (opt-in)
     double* own_inst = nullptr;
-    ~bp_cands() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    }
 };
 
 static std::string read_text(const char* path) {
@@ -990,29 +909,25 @@ static void pipeline_enqueue(bp_pipeline* p, hipStream_t s) {
     bp::YoloNet& yn = *p->y->net;
     bp::KpdNet& kn = *p->k->net;
     const int reso = yn.reso();
-    bp::ResizeTables t{p->hb, p->hk, p->ksh, p->vb, p->vk, p->ksv};
     // a1: Pillow-exact bicubic stretch to reso x reso, BGR -> RGB, /255, straight into the detector's NHWC input
 #ifdef BP_EXPERIMENTAL   // timing experiment only (WRONG results): BP_ABLATE_RESIZE=1 leaves both resize launches out of
     // the frame (the detector sees whatever its input buffer holds) -- the upper bound of what fusing them into the stem could buy (round-4 verdict item 6; tools/ab_resize.sh)
     static const bool no_resize = std::getenv("BP_ABLATE_RESIZE") != nullptr;
-    if (!no_resize) bp::launch_resize_bicubic(p->frames, p->batch, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    if (!no_resize) p->resize.enqueue(p->batch, p->H, p->W, yn.input_nhwc(), reso, s);
 #else
-    bp::launch_resize_bicubic(p->frames, p->batch, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    p->resize.enqueue(p->batch, p->H, p->W, yn.input_nhwc(), reso, s);
 #endif
     // a3-a5: detector + decode + arg-max objectness
     // every stage writes its part of the frame's result row directly (sel[8] | pts[8] | kp[50][6]): no gather launch
     const int R = BP_RESULT_FLOATS;
     yn.forward(yn.input_nhwc(), true, p->batch, nullptr, p->conf, p->num_classes, p->results, s, R);
     // a6-a7: box rescale + crop window + bilinear crop into the KPD's NHWC input
-    bp::launch_crop(p->frames, p->batch, p->H, p->W, p->use_fixed ? nullptr : p->results, reso,
+    bp::launch_crop(p->resize.frames, p->batch, p->H, p->W, p->use_fixed ? nullptr : p->results, reso,
                     p->use_fixed ? p->fixed_box : nullptr, kn.input_nhwc(), nullptr, p->results + 8, kn.in_h(), kn.in_w(), s, R, R);
     // a8-a9: KPD + heat-map arg-max
     kn.forward(kn.input_nhwc(), true, p->batch, p->hm, p->results + 16, s, R);
     // a10 (opt-in): decode, pPose-NMS, pruning and PnP on the records just written (pose_tail.hip)
-    if (p->pose_on && p->ransac_trials > 0) pose_tail_ransac(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->ransac_err,
-                                                             p->ransac_trials, p->ransac_samples.data(), p->ransac_need.data(),
-                                                             p->poses, p->ransac_ws, s);
-    else if (p->pose_on) bp::launch_pose_tail(p->results, p->batch, p->kp3d, p->cam, p->left_number, p->poses, s);
+    p->pose.enqueue(p->results, p->batch, s);
     BP_HIP(hipGetLastError());
 }
 
@@ -1025,46 +940,25 @@ int bp_pipeline_create(bp_yolo* y, bp_kpd* k, int frame_h, int frame_w, int batc
     BP_HIP(hipSetDevice(y->device));
     std::unique_ptr<bp_pipeline> p(new bp_pipeline);
     p->y = y; p->k = k; p->H = frame_h; p->W = frame_w; p->batch = batch; p->conf = conf; p->num_classes = num_classes;
-    const int reso = y->net->reso();
-    p->frames = d_frames ? d_frames : (uint8_t*)p->arena.alloc_bytes((size_t)batch * frame_h * frame_w * 3);
-    p->tmp = (uint8_t*)p->arena.alloc_bytes((size_t)batch * frame_h * reso * 3);
+    p->engines = {{y->net.get()}, {k->net.get()}};
+    p->resize.init(p->arena, d_frames, batch, frame_h, frame_w, y->net->reso());
     p->results = d_results ? d_results : p->arena.alloc((size_t)batch * BP_RESULT_FLOATS);
     p->hm = d_hm ? d_hm : p->arena.alloc((size_t)batch * 50 * k->net->out_h() * k->net->out_w());
     p->fixed_box = p->arena.alloc((size_t)batch * 4);
-    const bp::ResizePlan ph = bp::make_bicubic_plan(frame_w, reso), pv = bp::make_bicubic_plan(frame_h, reso);
-    p->ksh = ph.ksize; p->ksv = pv.ksize;
-    p->hb = (int*)p->arena.alloc_bytes(ph.bounds.size() * 4);
-    p->hk = (int*)p->arena.alloc_bytes(ph.coeffs.size() * 4);
-    p->vb = (int*)p->arena.alloc_bytes(pv.bounds.size() * 4);
-    p->vk = (int*)p->arena.alloc_bytes(pv.coeffs.size() * 4);
-    BP_HIP(hipMemcpy(p->hb, ph.bounds.data(), ph.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->hk, ph.coeffs.data(), ph.coeffs.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vb, pv.bounds.data(), pv.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vk, pv.coeffs.data(), pv.coeffs.size() * 4, hipMemcpyHostToDevice));
     BP_HIP(hipMemset(p->results, 0, (size_t)batch * BP_RESULT_FLOATS * sizeof(float)));
     *out = p.release();
     return 0;
     BP_CATCH
 }
 void bp_pipeline_destroy(bp_pipeline* p) { delete p; }
-uint8_t* bp_pipeline_frames(bp_pipeline* p) { return p ? p->frames : nullptr; }
+uint8_t* bp_pipeline_frames(bp_pipeline* p) { return p ? p->resize.frames : nullptr; }
 float* bp_pipeline_results(bp_pipeline* p) { return p ? p->results : nullptr; }
 float* bp_pipeline_heatmaps(bp_pipeline* p) { return p ? p->hm : nullptr; }
-int bp_pipeline_kernel_count(bp_pipeline* p) {
-    if (!p || !p->graph) return -1;
-    size_t n = 0;
-    if (hipGraphGetNodes(p->graph, nullptr, &n) != hipSuccess) return -1;
-    return (int)n;
-}
-
-static void drop_graph(bp_pipeline* p) {
-    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
-}
+int bp_pipeline_kernel_count(bp_pipeline* p) { return p ? p->graph.nodes() : -1; }
 
 int bp_pipeline_set_fixed_box(bp_pipeline* p, const float* box) {
     BP_TRY
-    drop_graph(p);
+    p->graph.drop();
     p->use_fixed = box != nullptr;
     if (box) {
         std::vector<float> h((size_t)p->batch * 4);
@@ -1079,39 +973,25 @@ int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, co
                                 double* d_poses) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    drop_graph(p);
+    p->graph.drop();
     if (!kp3d) {
-        p->pose_on = false;
+        p->pose.off();
         return 0;
     }
-    BP_CHECK(K, "null camera matrix");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
-    BP_HIP(hipSetDevice(p->y->device));
-    if (!p->kp3d) p->kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
-    if (!d_poses && !p->own_poses) {
-        p->own_poses = (double*)p->arena.alloc_bytes((size_t)p->batch * BP_POSE_DOUBLES * sizeof(double));
-        BP_HIP(hipMemset(p->own_poses, 0, (size_t)p->batch * BP_POSE_DOUBLES * sizeof(double)));
-    }
-    p->poses = d_poses ? d_poses : p->own_poses;
-    BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    p->cam = bp::make_pnp_cam(K);
-    p->left_number = left_number;
-    p->pose_on = true;
-    if (p->ransac_trials > 0)   // the RANSAC setting stays; its tables are per point count
-        ransac_tables(left_number < 50 ? left_number : 50, p->ransac_trials, p->ransac_conf, p->ransac_samples, p->ransac_need);
+    const int dev = p->y->device;
+    p->pose.set(p->arena, dev, kp3d, n_kp, K, left_number,
+                d_poses ? d_poses : bp::own_pose_rows(p->arena, dev, p->own_poses, p->batch));
     return 0;
     BP_CATCH
 }
-double* bp_pipeline_poses(bp_pipeline* p) { return p ? p->poses : nullptr; }
+double* bp_pipeline_poses(bp_pipeline* p) { return p ? p->pose.poses : nullptr; }
 
 int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
                          int left_number, double* d_poses, void* stream) {
     BP_TRY
     BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
     BP_CHECK(batch >= 0, "batch must be >= 0");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    bp::check_pose_points(n_kp, left_number);
     if (batch == 0) return 0;
     bp::launch_pose_tail(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
@@ -1125,8 +1005,7 @@ int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, 
     BP_CHECK(d_records && d_counts && d_kp3d && K && d_poses && d_merged && d_info, "null argument");
     BP_CHECK(frames >= 0, "frames must be >= 0");
     BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    bp::check_pose_points(n_kp, left_number);
     if (frames == 0) return 0;
     bp::launch_pose_tail_cands(d_records, d_counts, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, d_merged, d_info,
                                (hipStream_t)stream);
@@ -1142,8 +1021,7 @@ int bp_pose_instances_from_merged(const float* d_merged, const int* d_info, cons
     BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
     BP_CHECK(d_merged && d_info && d_poses && d_kp3d && K && d_inst_poses, "null argument");
     BP_CHECK(frames >= 0 && frames <= 65535, "frames must be in [0, 65535]");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
+    bp::check_pose_points(n_kp, left_number);
     if (frames == 0) return 0;
     bp::launch_pose_instances(d_merged, d_info, d_poses, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_inst_poses,
                               (hipStream_t)stream);
@@ -1194,13 +1072,13 @@ int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double
     BP_CHECK(d_pts3d && d_pts2d && K && d_Rt && d_status, "null argument");
     BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_ransac_batch: n must be in [0, 64] points per problem");
     BP_CHECK(P >= 0, "P must be >= 0");
-    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    bp::check_ransac_params(reproj_err, max_trials, confidence);
     if (P == 0) return 0;
     BP_CHECK(d_workspace && workspace_bytes >= bp::pnp_ransac_workspace_bytes(P, max_trials),
              "bp_solve_pnp_ransac_batch: workspace smaller than bp_pnp_ransac_workspace_bytes(P, max_trials)");
     BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_solve_pnp_ransac_batch: workspace must be 8-byte aligned");
     std::vector<int> samples, need;
-    ransac_tables(n, max_trials, confidence, samples, need);
+    bp::ransac_tables(n, max_trials, confidence, samples, need);
     bp::launch_pnp_ransac(d_pts3d, shared_3d ? 0 : (size_t)n * 3, d_pts2d, (size_t)n * 2, nullptr, n, P, bp::make_pnp_cam(K), reproj_err,
                           max_trials, samples.data(), need.data(), d_workspace, d_Rt, d_status, d_inliers, nullptr,
                           (hipStream_t)stream);
@@ -1212,29 +1090,15 @@ int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double
 int bp_pipeline_set_pose_ransac(bp_pipeline* p, double reproj_err, int max_trials, double confidence) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    drop_graph(p);
-    if (max_trials == 0) {
-        p->ransac_trials = 0;
-        return 0;
-    }
-    BP_CHECK(p->pose_on, "bp_pipeline_set_pose_ransac: set a pose solver first (bp_pipeline_set_pose_solver)");
-    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
-    BP_HIP(hipSetDevice(p->y->device));
-    const size_t bytes = pose_ransac_ws_bytes(p->batch, max_trials);
-    if (bytes > p->ransac_ws_bytes) {
-        p->ransac_ws = p->arena.alloc_bytes(bytes);
-        p->ransac_ws_bytes = bytes;
-    }
-    p->ransac_err = reproj_err;
-    p->ransac_conf = confidence;
-    ransac_tables(p->left_number < 50 ? p->left_number : 50, max_trials, confidence, p->ransac_samples, p->ransac_need);
-    p->ransac_trials = max_trials;
+    p->graph.drop();
+    BP_CHECK(max_trials == 0 || p->pose.on, "bp_pipeline_set_pose_ransac: set a pose solver first (bp_pipeline_set_pose_solver)");
+    p->pose.set_ransac(p->arena, p->y->device, p->batch, reproj_err, max_trials, confidence);
     return 0;
     BP_CATCH
 }
 
 size_t bp_pose_ransac_workspace_bytes(int batch, int max_trials) {
-    return batch > 0 && max_trials > 0 ? pose_ransac_ws_bytes(batch, max_trials) : 0;
+    return batch > 0 && max_trials > 0 ? bp::pose_ransac_ws_bytes(batch, max_trials) : 0;
 }
 
 int bp_pose_from_records_ransac(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
@@ -1243,85 +1107,36 @@ int bp_pose_from_records_ransac(const float* d_records, int batch, const double*
     BP_TRY
     BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
     BP_CHECK(batch >= 0, "batch must be >= 0");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
-    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    bp::check_pose_points(n_kp, left_number);
+    bp::check_ransac_params(reproj_err, max_trials, confidence);
     if (batch == 0) return 0;
-    BP_CHECK(d_workspace && workspace_bytes >= pose_ransac_ws_bytes(batch, max_trials),
+    BP_CHECK(d_workspace && workspace_bytes >= bp::pose_ransac_ws_bytes(batch, max_trials),
              "bp_pose_from_records_ransac: workspace smaller than bp_pose_ransac_workspace_bytes(batch, max_trials)");
     BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_pose_from_records_ransac: workspace must be 8-byte aligned");
     std::vector<int> samples, need;
-    ransac_tables(left_number < 50 ? left_number : 50, max_trials, confidence, samples, need);
-    pose_tail_ransac(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
+    bp::ransac_tables(bp::pose_points(left_number), max_trials, confidence, samples, need);
+    bp::pose_tail_ransac(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
                      d_poses, d_workspace, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
 }
 
-// (re)build the frame's hipGraph when the launch plan changed since the capture -- records the launches, executes nothing
-static void pipeline_capture(bp_pipeline* p) {
-    if (p->exec && (p->ver_y != p->y->net->plan_version() || p->ver_k != p->k->net->plan_version())) {
-        // launch policy / precision changed since the capture: the recorded kernels are stale
-        (void)hipGraphExecDestroy(p->exec);
-        (void)hipGraphDestroy(p->graph);
-        p->exec = nullptr;
-        p->graph = nullptr;
-    }
-    if (!p->exec) {
-        p->ver_y = p->y->net->plan_version();
-        p->ver_k = p->k->net->plan_version();
-        if (!p->cap_stream) BP_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
-        BP_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
-        try {
-            pipeline_enqueue(p, p->cap_stream);
-        } catch (...) {
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(p->cap_stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            throw;
-        }
-        BP_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
-        BP_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
-    }
-}
-
 int bp_pipeline_prepare(bp_pipeline* p) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    pipeline_capture(p);
+    p->graph.capture(p->engines, [p](hipStream_t s) { pipeline_enqueue(p, s); });
     return 0;
     BP_CATCH
-}
-
-static void pipeline_launch(bp_pipeline* p, int use_graph, hipStream_t s) {
-    if (!use_graph) {
-        pipeline_enqueue(p, s);
-        return;
-    }
-    pipeline_capture(p);
-    BP_HIP(hipGraphLaunch(p->exec, s));
 }
 
 int bp_pipeline_run(bp_pipeline* p, int use_graph, void* stream) {
     BP_TRY
     BP_CHECK(p, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    pipeline_launch(p, use_graph, s);
-    // Lone-frame latency mode (bp_*_set_prefetch): a launch that found a K slice on the wrong XCD raised the engine's error word and
-    // left its tile unstored, so the frame's record is void.  The mode is one-frame-at-a-time by definition: wait for the frame here,
-    // read the words, and on a fault clear them, switch the mode off for both engines and run the SAME frame again on the ordinary
-    // hand-off -- whoever drives the pipeline (FramePipeline.run, StreamedRunner, a C caller) gets a valid record or an error.
-    if (p->y->net->prefetch() || p->k->net->prefetch()) {
-        BP_HIP(hipSetDevice(p->y->device));
-        const int bad = p->y->net->take_xcd_errors(s) + p->k->net->take_xcd_errors(s);
-        if (bad) {
-            ++p->latency_faults;
-            p->y->net->set_prefetch(false);
-            p->k->net->set_prefetch(false);
-            pipeline_launch(p, use_graph, s);
-        }
-    }
+    auto launch = [&] { p->graph.launch(use_graph, s, p->engines, [p](hipStream_t q) { pipeline_enqueue(p, q); }); };
+    launch();
+    bp::latency_rerun(p->engines, p->y->device, s, p->latency_faults, launch);   // (lone-frame latency mode only)
     return 0;
     BP_CATCH
 }
@@ -1334,19 +1149,15 @@ int bp_pipeline_latency_faults(const bp_pipeline* p) { return p ? p->latency_fau
 static void scene_enqueue(bp_scene* p, hipStream_t s) {
     bp::YoloNet& yn = *p->y->net;
     const int reso = yn.reso(), R = BP_RESULT_FLOATS, K = (int)p->slots.size();
-    bp::ResizeTables t{p->hb, p->hk, p->ksh, p->vb, p->vk, p->ksv};
-    bp::launch_resize_bicubic(p->frames, 1, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    p->resize.enqueue(1, p->H, p->W, yn.input_nhwc(), reso, s);
     yn.forward_classes(yn.input_nhwc(), true, 1, nullptr, p->conf, p->num_classes, p->class_ids.data(), K, p->results, s, K * R, R);
     for (int k = 0; k < K; ++k) {
         bp_scene_slot& sl = p->slots[k];
         bp::KpdNet& kn = *sl.k->net;
         float* row = p->results + (size_t)k * R;
-        bp::launch_crop(p->frames, 1, p->H, p->W, row, reso, nullptr, kn.input_nhwc(), nullptr, row + 8, kn.in_h(), kn.in_w(), s, R, R);
+        bp::launch_crop(p->resize.frames, 1, p->H, p->W, row, reso, nullptr, kn.input_nhwc(), nullptr, row + 8, kn.in_h(), kn.in_w(), s, R, R);
         kn.forward(kn.input_nhwc(), true, 1, nullptr, row + 16, s, R);
-        if (sl.pose_on && sl.ransac_trials > 0)
-            pose_tail_ransac(row, 1, sl.kp3d, sl.cam, sl.left_number, sl.ransac_err, sl.ransac_trials, sl.ransac_samples.data(),
-                             sl.ransac_need.data(), sl.poses, sl.ransac_ws, s);
-        else if (sl.pose_on) bp::launch_pose_tail(row, 1, sl.kp3d, sl.cam, sl.left_number, sl.poses, s);
+        sl.pose.enqueue(row, 1, s);
     }
     BP_HIP(hipGetLastError());
 }
@@ -1362,28 +1173,18 @@ int bp_scene_create(bp_yolo* y, bp_kpd* const* kpds, const int* class_ids, int K
     p->y = y; p->H = frame_h; p->W = frame_w; p->conf = conf; p->num_classes = num_classes;
     p->class_ids.assign(class_ids, class_ids + K);
     p->slots.resize(K);
+    p->engines = {{y->net.get()}};
     for (int k = 0; k < K; ++k) {
         BP_CHECK(kpds[k], "null key-point engine");
         BP_CHECK(kpds[k]->net->out_c() == 50, "scene expects 50 key points");
         BP_CHECK(kpds[k]->device == y->device, "scene: every engine on the detector's device");
         for (int j = 0; j < k; ++j) BP_CHECK(kpds[j] != kpds[k], "scene: one key-point engine per object (its activations are the slot's)");
         p->slots[k].k = kpds[k];
+        p->engines.push_back({kpds[k]->net.get()});
     }
     BP_HIP(hipSetDevice(y->device));
-    const int reso = y->net->reso();
-    p->frames = d_frames ? d_frames : (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * frame_w * 3);
-    p->tmp = (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * reso * 3);
+    p->resize.init(p->arena, d_frames, 1, frame_h, frame_w, y->net->reso());
     p->results = d_results ? d_results : p->arena.alloc((size_t)K * BP_RESULT_FLOATS);
-    const bp::ResizePlan ph = bp::make_bicubic_plan(frame_w, reso), pv = bp::make_bicubic_plan(frame_h, reso);
-    p->ksh = ph.ksize; p->ksv = pv.ksize;
-    p->hb = (int*)p->arena.alloc_bytes(ph.bounds.size() * 4);
-    p->hk = (int*)p->arena.alloc_bytes(ph.coeffs.size() * 4);
-    p->vb = (int*)p->arena.alloc_bytes(pv.bounds.size() * 4);
-    p->vk = (int*)p->arena.alloc_bytes(pv.coeffs.size() * 4);
-    BP_HIP(hipMemcpy(p->hb, ph.bounds.data(), ph.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->hk, ph.coeffs.data(), ph.coeffs.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vb, pv.bounds.data(), pv.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vk, pv.coeffs.data(), pv.coeffs.size() * 4, hipMemcpyHostToDevice));
     BP_HIP(hipMemset(p->results, 0, (size_t)K * BP_RESULT_FLOATS * sizeof(float)));
     *out = p.release();
     return 0;
@@ -1392,44 +1193,21 @@ int bp_scene_create(bp_yolo* y, bp_kpd* const* kpds, const int* class_ids, int K
 void bp_scene_destroy(bp_scene* s) { delete s; }
 float* bp_scene_results(bp_scene* s) { return s ? s->results : nullptr; }
 double* bp_scene_poses(bp_scene* s) { return s ? s->own_poses : nullptr; }
-int bp_scene_kernel_count(bp_scene* s) {
-    if (!s || !s->graph) return -1;
-    size_t n = 0;
-    if (hipGraphGetNodes(s->graph, nullptr, &n) != hipSuccess) return -1;
-    return (int)n;
-}
-static void scene_drop_graph(bp_scene* p) {
-    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
-}
+int bp_scene_kernel_count(bp_scene* s) { return s ? s->graph.nodes() : -1; }
 
 int bp_scene_set_pose_solver(bp_scene* p, int k, const double* kp3d, int n_kp, const double* K, int left_number, double* d_poses_row) {
     BP_TRY
     BP_CHECK(p, "null argument");
     BP_CHECK(k >= 0 && k < (int)p->slots.size(), "scene: slot out of range");
-    bp_scene_slot& sl = p->slots[k];
-    scene_drop_graph(p);
+    bp::PoseSolver& pose = p->slots[k].pose;
+    p->graph.drop();
     if (!kp3d) {
-        sl.pose_on = false;
+        pose.off();
         return 0;
     }
-    BP_CHECK(K, "null camera matrix");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
-    BP_HIP(hipSetDevice(p->y->device));
-    if (!sl.kp3d) sl.kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
-    if (!d_poses_row && !p->own_poses) {
-        const size_t bytes = p->slots.size() * BP_POSE_DOUBLES * sizeof(double);
-        p->own_poses = (double*)p->arena.alloc_bytes(bytes);
-        BP_HIP(hipMemset(p->own_poses, 0, bytes));
-    }
-    sl.poses = d_poses_row ? d_poses_row : p->own_poses + (size_t)k * BP_POSE_DOUBLES;
-    BP_HIP(hipMemcpy(sl.kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    sl.cam = bp::make_pnp_cam(K);
-    sl.left_number = left_number;
-    sl.pose_on = true;
-    if (sl.ransac_trials > 0)
-        ransac_tables(left_number < 50 ? left_number : 50, sl.ransac_trials, sl.ransac_conf, sl.ransac_samples, sl.ransac_need);
+    const int dev = p->y->device;
+    pose.set(p->arena, dev, kp3d, n_kp, K, left_number,
+             d_poses_row ? d_poses_row : bp::own_pose_rows(p->arena, dev, p->own_poses, p->slots.size()) + (size_t)k * BP_POSE_DOUBLES);
     return 0;
     BP_CATCH
 }
@@ -1438,87 +1216,29 @@ int bp_scene_set_pose_ransac(bp_scene* p, int k, double reproj_err, int max_tria
     BP_TRY
     BP_CHECK(p, "null argument");
     BP_CHECK(k >= 0 && k < (int)p->slots.size(), "scene: slot out of range");
-    bp_scene_slot& sl = p->slots[k];
-    scene_drop_graph(p);
-    if (max_trials == 0) {
-        sl.ransac_trials = 0;
-        return 0;
-    }
-    BP_CHECK(sl.pose_on, "bp_scene_set_pose_ransac: set the slot's pose solver first (bp_scene_set_pose_solver)");
-    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
-    BP_HIP(hipSetDevice(p->y->device));
-    const size_t bytes = pose_ransac_ws_bytes(1, max_trials);
-    if (bytes > sl.ransac_ws_bytes) {
-        sl.ransac_ws = p->arena.alloc_bytes(bytes);
-        sl.ransac_ws_bytes = bytes;
-    }
-    sl.ransac_err = reproj_err;
-    sl.ransac_conf = confidence;
-    ransac_tables(sl.left_number < 50 ? sl.left_number : 50, max_trials, confidence, sl.ransac_samples, sl.ransac_need);
-    sl.ransac_trials = max_trials;
+    bp::PoseSolver& pose = p->slots[k].pose;
+    p->graph.drop();
+    BP_CHECK(max_trials == 0 || pose.on, "bp_scene_set_pose_ransac: set the slot's pose solver first (bp_scene_set_pose_solver)");
+    pose.set_ransac(p->arena, p->y->device, 1, reproj_err, max_trials, confidence);
     return 0;
     BP_CATCH
-}
-
-// bp_pipeline's rule, for the detector and every key-point engine: a plan that changed since the capture makes the graph stale
-static void scene_capture(bp_scene* p) {
-    bool stale = p->ver_y != p->y->net->plan_version();
-    for (const bp_scene_slot& sl : p->slots) stale = stale || sl.ver_k != sl.k->net->plan_version();
-    if (p->exec && stale) scene_drop_graph(p);
-    if (!p->exec) {
-        p->ver_y = p->y->net->plan_version();
-        for (bp_scene_slot& sl : p->slots) sl.ver_k = sl.k->net->plan_version();
-        if (!p->cap_stream) BP_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
-        BP_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
-        try {
-            scene_enqueue(p, p->cap_stream);
-        } catch (...) {
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(p->cap_stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            throw;
-        }
-        BP_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
-        BP_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
-    }
 }
 
 int bp_scene_prepare(bp_scene* p) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    scene_capture(p);
+    p->graph.capture(p->engines, [p](hipStream_t s) { scene_enqueue(p, s); });
     return 0;
     BP_CATCH
-}
-
-static void scene_launch(bp_scene* p, int use_graph, hipStream_t s) {
-    if (!use_graph) {
-        scene_enqueue(p, s);
-        return;
-    }
-    scene_capture(p);
-    BP_HIP(hipGraphLaunch(p->exec, s));
 }
 
 int bp_scene_run(bp_scene* p, int use_graph, void* stream) {
     BP_TRY
     BP_CHECK(p, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    scene_launch(p, use_graph, s);
-    // lone-frame latency mode: bp_pipeline_run's rule over every engine of the scene
-    bool latency = p->y->net->prefetch();
-    for (const bp_scene_slot& sl : p->slots) latency = latency || sl.k->net->prefetch();
-    if (latency) {
-        BP_HIP(hipSetDevice(p->y->device));
-        int bad = p->y->net->take_xcd_errors(s);
-        for (bp_scene_slot& sl : p->slots) bad += sl.k->net->take_xcd_errors(s);
-        if (bad) {
-            ++p->latency_faults;
-            p->y->net->set_prefetch(false);
-            for (bp_scene_slot& sl : p->slots) sl.k->net->set_prefetch(false);
-            scene_launch(p, use_graph, s);
-        }
-    }
+    auto launch = [&] { p->graph.launch(use_graph, s, p->engines, [p](hipStream_t q) { scene_enqueue(p, q); }); };
+    launch();
+    bp::latency_rerun(p->engines, p->y->device, s, p->latency_faults, launch);
     return 0;
     BP_CATCH
 }
@@ -1531,17 +1251,17 @@ static void cands_enqueue(bp_cands* p, hipStream_t s) {
     bp::YoloNet& yn = *p->y->net;
     bp::KpdNet& kn = *p->k->net;
     const int reso = yn.reso(), R = BP_RESULT_FLOATS, C = p->C;
-    bp::ResizeTables t{p->hb, p->hk, p->ksh, p->vb, p->vk, p->ksv};
-    bp::launch_resize_bicubic(p->frames, 1, p->H, p->W, p->tmp, yn.input_nhwc(), nullptr, reso, reso, t, 1, s);
+    const bp::PoseSolver& ps = p->pose;
+    p->resize.enqueue(1, p->H, p->W, yn.input_nhwc(), reso, s);
     yn.forward_nms(yn.input_nhwc(), true, 1, nullptr, p->conf, p->num_classes, p->class_id, p->nms_conf, C, p->results, p->counts, s,
                    C * R, R);
-    bp::launch_crop(p->frames, C, p->H, p->W, p->results, reso, nullptr, kn.input_nhwc(), nullptr, p->results + 8, kn.in_h(), kn.in_w(),
+    bp::launch_crop(p->resize.frames, C, p->H, p->W, p->results, reso, nullptr, kn.input_nhwc(), nullptr, p->results + 8, kn.in_h(), kn.in_w(),
                     s, R, R, C);
     kn.forward(kn.input_nhwc(), true, C, nullptr, p->results + 16, s, R);
-    if (p->pose_on)
-        bp::launch_pose_tail_cands(p->results, p->counts, 1, C, p->kp3d, p->cam, p->left_number, p->pose, p->merged, p->info, s);
-    if (p->pose_on && p->inst_on)
-        bp::launch_pose_instances(p->merged, p->info, p->pose, 1, C, p->kp3d, p->cam, p->left_number, p->inst, s);
+    if (ps.on)
+        bp::launch_pose_tail_cands(p->results, p->counts, 1, C, ps.kp3d, ps.cam, ps.left_number, ps.poses, p->merged, p->info, s);
+    if (ps.on && p->inst_on)
+        bp::launch_pose_instances(p->merged, p->info, ps.poses, 1, C, ps.kp3d, ps.cam, ps.left_number, p->inst, s);
     BP_HIP(hipGetLastError());
 }
 
@@ -1561,21 +1281,10 @@ int bp_cands_create(bp_yolo* y, bp_kpd* k, int max_candidates, int frame_h, int 
     std::unique_ptr<bp_cands> p(new bp_cands);
     p->y = y; p->k = k; p->C = C; p->H = frame_h; p->W = frame_w; p->conf = conf; p->nms_conf = nms_conf;
     p->num_classes = num_classes; p->class_id = class_id;
-    const int reso = y->net->reso();
-    p->frames = d_frame ? d_frame : (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * frame_w * 3);
-    p->tmp = (uint8_t*)p->arena.alloc_bytes((size_t)frame_h * reso * 3);
+    p->engines = {{y->net.get()}, {k->net.get()}};
+    p->resize.init(p->arena, d_frame, 1, frame_h, frame_w, y->net->reso());
     p->results = d_results ? d_results : p->arena.alloc((size_t)C * BP_RESULT_FLOATS);
     p->counts = (int*)p->arena.alloc_bytes(sizeof(int));
-    const bp::ResizePlan ph = bp::make_bicubic_plan(frame_w, reso), pv = bp::make_bicubic_plan(frame_h, reso);
-    p->ksh = ph.ksize; p->ksv = pv.ksize;
-    p->hb = (int*)p->arena.alloc_bytes(ph.bounds.size() * 4);
-    p->hk = (int*)p->arena.alloc_bytes(ph.coeffs.size() * 4);
-    p->vb = (int*)p->arena.alloc_bytes(pv.bounds.size() * 4);
-    p->vk = (int*)p->arena.alloc_bytes(pv.coeffs.size() * 4);
-    BP_HIP(hipMemcpy(p->hb, ph.bounds.data(), ph.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->hk, ph.coeffs.data(), ph.coeffs.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vb, pv.bounds.data(), pv.bounds.size() * 4, hipMemcpyHostToDevice));
-    BP_HIP(hipMemcpy(p->vk, pv.coeffs.data(), pv.coeffs.size() * 4, hipMemcpyHostToDevice));
     BP_HIP(hipMemset(p->results, 0, (size_t)C * BP_RESULT_FLOATS * sizeof(float)));
     BP_HIP(hipMemset(p->counts, 0, sizeof(int)));
     *out = p.release();
@@ -1585,50 +1294,31 @@ int bp_cands_create(bp_yolo* y, bp_kpd* k, int max_candidates, int frame_h, int 
 void bp_cands_destroy(bp_cands* s) { delete s; }
 float* bp_cands_results(bp_cands* s) { return s ? s->results : nullptr; }
 int* bp_cands_counts(bp_cands* s) { return s ? s->counts : nullptr; }
-double* bp_cands_pose(bp_cands* s) { return s ? s->pose : nullptr; }
+double* bp_cands_pose(bp_cands* s) { return s ? s->pose.poses : nullptr; }
 float* bp_cands_merged(bp_cands* s) { return s ? s->merged : nullptr; }
 int* bp_cands_info(bp_cands* s) { return s ? s->info : nullptr; }
 double* bp_cands_instance_poses(bp_cands* s) { return s && s->inst_on ? s->inst : nullptr; }
-int bp_cands_kernel_count(bp_cands* s) {
-    if (!s || !s->graph) return -1;
-    size_t n = 0;
-    if (hipGraphGetNodes(s->graph, nullptr, &n) != hipSuccess) return -1;
-    return (int)n;
-}
-static void cands_drop_graph(bp_cands* p) {
-    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
-}
+int bp_cands_kernel_count(bp_cands* s) { return s ? s->graph.nodes() : -1; }
 
 int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const double* K, int left_number, double* d_pose) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    cands_drop_graph(p);
+    p->graph.drop();
     if (!kp3d) {
-        p->pose_on = false;
+        p->pose.off();
         p->inst_on = false;          // the instance poses read the tail's outputs
         return 0;
     }
-    BP_CHECK(K, "null camera matrix");
-    BP_CHECK(n_kp == 50, "the pose solver takes one 3-D point per key point (50)");
-    BP_CHECK(left_number >= 0, "left_number must be >= 0");
-    BP_HIP(hipSetDevice(p->y->device));
-    if (!p->kp3d) {
-        p->kp3d = (double*)p->arena.alloc_bytes(50 * 3 * sizeof(double));
+    const int dev = p->y->device;
+    if (!p->info) {   // the tail's other outputs, before the tail can be on
+        BP_HIP(hipSetDevice(dev));
         p->merged = p->arena.alloc((size_t)p->C * 152);
-        p->info = (int*)p->arena.alloc_bytes(4 * sizeof(int));
         BP_HIP(hipMemset(p->merged, 0, (size_t)p->C * 152 * sizeof(float)));
-        BP_HIP(hipMemset(p->info, 0, 4 * sizeof(int)));
+        int* info = (int*)p->arena.alloc_bytes(4 * sizeof(int));
+        BP_HIP(hipMemset(info, 0, 4 * sizeof(int)));
+        p->info = info;
     }
-    if (!d_pose && !p->own_pose) {
-        p->own_pose = (double*)p->arena.alloc_bytes(BP_POSE_DOUBLES * sizeof(double));
-        BP_HIP(hipMemset(p->own_pose, 0, BP_POSE_DOUBLES * sizeof(double)));
-    }
-    p->pose = d_pose ? d_pose : p->own_pose;
-    BP_HIP(hipMemcpy(p->kp3d, kp3d, 50 * 3 * sizeof(double), hipMemcpyHostToDevice));
-    p->cam = bp::make_pnp_cam(K);
-    p->left_number = left_number;
-    p->pose_on = true;
+    p->pose.set(p->arena, dev, kp3d, n_kp, K, left_number, d_pose ? d_pose : bp::own_pose_rows(p->arena, dev, p->own_pose, 1));
     return 0;
     BP_CATCH
 }
@@ -1636,77 +1326,33 @@ int bp_cands_set_pose_solver(bp_cands* p, const double* kp3d, int n_kp, const do
 int bp_cands_set_instance_poses(bp_cands* p, int on, double* d_inst_poses) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    BP_CHECK(p->pose_on, "bp_cands_set_instance_poses: set a pose solver first (bp_cands_set_pose_solver)");
-    cands_drop_graph(p);
+    BP_CHECK(p->pose.on, "bp_cands_set_instance_poses: set a pose solver first (bp_cands_set_pose_solver)");
+    p->graph.drop();
     if (!on) {
         p->inst_on = false;
         return 0;
     }
-    BP_HIP(hipSetDevice(p->y->device));
-    const size_t bytes = (size_t)p->C * BP_POSE_DOUBLES * sizeof(double);
-    if (!d_inst_poses && !p->own_inst) {
-        p->own_inst = (double*)p->arena.alloc_bytes(bytes);
-        BP_HIP(hipMemset(p->own_inst, 0, bytes));
-    }
-    p->inst = d_inst_poses ? d_inst_poses : p->own_inst;
+    p->inst = d_inst_poses ? d_inst_poses : bp::own_pose_rows(p->arena, p->y->device, p->own_inst, p->C);
     p->inst_on = true;
     return 0;
     BP_CATCH
 }
 
-static void cands_capture(bp_cands* p) {
-    if (p->exec && (p->ver_y != p->y->net->plan_version() || p->ver_k != p->k->net->plan_version())) cands_drop_graph(p);
-    if (!p->exec) {
-        p->ver_y = p->y->net->plan_version();
-        p->ver_k = p->k->net->plan_version();
-        if (!p->cap_stream) BP_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
-        BP_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
-        try {
-            cands_enqueue(p, p->cap_stream);
-        } catch (...) {
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(p->cap_stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            throw;
-        }
-        BP_HIP(hipStreamEndCapture(p->cap_stream, &p->graph));
-        BP_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
-    }
-}
-
 int bp_cands_prepare(bp_cands* p) {
     BP_TRY
     BP_CHECK(p, "null argument");
-    cands_capture(p);
+    p->graph.capture(p->engines, [p](hipStream_t s) { cands_enqueue(p, s); });
     return 0;
     BP_CATCH
-}
-
-static void cands_launch(bp_cands* p, int use_graph, hipStream_t s) {
-    if (!use_graph) {
-        cands_enqueue(p, s);
-        return;
-    }
-    cands_capture(p);
-    BP_HIP(hipGraphLaunch(p->exec, s));
 }
 
 int bp_cands_run(bp_cands* p, int use_graph, void* stream) {
     BP_TRY
     BP_CHECK(p, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    cands_launch(p, use_graph, s);
-    // lone-frame latency mode: bp_pipeline_run's rule
-    if (p->y->net->prefetch() || p->k->net->prefetch()) {
-        BP_HIP(hipSetDevice(p->y->device));
-        const int bad = p->y->net->take_xcd_errors(s) + p->k->net->take_xcd_errors(s);
-        if (bad) {
-            ++p->latency_faults;
-            p->y->net->set_prefetch(false);
-            p->k->net->set_prefetch(false);
-            cands_launch(p, use_graph, s);
-        }
-    }
+    auto launch = [&] { p->graph.launch(use_graph, s, p->engines, [p](hipStream_t q) { cands_enqueue(p, q); }); };
+    launch();
+    bp::latency_rerun(p->engines, p->y->device, s, p->latency_faults, launch);
     return 0;
     BP_CATCH
 }
@@ -1825,7 +1471,7 @@ int bp_solve_pnp_ransac(const double* pts3d, const double* pts2d, int n, const d
                         int max_trials, double confidence, double* R, double* t, unsigned char* inliers) {
     BP_TRY
     BP_CHECK(pts3d && pts2d && K && R && t, "null argument");
-    BP_CHECK(reproj_err > 0 && max_trials >= 1 && confidence > 0 && confidence < 1, "RANSAC parameters out of range");
+    bp::check_ransac_params(reproj_err, max_trials, confidence);
     const int rc = bp::solve_pnp_ransac(pts3d, pts2d, n, K, reproj_err, max_trials, confidence, R, t, inliers);
     if (rc != 0) throw bp::Error("solve_pnp_ransac failed (need >= 6 points and a 6-point consensus)");
     return 0;

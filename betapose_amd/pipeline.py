@@ -26,7 +26,70 @@ POSE_DOUBLES = _lib.POSE_DOUBLES
 PNP_FAILED = "solve_pnp failed (need >= 6 non-degenerate points, or >= 4 coplanar ones)"   # bp_solve_pnp's error text
 
 
-class FramePipeline:
+class _FrameChain:
+    """What the three per-frame pipelines share -- the Python side of csrc/frame_chain.h.  A subclass names the prefix of
+    its C entry points in ``_C``, creates ``frames`` and ``results`` and hands its handle to ``_open``."""
+    _C = ""            # bp_pipeline / bp_scene / bp_cands
+    _h = None
+    poses = None       # torch f64 [rows, POSE_DOUBLES] once set_pose_solver was called
+
+    def _fn(self, name: str):
+        return getattr(_lib.lib(), "%s_%s" % (self._C, name))
+
+    def _call(self, name: str, *args):
+        _lib.check(self._fn(name)(self._h, *args))
+
+    def _open(self, h):
+        self._h = h
+        self._run = self._fn("run")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                self._fn("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _solver_args(self, kp3d, cam_K, rows: int):
+        """(kp3d [n, 3], cam_K [3, 3]) as contiguous f64 arrays for the C call; ``self.poses`` [rows, 166] exists afterwards."""
+        import torch
+        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
+        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
+        if self.poses is None:
+            self.poses = torch.zeros((rows, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
+            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
+        return k3, Kc
+
+    def enqueue(self, stream: Optional[int] = None):
+        """Launch the device part on ``stream`` (default: torch's current stream).  ``self.frames`` must already hold the
+        frame(s); ``self.results`` (and ``self.poses``) are valid once the stream reaches this point."""
+        _lib.check(self._run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
+
+    def prepare(self):
+        """Set-up: build the frame's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
+        if self.use_graph:
+            self._call("prepare")
+        return self
+
+    def kernel_count(self) -> int:
+        return self._fn("kernel_count")(self._h)
+
+    def run(self, frames_bgr_u8) -> np.ndarray:
+        """Convenience: upload the frame(s) (numpy [H,W,3] / [B,H,W,3] u8 or cuda tensor), run, return the records
+        [rows,316] (host)."""
+        import torch
+        f = frames_bgr_u8 if hasattr(frames_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frames_bgr_u8))
+        if f.dim() == 3:
+            f = f.unsqueeze(0)
+        self.frames.copy_(f, non_blocking=True)
+        self.enqueue()
+        return self.results.cpu().numpy()
+
+
+class FramePipeline(_FrameChain):
+    _C = "bp_pipeline"
+
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, batch: int = 1,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, keep_heatmaps: bool = False,
                  frames=None):
@@ -35,7 +98,6 @@ class FramePipeline:
         self.det, self.pose = det_model, getattr(pose_model, "pyranet", pose_model)
         self.H, self.W, self.batch = int(frame_h), int(frame_w), int(batch)
         self.use_graph = bool(use_graph)
-        dev = "cuda:%d" % self.det._device if self.det._device is not None else "cuda"
         self.det.cuda()
         self.pose.cuda()
         dev = "cuda:%d" % self.det._device
@@ -49,25 +111,16 @@ class FramePipeline:
                                                  float(confidence), int(num_classes), self.frames.data_ptr(),
                                                  self.results.data_ptr(),
                                                  self.heatmaps.data_ptr() if keep_heatmaps else None, C.byref(h)))
-        self._h = h
+        self._open(h)
         self._faults_seen = 0
-        self.poses = None          # torch f64 [B, POSE_DOUBLES] once set_pose_solver was called
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                _lib.lib().bp_pipeline_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def set_fixed_box(self, box_xyxy=None):
         """Throughput runs with a deterministic crop: box in frame pixels, or None."""
         if box_xyxy is None:
-            _lib.check(_lib.lib().bp_pipeline_set_fixed_box(self._h, None))
+            self._call("set_fixed_box", None)
         else:
             b = np.ascontiguousarray(box_xyxy, dtype=np.float32)
-            _lib.check(_lib.lib().bp_pipeline_set_fixed_box(self._h, b.ctypes.data))
+            self._call("set_fixed_box", b.ctypes.data)
 
     def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50, ransac=None):
         """Opt-in device pose tail: every run then also writes ``self.poses`` [B, 166] f64, the frame's pose record
@@ -75,18 +128,12 @@ class FramePipeline:
         ``kp3d`` [50, 3]: the 3-D key points; ``cam_K`` [3, 3]; ``left_number``: --left_keypoints.  None switches it off.
         ``ransac``: ``(reproj_err, max_trials, confidence)`` solves with the device RANSAC (``set_pose_ransac``) instead
         of the plain iterative PnP; None: the iterative tail."""
-        import torch
         if kp3d is None:
-            _lib.check(_lib.lib().bp_pipeline_set_pose_ransac(self._h, 0.0, 0, 0.0))
-            _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, None, 0, None, 0, None))
+            self._call("set_pose_ransac", 0.0, 0, 0.0)
+            self._call("set_pose_solver", None, 0, None, 0, None)
             return self
-        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
-        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
-        if self.poses is None:
-            self.poses = torch.zeros((self.batch, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
-            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
-        _lib.check(_lib.lib().bp_pipeline_set_pose_solver(self._h, k3.ctypes.data, k3.shape[0], Kc.ctypes.data,
-                                                          int(left_number), self.poses.data_ptr()))
+        k3, Kc = self._solver_args(kp3d, cam_K, self.batch)
+        self._call("set_pose_solver", k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number), self.poses.data_ptr())
         return self.set_pose_ransac(ransac)
 
     def set_pose_ransac(self, ransac=None):
@@ -94,38 +141,19 @@ class FramePipeline:
         hypotheses in parallel (bp_pipeline_set_pose_ransac) -- the host solver's result, its inlier set in slot 15 of
         the pose row.  None (or ``max_trials`` 0): back to the iterative tail."""
         err, trials, conf = (0.0, 0, 0.0) if ransac is None else ransac
-        _lib.check(_lib.lib().bp_pipeline_set_pose_ransac(self._h, float(err), int(trials), float(conf)))
+        self._call("set_pose_ransac", float(err), int(trials), float(conf))
         return self
 
     def enqueue(self, stream: Optional[int] = None):
         """Launch the device part on ``stream`` (default: torch's current stream).  ``self.frames`` must
         already hold the batch; ``self.results`` is valid once the stream reaches this point."""
-        _lib.check(_lib.lib().bp_pipeline_run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
+        super().enqueue(stream)
         if any(getattr(m, "_latency_mode", False) for m in (self.det, self.pose)):
             self._latency_check()
 
     def latency_faults(self) -> int:
         """Frames this pipeline ran twice because the lone-frame latency mode's placement check failed (bp_pipeline_latency_faults)."""
         return int(_lib.lib().bp_pipeline_latency_faults(self._h))
-
-    def prepare(self):
-        """Set-up: build the frame's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
-        if self.use_graph:
-            _lib.check(_lib.lib().bp_pipeline_prepare(self._h))
-        return self
-
-    def kernel_count(self) -> int:
-        return _lib.lib().bp_pipeline_kernel_count(self._h)
-
-    def run(self, frames_bgr_u8) -> np.ndarray:
-        """Convenience: upload frames (numpy [B,H,W,3] u8 or cuda tensor), run, return records [B,316] (host)."""
-        import torch
-        f = frames_bgr_u8 if hasattr(frames_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frames_bgr_u8))
-        if f.dim() == 3:
-            f = f.unsqueeze(0)
-        self.frames.copy_(f, non_blocking=True)
-        self.enqueue()
-        return self.results.cpu().numpy()
 
     def _latency_check(self) -> bool:
         """Lone-frame latency mode only (Darknet.set_prefetch).  ``bp_pipeline_run`` itself waits for the frame in that mode, reads the
@@ -144,13 +172,14 @@ class FramePipeline:
         return True
 
 
-class ScenePipeline:
+class ScenePipeline(_FrameChain):
     """A frame with several objects behind ONE multi-class detector pass (``bp_scene_*``): bicubic resize once, the shared
     detector once with the per-class select, then per object crop -> its key-point net -> arg-max -> (opt-in) its pose
     tail, all on one stream in one hipGraph.  ``pose_models``: {obj_id: FastPoseHIP}; ``class_of``: {obj_id: class id of
     the detector}.  ``results`` [K, 316] and ``poses`` [K, 166] hold one row per object in the order of ``obj_ids`` (the
     order of ``pose_models``); a row is the record ``FramePipeline`` writes for that object, select slots [6], [7] = class
     score, class id.  A class without a detection leaves index -1 in its row (``finish_record`` -> ``boxes`` None)."""
+    _C = "bp_scene"
 
     def __init__(self, det_model, pose_models: dict, class_of: dict, frame_h: int = 480, frame_w: int = 640,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, frames=None):
@@ -175,76 +204,38 @@ class ScenePipeline:
         self.frames = frames if frames is not None else torch.zeros((1, self.H, self.W, 3), dtype=torch.uint8, device=dev)
         assert tuple(self.frames.shape) == (1, self.H, self.W, 3) and self.frames.dtype == torch.uint8
         self.results = torch.zeros((self.K, RESULT_FLOATS), dtype=torch.float32, device=dev)
-        self.poses = None          # torch f64 [K, POSE_DOUBLES] once set_pose_solver was called
         kpds = (C.c_void_p * self.K)(*[m.handle for m in self.poses_nets])
         ids = (C.c_int * self.K)(*self.class_ids)
         h = C.c_void_p()
         _lib.check(_lib.lib().bp_scene_create(self.det.handle, C.cast(kpds, C.c_void_p), C.cast(ids, C.c_void_p), self.K, self.H,
                                               self.W, float(confidence), int(num_classes), self.frames.data_ptr(),
                                               self.results.data_ptr(), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                _lib.lib().bp_scene_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._open(h)
 
     def set_pose_solver(self, obj_id, kp3d=None, cam_K=None, left_number: int = 50, ransac=None):
         """``FramePipeline.set_pose_solver`` for one object of the scene: its runs then also write row
         ``obj_ids.index(obj_id)`` of ``self.poses``.  ``kp3d`` None switches that object's tail off."""
-        import torch
         k = self.obj_ids.index(obj_id)
-        L = _lib.lib()
         if kp3d is None:
-            _lib.check(L.bp_scene_set_pose_ransac(self._h, k, 0.0, 0, 0.0))
-            _lib.check(L.bp_scene_set_pose_solver(self._h, k, None, 0, None, 0, None))
+            self._call("set_pose_ransac", k, 0.0, 0, 0.0)
+            self._call("set_pose_solver", k, None, 0, None, 0, None)
             return self
-        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
-        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
-        if self.poses is None:
-            self.poses = torch.zeros((self.K, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
-            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
-        _lib.check(L.bp_scene_set_pose_solver(self._h, k, k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number),
-                                              self.poses.data_ptr() + k * POSE_DOUBLES * 8))
+        k3, Kc = self._solver_args(kp3d, cam_K, self.K)
+        self._call("set_pose_solver", k, k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number),
+                   self.poses.data_ptr() + k * POSE_DOUBLES * 8)
         err, trials, conf = (0.0, 0, 0.0) if ransac is None else ransac
-        _lib.check(L.bp_scene_set_pose_ransac(self._h, k, float(err), int(trials), float(conf)))
+        self._call("set_pose_ransac", k, float(err), int(trials), float(conf))
         return self
 
-    def enqueue(self, stream: Optional[int] = None):
-        """Launch the frame on ``stream`` (default: torch's current stream).  ``self.frames`` must already hold it;
-        ``self.results`` (and ``self.poses``) are valid once the stream reaches this point."""
-        _lib.check(_lib.lib().bp_scene_run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
 
-    def prepare(self):
-        """Build the scene's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
-        if self.use_graph:
-            _lib.check(_lib.lib().bp_scene_prepare(self._h))
-        return self
-
-    def kernel_count(self) -> int:
-        return _lib.lib().bp_scene_kernel_count(self._h)
-
-    def run(self, frame_bgr_u8) -> np.ndarray:
-        """Convenience: upload one frame (numpy [H,W,3] u8 or cuda tensor), run, return the rows [K,316] (host)."""
-        import torch
-        f = frame_bgr_u8 if hasattr(frame_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frame_bgr_u8))
-        if f.dim() == 3:
-            f = f.unsqueeze(0)
-        self.frames.copy_(f, non_blocking=True)
-        self.enqueue()
-        return self.results.cpu().numpy()
-
-
-class CandidatePipeline:
+class CandidatePipeline(_FrameChain):
     """A frame through several NMS survivors of the detector (``bp_cands_*``): bicubic resize, the detector, the select
     with box NMS (``write_results``' NMS branch live, up to ``candidates`` boxes), ONE crop launch and ONE key-point pass
     at batch ``candidates``, arg-max, (opt-in) the candidate pose tail -- pPose-NMS merges the candidates' key points and
     the PnP runs on ``result[0]``.  ``results`` [C, 316] holds one ``FramePipeline`` record per candidate in survivor
     order, ``counts`` [1] their number; unused rows carry index -1.  ``pose_model`` needs ``max_batch >= candidates``.
     With ``candidates=1`` the row (and the pose row) is ``FramePipeline``'s, bit for bit."""
+    _C = "bp_cands"
 
     def __init__(self, det_model, pose_model, frame_h: int = 480, frame_w: int = 640, candidates: int = 4,
                  nms_conf: float = 0.6, confidence: float = 0.01, num_classes: int = 80, class_id: int = 0,
@@ -263,7 +254,6 @@ class CandidatePipeline:
         self.frames = frames if frames is not None else torch.zeros((1, self.H, self.W, 3), dtype=torch.uint8, device=dev)
         assert tuple(self.frames.shape) == (1, self.H, self.W, 3) and self.frames.dtype == torch.uint8
         self.results = torch.zeros((Cn, RESULT_FLOATS), dtype=torch.float32, device=dev)
-        self.poses = None          # torch f64 [1, POSE_DOUBLES] once set_pose_solver was called
         self.merged = None         # torch f32 [C, MERGED_FLOATS]: device copies of the tail's merged poses ...
         self.info = None           # ... and int32 [4]: n, m, index of result[0], mask of the candidates merged into it
         self.inst_poses = None     # torch f64 [C, POSE_DOUBLES] with set_pose_solver(..., all_instances=True)
@@ -271,16 +261,8 @@ class CandidatePipeline:
         _lib.check(_lib.lib().bp_cands_create(self.det.handle, self.pose.handle, Cn, self.H, self.W, float(confidence),
                                               int(num_classes), int(class_id), float(nms_conf), self.frames.data_ptr(),
                                               self.results.data_ptr(), C.byref(h)))
-        self._h = h
+        self._open(h)
         self.counts = _device_view(_lib.lib().bp_cands_counts(self._h), (1,), torch.int32, self.results.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                _lib.lib().bp_cands_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def set_pose_solver(self, kp3d=None, cam_K=None, left_number: int = 50, all_instances: bool = False):
         """Opt-in candidate pose tail: every run then also writes ``self.poses`` [1, 166] f64 (``FramePipeline``'s pose
@@ -291,16 +273,11 @@ class CandidatePipeline:
         import torch
         L = _lib.lib()
         if kp3d is None:
-            _lib.check(L.bp_cands_set_pose_solver(self._h, None, 0, None, 0, None))
+            self._call("set_pose_solver", None, 0, None, 0, None)
             self.inst_poses = None
             return self
-        k3 = np.ascontiguousarray(np.asarray(kp3d, dtype=np.float64).reshape(-1, 3))
-        Kc = np.ascontiguousarray(np.asarray(cam_K, dtype=np.float64).reshape(3, 3))
-        if self.poses is None:
-            self.poses = torch.zeros((1, POSE_DOUBLES), dtype=torch.float64, device=self.results.device)
-            torch.cuda.current_stream(self.poses.device).synchronize()   # the fill is done before any stream writes rows
-        _lib.check(L.bp_cands_set_pose_solver(self._h, k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number),
-                                              self.poses.data_ptr()))
+        k3, Kc = self._solver_args(kp3d, cam_K, 1)
+        self._call("set_pose_solver", k3.ctypes.data, k3.shape[0], Kc.ctypes.data, int(left_number), self.poses.data_ptr())
         dev = self.results.device
         self.merged = _device_view(L.bp_cands_merged(self._h), (self.C, _lib.MERGED_FLOATS), torch.float32, dev)
         self.info = _device_view(L.bp_cands_info(self._h), (4,), torch.int32, dev)
@@ -308,34 +285,15 @@ class CandidatePipeline:
             if self.inst_poses is None:
                 self.inst_poses = torch.zeros((self.C, POSE_DOUBLES), dtype=torch.float64, device=dev)
                 torch.cuda.current_stream(dev).synchronize()
-            _lib.check(L.bp_cands_set_instance_poses(self._h, 1, self.inst_poses.data_ptr()))
+            self._call("set_instance_poses", 1, self.inst_poses.data_ptr())
         elif self.inst_poses is not None:
-            _lib.check(L.bp_cands_set_instance_poses(self._h, 0, None))
+            self._call("set_instance_poses", 0, None)
             self.inst_poses = None
         return self
 
-    def enqueue(self, stream: Optional[int] = None):
-        """Launch the frame on ``stream`` (default: torch's current stream).  ``self.frames`` must already hold it."""
-        _lib.check(_lib.lib().bp_cands_run(self._h, int(self.use_graph), stream if stream is not None else _lib.current_stream()))
-
-    def prepare(self):
-        """Build the frame's hipGraph now (capture + instantiate, nothing executes) instead of inside the first ``enqueue``."""
-        if self.use_graph:
-            _lib.check(_lib.lib().bp_cands_prepare(self._h))
-        return self
-
-    def kernel_count(self) -> int:
-        return _lib.lib().bp_cands_kernel_count(self._h)
-
     def run(self, frame_bgr_u8):
         """Convenience: upload one frame (numpy [H,W,3] u8 or cuda tensor), run, return (rows [C,316], count) (host)."""
-        import torch
-        f = frame_bgr_u8 if hasattr(frame_bgr_u8, "is_cuda") else torch.from_numpy(np.ascontiguousarray(frame_bgr_u8))
-        if f.dim() == 3:
-            f = f.unsqueeze(0)
-        self.frames.copy_(f, non_blocking=True)
-        self.enqueue()
-        return self.results.cpu().numpy(), int(self.counts.cpu()[0])
+        return super().run(frame_bgr_u8), int(self.counts.cpu()[0])
 
 
 # A frame's candidate results as ONE f32 row (StreamedRunner(candidates=C), the harness' gather): the pose row first (f64,

@@ -253,6 +253,83 @@ def test_graph_replay_and_kernel_counts(det15, poses):
     assert counts[4] < 4 * single
 
 
+@pytest.fixture(scope="module")
+def own_poses(cuda):
+    """Two key-point engines of this test's own (their precision is toggled): object 1 at max_batch 2, object 5."""
+    def make(obj, max_batch):
+        stream = fastpose_stream_from_state_dict(synth.synth_fastpose_state_dict(synth.object_seeds(obj)[1], 50), 50)
+        return FastPoseHIP.from_stream(stream, n_classes=50, max_batch=max_batch).cuda().set_precision("bf16x3")
+    return {1: make(1, 2), 5: make(5, 1)}
+
+
+@pytest.mark.parametrize("chain", ["pipeline", "scene", "cands"])
+def test_graph_follows_a_plan_change(det15, own_poses, chain):
+    """The rule the three chains share (csrc/frame_chain.h): a captured graph is rebuilt when an engine's launch plan
+    changed or the pose tail was toggled.  After ``set_precision`` on ONE key-point engine the graph chain must write what
+    a fresh eager chain over the same engines writes, bit for bit; the pose tail is one graph node."""
+    from betapose_amd.pipeline import CandidatePipeline
+    objs = [1, 5]
+    frame = helpers.frames(1)[0]
+    if chain == "pipeline":
+        changed = own_poses[1]
+
+        def make(use_graph):
+            return FramePipeline(det15, own_poses[1], 480, 640, batch=1, confidence=CONF, use_graph=use_graph)
+
+        def solver(c, on):
+            c.set_pose_solver(*((_kp3d(1), synth.CAM_K, LEFT) if on else ()))
+    elif chain == "scene":
+        changed = own_poses[5]                                # the second slot's engine
+
+        def make(use_graph):
+            return _scene(det15, own_poses, objs, solver=False, use_graph=use_graph)
+
+        def solver(c, on):
+            for o in objs if on else objs[1:]:               # off: the second slot's tail alone
+                c.set_pose_solver(o, *((_kp3d(o), synth.CAM_K, LEFT) if on else ()))
+    else:
+        changed = own_poses[1]
+
+        def make(use_graph):
+            return CandidatePipeline(det15, own_poses[1], 480, 640, candidates=2, confidence=CONF, class_id=CLASS_OF[1],
+                                     use_graph=use_graph)
+
+        def solver(c, on):
+            c.set_pose_solver(*((_kp3d(1), synth.CAM_K, LEFT) if on else ()))
+
+    def run(c):
+        c.run(frame)
+        return _bits(c.results.cpu().numpy()).copy(), _bits(c.poses.cpu().numpy()).copy()
+
+    g = make(True)
+    solver(g, True)
+    first = run(g)
+    changed.set_precision("f32")
+    try:
+        at_f32 = run(g)
+        ref = make(False)
+        solver(ref, True)
+        ref = run(ref)
+    finally:
+        changed.set_precision("bf16x3")
+    assert not np.array_equal(at_f32[0], first[0]), "input condition: the precision moves the key-point record"
+    for a, b in zip(at_f32, ref):
+        np.testing.assert_array_equal(a, b)
+
+    back = run(g)
+    n_on = g.kernel_count()
+    solver(g, False)
+    g.run(frame)
+    n_off = g.kernel_count()
+    solver(g, True)
+    again = run(g)
+    print("%s: graph nodes with the tail %d, without %d" % (chain, n_on, n_off))
+    assert n_off == n_on - 1 and g.kernel_count() == n_on
+    for a, b, c in zip(first, back, again):
+        np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(a, c)
+
+
 def _write_frames(tmp_path, frames):
     from PIL import Image
     indir = tmp_path / "rgb"
