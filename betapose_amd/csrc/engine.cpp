@@ -722,6 +722,14 @@ void Net::find_fuse_groups() {
         }
         return n == 1 ? idx : -1;
     };
+    // readers() finds the ops that start at a tensor's pointer.  A member of a concat buffer is also read THROUGH the buffer -- the convolution
+    // behind the route starts at the buffer's base -- and a head tensor by the decode kernels (f32_readers_): an output that is to stay inside
+    // the fused launch must be a whole allocation of its own that only ops read
+    auto private_out = [&](const ConvParams& c) {
+        for (const float* q : f32_readers_) if (q == c.out) return false;
+        const ActAlloc* a = find_act(c.out);
+        return a == nullptr || (a->base == c.out && c.out_ld == c.Cout);
+    };
     for (int j = 0; j < (int)ops_.size(); ++j) {
         const Op& c3 = ops_[j];
         if (c3.type != OP_CONV || c3.conv.ksize != 3 || c3.conv.stride != 1 || c3.conv.pad != 1) continue;
@@ -729,13 +737,13 @@ void Net::find_fuse_groups() {
         if (i < 0 || i >= j || ops_[i].type != OP_CONV) continue;
         const ConvParams& pre = ops_[i].conv;
         if (!(pre.ksize == 1 && pre.stride == 1 && pre.res == nullptr && pre.res_scale == nullptr && pre.store_mode == ST_NHWC && pre.Cout == c3.conv.Cin)) continue;
-        if (readers(pre.out) != 1 || ops_[i].pool_out) continue;
+        if (readers(pre.out) != 1 || !private_out(pre) || ops_[i].pool_out) continue;
         if (i != j - 1) continue;                // (the members are consecutive launches in both networks: nothing runs between them)
         FuseGroup g{i, j, -1};
         if (j + 1 < (int)ops_.size() && ops_[j + 1].type == OP_CONV) {
             const ConvParams& post = ops_[j + 1].conv;
             if (post.in == c3.conv.out && post.in_ld == c3.conv.out_ld && post.ksize == 1 && post.stride == 1 && c3.conv.res == nullptr &&
-                c3.conv.store_mode == ST_NHWC && readers(c3.conv.out) == 1 && !ops_[j].pool_out)
+                c3.conv.store_mode == ST_NHWC && readers(c3.conv.out) == 1 && private_out(c3.conv) && !ops_[j].pool_out)
                 g.post = j + 1;
         }
         fuse_groups_.push_back(g);
@@ -940,6 +948,12 @@ void Net::plan_planes(int prec, int mix_hw) {
         for (Op& op : ops_)
             if (op.type == OP_CONV && op.conv.res)
                 if (ActAlloc* r = find_act(op.conv.res); r && (op.conv.res - r->base) % 8 == 0 && r->elems % 8 == 0 && (op.conv.res_ld & 7) == 0) r->wanted = true;
+    // The unfused add / upsample / copy convert behind their fp32 store with 16-byte loads and 8-byte plane stores (launch_f32_to_planes): a
+    // view of theirs with C % 4, ld % 4 or an offset % 4 != 0 (an 18-channel concat member) cannot be converted, so its allocation stays
+    // on fp32 and its readers on the fp32 kernels -- decided here, not by a failed launch in the middle of a pass.
+    for (const Op& op : ops_)
+        if (op.type == OP_ADD || op.type == OP_UPSAMPLE || op.type == OP_COPYCH)
+            if (ActAlloc* o = find_act(op.out); o && o->wanted && !(op.C % 4 == 0 && op.out_ld % 4 == 0 && (op.out - o->base) % 4 == 0)) o->wanted = false;
     for (ActAlloc& a : acts_)
         if (a.wanted && !a.planes) {
             a.planes = (unsigned short*)arena_.alloc_bytes(3 * a.elems * sizeof(unsigned short));
@@ -991,8 +1005,9 @@ void Net::plan_planes(int prec, int mix_hw) {
         BP_HIP(hipGetLastError());
         BP_HIP(hipDeviceSynchronize());
     }
-    // Which fp32 tensors does anything still read?  Residual operands, the inputs of the pooling / shuffle / add kernels
-    // and of convolutions that run on the fp32 kernels; everything else that has planes is read through them only, and
+    // Which fp32 tensors does anything still read?  Residual operands, the inputs of the pooling / shuffle / add / upsample / copy
+    // kernels and of convolutions that run on the fp32 kernels, and what f32_readers_ lists (tensors read by kernels that are not
+    // ops: the YOLO heads); everything else that has planes is read through them only, and
     // its producers drop the fp32 store (4 of 10 bytes per element in the bf16x3 mode, 4 of 6 in the fp16 mode; the
     // dirty lines a kernel leaves behind are written back before its successor starts).  BP_KEEP_F32=1 keeps them all.
     static const bool keep_all = std::getenv("BP_KEEP_F32") != nullptr;
@@ -1003,7 +1018,7 @@ void Net::plan_planes(int prec, int mix_hw) {
     if (f16_res_ && np == 1)
         for (Op& op : ops_)
             if (op.type == OP_CONV && op.conv.res)
-                if (ActAlloc* r = find_act(op.conv.res); r && r->planes && (op.conv.res - r->base) % 4 == 0 && (op.conv.res_ld & 3) == 0)
+                if (ActAlloc* r = find_act(op.conv.res); r && r->planes && r->wanted && (op.conv.res - r->base) % 4 == 0 && (op.conv.res_ld & 3) == 0)
                     op.conv.res16 = r->planes + (op.conv.res - r->base);
     for (const Op& op : ops_) {
         if (op.type == OP_CONV) {
@@ -1016,6 +1031,7 @@ void Net::plan_planes(int prec, int mix_hw) {
             mark(op.a); mark(op.b);
         }
     }
+    for (const float* q : f32_readers_) mark(q);   // (readers that are not ops: the YOLO decode kernels read the head tensors)
     for (Op& op : ops_)
         if (op.type == OP_CONV && op.conv.out16)
             if (ActAlloc* o = find_act(op.conv.out)) op.conv.skip_f32 = o->f32_read ? 0 : 1;
@@ -1226,7 +1242,8 @@ void Net::run_op_unfused(const Op& op, int batch, hipStream_t s) {
             launch_conv(p, tile, s);
         } break;
         // (producers that are not convolutions: the pooling / shuffle kernels write their operand planes themselves; the
-        // unfused add / upsample / copy fall-backs, which the two networks' default cfgs never emit, convert behind them)
+        // unfused add / upsample / copy fall-backs convert behind them -- out16 is set only where plan_planes() found the view
+        // convertible.  The two networks' default cfgs never emit the three; tests/cfg_topologies.py has cfgs that do)
         case OP_MAXPOOL:
             launch_maxpool3s2p1(op.a, op.out, batch, op.H, op.W, op.C, op.OH, op.OW, s, op.out16, op.out16_plane, planes_np(precision_));
             break;
@@ -1340,9 +1357,13 @@ void Net::tap_copy(int i, int batch, float* d_out_nchw, hipStream_t s) {
         }
     // a tensor whose producers dropped the fp32 store (plan_planes) is rebuilt from its planes first: exact in the
     // bf16x3 mode (the planes ARE the fp32 value), the fp16-rounded value in the fp16 mode
+    // -- channel range by channel range, for the convolutions that really skipped the store: the unfused add / upsample / copy always
+    // store fp32, and what they stored is what the tap shows (in the fp16 mode the plane holds its rounded value)
     if (ActAlloc* a = find_act(t.p); a && a->planes && !a->f32_read && precision_ != PREC_F32)
-        launch_planes_to_f32(a->planes + (t.p - a->base), (long long)a->elems, precision_ == PREC_F16 ? 1 : 3, t.p, t.ld,
-                             (long long)batch * t.H * t.W, t.C, s);
+        for (const Op& o : ops_)
+            if (o.type == OP_CONV && o.conv.skip_f32 && o.conv.out16 && o.conv.out_ld == t.ld && o.conv.out >= t.p && o.conv.out < t.p + t.C)
+                launch_planes_to_f32(a->planes + (o.conv.out - a->base), (long long)a->elems, precision_ == PREC_F16 ? 1 : 3, o.conv.out, t.ld,
+                                     (long long)batch * t.H * t.W, std::min(o.conv.Cout, (int)(t.p + t.C - o.conv.out)), s);
     launch_nhwc_to_nchw(t.p, t.ld, d_out_nchw, batch, t.C, t.H, t.W, s);
     BP_HIP(hipGetLastError());
 }
@@ -1595,6 +1616,7 @@ YoloNet::YoloNet(const std::string& cfg_text, const float* stream, size_t n_floa
                 h.ah[a] = (float)an[2 * mask[a] + 1];
             }
             heads_.push_back(h);
+            f32_readers_.push_back(t.p);     // launch_yolo_decode* reads the fp32 head tensor: a convolution that also reads it (a route behind the [yolo] layer) must not cost it its store
             row_off += 3 * t.H * t.W;
         }
     }

@@ -134,9 +134,15 @@ protected:
     float* upload_weights(const float* host, size_t count);   // through the shared store (reused by clones)
     // activation allocations (new_tensor) and their operand planes: planes mirror the fp32 allocation element for element
     // (bp_common.h ConvParams::in16), so every view (pointer, ld) into an allocation has its planes view for free
+    // wanted: the producers of this allocation write its planes under the current plan -- some 16-bit convolution reads them AND every
+    // producer can write them (the unfused add / upsample / copy convert behind their fp32 store with 16-byte accesses: C, ld and the view
+    // offset must be multiples of 4); readers of an allocation that is not wanted stay on the fp32 kernels.
+    // f32_read: something reads the fp32 tensor -- a residual, a convolution on an fp32 kernel, the pooling / add / upsample / copy kernels
+    // (all found in ops_), or a kernel that is not an op at all and is listed in f32_readers_ (the YOLO heads' decode)
     struct ActAlloc { float* base = nullptr; size_t elems = 0; unsigned short* planes = nullptr; bool wanted = false;
-                      bool f32_read = true; };   // f32_read: something reads the fp32 tensor (a residual, a pooling kernel, a head)
+                      bool f32_read = true; };
     std::vector<ActAlloc> acts_;
+    std::vector<const float*> f32_readers_;   // fp32 activations read by kernels outside ops_: plan_planes() never drops their store
     ActAlloc* find_act(const float* p);
     void plan_planes(int prec, int mix_hw = 0);   // allocate the planes 16-bit consumers need, point every producer / consumer at them
     int max_batch_;
