@@ -125,6 +125,14 @@ PROTOTYPES = {
                                        vp]),
     "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                 C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "bp_icp_normal_equations": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp]),
+    "bp_icp_normal_equations_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,
+                                               C.c_double, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "bp_refine_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                  C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "bp_refine_depth_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, vp, vp]),
     "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
     "bp_pipeline_poses": (vp, [vp]),
     "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),

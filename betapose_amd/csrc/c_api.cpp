@@ -13,6 +13,7 @@
 #include "engine.h"
 #include "frame_chain.h"
 #include "frame_io.h"
+#include "icp.h"
 #include "pose_tail.h"
 #include "raster.h"
 
@@ -708,6 +709,123 @@ int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const
     bp::launch_vsd_finish(acc, d_test_index, T, P, n_tau, d_err, d_counts, s);
     BP_HIP(hipGetLastError());
     BP_HIP(hipStreamSynchronize(s));   // the renders live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+// what the four refinement calls check alike, and the parameter block they hand on
+static bp::IcpParams icp_params(const double* K, int T, double depth_scale, int iterations, double max_dist, double min_cos,
+                                int min_pixels, double pixel_center) {
+    BP_CHECK(T > 0, "T must be positive");
+    BP_CHECK(depth_scale > 0.0 && max_dist > 0.0, "depth_scale and max_dist must be positive");
+    BP_CHECK(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must lie in [0, 1]");
+    BP_CHECK(iterations >= 0 && iterations <= 1000 && min_pixels >= 0, "iterations must lie in 0 .. 1000, min_pixels >= 0");
+    return bp::IcpParams{K[0], K[4], K[2], K[5], pixel_center, depth_scale, max_dist, min_cos, min_pixels, iterations};
+}
+
+// poses per chunk of the device calls: the z-buffers and the posed meshes of a chunk each stay under RASTER_WS_BYTES
+static size_t icp_chunk(int chunk, int n, int P, size_t HW) {
+    size_t c = (size_t)chunk;
+    if (c == 0) c = std::min(RASTER_WS_BYTES / (HW * sizeof(float)), RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1));
+    return std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+}
+
+int bp_icp_normal_equations_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                                 const double* K, const uint16_t* depth_test, int T, int H, int W, double depth_scale,
+                                 const int* test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                                 double* out) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && out, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
+    BP_CHECK(bp::icp_normal_equations_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z,
+                                           out) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_refine_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         const uint16_t* depth_test, int T, int H, int W, double depth_scale, const int* test_index,
+                         int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                         double* poses_out, double* stats) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && poses_out && stats, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
+    BP_CHECK(bp::refine_depth_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z, poses_out,
+                                   stats) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_icp_normal_equations(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P,
+                            const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                            const int* d_test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                            int chunk, double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_out, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(chunk >= 0, "chunk must not be negative");
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
+    const int slices = bp::icp_slices(H, W);
+    bp::Arena a;
+    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(c * HW * sizeof(uint32_t));
+    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)c));
+    int* skipped = (int*)a.alloc_bytes(c * sizeof(int));
+    double* partial = (double*)a.alloc_bytes(c * slices * bp::ICP_ACC * sizeof(double));
+    BP_HIP(hipMemsetAsync(skipped, 0, c * sizeof(int), s));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)m * HW, s));   // +inf
+        bp::launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, m, nullptr, 0, K, H, W, pixel_center, near_z, ws, zbuf,
+                          skipped, s);
+        bp::launch_icp_accumulate(zbuf, d_poses + p0 * 12, m, d_depth_test, T, d_test_index + p0, H, W, prm, nullptr, partial, s);
+        bp::launch_icp_sum(partial, d_test_index + p0, T, m, slices, d_out + p0 * bp::ICP_ACC, s);
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_refine_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    const uint16_t* d_depth_test, int T, int H, int W, double depth_scale, const int* d_test_index,
+                    int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                    int chunk, double* d_poses_out, double* d_stats, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_poses_out && d_stats, "null argument");
+    BP_CHECK(d_poses_out != d_poses, "d_poses_out must not be d_poses: a rejected pose gets its input back");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(chunk >= 0, "chunk must not be negative");
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
+    const int slices = bp::icp_slices(H, W);
+    bp::Arena a;
+    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(c * HW * sizeof(uint32_t));
+    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)c));
+    int* skipped = (int*)a.alloc_bytes(c * sizeof(int));
+    double* partial = (double*)a.alloc_bytes(c * slices * bp::ICP_ACC * sizeof(double));
+    BP_HIP(hipMemsetAsync(skipped, 0, c * sizeof(int), s));
+    bp::launch_icp_init(d_poses, d_test_index, T, P, d_poses_out, d_stats, s);
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        double* pose = d_poses_out + p0 * 12;
+        double* stats = d_stats + p0 * bp::ICP_STATS;
+        // the whole loop is enqueued: no host round trip between the iterations
+        for (int k = 0; k <= iterations; ++k) {
+            BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)m * HW, s));   // +inf
+            bp::launch_raster(d_model, n, d_faces, F, pose, m, nullptr, 0, K, H, W, pixel_center, near_z, ws, zbuf, skipped, s);
+            bp::launch_icp_accumulate(zbuf, pose, m, d_depth_test, T, d_test_index + p0, H, W, prm, stats, partial, s);
+            bp::launch_icp_step(partial, m, slices, k, prm, d_poses + p0 * 12, pose, stats, s);
+        }
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
     return 0;
     BP_CATCH
 }

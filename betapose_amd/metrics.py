@@ -577,6 +577,116 @@ def pose_errors_vsd(gt_poses, est_poses, vertices, faces, K, depth_test_u16, tes
         return d_err.cpu().numpy(), d_counts.cpu().numpy()
 
 
+ICP_ACC = 29                                                # csrc/icp.h ICP_ACC
+ICP_STATUS = ("OK", "TOO_FEW", "SINGULAR", "DIVERGED", "REJECTED", "NO_IMAGE")   # stats[:, 5] (csrc/icp_math.inc)
+
+
+def _icp_args(poses, vertices, faces, K, depth_test_u16, test_index):
+    poses = _poses34(poses)
+    vertices, faces = _mesh_args(vertices, faces)
+    dtest = np.ascontiguousarray(depth_test_u16)
+    if dtest.dtype != np.uint16 or dtest.ndim != 3 or dtest.size == 0:
+        raise ValueError("depth_test_u16 must be a non-empty uint16 array [T, H, W]")
+    idx = np.ascontiguousarray(test_index, dtype=np.int32).reshape(-1)
+    if len(idx) != len(poses):
+        raise ValueError("test_index needs one entry per pose")
+    return poses, vertices, faces, np.ascontiguousarray(K, dtype=np.float64).reshape(9), dtest, idx
+
+
+def icp_normal_equations(poses, vertices, faces, K, depth_test_u16, test_index, depth_scale=0.001, max_dist=0.02,
+                         min_cos=0.25, pixel_center=0.0, near=0.01, device=None, chunk=None):
+    """One accumulation of refine_poses_depth at the given poses: float64 [P, 29] = the upper triangle of A = sum J^T J
+    row by row (21), b = sum J^T r (6), the number N of pixels that took part and E = sum r^2.  ``device=None``:
+    bp_icp_normal_equations_host; a torch device: bp_icp_normal_equations on it (bit-identical from call to call and
+    across ``chunk``).  A test index outside [0, T) gives a row of zeros."""
+    from . import _lib
+    poses, vertices, faces, Kf, dtest, idx = _icp_args(poses, vertices, faces, K, depth_test_u16, test_index)
+    T, H, W = dtest.shape
+    P = len(poses)
+    out = np.zeros((P, ICP_ACC), np.float64)
+    if P == 0:
+        return out
+    if device is None:
+        _lib.check(_lib.lib().bp_icp_normal_equations_host(
+            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), _lib.ptr(Kf), _lib.ptr(dtest),
+            T, H, W, float(depth_scale), _lib.ptr(idx), float(max_dist), float(min_cos), float(pixel_center), float(near),
+            _lib.ptr(out)))
+        return out
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
+        d_idx = torch.from_numpy(idx).to(dev)
+        d_out = torch.empty((P, ICP_ACC), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().bp_icp_normal_equations(
+            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_poses), P, _lib.ptr(Kf),
+            _lib.ptr(d_test), T, H, W, float(depth_scale), _lib.ptr(d_idx), float(max_dist), float(min_cos),
+            float(pixel_center), float(near), int(chunk or 0), _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy()
+
+
+def refine_poses_depth(poses, vertices, faces, K, depth_test_u16, test_index, depth_scale=0.001, iterations=8,
+                       max_dist=0.02, min_cos=0.25, min_pixels=32, pixel_center=0.0, near=0.01, device=None, chunk=None):
+    """Depth refinement of P estimated poses of one mesh -- projective point-to-plane ICP against the test depth image:
+    ``(poses_out [P, 3, 4] float64, stats [P, 6] float64)``, stats = (N_first, rms_first, N_last, rms_last,
+    iterations_done, status), status an index into ICP_STATUS.  Units are the mesh's (LineMod: metres); test image
+    ``test_index[p]`` of ``depth_test_u16`` [T, H, W] uint16 has depth ``raw * depth_scale``, 0 = missing.
+
+    Up to ``iterations`` times:
+      1. render the depth z_r of the mesh at the current pose (render_depth, the same conventions);
+      2. for every pixel (x, y) whose own render and whose four neighbours (x +- 1, y), (x, y +- 1) are inside the image
+         and drawn and whose test depth z_t is not 0: the ray d = ((x + c - cx) / fx, (y + c - cy) / fy, 1), the model
+         point q = z_r d (the neighbours' likewise), m = (q(x+1,y) - q(x-1,y)) x (q(x,y+1) - q(x,y-1)); the pixel is
+         left out when |m| = 0; n = m / |m| turned so that n.d <= 0; left out when -(n.d) / |d| < ``min_cos`` (grazing
+         pixels, internal depth edges) or |z_t - z_r| > ``max_dist`` (0.02 m is a fifth of the smallest LineMod
+         diameter); residual r = (z_t - z_r)(n.d), which is (s - q).n with s the observed point on the same ray;
+         q_c = q - t (the twist is about the object's origin), J = [q_c x n, n];
+      3. A = sum J^T J, b = sum J^T r, N, E = sum r^2, rms = sqrt(E / N);
+      4. stop before the step when N < ``min_pixels`` (TOO_FEW), the 6x6 solve finds no pivot (SINGULAR), or the
+         solution has |omega| > 0.5 rad or |v| > 4 max_dist (DIVERGED: the pose before that step is kept);
+      5. else A xi = b, xi = (omega, v), R <- exp(omega) R, t <- t + v.
+    One more accumulation without a step gives N_last and rms_last (for a pose that stopped early they are those of the
+    accumulation it stopped at).  A pose whose rms_last exceeds its rms_first is returned as it came, bit for bit, with
+    status REJECTED and the first pair repeated as the last; a test index outside [0, T) gives NO_IMAGE and the pose
+    unchanged.
+    ``device=None``: the host twin bp_refine_depth_host (no GPU needed); a torch device: bp_refine_depth on it, the loop
+    over the iterations enqueued without a host round trip, ``chunk`` poses at a time (None: a default that keeps the
+    workspaces under 256 MB).  Host and device take the same per-pixel decisions with the same bits and differ only in
+    the order of the sums; the device results are bit-identical from call to call and across chunk sizes."""
+    from . import _lib
+    poses, vertices, faces, Kf, dtest, idx = _icp_args(poses, vertices, faces, K, depth_test_u16, test_index)
+    T, H, W = dtest.shape
+    P = len(poses)
+    out, stats = poses.copy(), np.zeros((P, 6), np.float64)
+    if P == 0:
+        return out, stats
+    if device is None:
+        _lib.check(_lib.lib().bp_refine_depth_host(
+            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), _lib.ptr(Kf), _lib.ptr(dtest),
+            T, H, W, float(depth_scale), _lib.ptr(idx), int(iterations), float(max_dist), float(min_cos), int(min_pixels),
+            float(pixel_center), float(near), _lib.ptr(out), _lib.ptr(stats)))
+        return out, stats
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
+        d_idx = torch.from_numpy(idx).to(dev)
+        d_out = torch.empty((P, 12), dtype=torch.float64, device=dev)
+        d_stats = torch.empty((P, 6), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().bp_refine_depth(
+            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_poses), P, _lib.ptr(Kf),
+            _lib.ptr(d_test), T, H, W, float(depth_scale), _lib.ptr(d_idx), int(iterations), float(max_dist), float(min_cos),
+            int(min_pixels), float(pixel_center), float(near), int(chunk or 0), _lib.ptr(d_out), _lib.ptr(d_stats),
+            torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy().reshape(P, 3, 4), d_stats.cpu().numpy()
+
+
 def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
     """``Model3D.refine`` (utils/model.py:29-46): ``len - keep`` times, delete the first point (in row-major pair
     order) of the closest pair.  Two quirks of the reference are kept: the running minimum of a round starts at the
@@ -594,10 +704,20 @@ def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:
     return v
 
 
+def _depth_stack(depth_frames, nrs):
+    """(test [T, H, W], index [len(nrs)]) of the depth images of the scored frames ``nrs``; KeyError for a missing one."""
+    used = sorted(set(nrs))
+    for nr in used:
+        if nr not in depth_frames:
+            raise KeyError("no depth image for frame %d" % nr)
+    test = np.stack([np.asarray(depth_frames[nr]) for nr in used])
+    return test, np.array([used.index(nr) for nr in nrs], dtype=np.int32)
+
+
 def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model_vertices, cam_K, diameter_mm,
                      pixel_thresh: float = 5.0, symmetric: bool = False, device=None, symmetries=None,
                      image_width: int = 640, match_instances: bool = False, faces=None, depth_frames=None,
-                     depth_scale: float = 0.001):
+                     depth_scale: float = 0.001, refine_depth=None):
     """The metric loop of betapose_evaluate.py:204-266.  ``gt_frames[nr]`` = list of ``{'pose': 4x4, 'bbox': [x, y, w, h]}`` (one per ground-truth
     annotation compared; a bare dict is accepted for one).
     Returns dict(mean_add, mean_2d_acc, mean_iou, mean_add_err_mm, n).  ``symmetric``: also ADD-S (add_s_err) --
@@ -618,8 +738,17 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
     mean over (tau, theta) in BOP_VSD_TAUS x BOP_VSD_THETAS of the fraction of pairs with err(tau) < theta,
     ``mean_vsd_err``, the mean over pairs and taus, and ``mean_visib_fract``, the mean visible fraction of the scored
     ground-truth annotations (those that render at least one pixel).  A scored frame without a depth image raises
-    KeyError."""
-    ious, gts, ests, nrs = [], [], [], []
+    KeyError.
+    ``refine_depth``: a dict of keyword arguments of refine_poses_depth (``{}`` for its defaults; ``faces`` and
+    ``depth_frames`` are needed): every scored estimate is refined against its frame's depth image, with ``cam_K`` and on
+    ``device`` when one is given, BEFORE any error is computed, so every number above is that of the refined poses.  The
+    unrefined pose of each scored frame dict is kept under ``"pose_rgb"`` (4x4; with ``match_instances`` in the scored
+    instance's dict) and the refined one written over ``cam_R`` / ``cam_t``.  Added keys: ``refined``, the number of
+    scored estimates that took at least one step and kept it, ``rejected``, those returned as they came because the
+    residual grew, ``unchanged``, the rest (no step was taken: too few pixels, no image, ``iterations`` 0);
+    ``refined + rejected + unchanged`` is the number of scored pairs; ``mean_rms_first`` and ``mean_rms_last``, the mean
+    rms residual in metres over the estimates with at least one pixel before and after."""
+    ious, gts, ests, nrs, owners = [], [], [], [], []
     for f in final_result:
         nr = int(os.path.basename(f["imgname"])[0:-4])
         if nr not in gt_frames:
@@ -649,6 +778,7 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
                     gts.append(gt["pose"])
                     ests.append(pose)
                     nrs.append(nr)
+                    owners.append(s)
             continue
         for gt in entries:
             if len(f["result"]) < 1 or len(f["result"][0]) < 1:
@@ -665,6 +795,28 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
                 gts.append(gt["pose"])
                 ests.append(pose)
                 nrs.append(nr)
+                owners.append(f)
+    refine_counts = None
+    if refine_depth is not None:
+        if faces is None or depth_frames is None:
+            raise ValueError("refine_depth needs faces and depth_frames")
+        nan = float("nan")
+        refine_counts = {"refined": 0, "rejected": 0, "unchanged": 0, "mean_rms_first": nan, "mean_rms_last": nan}
+        if len(gts):
+            test, index = _depth_stack(depth_frames, nrs)
+            new, stats = refine_poses_depth(np.reshape(ests, (-1, 4, 4)), model_vertices, faces, cam_K, test, index, depth_scale,
+                                            device=device, **refine_depth)
+            for j, owner in enumerate(owners):
+                owner["pose_rgb"] = ests[j]
+                ests[j] = np.vstack([new[j], [0.0, 0.0, 0.0, 1.0]])
+                owner["cam_R"], owner["cam_t"] = ests[j][:3, :3].copy(), ests[j][:3, 3].reshape(3, 1).copy()
+            rejected = stats[:, 5] == ICP_STATUS.index("REJECTED")
+            moved = ~rejected & (stats[:, 4] > 0)
+            seen = stats[:, 0] > 0
+            refine_counts.update(refined=int(moved.sum()), rejected=int(rejected.sum()),
+                                 unchanged=int((~rejected & ~moved).sum()))
+            if seen.any():
+                refine_counts.update(mean_rms_first=float(stats[seen, 1].mean()), mean_rms_last=float(stats[seen, 3].mean()))
     if device is None:
         add_errs = [add_err(g, e, model_vertices) * 1000 for g, e in zip(gts, ests)]
         proj = [projection_error_2d(g, e, model_vertices, cam_K) for g, e in zip(gts, ests)]
@@ -678,6 +830,8 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
          "mean_2d_acc": float(np.mean(np.array(proj) < pixel_thresh)) if proj else float("nan"),
          "mean_iou": float(np.mean(np.array(ious) > 0.5)) if ious else float("nan"),
          "mean_add_err_mm": float(np.mean(add_errs)) if add_errs else float("nan"), "n": len(ious)}
+    if refine_counts is not None:
+        m.update(refine_counts)
     if symmetric:
         m["mean_adds"] = float(np.mean([a < diameter_mm / 10 for a in adds_errs])) if adds_errs else float("nan")
         m["mean_adds_err_mm"] = float(np.mean(adds_errs)) if adds_errs else float("nan")
@@ -694,12 +848,7 @@ def evaluate_results(final_result: List[dict], gt_frames: Dict[int, dict], model
         nan = float("nan")
         m["ar_vsd"] = m["mean_vsd_err"] = m["mean_visib_fract"] = nan
         if len(gts):
-            used = sorted(set(nrs))
-            for nr in used:
-                if nr not in depth_frames:
-                    raise KeyError("no depth image for frame %d" % nr)
-            test = np.stack([np.asarray(depth_frames[nr]) for nr in used])
-            index = np.array([used.index(nr) for nr in nrs], dtype=np.int32)
+            test, index = _depth_stack(depth_frames, nrs)
             err, counts = pose_errors_vsd(np.reshape(gts, (-1, 4, 4)), np.reshape(ests, (-1, 4, 4)), model_vertices, faces,
                                           cam_K, test, index, diameter_mm / 1000.0, depth_scale, device=device)
             m["ar_vsd"] = float(np.mean([[np.mean(err[:, k] < th) for th in BOP_VSD_THETAS] for k in range(err.shape[1])]))

@@ -56,6 +56,13 @@ def build_parser() -> argparse.ArgumentParser:
                         'one more line per object, "Mean vsd recall for seq XX is: ...", the average recall over the BOP '
                         'taus and thresholds.  With --synthetic the run scores its own poses against depth images rendered '
                         'from them (a closed loop that only exercises the path)')
+    p.add_argument('--refine_depth', nargs='?', type=int, default=None, const=8, metavar='ITERS',
+                   help='refine every scored pose against its frame\'s depth image before any error is computed: projective '
+                        'point-to-plane ICP on the run\'s GPU (metrics.refine_poses_depth; ITERS iterations, default 8).  Reads '
+                        'the mesh faces and the depth PNGs --vsd reads; the accuracy lines are then those of the refined '
+                        'poses, and one more line per object gives the numbers refined / rejected / unchanged and the mean rms '
+                        'residual before and after.  With --synthetic the run refines its own poses against depth images '
+                        'rendered from them (a closed loop that only exercises the path).  Default: off')
     p.add_argument('--shared_detector', default='', type=str, metavar='CFG[,WEIGHTS]',
                    help='occlusion_evaluate.py --obj_ids: ONE multi-class detector (Darknet cfg, .weights file) serves every '
                         'object -- one resize and one detector pass per frame, the best box of each object\'s class, then each '

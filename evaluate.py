@@ -72,10 +72,9 @@ def print_bop_metrics(base, obj_id, final_result, gt_frames, model_vertices, cam
     print("Mean mspd recall for seq %02d is: %.3f" % (obj_id, m["ar_mspd"]))
 
 
-def print_vsd_metrics(base, obj_id, seq_id, final_result, gt_frames, model_vertices, cam, diameter, device,
-                      match_instances=False):
-    """--vsd: the faces of the object's mesh, the depth images of the scored frames, VSD of the scored pairs on ``device``
-    and the average-recall line.  The camera is camera.yml's when the dataset has one, else the LineMod K PnP uses."""
+def load_depth_inputs(base, obj_id, seq_id, final_result, gt_frames, cam):
+    """What --vsd and --refine_depth read alike: the faces of the object's mesh, the depth images of the scored frames and
+    the camera -- camera.yml's when the dataset has one, else the LineMod K PnP uses."""
     from betapose_amd import sixd
     _, faces = metrics.load_ply_mesh(os.path.join(base, "models", "obj_%02d.ply" % obj_id))
     seq = os.path.join(base, "test", "%02d" % (obj_id if seq_id is None else seq_id))
@@ -85,15 +84,37 @@ def print_vsd_metrics(base, obj_id, seq_id, final_result, gt_frames, model_verti
         if nr in gt_frames and nr not in depth_frames:
             depth_frames[nr] = sixd.read_depth_png(os.path.join(seq, "depth", "%04d.png" % nr))
     K = cam if os.path.exists(os.path.join(base, "camera.yml")) else synth.CAM_K
+    return faces, depth_frames, K
+
+
+def print_vsd_metrics(base, obj_id, seq_id, final_result, gt_frames, model_vertices, cam, diameter, device,
+                      match_instances=False, depth_inputs=None):
+    """--vsd: VSD of the scored pairs on ``device`` and the average-recall line (``depth_inputs``: what load_depth_inputs
+    returned when --refine_depth has read it already)."""
+    faces, depth_frames, K = depth_inputs or load_depth_inputs(base, obj_id, seq_id, final_result, gt_frames, cam)
     m = metrics.evaluate_results(final_result, gt_frames, model_vertices, K, diameter, device=device, faces=faces,
                                  depth_frames=depth_frames, match_instances=match_instances)
     print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m["ar_vsd"]))
 
 
-def print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, size, device):
-    """--synthetic --vsd: a closed loop that only shows the path runs.  The mesh is the bounding box of the synthetic key
-    points, the ground truth is each frame's own estimated pose and its depth image is rendered from that pose, so a
-    frame whose pose puts the box in front of the camera scores 0 error and any other renders nothing and scores 1."""
+def refine_scored_poses(obj_id, final_result, gt_frames, model_vertices, depth_inputs, diameter, device, iterations,
+                        match_instances=False):
+    """--refine_depth: one evaluate_results pass with ``refine_depth`` set, on the camera of ``depth_inputs``.  It leaves
+    the refined pose of every scored frame dict in cam_R / cam_t (the unrefined one under "pose_rgb"), so every later
+    metric pass scores the refined poses; prints the counts line and returns the pass's metrics (VSD among them)."""
+    faces, depth_frames, K = depth_inputs
+    m = metrics.evaluate_results(final_result, gt_frames, model_vertices, K, diameter, device=device, faces=faces,
+                                 depth_frames=depth_frames, match_instances=match_instances,
+                                 refine_depth={"iterations": int(iterations)})
+    print("Depth refinement for seq %02d: %d refined, %d rejected, %d unchanged, mean rms %.5f -> %.5f" % (
+        obj_id, m["refined"], m["rejected"], m["unchanged"], m["mean_rms_first"], m["mean_rms_last"]))
+    return m
+
+
+def synthetic_depth_inputs(final_result, kp3d, cam_K, size, device):
+    """--synthetic --vsd / --refine_depth: a closed loop that only shows the path runs.  The mesh is the bounding box of
+    the synthetic key points, the ground truth is each frame's own estimated pose and its depth image is rendered from
+    that pose."""
     lo, hi = np.min(kp3d, axis=0), np.max(kp3d, axis=0)
     v = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=np.float64)
     faces = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
@@ -110,9 +131,26 @@ def print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, size, device):
         depth = metrics.render_depth(pose[None], v, faces, cam_K, size, device)[0][0]
         depth_frames[nr] = np.clip(np.round(depth.astype(np.float64) * 1000.0), 0, 65535).astype(np.uint16)
     diameter = float(np.linalg.norm(hi - lo)) * 1000.0
-    m = metrics.evaluate_results(final_result, gt_frames, v, cam_K, diameter, device=device, faces=faces,
-                                 depth_frames=depth_frames)
-    print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m["ar_vsd"]))
+    return v, faces, gt_frames, depth_frames, diameter
+
+
+def print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, size, device, vsd=True, refine_iterations=None):
+    """--synthetic --vsd: a frame whose pose puts the box in front of the camera scores 0 error and any other renders
+    nothing and scores 1.  ``refine_iterations`` (--synthetic --refine_depth): the poses are first refined against those
+    images -- they start at the poses the images were rendered from -- and the counts line and the accuracy lines of the
+    refined poses are printed; the VSD line only with ``vsd``."""
+    v, faces, gt_frames, depth_frames, diameter = synthetic_depth_inputs(final_result, kp3d, cam_K, size, device)
+    if refine_iterations is not None:
+        m = refine_scored_poses(obj_id, final_result, gt_frames, v, (faces, depth_frames, cam_K), diameter, device,
+                                refine_iterations)
+        print("Mean add accuracy for seq %02d is: %.3f" % (obj_id, m["mean_add"]))
+        print("2d reprojection accuracy for seq %02d is: %.3f" % (obj_id, m["mean_2d_acc"]))
+        print("Mean IoU for seq %02d is: %.3f" % (obj_id, m["mean_iou"]))
+    else:
+        m = metrics.evaluate_results(final_result, gt_frames, v, cam_K, diameter, device=device, faces=faces,
+                                     depth_frames=depth_frames)
+    if vsd:
+        print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m["ar_vsd"]))
 
 
 def main():
@@ -278,6 +316,14 @@ def main():
         write_json(final_result, args.outputpath)
         if gt_frames is not None:
             sym = obj_id in id_list(args.symmetric_ids)
+            depth_inputs, m_ref = None, None
+            if args.vsd or args.refine_depth is not None:
+                depth_inputs = load_depth_inputs(args.sixd_base, obj_id, 2 if args.occlusion else None, final_result,
+                                                 gt_frames, metric_cam)
+            if args.refine_depth is not None:   # before any error: the lines below are those of the refined poses
+                m_ref = refine_scored_poses(obj_id, final_result, gt_frames, model_vertices, depth_inputs, diameter,
+                                            torch.device("cuda", local), args.refine_depth,
+                                            match_instances=args.all_instances)
             m = metrics.evaluate_results(final_result, gt_frames, model_vertices, metric_cam, diameter, pixel_thresh,
                                          symmetric=sym, device=torch.device("cuda", local) if sym else None,
                                          match_instances=args.all_instances)
@@ -289,12 +335,15 @@ def main():
             if args.bop_metrics:
                 print_bop_metrics(args.sixd_base, obj_id, final_result, gt_frames, model_vertices, metric_cam, diameter,
                                   torch.device("cuda", local), match_instances=args.all_instances)
-            if args.vsd:
+            if args.vsd and m_ref is not None:      # the refinement pass has scored the refined poses already
+                print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m_ref["ar_vsd"]))
+            elif args.vsd:
                 print_vsd_metrics(args.sixd_base, obj_id, 2 if args.occlusion else None, final_result, gt_frames,
                                   model_vertices, metric_cam, diameter, torch.device("cuda", local),
-                                  match_instances=args.all_instances)
-        elif args.vsd and args.synthetic:
-            print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, synth_size, torch.device("cuda", local))
+                                  match_instances=args.all_instances, depth_inputs=depth_inputs)
+        elif (args.vsd or args.refine_depth is not None) and args.synthetic:
+            print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, synth_size, torch.device("cuda", local), vsd=args.vsd,
+                                refine_iterations=args.refine_depth)
     bpd.finalize()
 
 

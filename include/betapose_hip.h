@@ -45,6 +45,8 @@
  *   bp_render_depth, bp_render_depth_host
  *                          Renderer.render's depth image (OpenGL through vispy)   utils/renderer.py
  *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
+ *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
+ *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
@@ -287,6 +289,42 @@ int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const
                   const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
                   const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
                   double near_z, int chunk, double* d_err, int* d_counts, void* stream);
+/* Depth refinement of P estimated poses of one mesh: projective point-to-plane ICP of the mesh's render (as
+ * bp_render_depth draws it) against the test depth image d_test_index[p] of d_depth_test [T][H][W] uint16 (depth =
+ * raw * depth_scale in pose units, 0 = missing).  Up to `iterations` times: render at the current pose; every pixel
+ * whose render and whose four neighbours' renders are drawn and whose test depth is present gives the model point
+ * q = z_r d on its ray d, the normal n of the rendered surface from the neighbours' points (turned towards the camera),
+ * the residual r = (z_t - z_r)(n.d) and the row J = [(q - t) x n, n]; pixels with -(n.d)/|d| < min_cos or
+ * |z_t - z_r| > max_dist are left out.  A xi = b with A = sum J^T J, b = sum J^T r, xi = (omega, v), then
+ * R <- exp(omega) R, t <- t + v.  One more accumulation follows the last step.  A pose stops early with status
+ * 1 TOO_FEW (fewer than min_pixels pixels), 2 SINGULAR (no pivot), 3 DIVERGED (|omega| > 0.5 rad or |v| > 4 max_dist;
+ * the pose before that step is kept); 0 OK took every step.  A pose that ends with a larger rms residual than it began
+ * with is returned as it came, bit for bit, with status 4 REJECTED; a test index outside [0, T) gives 5 NO_IMAGE and the
+ * pose unchanged.  d_poses_out [P][12] (must not be d_poses); d_stats [P][6] f64 = (N_first, rms_first, N_last, rms_last,
+ * iterations_done, status), N the number of pixels that took part, the *_last pair describing the returned pose.
+ * Poses are processed `chunk` at a time (0: as many as keep the workspaces under 256 MB); the results do not depend on
+ * it and are bit-identical from run to run (no floating-point atomics).  The loop over the iterations runs on `stream`
+ * without a host round trip; the call synchronises `stream` at its end.
+ * bp_icp_normal_equations is ONE accumulation at the given poses: d_out [P][29] f64 = A's upper triangle row by row
+ * (21), b (6), N, E = sum r^2; zeros for a test index outside [0, T).
+ * The *_host calls are the same on host memory, without a GPU: every pixel's decision and term has the device's bits,
+ * the sums differ by the rounding of their order.  They refuse a face index outside [0, n). */
+int bp_refine_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    const uint16_t* d_depth_test, int T, int H, int W, double depth_scale, const int* d_test_index,
+                    int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                    int chunk, double* d_poses_out, double* d_stats, void* stream);
+int bp_refine_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         const uint16_t* depth_test, int T, int H, int W, double depth_scale, const int* test_index,
+                         int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                         double* poses_out, double* stats);
+int bp_icp_normal_equations(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P,
+                            const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                            const int* d_test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                            int chunk, double* d_out, void* stream);
+int bp_icp_normal_equations_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                                 const double* K, const uint16_t* depth_test, int T, int H, int W, double depth_scale,
+                                 const int* test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                                 double* out);
 /* one fused convolution on device tensors (unit tests / kernel benchmarks).  h_w: host OIHW filter, h_bias host or NULL.
  * d_in NHWC [N,H,W,Cin]; d_out per store_mode (0 NHWC, 1 nearest-x2 NHWC, 2 PixelShuffle(2) NHWC, 3 NCHW);
  * act 0 linear / 1 leaky(0.1) / 2 relu; d_res NHWC residual or NULL; splits 0 auto; tile -1 auto, else a kernel id

@@ -202,6 +202,13 @@ def main():
             os.makedirs(odir, exist_ok=True)
             write_json(final_result, odir)
             sym = o in symmetric
+            depth_inputs, m_ref = None, None
+            if args.vsd or args.refine_depth is not None:
+                depth_inputs = evaluate.load_depth_inputs(args.sixd_base, o, 2, final_result, frames_gt, cam)
+            if args.refine_depth is not None:   # before any error: the lines below are those of the refined poses
+                m_ref = evaluate.refine_scored_poses(o, final_result, frames_gt, model, depth_inputs, diameter,
+                                                     torch.device("cuda", local), args.refine_depth,
+                                                     match_instances=args.all_instances)
             m = metrics.evaluate_results(final_result, frames_gt, model, cam, diameter, 20.0, symmetric=sym,
                                          device=torch.device("cuda", local) if sym else None,
                                          match_instances=args.all_instances)
@@ -213,9 +220,12 @@ def main():
             if args.bop_metrics:
                 evaluate.print_bop_metrics(args.sixd_base, o, final_result, frames_gt, model, cam, diameter,
                                            torch.device("cuda", local), match_instances=args.all_instances)
-            if args.vsd:
+            if args.vsd and m_ref is not None:      # the refinement pass has scored the refined poses already
+                print("Mean vsd recall for seq %02d is: %.3f" % (o, m_ref["ar_vsd"]))
+            elif args.vsd:
                 evaluate.print_vsd_metrics(args.sixd_base, o, 2, final_result, frames_gt, model, cam, diameter,
-                                           torch.device("cuda", local), match_instances=args.all_instances)
+                                           torch.device("cuda", local), match_instances=args.all_instances,
+                                           depth_inputs=depth_inputs)
     bpd.finalize()
 
 
