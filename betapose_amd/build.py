@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbetapose_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_fused.hip", "conv_pl.hip", "conv_s1.hip", "conv_p3.hip", "aux_kernels.hip", "pose_metrics.hip", "pose_metrics_sym.hip", "raster.hip", "vsd.hip", "icp.hip", "pose_tail.hip", "pose_tail_cands.hip", "pose_tail_inst.hip", "pnp_ransac.hip", "engine.cpp", "host_post.cpp", "raster_host.cpp", "icp_host.cpp", "frame_io.cpp", "jpeg_bmp.cpp", "c_api.cpp", "darknet_compat.cpp"]
-HEADERS = ["bp_common.h", "engine.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "icp.h", "icp_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
+SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_fused.hip", "conv_pl.hip", "conv_s1.hip", "conv_p3.hip", "aux_kernels.hip", "pose_metrics.hip", "pose_metrics_sym.hip", "raster.hip", "vsd.hip", "icp.hip", "pose_tail.hip", "pose_tail_cands.hip", "pose_tail_inst.hip", "pnp_ransac.hip", "engine.cpp", "conv_plan.cpp", "host_post.cpp", "raster_host.cpp", "icp_host.cpp", "frame_io.cpp", "jpeg_bmp.cpp", "c_api.cpp", "darknet_compat.cpp"]
+HEADERS = ["bp_common.h", "engine.h", "conv_plan.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "icp.h", "icp_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
            os.path.join("..", "..", "include", "yolo_v2_class_compat.h")]
 # measured-and-superseded kernels (round-1/2 experiments) live in csrc/experimental/ and are compiled only into
 # libbetapose_hip_exp.so (--experimental); the product library has no input under that directory

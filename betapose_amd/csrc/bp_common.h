@@ -199,7 +199,7 @@ bool conv_tile_is_halo(int tile);
 bool conv_halo_eligible(const ConvParams& p, int tile);   // 3x3 / stride 1 / pad 1, Cin % 32 == 0, stage-packed filters, W within the LDS budget
 // K slices of a launch: `want` slices asked for -> slices and chunks per slice the kernel `tile` runs (the halo tiles cut K
 // by whole 32-channel groups = 9 chunks)
-void conv_split_plan(const ConvParams& p, int tile, int want, int* splits, int* cps);
+void conv_split_plan(const ConvParams& p, int tile, int want, int* splits, int* cps);   // conv_plan.cpp
 inline bool conv_tile_is_plh(int tile) { return tile == TILE_PLH128; }
 bool conv_plh_eligible(const ConvParams& p);  // TILE_PLH128 can run the layer (fp16, 3x3 / stride 1 / pad 1, W <= 126, whole channel groups per K slice)
 bool conv_pl_eligible(const ConvParams& p);   // planes + wpl present, Cin % 32 == 0, taps fit the 32-bit mask
@@ -226,9 +226,6 @@ bool conv_stem7_eligible(const ConvParams& p);   // ... on TILE_STEM7 (7x7 / str
 void conv_grid_setup(ConvParams& q, int bm, int bn);   // fills mtiles / n_tiles / work_blocks / pf_first from M, CoutPad, splits, xcd_home
 int conv_grid_blocks(const ConvParams& q);
 int xcc_base();                                                // engine.cpp: XCC_ID of block 0 (round-robin dispatch), -1: unusable
-bool conv_hybrid_plan(const ConvParams& p, int tile, size_t partial_floats, int* full, int* hs, int* hcps);   // engine.cpp
-bool conv_home_layout(int tile, int splits);                   // engine.cpp: the launch keeps all K slices of a tile on one XCD
-void conv_prefetch_of(ConvParams& p, const ConvParams& next, int next_tile, int next_splits, int next_cps);   // engine.cpp              // work blocks + padding + prefetch blocks
 int conv_tile_bm(int tile);
 int conv_tile_bn(int tile);
 

@@ -934,40 +934,30 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
         }
         if (p.out16) p.skip_f32 = 1;
     }
-    int sp = splits;
-    if (sp <= 0) {
-        const long long blocks = bp::conv_tiles(p, t);
-        sp = 1;
-        while (blocks * sp < 512 && p.nchunks / (sp + 1) >= 4 && sp < 64) ++sp;
-    }
-    if (t == bp::TILE_S1 || t == bp::TILE_P3) sp = 1;     // (a persistent grid: no K slices)
-    int per = 0;
-    bp::conv_split_plan(p, t, sp, &sp, &per);
+    // the launch set-up is the engine's (conv_plan.h): K cut, hybrid grid when the last round is badly filled, XCD-home layout
+    const bp::ConvLaunch l = bp::conv_launch_of(p, t, splits);
+    const int sp = l.splits, per = l.cps;
     p.splits = sp; p.chunks_per_split = per;
     if (sp > 1) {
         const int tiles = bp::conv_tiles(p, t);
-        p.partial = net.arena_.alloc((size_t)sp * tiles * bp::conv_tile_bm(t) * bp::conv_tile_bn(t));
+        p.partial = net.arena_.alloc(bp::conv_slab_floats(t, sp, tiles));
         p.tickets = (int*)net.arena_.alloc_bytes((size_t)(2 + 64) * tiles * sizeof(int));
         BP_HIP(hipMemset(p.tickets, 0, (size_t)(2 + 64) * tiles * sizeof(int)));
     }
-    if (sp == 1 && !std::getenv("BP_CONV_SELF_PREFETCH")) {   // as the engine launches it: hybrid grid when the last round is badly filled
-        const size_t cap = (size_t)8 * 256 * bp::conv_tile_bm(t) * bp::conv_tile_bn(t);     // <= 8 slices of <= 256 tail tiles
-        int full = 0, hs = 0, hcps = 0;
-        if (bp::conv_hybrid_plan(p, t, cap, &full, &hs, &hcps)) {
-            const int tail = bp::conv_tiles(p, t) - full;
-            p.partial = net.arena_.alloc((size_t)hs * tail * bp::conv_tile_bm(t) * bp::conv_tile_bn(t));
-            p.tickets = (int*)net.arena_.alloc_bytes((size_t)tail * sizeof(int));
-            BP_HIP(hipMemset(p.tickets, 0, (size_t)tail * sizeof(int)));
-            p.hy_full = full; p.hy_splits = hs; p.hy_cps = hcps;
-        }
+    bp::HybridTail h;
+    if (sp == 1 && !std::getenv("BP_CONV_SELF_PREFETCH") && bp::conv_hybrid_plan(p, t, bp::conv_slab_floats(t, 8, 256), &h)) {   // (<= 8 slices of <= 256 tail tiles)
+        p.partial = net.arena_.alloc(h.slab_floats);
+        p.tickets = (int*)net.arena_.alloc_bytes((size_t)h.tiles * sizeof(int));
+        BP_HIP(hipMemset(p.tickets, 0, (size_t)h.tiles * sizeof(int)));
+        p.hy_full = h.full; p.hy_splits = h.splits; p.hy_cps = h.cps;
     }
-    if (bp::conv_home_layout(t, sp)) {   // as the engine launches it: all K slices of a tile on one XCD, hand-off through that XCD's L2
+    if (bp::conv_home_layout(t, sp)) {   // all K slices of a tile on one XCD, hand-off through that XCD's L2
         const int tiles = bp::conv_tiles(p, t);
         p.xcd_home = 1;
         p.tickets_local = p.tickets + tiles;
         p.xcc_of = p.tickets + 2 * tiles;
     }
-    if (std::getenv("BP_CONV_SELF_PREFETCH")) bp::conv_prefetch_of(p, p, t, sp, per);   // (tests: the launch carries prefetch blocks, for its own filters)
+    if (std::getenv("BP_CONV_SELF_PREFETCH")) bp::conv_prefetch_of(p, p, l);   // (tests: the launch carries prefetch blocks, for its own filters)
     bp::launch_conv(p, t, s);
     BP_HIP(hipStreamSynchronize(s));
     if (const char* e = std::getenv("BP_CONV_STAMPS")) {   // debug: per-block s_memtime marks of one extra launch

@@ -1153,15 +1153,6 @@ bool conv_h16_eligible(const ConvParams& p) {   // the fp32-activation 16-bit ke
     return (p.w16 != nullptr || p.w16s != nullptr) && (p.Cin % 32 == 0) && (p.in_ld % 4 == 0) && p.ksize <= 8;
 }
 
-void conv_split_plan(const ConvParams& p, int tile, int want, int* splits, int* cps) {
-    const int unit = ((conv_tile_is_halo(tile) || conv_tile_is_plh(tile)) && p.nchunks % 9 == 0 && p.nchunks >= 9) ? 9 : 1;          // chunks that stay together (a layer the halo tiles cannot run is refused by the launcher)
-    const int units = p.nchunks / unit;
-    int s = want < 1 ? 1 : (want > units ? units : want);
-    const int per = (units + s - 1) / s;
-    s = (units + per - 1) / per;
-    *splits = s; *cps = per * unit;
-}
-
 int conv_tiles(const ConvParams& p, int tile) {
     const int bm = conv_tile_bm(tile), bn = conv_tile_bn(tile);
     return ((p.M + bm - 1) / bm) * ((p.CoutPad + bn - 1) / bn);

@@ -442,6 +442,9 @@ static int p3_rows_needed(const ConvParams& p, long long M) {
 }
 
 bool conv_p3_eligible(const ConvParams& p, long long M) {
+    // a persistent grid pays its start-up over the work it walks: layers of the batched runs only
+    if (M < 4096) return false;
+    if (p.ksize != 1 && !(p.ksize == 3 && p3_width_class(p.W))) return false;       // (the cheap rejections first)
     if (!(conv_pl_eligible(p) && p.wpl != nullptr && p.mfma_mode == PREC_F16)) return false;
     if (p.store_mode != ST_NHWC || p.res_scale != nullptr || p.pool_out != nullptr) return false;
     if ((p.Cout & 7) || (p.out_ld & 7) || p.CoutPad < P3_BN) return false;       // (16-B stores of 8 fp16 channels)
@@ -449,8 +452,6 @@ bool conv_p3_eligible(const ConvParams& p, long long M) {
     if (p.out16 != nullptr && p.out_np != 1) return false;
     if (M * p.out_ld * 4 >= (long long)OOB || (p.res && M * p.res_ld * 4 >= (long long)OOB)) return false;
     if (M >= (1 << 24) || (long long)(p.N * (p.H + 1) + 1) * (p.W + 2) >= (1 << 24)) return false;       // (fast_div's range)
-    // a persistent grid pays its start-up over the work it walks: layers of the batched runs only
-    if (M < 4096) return false;
     if (p.ksize == 1)      // the 1x1 form: stride 1, whole 128-channel groups, at least two of them
         return p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W && p.Kpad == p.Cin && p.Cin % 128 == 0 && p.Cin >= 256;
     return conv_plh_eligible(p) && p3_width_class(p.W) && p3_rows_needed(p, M) <= p3_hrt(p.W);

@@ -357,7 +357,7 @@ bool conv_s1_eligible(const ConvParams& p, long long M) {
     if (!(p.ksize == 1 && p.pad == 0 && (p.stride == 1 || p.stride == 2) && p.Kpad == p.Cin && p.store_mode == ST_NHWC)) return false;
     const int nch = p.nchunks;
     if (!(nch == 2 || nch == 4 || nch == 8 || nch == 12 || nch == 16 || nch == 32)) return false;      // K = 64, 128, 256, 384, 512, 1 024 (the instantiated forms)
-    if (M < 2048 || p.pool_out != nullptr) return false;       // (the cheap rejections first: choose_launch asks for every fp16 convolution of every eager pass)
+    if (M < 2048 || p.pool_out != nullptr) return false;
     // K = 1 024 (64 columns per block, two K halves per column half), measured at batch 28 against the 64x64 plane tile on one box: 1 024 -> 256
     // ties (16.0 against 16.2 us), 13x13 1 024 -> 512 loses (17.4 against 16.3), 1 024 -> 2 048 / stride 2 wins (30.2 against 36.5): the wide
     // layers only.  (K = 512: 512 -> 128 16.7 against 20.8 us, 26x26 512 -> 256 17.2 against 18.8 -- all of them.)  BP_S1_K512=1 takes every

@@ -50,571 +50,6 @@ float* Net::upload_weights(const float* host, size_t count) {
     return d;
 }
 
-// Split-K slice counts measured on MI355X for every batch-1 conv shape of the two networks, one kernel at a time
-// (tools/tune_conv.py, 64x64 tile): {M, CoutPad, K-chunks, slices}.  Other shapes use the heuristic below.
-struct SplitEntry { int M, CoutPad, nchunks, splits; };
-static const SplitEntry kSplitTable[] = {
-    {    80,   512,   64,  6},
-    {    80,   512,  144, 12},
-    {    80,  2048,   16,  3},
-    {    80,  2048,   32,  3},
-    {   169,    64,   32, 10},
-    {   169,   256,   16,  5},
-    {   169,   512,   32,  5},
-    {   169,  1024,  144,  5},
-    {   320,   256,   32,  5},
-    {   320,   256,   72,  8},
-    {   320,   512,   32,  5},
-    {   320,  1024,    8,  1},
-    {   320,  1024,   16,  3},
-    {   320,  1024,  144,  6},
-    {   676,    64,   16,  4},
-    {   676,   128,    8,  3},
-    {   676,   256,   16,  3},
-    {   676,   256,   24,  5},
-    {   676,   512,   72,  5},
-    {  1280,   128,   16,  3},
-    {  1280,   128,   36,  5},
-    {  1280,   256,   16,  3},
-    {  1280,   512,    4,  1},
-    {  1280,   512,    8,  1},
-    {  1280,   512,   72,  3},
-    {  2704,    64,    8,  1},
-    {  2704,   128,    8,  1},
-    {  2704,   128,   12,  2},
-    {  2704,   256,   36,  4},
-    {  5120,    64,    2,  1},
-    {  5120,    64,    8,  1},
-    {  5120,    64,   18,  3},
-    {  5120,    64,   36,  3},
-    {  5120,   128,    8,  1},
-    {  5120,   256,    2,  1},
-    { 10816,    64,    4,  1},
-    { 10816,   128,   18,  3},
-    { 43264,    64,    2,  1},
-    { 43264,    64,    9,  1},
-};
-
-// 16-bit precision modes: {M, CoutPad, K-chunks} -> {tile, slices}, measured one kernel at a time over both kernel
-// families (tools/tune_conv.py [--f16 | --kg], profiles/r02_tune_{b3,f16,b3_kernels}.txt: at batch 1 the 64x64-block
-// kernels of conv_igemm.hip win every shape of the two networks, in the bf16x3 mode its filters-direct variant; the
-// slice counts are those the whole pipeline runs fastest with, which are higher than a kernel timed alone prefers);
-// other shapes use the heuristic in choose_h16.
-// COVERAGE: the rows below are the conv shapes of the two networks at BATCH 1 (M = OH x OW of one 416x416 frame / one 320x256 crop);
-// the conv_pl tables further down also carry batch 28 (BASELINE configs[2]).  Any other batch size or input resolution takes the
-// heuristics in choose_h16 / choose_pl, which are measured at batch 2, 4 and 28 only (tools/batch_check.sh, profiles/r04_batched.txt).
-struct PlanEntry { int M, CoutPad, nchunks, tile, splits; };
-static const PlanEntry kPlanB3[] = {
-    // (round 4, TILE_BD_K2 rows: the filters-direct tile with two K groups inside an eight-wave block and about half the K slices
-    // between blocks -- alone it is no faster than the four-wave tile on any shape (tools/bench_bdk2.py, profiles/r04_bdk2_kernels.txt),
-    // in the pipeline the plan with these rows is +2-2.8 % on three boxes (tools/plans/bdk2*.txt, profiles/r04_ab_bdk2.txt): fewer
-    // blocks and slabs for the same work)
-    // round 4, conv_halo.hip: the 3x3 / stride-1 layers on the tap-resident halo tile -- rows apply where conv_halo_eligible()
-    // holds (a stride-2 layer of the same {M, CoutPad, K-chunks} falls through to its filters-direct row below).  Slice counts from
-    // A/B runs of the whole pipeline, four frames in flight (profiles/r04_halo_ab.txt)
-    // (first the 64x128 tile with 8 / 6 / 4 / 3 / 2 slices: +4-5 %; then the 64x64 tile with two K groups inside the block and half the
-    // slices -- none at 52x52: a further +1.2-2 %, tools/plans/k2*.txt)
-    {   169,  1024,  144, TILE_HALO64K2,  4},
-    {   320,  1024,  144, TILE_HALO64K2,  4},
-    {   676,   512,   72, TILE_HALO64K2,  2},
-    {  1280,   512,   72, TILE_HALO64K2,  2},
-    {  2704,   256,   36, TILE_HALO64K2,  1},
-    {    80,   512,   64, TILE_BD_K2,  4},
-    {    80,   512,  144, TILE_BD_K2,  6},
-    {    80,  2048,   16, TILE_BD_K2,  2},
-    {    80,  2048,   32, TILE_BD_K2,  2},
-    {   169,    64,   32, TILE_BD_K2,  6},
-    {   169,   256,   16, TILE_BD_K2,  3},
-    {   169,   512,   32, TILE_BD_K2,  6},
-    {   169,  1024,  144, TILE_64x64_BD,  5},
-    {   320,   256,   32, TILE_BD_K2,  6},
-    {   320,   256,   72, TILE_BD_K2,  6},
-    {   320,   512,   32, TILE_BD_K2,  3},
-    {   320,  1024,    8, TILE_BD_K2,  1},
-    {   320,  1024,   16, TILE_BD_K2,  2},
-    {   320,  1024,  144, TILE_64x64_BD,  6},
-    {   676,    64,   16, TILE_BD_K2,  3},
-    {   676,   128,    8, TILE_BD_K2,  1},
-    {   676,   256,   16, TILE_BD_K2,  3},
-    {   676,   256,   24, TILE_BD_K2,  3},
-    {   676,   512,   72, TILE_64x64_BD,  5},
-    {  1280,   128,   16, TILE_BD_K2,  3},
-    {  1280,   128,   36, TILE_BD_K2,  3},
-    {  1280,   256,   16, TILE_BD_K2,  2},
-    {  1280,   512,    4, TILE_64x64_BD,  1},
-    {  1280,   512,    8, TILE_BD_K2,  1},
-    {  1280,   512,   72, TILE_64x64_BD,  3},
-    {  2704,    64,    8, TILE_BD_K2,  1},
-    {  2704,   128,    8, TILE_BD_K2,  1},
-    {  2704,   128,   12, TILE_BD_K2,  1},
-    {  2704,   256,   36, TILE_64x64_BD,  2},   // in the pipeline: 2 slices 933, 3: 929, 4: 921, 5+: 910 frames/s (tools/tune_splits_insitu.py)
-    {  5120,    64,    2, TILE_64x64_BD,  1},
-    {  5120,    64,    8, TILE_BD_K2,  1},
-    {  5120,    64,   18, TILE_BD_K2,  2},
-    {  5120,    64,   36, TILE_BD_K2,  2},
-    {  5120,   128,    8, TILE_BD_K2,  1},
-    {  5120,   256,    2, TILE_64x64_BD,  1},
-    { 10816,    64,    4, TILE_BD_K2,  1},
-    { 10816,   128,   18, TILE_BD_K2,  1},
-    { 43264,    64,    2, TILE_64x64_BD,  1},
-    { 43264,    64,    9, TILE_64x64_BD,  1},
-    {0, 0, 0, 0, 0},
-};
-// The lone-frame latency mode (Net::set_prefetch) keeps the four-wave filters-direct tile on the rows the table above gives to TILE_BD_K2:
-// its XCD-local hand-off and filter prefetch blocks exist for that tile (conv_home_layout, conv_prefetch_of), and one frame at a time
-// they are worth more than the K groups (2.46 against 2.56 ms per frame).  Slice counts: the round-3 table.
-static const PlanEntry kPlanB3Lone[] = {
-    {    80,   512,   64, TILE_64x64_BD,  6},
-    {    80,   512,  144, TILE_64x64_BD, 10},
-    {    80,  2048,   16, TILE_64x64_BD,  3},
-    {    80,  2048,   32, TILE_64x64_BD,  3},
-    {   169,    64,   32, TILE_64x64_BD, 10},
-    {   169,   256,   16, TILE_64x64_BD,  5},
-    {   169,   512,   32, TILE_64x64_BD,  5},
-    {   320,   256,   32, TILE_64x64_BD,  5},
-    {   320,   256,   72, TILE_64x64_BD,  8},
-    {   320,   512,   32, TILE_64x64_BD,  5},
-    {   320,  1024,    8, TILE_64x64_BD,  1},
-    {   320,  1024,   16, TILE_64x64_BD,  3},
-    {   676,    64,   16, TILE_64x64_BD,  5},
-    {   676,   128,    8, TILE_64x64_BD,  1},
-    {   676,   256,   16, TILE_64x64_BD,  3},
-    {   676,   256,   24, TILE_64x64_BD,  5},
-    {  1280,   128,   16, TILE_64x64_BD,  3},
-    {  1280,   128,   36, TILE_64x64_BD,  5},
-    {  1280,   256,   16, TILE_64x64_BD,  3},
-    {  1280,   512,    8, TILE_64x64_BD,  1},
-    {  2704,    64,    8, TILE_64x64_BD,  1},
-    {  2704,   128,    8, TILE_64x64_BD,  1},
-    {  2704,   128,   12, TILE_64x64_BD,  1},
-    {  5120,    64,    8, TILE_64x64_BD,  1},
-    {  5120,    64,   18, TILE_64x64_BD,  3},
-    {  5120,    64,   36, TILE_64x64_BD,  3},
-    {  5120,   128,    8, TILE_64x64_BD,  1},
-    { 10816,    64,    4, TILE_64x64_BD,  1},
-    { 10816,   128,   18, TILE_64x64_BD,  2},
-    {0, 0, 0, 0, 0},
-};
-#ifdef BP_EXPERIMENTAL
-// (fp16, batch 1: the filters-direct variant wins 40 of 47 shapes alone by 4.5 % in the sum, profiles/r02_tune_f16.txt, and
-// LOSES in the pipeline -- 1 329 against 1 381 frames/s, A/B on one box -- so the batch-1 rows stay on the staged kernel)
-static const PlanEntry kPlanF16[] = {
-    {    80,   512,   64, 0,  5},
-    {    80,   512,  144, 0,  6},
-    {    80,  2048,   16, 0,  1},
-    {    80,  2048,   32, 0,  3},
-    {   169,    64,   32, 0,  4},
-    {   169,   256,   16, 0,  1},
-    {   169,   512,   32, 0,  3},
-    {   169,  1024,  144, 0,  5},
-    {   320,   256,   32, 0,  3},
-    {   320,   256,   72, 0,  5},
-    {   320,   512,   32, 0,  3},
-    {   320,  1024,    8, 0,  1},
-    {   320,  1024,   16, 0,  1},
-    {   320,  1024,  144, 0,  5},
-    {   676,    64,   16, 0,  1},
-    {   676,   128,    8, 0,  1},
-    {   676,   256,   16, 0,  1},
-    {   676,   256,   24, 0,  1},
-    {   676,   512,   72, 0,  5},
-    {  1280,   128,   16, 0,  1},
-    {  1280,   128,   36, 0,  3},
-    {  1280,   256,   16, 0,  1},
-    {  1280,   512,    4, 0,  1},
-    {  1280,   512,    8, 0,  1},
-    {  1280,   512,   72, 0,  3},
-    {  2704,    64,    8, 0,  1},
-    {  2704,   128,    8, 0,  1},
-    {  2704,   128,   12, 0,  1},
-    {  2704,   256,   36, 0,  1},
-    {  5120,    64,    2, 0,  1},
-    {  5120,    64,    8, 0,  1},
-    {  5120,    64,   18, 0,  1},
-    {  5120,    64,   36, 0,  3},
-    {  5120,   128,    8, 0,  1},
-    {  5120,   256,    2, 0,  1},
-    { 10816,    64,    4, 0,  1},
-    { 10816,   128,   18, 0,  1},
-    { 43264,    64,    2, 0,  1},
-    { 43264,    64,    9, 0,  1},
-    // batch 28 (BASELINE configs[2]; profiles/r02_tune_f16_batch28.txt, with the 128x64 block and the filters-direct kernel among the candidates)
-    {  2240,   512,   64, 1,  1},
-    {  2240,   512,  144, 1,  1},
-    {  2240,  2048,   16, 0,  1},
-    {  2240,  2048,   32, 0,  1},
-    {  4732,    64,   32, 12,  1},
-    {  4732,   256,   16, 1,  1},
-    {  4732,   512,   32, 12,  1},
-    {  4732,  1024,  144, 1,  1},
-    {  8960,   256,   32, 6,  1},
-    {  8960,   256,   72, 6,  1},
-    {  8960,   512,   32, 0,  1},
-    {  8960,  1024,    8, 0,  1},
-    {  8960,  1024,   16, 0,  1},
-    {  8960,  1024,  144, 1,  1},
-    { 18928,    64,   16, 0,  1},
-    { 18928,   128,    8, 6,  1},
-    { 18928,   256,   16, 0,  1},
-    { 18928,   256,   24, 0,  1},
-    { 18928,   512,   72, 6,  1},
-    { 35840,   128,   16, 0,  1},
-    { 35840,   128,   36, 0,  1},
-    { 35840,   256,   16, 6,  1},
-    { 35840,   512,    4, 0,  1},
-    { 35840,   512,    8, 0,  1},
-    { 35840,   512,   72, 6,  1},
-    { 75712,    64,    8, 0,  1},
-    { 75712,   128,    8, 0,  1},
-    { 75712,   128,   12, 6,  1},
-    { 75712,   256,   36, 6,  1},
-    {143360,    64,    2, 0,  1},
-    {143360,    64,    8, 0,  1},
-    {143360,    64,   18, 12,  1},
-    {143360,    64,   36, 12,  1},
-    {143360,   128,    8, 6,  1},
-    {143360,   256,    2, 0,  1},
-    {302848,    64,    4, 0,  1},
-    {302848,   128,   18, 6,  1},
-    {1211392,    64,    2, 12,  1},
-    {1211392,    64,    9, 1,  1},
-    {0, 0, 0, 0, 0},
-};
-#endif   // BP_EXPERIMENTAL
-
-// experiment hook (tools only): BP_PLAN_FILE names a text file of "M CoutPad nchunks tile splits" lines that take
-// precedence over the built-in bf16x3 table, so a tuning sweep can be tried in the whole pipeline without a rebuild
-static const std::vector<PlanEntry>& plan_file_entries() {
-    static const std::vector<PlanEntry> entries = [] {
-        std::vector<PlanEntry> v;
-        if (const char* path = std::getenv("BP_PLAN_FILE")) {
-            if (FILE* f = std::fopen(path, "r")) {
-                PlanEntry e;
-                while (std::fscanf(f, "%d %d %d %d %d", &e.M, &e.CoutPad, &e.nchunks, &e.tile, &e.splits) == 5) v.push_back(e);
-                std::fclose(f);
-            }
-        }
-        return v;
-    }();
-    return entries;
-}
-
-// conv_pl.hip, bf16x3 mode, batch 1: {M, CoutPad, K-chunks} -> {tile, slices}, every conv shape of the two networks timed alone with the
-// epilogue the networks run (residual + operand planes; tools/tune_conv.py --pl, profiles/r03_tune_pl_b3.txt)
-static const PlanEntry kPlanPL3[] = {
-    {    80,   512,   64, TILE_PL64,  6},
-    {    80,   512,  144, TILE_PL64, 10},
-    {    80,  2048,   16, TILE_PL64,  3},
-    {    80,  2048,   32, TILE_PL64,  3},
-    {   169,    64,   32, TILE_PL64, 10},
-    {   169,   256,   16, TILE_PL64,  4},
-    {   169,   512,   32, TILE_PL64,  4},
-    {   169,  1024,  144, TILE_PL64,  5},
-    {   320,   256,   32, TILE_PL64,  4},
-    {   320,   256,   72, TILE_PL64,  5},
-    {   320,   512,   32, TILE_PL64,  3},
-    {   320,  1024,    8, TILE_PL64,  1},
-    {   320,  1024,   16, TILE_PL64,  1},
-    {   320,  1024,  144, TILE_PL64,  3},
-    {   676,    64,   16, TILE_PL64,  5},
-    {   676,   128,    8, TILE_PL64,  1},
-    {   676,   256,   16, TILE_PL64,  3},
-    {   676,   256,   24, TILE_PL64,  3},
-    {   676,   512,   72, TILE_PL64,  2},
-    {  1280,   128,   16, TILE_PL64,  3},
-    {  1280,   128,   36, TILE_PL64,  4},
-    {  1280,   256,   16, TILE_PL64,  1},
-    {  1280,   512,    4, TILE_PL64,  1},
-    {  1280,   512,    8, TILE_PL64,  1},
-    {  1280,   512,   72, TILE_PL64,  3},
-    {  2704,    64,    8, TILE_PL64,  1},
-    {  2704,   128,    8, TILE_PL64,  1},
-    {  2704,   128,   12, TILE_PL64,  1},
-    {  2704,   256,   36, TILE_PL64,  1},
-    {  5120,    64,    2, TILE_PL64,  1},
-    {  5120,    64,    8, TILE_PL64,  1},
-    {  5120,    64,   18, TILE_PL64,  1},
-    {  5120,    64,   36, TILE_PL64,  2},
-    {  5120,   128,    8, TILE_PL64,  1},
-    {  5120,   256,    2, TILE_PL64,  1},
-    { 10816,    64,    4, TILE_PL64,  1},
-    { 10816,   128,   18, TILE_PL64,  1},
-    { 43264,    64,    2, TILE_PL64,  1},
-    { 43264,    64,    9, TILE_PL64,  1},
-    {0, 0, 0, 0, 0},
-};
-// ... fp16 mode (tools/tune_conv.py --pl --f16, profiles/r03_tune_pl_f16.txt)
-static const PlanEntry kPlanPL1[] = {
-    {    80,   512,   64, TILE_PL64,  4},
-    {    80,   512,  144, TILE_PL64,  6},
-    {    80,  2048,   16, TILE_PL64,  1},
-    {    80,  2048,   32, TILE_PL64,  1},
-    {   169,    64,   32, TILE_PL64,  4},
-    {   169,   256,   16, TILE_PL64,  3},
-    {   169,   512,   32, TILE_PL64,  4},
-    {   169,  1024,  144, TILE_PL64,  4},
-    {   320,   256,   32, TILE_PL64,  4},
-    {   320,   256,   72, TILE_PL64,  4},
-    {   320,   512,   32, TILE_PL64,  3},
-    {   320,  1024,    8, TILE_PL64,  1},
-    {   320,  1024,   16, TILE_PL64,  1},
-    {   320,  1024,  144, TILE_PL64,  3},
-    {   676,    64,   16, TILE_PL64,  1},
-    {   676,   128,    8, TILE_PL64,  1},
-    {   676,   256,   16, TILE_PL64,  1},
-    {   676,   256,   24, TILE_PL64,  1},
-    {   676,   512,   72, TILE_PL64,  2},
-    {  1280,   128,   16, TILE_PL64,  1},
-    {  1280,   128,   36, TILE_PL64,  3},
-    {  1280,   256,   16, TILE_PL64,  1},
-    {  1280,   512,    4, TILE_PL64,  1},
-    {  1280,   512,    8, TILE_PL64,  1},
-    {  1280,   512,   72, TILE_PL64,  3},
-    {  2704,    64,    8, TILE_PL64,  1},
-    {  2704,   128,    8, TILE_PL64,  1},
-    {  2704,   128,   12, TILE_PL64,  1},
-    {  2704,   256,   36, TILE_PL64,  1},
-    {  5120,    64,    2, TILE_PL64,  1},
-    {  5120,    64,    8, TILE_PL64,  1},
-    {  5120,    64,   18, TILE_PL64,  1},
-    {  5120,    64,   36, TILE_PL64,  1},
-    {  5120,   128,    8, TILE_PL64,  1},
-    {  5120,   256,    2, TILE_PL64,  1},
-    { 10816,    64,    4, TILE_PL64,  1},
-    { 10816,   128,   18, TILE_PL64,  1},
-    { 43264,    64,    2, TILE_PL64,  1},
-    { 43264,    64,    9, TILE_PL64,  1},
-    // batch 28 (BASELINE configs[2]; tools/tune_conv.py --pl --f16 --big --batch 28, profiles/r03_tune_pl_f16_batch28.txt)
-    // round 4: the 3x3 / stride-1 layers on the halo form of the 128x128 tile (TILE_PLH128; tools/bench_plh.py, profiles/r04_plh_kernels.txt:
-    // 7-10 % faster alone than the best all-DMA tile, +1.7-2.6 % on configs[2]).  A row is taken only by layers the tile can run
-    // (choose_pl checks conv_plh_eligible): the stride-2 layers that share a row's key fall through to the row below it
-    {   4732,  1024,  144, TILE_PLH128,  1},
-    {   8960,  1024,  144, TILE_PLH128,  1},   // DUC1 / DUC2 (round 5: their PixelShuffle stores take the staged epilogue in conv_pl.hip too)
-    {  35840,   512,   72, TILE_PLH128,  1},
-    {   8960,   256,   72, TILE_PLH128,  1},
-    {  18928,   512,   72, TILE_PLH128,  1},
-    {  35840,   128,   36, TILE_PLH128,  1},
-    {  75712,   256,   36, TILE_PLH128,  1},
-    { 302848,   128,   18, TILE_PLH128,  1},   // the 104x104 layers (round 5: 384 halo rows); BP_PLH_W63=1 keeps them on the 256x128 all-DMA tile (A/B runs)
-    {   2240,   512,   64, TILE_PL64,  1},
-    {   2240,   512,  144, TILE_PL64,  1},
-    {   2240,  2048,   16, TILE_PL64,  1},
-    {   2240,  2048,   32, TILE_PL128,  1},
-    {   4732,    64,   32, TILE_PL64,  1},
-    {   4732,   256,   16, TILE_PL128x64,  1},
-    {   4732,   512,   32, TILE_PL64,  1},
-    {   4732,  1024,  144, TILE_PL128,  1},
-    {   8960,   256,   32, TILE_PL64,  1},
-    {   8960,   256,   72, TILE_PL64,  1},
-    {   8960,   512,   32, TILE_PL64,  1},
-    {   8960,  1024,    8, TILE_PL64,  1},
-    {   8960,  1024,   16, TILE_PL64,  1},
-    {   8960,  1024,  144, TILE_PL256x128,  1},
-    {  18928,    64,   16, TILE_PL64,  1},
-    {  18928,   128,    8, TILE_PL64,  1},
-    {  18928,   256,   16, TILE_PL64,  1},
-    {  18928,   256,   24, TILE_PL64,  1},
-    {  18928,   512,   72, TILE_PL256x128,  1},
-    {  35840,   128,   16, TILE_PL64,  1},
-    {  35840,   128,   36, TILE_PL64,  1},
-    {  35840,   256,   16, TILE_PL64,  1},
-    {  35840,   512,    4, TILE_PL64,  1},
-    {  35840,   512,    8, TILE_PL64,  1},
-    {  35840,   512,   72, TILE_PL256x128,  1},
-    {  75712,    64,    8, TILE_PL64,  1},
-    {  75712,   128,    8, TILE_PL64,  1},
-    {  75712,   128,   12, TILE_PL256x128,  1},
-    {  75712,   256,   36, TILE_PL128,  1},
-    { 143360,    64,    2, TILE_PL64,  1},
-    { 143360,    64,    8, TILE_PL64,  1},
-    { 143360,    64,   18, TILE_PL64,  1},
-    { 143360,    64,   36, TILE_PL64,  1},
-    { 143360,   128,    8, TILE_PL64,  1},
-    { 143360,   256,    2, TILE_PL64,  1},
-    { 302848,    64,    4, TILE_PL64,  1},
-    { 302848,   128,   18, TILE_PL256x128,  1},
-    {1211392,    64,    2, TILE_PL64,  1},
-    {1211392,    64,    9, TILE_PL64,  1},
-    {0, 0, 0, 0, 0},
-};
-
-// the halo plane tile runs the layer; BP_PLH_W63=1: maps up to 63 wide only, as before round 5 (A/B runs)
-static bool plh_ok(const ConvParams& c) {
-    static const bool w63 = std::getenv("BP_PLH_W63") != nullptr;
-    return conv_plh_eligible(c) && (c.W <= 63 || !w63);
-}
-
-// conv_pl.hip (operand planes + LDS-DMA): which block tile, how many K slices
-static void choose_pl(const ConvParams& c, long long M, int mode, int sk_max, int* tile, int* splits) {
-    for (const PlanEntry& e : plan_file_entries())
-        if (e.M == (int)M && e.CoutPad == c.CoutPad && e.nchunks == c.nchunks && conv_tile_is_pl(e.tile) &&
-            (!conv_tile_is_plh(e.tile) || plh_ok(c)) &&
-            (e.tile != TILE_S1 || (e.splits == 1 && conv_s1_eligible(c, M))) &&
-            (e.tile != TILE_P3 || (e.splits == 1 && conv_p3_eligible(c, M)))) { *tile = e.tile; *splits = e.splits; return; }   // (a plan-file row naming the streaming 1x1 kernel for a layer it cannot run is ignored, not a failed launch)
-    for (const PlanEntry* e = (mode == PREC_F16 ? kPlanPL1 : kPlanPL3); e->M != 0; ++e)   // tables end with a zero row
-        if (e->M == (int)M && e->CoutPad == c.CoutPad && e->nchunks == c.nchunks &&
-            (!conv_tile_is_plh(e->tile) || plh_ok(c))) { *tile = e->tile; *splits = e->splits; return; }     // (a 3x3 row also matches stride-2 / 1x1 layers of the same K)
-    // other shapes (batched runs): the 128x128 block once its grid covers the chip (half the operand bytes per FLOP of the
-    // 64x64 block: profiles/r03_bench_pl_batch28.txt), else the 64x64 block with enough K slices to fill it
-    // (short K loops -- the 1x1 layers of the bottlenecks -- stay on the 64x64 block even then: a 128x128 block runs one per
-    // CU and its prologue / epilogue are not covered by a neighbour's K loop; profiles/r03_tune_pl_f16_batch28.txt)
-    const long long tiles128 = ((M + 127) / 128) * ((c.CoutPad + 127) / 128);
-    int t = (c.CoutPad >= 128 && tiles128 >= 192 && c.nchunks >= 32) ? TILE_PL128 : TILE_PL64;
-    if (t == TILE_PL128 && mode == PREC_F16 && plh_ok(c)) t = TILE_PLH128;     // 3x3 / stride 1: the halo form beats the all-DMA tile wherever both run
-    int s = 1;
-    if (t == TILE_PL64) {
-        const long long blocks = ((M + 63) / 64) * (c.CoutPad / 64);
-        const int min_chunks = mode == PREC_F16 ? 8 : 4;
-        while (blocks * s < 256 && c.nchunks / (s + 1) >= min_chunks && s < sk_max) ++s;
-    }
-    *tile = t; *splits = s;
-}
-#ifdef BP_EXPERIMENTAL   // BP_B3_PL64BD=1: bf16x3 on planes with the filters-direct plane tile (conv_pl.hip BDIR; A/B runs)
-static void pl64_form(const ConvParams& c, int mode, int* tile) {
-    static const bool bd = std::getenv("BP_B3_PL64BD") != nullptr;
-    if (*tile == TILE_PL64 && mode == PREC_BF16X3 && c.wbd && bd) *tile = TILE_PL64BD;
-}
-#else
-static void pl64_form(const ConvParams&, int, int*) {}
-#endif
-
-static void choose_h16(const ConvParams& c, long long M, int mode, int sk_max, int* tile, int* splits, bool lone = false) {
-    // layers with operand planes (the fp16 mode; bf16x3 under BP_B3_PLANES) run on conv_pl.hip
-#ifdef BP_EXPERIMENTAL   // BP_LEGACY=1: the fp32-activation kernels in every mode (A/B runs of the whole pipeline)
-    static const bool legacy = std::getenv("BP_LEGACY") != nullptr;
-#else
-    constexpr bool legacy = false;
-#endif
-    if (conv_pl_eligible(c) && !legacy) { choose_pl(c, M, mode, sk_max, tile, splits); pl64_form(c, mode, tile); return; }
-    if (mode == PREC_BF16X3)
-        for (const PlanEntry& e : plan_file_entries())
-            if (e.M == (int)M && e.CoutPad == c.CoutPad && e.nchunks == c.nchunks && !conv_tile_is_pl(e.tile) &&
-                (!conv_tile_is_halo(e.tile) || conv_halo_eligible(c, e.tile))) { *tile = e.tile; *splits = e.splits; return; }
-    static const bool halo_off = std::getenv("BP_NO_HALO") != nullptr;   // A/B runs: the round-3 plan (filters-direct kernel everywhere)
-#ifdef BP_EXPERIMENTAL
-    for (const PlanEntry* e = (mode == PREC_F16 ? kPlanF16 : kPlanB3); e->M != 0; ++e)   // tables end with a zero row
-#else
-    for (const PlanEntry* e = kPlanB3; e->M != 0; ++e)
-#endif
-        if (e->M == (int)M && e->CoutPad == c.CoutPad && e->nchunks == c.nchunks &&
-            (!conv_tile_is_halo(e->tile) || (!halo_off && mode == PREC_BF16X3 && conv_halo_eligible(c, e->tile)))) {
-            *tile = e->tile; *splits = e->splits;
-            if (lone && e->tile == TILE_BD_K2)
-                for (const PlanEntry* l = kPlanB3Lone; l->M != 0; ++l)
-                    if (l->M == e->M && l->CoutPad == e->CoutPad && l->nchunks == e->nchunks) { *tile = l->tile; *splits = l->splits; break; }
-            return;
-        }
-    int t = TILE_64x64_BD;   // bf16x3: the filters-direct 64x64 kernel at every batch size (profiles/r02_tune_b3_batch28.txt)
-    // ... except the 3x3 / stride-1 layers of batched runs once one slice of halo tiles fills the chip: the 64x128 halo tile is
-    // 1.2-1.5x the filters-direct kernel there (batch 28: 52x52 128 -> 256 217.6 against 319.0 us, 40x32 256 -> 512 378.8 against
-    // 545.1 us; tools/bench_halo.py --batch 28, profiles/r04_halo_kernels.txt); BP_HALO_BATCH_MIN_TILES moves the threshold (A/B runs)
-    static const int halo_min_tiles = std::getenv("BP_HALO_BATCH_MIN_TILES") ? std::atoi(std::getenv("BP_HALO_BATCH_MIN_TILES")) : 64;   // (64: batch 2 x 4 streams 1 118 -> 1 209, 4 x 3 1 274 -> 1 384, 28 x 2 1 509 -> 1 754 frames/s; 256 and 16 lose 4-8 % of that at batch 2 / 4)
-    if (mode == PREC_BF16X3 && !halo_off && c.in16 == nullptr) {
-        const int ht = conv_halo_eligible(c, TILE_HALO128) ? TILE_HALO128 : (conv_halo_eligible(c, TILE_HALO64K2) ? TILE_HALO64K2 : -1);
-        if (ht >= 0 && ((M + 63) / 64) * (c.CoutPad / conv_tile_bn(ht)) >= halo_min_tiles) { *tile = ht; *splits = 1; return; }
-    }
-#ifdef BP_EXPERIMENTAL
-    const long long tiles128 = ((M + 127) / 128) * ((c.CoutPad + 127) / 128);
-    if (!(mode == PREC_BF16X3 && c.w16s)) t = (c.CoutPad >= 128 && tiles128 >= 128) ? TILE_W64_2x2 : TILE_64x64;
-#endif
-    const int bm = conv_tile_bm(t), bn = conv_tile_bn(t);
-    const long long blocks = ((M + bm - 1) / bm) * ((c.CoutPad + bn - 1) / bn);
-    const int target = t == TILE_W64_2x2 ? 256 : (mode == PREC_F16 ? 128 : 512);
-    const int min_chunks = mode == PREC_F16 ? 8 : 4;
-    int s = 1;
-    while (blocks * s < target && c.nchunks / (s + 1) >= min_chunks && s < sk_max) ++s;
-    *tile = t; *splits = s;
-}
-
-// a forced kernel id (bp_*_set_policy, tests and sweeps) applies to the layers it can run and is ignored for the others:
-// the fp32-MFMA tiles run any layer (they read the fp32 activations), the operand-plane tiles the layers with planes
-static bool tile_runs(int tile, const ConvParams& c, long long M = 0) {
-    // a layer planned on the operand planes (in16 + wpl) may have NO fp32 input: plan_planes() dropped the fp32 store of producers
-    // whose readers all take the planes.  The kernels that read fp32 activations are therefore never forced onto such a layer
-    // (round-3 advisor finding: a forced tile 0 / 1 in the fp16 mode read tensors nobody stored)
-    const bool on_planes = c.in16 != nullptr && c.wpl != nullptr;
-    if (tile == TILE_64x64 || tile == TILE_128x64) return !on_planes;
-    if (tile == TILE_S1) return conv_s1_eligible(c, M);
-    if (tile == TILE_P3) return conv_p3_eligible(c, M);
-    if (conv_tile_is_pl(tile)) return c.mfma_mode != PREC_F32 && conv_pl_eligible(c) && (!conv_tile_is_plh(tile) || conv_plh_eligible(c));
-    if (tile == TILE_64x64_BD || tile == TILE_BD_K2) return c.mfma_mode == PREC_BF16X3 && conv_h16_eligible(c) && c.w16s != nullptr && !on_planes;
-    if (conv_tile_is_halo(tile)) return c.mfma_mode == PREC_BF16X3 && c.in16 == nullptr && conv_halo_eligible(c, tile);
-#ifdef BP_EXPERIMENTAL
-    if (tile >= 0 && tile <= TILE_LAST) return c.mfma_mode != PREC_F32 && conv_h16_eligible(c);
-#endif
-    return false;
-}
-
-// the 3x3 / stride-1 RGB stem runs as a direct convolution (conv_igemm.hip stem3x3_kernel) unless a tile is forced;
-// BP_NO_STEM3=1: on the fp32 MFMA kernel as before (A/B runs)
-static bool stem3_wanted(const ConvParams& c, int force_tile) {
-    static const bool off = std::getenv("BP_NO_STEM3") != nullptr;
-    return !off && (force_tile < 0 || force_tile == TILE_STEM3) && conv_stem3_eligible(c);
-}
-
-// the 7x7 / stride-2 RGB stem runs on the fp16 matrix pipe when the ENGINE is in an fp16 mode (the layer itself is not 16-bit eligible: 3 input
-// channels); BP_NO_STEM7=1: on the fp32 MFMA kernel as before (A/B runs)
-static bool stem7_wanted(const ConvParams& c, int force_tile) {
-    static const bool off = std::getenv("BP_NO_STEM7") != nullptr;
-    return !off && force_tile < 0 && c.net_prec == PREC_F16 && conv_stem7_eligible(c);
-}
-
-static void choose_launch(const Op& op, int batch, int force_tile, int sk_target, int sk_min_chunks, int sk_max,
-                          int* tile, int* splits, int* cps, bool lone = false) {
-    const int mode = op.conv.mfma_mode;
-    const ConvParams& c = op.conv;
-    const long long M = (long long)batch * c.OH * c.OW;
-    int t = TILE_64x64;   // fp32 MFMA kernel: 128x64 measured slower on every layer of both networks (tools/bench_conv.py)
-    int s = 1;
-    if (mode != PREC_F32) {
-        choose_h16(c, M, mode, sk_max, &t, &s, lone);
-        if (t == TILE_S1 && op.pool_out) t = TILE_PL64;     // (a plan-file row: the SE pool rides in the 64-row epilogue of the plane tile only)
-        // round 5: the 1x1 layers of the batched fp16 runs (one K slice on a conv_pl tile, no SE pool in the epilogue) on the persistent
-        // streaming kernel (conv_s1.hip); BP_NO_S1=1: the plane tiles as before (A/B runs)
-        static const bool s1_off = std::getenv("BP_NO_S1") != nullptr;
-        if (!s1_off && mode == PREC_F16 && s == 1 && conv_tile_is_pl(t) && !op.pool_out && conv_s1_eligible(c, M)) t = TILE_S1;
-        // round 6: the 3x3 / stride-1 layers of the batched fp16 runs that were planned on the halo plane tile, on the persistent kernel
-        // (conv_p3.hip); BP_NO_P3=1: the halo plane tile as before (A/B runs)
-        static const bool p3_off = std::getenv("BP_NO_P3") != nullptr;
-        if (!p3_off && mode == PREC_F16 && s == 1 && t == TILE_PLH128 && !op.pool_out && conv_p3_eligible(c, M)) t = TILE_P3;
-        // ... and its 1x1 form (128-channel groups as the "halo", four chunks as the "taps") for the 1x1 layers with K >= 512, whether they were
-        // planned on the plane tile or on the streaming kernel (28 frames, f16r, one launch at a time, profiles/r06_bench_p1.txt: 20x16 1 024 -> 256
-        // 15.1 / 16.4 -> 12.3 us, 13x13 1 024 -> 512 15.0 / 16.4 -> 12.5, 26x26 512 -> 256 17.2 / 16.5 -> 13.4, 40x32 512 -> 128 17.7 / 16.8 -> 15.5;
-        // at K = 256 the streaming kernel keeps its layers: 256 -> 1 024 16.3 against 17.9, 52x52 256 -> 128 15.7 against 16.4)
-        // BP_P3_K1 = 0: off; 2: every eligible 1x1 layer (sweeps)
-        static const int p3_k1 = std::getenv("BP_P3_K1") ? std::atoi(std::getenv("BP_P3_K1")) : 1;
-        if (!p3_off && p3_k1 && mode == PREC_F16 && s == 1 && c.ksize == 1 && conv_tile_is_pl(t) && !op.pool_out && conv_p3_eligible(c, M) &&
-            (p3_k1 == 2 || c.Cin >= 512)) t = TILE_P3;
-        if (force_tile >= 0 && !((force_tile == TILE_S1 || force_tile == TILE_P3) && op.pool_out) && tile_runs(force_tile, c, M)) t = force_tile;
-        if (!(sk_target == 512 && sk_min_chunks == 4 && sk_max == 8)) {   // explicit policy (tests, sweeps)
-            const long long blocks = ((M + conv_tile_bm(t) - 1) / conv_tile_bm(t)) *
-                                     ((c.CoutPad + conv_tile_bn(t) - 1) / conv_tile_bn(t));
-            s = 1;
-            while (blocks * s < sk_target && c.nchunks / (s + 1) >= sk_min_chunks && s < sk_max) ++s;
-        }
-        if (t == TILE_S1 || t == TILE_P3) s = 1;     // (a persistent grid: no K slices)
-    } else if (stem3_wanted(c, force_tile)) {
-        t = TILE_STEM3;       // the RGB 3x3 stem: direct convolution, no K slices
-    } else if (stem7_wanted(c, force_tile)) {
-        t = TILE_STEM7;       // the 7x7 / stride-2 RGB stem in the fp16 modes: fp16 MFMA over im2col rows in LDS, no K slices
-    } else {
-        if ((force_tile == TILE_64x64 || force_tile == TILE_128x64) && tile_runs(force_tile, c)) t = force_tile;
-        const int bm = conv_tile_bm(t);
-        const long long blocks = ((M + bm - 1) / bm) * (c.CoutPad / 64);
-        while (blocks * s < sk_target && c.nchunks / (s + 1) >= sk_min_chunks && s < sk_max) ++s;
-        if (t == TILE_64x64 && sk_target == 512 && sk_min_chunks == 4 && sk_max == 8)   // default policy: measured table
-            for (const SplitEntry& e : kSplitTable)
-                if (e.M == (int)M && e.CoutPad == c.CoutPad && e.nchunks == c.nchunks) { s = e.splits; break; }
-    }
-    {   // experiment hook (tools only): BP_SPLIT_PCT scales the slice count, e.g. 50 halves it
-        static const int pct = std::getenv("BP_SPLIT_PCT") ? std::atoi(std::getenv("BP_SPLIT_PCT")) : 100;
-        if (pct != 100 && s > 1) s = std::max(1, (s * pct + 50) / 100);
-    }
-    int per = 0;
-    conv_split_plan(c, t, s, &s, &per);
-    *tile = t; *splits = s; *cps = per;
-}
-
 int Net::add_conv(const std::string& name, const Tensor& in, const Tensor& out_view, const ConvWeights& cw, int Cout,
                   int k, int stride, int pad, int act, int store_mode, const Tensor* res, const float* res_scale,
                   int res_after_act, float bn_eps, int OH, int OW) {
@@ -685,17 +120,12 @@ size_t Net::workspace_need() const {
         if (op.type != OP_CONV) continue;
         for (int lone = 0; lone < 2; ++lone)      // every batch size under the throughput plan, then under the lone-frame plan
             for (int b = 1; b <= max_batch_; ++b) {
-                int tile, splits, cps;
-                choose_launch(op, b, force_tile_, sk_target_, sk_min_chunks_, 64, &tile, &splits, &cps, lone != 0);
                 // worst case over policies that may be set later: allow up to 64 splits at batch 1
-                ConvParams q = op.conv; q.N = b; q.M = b * q.OH * q.OW; q.splits = splits;
-                if (splits > 1) {
-                    need = std::max(need, (size_t)splits * conv_tiles(q, tile) * conv_tile_bm(tile) * conv_tile_bn(tile));
-                } else {   // a hybrid grid parks the slices of its last tiles (ConvParams::hy_*)
-                    int full = 0, hs = 0, hcps = 0;
-                    if (conv_hybrid_plan(q, tile, (size_t)-1, &full, &hs, &hcps))
-                        need = std::max(need, (size_t)hs * (conv_tiles(q, tile) - full) * conv_tile_bm(tile) * conv_tile_bn(tile));
-                }
+                const ConvLaunch l = plan_conv(op, b, PlanPolicy{policy_.force_tile, policy_.sk_target, policy_.sk_min_chunks, 64, lone != 0});
+                ConvParams q = op.conv; q.N = b; q.M = b * q.OH * q.OW; q.splits = l.splits;
+                HybridTail h;      // a hybrid grid parks the slices of its last tiles (ConvParams::hy_*)
+                if (l.splits > 1) need = std::max(need, conv_slab_floats(l.tile, l.splits, conv_tiles(q, l.tile)));
+                else if (conv_hybrid_plan(q, l.tile, (size_t)-1, &h)) need = std::max(need, h.slab_floats);
             }
     }
     return std::max(need, (size_t)4 << 20);   // headroom so a later policy change can still split small layers
@@ -750,18 +180,37 @@ void Net::find_fuse_groups() {
     }
 }
 
-// Which groups run fused under the current plan at this batch size: bf16x3 on the fp32-activation path, every member eligible for the
+// The plan of one pass at this batch size, made once per (batch, plan version): every convolution's launch, then the fusion roles.
+// Which groups run fused: bf16x3 on the fp32-activation path or fp16 on the operand planes, every member eligible for the
 // fused kernel, enough patches to be worth a launch of their own.  A three-member group whose last 1x1 cannot join (the SE blocks'
 // conv3 carries the average pool in its epilogue) falls back to its first two members.
-void Net::plan_roles(int batch) {
-    if (roles_batch_ == batch && roles_version_ == plan_version_) return;
-    roles_.assign(ops_.size(), FR_NONE);
-    role_group_.assign(ops_.size(), -1);
-    roles_batch_ = batch; roles_version_ = plan_version_;
+const std::vector<Net::OpPlan>& Net::plan(int batch) {
+    BP_CHECK(batch >= 1 && batch <= max_batch_, "batch out of range");
+    if (plans_version_ != plan_version_) { plans_.assign(max_batch_, {}); plans_version_ = plan_version_; }
+    std::vector<OpPlan>& pl = plans_[batch - 1];
+    if (pl.size() == ops_.size()) return pl;
+    pl.assign(ops_.size(), OpPlan{});
+    int ord = 0;
+    for (size_t i = 0; i < ops_.size(); ++i) {
+        const Op& op = ops_[i];
+        if (op.type == OP_AVGPOOL) pl[i].pooled = i > 0 && ops_[i - 1].type == OP_CONV && ops_[i - 1].pool_out == op.out && pl[i - 1].pooled;
+        if (op.type != OP_CONV) continue;
+        ConvLaunch& l = pl[i].launch;
+        l = plan_conv(op, batch, policy_);
+        ConvParams q = op.conv; q.M = batch * q.OH * q.OW;
+        const int planned = l.splits;
+        while (l.splits > 1 && conv_slab_floats(l.tile, l.splits, conv_tiles(q, l.tile)) > partial_floats_) conv_split_plan(q, l.tile, l.splits - 1, &l.splits, &l.cps);
+        static bool warned = false;   // (a policy / plan file set after finalize() may ask for more slab space than the workspace holds: say so once)
+        if (l.splits != planned && !warned && (warned = true))
+            std::fprintf(stderr, "betapose_hip: %s planned with %d K slices runs with %d (split-K workspace of %zu floats)\n",
+                         op.name.c_str(), planned, l.splits, partial_floats_);
+        pl[i].conv_ord = ord++;
+        pl[i].pooled = pool_in_epilogue(op, batch, l.tile);
+    }
     static const bool env_off = std::getenv("BP_NO_FUSION") != nullptr;
     static const int min_blocks = env_int_early("BP_FUSE_MIN_BLOCKS", 48);
-    if (!fusion_ || env_off || precision_ == PREC_F32 || force_tile_ >= 0) return;      // (bf16x3 on fp32 activations, fp16 on the operand planes)
-    for (int gi = 0; gi < (int)fuse_groups_.size(); ++gi) {
+    if (!fusion_ || env_off || precision_ == PREC_F32 || policy_.force_tile >= 0) return pl;
+    for (int gi = 0; gi < (int)fuse_groups_.size(); ++gi) {      // (prepare_conv reads the launches made above)
         const FuseGroup& g = fuse_groups_[gi];
         ConvParams a, b, c;
         int ta, tb, tc;
@@ -773,19 +222,19 @@ void Net::plan_roles(int batch) {
             three = conv_fused_eligible(a, b, &c) && conv_fused_blocks(a, b, &c) >= min_blocks;
         }
         if (three) {
-            roles_[g.pre] = roles_[g.c3] = FR_SKIP; roles_[g.post] = FR_HEAD3;
-            role_group_[g.pre] = role_group_[g.c3] = role_group_[g.post] = gi;
+            pl[g.pre].role = pl[g.c3].role = FR_SKIP; pl[g.post].role = FR_HEAD3;
+            pl[g.pre].group = pl[g.c3].group = pl[g.post].group = gi;
         } else if (conv_fused_eligible(a, b, nullptr) && conv_fused_blocks(a, b, nullptr) >= min_blocks) {
-            roles_[g.pre] = FR_SKIP; roles_[g.c3] = FR_HEAD2;
-            role_group_[g.pre] = role_group_[g.c3] = gi;
+            pl[g.pre].role = FR_SKIP; pl[g.c3].role = FR_HEAD2;
+            pl[g.pre].group = pl[g.c3].group = gi;
         }
     }
+    return pl;
 }
 
 int Net::fused_launches(int batch) {
-    plan_roles(batch);
     int n = 0;
-    for (int r : roles_) n += r == FR_HEAD2 || r == FR_HEAD3;
+    for (const OpPlan& o : plan(batch)) n += o.role == FR_HEAD2 || o.role == FR_HEAD3;
     return n;
 }
 
@@ -1039,9 +488,6 @@ void Net::plan_planes(int prec, int mix_hw) {
 
 static int planes_np(int prec) { return prec == PREC_F16 ? 1 : 3; }
 
-// filter prefetch (ConvParams::pf_*): one extra block per (N-tile, K-slice) pair of the next launch pulls at most this much
-static int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v ? std::atoi(v) : dflt; }
-static const int kPrefetchCap = env_int("BP_PF_CAP_KB", 128) * 1024;
 // XCC_ID of block 0 of a launch, or -1 when the dispatch is not the round robin ConvParams::xcd_home relies on (or
 // BP_NO_XCD_HOME=1): one probe launch per process, 64 blocks, every block b must report (base + b) % 8
 int xcc_base() {
@@ -1071,52 +517,6 @@ int xcc_base() {
     return base;
 }
 
-// p's launch carries the prefetch blocks for `next` (launched with tile nt, ns K slices of nc chunks), when next's work
-// blocks of residue x read the N-tiles n == x (mod min(N-tiles, 8)) -- the xcd_home layout, or the plain one-slice grid of the
-// 64x64 filters-direct kernel -- from a filter image that is contiguous per (N-tile, K-slice) pair
-// Hybrid grid of a one-slice conv_pl launch (ConvParams::hy_*): when the launch is ONE block per CU plus a few more (256 < tiles
-// <= 422 on 256 CUs), 256 tiles run whole and the rest are cut along K so that they spread over every CU instead of doubling
-// up on a few.  Measured at batch 28, fp16 (profiles/r03_hybrid_grid.txt): 296 tiles of 256x128 72.2 -> 65.9 us, 280 tiles
-// 124.8 -> 106.1 us, 296 tiles of 128x128 72.5 -> 67.5 us; with several blocks per CU in flight the dispatcher balances the
-// tail by itself and the cut only adds its reduction (1 184 tiles of 128x128: 79.8 -> 98.8 us), so longer grids stay whole.
-// In the PIPELINE it loses -- fp16 batch 28 x 3 streams 3 940-4 010 against 4 060-4 140 frames/s, the other runs unchanged: with
-// other streams' blocks on the CUs there is no "one block per CU" to complete -- so it is OFF unless BP_HYBRID=1 (A/B runs, tests).
-bool conv_hybrid_plan(const ConvParams& p, int tile, size_t partial_floats, int* full, int* hs, int* hcps) {
-    // (read per call on purpose: tests/test_gpu_conv.py::test_conv_pl_hybrid_grid toggles it inside one process; the lookup only runs
-    // for one-slice conv_pl launches in eager mode and at graph capture, never in a graph replay)
-    const bool off = std::getenv("BP_HYBRID") == nullptr;
-    if (off || !conv_tile_is_pl(tile) || p.splits != 1 || p.xcd_home || p.nchunks < 16) return false;
-    if (!(tile == TILE_PL64 || tile == TILE_PL128 || tile == TILE_PL128x64 || tile == TILE_PL256x128)) return false;
-    const int T = conv_tiles(p, tile), unit = 256;
-    const int rem = T - unit;
-    if (rem <= 0 || rem * 100 > unit * 65) return false;
-    int s = std::min(std::min(unit / rem, 8), p.nchunks / 8);
-    if (s < 2) return false;
-    const int cps = (p.nchunks + s - 1) / s;
-    s = (p.nchunks + cps - 1) / cps;
-    if ((size_t)s * rem * conv_tile_bm(tile) * conv_tile_bn(tile) > partial_floats) return false;
-    *full = unit; *hs = s; *hcps = cps;
-    return true;
-}
-
-bool conv_home_layout(int tile, int splits) {
-    return splits > 1 && splits <= 64 && xcc_base() >= 0 && (tile == TILE_64x64_BD || (conv_tile_is_pl(tile) && !conv_tile_is_plh(tile)));
-}
-void conv_prefetch_of(ConvParams& p, const ConvParams& next, int nt, int ns, int nc) {
-    p.pf_ptr = nullptr;
-    const bool plbd = nt == TILE_PL64BD && next.mfma_mode == PREC_BF16X3 && next.wbd && conv_home_layout(nt, ns);
-    const bool pl = plbd || (next.mfma_mode != PREC_F32 && (nt == TILE_PL64) && next.wpl && conv_home_layout(nt, ns));
-    const bool bd = nt == TILE_64x64_BD && next.mfma_mode == PREC_BF16X3 && next.w16s && (ns == 1 || conv_home_layout(nt, ns));
-    const int ntn = (next.CoutPad + 63) / 64;
-    if (!(pl || bd) || (ntn & (ntn - 1)) != 0 || xcc_base() < 0) return;
-    const int np = planes_np(next.mfma_mode);
-    p.pf_ptr = plbd ? (const void*)next.wbd : pl ? (const void*)next.wpl : (const void*)next.w16s;
-    p.pf_ntn = ntn; p.pf_splits = ns; p.pf_cps = nc; p.pf_nchunks = next.nchunks;
-    p.pf_chunk_bytes = np * 4096;                  // 64 filter rows x 32 k x 2 B per plane
-    p.pf_tile_stride = next.nchunks * p.pf_chunk_bytes;
-    p.pf_cap = kPrefetchCap;
-}
-
 // The SE blocks' average pool inside the producing conv's epilogue (ConvParams::pool_out): for the 64-row tiles with the
 // staged vector epilogue, when a tile never spans two images.  BP_NO_POOL_FUSION=1: the separate kernel (A/B, tests).
 bool Net::pool_in_epilogue(const Op& conv, int batch, int tile) const {
@@ -1126,69 +526,46 @@ bool Net::pool_in_epilogue(const Op& conv, int batch, int tile) const {
     if (c.store_mode != ST_NHWC || c.res || c.res_scale || c.act != ACT_LINEAR || (c.out_ld & 3) || (c.Cout & 3)) return false;
     return batch == 1 || (c.OH * c.OW) % 64 == 0;
 }
-bool Net::pooled_by_conv(const Op& pool, int batch) const {
-    if (&pool == ops_.data()) return false;
-    const Op& prev = *(&pool - 1);
-    if (prev.type != OP_CONV || prev.pool_out != pool.out) return false;
-    int tile, splits, cps;
-    choose_launch(prev, batch, force_tile_, sk_target_, sk_min_chunks_, sk_max_splits_, &tile, &splits, &cps, prefetch_);
-    return pool_in_epilogue(prev, batch, tile);
-}
 
-// the launch descriptor of convolution `op` at this batch size under the current plan: tile, K slices, workspaces, epilogue extras
+// the launch descriptor of convolution `op` at this batch size under the current plan: tile, K slices, workspaces, epilogue extras.
+// What follows from the plan alone comes from plan(batch); the stamp pointer, the XCD-home mark, the hybrid tail and the prefetch fields
+// are made here, per launch
 void Net::prepare_conv(const Op& op, int batch, ConvParams& p, int& tile) {
-    {
-        {
-            p = op.conv;
-            p.N = batch;
-            p.M = batch * p.OH * p.OW;
-            int splits, cps;
-            choose_launch(op, batch, force_tile_, sk_target_, sk_min_chunks_, sk_max_splits_, &tile, &splits, &cps, prefetch_);
-            const int planned = splits;
-            while (splits > 1 && (size_t)splits * conv_tiles(p, tile) * conv_tile_bm(tile) * conv_tile_bn(tile) > partial_floats_) {
-                conv_split_plan(p, tile, splits - 1, &splits, &cps);
-            }
-            if (splits != planned) {   // (a policy / plan file set after finalize() may ask for more slab space than the workspace holds: say so once)
-                static bool warned = false;
-                if (!warned) {
-                    warned = true;
-                    std::fprintf(stderr, "betapose_hip: %s planned with %d K slices runs with %d (split-K workspace of %zu floats)\n",
-                                 op.name.c_str(), planned, splits, partial_floats_);
-                }
-            }
-            p.splits = splits; p.chunks_per_split = cps; p.partial = partial_; p.tickets = tickets_;
-            p.tickets_local = tickets_ + tickets_count_;
-            p.xcc_of = tickets_ + 2 * tickets_count_;
-            p.err_word = tickets_ + (2 + 64) * tickets_count_;
-            p.stamps = nullptr;
-            if (stamps_) {   // in-situ timing (set_stamps): this conv's region of the stamp buffer, when its grid fits
-                int ord = 0;
-                for (const Op* q = ops_.data(); q != &op; ++q) ord += q->type == OP_CONV;
-                if ((long long)conv_tiles(p, tile) * splits <= stamp_slots_) p.stamps = stamps_ + ((size_t)ord * stamp_slots_) * 8;
-            }
-            // lone-frame latency mode (set_prefetch; bp_common.h "launch layout by XCD"): all K slices of a tile on one XCD with
-            // the hand-off through its L2 (xcd_home), and blocks that pull the next convolution's filters into the L2 that
-            // will read them (pf_*; a hint: a wrong guess about the next launch costs bandwidth, not correctness).  One frame
-            // at a time: 377 -> 384 -> 395 frames/s (fp16 533 -> 545 -> 558); with four in flight 916 -> 908 -> 895, so it is
-            // a mode, not the default (profiles/r03_prefetch_ab.txt)
-            p.xcd_home = (prefetch_ && conv_home_layout(tile, splits)) ? (std::getenv("BP_XCD_FAULT") ? 3 : 1) : 0;   // (3: the tests' fault injection, conv_dev.h xcd_home_mark)   // (with four frames in flight it gains nothing even on launches whose tiles divide evenly over the XCDs: 898 against 896)
-            p.pool_out = pool_in_epilogue(op, batch, tile) ? op.pool_out : nullptr;
-            p.hy_splits = 0;
-            if (splits == 1 && !p.pool_out && conv_hybrid_plan(p, tile, partial_floats_, &p.hy_full, &p.hy_splits, &p.hy_cps)) {
-                if ((long long)(conv_tiles(p, tile) - p.hy_full) > (long long)tickets_count_) p.hy_splits = 0;
-            }
-            p.pf_ptr = nullptr;
-            if (prefetch_ && (tile == TILE_64x64_BD || conv_tile_is_pl(tile))) {
-                for (const Op* q = &op + 1; q != ops_.data() + ops_.size(); ++q) {
-                    if (q->type != OP_CONV) continue;
-                    ConvParams n = q->conv;
-                    n.N = batch; n.M = batch * n.OH * n.OW;
-                    int nt, ns, nc;
-                    choose_launch(*q, batch, force_tile_, sk_target_, sk_min_chunks_, sk_max_splits_, &nt, &ns, &nc, prefetch_);
-                    conv_prefetch_of(p, n, nt, ns, nc);
-                    break;
-                }
-            }
+    const std::vector<OpPlan>& pl = plan(batch);
+    const size_t idx = &op - ops_.data();
+    const ConvLaunch& l = pl[idx].launch;
+    tile = l.tile;
+    p = op.conv;
+    p.N = batch;
+    p.M = batch * p.OH * p.OW;
+    p.splits = l.splits; p.chunks_per_split = l.cps; p.partial = partial_; p.tickets = tickets_;
+    p.tickets_local = tickets_ + tickets_count_;
+    p.xcc_of = tickets_ + 2 * tickets_count_;
+    p.err_word = tickets_ + (2 + 64) * tickets_count_;
+    p.stamps = nullptr;
+    // in-situ timing (set_stamps): this conv's region of the stamp buffer, when its grid fits
+    if (stamps_ && (long long)conv_tiles(p, tile) * l.splits <= stamp_slots_) p.stamps = stamps_ + ((size_t)pl[idx].conv_ord * stamp_slots_) * 8;
+    // lone-frame latency mode (set_prefetch; bp_common.h "launch layout by XCD"): all K slices of a tile on one XCD with
+    // the hand-off through its L2 (xcd_home), and blocks that pull the next convolution's filters into the L2 that
+    // will read them (pf_*; a hint: a wrong guess about the next launch costs bandwidth, not correctness).  One frame
+    // at a time: 377 -> 384 -> 395 frames/s (fp16 533 -> 545 -> 558); with four in flight 916 -> 908 -> 895, so it is
+    // a mode, not the default (profiles/r03_prefetch_ab.txt)
+    p.xcd_home = (policy_.lone && conv_home_layout(tile, l.splits)) ? (std::getenv("BP_XCD_FAULT") ? 3 : 1) : 0;   // (3: the tests' fault injection, conv_dev.h xcd_home_mark)   // (with four frames in flight it gains nothing even on launches whose tiles divide evenly over the XCDs: 898 against 896)
+    p.pool_out = pl[idx].pooled ? op.pool_out : nullptr;
+    p.hy_splits = 0;
+    HybridTail h;
+    if (l.splits == 1 && !p.pool_out && conv_hybrid_plan(p, tile, partial_floats_, &h)) {
+        p.hy_full = h.full; p.hy_cps = h.cps;
+        p.hy_splits = (size_t)h.tiles > tickets_count_ ? 0 : h.splits;
+    }
+    p.pf_ptr = nullptr;
+    if (policy_.lone && (tile == TILE_64x64_BD || conv_tile_is_pl(tile))) {
+        size_t q = idx + 1;
+        while (q < ops_.size() && ops_[q].type != OP_CONV) ++q;
+        if (q < ops_.size()) {
+            ConvParams n = ops_[q].conv;
+            n.N = batch; n.M = batch * n.OH * n.OW;
+            conv_prefetch_of(p, n, pl[q].launch);
         }
     }
 }
@@ -1211,12 +588,11 @@ void Net::emit_conv_ops(int batch, std::vector<MegaOp>& out) {
 
 void Net::run_op(const Op& op, int batch, hipStream_t s) {
     if (op.type == OP_CONV) {
-        plan_roles(batch);
-        const int idx = (int)(&op - ops_.data());
-        const int role = roles_[idx];
+        const OpPlan& o = plan(batch)[&op - ops_.data()];
+        const int role = o.role;
         if (role == FR_SKIP) return;                       // computed inside the group's one launch (at its last member)
         if (role == FR_HEAD2 || role == FR_HEAD3) {
-            const FuseGroup& g = fuse_groups_[role_group_[idx]];
+            const FuseGroup& g = fuse_groups_[o.group];
             ConvParams a, b, c;
             int ta, tb, tc;
             prepare_conv(ops_[g.pre], batch, a, ta);
@@ -1263,7 +639,7 @@ void Net::run_op_unfused(const Op& op, int batch, hipStream_t s) {
             launch_pixel_shuffle2(op.a, op.out, batch, op.H, op.W, op.C, s, op.out16, op.out16_plane, planes_np(precision_));
             break;
         case OP_AVGPOOL:
-            if (pooled_by_conv(op, batch)) break;      // its slice sums were written by the producing conv's epilogue
+            if (plan(batch)[&op - ops_.data()].pooled) break;      // its slice sums were written by the producing conv's epilogue
             // (a tensor whose fp32 store was dropped because only its plane is read -- plan_planes -- is rebuilt from the plane for this kernel)
             if (ActAlloc* a = find_act(op.a); a && a->planes && !a->f32_read && precision_ != PREC_F32)
                 launch_planes_to_f32(a->planes + (op.a - a->base), (long long)a->elems, precision_ == PREC_F16 ? 1 : 3, const_cast<float*>(op.a), op.a_ld,
@@ -1272,7 +648,7 @@ void Net::run_op_unfused(const Op& op, int batch, hipStream_t s) {
             break;
         case OP_FC: {
             int parts = op.in_parts;
-            if (&op != ops_.data() && (&op - 1)->type == OP_AVGPOOL && (&op - 1)->out == op.a && pooled_by_conv(*(&op - 1), batch))
+            if (&op != ops_.data() && (&op - 1)->type == OP_AVGPOOL && (&op - 1)->out == op.a && plan(batch)[&op - 1 - ops_.data()].pooled)
                 parts = ((&op - 1)->H * (&op - 1)->W + 63) / 64;
             launch_fc(op.a, op.w, op.bias, op.out, batch, op.Cin, op.Cout, op.act, parts, op.in_scale, s);
         } break;
@@ -1297,8 +673,7 @@ int Net::profile(int batch, int iters, float* ms, int* info, int cap, hipStream_
     run_ops(batch, s);   // warm
     for (int it = 0; it < iters; ++it) {
         for (int i = 0; i < n; ++i) {
-            plan_roles(batch);
-            if (ops_[i].type == OP_CONV && roles_[i] != FR_SKIP) {      // (a member computed inside its block's one launch launches nothing: empty bracket)
+            if (ops_[i].type == OP_CONV && plan(batch)[i].role != FR_SKIP) {      // (a member computed inside its block's one launch launches nothing: empty bracket)
                 ConvProfHook hook{ev[2 * i], ev[2 * i + 1]};
                 g_conv_prof = &hook;
                 try { run_op(ops_[i], batch, s); } catch (...) { g_conv_prof = nullptr; throw; }
@@ -1320,12 +695,13 @@ int Net::profile(int batch, int iters, float* ms, int* info, int cap, hipStream_
     for (int i = 0; i < n; ++i) {
         ms[i] = (float)(acc[i] / iters);
         // an average pool whose slice sums ride in the producing conv's epilogue launches nothing: 0 ms, info tile = -1
-        const bool fused_away = ops_[i].type == OP_AVGPOOL && pooled_by_conv(ops_[i], batch);
+        const OpPlan& o = plan(batch)[i];
+        const bool fused_away = ops_[i].type == OP_AVGPOOL && o.pooled;
         if (fused_away) ms[i] = 0.f;
         if (info) {
-            int tile = 0, splits = 1, cps = 0, vec = 0, conv = ops_[i].type == OP_CONV;
+            int tile = 0, splits = 1, vec = 0, conv = ops_[i].type == OP_CONV;
             if (conv) {
-                choose_launch(ops_[i], batch, force_tile_, sk_target_, sk_min_chunks_, sk_max_splits_, &tile, &splits, &cps, prefetch_);
+                tile = o.launch.tile; splits = o.launch.splits;
                 vec = conv_vec_mode(ops_[i].conv) ? 1 : 0;
                 if (ops_[i].conv.mfma_mode != PREC_F32 && tile != TILE_64x64 && tile != TILE_128x64)
                     vec = 1 + ops_[i].conv.mfma_mode;   // 2 fp16 operands, 3 bf16x3 operands
@@ -1333,9 +709,8 @@ int Net::profile(int batch, int iters, float* ms, int* info, int cap, hipStream_
             // members of a fused block (conv_fused.hip): the skipped ones launch nothing (tile -1, like the pooled average pools), the
             // last one carries the block's one launch (TILE_FUSED); their FLOPs / bytes belong to that launch (bench.py adds them up)
             if (conv) {
-                plan_roles(batch);
-                if (roles_[i] == FR_SKIP) { tile = -1; ms[i] = 0.f; }
-                else if (roles_[i] == FR_HEAD2 || roles_[i] == FR_HEAD3) { tile = TILE_FUSED; splits = 1; vec = 1 + ops_[i].conv.mfma_mode; }
+                if (o.role == FR_SKIP) { tile = -1; ms[i] = 0.f; }
+                else if (o.role == FR_HEAD2 || o.role == FR_HEAD3) { tile = TILE_FUSED; splits = 1; vec = 1 + ops_[i].conv.mfma_mode; }
             }
             info[4 * i] = conv; info[4 * i + 1] = fused_away ? -1 : tile; info[4 * i + 2] = vec; info[4 * i + 3] = splits;
         }
@@ -1348,10 +723,10 @@ void Net::tap_copy(int i, int batch, float* d_out_nchw, hipStream_t s) {
     const Tensor& t = taps_[i];
     // a tensor that lives only inside a fused block (conv_fused.hip) is rebuilt here by the unfused launches of the members that make it:
     // their inputs are intact (one allocation per layer output) -- the tap then shows what the UNFUSED kernels compute from the same input
-    plan_roles(batch);
+    const std::vector<OpPlan>& pl = plan(batch);
     for (int j = 0; j < (int)ops_.size(); ++j)
-        if (ops_[j].type == OP_CONV && roles_[j] == FR_SKIP && ops_[j].conv.out == t.p) {
-            const FuseGroup& g = fuse_groups_[role_group_[j]];
+        if (ops_[j].type == OP_CONV && pl[j].role == FR_SKIP && ops_[j].conv.out == t.p) {
+            const FuseGroup& g = fuse_groups_[pl[j].group];
             run_op_unfused(ops_[g.pre], batch, s);
             if (j == g.c3) run_op_unfused(ops_[g.c3], batch, s);
         }

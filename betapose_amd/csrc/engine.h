@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bp_common.h"
+#include "conv_plan.h"
 
 namespace bp {
 
@@ -92,9 +93,9 @@ public:
     const char* tap_name(int i) const { return tap_names_[i].c_str(); }
     void tap_shape(int i, int* C, int* H, int* W) const { *C = taps_[i].C; *H = taps_[i].H; *W = taps_[i].W; }
     void tap_copy(int i, int batch, float* d_out_nchw, hipStream_t s);
-    void set_splitk_policy(int target_blocks, int min_chunks) { sk_target_ = target_blocks; sk_min_chunks_ = min_chunks; ++plan_version_; }
-    void set_max_splits(int m) { sk_max_splits_ = m; ++plan_version_; }
-    void set_force_tile(int t) { force_tile_ = t; ++plan_version_; }
+    void set_splitk_policy(int target_blocks, int min_chunks) { policy_.sk_target = target_blocks; policy_.sk_min_chunks = min_chunks; ++plan_version_; }
+    void set_max_splits(int m) { policy_.sk_max = m; ++plan_version_; }
+    void set_force_tile(int t) { policy_.force_tile = t; ++plan_version_; }
     // PREC_F16 / PREC_BF16X3: eligible convs (Cin % 32 == 0) run on the 16-bit MFMA kernels with converted filter copies
     // prec 3 (PREC_F16_RES): the fp16 mode with fp16 SKIP CONNECTIONS -- a residual is read from the fp16 plane its producer wrote
     // for the next convolution, and a tensor that only convolutions and residual adds read loses its fp32 store (ConvParams::res16)
@@ -109,7 +110,7 @@ public:
     // lone-frame latency mode: split-K hand-off inside one XCD's L2 + blocks that pull the next layer's filters into the L2
     // that will read them (bp_common.h ConvParams::xcd_home / pf_*).  Off by default: +4.7 % one frame at a time, -1 .. -2 %
     // with two to four in flight
-    void set_prefetch(bool on) { prefetch_ = on; ++plan_version_; }
+    void set_prefetch(bool on) { policy_.lone = on; ++plan_version_; }
     // conv -> conv fusion of whole residual / bottleneck blocks (conv_fused.hip, round 5; on by default, BP_NO_FUSION=1 / set_fusion(false)
     // for the unfused plan: A/B runs, the fused-vs-unfused tests)
     void set_fusion(bool on) { fusion_ = on; ++plan_version_; }
@@ -117,8 +118,7 @@ public:
     int fused_launches(int batch);        // groups the current plan runs as ONE launch at this batch size
     int take_xcd_errors(hipStream_t s);   // non-zero: some launch of the latency mode found a K slice on the wrong XCD and skipped its tile -- run the frame again without the mode
     bool pool_in_epilogue(const Op& conv, int batch, int tile) const;
-    bool pooled_by_conv(const Op& pool, int batch) const;
-    bool prefetch() const { return prefetch_; }
+    bool prefetch() const { return policy_.lone; }
     const char* op_name(int i) const { return ops_[i].name.c_str(); }
 
 protected:
@@ -157,24 +157,25 @@ protected:
     size_t partial_floats_ = 0;
     int* tickets_ = nullptr;
     size_t tickets_count_ = 0;
-    int sk_target_ = 512, sk_min_chunks_ = 4, sk_max_splits_ = 8;
-    int force_tile_ = -1;
+    PlanPolicy policy_;           // forced tile, split-K fill rule, lone-frame mode (conv_plan.h)
     bool darknet_bn_ = false;
     int precision_ = PREC_F32;
     unsigned long long* stamps_ = nullptr;
     int stamp_slots_ = 0;
-    bool prefetch_ = false;
     // fusion groups: consecutive convolutions [1x1] -> [3x3 / stride 1] (-> [1x1]) whose intermediate tensors nobody else reads (found once, in
-    // finalize()); which of them run fused is a property of the plan (precision, batch size): roles_ caches it per (batch, plan version)
+    // finalize()); which of them run fused is a property of the plan (precision, batch size, policy)
     struct FuseGroup { int pre, c3, post; };
     enum FuseRole : int { FR_NONE = 0, FR_SKIP = 1, FR_HEAD2 = 2, FR_HEAD3 = 3 };
     std::vector<FuseGroup> fuse_groups_;
-    std::vector<int> roles_, role_group_;
-    int roles_batch_ = -1;
-    unsigned roles_version_ = ~0u;
     bool fusion_ = true;
     void find_fuse_groups();
-    void plan_roles(int batch);
+    // The plan of one pass, per op: the convolution's launch (after the clamp to the split-K workspace), its ordinal among the convolutions,
+    // whether the SE average pool rides in its epilogue (on the OP_AVGPOOL behind it: it launches nothing), its fuse role and group.
+    // One vector per batch size 1..max_batch_, filled on first use, all dropped when plan_version_ moves.
+    struct OpPlan { ConvLaunch launch; int conv_ord = -1; bool pooled = false; int role = FR_NONE, group = -1; };
+    std::vector<std::vector<OpPlan>> plans_;
+    unsigned plans_version_ = ~0u;
+    const std::vector<OpPlan>& plan(int batch);
     void run_op_unfused(const Op& op, int batch, hipStream_t s);
     bool f16_res_ = false;        // fp16 skip connections (set_precision(PREC_F16_RES))
     unsigned plan_version_ = 0;   // bumped whenever launches would change (captured graphs must be rebuilt)

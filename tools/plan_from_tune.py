@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/tune_conv.py output -> plan lines ("M CoutPad nchunks tile splits", one per distinct shape) for BP_PLAN_FILE, or
-with --cpp the initializer rows of engine.cpp's kPlanB3.  `--only rd4,kg4` keeps a new tile only where it wins by
+with --cpp the initializer rows of conv_plan.cpp's kPlanB3.  `--only rd4,kg4` keeps a new tile only where it wins by
 --margin percent over the 64x64-block kernel (isolated timings are noisy at the 2-3 % level)."""
 import re
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-shape split-K tuning: time every distinct conv shape of both networks alone with each candidate slice count
-and print the table engine.cpp embeds (kSplitTable).  Run on an MI355X: python tools/tune_conv.py"""
+and print the table conv_plan.cpp embeds (kSplitTable).  Run on an MI355X: python tools/tune_conv.py"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -11,8 +11,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = open(os.path.join(ROOT, "betapose_amd", "csrc", "engine.cpp")).read()
-a = src.index("static const PlanEntry kPlanB3[] = {")
+src = open(os.path.join(ROOT, "betapose_amd", "csrc", "conv_plan.cpp")).read()
+a = src.index("static const PlanRow kPlanB3[] = {")
 TILE_ID = {"TILE_64x64_BD": 12, "TILE_BD_K2": 24, "TILE_HALO64K2": 23, "TILE_HALO128": 22, "TILE_HALO64": 21}
 rows = re.findall(r"\{\s*(\d+),\s*(\d+),\s*(\d+),\s*(TILE_\w+),\s*(\d+)\}", src[a:src.index("};", a)])
 plan = {}
