@@ -923,13 +923,30 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
         if (store_mode == bp::ST_UP2) out_elems *= 4;
         p.out16 = d_out_planes; p.out16_plane = out_elems; p.out_np = np;
     }
-    // BP_CONV_F16R=1 (bench tools): the launch as the engine's 'f16r' plan makes it -- the skip connection read from an fp16 plane of the
-    // residual tensor (ConvParams::res16) and, when output planes are asked for, the fp32 store dropped (ConvParams::skip_f32)
+    // BP_CONV_F16R=1 (bench tools, tests/test_gpu_conv.py; read per call): the launch as the engine's 'f16r' plan makes it -- the skip
+    // connection read from an fp16 plane of the residual tensor (ConvParams::res16) and, when output planes are asked for, the fp32 store
+    // dropped (ConvParams::skip_f32)
     if (prec == bp::PREC_F16 && std::getenv("BP_CONV_F16R")) {
         if (p.res) {
             const long long n_res = (long long)N * OH * OW;
             unsigned short* r16 = (unsigned short*)net.arena_.alloc_bytes((size_t)n_res * p.res_ld * 2);
-            bp::launch_f32_to_planes(p.res, p.res_ld, n_res, Cout, r16, n_res * p.res_ld, 1, s);
+            if (Cout % 4 == 0) bp::launch_f32_to_planes(p.res, p.res_ld, n_res, Cout, r16, n_res * p.res_ld, 1, s);
+            else {
+                // Cout % 4 != 0 (the element-wise epilogue's layers): the converter moves four channels at a time, and the caller's residual is
+                // dense (ld == Cout) -- the tensor as one run of quads, its last 1-3 elements rounded on the host (RNE, as the device does)
+                const long long total = n_res * p.res_ld, quads = total / 4;
+                if (quads > 0) bp::launch_f32_to_planes(p.res, 4, quads, 4, r16, total, 1, s);
+                const int nt = (int)(total - 4 * quads);
+                if (nt > 0) {
+                    float tail32[3];
+                    unsigned short tail16[3];
+                    BP_HIP(hipStreamSynchronize(s));      // (the caller's residual is ordered on `s`; the copies below run on the null stream and are
+                                                          // safe only because hipMemcpy returns when the copy is done -- before the launch on `s` is enqueued)
+                    BP_HIP(hipMemcpy(tail32, p.res + 4 * quads, nt * sizeof(float), hipMemcpyDeviceToHost));
+                    for (int i = 0; i < nt; ++i) { const _Float16 h = (_Float16)tail32[i]; std::memcpy(&tail16[i], &h, 2); }
+                    BP_HIP(hipMemcpy(r16 + 4 * quads, tail16, nt * 2, hipMemcpyHostToDevice));
+                }
+            }
             p.res16 = r16;
         }
         if (p.out16) p.skip_f32 = 1;

@@ -26,11 +26,19 @@ for _n, _i in (("kg1", 7), ("kg2", 8), ("kg4", 9), ("rd4", 10), ("rd8", 11)):
 
 def conv2d_nhwc(x, weight, bias=None, stride: int = 1, pad: int = 0, act: str = "linear", store: str = "nhwc",
                 res=None, res_after_act: bool = False, tile: str = "auto", splits: int = 0, iters: int = 0,
-                planes: bool = False):
+                planes: bool = False, out=None):
     """One fused convolution.  ``x``: cuda f32 [N,H,W,Cin] (NHWC); ``weight``: host
     numpy/torch [Cout,Cin,k,k]; returns the output tensor laid out per ``store`` and,
     when ``iters`` > 0, also the measured ms per launch.  ``planes``: also return the operand planes the epilogue
-    emits for the next layer (int16 tensor [np, *out.shape]: np = 1 fp16 bits / 3 bf16 bits)."""
+    emits for the next layer (int16 tensor [np, *out.shape]: np = 1 fp16 bits / 3 bf16 bits).
+
+    ``out``: a caller-allocated output tensor (cuda f32, contiguous, the shape ``store`` gives) that the launch writes and
+    the call returns, instead of a fresh one -- a caller that pre-fills it sees which elements the launch stored.
+
+    Environment, read by the library on every call: ``BP_CONV_F16R=1`` makes an ``*_f16`` launch as the engine's ``f16r``
+    plan makes it -- ``res`` is rounded to its fp16 plane and the kernel reads the skip connection from that plane
+    (ConvParams::res16), and with ``planes=True`` the fp32 store is dropped (ConvParams::skip_f32): only the returned plane
+    is written, the fp32 tensor keeps whatever it held (unspecified, unless the caller passed ``out``)."""
     import torch
     _lib.require_gpu()
     w = np.ascontiguousarray(weight.detach().cpu().numpy() if hasattr(weight, "detach") else weight, dtype=np.float32)
@@ -42,13 +50,17 @@ def conv2d_nhwc(x, weight, bias=None, stride: int = 1, pad: int = 0, act: str = 
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     x = x.contiguous()
     if store == "nhwc":
-        out = torch.empty((N, OH, OW, Cout), device=x.device, dtype=torch.float32)
+        shape = (N, OH, OW, Cout)
     elif store == "up2":
-        out = torch.empty((N, 2 * OH, 2 * OW, Cout), device=x.device, dtype=torch.float32)
+        shape = (N, 2 * OH, 2 * OW, Cout)
     elif store == "pixshuf":
-        out = torch.empty((N, 2 * OH, 2 * OW, Cout // 4), device=x.device, dtype=torch.float32)
+        shape = (N, 2 * OH, 2 * OW, Cout // 4)
     else:
-        out = torch.empty((N, Cout, OH, OW), device=x.device, dtype=torch.float32)
+        shape = (N, Cout, OH, OW)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif not (tuple(out.shape) == shape and out.dtype == torch.float32 and out.device == x.device and out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (shape, x.device))
     ms = C.c_float(0)
     pl = None
     if planes:

@@ -2,6 +2,8 @@
 inputs: every kernel size / stride / channel class / epilogue / store mode the two
 networks use, both tile shapes, forced split-K.  Tolerance: fp32 accumulation-order
 noise only (|d| <= 2e-5 * (1 + |ref|) at O(1) activations)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -671,3 +673,265 @@ def test_conv_halo_full_size_layers(cuda):
         _check(y1.cpu().permute(0, 3, 1, 2), ref)
         bd = ops.conv2d_nhwc(x1.to(cuda), w, None, pad=1, tile="bd_b3", splits=splits)
         assert float((y1 - bd).abs().max()) < 2e-5
+
+
+# ---- the fp16-skip-connection launch form of every kernel family, alone.  In the engine's 'f16r' mode a convolution launch differs from a
+# plain fp16 launch in two fields: ConvParams::res16 (the skip connection is read from the fp16 plane of the residual tensor, 2 bytes per
+# element) and ConvParams::skip_f32 (the fp32 store is dropped, only the fp16 plane is written).  BP_CONV_F16R=1 (c_api.cpp bp_conv2d_planes,
+# read on every call) makes exactly that launch: the residual is rounded to its plane by the hook, and with planes=True the fp32 store goes.
+#
+# The oracle needs no tolerance of its own.  R is an fp32 randn residual (almost no element is an fp16 number), R16 = fp16(R) widened.  Per
+# case three launches of the same tile with the same K cut:
+#   A  plain f16, residual R16 (fp32 tensor), planes=True
+#   B  BP_CONV_F16R=1, residual R, no planes          -> res16 alone (the fp32 store is kept)
+#   C  BP_CONV_F16R=1, residual R, planes=True, out= pre-filled with a sentinel bit pattern   -> res16 and skip_f32
+# and  1. B == A bit for bit (the widened fp16 residual is the same fp32 number either way; same tile, K cut and MFMA sequence)
+#      2. C's plane == A's plane bit for bit, and C's fp32 buffer still holds the sentinel in EVERY element
+#      3. B differs from a plain f16 launch given the unrounded R by more than 1e-6 somewhere (the plane was really read)
+#      4. A matches fp64 torch on the fp16-rounded x, w and R16 at the file's accumulation-order bar
+#      5. B and C are bit-reproducible.
+# Point 1 holds for conv_s1 at K = 1 024 too: its LDS plan (s1_plan) differs with the residual's byte width only in `rbuf` and the offsets
+# behind it -- the look-ahead NL is min(nl, 2) with nl >= 2 required, MS / NG / the grid do not depend on it -- and the two K halves' partial
+# sums are added as own + partner's, one commutative fp32 add per element, whatever the plan.  No row is relaxed.
+#
+# NOT covered here (the hook cannot make these launches): res16 together with the SE channel scale (ConvParams::res_scale -- the hook never
+# sets it), and the fp16 form of conv_fused.hip (no single-launch hook).
+F16R_SENTINEL = 0x7FC5A5A5      # a NaN with a payload: no kernel produces these bits
+
+
+def _f16r_sentinel(shape, dev):
+    return torch.full(tuple(shape), F16R_SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
+
+
+@functools.lru_cache(maxsize=4)
+def _f16r_problem(N, H, W, Cin, Cout, k, st, pad, spread, has_res, seed):
+    """Operands of one case (fp16-rounded x and w, bias, R, R16) and the fp64 convolution + bias of them (NCHW), computed once and shared by
+    the tiles, K cuts and add orders of the case.  Nothing here is modified by its users."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, H, W, Cin, generator=g)
+    if spread:
+        x = x * torch.exp(spread * torch.randn(N, H, W, 1, generator=g))
+    x = x.half().float()
+    w = (torch.randn(Cout, Cin, k, k, generator=g) / np.sqrt(Cin * k * k)).half().float()
+    b = torch.randn(Cout, generator=g)
+    OH, OW = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+    R = torch.randn(N, OH, OW, Cout, generator=g) if has_res else None
+    R16 = R.half().float() if has_res else None
+    y64 = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), b.double(), stride=st, padding=pad)
+    return x, w, b, R, R16, y64
+
+
+def _f16r_ref(y64, r_nhwc, act, after, store):
+    """fp64 epilogue on the shared convolution: NHWC, laid out as `store` lays the output out."""
+    r = r_nhwc.double().permute(0, 3, 1, 2) if r_nhwc is not None else None
+    if r is not None and store == "pixshuf":
+        # a PixelShuffle launch runs on pre-permuted filters (engine.cpp add_conv: channel co is the kernel's column (co & 3) Cout / 4 + (co >> 2))
+        # and reads its residual in the kernel's column order
+        co = torch.arange(r.shape[1])
+        r = r[:, (co & 3) * (r.shape[1] // 4) + (co >> 2)]
+    y = y64 + r if (r is not None and not after) else y64
+    y = F.leaky_relu(y, 0.1) if act == "leaky" else (F.relu(y) if act == "relu" else y)
+    if r is not None and after:
+        y = y + r
+    if store == "up2":
+        y = F.interpolate(y, scale_factor=2, mode="nearest")
+    elif store == "pixshuf":
+        y = F.pixel_shuffle(y, 2)
+    return y.permute(0, 2, 3, 1)
+
+
+def _bits_differ(a, b):
+    ne = a.view(torch.int32) != b.view(torch.int32) if a.dtype == torch.float32 else a != b
+    n = int(ne.sum())
+    first = tuple(int(i) for i in ne.nonzero()[0]) if n else None
+    return "%d of %d elements differ, first at %s" % (n, ne.numel(), first)
+
+
+def _f16r_check(cuda, monkeypatch, prob, k, st, pad, tile, splits, orders=(("relu", False), ("leaky", True)), store="nhwc"):
+    x, w, b, R, R16, y64 = prob
+    xd = x.to(cuda)
+    Rd, R16d = (R.to(cuda), R16.to(cuda)) if R is not None else (None, None)
+    if R is not None:
+        assert float((R != R16).float().mean()) > 0.9       # the reference's own premise: R is not made of fp16 numbers
+    for act, after in orders:
+        kw = dict(stride=st, pad=pad, act=act, store=store, res_after_act=after, tile=tile, splits=splits)
+        monkeypatch.delenv("BP_CONV_F16R", raising=False)
+        A, plA = ops.conv2d_nhwc(xd, w, b, res=R16d, planes=True, **kw)
+        U = ops.conv2d_nhwc(xd, w, b, res=Rd, **kw) if R is not None else None
+        monkeypatch.setenv("BP_CONV_F16R", "1")
+        B = [ops.conv2d_nhwc(xd, w, b, res=Rd, **kw) for _ in range(2)] if R is not None else None
+        Cs = []
+        for _ in range(2):
+            buf = _f16r_sentinel(A.shape, cuda)
+            ret, pl = ops.conv2d_nhwc(xd, w, b, res=Rd, planes=True, out=buf, **kw)
+            assert ret is buf
+            Cs.append((buf, pl))
+        monkeypatch.delenv("BP_CONV_F16R")
+        what = "%s %s splits=%d %s add %s the activation" % (tile, store, splits, act, "after" if after else "before")
+        # 4. A against the definition (and the definition tells R from R16)
+        ref = _f16r_ref(y64, R16, act, after, store)
+        scale = max(1.0, float(ref.abs().mean()))
+        _check(A.cpu(), ref.float(), tol=2e-5 * scale)
+        if R is not None:
+            assert float((_f16r_ref(y64, R, act, after, store) - ref).abs().max()) > 1e-6
+            # 1. res16 alone: the same bits as the fp32 tensor that holds the same numbers
+            assert torch.equal(B[0], A), what + ": res16 launch != fp32-residual launch, " + _bits_differ(B[0], A)
+            # 3. ... and really read from the plane
+            assert float((B[0] - U).abs().max()) > 1e-6, what
+            assert torch.equal(B[1], B[0]), what
+        # 2. res16 + skip_f32: the same plane, and not one fp32 element stored
+        assert torch.equal(Cs[0][1], plA), what + ": plane of the f16r launch != plane of the fp32 launch, " + _bits_differ(Cs[0][1], plA)
+        for buf, _ in Cs:
+            touched = buf.view(torch.int32) != F16R_SENTINEL
+            assert not bool(touched.any()), what + ": skip_f32 launch stored %d fp32 elements" % int(touched.sum())
+        # 5.
+        assert torch.equal(Cs[1][1], Cs[0][1]), what
+        # (the plane is the RNE fp16 of the fp32 output: a dropped store loses nothing the next layer reads)
+        assert torch.equal(_planes_to_f32(plA, "f16"), A.half().float()), what
+
+
+# Shared epilogue, staged path (conv_tail.inc -> conv_dev.h epilogue_rows).  A thread owns 4 channels of a row: EP_ROWS = threads / (BN / 4)
+# rows per pass, EP_PASSES = BM / EP_ROWS passes, in EP_SLABS slabs.  The three residual-load forms, by tile (fp16 instances of conv_pl.hip):
+#   pl64       BM  64, BN  64, 256 threads: 4 passes              -> EP_PF: rows requested into registers before the tile is staged (load_res4);
+#                                                                   with K slices the request sits behind the ticket (BP_PREFETCH_RES)
+#   pl128      BM 128, BN 128, 256 threads: 16 passes, one slab   -> GRP: groups of eight passes, 8-byte loads
+#   pl128x64   BM 128, BN  64, 256 threads: 8 passes, one slab    -> GRP (one group)
+#   plh128     as pl128 (3x3 / stride 1 only)                     -> GRP
+#   pl256x128  BM 256, BN 128, 512 threads: 16 passes in 4 slabs of 4 -> neither: one load_res4 per pass, each slab's rows offset by
+#                                                                   sl * SLAB_ROWS * res_ld * 2 bytes
+# NOT reached: the three-blocks-per-CU instances of plh128 (template parameter B3: two slabs of eight passes, i.e. GRP plus the 2-byte slab offset).
+# They are launched for grids of more than 512 tiles of 128x128 only, and no case here is that large.
+F16R_STAGED = [
+    # N, H, W, Cin, Cout, k, stride, pad
+    (1, 13, 13, 64, 128, 1, 1, 0),      # 1x1
+    (2, 13, 13, 128, 256, 3, 1, 1),     # M tail (338 rows)
+    (1, 7, 5, 96, 64, 3, 1, 1),         # odd sizes, M = 35 far below every tile, Cout below the 128-wide tiles
+    (1, 10, 8, 256, 512, 1, 2, 0),      # 1x1 / stride 2
+    (3, 9, 11, 32, 192, 3, 1, 1),       # Cout overhang on the 128-wide tiles (192 = 128 + 64), rows of three images in a tile
+]
+
+
+def _f16r_staged_params():
+    out = []
+    for case in F16R_STAGED:
+        N, H, W, Cin, Cout, k, st, pad = case
+        for tile in PL_TILES + ["plh128"]:
+            if tile == "plh128" and not (k == 3 and st == 1):
+                continue
+            for splits in (1, 3):
+                if splits > 1 and Cin * k * k // 32 < 2 * splits:      # the file's rule: too few K-chunks to split
+                    continue
+                # beyond the file's rule: the halo tile cuts K by whole channel groups (conv_plan.cpp conv_split_plan: nine chunks stay together and
+                # the slice count is clamped to the groups), so with fewer groups than slices the launch IS the splits = 1 one -- dropped as a duplicate
+                # (exactly one case: (3, 9, 11, 32, 192), one group)
+                if splits > 1 and tile == "plh128" and Cin // 32 < splits:
+                    continue
+                out.append(pytest.param(case, tile, splits, id="%dx%dx%dx%d-%d-k%ds%d-%s-s%d" % (N, H, W, Cin, Cout, k, st, tile, splits)))
+    return out
+
+
+@pytest.mark.parametrize("case,tile,splits", _f16r_staged_params())
+def test_conv_f16r_staged_epilogue(cuda, monkeypatch, case, tile, splits):
+    """res16 / skip_f32 in the three residual-load forms of the staged epilogue, one slice and three."""
+    N, H, W, Cin, Cout, k, st, pad = case
+    prob = _f16r_problem(N, H, W, Cin, Cout, k, st, pad, 0.0, True, 3100 + F16R_STAGED.index(case))
+    _f16r_check(cuda, monkeypatch, prob, k, st, pad, tile + "_f16", splits)
+
+
+def test_conv_f16r_hybrid_grid(cuda, monkeypatch):
+    """... and on a hybrid grid (the shape of test_conv_pl_hybrid_grid: 256 whole tiles + 40 cut along K, whose residual rows are read
+    behind the ticket by the slice that reduces)."""
+    monkeypatch.setenv("BP_HYBRID", "1")
+    prob = _f16r_problem(1, 74, 128, 64, 512, 3, 1, 1, 0.0, True, 3150)
+    _f16r_check(cuda, monkeypatch, prob, 3, 1, 1, "pl128_f16", 1)
+    x, w, b, R, R16, _ = prob
+    kw = dict(pad=1, act="leaky", res=R16.to(cuda), res_after_act=True, tile="pl128_f16", splits=1)
+    cut = ops.conv2d_nhwc(x.to(cuda), w, b, **kw)
+    monkeypatch.delenv("BP_HYBRID")
+    assert not torch.equal(cut, ops.conv2d_nhwc(x.to(cuda), w, b, **kw))      # the grid really was the hybrid one
+
+
+# Element-wise fallback (conv_dev.h epilogue_store): the 2-byte scalar residual load, and `keep32` in its three store modes.  The staged path
+# refuses Cout % 4 != 0, and up2 / pixshuf stores when a residual is present.
+F16R_FALLBACK = [
+    # N, H, W, Cin, Cout, store
+    (1, 20, 16, 128, 50, "nhwc"),       # conv_out class: Cout % 4 != 0
+    (1, 7, 5, 64, 50, "nhwc"),          # ... and a residual whose element count is no multiple of 4 (1 750: the hook rounds the last two on the host)
+    (2, 10, 8, 64, 128, "up2"),
+    (2, 10, 8, 64, 128, "pixshuf"),
+]
+
+
+@pytest.mark.parametrize("tile", PL_TILES + ["plh128"])      # (varies fastest: a case's operands and reference are built once)
+@pytest.mark.parametrize("case", F16R_FALLBACK, ids=lambda c: "%dx%dx%dx%d-%d-%s" % c)
+def test_conv_f16r_elementwise_epilogue(cuda, monkeypatch, case, tile):
+    N, H, W, Cin, Cout, store = case
+    prob = _f16r_problem(N, H, W, Cin, Cout, 3, 1, 1, 0.0, True, 3200 + F16R_FALLBACK.index(case))
+    _f16r_check(cuda, monkeypatch, prob, 3, 1, 1, tile + "_f16", 1, store=store)
+
+
+@pytest.mark.parametrize("tile", PL_TILES + ["plh128"])
+@pytest.mark.parametrize("store", ["up2", "pixshuf"])
+def test_conv_f16r_staged_store_modes_drop_f32(cuda, monkeypatch, store, tile):
+    """Without a residual the up2 and pixshuf stores go through the staged epilogue (Up2Rows: four stores per pass; PixShufRows): skip_f32
+    there -- the same planes, no fp32 element stored."""
+    prob = _f16r_problem(2, 10, 8, 64, 128, 3, 1, 1, 0.0, False, 3300)
+    _f16r_check(cuda, monkeypatch, prob, 3, 1, 1, tile + "_f16", 1, store=store)
+
+
+# conv_p3.hip, RES == 1: the skip connection as 16-byte loads of the fp16 plane (load_res16: 8 channels of the lane's pixel, handed to their
+# lanes by v_permlane32_swap), requested inside the tile's last channel group (rr16; two blocks per CU, what the engine plans).  A is the SAME
+# tile with the fp32 residual (RES == 2).
+# The grid is 8 * min(ceil(T / 8), 32 * BPC) blocks for T tiles (launch_conv_p3): a block walks a SECOND tile -- the persistent loop: rr16 requested
+# with this tile's m0 / n0 after tile_setup has rebuilt the next tile's, the m0 / n0 hand-over behind the epilogue -- only when T > 512 (BPC = 2) or
+# T > 768 (BPC = 3).  Only the last row of F16R_P3 and the last row of the 1x1 test are that large.
+F16R_P3 = [
+    # N, H, W, Cin, Cout       (one per width class)
+    (28, 13, 13, 64, 128),      # W = 13, an M tail of 124 rows
+    (14, 20, 16, 64, 256),      # W = 16
+    (7, 26, 26, 64, 256),       # W = 26
+    (4, 40, 32, 64, 136),       # W = 32, Cout overhang (CoutPad 192: the second N tile's waves 1-3 own no channel)
+    (2, 52, 52, 32, 128),       # W = 52, one channel group (the request sits in the tile's only group)
+    (1, 104, 104, 64, 128),     # W = 104
+    (28, 26, 26, 32, 128),      # 148 tiles on 152 blocks: ONE tile per block, the XCD ranges of 18 and 19 tiles unevenly filled
+    (28, 52, 52, 32, 256),      # 1 184 tiles on 512 blocks: two and three tiles per block (the persistent loop with the fp16 residual)
+]
+
+
+@pytest.mark.parametrize("shape", F16R_P3, ids=lambda c: "%dx%dx%dx%d-%d" % c)
+def test_conv_f16r_p3_3x3(cuda, monkeypatch, shape):
+    N, H, W, Cin, Cout = shape
+    prob = _f16r_problem(N, H, W, Cin, Cout, 3, 1, 1, 0.5, True, 3400 + F16R_P3.index(shape))
+    _f16r_check(cuda, monkeypatch, prob, 3, 1, 1, "p3_f16", 1)
+
+
+@pytest.mark.parametrize("shape", [F16R_P3[0], F16R_P3[3], F16R_P3[7]], ids=lambda c: "%dx%dx%dx%d-%d" % c)
+def test_conv_f16r_p3_3x3_requests_inside_the_epilogue(cuda, monkeypatch, shape):
+    """BP_P3_BPC=3 (read per call): the three-blocks-per-CU instance, whose skip-connection rows are requested inside the epilogue, one pixel
+    sub-tile ahead (rl) -- the other register staging of RES == 1.  The last shape is 1 184 tiles on 768 blocks: one and two tiles per block, so rl
+    is also requested in an epilogue that the next tile's loads overlap."""
+    N, H, W, Cin, Cout = shape
+    monkeypatch.setenv("BP_P3_BPC", "3")
+    prob = _f16r_problem(N, H, W, Cin, Cout, 3, 1, 1, 0.5, True, 3400 + F16R_P3.index(shape))
+    _f16r_check(cuda, monkeypatch, prob, 3, 1, 1, "p3_f16", 1)
+
+
+@pytest.mark.parametrize("shape", [(28, 13, 13, 1024, 512), (9, 26, 26, 256, 136), (28, 13, 13, 256, 2048)], ids=lambda c: "%dx%dx%dx%d-%d" % c)
+def test_conv_f16r_p3_1x1_form(cuda, monkeypatch, shape):
+    """The 1x1 form of conv_p3 (four taps per group: the request sits at tap 1 of the last group): eight groups with an M tail (148 tiles, one per
+    block), the shortest K it takes with a Cout overhang (48 tiles), and 592 tiles on 512 blocks -- ten blocks of every XCD walk a second tile (in
+    this form the next tile's geometry is rebuilt one group BEFORE the group that requests the residual)."""
+    N, H, W, Cin, Cout = shape
+    prob = _f16r_problem(N, H, W, Cin, Cout, 1, 1, 0, 0.5, True, 3500 + Cin + Cout)
+    _f16r_check(cuda, monkeypatch, prob, 1, 1, 0, "p3_f16", 1)
+
+
+@pytest.mark.parametrize("shape", S1_SHAPES, ids=lambda c: "%dx%dx%dx%d-%d-s%d" % c[:6])
+def test_conv_f16r_s1(cuda, monkeypatch, shape):
+    """conv_s1.hip: the skip-connection tile through LDS as [32 rows][GW x 2 B] in 1 KB pieces (GW = 128 columns: 4 rows per piece; K = 1 024,
+    GW = 64: 8 rows per piece), with the LDS plan of res_bytes == 2.  Every row of S1_SHAPES with a residual, both add orders: every K class,
+    stride 2, the Cout overhang, the M tail.  K = 1 024 is held to bit equality too (see the section's head)."""
+    N, H, W, Cin, Cout, st = shape[:6]
+    monkeypatch.setenv("BP_S1_K512", "1")
+    prob = _f16r_problem(N, H, W, Cin, Cout, 1, st, 0, 0.5, True, 3600 + S1_SHAPES.index(shape))
+    _f16r_check(cuda, monkeypatch, prob, 1, st, 0, "s1_f16", 1)
