@@ -129,6 +129,125 @@ static int default_precision() {
     throw bp::Error("BP_PRECISION must be f32, bf16x3, f16 or f16r, not '" + v + "'");
 }
 
+// ------------------------------------------------------------------ what bp_yolo_* and bp_kpd_* do alike
+// One body per operation over either handle type E; the exports forward to it.  with_net runs f(net) and turns an exception
+// into -1 and bp_last_error(); a null handle is answered here, before any device call: -1 and "null argument".
+template <class E, class F> static int with_net(const E* e, F f) {
+    BP_TRY
+    if (!e) throw bp::Error("null argument");
+    return f(*e->net);
+    BP_CATCH
+}
+
+// A new handle around the net `make` builds on `device`: a creator's net takes the default precision, a clone the
+// precision and fusion flag of `like`.
+template <class E, class Make> static void adopt(E** out, int device, const bp::Net* like, Make make) {
+    BP_HIP(hipSetDevice(device));
+    std::unique_ptr<E> e(new E);
+    e->device = device;
+    e->net.reset(make());
+    const int prec = like ? like->precision_id() : default_precision();
+    if (prec != bp::PREC_F32) e->net->set_precision(prec);
+    if (like) e->net->set_fusion(like->fusion());
+    *out = e.release();
+}
+
+template <class E> static int engine_clone(const E* e, E** out) {
+    return with_net(e, [&](const bp::Net& src) {
+        BP_CHECK(out, "null argument");
+        adopt(out, e->device, &src, [&] { return e->net->clone(); });
+        return 0;
+    });
+}
+template <class E> static int engine_tap_count(const E* e) {
+    return with_net(e, [](const bp::Net& n) { return n.tap_count(); });
+}
+template <class E> static int engine_tap_info(const E* e, int i, char* name, int cap, int* C, int* H, int* W) {
+    return with_net(e, [&](const bp::Net& n) {
+        if (!C || !H || !W) throw bp::Error("null argument");
+        if (i < 0 || i >= n.tap_count()) throw bp::Error("tap index");
+        if (name && cap > 0) std::snprintf(name, cap, "%s", n.tap_name(i));
+        n.tap_shape(i, C, H, W);
+        return 0;
+    });
+}
+template <class E> static int engine_tap_copy(E* e, int i, int batch, float* d_out, void* stream) {
+    return with_net(e, [&](bp::Net& n) {
+        BP_CHECK(d_out, "null argument");
+        n.tap_copy(i, batch, d_out, (hipStream_t)stream);
+        return 0;
+    });
+}
+template <class E> static int engine_set_policy(E* e, int t, int mc, int ms, int ft) {
+    return with_net(e, [&](bp::Net& n) {
+        BP_CHECK(t >= 1 && mc >= 1 && ms >= 1 && ft >= -1 && ft <= bp::TILE_LAST, "policy values out of range");
+        n.set_splitk_policy(t, mc);
+        n.set_max_splits(ms);
+        n.set_force_tile(ft);
+        return 0;
+    });
+}
+template <class E> static int engine_set_precision(E* e, int prec) {
+    return with_net(e, [&](bp::Net& n) {
+        BP_HIP(hipSetDevice(e->device));
+        n.set_precision(prec);
+        return 0;
+    });
+}
+template <class E> static int engine_op_stats(const E* e, double* flops, double* bytes, int cap) {
+    return with_net(e, [&](const bp::Net& n) {
+        const auto& ops = n.ops();
+        for (int i = 0; i < (int)ops.size() && i < cap; ++i) {
+            if (flops) flops[i] = ops[i].flops;
+            if (bytes) bytes[i] = ops[i].bytes;
+        }
+        return (int)ops.size();
+    });
+}
+template <class E> static int engine_profile(E* e, int batch, int iters, float* ms, int* info, int cap, void* stream) {
+    return with_net(e, [&](bp::Net& n) { return n.profile(batch, iters, ms, info, cap, (hipStream_t)stream); });
+}
+template <class E> static int engine_set_prefetch(E* e, int on) {
+    return with_net(e, [&](bp::Net& n) { n.set_prefetch(on != 0); return 0; });
+}
+// conv -> conv fusion of residual / bottleneck blocks (conv_fused.hip): on by default
+template <class E> static int engine_set_fusion(E* e, int on) {
+    return with_net(e, [&](bp::Net& n) { n.set_fusion(on != 0); return 0; });
+}
+// *launches = fused groups that run as ONE launch at `batch`
+template <class E> static int engine_fused_launches(E* e, int batch, int* launches) {
+    return with_net(e, [&](bp::Net& n) {
+        BP_CHECK(launches && batch >= 1 && batch <= n.max_batch(), "arguments");
+        BP_HIP(hipSetDevice(e->device));
+        *launches = n.fused_launches(batch);
+        return 0;
+    });
+}
+template <class E> static int engine_xcd_errors(E* e, int* count, void* stream) {
+    return with_net(e, [&](bp::Net& n) {
+        BP_CHECK(count, "null argument");
+        BP_HIP(hipSetDevice(e->device));
+        *count = n.take_xcd_errors((hipStream_t)stream);
+        return 0;
+    });
+}
+template <class E> static int engine_set_stamps(E* e, unsigned long long* d_buf, int slots) {
+    return with_net(e, [&](bp::Net& n) { n.set_stamps(d_buf, slots); return 0; });
+}
+template <class E> static int engine_op_name(const E* e, int i, char* out, int cap) {
+    return with_net(e, [&](const bp::Net& net) {
+        if (i < 0 || i >= (int)net.ops().size() || !out || cap <= 0) return -1;
+        const bp::Op& op = net.ops()[i];
+        if (op.type == bp::OP_CONV)   // "<name> k<ksize> <OH>x<OW> <Cin>-><Cout> s<stride>"
+            std::snprintf(out, (size_t)cap, "%s k%d %dx%d %d->%d s%d", net.op_name(i), op.conv.ksize, op.conv.OH, op.conv.OW,
+                          op.conv.Cin, op.conv.Cout, op.conv.stride);
+        else
+            std::snprintf(out, (size_t)cap, "%s", net.op_name(i));
+        return op.type == bp::OP_CONV ? 1 : 0;
+    });
+}
+template <class E> static size_t engine_device_bytes(const E* e) { return e ? e->net->device_bytes() : 0; }
+
 extern "C" {
 
 const char* bp_last_error(void) { return g_err.c_str(); }
@@ -190,12 +309,7 @@ int bp_yolo_create_from_memory(const char* cfg_text, const float* stream, size_t
                                int device, bp_yolo** out) {
     BP_TRY
     BP_CHECK(cfg_text && stream && out, "null argument");
-    BP_HIP(hipSetDevice(device));
-    std::unique_ptr<bp_yolo> y(new bp_yolo);
-    y->device = device;
-    y->net.reset(new bp::YoloNet(cfg_text, stream, n_floats, reso, max_batch));
-    if (default_precision() != bp::PREC_F32) y->net->set_precision(default_precision());
-    *out = y.release();
+    adopt(out, device, nullptr, [&] { return new bp::YoloNet(cfg_text, stream, n_floats, reso, max_batch); });
     return 0;
     BP_CATCH
 }
@@ -233,29 +347,13 @@ int bp_yolo_create_darknet(const char* cfg_path, const char* weights_path, int r
     BP_CHECK(cfg_path && weights_path && out, "null argument");
     const std::string cfg = read_text(cfg_path);
     const std::vector<float> stream = read_weights_file(weights_path);
-    BP_HIP(hipSetDevice(device));
-    std::unique_ptr<bp_yolo> y(new bp_yolo);
-    y->device = device;
-    y->net.reset(new bp::YoloNet(cfg, stream.data(), stream.size(), reso, max_batch, nullptr, /*darknet_bn=*/true));
-    if (default_precision() != bp::PREC_F32) y->net->set_precision(default_precision());
-    *out = y.release();
+    adopt(out, device, nullptr,
+          [&] { return new bp::YoloNet(cfg, stream.data(), stream.size(), reso, max_batch, nullptr, /*darknet_bn=*/true); });
     return 0;
     BP_CATCH
 }
 
-int bp_yolo_clone(const bp_yolo* y, bp_yolo** out) {
-    BP_TRY
-    BP_CHECK(y && out, "null argument");
-    BP_HIP(hipSetDevice(y->device));
-    std::unique_ptr<bp_yolo> c(new bp_yolo);
-    c->device = y->device;
-    c->net.reset(y->net->clone());
-    if (y->net->precision() != bp::PREC_F32) c->net->set_precision(y->net->precision_id());
-    c->net->set_fusion(y->net->fusion());
-    *out = c.release();
-    return 0;
-    BP_CATCH
-}
+int bp_yolo_clone(const bp_yolo* y, bp_yolo** out) { return engine_clone(y, out); }
 void bp_yolo_destroy(bp_yolo* y) { delete y; }
 int bp_yolo_rows(const bp_yolo* y) { return y ? y->net->rows() : -1; }
 int bp_yolo_attrs(const bp_yolo* y) { return y ? y->net->attrs() : -1; }
@@ -317,51 +415,23 @@ int bp_yolo_forward_select_nms(bp_yolo* y, const float* d_img, int batch, float 
     BP_CATCH
 }
 
-static int tap_info(const bp::Net& n, int i, char* name, int cap, int* C, int* H, int* W) {
-    if (i < 0 || i >= n.tap_count()) { g_err = "tap index"; return -1; }
-    if (name && cap > 0) std::snprintf(name, cap, "%s", n.tap_name(i));
-    n.tap_shape(i, C, H, W);
-    return 0;
-}
-int bp_yolo_tap_count(const bp_yolo* y) { return y ? y->net->tap_count() : -1; }
+int bp_yolo_tap_count(const bp_yolo* y) { return engine_tap_count(y); }
 int bp_yolo_tap_info(const bp_yolo* y, int i, char* name, int cap, int* C, int* H, int* W) {
-    if (!y || !C || !H || !W) { g_err = "null argument"; return -1; }
-    return tap_info(*y->net, i, name, cap, C, H, W);
+    return engine_tap_info(y, i, name, cap, C, H, W);
 }
 int bp_yolo_tap_copy(bp_yolo* y, int i, int batch, float* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(y && d_out, "null argument");
-    y->net->tap_copy(i, batch, d_out, (hipStream_t)stream);
-    return 0;
-    BP_CATCH
+    return engine_tap_copy(y, i, batch, d_out, stream);
 }
 
 // ------------------------------------------------------------------ key-point detector
 int bp_kpd_create(const float* stream, size_t n_floats, int n_classes, int max_batch, int device, bp_kpd** out) {
     BP_TRY
     BP_CHECK(stream && out, "null argument");
-    BP_HIP(hipSetDevice(device));
-    std::unique_ptr<bp_kpd> k(new bp_kpd);
-    k->device = device;
-    k->net.reset(new bp::KpdNet(stream, n_floats, n_classes, max_batch));
-    if (default_precision() != bp::PREC_F32) k->net->set_precision(default_precision());
-    *out = k.release();
+    adopt(out, device, nullptr, [&] { return new bp::KpdNet(stream, n_floats, n_classes, max_batch); });
     return 0;
     BP_CATCH
 }
-int bp_kpd_clone(const bp_kpd* k, bp_kpd** out) {
-    BP_TRY
-    BP_CHECK(k && out, "null argument");
-    BP_HIP(hipSetDevice(k->device));
-    std::unique_ptr<bp_kpd> c(new bp_kpd);
-    c->device = k->device;
-    c->net.reset(k->net->clone());
-    if (k->net->precision() != bp::PREC_F32) c->net->set_precision(k->net->precision_id());
-    c->net->set_fusion(k->net->fusion());
-    *out = c.release();
-    return 0;
-    BP_CATCH
-}
+int bp_kpd_clone(const bp_kpd* k, bp_kpd** out) { return engine_clone(k, out); }
 void bp_kpd_destroy(bp_kpd* k) { delete k; }
 int bp_kpd_forward(bp_kpd* k, const float* d_inps, int batch, float* d_hm, void* stream) {
     BP_TRY
@@ -407,75 +477,40 @@ int bp_kpd_launch_count(bp_kpd* k, int batch) {
     return (int)n;
     BP_CATCH
 }
-int bp_kpd_tap_count(const bp_kpd* k) { return k ? k->net->tap_count() : -1; }
+int bp_kpd_tap_count(const bp_kpd* k) { return engine_tap_count(k); }
 int bp_kpd_tap_info(const bp_kpd* k, int i, char* name, int cap, int* C, int* H, int* W) {
-    if (!k || !C || !H || !W) { g_err = "null argument"; return -1; }
-    return tap_info(*k->net, i, name, cap, C, H, W);
+    return engine_tap_info(k, i, name, cap, C, H, W);
 }
 int bp_kpd_tap_copy(bp_kpd* k, int i, int batch, float* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(k && d_out, "null argument");
-    k->net->tap_copy(i, batch, d_out, (hipStream_t)stream);
-    return 0;
-    BP_CATCH
+    return engine_tap_copy(k, i, batch, d_out, stream);
 }
 
-int bp_yolo_set_policy(bp_yolo* y, int t, int mc, int ms, int ft) {
-    BP_TRY
-    BP_CHECK(y, "null argument");
-    BP_CHECK(t >= 1 && mc >= 1 && ms >= 1 && ft >= -1 && ft <= bp::TILE_LAST, "policy values out of range");
-    y->net->set_splitk_policy(t, mc);
-    y->net->set_max_splits(ms);
-    y->net->set_force_tile(ft);
-    return 0;
-    BP_CATCH
-}
-int bp_yolo_set_precision(bp_yolo* y, int prec) {
-    BP_TRY
-    BP_CHECK(y, "null argument");
-    BP_HIP(hipSetDevice(y->device));
-    y->net->set_precision(prec);
-    return 0;
-    BP_CATCH
-}
-int bp_kpd_set_precision(bp_kpd* k, int prec) {
-    BP_TRY
-    BP_CHECK(k, "null argument");
-    BP_HIP(hipSetDevice(k->device));
-    k->net->set_precision(prec);
-    return 0;
-    BP_CATCH
-}
-int bp_kpd_set_policy(bp_kpd* k, int t, int mc, int ms, int ft) {
-    BP_TRY
-    BP_CHECK(k, "null argument");
-    BP_CHECK(t >= 1 && mc >= 1 && ms >= 1 && ft >= -1 && ft <= bp::TILE_LAST, "policy values out of range");
-    k->net->set_splitk_policy(t, mc);
-    k->net->set_max_splits(ms);
-    k->net->set_force_tile(ft);
-    return 0;
-    BP_CATCH
-}
-static int op_stats(const bp::Net& n, double* flops, double* bytes, int cap) {
-    const auto& ops = n.ops();
-    for (int i = 0; i < (int)ops.size() && i < cap; ++i) {
-        if (flops) flops[i] = ops[i].flops;
-        if (bytes) bytes[i] = ops[i].bytes;
-    }
-    return (int)ops.size();
-}
-int bp_yolo_op_stats(const bp_yolo* y, double* flops, double* bytes, int cap) { return op_stats(*y->net, flops, bytes, cap); }
-int bp_kpd_op_stats(const bp_kpd* k, double* flops, double* bytes, int cap) { return op_stats(*k->net, flops, bytes, cap); }
+int bp_yolo_set_policy(bp_yolo* y, int t, int mc, int ms, int ft) { return engine_set_policy(y, t, mc, ms, ft); }
+int bp_kpd_set_policy(bp_kpd* k, int t, int mc, int ms, int ft) { return engine_set_policy(k, t, mc, ms, ft); }
+int bp_yolo_set_precision(bp_yolo* y, int prec) { return engine_set_precision(y, prec); }
+int bp_kpd_set_precision(bp_kpd* k, int prec) { return engine_set_precision(k, prec); }
+int bp_yolo_op_stats(const bp_yolo* y, double* flops, double* bytes, int cap) { return engine_op_stats(y, flops, bytes, cap); }
+int bp_kpd_op_stats(const bp_kpd* k, double* flops, double* bytes, int cap) { return engine_op_stats(k, flops, bytes, cap); }
 int bp_yolo_profile(bp_yolo* y, int batch, int iters, float* ms, int* info, int cap, void* stream) {
-    BP_TRY
-    return y->net->profile(batch, iters, ms, info, cap, (hipStream_t)stream);
-    BP_CATCH
+    return engine_profile(y, batch, iters, ms, info, cap, stream);
 }
 int bp_kpd_profile(bp_kpd* k, int batch, int iters, float* ms, int* info, int cap, void* stream) {
-    BP_TRY
-    return k->net->profile(batch, iters, ms, info, cap, (hipStream_t)stream);
-    BP_CATCH
+    return engine_profile(k, batch, iters, ms, info, cap, stream);
 }
+int bp_yolo_set_prefetch(bp_yolo* y, int on) { return engine_set_prefetch(y, on); }
+int bp_kpd_set_prefetch(bp_kpd* k, int on) { return engine_set_prefetch(k, on); }
+int bp_yolo_set_fusion(bp_yolo* y, int on) { return engine_set_fusion(y, on); }
+int bp_kpd_set_fusion(bp_kpd* k, int on) { return engine_set_fusion(k, on); }
+int bp_yolo_fused_launches(bp_yolo* y, int batch, int* launches) { return engine_fused_launches(y, batch, launches); }
+int bp_kpd_fused_launches(bp_kpd* k, int batch, int* launches) { return engine_fused_launches(k, batch, launches); }
+int bp_yolo_xcd_errors(bp_yolo* y, int* count, void* stream) { return engine_xcd_errors(y, count, stream); }
+int bp_kpd_xcd_errors(bp_kpd* k, int* count, void* stream) { return engine_xcd_errors(k, count, stream); }
+int bp_yolo_set_stamps(bp_yolo* y, unsigned long long* d_buf, int slots) { return engine_set_stamps(y, d_buf, slots); }
+int bp_kpd_set_stamps(bp_kpd* k, unsigned long long* d_buf, int slots) { return engine_set_stamps(k, d_buf, slots); }
+int bp_yolo_op_name(const bp_yolo* y, int i, char* out, int cap) { return engine_op_name(y, i, out, cap); }
+int bp_kpd_op_name(const bp_kpd* k, int i, char* out, int cap) { return engine_op_name(k, i, out, cap); }
+size_t bp_yolo_device_bytes(const bp_yolo* y) { return engine_device_bytes(y); }
+size_t bp_kpd_device_bytes(const bp_kpd* k) { return engine_device_bytes(k); }
 int bp_calibrate_ticks(long long ticks, float* ms, void* stream) {
     BP_TRY
     BP_CHECK(ms && ticks > 0, "arguments");
@@ -494,59 +529,6 @@ int bp_calibrate_ticks(long long ticks, float* ms, void* stream) {
     return 0;
     BP_CATCH
 }
-int bp_yolo_set_prefetch(bp_yolo* y, int on) { y->net->set_prefetch(on != 0); return 0; }
-int bp_kpd_set_prefetch(bp_kpd* k, int on) { k->net->set_prefetch(on != 0); return 0; }
-// conv -> conv fusion of residual / bottleneck blocks (conv_fused.hip): on by default; *launches = groups that run as ONE launch at `batch`
-int bp_yolo_set_fusion(bp_yolo* y, int on) { y->net->set_fusion(on != 0); return 0; }
-int bp_kpd_set_fusion(bp_kpd* k, int on) { k->net->set_fusion(on != 0); return 0; }
-int bp_yolo_fused_launches(bp_yolo* y, int batch, int* launches) {
-    BP_TRY
-    BP_CHECK(y && launches && batch >= 1 && batch <= y->net->max_batch(), "arguments");
-    BP_HIP(hipSetDevice(y->device));
-    *launches = y->net->fused_launches(batch);
-    return 0;
-    BP_CATCH
-}
-int bp_kpd_fused_launches(bp_kpd* k, int batch, int* launches) {
-    BP_TRY
-    BP_CHECK(k && launches && batch >= 1 && batch <= k->net->max_batch(), "arguments");
-    BP_HIP(hipSetDevice(k->device));
-    *launches = k->net->fused_launches(batch);
-    return 0;
-    BP_CATCH
-}
-int bp_yolo_xcd_errors(bp_yolo* y, int* count, void* stream) {
-    BP_TRY
-    BP_CHECK(y && count, "null argument");
-    BP_HIP(hipSetDevice(y->device));
-    *count = y->net->take_xcd_errors((hipStream_t)stream);
-    return 0;
-    BP_CATCH
-}
-int bp_kpd_xcd_errors(bp_kpd* k, int* count, void* stream) {
-    BP_TRY
-    BP_CHECK(k && count, "null argument");
-    BP_HIP(hipSetDevice(k->device));
-    *count = k->net->take_xcd_errors((hipStream_t)stream);
-    return 0;
-    BP_CATCH
-}
-int bp_yolo_set_stamps(bp_yolo* y, unsigned long long* d_buf, int slots) { y->net->set_stamps(d_buf, slots); return 0; }
-int bp_kpd_set_stamps(bp_kpd* k, unsigned long long* d_buf, int slots) { k->net->set_stamps(d_buf, slots); return 0; }
-static int op_name(const bp::Net& net, int i, char* out, int cap) {
-    if (i < 0 || i >= (int)net.ops().size() || !out || cap <= 0) return -1;
-    const bp::Op& op = net.ops()[i];
-    if (op.type == bp::OP_CONV)   // "<name> k<ksize> <OH>x<OW> <Cin>-><Cout> s<stride>"
-        std::snprintf(out, (size_t)cap, "%s k%d %dx%d %d->%d s%d", net.op_name(i), op.conv.ksize, op.conv.OH, op.conv.OW, op.conv.Cin,
-                      op.conv.Cout, op.conv.stride);
-    else
-        std::snprintf(out, (size_t)cap, "%s", net.op_name(i));
-    return op.type == bp::OP_CONV ? 1 : 0;
-}
-int bp_yolo_op_name(const bp_yolo* y, int i, char* out, int cap) { return op_name(*y->net, i, out, cap); }
-int bp_kpd_op_name(const bp_kpd* k, int i, char* out, int cap) { return op_name(*k->net, i, out, cap); }
-size_t bp_yolo_device_bytes(const bp_yolo* y) { return y->net->device_bytes(); }
-size_t bp_kpd_device_bytes(const bp_kpd* k) { return k->net->device_bytes(); }
 
 // ------------------------------------------------------------------ stand-alone stages
 int bp_crop(const uint8_t* d_frames, int batch, int H, int W, const float* d_sel, int reso, const float* d_boxes,

@@ -20,6 +20,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._engine import _Engine
 from .cfg import parse_cfg, parse_cfg_text, yolov3_single_cfg_text
 from .weights import darknet_stream_size, read_darknet_weights
 
@@ -52,7 +53,9 @@ def check_class_ids(class_ids, n_classes: int, num_classes: int = 80):
     return ids
 
 
-class Darknet:
+class Darknet(_Engine):
+    _C = "bp_yolo"
+
     def __init__(self, cfgfile: str, reso: int = 416, max_batch: int = 1, device: Optional[int] = None):
         self.blocks = parse_cfg(cfgfile)
         self.reso = int(reso)
@@ -86,16 +89,6 @@ class Darknet:
         self._destroy()
         return self
 
-    def eval(self):
-        self.training = False
-        return self
-
-    def cuda(self, device=None):
-        if device is not None:
-            self._device = int(device) if not hasattr(device, "index") else device.index
-        self._ensure()
-        return self
-
     def to(self, device):
         return self.cuda(device)
 
@@ -121,30 +114,11 @@ class Darknet:
         self.rows = _lib.lib().bp_yolo_rows(h)
         self.attrs = _lib.lib().bp_yolo_attrs(h)
 
-    def _destroy(self):
-        if self._h is not None:
-            _lib.lib().bp_yolo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        self._ensure()
-        return self._h
-
     def _prep(self, x):
-        import torch
         self._ensure()
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.reso or x.shape[3] != self.reso:
             raise ValueError("expected [B,3,%d,%d], got %s" % (self.reso, self.reso, tuple(x.shape)))
-        if x.shape[0] > self.max_batch:
-            raise ValueError("batch %d > max_batch %d" % (x.shape[0], self.max_batch))
-        return x.to(device="cuda:%d" % self._device, dtype=torch.float32).contiguous()
+        return self._on_device(x)
 
     def forward(self, x):
         """f32[B,3,R,R] (RGB 0..1) -> f32[B, rows, 5+C] in DetectionLayer row order."""
@@ -204,113 +178,6 @@ class Darknet:
                                                          int(class_id), float(nms_conf), Cn, pred.data_ptr() if want_pred else None,
                                                          sel.data_ptr(), counts.data_ptr(), _lib.current_stream()))
         return (sel, counts, pred) if want_pred else (sel, counts)
-
-    # ---- inspection hooks (tests)
-    def taps(self):
-        self._ensure()
-        L = _lib.lib()
-        out = []
-        name = C.create_string_buffer(64)
-        c, h, w = C.c_int(), C.c_int(), C.c_int()
-        for i in range(L.bp_yolo_tap_count(self._h)):
-            _lib.check(L.bp_yolo_tap_info(self._h, i, name, 64, C.byref(c), C.byref(h), C.byref(w)))
-            out.append((name.value.decode(), c.value, h.value, w.value))
-        return out
-
-    def tap(self, i: int, batch: int = 1):
-        import torch
-        name, c, h, w = self.taps()[i]
-        t = torch.empty((batch, c, h, w), device="cuda:%d" % self._device, dtype=torch.float32)
-        _lib.check(_lib.lib().bp_yolo_tap_copy(self._h, i, batch, t.data_ptr(), _lib.current_stream()))
-        return t
-
-    def set_policy(self, sk_target_blocks: int = 512, sk_min_chunks: int = 4, sk_max_splits: int = 8,
-                   force_tile: int = -1):
-        self._ensure()
-        _lib.check(_lib.lib().bp_yolo_set_policy(self._h, sk_target_blocks, sk_min_chunks, sk_max_splits, force_tile))
-
-    def set_precision(self, precision: str = "bf16x3"):
-        """'f32' (fp32 MFMA), 'bf16x3' (fp32-accurate: exact 3-way bf16 operand split on the bf16 MFMA) or 'f16'
-        (fp16 operands, fp32 accumulate: carries fp16 rounding); 'f16r' = 'f16' with fp16 skip connections (residuals read from the fp16
-        operand planes, fp32 copies of tensors that only convolutions and residual adds read are dropped)."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_yolo_set_precision(self._h, {"f32": 0, "f16": 1, "bf16x3": 2, "f16r": 3}[precision]))
-        self._precision = precision
-        return self
-
-    def clone(self):
-        """Second engine over the same device filters (own activations): one per concurrent stream."""
-        import copy
-        self._ensure()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().bp_yolo_clone(self._h, C.byref(h)))   # first: a failed clone must not leave a copy owning self._h
-        other = copy.copy(self)
-        other._h = h
-        return other
-
-    def profile(self, batch: int = 1, iters: int = 10):
-        """Eager pass with hipEvent pairs per op -> (ms[n_ops], info[n_ops,4] = is_conv, tile, vec, splits)."""
-        self._ensure()
-        L = _lib.lib()
-        n = L.bp_yolo_profile(self._h, batch, iters, None, None, 0, _lib.current_stream())
-        ms = (C.c_float * n)()
-        info = (C.c_int * (4 * n))()
-        rc = L.bp_yolo_profile(self._h, batch, iters, ms, info, n, _lib.current_stream())
-        if rc < 0:
-            _lib.check(rc)
-        return np.array(ms, dtype=np.float64), np.array(info, dtype=np.int64).reshape(n, 4)
-
-    def set_prefetch(self, on: bool = True):
-        """Lone-frame latency mode (include/betapose_hip.h bp_*_set_prefetch): split-K hand-off inside one XCD's L2 +
-        prefetch of the next layer's filters.  Bit-identical results; pays with one frame at a time, costs with several in flight."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_yolo_set_prefetch(self._h, int(bool(on))))
-        self._latency_mode = bool(on)
-
-    def set_fusion(self, on: bool = True):
-        """Conv -> conv fusion of whole residual / bottleneck blocks (include/betapose_hip.h bp_*_set_fusion; default on)."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_yolo_set_fusion(self._h, int(bool(on))))
-
-    def fused_launches(self, batch: int = 1) -> int:
-        self._ensure()
-        n = C.c_int(0)
-        _lib.check(_lib.lib().bp_yolo_fused_launches(self._h, int(batch), C.byref(n)))
-        return int(n.value)
-
-    def xcd_errors(self) -> int:
-        """Non-zero when a launch of the latency mode found a K slice on the wrong XCD since the last call (include/betapose_hip.h
-        bp_*_xcd_errors): its tile was not stored, the frame must be run again with the mode off.  Waits for the current stream."""
-        if not getattr(self, "_latency_mode", False) or self._h is None:
-            return 0
-        n = C.c_int(0)
-        _lib.check(_lib.lib().bp_yolo_xcd_errors(self._h, C.byref(n), _lib.current_stream()))
-        return int(n.value)
-
-    def set_stamps(self, buf=None, slots: int = 0):
-        """In-situ conv timing (include/betapose_hip.h bp_*_set_stamps): ``buf`` a cuda int64 tensor of
-        n_convs * slots * 8 elements, or None to switch it off."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_yolo_set_stamps(self._h, buf.data_ptr() if buf is not None else None, int(slots)))
-
-    def op_names(self):
-        """[(layer name, is_convolution)] in op order."""
-        self._ensure()
-        n = _lib.lib().bp_yolo_op_stats(self._h, None, None, 0)
-        name = C.create_string_buffer(96)
-        out = []
-        for i in range(n):
-            is_conv = _lib.lib().bp_yolo_op_name(self._h, i, name, 96)
-            out.append((name.value.decode(), bool(is_conv == 1)))
-        return out
-
-    def op_stats(self):
-        self._ensure()
-        n = _lib.lib().bp_yolo_op_stats(self._h, None, None, 0)
-        f = (C.c_double * n)()
-        b = (C.c_double * n)()
-        _lib.lib().bp_yolo_op_stats(self._h, f, b, n)
-        return np.array(f), np.array(b)
 
 
 def sel_to_dets(sel) -> "object":

@@ -18,6 +18,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _lib
+from ._engine import _Engine
 from .weights import fastpose_stream_from_state_dict, fastpose_stream_size, load_kpd_pkl
 
 # main_fast_inference.py:29-32
@@ -26,8 +27,9 @@ ALLPATHS = ['NULL', 'seq1_model', 'seq2_model', 'NULL', 'seq4_model', 'seq5_mode
             'seq14_model', 'seq15_model']
 
 
-class FastPoseHIP:
+class FastPoseHIP(_Engine):
     """Engine wrapper.  ``state_dict`` values may be numpy arrays or torch tensors."""
+    _C = "bp_kpd"
 
     def __init__(self, state_dict: Dict[str, object], n_classes: int = 50, max_batch: int = 1,
                  device: Optional[int] = None):
@@ -60,40 +62,11 @@ class FastPoseHIP:
                                             self.max_batch, self._device, C.byref(h)))
         self._h = h
 
-    def _destroy(self):
-        if self._h is not None:
-            _lib.lib().bp_kpd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        self._ensure()
-        return self._h
-
-    def cuda(self, device=None):
-        if device is not None:
-            self._device = int(device) if not hasattr(device, "index") else device.index
-        self._ensure()
-        return self
-
-    def eval(self):
-        self.training = False
-        return self
-
     def _prep(self, x):
-        import torch
         self._ensure()
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 320, 256):
             raise ValueError("expected [B,3,320,256], got %s" % (tuple(x.shape),))
-        if x.shape[0] > self.max_batch:
-            raise ValueError("batch %d > max_batch %d" % (x.shape[0], self.max_batch))
-        return x.to(device="cuda:%d" % self._device, dtype=torch.float32).contiguous()
+        return self._on_device(x)
 
     def forward(self, x):
         import torch
@@ -117,110 +90,6 @@ class FastPoseHIP:
                                                     hm.data_ptr() if want_hm else None, kp.data_ptr(),
                                                     _lib.current_stream()))
         return (kp, hm) if want_hm else kp
-
-    def taps(self):
-        self._ensure()
-        L = _lib.lib()
-        out = []
-        name = C.create_string_buffer(64)
-        c, h, w = C.c_int(), C.c_int(), C.c_int()
-        for i in range(L.bp_kpd_tap_count(self._h)):
-            _lib.check(L.bp_kpd_tap_info(self._h, i, name, 64, C.byref(c), C.byref(h), C.byref(w)))
-            out.append((name.value.decode(), c.value, h.value, w.value))
-        return out
-
-    def tap(self, i: int, batch: int = 1):
-        import torch
-        name, c, h, w = self.taps()[i]
-        t = torch.empty((batch, c, h, w), device="cuda:%d" % self._device, dtype=torch.float32)
-        _lib.check(_lib.lib().bp_kpd_tap_copy(self._h, i, batch, t.data_ptr(), _lib.current_stream()))
-        return t
-
-    def set_policy(self, sk_target_blocks: int = 512, sk_min_chunks: int = 4, sk_max_splits: int = 8,
-                   force_tile: int = -1):
-        self._ensure()
-        _lib.check(_lib.lib().bp_kpd_set_policy(self._h, sk_target_blocks, sk_min_chunks, sk_max_splits, force_tile))
-
-    def set_precision(self, precision: str = "bf16x3"):
-        """'f32' (fp32 MFMA), 'bf16x3' (fp32-accurate: exact 3-way bf16 operand split on the bf16 MFMA) or 'f16'
-        (fp16 operands, fp32 accumulate: carries fp16 rounding)."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_kpd_set_precision(self._h, {"f32": 0, "f16": 1, "bf16x3": 2, "f16r": 3}[precision]))
-        self._precision = precision
-        return self
-
-    def clone(self):
-        """Second engine over the same device filters (own activations): one per concurrent stream."""
-        import copy
-        self._ensure()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().bp_kpd_clone(self._h, C.byref(h)))   # first: a failed clone must not leave a copy owning self._h
-        other = copy.copy(self)
-        other._h = h
-        return other
-
-    def profile(self, batch: int = 1, iters: int = 10):
-        """Eager pass with hipEvent pairs per op -> (ms[n_ops], info[n_ops,4] = is_conv, tile, vec, splits)."""
-        self._ensure()
-        L = _lib.lib()
-        n = L.bp_kpd_profile(self._h, batch, iters, None, None, 0, _lib.current_stream())
-        ms = (C.c_float * n)()
-        info = (C.c_int * (4 * n))()
-        rc = L.bp_kpd_profile(self._h, batch, iters, ms, info, n, _lib.current_stream())
-        if rc < 0:
-            _lib.check(rc)
-        return np.array(ms, dtype=np.float64), np.array(info, dtype=np.int64).reshape(n, 4)
-
-    def set_prefetch(self, on: bool = True):
-        """Lone-frame latency mode (include/betapose_hip.h bp_*_set_prefetch), see Darknet.set_prefetch."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_kpd_set_prefetch(self._h, int(bool(on))))
-        self._latency_mode = bool(on)
-
-    def set_fusion(self, on: bool = True):
-        """Conv -> conv fusion of whole residual / bottleneck blocks (include/betapose_hip.h bp_*_set_fusion; default on)."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_kpd_set_fusion(self._h, int(bool(on))))
-
-    def fused_launches(self, batch: int = 1) -> int:
-        self._ensure()
-        n = C.c_int(0)
-        _lib.check(_lib.lib().bp_kpd_fused_launches(self._h, int(batch), C.byref(n)))
-        return int(n.value)
-
-    def xcd_errors(self) -> int:
-        """Non-zero when a launch of the latency mode found a K slice on the wrong XCD since the last call (include/betapose_hip.h
-        bp_*_xcd_errors): its tile was not stored, the frame must be run again with the mode off.  Waits for the current stream."""
-        if not getattr(self, "_latency_mode", False) or self._h is None:
-            return 0
-        n = C.c_int(0)
-        _lib.check(_lib.lib().bp_kpd_xcd_errors(self._h, C.byref(n), _lib.current_stream()))
-        return int(n.value)
-
-    def set_stamps(self, buf=None, slots: int = 0):
-        """In-situ conv timing (include/betapose_hip.h bp_*_set_stamps): ``buf`` a cuda int64 tensor of
-        n_convs * slots * 8 elements, or None to switch it off."""
-        self._ensure()
-        _lib.check(_lib.lib().bp_kpd_set_stamps(self._h, buf.data_ptr() if buf is not None else None, int(slots)))
-
-    def op_names(self):
-        """[(layer name, is_convolution)] in op order."""
-        self._ensure()
-        n = _lib.lib().bp_kpd_op_stats(self._h, None, None, 0)
-        name = C.create_string_buffer(96)
-        out = []
-        for i in range(n):
-            is_conv = _lib.lib().bp_kpd_op_name(self._h, i, name, 96)
-            out.append((name.value.decode(), bool(is_conv == 1)))
-        return out
-
-    def op_stats(self):
-        self._ensure()
-        n = _lib.lib().bp_kpd_op_stats(self._h, None, None, 0)
-        f = (C.c_double * n)()
-        b = (C.c_double * n)()
-        _lib.lib().bp_kpd_op_stats(self._h, f, b, n)
-        return np.array(f), np.array(b)
 
 
 class InferenNet_fast:

@@ -374,6 +374,106 @@ def frame_sharded_owner(n_objects: int, world: int):
     return owner
 
 
+def _copy_rows(rec, pose, pipe):
+    rec.copy_(pipe.results, non_blocking=True)
+    if pose is not None:
+        pose.copy_(pipe.poses, non_blocking=True)
+
+
+class _InflightRing:
+    """The frames-in-flight machinery of the runners, and the only holder of it: ``S`` streams, ``2 S`` pinned record
+    (and optional pose) slots with an event each, the queue of launches in flight, and the loader slots checked out of
+    the source with the number of launches that still read each.  Launch j runs on stream ``j % S`` and lands in slot
+    ``j % 2S``; the runner decides what a launch is and finishes the oldest one once the ring is ``full``.  Every index
+    ``frames`` yields is released exactly once: by the ``finish`` of its last reader, by ``reads(idx, 0)``, or by ``abort``."""
+
+    def __init__(self, device, S: int, rec_shape, pose_shape=None, copy_out=_copy_rows):
+        """``rec_shape`` / ``pose_shape``: what one launch brings back (f32 rows / f64 pose rows or None);
+        ``copy_out(rec_slot, pose_slot, pipe)`` queues the copies from ``pipe`` on the current stream."""
+        import torch
+        self.S = S
+        self.streams = [torch.cuda.Stream(device=device) for _ in range(S)] if device is not None else []   # None: no engine, no launch
+        self._pinned = [torch.empty(rec_shape, dtype=torch.float32).pin_memory() for _ in range(2 * S)]
+        self._pinned_pose = [torch.empty(pose_shape, dtype=torch.float64).pin_memory() if pose_shape is not None else None
+                             for _ in range(2 * S)]
+        self._events = [torch.cuda.Event() for _ in range(2 * S)]
+        self._copy_out = copy_out
+        self._upload, self._on_stream = _lib.lib().bp_upload, torch.cuda.stream
+        self.inflight = []         # (slot, tag, loader indices the launch reads), oldest first
+        self.launched = 0          # j: launches submitted since ``frames`` began
+        self.lane = 0              # j % S: the stream (and frame buffer) the next launch runs on
+        self._out = {}             # loader index checked out -> launches that still read it
+        self._source = None
+
+    def frames(self, source):
+        """Iterate ``source``; each ``(index, frame, host_address)`` is checked out, with one reader, as it is yielded."""
+        self._source, self.launched, self.lane = source, 0, 0
+        for item in source:
+            self._out[item[0]] = 1
+            yield item
+
+    def reads(self, idx, launches: int):
+        """``launches`` launches will read loader slot ``idx`` instead of one; 0 hands it back at once."""
+        if launches:
+            self._out[idx] = launches
+        else:
+            del self._out[idx]
+            self._source.release(idx)
+
+    @property
+    def full(self) -> bool:
+        return len(self.inflight) > self.S
+
+    def upload(self, dst: int, addr: int, nbytes: int):
+        """Host frame -> device address ``dst`` on the next launch's stream (which orders it behind that stream's previous launch)."""
+        _lib.check(self._upload(dst, addr, nbytes, self.streams[self.lane].cuda_stream))
+
+    def submit(self, pipe, tag, idxs):
+        """Launch ``pipe`` on the lane's stream, copy its rows into the lane's pinned slot and record the slot's event.
+        ``idxs``: the loader slots the launch reads; ``tag`` comes back from ``finish``."""
+        st, slot = self.streams[self.lane], self.launched % len(self._events)
+        with self._on_stream(st):
+            pipe.enqueue(st.cuda_stream)
+            self._copy_out(self._pinned[slot], self._pinned_pose[slot], pipe)
+            self._events[slot].record(st)
+        self.inflight.append((slot, tag, idxs))
+        self.launched += 1
+        self.lane = self.launched % self.S
+
+    def finish(self):
+        """Wait for the oldest launch -> ``(tag, rows, pose rows or None)`` (host copies); loader slots whose last reader
+        it was are released first."""
+        slot, tag, idxs = self.inflight.pop(0)
+        self._events[slot].synchronize()
+        recs = self._pinned[slot].numpy().copy()
+        poses = self._pinned_pose[slot].numpy().copy() if self._pinned_pose[slot] is not None else None
+        for idx in idxs:
+            self._out[idx] -= 1
+            if not self._out[idx]:
+                del self._out[idx]
+                self._source.release(idx)
+        return tag, recs, poses
+
+    def abort(self):
+        """After an error mid-stream (a broken frame, a failed launch, a raising callback): let the device drain, then
+        hand the loader every slot still checked out so it can be closed or iterated further."""
+        if self.inflight or self._out:
+            for st in self.streams:
+                st.synchronize()
+            for idx in list(self._out):
+                try:
+                    self._source.release(idx)
+                except Exception:
+                    pass
+            self.inflight.clear()
+            self._out.clear()
+
+
+def _check_frame(idx, frame, H: int, W: int):
+    if frame.shape != (H, W, 3):
+        raise ValueError("frame %d is %s, pipeline was built for %s" % (idx, frame.shape, (H, W, 3)))
+
+
 class StreamedRunner:
     """Keeps ``streams`` frames in flight: one engine clone + one hipGraph per HIP stream over shared filters, frame
     uploads straight from the loader's pinned slots, records copied back into a ring of pinned buffers.  At batch 1
@@ -394,65 +494,52 @@ class StreamedRunner:
         ``batch`` frames per launch and stream (the reference's ``--detbatch``, dataloader.py:284-289): the engines
         must have been created with ``max_batch >= batch``.  More frames per launch mean fewer launches, K slices and
         hand-offs per frame: 1 -> 2 -> 4 frames per launch run 945 -> 1 100 -> 1 290 frames/s."""
-        import torch
         S = max(1, int(streams))
         B = max(1, int(batch))
         pose = getattr(pose_model, "pyranet", pose_model)
         dets = [det_model] + [det_model.clone() for _ in range(S - 1)]
         poses = [pose] + [pose.clone() for _ in range(S - 1)]
         self.C = None if candidates is None else int(candidates)
-        self._instances = bool(all_instances)
-        if self._instances and (self.C is None or pose_solver is None):
+        instances = bool(all_instances)
+        if instances and (self.C is None or pose_solver is None):
             raise ValueError("StreamedRunner: all_instances needs candidates=C and a pose_solver")
+        self.B, self.H, self.W = B, int(frame_h), int(frame_w)
+        with_pose = pose_solver is not None
         if self.C is not None:
             if B != 1:
                 raise ValueError("StreamedRunner: candidates run one frame per launch (batch=1), not batch=%d" % B)
-            if pose_solver is not None and len(pose_solver) > 3 and pose_solver[3] is not None:
+            if with_pose and len(pose_solver) > 3 and pose_solver[3] is not None:
                 raise ValueError("StreamedRunner: the candidate pose tail has no RANSAC variant")
             self.pipes = [CandidatePipeline(dets[k], poses[k], frame_h, frame_w, candidates=self.C, nms_conf=nms_conf,
                                             confidence=confidence, num_classes=num_classes, use_graph=use_graph) for k in range(S)]
-        else:
-            self.pipes = [FramePipeline(dets[k], poses[k], frame_h, frame_w, batch=B, confidence=confidence,
-                                        num_classes=num_classes, use_graph=use_graph) for k in range(S)]
-        dev = self.pipes[0].frames.device
-        self.S, self.B, self.H, self.W = S, B, int(frame_h), int(frame_w)
-        self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
-        if self.C is not None:
-            self._with_pose = pose_solver is not None
-            if self._with_pose:
+            if with_pose:
                 for cp in self.pipes:
-                    cp.set_pose_solver(*pose_solver[:3], all_instances=self._instances)
-            W_ = candidate_row_floats(self.C, self._with_pose, self._instances)
-            self._pinned = [torch.empty((W_,), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
-            self._events = [torch.cuda.Event() for _ in range(2 * S)]
-            self._pinned_pose = None
+                    cp.set_pose_solver(*pose_solver[:3], all_instances=instances)
+            self._ring = _InflightRing(self.pipes[0].frames.device, S, (candidate_row_floats(self.C, with_pose, instances),),
+                                       copy_out=lambda row, _, cp: _pack_candidate_row(row, cp, with_pose, instances))
             return
-        self._pinned = [torch.empty((B, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
-        self._events = [torch.cuda.Event() for _ in range(2 * S)]
-        self._pinned_pose = None
-        if pose_solver is not None:
+        self.pipes = [FramePipeline(dets[k], poses[k], frame_h, frame_w, batch=B, confidence=confidence,
+                                    num_classes=num_classes, use_graph=use_graph) for k in range(S)]
+        if with_pose:
             for fp in self.pipes:
                 fp.set_pose_solver(*pose_solver)
-            self._pinned_pose = [torch.empty((B, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
+        self._ring = _InflightRing(self.pipes[0].frames.device, S, (B, RESULT_FLOATS), (B, POSE_DOUBLES) if with_pose else None)
 
     def run(self, source, on_record) -> int:
         """``source`` yields ``(index, frame[H,W,3] u8 BGR, host_address)`` and has ``release(index)`` (FrameLoader);
         ``on_record(index, rec[316])`` -- ``(index, rec[316], pose_row[166])`` with a pose solver -- is called in source
         order once the frame's record is on the host.
         Returns the number of frames processed."""
-        import torch
-        L = _lib.lib()
-        S, B, NS, nbytes = self.S, self.B, 2 * self.S, self.H * self.W * 3
-        inflight = []          # (launch number, [source indices of its frames])
+        ring, B, nbytes = self._ring, self.B, self.H * self.W * 3
         pending = []           # source indices uploaded into the current launch's batch slots
 
-        def finish():
-            j, idxs = inflight.pop(0)
-            self._events[j % NS].synchronize()
-            recs = self._pinned[j % NS].numpy().copy()
-            poses = self._pinned_pose[j % NS].numpy().copy() if self._pinned_pose is not None else None
-            for b, idx in enumerate(idxs):
-                source.release(idx)
+        def launch():
+            idxs = tuple(pending)
+            pending.clear()
+            ring.submit(self.pipes[ring.lane], idxs, idxs)
+
+        def deliver():
+            idxs, recs, poses = ring.finish()
             if self.C is not None:
                 on_record(idxs[0], recs)
                 return
@@ -462,56 +549,24 @@ class StreamedRunner:
                 else:
                     on_record(idx, recs[b], poses[b])
 
-        def launch(j):
-            k = j % S
-            st = self.streams[k]
-            with torch.cuda.stream(st):
-                self.pipes[k].enqueue(st.cuda_stream)
-                if self.C is not None:
-                    _pack_candidate_row(self._pinned[j % NS], self.pipes[k], self._with_pose, self._instances)
-                else:
-                    self._pinned[j % NS].copy_(self.pipes[k].results, non_blocking=True)
-                if self._pinned_pose is not None:
-                    self._pinned_pose[j % NS].copy_(self.pipes[k].poses, non_blocking=True)
-                self._events[j % NS].record(st)
-            inflight.append((j, list(pending)))
-            pending.clear()
-
-        j, n = 0, 0
+        n = 0
         try:
-            for idx, frame, addr in source:
-                if frame.shape != (self.H, self.W, 3):
-                    source.release(idx)
-                    raise ValueError("frame %d is %s, pipeline was built for %s" % (idx, frame.shape, (self.H, self.W, 3)))
-                k = j % S
-                st = self.streams[k]
-                with torch.cuda.stream(st):
-                    _lib.check(L.bp_upload(self.pipes[k].frames.data_ptr() + len(pending) * nbytes, addr, nbytes, st.cuda_stream))
+            for idx, frame, addr in ring.frames(source):
+                _check_frame(idx, frame, self.H, self.W)
+                ring.upload(self.pipes[ring.lane].frames.data_ptr() + len(pending) * nbytes, addr, nbytes)
                 pending.append(idx)
                 n += 1
                 if len(pending) == B:
-                    launch(j)
-                    j += 1
-                    if len(inflight) > S:      # (the stream's own order keeps a launch's frame slots safe from the next upload)
-                        finish()
+                    launch()
+                    if ring.full:              # (the stream's own order keeps a launch's frame slots safe from the next upload)
+                        deliver()
             if pending:                        # ragged last launch: the unused slots keep their previous frames, whose
-                launch(j)                      # records nobody reads
-                j += 1
-            while inflight:
-                finish()
-        finally:
-            # an error mid-stream (a broken frame, a failed launch): let the device drain, then hand the loader its
-            # slots back so it can be closed or iterated further
-            if inflight or pending:
-                for st in self.streams:
-                    st.synchronize()
-                for idx in [i for _, idxs in inflight for i in idxs] + pending:
-                    try:
-                        source.release(idx)
-                    except Exception:
-                        pass
-                inflight.clear()
-                pending.clear()
+                launch()                       # records nobody reads
+            while ring.inflight:
+                deliver()
+        except BaseException:
+            ring.abort()
+            raise
         return n
 
 
@@ -536,20 +591,19 @@ class MultiObjectRunner:
     def __init__(self, engines: dict, obj_ids: List[int], frame_h: int = 480, frame_w: int = 640, streams: int = 4,
                  confidence: float = 0.01, num_classes: int = 80, use_graph: bool = True, pose_solvers: Optional[dict] = None,
                  shared_detector=None):
-        import torch
         self.obj_ids = list(obj_ids)
         S = max(1, int(streams))
-        self.S, self.H, self.W = S, int(frame_h), int(frame_w)
+        self.H, self.W = int(frame_h), int(frame_w)
         self.pipes = {}            # (stream, obj_id) -> FramePipeline over the stream's shared frame buffer
         self.scenes = None         # shared_detector: one ScenePipeline per stream
-        dev = None
         self.frame_bufs = []
+        rows = 1                   # rows a launch brings back: one unit, or a frame's K behind the shared detector
         if shared_detector is not None:
             det, class_of = shared_detector
             missing = [o for o in self.obj_ids if o not in engines]
             if missing:
                 raise ValueError("shared detector: no key-point engine for objects %s" % missing)
-            K = len(self.obj_ids)
+            rows = len(self.obj_ids)
             self.scenes = []
             for k in range(S):
                 poses = {o: getattr(engines[o], "pyranet", engines[o]) for o in self.obj_ids}
@@ -563,164 +617,62 @@ class MultiObjectRunner:
                         sp.set_pose_solver(o, *pose_solvers[o])
                 self.scenes.append(sp)
                 self.frame_bufs.append(sp.frames)
-            dev = self.frame_bufs[0].device
-            self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
-            self._pinned = [torch.empty((K, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
-            self._events = [torch.cuda.Event() for _ in range(2 * S)]
-            self._pinned_pose = None
-            if pose_solvers is not None:
-                self._pinned_pose = [torch.empty((K, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
-            return
-        for k in range(S):
-            buf = None
-            for oid, (det, pose) in engines.items():
-                pose = getattr(pose, "pyranet", pose)
-                d, p_ = (det, pose) if k == 0 else (det.clone(), pose.clone())
-                fp = FramePipeline(d, p_, frame_h, frame_w, batch=1, confidence=confidence, num_classes=num_classes,
-                                   use_graph=use_graph, frames=buf)
-                if pose_solvers is not None:
-                    fp.set_pose_solver(*pose_solvers[oid])
-                buf = fp.frames
-                dev = buf.device
-                self.pipes[(k, oid)] = fp
-            self.frame_bufs.append(buf)
-        self.streams = [torch.cuda.Stream(device=dev) for _ in range(S)] if dev is not None else []
-        self._pinned = [torch.empty((1, RESULT_FLOATS), dtype=torch.float32).pin_memory() for _ in range(2 * S)]
-        self._events = [torch.cuda.Event() for _ in range(2 * S)]
-        self._pinned_pose = None
-        if pose_solvers is not None:
-            self._pinned_pose = [torch.empty((1, POSE_DOUBLES), dtype=torch.float64).pin_memory() for _ in range(2 * S)]
+        else:
+            for k in range(S):
+                buf = None
+                for oid, (det, pose) in engines.items():
+                    pose = getattr(pose, "pyranet", pose)
+                    d, p_ = (det, pose) if k == 0 else (det.clone(), pose.clone())
+                    fp = FramePipeline(d, p_, frame_h, frame_w, batch=1, confidence=confidence, num_classes=num_classes,
+                                       use_graph=use_graph, frames=buf)
+                    if pose_solvers is not None:
+                        fp.set_pose_solver(*pose_solvers[oid])
+                    buf = fp.frames
+                    self.pipes[(k, oid)] = fp
+                self.frame_bufs.append(buf)
+        dev = self.frame_bufs[0].device if self.frame_bufs[0] is not None else None
+        self._ring = _InflightRing(dev, S, (rows, RESULT_FLOATS), (rows, POSE_DOUBLES) if pose_solvers is not None else None)
 
     def run(self, source, frame_positions: List[int], owned, on_record) -> int:
         """``source``: FrameLoader over the frames this rank touches (in ``frame_positions`` order: position of each
         in the global frame list); ``owned(u)`` tells whether unit u belongs to this rank;
-        ``on_record(u, rec[316])`` receives every owned unit's record.  Returns the number of units run."""
-        import torch
-        if self.scenes is not None:
-            return self._run_shared(source, frame_positions, owned, on_record)
-        L = _lib.lib()
-        S, NS, nbytes, K = self.S, 2 * self.S, self.H * self.W * 3, len(self.obj_ids)
-        inflight = []              # (sequence number, unit, loader index or None when this is not the frame's last unit)
-        pending = {}               # loader index -> units still in flight
+        ``on_record(u, rec[316])`` receives every owned unit's record.  Returns the number of units run.
+        Behind a shared detector a frame is the unit in flight (``streams`` of them): its K rows come back together and
+        are handed out unit by unit."""
+        ring, nbytes, K, shared = self._ring, self.H * self.W * 3, len(self.obj_ids), self.scenes is not None
 
-        def finish():
-            j, u, idx = inflight.pop(0)
-            self._events[j % NS].synchronize()
-            rec = self._pinned[j % NS].numpy()[0].copy()
-            pose = self._pinned_pose[j % NS].numpy()[0].copy() if self._pinned_pose is not None else None
-            pending[idx] -= 1
-            if pending[idx] == 0:
-                del pending[idx]
-                source.release(idx)
-            if pose is None:
-                on_record(u, rec)
-            else:
-                on_record(u, rec, pose)
+        def deliver():
+            u, recs, poses = ring.finish()     # u: the launch's first unit, one row per unit
+            for r in range(len(recs)):
+                if poses is None:
+                    on_record(u + r, recs[r])
+                else:
+                    on_record(u + r, recs[r], poses[r])
 
-        j = 0
         try:
-            for idx, frame, addr in source:
-                if frame.shape != (self.H, self.W, 3):
-                    source.release(idx)
-                    raise ValueError("frame %d is %s, pipeline was built for %s" % (idx, frame.shape, (self.H, self.W, 3)))
-                units = [frame_positions[idx] * K + oi for oi in range(K) if owned(frame_positions[idx] * K + oi)]
-                if not units:
-                    source.release(idx)
-                    continue
-                pending[idx] = len(units)
+            for idx, frame, addr in ring.frames(source):
+                _check_frame(idx, frame, self.H, self.W)
+                f = frame_positions[idx]
+                units = [u for u in range(f * K, f * K + K) if owned(u)]
+                if shared and units:
+                    if len(units) < K:
+                        raise ValueError("shared detector: the units of frame %d are split over ranks (shard by frame)" % f)
+                    units = units[:1]
+                ring.reads(idx, len(units))    # nobody's frame: released at once without a launch
                 for u in units:
-                    k = j % S
-                    st = self.streams[k]
                     # the stream's frame buffer is only rewritten after the stream's previous unit finished reading it
                     # (same stream: in order)
-                    with torch.cuda.stream(st):
-                        _lib.check(L.bp_upload(self.frame_bufs[k].data_ptr(), addr, nbytes, st.cuda_stream))
-                        fp = self.pipes[(k, self.obj_ids[u % K])]
-                        fp.enqueue(st.cuda_stream)
-                        self._pinned[j % NS].copy_(fp.results, non_blocking=True)
-                        if self._pinned_pose is not None:
-                            self._pinned_pose[j % NS].copy_(fp.poses, non_blocking=True)
-                        self._events[j % NS].record(st)
-                    inflight.append((j, u, idx))
-                    j += 1
-                    if len(inflight) > S:
-                        finish()
-            while inflight:
-                finish()
-        finally:
-            if inflight:
-                for st in self.streams:
-                    st.synchronize()
-                for idx in list(pending):
-                    try:
-                        source.release(idx)
-                    except Exception:
-                        pass
-                inflight.clear()
-        return j
-
-
-    def _run_shared(self, source, frame_positions, owned, on_record) -> int:
-        """``run`` behind a shared detector: a frame is the unit in flight (``streams`` of them), its K rows come back
-        together and are handed out unit by unit."""
-        import torch
-        L = _lib.lib()
-        S, NS, nbytes, K = self.S, 2 * self.S, self.H * self.W * 3, len(self.obj_ids)
-        inflight = []              # (sequence number, frame position, loader index)
-
-        def finish():
-            j, f, idx = inflight.pop(0)
-            self._events[j % NS].synchronize()
-            recs = self._pinned[j % NS].numpy().copy()
-            poses = self._pinned_pose[j % NS].numpy().copy() if self._pinned_pose is not None else None
-            source.release(idx)
-            for oi in range(K):
-                if poses is None:
-                    on_record(f * K + oi, recs[oi])
-                else:
-                    on_record(f * K + oi, recs[oi], poses[oi])
-
-        j = 0
-        try:
-            for idx, frame, addr in source:
-                if frame.shape != (self.H, self.W, 3):
-                    source.release(idx)
-                    raise ValueError("frame %d is %s, pipeline was built for %s" % (idx, frame.shape, (self.H, self.W, 3)))
-                f = frame_positions[idx]
-                mine = [owned(f * K + oi) for oi in range(K)]
-                if not any(mine):
-                    source.release(idx)
-                    continue
-                if not all(mine):
-                    source.release(idx)
-                    raise ValueError("shared detector: the units of frame %d are split over ranks (shard by frame)" % f)
-                k = j % S
-                st = self.streams[k]
-                with torch.cuda.stream(st):
-                    _lib.check(L.bp_upload(self.frame_bufs[k].data_ptr(), addr, nbytes, st.cuda_stream))
-                    sp = self.scenes[k]
-                    sp.enqueue(st.cuda_stream)
-                    self._pinned[j % NS].copy_(sp.results, non_blocking=True)
-                    if self._pinned_pose is not None:
-                        self._pinned_pose[j % NS].copy_(sp.poses, non_blocking=True)
-                    self._events[j % NS].record(st)
-                inflight.append((j, f, idx))
-                j += 1
-                if len(inflight) > S:
-                    finish()
-            while inflight:
-                finish()
-        finally:
-            if inflight:
-                for st in self.streams:
-                    st.synchronize()
-                for _, _, idx in inflight:
-                    try:
-                        source.release(idx)
-                    except Exception:
-                        pass
-                inflight.clear()
-        return j * K
+                    k = ring.lane
+                    ring.upload(self.frame_bufs[k].data_ptr(), addr, nbytes)
+                    ring.submit(self.scenes[k] if shared else self.pipes[(k, self.obj_ids[u % K])], u, (idx,))
+                    if ring.full:
+                        deliver()
+            while ring.inflight:
+                deliver()
+        except BaseException:
+            ring.abort()
+            raise
+        return ring.launched * (K if shared else 1)
 
 
 def finish_record(rec: np.ndarray, imgname: str, kp_3d: np.ndarray, cam_K: np.ndarray, left_number: int = 50,

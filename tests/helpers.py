@@ -44,3 +44,23 @@ def yolo_input_from_frame(frame_bgr, reso=416):
     img = Image.fromarray(np.ascontiguousarray(frame_bgr[:, :, ::-1])).resize((reso, reso), 3)
     a = np.asarray(img, dtype=np.uint8).transpose(2, 0, 1).copy()
     return torch.from_numpy(a).float().div(255).unsqueeze(0)
+
+
+class CountingSource:
+    """An in-memory frame source with ``FrameLoader``'s surface for the runners: yields ``(i, frame, host address)`` and
+    records every ``release(i)``, so a test can tell that each slot it handed out came back exactly once."""
+
+    def __init__(self, frame_list):
+        self.frames = [np.ascontiguousarray(f) for f in frame_list]
+        self.yielded, self.released = [], []
+
+    def __iter__(self):
+        for i, f in enumerate(self.frames):
+            self.yielded.append(i)
+            yield i, f, f.ctypes.data
+
+    def release(self, i):
+        self.released.append(i)
+
+    def assert_each_released_once(self):
+        assert sorted(self.released) == self.yielded, (self.yielded, self.released)

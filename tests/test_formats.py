@@ -133,6 +133,35 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "libbetapose_hip.so does not export %s" % name
 
 
+# the operations bp_yolo_* and bp_kpd_* both export -> their arguments behind the engine handle
+TWIN_ARGS = {
+    "clone": None,                                   # filled in by the test: a real out pointer
+    "tap_count": (), "tap_info": (0, None, 0, None, None, None), "tap_copy": (0, 1, None, None),
+    "set_policy": (512, 4, 8, -1), "set_precision": (2,), "op_stats": (None, None, 0),
+    "profile": (1, 1, None, None, 0, None), "set_prefetch": (1,), "set_fusion": (1,), "fused_launches": (1, None),
+    "xcd_errors": (None, None), "set_stamps": (None, 0), "op_name": (0, None, 0), "device_bytes": (),
+}
+
+
+@pytest.mark.parametrize("prefix", ["bp_yolo", "bp_kpd"])
+def test_twin_entry_points_answer_a_null_handle(prefix):
+    """Every operation the two engine handles share refuses a null handle the same way, before touching a device:
+    -1 and "null argument" (``device_bytes``: 0)."""
+    lib = _lib.lib()
+    assert len(TWIN_ARGS) == 15
+    for op, args in TWIN_ARGS.items():
+        fn = getattr(lib, "%s_%s" % (prefix, op))
+        if op == "device_bytes":
+            assert fn(None) == 0
+            continue
+        out = ctypes.c_void_p()
+        lib.bp_stream_create_masked(None, 0, None)    # leaves another text in bp_last_error()
+        assert lib.bp_last_error() != b"null argument"
+        assert fn(None, *((ctypes.byref(out),) if op == "clone" else args)) == -1, op
+        assert lib.bp_last_error() == b"null argument", (op, lib.bp_last_error())
+        assert not out.value
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

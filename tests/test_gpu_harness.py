@@ -228,3 +228,85 @@ def test_fused_frames_per_launch_matches_one_frame_per_launch(tmp_path):
     for e1, e3 in zip(outs[1], outs[3]):
         k1, k3 = np.asarray(e1["keypoints"]).reshape(-1, 3), np.asarray(e3["keypoints"]).reshape(-1, 3)
         assert np.abs(k1[:, :2] - k3[:, :2]).max() <= 5e-3 and np.abs(k1[:, 2] - k3[:, 2]).max() <= 2e-4
+
+
+def _engines(max_batch=1):
+    from betapose_amd.darknet import Darknet
+    from betapose_amd.kpd import FastPoseHIP
+    from betapose_amd.weights import fastpose_stream_from_state_dict
+    det = Darknet("yolo/cfg/yolov3-single.cfg", reso=416, max_batch=max_batch).load_stream(helpers.yolo_stream()).cuda()
+    pose = FastPoseHIP.from_stream(fastpose_stream_from_state_dict(helpers.kpd_state_dict(), 50), n_classes=50,
+                                   max_batch=max_batch).cuda()
+    return det, pose
+
+
+def _raise_at(unit, inner):
+    def owned(u):
+        if u == unit:
+            raise RuntimeError("owned(%d)" % u)
+        return inner(u)
+    return owned
+
+
+def test_streamed_runner_releases_every_slot_once(cuda):
+    """Batch 2, 5 frames, 2 streams (two full launches and a ragged one): records in source order and every loader slot
+    back exactly once -- also when ``on_record`` raises with launches still in flight."""
+    from betapose_amd.pipeline import StreamedRunner
+    from betapose_amd import synth
+    runner = StreamedRunner(*_engines(2), 480, 640, streams=2, batch=2)
+    src = helpers.CountingSource(synth.synth_frames(5, 321))
+    seen = []
+    assert runner.run(src, lambda i, rec: seen.append(i)) == 5
+    assert seen == [0, 1, 2, 3, 4] and src.yielded == seen
+    src.assert_each_released_once()
+
+    def on_record(i, rec):
+        if i == 2:
+            raise RuntimeError("on_record(2)")
+    src = helpers.CountingSource(synth.synth_frames(5, 321))
+    with pytest.raises(RuntimeError, match=r"on_record\(2\)"):
+        runner.run(src, on_record)
+    src.assert_each_released_once()
+
+
+def test_multi_object_runner_releases_every_slot_once(cuda):
+    """Per-object mode, two objects, 4 frames: units 0, 3, 4 are this rank's, frame 3 is nobody's (released with no
+    record); an ``owned`` that raises propagates and still leaves no slot checked out."""
+    from betapose_amd.pipeline import MultiObjectRunner
+    from betapose_amd import synth
+    det, pose = _engines()
+    runner = MultiObjectRunner({1: (det, pose), 2: (det.clone(), pose.clone())}, [1, 2], 480, 640, streams=2)
+    mine = lambda u: u in {0, 3, 4}
+    src = helpers.CountingSource(synth.synth_frames(4, 321))
+    seen = []
+    assert runner.run(src, [0, 1, 2, 3], mine, lambda u, rec: seen.append(u)) == 3
+    assert seen == [0, 3, 4] and src.yielded == [0, 1, 2, 3]
+    src.assert_each_released_once()
+    src = helpers.CountingSource(synth.synth_frames(4, 321))
+    seen = []
+    with pytest.raises(RuntimeError, match=r"owned\(3\)"):
+        runner.run(src, [0, 1, 2, 3], _raise_at(3, mine), lambda u, rec: seen.append(u))
+    assert src.yielded == [0, 1] and set(seen) <= {0}
+    src.assert_each_released_once()
+
+
+def test_shared_runner_releases_every_slot_once(cuda):
+    """Shared-detector mode over the scene tests' engines: a frame split over ranks is refused, an ``owned`` that raises
+    propagates, and either way every loader slot comes back exactly once."""
+    from betapose_amd.pipeline import MultiObjectRunner
+    from test_gpu_scene import CLASS_OF, CONF, OBJS, _det15, _pose
+    K = len(OBJS)
+    runner = MultiObjectRunner({o: _pose(o) for o in OBJS}, OBJS, 480, 640, streams=2, confidence=CONF,
+                               shared_detector=(_det15(), CLASS_OF))
+    src = helpers.CountingSource(helpers.frames(4))
+    seen = []
+    with pytest.raises(ValueError, match="the units of frame 1 are split over ranks"):
+        runner.run(src, [0, 1, 2, 3], lambda u: u != K + 1, lambda u, rec: seen.append(u))
+    assert src.yielded == [0, 1] and set(seen) <= set(range(K))
+    src.assert_each_released_once()
+    src = helpers.CountingSource(helpers.frames(4))
+    seen = []
+    with pytest.raises(RuntimeError, match=r"owned\(%d\)" % (2 * K)):
+        runner.run(src, [0, 1, 2, 3], _raise_at(2 * K, lambda u: True), lambda u, rec: seen.append(u))
+    assert src.yielded == [0, 1, 2] and seen == sorted(seen) and set(seen) <= set(range(2 * K))
+    src.assert_each_released_once()
