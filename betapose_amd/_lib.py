@@ -123,6 +123,14 @@ PROTOTYPES = {
                                   vp]),
     "bp_render_depth_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp,
                                        vp]),
+    "bp_render_color": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double,
+                                  C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, vp]),
+    "bp_render_color_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp]),
+    "bp_draw_boxes": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]),
+    "bp_draw_boxes_host": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
+    "bp_overlay": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_overlay_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                 C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "bp_icp_normal_equations": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,

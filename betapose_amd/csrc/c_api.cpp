@@ -654,6 +654,166 @@ int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, con
     BP_CATCH
 }
 
+// what the colour renderer's calls check of image_index (host, may be NULL): pose p -> image p needs I == P, otherwise
+// non-decreasing values in [0, I), which lets a call split its work into pose ranges without splitting an image
+static void raster_check_image_index(const int* image_index, int P, int I) {
+    BP_CHECK(I > 0, "I must be positive");
+    if (!image_index) {
+        BP_CHECK(I == P, "without image_index the call needs I == P");
+        return;
+    }
+    for (int p = 0; p < P; ++p) {
+        BP_CHECK(image_index[p] >= 0 && image_index[p] < I, "image_index must lie in [0, I)");
+        BP_CHECK(p == 0 || image_index[p] >= image_index[p - 1], "image_index must be non-decreasing");
+    }
+}
+
+// poses [*p0, return) of the call go to images [i0, i1); *p0 on entry: the first pose not yet consumed
+static int raster_pose_range(const int* image_index, int P, int i1, int p0) {
+    if (!image_index) return std::min(P, i1);
+    int p = p0;
+    while (p < P && image_index[p] < i1) ++p;
+    return p;
+}
+
+int bp_render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                         const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
+                         double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                         unsigned char* color, float* depth, int* skipped) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && colors && K && light && color && depth && skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
+    BP_CHECK(bp::render_color_host(poses, P, vertices, n, faces, F, colors, image_index, I, K, H, W, pixel_center, near_z, ambient,
+                                   light, accumulate, color, depth, skipped) == 0,
+             "a face index lies outside [0, n)");   // (its scan comes before it touches anything)
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_color(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
+                    const double* d_poses, int P, const int* image_index, int I, const double* K, int H, int W,
+                    double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                    unsigned char* d_color, float* d_depth, int* d_skipped, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_colors && d_poses && K && light && d_color && d_depth && d_skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    // images in flight: 8 bytes of key per pixel; poses in flight: their vertex workspace; each under RASTER_WS_BYTES
+    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 8), (size_t)I));
+    const size_t pchunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1), (size_t)P));
+    bp::Arena a;
+    unsigned long long* keys = (unsigned long long*)a.alloc_bytes(ichunk * HW * 8);
+    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)pchunk));
+    int* d_index = nullptr;
+    if (image_index) {
+        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
+        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
+    const bp::ColorLight lt{ambient, light[0], light[1], light[2]};
+    int p0 = 0;
+    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
+        const int m = (int)std::min(ichunk, (size_t)I - i0);
+        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
+        bp::launch_color_clear(keys, d_depth + i0 * HW, accumulate, (size_t)m * HW, s);
+        for (int q0 = p0; q0 < p1; q0 += (int)pchunk) {
+            const int c = std::min((int)pchunk, p1 - q0);
+            bp::launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, K, pixel_center, near_z, ws, s);
+            bp::launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, K, H, W, pixel_center, near_z, keys,
+                                        d_skipped, s);
+        }
+        bp::launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, K, H, W, pixel_center, near_z, lt,
+                                 d_color + i0 * HW * 3, d_depth + i0 * HW, s);
+        p0 = p1;
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the keys and the vertex workspace live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+static void raster_check_boxes(int P, int I, int H, int W, double near_z) {
+    BP_CHECK(P > 0 && I > 0 && H > 0 && W > 0, "P, I, H and W must be positive");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+    BP_CHECK(P <= (1 << 24), "P must not exceed 2^24");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+}
+
+int bp_draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
+                       const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                       unsigned char* color) {
+    BP_TRY
+    BP_CHECK(poses && corners && corner_colors && K && color, "null argument");
+    raster_check_boxes(P, I, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    bp::draw_boxes_host(poses, P, corners, corner_colors, image_index, I, K, H, W, pixel_center, near_z, color);
+    return 0;
+    BP_CATCH
+}
+
+int bp_draw_boxes(const double* d_poses, int P, const double* d_corners, const unsigned char* d_corner_colors,
+                  const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                  unsigned char* d_color, void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_corners && d_corner_colors && K && d_color, "null argument");
+    raster_check_boxes(P, I, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 4), (size_t)I));
+    bp::Arena a;
+    uint32_t* ids = (uint32_t*)a.alloc_bytes(ichunk * HW * 4);
+    int* d_index = nullptr;
+    if (image_index) {
+        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
+        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    int p0 = 0;
+    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
+        const int m = (int)std::min(ichunk, (size_t)I - i0);
+        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
+        if (p1 > p0)
+            bp::launch_draw_boxes(d_poses, p0, p1 - p0, d_corners, d_corner_colors, d_index, (int)i0, m, K, H, W, pixel_center,
+                                  near_z, ids, d_color + i0 * HW * 3, s);
+        p0 = p1;
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the id planes live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,
+                    unsigned char* out) {
+    BP_TRY
+    BP_CHECK(frames && color && depth && out, "null argument");
+    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+    BP_CHECK(alpha >= 0 && alpha <= 256, "alpha must lie in 0 .. 256");
+    bp::overlay_host(frames, color, depth, I, H, W, alpha, out);
+    return 0;
+    BP_CATCH
+}
+
+int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, const float* d_depth, int I, int H, int W, int alpha,
+               unsigned char* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_frames && d_color && d_depth && d_out, "null argument");
+    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+    BP_CHECK(alpha >= 0 && alpha <= 256, "alpha must lie in 0 .. 256");
+    hipStream_t s = (hipStream_t)stream;
+    bp::launch_overlay(d_frames, d_color, d_depth, (size_t)I * H * W, alpha, d_out, s);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
 int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
                   const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
                   const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,

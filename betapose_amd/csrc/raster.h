@@ -31,6 +31,51 @@ void launch_raster(const double* model, int n, const int* faces, int F, const do
                    int* skipped, hipStream_t s);
 // +inf -> 0 over `count` values, in place: the z-buffer becomes the public depth image
 void launch_raster_finish(uint32_t* zbuf, size_t count, hipStream_t s);
+// launch_raster's first half alone, for the colour renderer: the camera-space xyz and the snapped uv of `poses` poses
+// into vertex_ws (raster_vertex_bytes(n, poses): xyz [poses][n][3] f64, then uv [poses][n][2] i32)
+void launch_raster_transform(const double* model, int n, const double* poses, int count, const double* K, double pixel_center,
+                             double near, void* vertex_ws, hipStream_t s);
+
+// ---- raster_color_host.cpp: the host twins of the colour renderer (raster_color.hip), all pointers host.  colors
+// [n][3] u8, image_index [P] or NULL (pose p -> image p), light [3]; color [I][H][W][3] u8, depth [I][H][W] f32.
+// render_color_host returns -1 for a face index outside [0, n), else 0.
+int render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                      const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
+                      double pixel_center, double near, double ambient, const double* light, int accumulate,
+                      unsigned char* color, float* depth, int* skipped);
+void draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
+                     const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near,
+                     unsigned char* color);
+void overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,
+                  unsigned char* out);
+
+// ---- raster_color.hip
+struct ColorLight {
+    double ambient;
+    double x, y, z;     // light position in camera space
+};
+constexpr unsigned long long COLOR_MAX_IDS = 0xFFFFFFFEull;     // P * F above this is refused: fragment ids stay below 2^32 - 1
+// keys [images][H][W] u64 <- the empty key, or with `accumulate` the kept key of every pixel of depth [images][H][W]
+// that holds something
+void launch_color_clear(unsigned long long* keys, const float* depth, int accumulate, size_t count, hipStream_t s);
+// z-test of poses [q0, q0 + count) of the call (vertex_ws: their launch_raster_transform) into keys, whose first image is
+// image img0 of the call; d_image_index [P] of the call or NULL; fragment ids are (call's pose slot) * F + face.  ADDS the
+// skipped triangles to skipped[q0 ..].
+void launch_color_visibility(const int* faces, int F, int n, const void* vertex_ws, int q0, int count,
+                             const int* d_image_index, int img0, const double* K, int H, int W, double pixel_center,
+                             double near, unsigned long long* keys, int* skipped, hipStream_t s);
+// colour and depth of `images` images from their keys: the winner shaded from model, faces, colors and the call's poses
+void launch_color_resolve(const unsigned long long* keys, int images, const double* model, const int* faces, int F,
+                          const unsigned char* colors, const double* poses, const double* K, int H, int W,
+                          double pixel_center, double near, const ColorLight& light, unsigned char* color, float* depth,
+                          hipStream_t s);
+// the 12 box edges of poses [q0, q0 + count) of the call over color, whose first image is image img0 of the call; ids
+// [images][H][W] u32 is scratch that the call clears itself
+void launch_draw_boxes(const double* poses, int q0, int count, const double* corners, const unsigned char* corner_colors,
+                       const int* d_image_index, int img0, int images, const double* K, int H, int W, double pixel_center,
+                       double near, uint32_t* ids, unsigned char* color, hipStream_t s);
+void launch_overlay(const unsigned char* frames, const unsigned char* color, const float* depth, size_t pixels, int alpha,
+                    unsigned char* out, hipStream_t s);
 
 // ---- vsd.hip
 // acc [pairs][VSD_ACC] (zeroed by the caller) += the counts of pairs [0, pairs): zbuf holds the ground-truth renders

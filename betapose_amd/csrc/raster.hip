@@ -153,6 +153,16 @@ void launch_raster(const double* model, int n, const int* faces, int F, const do
                        uv, poses, cam, H, W, zbuf, skipped);
 }
 
+void launch_raster_transform(const double* model, int n, const double* poses, int count, const double* K, double pixel_center,
+                             double near, void* vertex_ws, hipStream_t s) {
+    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+    double* xyz = (double*)vertex_ws;
+    int* uv = (int*)(xyz + (size_t)count * n * 3);
+    const int gy = count < 65535 ? count : 65535;
+    hipLaunchKernelGGL(raster_transform_kernel, dim3((n + RS_THREADS - 1) / RS_THREADS, gy), dim3(RS_THREADS), 0, s, model, n,
+                       poses, count, (const double*)nullptr, count, cam, xyz, uv);
+}
+
 void launch_raster_finish(uint32_t* zbuf, size_t count, hipStream_t s) {
     size_t blocks = (count + RS_THREADS - 1) / RS_THREADS;
     if (blocks > 65535) blocks = 65535;

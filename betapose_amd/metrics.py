@@ -322,6 +322,30 @@ def load_ply_mesh(path: str):
     ``load_ply_vertices`` reads them (same formats, same units: the file's own, nothing is scaled) and the
     ``vertex_indices`` / ``vertex_index`` list of its face element.  A polygon of more than three vertices is
     fan-triangulated about its first vertex, (v0, v1, v2), (v0, v2, v3), ...; one of fewer than three is dropped."""
+    return _read_ply_mesh(path)[:2]
+
+
+def load_ply_colored_mesh(path: str):
+    """``(vertices [n, 3] float64, faces [F, 3] int32, colors [n, 3] uint8 RGB)``: ``load_ply_mesh`` plus the ``red``,
+    ``green``, ``blue`` properties of the vertex element (ASCII and both binary byte orders; float colours in [0, 1]
+    are scaled to 0 .. 255).  A file without them gives 128 everywhere, the reference's 0.5 grey (utils/model.py)."""
+    vertices, faces, colors = _read_ply_mesh(path)
+    if colors is None:
+        colors = np.full((len(vertices), 3), 128, np.uint8)
+    return vertices, faces, colors
+
+
+def _ply_colors(cols, kinds):
+    """uint8 [n, 3] of three colour columns; ``kinds`` their numpy type codes (a float column holds [0, 1])."""
+    out = []
+    for c, k in zip(cols, kinds):
+        c = np.asarray(c, dtype=np.float64)
+        out.append(np.clip(np.floor(c * 255.0 + 0.5) if k[0] == "f" else c, 0, 255).astype(np.uint8))
+    return np.ascontiguousarray(np.stack(out, axis=1))
+
+
+def _read_ply_mesh(path: str):
+    """(vertices, faces, colors or None) of a .ply file; load_ply_mesh and load_ply_colored_mesh."""
     with open(path, "rb") as f:
         head = b""
         while not head.rstrip().endswith(b"end_header"):
@@ -348,7 +372,8 @@ def load_ply_mesh(path: str):
         if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
             raise ValueError("%s: unknown PLY format %s" % (path, fmt))
         end = ">" if fmt == "binary_big_endian" else "<"
-        vertices, faces = None, None
+        vertices, faces, colors = None, None, None
+        rgb = ("red", "green", "blue")
         for name, count, props in elems:
             has_list = any(len(p_) == 3 for p_ in props)
             names = [p_[0] for p_ in props]
@@ -369,6 +394,8 @@ def load_ply_mesh(path: str):
                 if name == "vertex":
                     v = np.frombuffer(buf, dtype=dt, count=count)
                     vertices = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float64)
+                    if all(a in names for a in rgb):
+                        colors = _ply_colors([v[a] for a in rgb], [dict(props)[a] for a in rgb])
                 continue
             for _ in range(count):
                 vals = []
@@ -402,6 +429,9 @@ def load_ply_mesh(path: str):
             if name == "vertex":
                 ix = [names.index(a) for a in ("x", "y", "z")]
                 vertices = np.array([[r[i][0] for i in ix] for r in rows], dtype=np.float64).reshape(count, 3)
+                if all(a in names for a in rgb):
+                    cx = [names.index(a) for a in rgb]
+                    colors = _ply_colors([[r[i][0] for r in rows] for i in cx], [props[i][1] for i in cx])
             elif name == "face":
                 tris = []
                 for r in rows:
@@ -410,7 +440,7 @@ def load_ply_mesh(path: str):
                 faces = np.array(tris, dtype=np.int32).reshape(-1, 3)
         if vertices is None or faces is None:
             raise ValueError("%s: needs a vertex and a face element" % path)
-        return vertices, faces
+        return vertices, faces, colors
 
 
 BOP_VSD_TAUS = tuple(0.05 * k for k in range(1, 11))        # misalignment tolerances, fractions of the object diameter
@@ -471,6 +501,157 @@ def render_depth(poses, vertices, faces, K, size, device=None, pixel_center=0.0,
                                               _lib.ptr(d_depth), _lib.ptr(d_skipped),
                                               torch.cuda.current_stream(dev).cuda_stream))
         return d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+
+
+def _image_index(image_index, images, P):
+    """(int32 [P] or None, I) as the colour renderer's calls take them; the library checks the rules."""
+    if image_index is None:
+        return None, P if images is None else int(images)
+    image_index = np.ascontiguousarray(image_index, dtype=np.int32).reshape(-1)
+    if len(image_index) != P:
+        raise ValueError("image_index needs one entry per pose")
+    return image_index, (int(image_index.max()) + 1 if images is None and P else int(images or 0))
+
+
+def render_color(poses, vertices, faces, colors, K, size, device=None, image_index=None, images=None, pixel_center=0.0,
+                 near=0.01, ambient=0.5, light=(0.0, 0.0, 0.0), into=None):
+    """Shaded colour images of a triangle mesh with per-vertex colours: ``(color [I, H, W, 3] uint8, depth [I, H, W]
+    float32, skipped [P] int32)``.  Geometry, coverage and depth are ``render_depth``'s; ``colors`` [n, 3] uint8 come
+    back in the channel order they were given in.  ``image_index`` [P] (non-decreasing, values in [0, ``images``)) draws
+    several poses into one image; None draws pose p into image p.  Per pixel the nearest fragment wins, among equal
+    depths the lowest pose, then the lowest face; its colour is the perspective-correct mix of its vertices' colours
+    times ``min(ambient + 0.5 max(L . N, 0), 1)`` with the face normal N turned towards the camera and L the unit vector
+    from the surface point to ``light`` (camera space): the reference's fragment shader.  Background:
+    colour 0, depth 0.  ``into=(color, depth)``: accumulate over an earlier result (of any mesh); the arrays are not
+    modified, the updated copies are returned.  An earlier pixel gives way to a nearer fragment and also to one of
+    EXACTLY its depth (same float32 bits): the later call wins such a tie.  ``device=None``: the host twin; a torch device: bp_render_color on it.
+    The two are byte-identical."""
+    from . import _lib
+    poses = _poses34(poses)
+    vertices, faces = _mesh_args(vertices, faces)
+    colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+    if len(colors) != len(vertices):
+        raise ValueError("colors needs one row per vertex")
+    H, W = int(size[0]), int(size[1])
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
+    P = len(poses)
+    index, I = _image_index(image_index, images, P)
+    if into is not None:
+        color = np.array(into[0], dtype=np.uint8, order="C")
+        depth = np.array(into[1], dtype=np.float32, order="C")
+        I = len(depth) if images is None else I
+        if color.shape != (I, H, W, 3) or depth.shape != (I, H, W):
+            raise ValueError("into=(color, depth) must have the shapes [I, H, W, 3] and [I, H, W]")
+    else:
+        color, depth = np.zeros((I, H, W, 3), np.uint8), np.zeros((I, H, W), np.float32)
+    if P == 0:
+        return color, depth, np.zeros(0, np.int32)
+    acc = int(into is not None)
+    if device is None:
+        skipped = np.empty(P, np.int32)
+        _lib.check(_lib.lib().bp_render_color_host(_lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces),
+                                                   len(faces), _lib.ptr(colors), _lib.ptr(index), I, _lib.ptr(Kf), H, W,
+                                                   float(pixel_center), float(near), float(ambient), _lib.ptr(lt), acc,
+                                                   _lib.ptr(color), _lib.ptr(depth), _lib.ptr(skipped)))
+        return color, depth, skipped
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_colors = torch.from_numpy(colors).to(dev)
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_color, d_depth = torch.from_numpy(color).to(dev), torch.from_numpy(depth).to(dev)
+        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().bp_render_color(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces),
+                                              _lib.ptr(d_colors), _lib.ptr(d_poses), P, _lib.ptr(index), I, _lib.ptr(Kf), H, W,
+                                              float(pixel_center), float(near), float(ambient), _lib.ptr(lt), acc,
+                                              _lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_skipped),
+                                              torch.cuda.current_stream(dev).cuda_stream))
+        return d_color.cpu().numpy(), d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+
+
+# Model3D._compute_bbox of the reference (utils/model.py:50-72): the corners of the axis-aligned box, x outermost, then
+# z, then y, min before max; their colours; the 12 edges are csrc/raster_color_math.inc rc_box_edge
+BOX_CORNER_COLORS = ((1.0, 0.0, 0.0), (1.0, 1.0, 0.0), (0.0, 1.0, 0.0), (0.0, 1.0, 1.0),
+                     (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), (0.5, 0.0, 0.5), (0.0, 0.5, 0.5))
+
+
+def box_corners(vertices):
+    """The 8 corners [8, 3] of the axis-aligned bounding box of ``vertices`` in the reference's order."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    return np.array([[(lo, hi)[k >> 2 & 1][0], (lo, hi)[k & 1][1], (lo, hi)[k >> 1 & 1][2]] for k in range(8)])
+
+
+def colors_u8(colors):
+    """float colours in [0, 1] -> uint8, rounded to nearest."""
+    return np.clip(np.floor(np.asarray(colors, dtype=np.float64) * 255.0 + 0.5), 0, 255).astype(np.uint8)
+
+
+def draw_boxes(color, poses, corners, K, corner_colors=None, device=None, image_index=None, pixel_center=0.0, near=0.01):
+    """The 12 edges of the box with object-frame ``corners`` [8, 3] (box_corners) at ``poses``, one pixel wide over
+    ``color`` [I, H, W, 3] uint8, no depth test; returns the drawn copy.  ``corner_colors`` [8, 3] uint8 (default: the
+    reference's, as RGB); an edge mixes its two corners' colours.  An edge crossing z = ``near`` is shortened, one wholly
+    behind dropped; where edges overlap the highest (pose, edge) wins.  ``device`` as render_color; byte-identical."""
+    from . import _lib
+    poses = _poses34(poses)
+    color = np.array(color, dtype=np.uint8, order="C")
+    if color.ndim != 4 or color.shape[3] != 3:
+        raise ValueError("color must be [I, H, W, 3]")
+    I, H, W = color.shape[:3]
+    corners = np.ascontiguousarray(corners, dtype=np.float64).reshape(8, 3)
+    cc = np.ascontiguousarray(colors_u8(BOX_CORNER_COLORS) if corner_colors is None else corner_colors, dtype=np.uint8).reshape(8, 3)
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    P = len(poses)
+    if P == 0:
+        return color
+    index, _ = _image_index(image_index, I, P)
+    if device is None:
+        _lib.check(_lib.lib().bp_draw_boxes_host(_lib.ptr(poses), P, _lib.ptr(corners), _lib.ptr(cc), _lib.ptr(index), I,
+                                                 _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(color)))
+        return color
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_corners, d_cc = torch.from_numpy(corners).to(dev), torch.from_numpy(cc).to(dev)
+        d_color = torch.from_numpy(color).to(dev)
+        _lib.check(_lib.lib().bp_draw_boxes(_lib.ptr(d_poses), P, _lib.ptr(d_corners), _lib.ptr(d_cc), _lib.ptr(index), I,
+                                            _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(d_color),
+                                            torch.cuda.current_stream(dev).cuda_stream))
+        return d_color.cpu().numpy()
+
+
+def overlay(frames, color, depth, alpha=128, device=None):
+    """``frames`` [I, H, W, 3] uint8 with the render (``color``, ``depth`` of render_color) blended over them where
+    depth > 0: ``(alpha color + (256 - alpha) frame + 128) >> 8``; alpha 256 pastes.  ``device`` as render_color."""
+    from . import _lib
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    color = np.ascontiguousarray(color, dtype=np.uint8)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if frames.ndim != 4 or frames.shape[3] != 3 or color.shape != frames.shape or depth.shape != frames.shape[:3]:
+        raise ValueError("frames and color must be [I, H, W, 3], depth [I, H, W]")
+    I, H, W = depth.shape
+    if I == 0:
+        return frames.copy()
+    if device is None:
+        out = np.empty_like(frames)
+        _lib.check(_lib.lib().bp_overlay_host(_lib.ptr(frames), _lib.ptr(color), _lib.ptr(depth), I, H, W, int(alpha),
+                                              _lib.ptr(out)))
+        return out
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_frames, d_color = torch.from_numpy(frames).to(dev), torch.from_numpy(color).to(dev)
+        d_depth = torch.from_numpy(depth).to(dev)
+        d_out = torch.empty_like(d_frames)
+        _lib.check(_lib.lib().bp_overlay(_lib.ptr(d_frames), _lib.ptr(d_color), _lib.ptr(d_depth), I, H, W, int(alpha),
+                                         _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy()
 
 
 def vsd_masks(depth_test, depth_gt, depth_est, K, delta, pixel_center=0.0):
@@ -870,6 +1051,17 @@ class Model3D:
 
     def load(self, path, demean=False, scale=1.0):
         self.vertices = load_ply_vertices(path) * scale
+
+    def load_mesh(self, path, scale=1.0):
+        """What the renderer (betapose_amd/renderer.py) draws, which ``load`` does not read: ``indices`` [F, 3], ``colors``
+        [n, 3] floats in [0, 1] (RGB as the file has them, 0.5 without) and ``bb``, the 8 box corners of
+        ``_compute_bbox`` (utils/model.py:50-64), next to ``vertices``."""
+        v, f, c = load_ply_colored_mesh(path)
+        self.vertices = v * scale
+        self.indices = f
+        self.colors = c.astype(np.float64) / 255.0
+        self.bb = box_corners(self.vertices)
+        self.bb_colors = np.array(BOX_CORNER_COLORS)
 
     def refine(self, total_kp=30, save=False, save_path="test.ply"):
         self.vertices = refine_keypoints(self.vertices, total_kp)

@@ -25,8 +25,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--inp_dim', dest='inp_dim', type=str, default='416')
     p.add_argument('--conf', dest='confidence', type=float, default=0.01)
     p.add_argument('--nms', dest='nms_thesh', type=float, default=0.6)
-    p.add_argument('--save_img', default=False, action='store_true')
-    p.add_argument('--vis', default=False, action='store_true')
+    p.add_argument('--save_img', default=False, action='store_true',
+                   help='write <outdir>/vis/<imgname>.png: the frame with the estimated pose(s) drawn as shaded mesh and '
+                        '3-D box, the ground-truth box in green')
+    p.add_argument('--vis', default=False, action='store_true',
+                   help='accepted for the reference command lines and unused: there is no display, use --save_img')
     p.add_argument('--format', type=str, default=None)
     p.add_argument('--detbatch', type=int, default=1)
     p.add_argument('--posebatch', type=int, default=80)

@@ -111,6 +111,29 @@ def refine_scored_poses(obj_id, final_result, gt_frames, model_vertices, depth_i
     return m
 
 
+def render_model(base, obj_id, kp3d=None):
+    """What --save_img draws for an object: its coloured mesh in metres, or without a dataset a grey box around the key
+    points."""
+    from betapose_amd import renderer
+    if base is None:
+        return renderer.BoxModel(kp3d)
+    model = metrics.Model3D()
+    model.load_mesh(os.path.join(base, "models", "obj_%02d.ply" % obj_id), scale=0.001)
+    return model
+
+
+def save_images(args, obj_id, final_result, gt_frames, kp3d, cam_K, device):
+    """--save_img: <outdir>/vis/<imgname>.png, the frame with the estimated pose's mesh at alpha 128, its 3-D box and the
+    ground-truth box in green (betapose_amd/renderer.py save_pose_images), rendered on ``device`` a batch of frames at a
+    time."""
+    from betapose_amd import renderer
+    t0 = time.time()
+    model = render_model(None if gt_frames is None else args.sixd_base, obj_id, kp3d)
+    n = renderer.save_pose_images([{"model": model, "results": final_result, "gt": gt_frames}], args.inputpath,
+                                  args.outputpath, cam_K, device, all_instances=args.all_instances)
+    print("Saved %d images to %s (%.1f frames/sec)" % (n, os.path.join(args.outputpath, "vis"), n / max(time.time() - t0, 1e-9)))
+
+
 def synthetic_depth_inputs(final_result, kp3d, cam_K, size, device):
     """--synthetic --vsd / --refine_depth: a closed loop that only shows the path runs.  The mesh is the bounding box of
     the synthetic key points, the ground truth is each frame's own estimated pose and its depth image is rendered from
@@ -344,6 +367,8 @@ def main():
         elif (args.vsd or args.refine_depth is not None) and args.synthetic:
             print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, synth_size, torch.device("cuda", local), vsd=args.vsd,
                                 refine_iterations=args.refine_depth)
+        if args.save_img:   # after the refinement: cam_R / cam_t hold the poses the lines above were scored on
+            save_images(args, obj_id, final_result, gt_frames, kp3d, cam_K, torch.device("cuda", local))
     bpd.finalize()
 
 

@@ -44,6 +44,9 @@
  *   bp_pose_errors_sym     no reference counterpart: the BOP errors MSSD and MSPD over an object's symmetry set
  *   bp_render_depth, bp_render_depth_host
  *                          Renderer.render's depth image (OpenGL through vispy)   utils/renderer.py
+ *   bp_render_color, bp_draw_boxes, bp_overlay (and their _host twins)
+ *                          Renderer.draw_model / draw_boundingbox / finish and      utils/renderer.py:137-181
+ *                          draw_detections_3D's paste over the frame                utils/utils.py:269-301
  *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
  *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
  *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
@@ -278,6 +281,53 @@ int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, con
                     int H, int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, void* stream);
 int bp_render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
                          int H, int W, double pixel_center, double near_z, float* depth, int* skipped);
+/* Colour images of a triangle mesh with per-vertex colours at P poses, several poses per image.  Geometry, coverage and
+ * depth are bp_render_depth's, unchanged.  d_colors [n][3] uint8 (channel order is the caller's); image_index HOST [P]
+ * int32, the image each pose is drawn into, non-decreasing with values in [0, I), or NULL for pose p -> image p (then
+ * I == P).  Of the fragments of a pixel the one with the smallest 64-bit key (f32 depth bits << 32) | (p * F + f) wins:
+ * nearest first, then the lowest pose slot, then the lowest face; P * F <= 2^32 - 2.  The winner's colour: with A, B, C
+ * the face's camera-space vertices in the face's own order, X the point of the pixel's ray at the fragment's f64 depth
+ * and n = (B - A) x (C - A), the weights ((B - X) x (C - X)) . n / n.n (and cyclic) are clamped to [0, 1] and normalised
+ * (1/3 each for a degenerate face) and mix the vertex colours in f64; N = +-n / |n| facing the camera,
+ * L = (light - X) / |light - X| (0 at the light), light_w = min(ambient + 0.5 max(L . N, 0), 1); a channel is
+ * min(255, floor(light_w c + 0.5)).  light: host [3], camera space.  d_color [I][H][W][3] uint8 (0 where nothing is
+ * drawn), d_depth [I][H][W] f32 (0 where nothing is drawn; equal to bp_render_depth's bit for bit when every image
+ * holds one pose), d_skipped [P] as bp_render_depth.  accumulate != 0: d_color and d_depth hold an earlier call's
+ * result (of any mesh) on entry; a pixel with depth > 0 takes part with the key (depth bits << 32) | 0xFFFFFFFF and
+ * keeps its colour and depth unless a fragment with a smaller key arrives.  accumulate == 0: every byte of both is
+ * written.  Images and poses are processed in chunks that keep the workspaces under 256 MB; the result does not depend
+ * on it and is the same from run to run.  bp_render_color_host is the same on host memory, without a GPU, byte-identical;
+ * it refuses a face index outside [0, n).  bp_render_color synchronises `stream`. */
+int bp_render_color(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
+                    const double* d_poses, int P, const int* image_index, int I, const double* K, int H, int W,
+                    double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                    unsigned char* d_color, float* d_depth, int* d_skipped, void* stream);
+int bp_render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                         const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
+                         double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                         unsigned char* color, float* depth, int* skipped);
+/* The 12 edges of a 3-D bounding box at P poses, drawn one pixel wide over d_color [I][H][W][3] uint8 without a depth
+ * test (Renderer.draw_boundingbox, utils/renderer.py).  d_corners [8][3] f64 object frame in the order of
+ * Model3D._compute_bbox (x outermost, then z, then y, min before max), d_corner_colors [8][3] uint8; image_index, I,
+ * K, pixel_center as bp_render_color.  An edge is clipped against z = near_z (dropped when wholly behind, shortened
+ * when it crosses), projected, clipped to +-2^20 px, snapped to 1/256 px and stepped along its major axis over the
+ * pixel positions inside the image; a pixel's colour mixes the two corner colours linearly by its position along the
+ * snapped edge, in integers.  Where edges overlap the highest (pose slot, edge) wins.  P <= 2^24.  bp_draw_boxes_host is
+ * the same on host memory, byte-identical.  bp_draw_boxes synchronises `stream`. */
+int bp_draw_boxes(const double* d_poses, int P, const double* d_corners, const unsigned char* d_corner_colors,
+                  const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                  unsigned char* d_color, void* stream);
+int bp_draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
+                       const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                       unsigned char* color);
+/* A render over frames: where depth > 0, out = (alpha color + (256 - alpha) frame + 128) >> 8 per channel, elsewhere
+ * out = frame; alpha in 0 .. 256 (256: the reference's out[mask] = col[mask], utils/utils.py:299-300).  frames, color,
+ * out [I][H][W][3] uint8, depth [I][H][W] f32; out may be frames.  bp_overlay is enqueued on `stream` and does not
+ * synchronise it. */
+int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, const float* d_depth, int I, int H, int W,
+               int alpha, unsigned char* d_out, void* stream);
+int bp_overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W,
+                    int alpha, unsigned char* out);
 /* BOP's Visible Surface Discrepancy (step cost, normalised by the diameter, visibility mode bop19) of P pose pairs of
  * one mesh: both poses of a pair are rendered as bp_render_depth does and compared with the test depth image
  * d_test_index[p] of d_depth_test [T][H][W] uint16 (depth = raw * depth_scale in pose units, 0 = missing).  taus: host,

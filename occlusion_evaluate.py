@@ -188,6 +188,7 @@ def main():
         allpose = bpd.gather_records(mine_poses.view(np.float32), mine, n_units, max_local=most)
 
     if rank == 0:
+        drawn = []      # --save_img: every object's scored results, drawn into one image per frame at the end
         for oi, o in enumerate(obj_ids):
             frames_gt, model, kp3d, diameter, cam = gt[o]
             final_result = []
@@ -226,6 +227,13 @@ def main():
                 evaluate.print_vsd_metrics(args.sixd_base, o, 2, final_result, frames_gt, model, cam, diameter,
                                            torch.device("cuda", local), match_instances=args.all_instances,
                                            depth_inputs=depth_inputs)
+            if args.save_img:
+                drawn.append({"model": evaluate.render_model(args.sixd_base, o), "results": final_result, "gt": frames_gt})
+        if args.save_img:
+            from betapose_amd import renderer
+            n = renderer.save_pose_images(drawn, args.inputpath, args.outputpath, synth.CAM_K, torch.device("cuda", local),
+                                          all_instances=args.all_instances)
+            print("Saved %d images to %s" % (n, os.path.join(args.outputpath, "vis")))
     bpd.finalize()
 
 
