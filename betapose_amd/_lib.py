@@ -133,6 +133,18 @@ PROTOTYPES = {
     "bp_overlay_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                 C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "bp_annotate_keypoints": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, C.c_int,
+                                        vp, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "bp_annotate_keypoints_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp,
+                                             C.c_int, vp, C.c_double, C.c_double, vp, vp, vp]),
+    "bp_mask_boxes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, vp, C.c_double, vp, vp, vp]),
+    "bp_mask_boxes_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, vp, C.c_double, vp, vp]),
+    "bp_vertex_boxes": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+    "bp_vertex_boxes_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
+    "bp_kpd_targets": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp,
+                                 vp]),
+    "bp_kpd_targets_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp,
+                                      vp]),
     "bp_icp_normal_equations": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp]),
     "bp_icp_normal_equations_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,

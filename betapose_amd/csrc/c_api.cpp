@@ -10,6 +10,7 @@
 #include <sstream>
 #include <vector>
 
+#include "annotate.h"
 #include "engine.h"
 #include "frame_chain.h"
 #include "frame_io.h"
@@ -851,6 +852,146 @@ int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const
     bp::launch_vsd_finish(acc, d_test_index, T, P, n_tau, d_err, d_counts, s);
     BP_HIP(hipGetLastError());
     BP_HIP(hipStreamSynchronize(s));   // the renders live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+// ---- the key-point annotator (annotate.hip / annotate_host.cpp)
+static void annot_check_image(int P, int H, int W) {
+    BP_CHECK(P > 0 && H > 0 && W > 0, "P, H and W must be positive");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+}
+// scene depth and scene index come together; every index (host copy) must name one of the T images
+static void annot_check_scene(const void* scene_depth, const void* scene_index, const int* host_index, int P, int T) {
+    BP_CHECK((scene_depth != nullptr) == (scene_index != nullptr), "scene_depth and scene_index are given together");
+    if (!scene_depth) return;
+    BP_CHECK(T > 0, "T must be positive");
+    for (int p = 0; p < P; ++p) BP_CHECK(host_index[p] >= 0 && host_index[p] < T, "a scene index lies outside [0, T)");
+}
+// the device calls read the index back to check it before any kernel uses it
+static void annot_check_scene_device(const float* d_scene_depth, const int* d_scene_index, int P, int T, hipStream_t s) {
+    std::vector<int> idx;
+    if (d_scene_depth && d_scene_index) {
+        idx.resize(P);
+        BP_HIP(hipMemcpyAsync(idx.data(), d_scene_index, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s));
+        BP_HIP(hipStreamSynchronize(s));
+    }
+    annot_check_scene(d_scene_depth, d_scene_index, idx.data(), P, T);
+}
+
+int bp_annotate_keypoints_host(const double* poses, int P, const double* kp, int Kp, const double* K, int H, int W,
+                               double pixel_center, double near_z, const float* model_depth, const float* scene_depth, int T,
+                               const int* scene_index, double self_tol, double delta, double* xy, double* z,
+                               unsigned char* flags) {
+    BP_TRY
+    BP_CHECK(poses && kp && K && xy && z && flags, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(Kp > 0 && (long long)P * Kp < (1ll << 31), "Kp must be positive and P * Kp below 2^31");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
+    bp::annotate_keypoints_host(poses, P, kp, Kp, K, H, W, pixel_center, near_z, model_depth, scene_depth, scene_index, self_tol,
+                                delta, xy, z, flags);
+    return 0;
+    BP_CATCH
+}
+
+int bp_annotate_keypoints(const double* d_poses, int P, const double* d_kp, int Kp, const double* K, int H, int W,
+                          double pixel_center, double near_z, const float* d_model_depth, const float* d_scene_depth, int T,
+                          const int* d_scene_index, double self_tol, double delta, double* d_xy, double* d_z,
+                          unsigned char* d_flags, void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_kp && K && d_xy && d_z && d_flags, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(Kp > 0 && (long long)P * Kp < (1ll << 31), "Kp must be positive and P * Kp below 2^31");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, s);
+    bp::launch_annotate_keypoints(d_poses, P, d_kp, Kp, K, H, W, pixel_center, near_z, d_model_depth, d_scene_depth,
+                                  d_scene_index, self_tol, delta, d_xy, d_z, d_flags, s);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_mask_boxes_host(const float* depth, int P, int H, int W, const double* K, double pixel_center, const float* scene_depth,
+                       int T, const int* scene_index, double delta, int* boxes, int* counts) {
+    BP_TRY
+    BP_CHECK(depth && K && boxes && counts, "null argument");
+    annot_check_image(P, H, W);
+    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
+    bp::mask_boxes_host(depth, P, H, W, K, pixel_center, scene_depth, scene_index, delta, boxes, counts);
+    return 0;
+    BP_CATCH
+}
+
+int bp_mask_boxes(const float* d_depth, int P, int H, int W, const double* K, double pixel_center, const float* d_scene_depth,
+                  int T, const int* d_scene_index, double delta, int* d_boxes, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(d_depth && K && d_boxes && d_counts, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(P < (1 << 28), "P must be below 2^28");
+    hipStream_t s = (hipStream_t)stream;
+    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, s);
+    bp::Arena a;
+    int* acc = (int*)a.alloc_bytes((size_t)P * 2 * bp::ANNOT_BOX_INTS * sizeof(int));
+    bp::launch_mask_boxes(d_depth, P, H, W, K, pixel_center, d_scene_depth, d_scene_index, delta, acc, d_boxes, d_counts, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+int bp_vertex_boxes_host(const double* poses, int P, const double* vertices, int n, const double* K, int H, int W, int* boxes) {
+    BP_TRY
+    BP_CHECK(poses && vertices && K && boxes, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(n > 0, "n must be positive");
+    bp::vertex_boxes_host(poses, P, vertices, n, K, H, W, boxes);
+    return 0;
+    BP_CATCH
+}
+
+int bp_vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n, const double* K, int H, int W, int* d_boxes,
+                    void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_vertices && K && d_boxes, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(n > 0 && P < (1 << 28), "n must be positive and P below 2^28");
+    hipStream_t s = (hipStream_t)stream;
+    bp::Arena a;
+    int* acc = (int*)a.alloc_bytes((size_t)P * bp::ANNOT_BOX_INTS * sizeof(int));
+    bp::launch_vertex_boxes(d_poses, P, d_vertices, n, K, H, W, acc, d_boxes, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
+    return 0;
+    BP_CATCH
+}
+
+static void annot_check_targets(int B, int Kp, int inpH, int inpW, int resH, int resW, int size) {
+    BP_CHECK(B > 0 && Kp > 0 && inpH > 0 && inpW > 0 && resH > 0 && resW > 0, "B, Kp and the resolutions must be positive");
+    BP_CHECK(size >= 1 && size % 2 == 1 && size <= 1025, "the Gaussian table needs an odd size of at most 1025");
+    // (the kernel indexes rows in groups of four floats: the width counts rounded up to a multiple of 4)
+    BP_CHECK((long long)B * Kp * resH * ((resW + 3) / 4 * 4) < (1ll << 31), "the target tensor must hold fewer than 2^31 values");
+}
+
+int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
+                        int resW, const float* g, int size, float* out, int* centres, float* set_mask) {
+    BP_TRY
+    BP_CHECK(parts && ul && br && g && out && centres, "null argument");
+    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
+    bp::kpd_targets_host(parts, ul, br, B, Kp, inpH, inpW, resH, resW, g, size, out, centres, set_mask);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
+                   int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream) {
+    BP_TRY
+    BP_CHECK(d_parts && d_ul && d_br && d_g && d_out && d_centres, "null argument");
+    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
+    bp::launch_kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask,
+                           (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
 }

@@ -48,6 +48,14 @@
  *                          Renderer.draw_model / draw_boundingbox / finish and      utils/renderer.py:137-181
  *                          draw_detections_3D's paste over the frame                utils/utils.py:269-301
  *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
+ *   bp_annotate_keypoints, bp_vertex_boxes (and their _host twins)
+ *                          sinobj.apply_pose / project_all / project_kp     2_keypoint_annotator/annotate_keypoint.py:108-175
+ *                          plus the visibility flags the annotator meant to write (kp_label's docstring, wrap_kp)
+ *   bp_mask_boxes, bp_mask_boxes_host
+ *                          get_bbox_from_mask over a render, and over its BOP-visible part    utils/utils.py:136-151
+ *   bp_kpd_targets, bp_kpd_targets_host
+ *                          generateSampleBox's label half: transformBox +    train_KPD/src/utils/pose.py:113-126
+ *                          drawGaussian per part                               train_KPD/src/utils/img.py:61-110
  *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
  *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
@@ -339,6 +347,53 @@ int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const
                   const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
                   const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
                   double near_z, int chunk, double* d_err, int* d_counts, void* stream);
+/* Key-point annotation of P poses x Kp model points (stage 2 of the reference).  Per pair: X = R m + t,
+ * u = (fx X + s Y) / Z + cx, v = fy Y / Z + cy (K = [fx s cx; 0 fy cy; 0 0 1]), and the pixel the projection falls in,
+ * (floor(u - pixel_center + 0.5), floor(v - pixel_center + 0.5)).  d_xy [P][Kp][2] f64 = (u, v), d_z [P][Kp] f64 = Z,
+ * d_flags [P][Kp] uint8, bits: 1 FRONT (Z >= near_z); 2 IN_IMAGE (that pixel exists); 4 SELF_VISIBLE (FRONT and IN_IMAGE,
+ * and not: the pose's own render covers the pixel (D > 0) with D < Z - self_tol); 8 SCENE_VISIBLE (FRONT and IN_IMAGE,
+ * and the scene depth S at the pixel is 0 = missing or Z - S <= delta); 16 SCENE_KNOWN (S > 0).  d_model_depth
+ * [P][H][W] f32 is bp_render_depth's output for the same poses and pixel_center, or NULL; d_scene_depth [T][H][W] f32 in
+ * pose units with d_scene_index [P], or both NULL.  A depth input that is not given leaves its visibility bit set for
+ * every FRONT and IN_IMAGE point.  A point that is not FRONT gets xy = (-1, -1), z = Z and flags 0.  A scene index
+ * outside [0, T) is an error (the device call reads the index back to check it, which synchronises `stream` once; its
+ * kernel is then enqueued on `stream` without another synchronisation).  bp_annotate_keypoints_host is the same on host
+ * memory, without a GPU, bit-identical. */
+int bp_annotate_keypoints(const double* d_poses, int P, const double* d_kp, int Kp, const double* K, int H, int W,
+                          double pixel_center, double near_z, const float* d_model_depth, const float* d_scene_depth, int T,
+                          const int* d_scene_index, double self_tol, double delta, double* d_xy, double* d_z,
+                          unsigned char* d_flags, void* stream);
+int bp_annotate_keypoints_host(const double* poses, int P, const double* kp, int Kp, const double* K, int H, int W,
+                               double pixel_center, double near_z, const float* model_depth, const float* scene_depth, int T,
+                               const int* scene_index, double self_tol, double delta, double* xy, double* z,
+                               unsigned char* flags);
+/* Boxes of P depth images d_depth [P][H][W] f32 (0 = nothing): d_boxes [P][2][4] int32, box 0 around the covered pixels
+ * (depth > 0), box 1 around those of them that are visible by bp_vsd_errors' rule for the ground truth (distances along
+ * the pixel's ray; visible when not more than delta behind the scene surface, or the scene depth is 0 = missing), each
+ * (xmin, xmax, ymin, ymax) inclusive and -1 x4 when empty; d_counts [P][2] int32 the two pixel counts.  The scene depth
+ * is given as in bp_annotate_keypoints; without it box 1 equals box 0.  Integer reductions only: bit-identical from run
+ * to run and to bp_mask_boxes_host.  Synchronises `stream`. */
+int bp_mask_boxes(const float* d_depth, int P, int H, int W, const double* K, double pixel_center, const float* d_scene_depth,
+                  int T, const int* d_scene_index, double delta, int* d_boxes, int* d_counts, void* stream);
+int bp_mask_boxes_host(const float* depth, int P, int H, int W, const double* K, double pixel_center, const float* scene_depth,
+                       int T, const int* scene_index, double delta, int* boxes, int* counts);
+/* The reference's mask_bbox of P poses of n vertices: every vertex is projected as above and splatted into pixel
+ * (int(u), int(v)), truncated toward zero; d_boxes [P][4] int32 = (xmin, xmax, ymin, ymax) over the vertices with
+ * 0 < int(u) < W and 0 < int(v) < H (the reference's strict bounds), -1 x4 when there is none.  Synchronises `stream`. */
+int bp_vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n, const double* K, int H, int W, int* d_boxes,
+                    void* stream);
+int bp_vertex_boxes_host(const double* poses, int P, const double* vertices, int n, const double* K, int H, int W, int* boxes);
+/* Heat-map targets of B samples x Kp parts (generateSampleBox, 'coco' branch): d_parts [B][Kp][2] f64 image
+ * coordinates, windows d_ul, d_br [B][2] f32, d_g [size][size] f32 the Gaussian patch (size odd; drawGaussian's
+ * 6 sigma + 1).  A part is drawn iff x > 0 and it lies strictly inside its window; its centre is transformBox's (float32
+ * arithmetic, round half to even; only resH scales, as there); d_out [B][Kp][resH][resW] f32 holds d_g clipped to the
+ * map about the centre and 0 elsewhere, d_centres [B][Kp][2] int32 the centre, (-1, -1) for a part that is not drawn;
+ * d_set_mask (same shape as d_out, or NULL) is filled with ones.  Every element is written.  Enqueued on `stream`
+ * without synchronising it. */
+int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
+                   int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream);
+int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
+                        int resW, const float* g, int size, float* out, int* centres, float* set_mask);
 /* Depth refinement of P estimated poses of one mesh: projective point-to-plane ICP of the mesh's render (as
  * bp_render_depth draws it) against the test depth image d_test_index[p] of d_depth_test [T][H][W] uint16 (depth =
  * raw * depth_scale in pose units, 0 = missing).  Up to `iterations` times: render at the current pose; every pixel
