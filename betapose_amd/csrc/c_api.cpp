@@ -1,45 +1,19 @@
-// extern "C" boundary of libbetapose_hip.so -- see include/betapose_hip.h.
-#include "../../include/betapose_hip.h"
-
-#include <algorithm>
-#include <cmath>
+// extern "C" boundary of libbetapose_hip.so -- see include/betapose_hip.h.  This unit: version, devices, streams, the
+// engines, the stand-alone stage ops and the per-frame device chains.  The other subsystems' entry points are
+// c_api_conv.cpp (the single-layer convolution harness), c_api_pose.cpp (pose solvers), c_api_eval.cpp (evaluation tools)
+// and c_api_io.cpp (frame input).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <memory>
 #include <sstream>
 #include <vector>
 
-#include "annotate.h"
-#include "engine.h"
+#include "c_api_util.h"
 #include "frame_chain.h"
-#include "frame_io.h"
-#include "icp.h"
-#include "pose_tail.h"
-#include "raster.h"
 
+// bp_last_error()'s text: the one such string of the library (c_api_util.h)
 static thread_local std::string g_err;
-
-#define BP_TRY try {
-#define BP_CATCH                                   \
-    }                                              \
-    catch (const std::exception& e) {              \
-        g_err = e.what();                          \
-        return -1;                                 \
-    }                                              \
-    catch (...) {                                  \
-        g_err = "unknown error";                   \
-        return -1;                                 \
-    }
-
-struct bp_yolo {
-    std::unique_ptr<bp::YoloNet> net;
-    int device;
-};
-struct bp_kpd {
-    std::unique_ptr<bp::KpdNet> net;
-    int device;
-};
+void bp::set_last_error(const char* text) { g_err = text; }
 
 // The per-frame device chains.  What they share -- the frame's graph, the latency mode's re-run, the resize stage and the
 // pose solver -- is frame_chain.h; `engines` lists the detector, then the key-point engine(s).
@@ -577,737 +551,11 @@ int bp_resize_bicubic(const uint8_t* d_in, int batch, int H, int W, int oh, int 
     BP_CATCH
 }
 
-int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* K, int want,
-                   double* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_gt && d_est && d_out, "null argument");
-    BP_CHECK(n > 0 && P > 0, "n and P must be positive");
-    BP_CHECK(want >= 1 && want <= 7, "want must be a non-empty mask of 1 (ADD), 2 (ADD-S), 4 (2-D)");
-    BP_CHECK(K || !(want & 4), "K is required for the 2-D projection error");
-    hipStream_t s = (hipStream_t)stream;
-    bp::Arena a;
-    double* partial = (double*)a.alloc_bytes((size_t)P * bp::pose_error_blocks(n) * 3 * sizeof(double));
-    bp::launch_pose_errors(d_model, n, d_gt, d_est, P, K, want, partial, d_out, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // partials live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym,
-                       int S, const double* K, int want, double* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_gt && d_est && d_sym && d_out, "null argument");
-    BP_CHECK(n > 0 && P > 0 && S > 0, "n, P and S must be positive");
-    BP_CHECK(want >= 1 && want <= 3, "want must be a non-empty mask of 1 (MSSD), 2 (MSPD)");
-    BP_CHECK(K || !(want & 2), "K is required for the projection distance (MSPD)");
-    hipStream_t s = (hipStream_t)stream;
-    bp::Arena a;
-    double* scratch = (double*)a.alloc_bytes(bp::pose_errors_sym_scratch_bytes(n, P, S));
-    bp::launch_pose_errors_sym(d_model, n, d_gt, d_est, P, d_sym, S, K, want, scratch, d_out, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the per-symmetry maxima live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-// what the three rasteriser calls check alike
-static void raster_check_sizes(int n, int F, int P, int H, int W, double near_z) {
-    BP_CHECK(n > 0 && F > 0 && P > 0 && H > 0 && W > 0, "n, F, P, H and W must be positive");
-    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
-    BP_CHECK(near_z > 0.0, "near must be positive");
-}
-constexpr size_t RASTER_WS_BYTES = (size_t)256 << 20;      // what the chunked calls keep their workspaces under
-
-int bp_render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
-                         int H, int W, double pixel_center, double near_z, float* depth, int* skipped) {
-    BP_TRY
-    BP_CHECK(poses && vertices && faces && K && depth && skipped, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    BP_CHECK(bp::render_depth_host(poses, P, vertices, n, faces, F, K, H, W, pixel_center, near_z, depth, skipped) == 0,
-             "a face index lies outside [0, n)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
-                    int H, int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_faces && d_poses && K && d_depth && d_skipped, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W;
-    size_t chunk = RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1);
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)P));
-    bp::Arena a;
-    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)chunk));
-    BP_HIP(hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)P * HW, s));   // +inf
-    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
-    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
-        const int c = (int)std::min(chunk, (size_t)P - p0);
-        bp::launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, c, nullptr, 0, K, H, W, pixel_center, near_z, ws,
-                          (uint32_t*)d_depth + p0 * HW, d_skipped + p0, s);
-    }
-    bp::launch_raster_finish((uint32_t*)d_depth, (size_t)P * HW, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the vertex workspace lives in a local arena
-    return 0;
-    BP_CATCH
-}
-
-// what the colour renderer's calls check of image_index (host, may be NULL): pose p -> image p needs I == P, otherwise
-// non-decreasing values in [0, I), which lets a call split its work into pose ranges without splitting an image
-static void raster_check_image_index(const int* image_index, int P, int I) {
-    BP_CHECK(I > 0, "I must be positive");
-    if (!image_index) {
-        BP_CHECK(I == P, "without image_index the call needs I == P");
-        return;
-    }
-    for (int p = 0; p < P; ++p) {
-        BP_CHECK(image_index[p] >= 0 && image_index[p] < I, "image_index must lie in [0, I)");
-        BP_CHECK(p == 0 || image_index[p] >= image_index[p - 1], "image_index must be non-decreasing");
-    }
-}
-
-// poses [*p0, return) of the call go to images [i0, i1); *p0 on entry: the first pose not yet consumed
-static int raster_pose_range(const int* image_index, int P, int i1, int p0) {
-    if (!image_index) return std::min(P, i1);
-    int p = p0;
-    while (p < P && image_index[p] < i1) ++p;
-    return p;
-}
-
-int bp_render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
-                         const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
-                         double pixel_center, double near_z, double ambient, const double* light, int accumulate,
-                         unsigned char* color, float* depth, int* skipped) {
-    BP_TRY
-    BP_CHECK(poses && vertices && faces && colors && K && light && color && depth && skipped, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    raster_check_image_index(image_index, P, I);
-    BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
-    BP_CHECK(bp::render_color_host(poses, P, vertices, n, faces, F, colors, image_index, I, K, H, W, pixel_center, near_z, ambient,
-                                   light, accumulate, color, depth, skipped) == 0,
-             "a face index lies outside [0, n)");   // (its scan comes before it touches anything)
-    return 0;
-    BP_CATCH
-}
-
-int bp_render_color(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
-                    const double* d_poses, int P, const int* image_index, int I, const double* K, int H, int W,
-                    double pixel_center, double near_z, double ambient, const double* light, int accumulate,
-                    unsigned char* d_color, float* d_depth, int* d_skipped, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_faces && d_colors && d_poses && K && light && d_color && d_depth && d_skipped, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    raster_check_image_index(image_index, P, I);
-    BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W;
-    // images in flight: 8 bytes of key per pixel; poses in flight: their vertex workspace; each under RASTER_WS_BYTES
-    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 8), (size_t)I));
-    const size_t pchunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1), (size_t)P));
-    bp::Arena a;
-    unsigned long long* keys = (unsigned long long*)a.alloc_bytes(ichunk * HW * 8);
-    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)pchunk));
-    int* d_index = nullptr;
-    if (image_index) {
-        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
-        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
-    const bp::ColorLight lt{ambient, light[0], light[1], light[2]};
-    int p0 = 0;
-    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
-        const int m = (int)std::min(ichunk, (size_t)I - i0);
-        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
-        bp::launch_color_clear(keys, d_depth + i0 * HW, accumulate, (size_t)m * HW, s);
-        for (int q0 = p0; q0 < p1; q0 += (int)pchunk) {
-            const int c = std::min((int)pchunk, p1 - q0);
-            bp::launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, K, pixel_center, near_z, ws, s);
-            bp::launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, K, H, W, pixel_center, near_z, keys,
-                                        d_skipped, s);
-        }
-        bp::launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, K, H, W, pixel_center, near_z, lt,
-                                 d_color + i0 * HW * 3, d_depth + i0 * HW, s);
-        p0 = p1;
-    }
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the keys and the vertex workspace live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-static void raster_check_boxes(int P, int I, int H, int W, double near_z) {
-    BP_CHECK(P > 0 && I > 0 && H > 0 && W > 0, "P, I, H and W must be positive");
-    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
-    BP_CHECK(P <= (1 << 24), "P must not exceed 2^24");
-    BP_CHECK(near_z > 0.0, "near must be positive");
-}
-
-int bp_draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
-                       const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
-                       unsigned char* color) {
-    BP_TRY
-    BP_CHECK(poses && corners && corner_colors && K && color, "null argument");
-    raster_check_boxes(P, I, H, W, near_z);
-    raster_check_image_index(image_index, P, I);
-    bp::draw_boxes_host(poses, P, corners, corner_colors, image_index, I, K, H, W, pixel_center, near_z, color);
-    return 0;
-    BP_CATCH
-}
-
-int bp_draw_boxes(const double* d_poses, int P, const double* d_corners, const unsigned char* d_corner_colors,
-                  const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
-                  unsigned char* d_color, void* stream) {
-    BP_TRY
-    BP_CHECK(d_poses && d_corners && d_corner_colors && K && d_color, "null argument");
-    raster_check_boxes(P, I, H, W, near_z);
-    raster_check_image_index(image_index, P, I);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W;
-    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 4), (size_t)I));
-    bp::Arena a;
-    uint32_t* ids = (uint32_t*)a.alloc_bytes(ichunk * HW * 4);
-    int* d_index = nullptr;
-    if (image_index) {
-        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
-        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    int p0 = 0;
-    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
-        const int m = (int)std::min(ichunk, (size_t)I - i0);
-        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
-        if (p1 > p0)
-            bp::launch_draw_boxes(d_poses, p0, p1 - p0, d_corners, d_corner_colors, d_index, (int)i0, m, K, H, W, pixel_center,
-                                  near_z, ids, d_color + i0 * HW * 3, s);
-        p0 = p1;
-    }
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the id planes live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-int bp_overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,
-                    unsigned char* out) {
-    BP_TRY
-    BP_CHECK(frames && color && depth && out, "null argument");
-    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
-    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
-    BP_CHECK(alpha >= 0 && alpha <= 256, "alpha must lie in 0 .. 256");
-    bp::overlay_host(frames, color, depth, I, H, W, alpha, out);
-    return 0;
-    BP_CATCH
-}
-
-int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, const float* d_depth, int I, int H, int W, int alpha,
-               unsigned char* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(d_frames && d_color && d_depth && d_out, "null argument");
-    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
-    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
-    BP_CHECK(alpha >= 0 && alpha <= 256, "alpha must lie in 0 .. 256");
-    hipStream_t s = (hipStream_t)stream;
-    bp::launch_overlay(d_frames, d_color, d_depth, (size_t)I * H * W, alpha, d_out, s);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
-                  const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
-                  const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
-                  double near_z, int chunk, double* d_err, int* d_counts, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_faces && d_gt && d_est && K && d_depth_test && d_test_index && taus && d_err && d_counts,
-             "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    BP_CHECK(T > 0, "T must be positive");
-    BP_CHECK(n_tau >= 1 && n_tau <= bp::VSD_MAX_TAUS, "n_tau must lie in 1 .. 16");
-    BP_CHECK(diameter > 0.0 && depth_scale > 0.0 && chunk >= 0, "diameter and depth_scale must be positive, chunk >= 0");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W;
-    size_t c = (size_t)chunk;
-    if (c == 0)   // both workspaces (2 c z-buffers, 2 c posed meshes) under RASTER_WS_BYTES
-        c = std::min(RASTER_WS_BYTES / (2 * HW * sizeof(float)), RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 2));
-    c = std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
-    bp::VsdTaus tv{};
-    for (int k = 0; k < n_tau; ++k) tv.tau[k] = taus[k];
-    bp::Arena a;
-    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(2 * c * HW * sizeof(uint32_t));
-    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)(2 * c)));
-    int* skipped = (int*)a.alloc_bytes(2 * c * sizeof(int));
-    int* acc = (int*)a.alloc_bytes((size_t)P * bp::VSD_ACC * sizeof(int));
-    BP_HIP(hipMemsetAsync(acc, 0, (size_t)P * bp::VSD_ACC * sizeof(int), s));
-    BP_HIP(hipMemsetAsync(skipped, 0, 2 * c * sizeof(int), s));
-    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
-        const int m = (int)std::min(c, (size_t)P - p0);
-        BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, 2 * (size_t)m * HW, s));   // +inf
-        bp::launch_raster(d_model, n, d_faces, F, d_gt + p0 * 12, m, d_est + p0 * 12, m, K, H, W, pixel_center, near_z, ws, zbuf,
-                          skipped, s);
-        bp::launch_vsd_reduce(zbuf, m, d_depth_test, T, d_test_index + p0, H, W, K, pixel_center, depth_scale, delta, tv, n_tau,
-                              diameter, acc + p0 * bp::VSD_ACC, s);
-    }
-    bp::launch_vsd_finish(acc, d_test_index, T, P, n_tau, d_err, d_counts, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the renders live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-// ---- the key-point annotator (annotate.hip / annotate_host.cpp)
-static void annot_check_image(int P, int H, int W) {
-    BP_CHECK(P > 0 && H > 0 && W > 0, "P, H and W must be positive");
-    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
-}
-// scene depth and scene index come together; every index (host copy) must name one of the T images
-static void annot_check_scene(const void* scene_depth, const void* scene_index, const int* host_index, int P, int T) {
-    BP_CHECK((scene_depth != nullptr) == (scene_index != nullptr), "scene_depth and scene_index are given together");
-    if (!scene_depth) return;
-    BP_CHECK(T > 0, "T must be positive");
-    for (int p = 0; p < P; ++p) BP_CHECK(host_index[p] >= 0 && host_index[p] < T, "a scene index lies outside [0, T)");
-}
-// the device calls read the index back to check it before any kernel uses it
-static void annot_check_scene_device(const float* d_scene_depth, const int* d_scene_index, int P, int T, hipStream_t s) {
-    std::vector<int> idx;
-    if (d_scene_depth && d_scene_index) {
-        idx.resize(P);
-        BP_HIP(hipMemcpyAsync(idx.data(), d_scene_index, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s));
-        BP_HIP(hipStreamSynchronize(s));
-    }
-    annot_check_scene(d_scene_depth, d_scene_index, idx.data(), P, T);
-}
-
-int bp_annotate_keypoints_host(const double* poses, int P, const double* kp, int Kp, const double* K, int H, int W,
-                               double pixel_center, double near_z, const float* model_depth, const float* scene_depth, int T,
-                               const int* scene_index, double self_tol, double delta, double* xy, double* z,
-                               unsigned char* flags) {
-    BP_TRY
-    BP_CHECK(poses && kp && K && xy && z && flags, "null argument");
-    annot_check_image(P, H, W);
-    BP_CHECK(Kp > 0 && (long long)P * Kp < (1ll << 31), "Kp must be positive and P * Kp below 2^31");
-    BP_CHECK(near_z > 0.0, "near must be positive");
-    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
-    bp::annotate_keypoints_host(poses, P, kp, Kp, K, H, W, pixel_center, near_z, model_depth, scene_depth, scene_index, self_tol,
-                                delta, xy, z, flags);
-    return 0;
-    BP_CATCH
-}
-
-int bp_annotate_keypoints(const double* d_poses, int P, const double* d_kp, int Kp, const double* K, int H, int W,
-                          double pixel_center, double near_z, const float* d_model_depth, const float* d_scene_depth, int T,
-                          const int* d_scene_index, double self_tol, double delta, double* d_xy, double* d_z,
-                          unsigned char* d_flags, void* stream) {
-    BP_TRY
-    BP_CHECK(d_poses && d_kp && K && d_xy && d_z && d_flags, "null argument");
-    annot_check_image(P, H, W);
-    BP_CHECK(Kp > 0 && (long long)P * Kp < (1ll << 31), "Kp must be positive and P * Kp below 2^31");
-    BP_CHECK(near_z > 0.0, "near must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, s);
-    bp::launch_annotate_keypoints(d_poses, P, d_kp, Kp, K, H, W, pixel_center, near_z, d_model_depth, d_scene_depth,
-                                  d_scene_index, self_tol, delta, d_xy, d_z, d_flags, s);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_mask_boxes_host(const float* depth, int P, int H, int W, const double* K, double pixel_center, const float* scene_depth,
-                       int T, const int* scene_index, double delta, int* boxes, int* counts) {
-    BP_TRY
-    BP_CHECK(depth && K && boxes && counts, "null argument");
-    annot_check_image(P, H, W);
-    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
-    bp::mask_boxes_host(depth, P, H, W, K, pixel_center, scene_depth, scene_index, delta, boxes, counts);
-    return 0;
-    BP_CATCH
-}
-
-int bp_mask_boxes(const float* d_depth, int P, int H, int W, const double* K, double pixel_center, const float* d_scene_depth,
-                  int T, const int* d_scene_index, double delta, int* d_boxes, int* d_counts, void* stream) {
-    BP_TRY
-    BP_CHECK(d_depth && K && d_boxes && d_counts, "null argument");
-    annot_check_image(P, H, W);
-    BP_CHECK(P < (1 << 28), "P must be below 2^28");
-    hipStream_t s = (hipStream_t)stream;
-    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, s);
-    bp::Arena a;
-    int* acc = (int*)a.alloc_bytes((size_t)P * 2 * bp::ANNOT_BOX_INTS * sizeof(int));
-    bp::launch_mask_boxes(d_depth, P, H, W, K, pixel_center, d_scene_depth, d_scene_index, delta, acc, d_boxes, d_counts, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-int bp_vertex_boxes_host(const double* poses, int P, const double* vertices, int n, const double* K, int H, int W, int* boxes) {
-    BP_TRY
-    BP_CHECK(poses && vertices && K && boxes, "null argument");
-    annot_check_image(P, H, W);
-    BP_CHECK(n > 0, "n must be positive");
-    bp::vertex_boxes_host(poses, P, vertices, n, K, H, W, boxes);
-    return 0;
-    BP_CATCH
-}
-
-int bp_vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n, const double* K, int H, int W, int* d_boxes,
-                    void* stream) {
-    BP_TRY
-    BP_CHECK(d_poses && d_vertices && K && d_boxes, "null argument");
-    annot_check_image(P, H, W);
-    BP_CHECK(n > 0 && P < (1 << 28), "n must be positive and P below 2^28");
-    hipStream_t s = (hipStream_t)stream;
-    bp::Arena a;
-    int* acc = (int*)a.alloc_bytes((size_t)P * bp::ANNOT_BOX_INTS * sizeof(int));
-    bp::launch_vertex_boxes(d_poses, P, d_vertices, n, K, H, W, acc, d_boxes, s);
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-static void annot_check_targets(int B, int Kp, int inpH, int inpW, int resH, int resW, int size) {
-    BP_CHECK(B > 0 && Kp > 0 && inpH > 0 && inpW > 0 && resH > 0 && resW > 0, "B, Kp and the resolutions must be positive");
-    BP_CHECK(size >= 1 && size % 2 == 1 && size <= 1025, "the Gaussian table needs an odd size of at most 1025");
-    // (the kernel indexes rows in groups of four floats: the width counts rounded up to a multiple of 4)
-    BP_CHECK((long long)B * Kp * resH * ((resW + 3) / 4 * 4) < (1ll << 31), "the target tensor must hold fewer than 2^31 values");
-}
-
-int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
-                        int resW, const float* g, int size, float* out, int* centres, float* set_mask) {
-    BP_TRY
-    BP_CHECK(parts && ul && br && g && out && centres, "null argument");
-    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
-    bp::kpd_targets_host(parts, ul, br, B, Kp, inpH, inpW, resH, resW, g, size, out, centres, set_mask);
-    return 0;
-    BP_CATCH
-}
-
-int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
-                   int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream) {
-    BP_TRY
-    BP_CHECK(d_parts && d_ul && d_br && d_g && d_out && d_centres, "null argument");
-    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
-    bp::launch_kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask,
-                           (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-// what the four refinement calls check alike, and the parameter block they hand on
-static bp::IcpParams icp_params(const double* K, int T, double depth_scale, int iterations, double max_dist, double min_cos,
-                                int min_pixels, double pixel_center) {
-    BP_CHECK(T > 0, "T must be positive");
-    BP_CHECK(depth_scale > 0.0 && max_dist > 0.0, "depth_scale and max_dist must be positive");
-    BP_CHECK(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must lie in [0, 1]");
-    BP_CHECK(iterations >= 0 && iterations <= 1000 && min_pixels >= 0, "iterations must lie in 0 .. 1000, min_pixels >= 0");
-    return bp::IcpParams{K[0], K[4], K[2], K[5], pixel_center, depth_scale, max_dist, min_cos, min_pixels, iterations};
-}
-
-// poses per chunk of the device calls: the z-buffers and the posed meshes of a chunk each stay under RASTER_WS_BYTES
-static size_t icp_chunk(int chunk, int n, int P, size_t HW) {
-    size_t c = (size_t)chunk;
-    if (c == 0) c = std::min(RASTER_WS_BYTES / (HW * sizeof(float)), RASTER_WS_BYTES / bp::raster_vertex_bytes(n, 1));
-    return std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
-}
-
-int bp_icp_normal_equations_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
-                                 const double* K, const uint16_t* depth_test, int T, int H, int W, double depth_scale,
-                                 const int* test_index, double max_dist, double min_cos, double pixel_center, double near_z,
-                                 double* out) {
-    BP_TRY
-    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && out, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
-    BP_CHECK(bp::icp_normal_equations_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z,
-                                           out) == 0,
-             "a face index lies outside [0, n)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_refine_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
-                         const uint16_t* depth_test, int T, int H, int W, double depth_scale, const int* test_index,
-                         int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
-                         double* poses_out, double* stats) {
-    BP_TRY
-    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && poses_out && stats, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
-    BP_CHECK(bp::refine_depth_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z, poses_out,
-                                   stats) == 0,
-             "a face index lies outside [0, n)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_icp_normal_equations(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P,
-                            const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
-                            const int* d_test_index, double max_dist, double min_cos, double pixel_center, double near_z,
-                            int chunk, double* d_out, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_out, "null argument");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    BP_CHECK(chunk >= 0, "chunk must not be negative");
-    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
-    const int slices = bp::icp_slices(H, W);
-    bp::Arena a;
-    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(c * HW * sizeof(uint32_t));
-    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)c));
-    int* skipped = (int*)a.alloc_bytes(c * sizeof(int));
-    double* partial = (double*)a.alloc_bytes(c * slices * bp::ICP_ACC * sizeof(double));
-    BP_HIP(hipMemsetAsync(skipped, 0, c * sizeof(int), s));
-    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
-        const int m = (int)std::min(c, (size_t)P - p0);
-        BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)m * HW, s));   // +inf
-        bp::launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, m, nullptr, 0, K, H, W, pixel_center, near_z, ws, zbuf,
-                          skipped, s);
-        bp::launch_icp_accumulate(zbuf, d_poses + p0 * 12, m, d_depth_test, T, d_test_index + p0, H, W, prm, nullptr, partial, s);
-        bp::launch_icp_sum(partial, d_test_index + p0, T, m, slices, d_out + p0 * bp::ICP_ACC, s);
-    }
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
-    return 0;
-    BP_CATCH
-}
-
-int bp_refine_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
-                    const uint16_t* d_depth_test, int T, int H, int W, double depth_scale, const int* d_test_index,
-                    int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
-                    int chunk, double* d_poses_out, double* d_stats, void* stream) {
-    BP_TRY
-    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_poses_out && d_stats, "null argument");
-    BP_CHECK(d_poses_out != d_poses, "d_poses_out must not be d_poses: a rejected pose gets its input back");
-    raster_check_sizes(n, F, P, H, W, near_z);
-    BP_CHECK(chunk >= 0, "chunk must not be negative");
-    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
-    const int slices = bp::icp_slices(H, W);
-    bp::Arena a;
-    uint32_t* zbuf = (uint32_t*)a.alloc_bytes(c * HW * sizeof(uint32_t));
-    void* ws = a.alloc_bytes(bp::raster_vertex_bytes(n, (int)c));
-    int* skipped = (int*)a.alloc_bytes(c * sizeof(int));
-    double* partial = (double*)a.alloc_bytes(c * slices * bp::ICP_ACC * sizeof(double));
-    BP_HIP(hipMemsetAsync(skipped, 0, c * sizeof(int), s));
-    bp::launch_icp_init(d_poses, d_test_index, T, P, d_poses_out, d_stats, s);
-    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
-        const int m = (int)std::min(c, (size_t)P - p0);
-        double* pose = d_poses_out + p0 * 12;
-        double* stats = d_stats + p0 * bp::ICP_STATS;
-        // the whole loop is enqueued: no host round trip between the iterations
-        for (int k = 0; k <= iterations; ++k) {
-            BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)m * HW, s));   // +inf
-            bp::launch_raster(d_model, n, d_faces, F, pose, m, nullptr, 0, K, H, W, pixel_center, near_z, ws, zbuf, skipped, s);
-            bp::launch_icp_accumulate(zbuf, pose, m, d_depth_test, T, d_test_index + p0, H, W, prm, stats, partial, s);
-            bp::launch_icp_step(partial, m, slices, k, prm, d_poses + p0 * 12, pose, stats, s);
-        }
-    }
-    BP_HIP(hipGetLastError());
-    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
-    return 0;
-    BP_CATCH
-}
-
 int bp_heatmap_argmax(const float* d_hm, int batch, int C, int H, int W, float* d_kp, void* stream) {
     BP_TRY
     BP_CHECK(d_hm && d_kp && batch > 0 && C > 0 && H > 0 && W > 0, "bad argument");
     bp::launch_heatmap_argmax(d_hm, batch, C, H, W, d_kp, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_conv2d(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
-              int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
-              float* d_out, int iters, float* ms_per_iter, void* stream) {
-    return bp_conv2d_planes(d_in, N, H, W, Cin, h_w, h_bias, Cout, k, stride, pad, act, store_mode, d_res, res_after_act, tile,
-                            splits, d_out, nullptr, iters, ms_per_iter, stream);
-}
-
-int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
-                     int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
-                     float* d_out, unsigned short* d_out_planes, int iters, float* ms_per_iter, void* stream) {
-    BP_TRY
-    BP_CHECK(d_in && h_w && d_out, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    struct OneConv : bp::Net {
-        OneConv() : Net(1) {}
-        using Net::add_conv;
-        using Net::finalize;
-        using Net::ops_;
-        using Net::partial_;
-        using Net::partial_floats_;
-        using Net::arena_;
-    } net;
-    const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
-    bp::Tensor in; in.p = const_cast<float*>(d_in); in.H = H; in.W = W; in.C = Cin; in.ld = Cin;
-    bp::Tensor out; out.p = d_out; out.H = OH; out.W = OW; out.C = Cout;
-    out.ld = store_mode == bp::ST_PIXSHUF ? Cout / 4 : Cout;
-    bp::Tensor res; res.p = const_cast<float*>(d_res); res.ld = Cout; res.C = Cout; res.H = OH; res.W = OW;
-    bp::ConvWeights cw; cw.w = h_w; cw.bias = h_bias;
-    net.add_conv("conv", in, out, cw, Cout, k, stride, pad, act, store_mode, d_res ? &res : nullptr, nullptr,
-                 res_after_act, 1e-5f, OH, OW);
-    int t = tile;
-    int prec = bp::PREC_F32;
-    if (t >= 256) {   // + 256: fp16-MFMA operands, + 512: bf16x3 split operands
-        prec = t >= 512 ? bp::PREC_BF16X3 : bp::PREC_F16;
-        t -= t >= 512 ? 512 : 256;
-        BP_CHECK(Cin % 32 == 0, "layer is not eligible for the 16-bit MFMA paths (needs Cin % 32 == 0)");
-        net.set_precision(prec);
-        net.ops_[0].conv.mfma_mode = prec;
-#ifndef BP_EXPERIMENTAL
-        BP_CHECK(bp::conv_tile_is_pl(t) || ((t == bp::TILE_64x64_BD || t == bp::TILE_BD_K2 || bp::conv_tile_is_halo(t)) && prec == bp::PREC_BF16X3),
-                 "this kernel id exists only in the experimental library (python -m betapose_amd.build --experimental, BP_LIB)");
-#endif
-    } else {
-        if (t < 0 && bp::conv_stem3_eligible(net.ops_[0].conv)) t = bp::TILE_STEM3;      // as the engine plans it
-        BP_CHECK(t <= bp::TILE_128x64 || (t == bp::TILE_STEM3 && bp::conv_stem3_eligible(net.ops_[0].conv)) || (t == bp::TILE_STEM7 && bp::conv_stem7_eligible(net.ops_[0].conv)),
-                 "this tile needs a 16-bit precision mode (tile + 256 / + 512), or the layer is not a 3x3 / stride-1 / 4-channel-packed stem");
-    }
-    bp::ConvParams p = net.ops_[0].conv;
-    p.N = N; p.M = N * OH * OW;
-    if (t < 0) t = bp::TILE_64x64;
-    const int np = prec == bp::PREC_F16 ? 1 : 3;
-    if (bp::conv_tile_is_pl(t)) {
-        // the caller's activations are fp32: their operand planes are made here, as the layer's producer would have
-        const long long in_elems = (long long)N * H * W * Cin;
-        BP_CHECK(Cin % 32 == 0 && k * k <= 32, "layer is not eligible for the operand-plane kernels (needs Cin % 32 == 0, k*k <= 32)");
-        unsigned short* d_in16 = (unsigned short*)net.arena_.alloc_bytes((size_t)np * in_elems * 2);
-        bp::launch_f32_to_planes(d_in, Cin, (long long)N * H * W, Cin, d_in16, in_elems, np, s);
-        p.in16 = d_in16; p.in16_plane = in_elems;
-        auto& packed = np == 1 ? net.weight_store()->wpl1 : net.weight_store()->wpl3;
-        auto it = packed.find(p.w);
-        if (it == packed.end()) {
-            unsigned short* d = (unsigned short*)net.weight_store()->arena.alloc_bytes((size_t)np * p.CoutPad * p.Kpad * 2);
-            bp::launch_pack_wpl(p.w, d, p.CoutPad, p.Kpad, p.Cin, p.ksize, np, s);
-            it = packed.emplace(p.w, d).first;
-        }
-        p.wpl = it->second;
-        if (t == bp::TILE_PL64BD) {   // the filters-direct plane tile reads stage-packed fragments in the plane kernels' K order
-            auto& staged = net.weight_store()->wbd3;
-            auto ib = staged.find(p.w);
-            if (ib == staged.end()) {
-                unsigned short* d = (unsigned short*)net.weight_store()->arena.alloc_bytes((size_t)3 * p.CoutPad * p.Kpad * 2);
-                bp::launch_f32_to_bf16x3_staged(p.w, d, p.CoutPad, p.Kpad, s, p.Cin);
-                ib = staged.emplace(p.w, d).first;
-            }
-            p.wbd = ib->second;
-        }
-    }
-    if (const char* e = std::getenv("BP_PL_ABL")) p.abl = std::atoi(e);   // (read by experimental builds only)
-    if (d_out_planes) {   // the epilogue's operand planes of the output (any kernel): [np][the output tensor's elements]
-        BP_CHECK(prec != bp::PREC_F32, "output planes need a 16-bit precision mode");
-        long long out_elems = (long long)N * OH * OW * Cout;
-        if (store_mode == bp::ST_UP2) out_elems *= 4;
-        p.out16 = d_out_planes; p.out16_plane = out_elems; p.out_np = np;
-    }
-    // BP_CONV_F16R=1 (bench tools, tests/test_gpu_conv.py; read per call): the launch as the engine's 'f16r' plan makes it -- the skip
-    // connection read from an fp16 plane of the residual tensor (ConvParams::res16) and, when output planes are asked for, the fp32 store
-    // dropped (ConvParams::skip_f32)
-    if (prec == bp::PREC_F16 && std::getenv("BP_CONV_F16R")) {
-        if (p.res) {
-            const long long n_res = (long long)N * OH * OW;
-            unsigned short* r16 = (unsigned short*)net.arena_.alloc_bytes((size_t)n_res * p.res_ld * 2);
-            if (Cout % 4 == 0) bp::launch_f32_to_planes(p.res, p.res_ld, n_res, Cout, r16, n_res * p.res_ld, 1, s);
-            else {
-                // Cout % 4 != 0 (the element-wise epilogue's layers): the converter moves four channels at a time, and the caller's residual is
-                // dense (ld == Cout) -- the tensor as one run of quads, its last 1-3 elements rounded on the host (RNE, as the device does)
-                const long long total = n_res * p.res_ld, quads = total / 4;
-                if (quads > 0) bp::launch_f32_to_planes(p.res, 4, quads, 4, r16, total, 1, s);
-                const int nt = (int)(total - 4 * quads);
-                if (nt > 0) {
-                    float tail32[3];
-                    unsigned short tail16[3];
-                    BP_HIP(hipStreamSynchronize(s));      // (the caller's residual is ordered on `s`; the copies below run on the null stream and are
-                                                          // safe only because hipMemcpy returns when the copy is done -- before the launch on `s` is enqueued)
-                    BP_HIP(hipMemcpy(tail32, p.res + 4 * quads, nt * sizeof(float), hipMemcpyDeviceToHost));
-                    for (int i = 0; i < nt; ++i) { const _Float16 h = (_Float16)tail32[i]; std::memcpy(&tail16[i], &h, 2); }
-                    BP_HIP(hipMemcpy(r16 + 4 * quads, tail16, nt * 2, hipMemcpyHostToDevice));
-                }
-            }
-            p.res16 = r16;
-        }
-        if (p.out16) p.skip_f32 = 1;
-    }
-    // the launch set-up is the engine's (conv_plan.h): K cut, hybrid grid when the last round is badly filled, XCD-home layout
-    const bp::ConvLaunch l = bp::conv_launch_of(p, t, splits);
-    const int sp = l.splits, per = l.cps;
-    p.splits = sp; p.chunks_per_split = per;
-    if (sp > 1) {
-        const int tiles = bp::conv_tiles(p, t);
-        p.partial = net.arena_.alloc(bp::conv_slab_floats(t, sp, tiles));
-        p.tickets = (int*)net.arena_.alloc_bytes((size_t)(2 + 64) * tiles * sizeof(int));
-        BP_HIP(hipMemset(p.tickets, 0, (size_t)(2 + 64) * tiles * sizeof(int)));
-    }
-    bp::HybridTail h;
-    if (sp == 1 && !std::getenv("BP_CONV_SELF_PREFETCH") && bp::conv_hybrid_plan(p, t, bp::conv_slab_floats(t, 8, 256), &h)) {   // (<= 8 slices of <= 256 tail tiles)
-        p.partial = net.arena_.alloc(h.slab_floats);
-        p.tickets = (int*)net.arena_.alloc_bytes((size_t)h.tiles * sizeof(int));
-        BP_HIP(hipMemset(p.tickets, 0, (size_t)h.tiles * sizeof(int)));
-        p.hy_full = h.full; p.hy_splits = h.splits; p.hy_cps = h.cps;
-    }
-    if (bp::conv_home_layout(t, sp)) {   // all K slices of a tile on one XCD, hand-off through that XCD's L2
-        const int tiles = bp::conv_tiles(p, t);
-        p.xcd_home = 1;
-        p.tickets_local = p.tickets + tiles;
-        p.xcc_of = p.tickets + 2 * tiles;
-    }
-    if (std::getenv("BP_CONV_SELF_PREFETCH")) bp::conv_prefetch_of(p, p, l);   // (tests: the launch carries prefetch blocks, for its own filters)
-    bp::launch_conv(p, t, s);
-    BP_HIP(hipStreamSynchronize(s));
-    if (const char* e = std::getenv("BP_CONV_STAMPS")) {   // debug: per-block s_memtime marks of one extra launch
-        const int nb = bp::conv_tiles(p, t) * p.splits;
-        unsigned long long* d = (unsigned long long*)net.arena_.alloc_bytes((size_t)nb * 8 * 8);
-        BP_HIP(hipMemset(d, 0, (size_t)nb * 64));
-        bp::ConvParams q = p; q.stamps = d;
-        bp::launch_conv(q, t, s);
-        BP_HIP(hipStreamSynchronize(s));
-        std::vector<unsigned long long> h((size_t)nb * 8);
-        BP_HIP(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        for (int b = 0; b < nb; ++b)
-            if (h[(size_t)b * 8]) t0 = std::min(t0, h[(size_t)b * 8]);
-        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = 0;
-        int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int b = 0; b < nb; ++b)
-            for (int k = 0; k < 8; ++k) {
-                const unsigned long long v = h[(size_t)b * 8 + k];
-                if (!v) continue;
-                acc[k] += (double)(v - h[(size_t)b * 8]); ++cnt[k];      // relative to the block's own entry
-                last = std::max(last, (double)(v - t0));
-            }
-        auto mean = [&](int k) { return cnt[k] ? acc[k] / cnt[k] : 0.0; };
-        if (std::getenv("BP_W64_ABLATE") && (std::atoi(std::getenv("BP_W64_ABLATE")) & 64)) {
-            double sum[4] = {0, 0, 0, 0};
-            for (int b = 0; b < nb; ++b) for (int k = 0; k < 4; ++k) sum[k] += (double)h[(size_t)b * 8 + 4 + k];
-            const double stages = 2.0 * p.chunks_per_split * nb;
-            std::fprintf(stderr, "[stage timing] cycles per stage: issue slots 0..UPW %.0f | slots ..SYNC %.0f | wait+barrier %.0f | SYNC..end %.0f\n",
-                         sum[0] / stages, sum[1] / stages, sum[2] / stages, sum[3] / stages);
-        }
-        std::fprintf(stderr, "[stamps] blocks=%d  mean 10-ns ticks (s_memrealtime, 100 MHz) since the block's entry: index math done %.0f | chunk 0 in LDS %.0f | "
-                     "K loop done %.0f | in-block sums (conv_kg) or cycles parked at the stage waits (conv_pl) %.0f | slab parked + ticket %.0f (%d blocks) | slices combined %.0f (%d) | stores done %.0f (%d) | "
-                     "last mark of the grid %.0f after the first entry\n", nb, mean(1), mean(2), mean(3), mean(7), mean(5), cnt[5], mean(6),
-                     cnt[6], mean(4), cnt[4], last);
-    }
-    if (iters > 0 && ms_per_iter) {
-        hipEvent_t e0, e1;
-        BP_HIP(hipEventCreate(&e0));
-        BP_HIP(hipEventCreate(&e1));
-        BP_HIP(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) bp::launch_conv(p, t, s);
-        BP_HIP(hipEventRecord(e1, s));
-        BP_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BP_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_iter = ms / iters;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     return 0;
     BP_CATCH
 }
@@ -1394,138 +642,12 @@ int bp_pipeline_set_pose_solver(bp_pipeline* p, const double* kp3d, int n_kp, co
 }
 double* bp_pipeline_poses(bp_pipeline* p) { return p ? p->pose.poses : nullptr; }
 
-int bp_pose_from_records(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
-                         int left_number, double* d_poses, void* stream) {
-    BP_TRY
-    BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
-    BP_CHECK(batch >= 0, "batch must be >= 0");
-    bp::check_pose_points(n_kp, left_number);
-    if (batch == 0) return 0;
-    bp::launch_pose_tail(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_pose_from_candidate_records(const float* d_records, const int* d_counts, int frames, int C, const double* d_kp3d, int n_kp,
-                                   const double* K, int left_number, double* d_poses, float* d_merged, int* d_info, void* stream) {
-    BP_TRY
-    BP_CHECK(d_records && d_counts && d_kp3d && K && d_poses && d_merged && d_info, "null argument");
-    BP_CHECK(frames >= 0, "frames must be >= 0");
-    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
-    bp::check_pose_points(n_kp, left_number);
-    if (frames == 0) return 0;
-    bp::launch_pose_tail_cands(d_records, d_counts, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_poses, d_merged, d_info,
-                               (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_pose_instances_from_merged(const float* d_merged, const int* d_info, const double* d_poses, int frames, int C,
-                                  const double* d_kp3d, int n_kp, const double* K, int left_number, double* d_inst_poses,
-                                  void* stream) {
-    BP_TRY
-    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "1 to 8 candidates per frame (BP_MAX_CANDIDATES)");
-    BP_CHECK(d_merged && d_info && d_poses && d_kp3d && K && d_inst_poses, "null argument");
-    BP_CHECK(frames >= 0 && frames <= 65535, "frames must be in [0, 65535]");
-    bp::check_pose_points(n_kp, left_number);
-    if (frames == 0) return 0;
-    bp::launch_pose_instances(d_merged, d_info, d_poses, frames, C, d_kp3d, bp::make_pnp_cam(K), left_number, d_inst_poses,
-                              (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_solve_pnp_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
-                       double* d_Rt, int* d_status, void* stream) {
-    BP_TRY
-    BP_CHECK(d_pts3d && d_pts2d && K && d_Rt && d_status, "null argument");
-    BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_batch: n must be in [0, 64] points per problem");
-    BP_CHECK(P >= 0, "P must be >= 0");
-    if (P == 0) return 0;
-    bp::launch_solve_pnp_batch(d_pts3d, shared_3d, d_pts2d, n, P, bp::make_pnp_cam(K), d_Rt, d_status, (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
-int bp_pnp_ransac_samples(int n, int max_trials, int* idx) {
-    BP_TRY
-    BP_CHECK(idx, "null argument");
-    BP_CHECK(n >= 6 && max_trials >= 1, "bp_pnp_ransac_samples: needs n >= 6 points and max_trials >= 1");
-    bp::pnp_ransac_samples(n, max_trials, idx);
-    return 0;
-    BP_CATCH
-}
-
-int bp_pnp_ransac_trials_needed(int n, double confidence, int* need) {
-    BP_TRY
-    BP_CHECK(need, "null argument");
-    BP_CHECK(n >= 1 && confidence > 0 && confidence < 1, "bp_pnp_ransac_trials_needed: needs n >= 1 and a confidence in (0, 1)");
-    bp::pnp_ransac_trials_needed(n, confidence, need);
-    return 0;
-    BP_CATCH
-}
-
-size_t bp_pnp_ransac_workspace_bytes(int P, int max_trials) {
-    return P > 0 && max_trials > 0 ? bp::pnp_ransac_workspace_bytes(P, max_trials) : 0;
-}
-
-int bp_solve_pnp_ransac_batch(const double* d_pts3d, int shared_3d, const double* d_pts2d, int n, int P, const double* K,
-                              double reproj_err, int max_trials, double confidence, double* d_Rt, int* d_status,
-                              unsigned char* d_inliers, void* d_workspace, size_t workspace_bytes, void* stream) {
-    BP_TRY
-    BP_CHECK(d_pts3d && d_pts2d && K && d_Rt && d_status, "null argument");
-    BP_CHECK(n >= 0 && n <= BP_PNP_MAX_POINTS, "bp_solve_pnp_ransac_batch: n must be in [0, 64] points per problem");
-    BP_CHECK(P >= 0, "P must be >= 0");
-    bp::check_ransac_params(reproj_err, max_trials, confidence);
-    if (P == 0) return 0;
-    BP_CHECK(d_workspace && workspace_bytes >= bp::pnp_ransac_workspace_bytes(P, max_trials),
-             "bp_solve_pnp_ransac_batch: workspace smaller than bp_pnp_ransac_workspace_bytes(P, max_trials)");
-    BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_solve_pnp_ransac_batch: workspace must be 8-byte aligned");
-    std::vector<int> samples, need;
-    bp::ransac_tables(n, max_trials, confidence, samples, need);
-    bp::launch_pnp_ransac(d_pts3d, shared_3d ? 0 : (size_t)n * 3, d_pts2d, (size_t)n * 2, nullptr, n, P, bp::make_pnp_cam(K), reproj_err,
-                          max_trials, samples.data(), need.data(), d_workspace, d_Rt, d_status, d_inliers, nullptr,
-                          (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
-    return 0;
-    BP_CATCH
-}
-
 int bp_pipeline_set_pose_ransac(bp_pipeline* p, double reproj_err, int max_trials, double confidence) {
     BP_TRY
     BP_CHECK(p, "null argument");
     p->graph.drop();
     BP_CHECK(max_trials == 0 || p->pose.on, "bp_pipeline_set_pose_ransac: set a pose solver first (bp_pipeline_set_pose_solver)");
     p->pose.set_ransac(p->arena, p->y->device, p->batch, reproj_err, max_trials, confidence);
-    return 0;
-    BP_CATCH
-}
-
-size_t bp_pose_ransac_workspace_bytes(int batch, int max_trials) {
-    return batch > 0 && max_trials > 0 ? bp::pose_ransac_ws_bytes(batch, max_trials) : 0;
-}
-
-int bp_pose_from_records_ransac(const float* d_records, int batch, const double* d_kp3d, int n_kp, const double* K,
-                                int left_number, double reproj_err, int max_trials, double confidence, double* d_poses,
-                                void* d_workspace, size_t workspace_bytes, void* stream) {
-    BP_TRY
-    BP_CHECK(d_records && d_kp3d && K && d_poses, "null argument");
-    BP_CHECK(batch >= 0, "batch must be >= 0");
-    bp::check_pose_points(n_kp, left_number);
-    bp::check_ransac_params(reproj_err, max_trials, confidence);
-    if (batch == 0) return 0;
-    BP_CHECK(d_workspace && workspace_bytes >= bp::pose_ransac_ws_bytes(batch, max_trials),
-             "bp_pose_from_records_ransac: workspace smaller than bp_pose_ransac_workspace_bytes(batch, max_trials)");
-    BP_CHECK(((uintptr_t)d_workspace & 7) == 0, "bp_pose_from_records_ransac: workspace must be 8-byte aligned");
-    std::vector<int> samples, need;
-    bp::ransac_tables(bp::pose_points(left_number), max_trials, confidence, samples, need);
-    bp::pose_tail_ransac(d_records, batch, d_kp3d, bp::make_pnp_cam(K), left_number, reproj_err, max_trials, samples.data(), need.data(),
-                     d_poses, d_workspace, (hipStream_t)stream);
-    BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
 }
@@ -1761,212 +883,6 @@ int bp_cands_run(bp_cands* p, int use_graph, void* stream) {
     auto launch = [&] { p->graph.launch(use_graph, s, p->engines, [p](hipStream_t q) { cands_enqueue(p, q); }); };
     launch();
     bp::latency_rerun(p->engines, p->y->device, s, p->latency_faults, launch);
-    return 0;
-    BP_CATCH
-}
-
-// ------------------------------------------------------------------ xcd mode (mega.inc): prototype entry point, experimental library only
-#ifdef BP_EXPERIMENTAL
-// The convolution launch lists of up to eight detector engines (clones: own activations, shared filters), one per XCD, in ONE
-// persistent launch; `iters` launches timed with events.  The engines' inputs must already be in place (a forward pass of the
-// ordinary path leaves them there); afterwards every engine's activations hold what its own launches would have produced.
-int bp_mega_yolo_convs_stamped(bp_yolo** ys, int n, int blocks_per_xcd, int iters, float* ms_per_launch, unsigned* err_word,
-                               float* op_us, int* op_info, int cap, void* stream);
-int bp_mega_yolo_convs(bp_yolo** ys, int n, int blocks_per_xcd, int iters, float* ms_per_launch, unsigned* err_word, void* stream) {
-    return bp_mega_yolo_convs_stamped(ys, n, blocks_per_xcd, iters, ms_per_launch, err_word, nullptr, nullptr, 0, stream);
-}
-// ... with per-op marks of XCD 0's launch list: op_us[i] = duration of op i incl. its barrier, op_info[3 i] = {type, items, K slices}
-int bp_mega_yolo_convs_stamped(bp_yolo** ys, int n, int blocks_per_xcd, int iters, float* ms_per_launch, unsigned* err_word,
-                               float* op_us, int* op_info, int cap, void* stream) {
-    BP_TRY
-    BP_CHECK(ys && n >= 1 && n <= 8 && blocks_per_xcd >= 1 && blocks_per_xcd <= 256 && iters >= 1, "bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    BP_HIP(hipSetDevice(ys[0]->device));
-    bp::MegaArgs a{};
-    std::vector<void*> dev;
-    size_t lds = 0;
-    for (int k = 0; k < n; ++k) {
-        std::vector<bp::MegaOp> ops;
-        ys[k]->net->emit_conv_ops(1, ops);
-        if (const char* e = std::getenv("BP_MEGA_EXP")) {          // prototype experiments: 1 = barriers only (no work items), 2 = without the RGB stem
-            const int m = std::atoi(e);
-            for (bp::MegaOp& o : ops) {
-                if (m == 1) o.items = 0;
-                if (m == 2 && o.type == bp::MO_STEM3) o.items = 0;
-            }
-        }
-        for (const bp::MegaOp& o : ops) lds = std::max(lds, bp::mega_lds_bytes(o));
-        void* d = nullptr;
-        BP_HIP(hipMalloc(&d, ops.size() * sizeof(bp::MegaOp)));
-        dev.push_back(d);
-        BP_HIP(hipMemcpy(d, ops.data(), ops.size() * sizeof(bp::MegaOp), hipMemcpyHostToDevice));
-        a.prog[k] = (const bp::MegaOp*)d;
-        a.n_ops[k] = (int)ops.size();
-    }
-    unsigned* sync = nullptr;
-    BP_HIP(hipMalloc((void**)&sync, 129 * sizeof(unsigned)));
-    dev.push_back(sync);
-    a.sync = sync;
-    a.nb = blocks_per_xcd;
-    unsigned long long* d_st = nullptr;
-    if (op_us) {
-        BP_HIP(hipMalloc((void**)&d_st, 8 * 512 * sizeof(unsigned long long)));
-        BP_HIP(hipMemset(d_st, 0, 8 * 512 * sizeof(unsigned long long)));
-        dev.push_back(d_st);
-        a.stamps = d_st;
-    }
-    hipEvent_t e0, e1;
-    BP_HIP(hipEventCreate(&e0));
-    BP_HIP(hipEventCreate(&e1));
-    bp::launch_mega(a, lds, s);                 // warm
-    BP_HIP(hipStreamSynchronize(s));
-    BP_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) bp::launch_mega(a, lds, s);
-    BP_HIP(hipEventRecord(e1, s));
-    BP_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    BP_HIP(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_per_launch) *ms_per_launch = ms / iters;
-    unsigned err = 0;
-    BP_HIP(hipMemcpy(&err, sync + 128, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (err_word) *err_word = err;
-    if (op_us) {
-        std::vector<unsigned long long> h(512);
-        BP_HIP(hipMemcpy(h.data(), d_st, 512 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<bp::MegaOp> ops;
-        ys[0]->net->emit_conv_ops(1, ops);
-        for (int i = 0; i < (int)ops.size() && i < cap; ++i) {
-            op_us[i] = (float)((double)(h[i + 1] - h[i]) / 100.0);         // 100 MHz reference clock
-            if (op_info) { op_info[3 * i] = ops[i].type; op_info[3 * i + 1] = ops[i].items; op_info[3 * i + 2] = ops[i].conv.splits; }
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    for (void* d : dev) (void)hipFree(d);
-    return 0;
-    BP_CATCH
-}
-#endif
-
-// ------------------------------------------------------------------ host post-processing
-int bp_solve_pnp(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t) {
-    BP_TRY
-    BP_CHECK(pts3d && pts2d && K && R && t, "null argument");
-    const int rc = bp::solve_pnp(pts3d, pts2d, n, K, R, t);
-    if (rc != 0) throw bp::Error("solve_pnp failed (need >= 6 non-degenerate points, or >= 4 coplanar ones)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_solve_pnp_status(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t, int* status) {
-    BP_TRY
-    BP_CHECK(pts3d && pts2d && K && R && t && status, "null argument");
-    *status = bp::solve_pnp(pts3d, pts2d, n, K, R, t);
-    return 0;
-    BP_CATCH
-}
-
-int bp_solve_pnp_refined(const double* pts3d, const double* pts2d, int n, const double* K, double* R, double* t) {
-    BP_TRY
-    BP_CHECK(pts3d && pts2d && K && R && t, "null argument");
-    const int rc = bp::solve_pnp_refined(pts3d, pts2d, n, K, R, t);
-    if (rc != 0) throw bp::Error("solve_pnp_refined failed (need >= 6 non-degenerate points)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_solve_pnp_ransac(const double* pts3d, const double* pts2d, int n, const double* K, double reproj_err,
-                        int max_trials, double confidence, double* R, double* t, unsigned char* inliers) {
-    BP_TRY
-    BP_CHECK(pts3d && pts2d && K && R && t, "null argument");
-    bp::check_ransac_params(reproj_err, max_trials, confidence);
-    const int rc = bp::solve_pnp_ransac(pts3d, pts2d, n, K, reproj_err, max_trials, confidence, R, t, inliers);
-    if (rc != 0) throw bp::Error("solve_pnp_ransac failed (need >= 6 points and a 6-point consensus)");
-    return 0;
-    BP_CATCH
-}
-
-int bp_pose_nms(const float* bboxes, const float* bbox_scores, const float* preds, const float* scores, int n, int K,
-                int* out_pick, float* out_pose, float* out_score, float* out_prop) {
-    BP_TRY
-    BP_CHECK(n >= 0 && K >= 1, "bad sizes");
-    BP_CHECK(n == 0 || (bboxes && bbox_scores && preds && scores && out_pick && out_pose && out_score && out_prop), "null argument");
-    return bp::pose_nms(bboxes, bbox_scores, preds, scores, n, K, out_pick, out_pose, out_score, out_prop);
-    BP_CATCH
-}
-
-// ------------------------------------------------------------------ frame input (host)
-struct bp_loader {
-    std::unique_ptr<bp::FrameLoader> l;
-};
-
-static void* pinned_alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return p;
-}
-static void pinned_free(void* p) { (void)hipHostFree(p); }
-
-int bp_png_info(const unsigned char* data, size_t n, int* h, int* w, int* channels) {
-    BP_TRY
-    BP_CHECK(data, "null argument");
-    bp::png_info(data, n, h, w, channels);
-    return 0;
-    BP_CATCH
-}
-
-int bp_png_decode_bgr(const unsigned char* data, size_t n, unsigned char* out_bgr, size_t cap, int* h, int* w) {
-    BP_TRY
-    BP_CHECK(data && out_bgr, "null argument");
-    static thread_local std::vector<uint8_t> scratch;
-    bp::png_decode_bgr(data, n, out_bgr, cap, h, w, scratch);
-    return 0;
-    BP_CATCH
-}
-
-int bp_loader_create(const char* const* paths, int n, int H, int W, int threads, int depth, int pinned, bp_loader** out) {
-    BP_TRY
-    BP_CHECK(paths && out && n >= 0, "null argument");
-    std::vector<std::string> v;
-    for (int i = 0; i < n; ++i) {
-        BP_CHECK(paths[i], "null path");
-        v.emplace_back(paths[i]);
-    }
-    int ndev = 0;
-    const bool pin = pinned && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-    if (!pin) (void)hipGetLastError();
-    auto* L = new bp_loader;
-    try {
-        L->l.reset(new bp::FrameLoader(std::move(v), H, W, threads, depth, pin ? pinned_alloc : nullptr,
-                                       pin ? pinned_free : nullptr));
-    } catch (...) {
-        delete L;
-        throw;
-    }
-    *out = L;
-    return 0;
-    BP_CATCH
-}
-
-void bp_loader_destroy(bp_loader* l) { delete l; }
-
-int bp_loader_next(bp_loader* l, long long* index, const unsigned char** bgr) {
-    BP_TRY
-    BP_CHECK(l, "null argument");
-    std::string err;
-    const int rc = l->l->next(index, bgr, &err);
-    if (rc < 0) g_err = err;
-    return rc;
-    BP_CATCH
-}
-
-int bp_loader_release(bp_loader* l, long long index) {
-    BP_TRY
-    BP_CHECK(l, "null argument");
-    l->l->release(index);
     return 0;
     BP_CATCH
 }

@@ -1,0 +1,390 @@
+// extern "C" boundary, the evaluation tools: pose metrics, depth and colour rasterisers, boxes, overlay, VSD, the key-point
+// annotator and the depth refinement, host and device -- see include/betapose_hip.h.  Every function checks its
+// arguments and makes one bp:: call: the host twin (*_host.cpp) or the device driver (eval_device.cpp).  What a host /
+// device pair checks alike is stated once, in the check functions.
+#include <vector>
+
+#include "annotate.h"
+#include "c_api_util.h"
+#include "icp.h"
+#include "pose_tail.h"
+#include "raster.h"
+
+static void check_pixels(int H, int W) { BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24"); }
+
+// what the rasteriser calls check alike
+static void raster_check_sizes(int n, int F, int P, int H, int W, double near_z) {
+    BP_CHECK(n > 0 && F > 0 && P > 0 && H > 0 && W > 0, "n, F, P, H and W must be positive");
+    check_pixels(H, W);
+    BP_CHECK(near_z > 0.0, "near must be positive");
+}
+
+// what the colour renderer's calls check of image_index (host, may be NULL): pose p -> image p needs I == P, otherwise
+// non-decreasing values in [0, I), which lets a call split its work into pose ranges without splitting an image
+static void raster_check_image_index(const int* image_index, int P, int I) {
+    BP_CHECK(I > 0, "I must be positive");
+    if (!image_index) {
+        BP_CHECK(I == P, "without image_index the call needs I == P");
+        return;
+    }
+    for (int p = 0; p < P; ++p) {
+        BP_CHECK(image_index[p] >= 0 && image_index[p] < I, "image_index must lie in [0, I)");
+        BP_CHECK(p == 0 || image_index[p] >= image_index[p - 1], "image_index must be non-decreasing");
+    }
+}
+
+static void raster_check_color(int n, int F, int P, int H, int W, double near_z, const int* image_index, int I) {
+    raster_check_sizes(n, F, P, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
+}
+
+static void raster_check_boxes(int P, int I, int H, int W, double near_z) {
+    BP_CHECK(P > 0 && I > 0 && H > 0 && W > 0, "P, I, H and W must be positive");
+    check_pixels(H, W);
+    BP_CHECK(P <= (1 << 24), "P must not exceed 2^24");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+}
+
+static void raster_check_overlay(int I, int H, int W, int alpha) {
+    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
+    check_pixels(H, W);
+    BP_CHECK(alpha >= 0 && alpha <= 256, "alpha must lie in 0 .. 256");
+}
+
+// ---- the key-point annotator (annotate.hip / annotate_host.cpp)
+static void annot_check_image(int P, int H, int W) {
+    BP_CHECK(P > 0 && H > 0 && W > 0, "P, H and W must be positive");
+    check_pixels(H, W);
+}
+static void annot_check_keypoints(int P, int H, int W, int Kp, double near_z) {
+    annot_check_image(P, H, W);
+    BP_CHECK(Kp > 0 && (long long)P * Kp < (1ll << 31), "Kp must be positive and P * Kp below 2^31");
+    BP_CHECK(near_z > 0.0, "near must be positive");
+}
+// scene depth and scene index come together; every index (host copy) must name one of the T images
+static void annot_check_scene(const void* scene_depth, const void* scene_index, const int* host_index, int P, int T) {
+    BP_CHECK((scene_depth != nullptr) == (scene_index != nullptr), "scene_depth and scene_index are given together");
+    if (!scene_depth) return;
+    BP_CHECK(T > 0, "T must be positive");
+    for (int p = 0; p < P; ++p) BP_CHECK(host_index[p] >= 0 && host_index[p] < T, "a scene index lies outside [0, T)");
+}
+// the device calls read the index back to check it before any kernel uses it
+static void annot_check_scene_device(const float* d_scene_depth, const int* d_scene_index, int P, int T, hipStream_t s) {
+    std::vector<int> idx;
+    if (d_scene_depth && d_scene_index) {
+        idx.resize(P);
+        BP_HIP(hipMemcpyAsync(idx.data(), d_scene_index, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s));
+        BP_HIP(hipStreamSynchronize(s));
+    }
+    annot_check_scene(d_scene_depth, d_scene_index, idx.data(), P, T);
+}
+
+static void annot_check_targets(int B, int Kp, int inpH, int inpW, int resH, int resW, int size) {
+    BP_CHECK(B > 0 && Kp > 0 && inpH > 0 && inpW > 0 && resH > 0 && resW > 0, "B, Kp and the resolutions must be positive");
+    BP_CHECK(size >= 1 && size % 2 == 1 && size <= 1025, "the Gaussian table needs an odd size of at most 1025");
+    // (the kernel indexes rows in groups of four floats: the width counts rounded up to a multiple of 4)
+    BP_CHECK((long long)B * Kp * resH * ((resW + 3) / 4 * 4) < (1ll << 31), "the target tensor must hold fewer than 2^31 values");
+}
+
+// what the four refinement calls check alike, and the parameter block they hand on
+static bp::IcpParams icp_params(const double* K, int T, double depth_scale, int iterations, double max_dist, double min_cos,
+                                int min_pixels, double pixel_center) {
+    BP_CHECK(T > 0, "T must be positive");
+    BP_CHECK(depth_scale > 0.0 && max_dist > 0.0, "depth_scale and max_dist must be positive");
+    BP_CHECK(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must lie in [0, 1]");
+    BP_CHECK(iterations >= 0 && iterations <= 1000 && min_pixels >= 0, "iterations must lie in 0 .. 1000, min_pixels >= 0");
+    return bp::IcpParams{K[0], K[4], K[2], K[5], pixel_center, depth_scale, max_dist, min_cos, min_pixels, iterations};
+}
+
+extern "C" {
+
+int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* K, int want,
+                   double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_gt && d_est && d_out, "null argument");
+    BP_CHECK(n > 0 && P > 0, "n and P must be positive");
+    BP_CHECK(want >= 1 && want <= 7, "want must be a non-empty mask of 1 (ADD), 2 (ADD-S), 4 (2-D)");
+    BP_CHECK(K || !(want & 4), "K is required for the 2-D projection error");
+    bp::pose_errors(d_model, n, d_gt, d_est, P, K, want, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym,
+                       int S, const double* K, int want, double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_gt && d_est && d_sym && d_out, "null argument");
+    BP_CHECK(n > 0 && P > 0 && S > 0, "n, P and S must be positive");
+    BP_CHECK(want >= 1 && want <= 3, "want must be a non-empty mask of 1 (MSSD), 2 (MSPD)");
+    BP_CHECK(K || !(want & 2), "K is required for the projection distance (MSPD)");
+    bp::pose_errors_sym(d_model, n, d_gt, d_est, P, d_sym, S, K, want, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         int H, int W, double pixel_center, double near_z, float* depth, int* skipped) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth && skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(bp::render_depth_host(poses, P, vertices, n, faces, F, K, H, W, pixel_center, near_z, depth, skipped) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    int H, int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth && d_skipped, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    bp::render_depth(d_poses, P, d_model, n, d_faces, F, K, H, W, pixel_center, near_z, d_depth, d_skipped, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                         const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
+                         double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                         unsigned char* color, float* depth, int* skipped) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && colors && K && light && color && depth && skipped, "null argument");
+    raster_check_color(n, F, P, H, W, near_z, image_index, I);
+    BP_CHECK(bp::render_color_host(poses, P, vertices, n, faces, F, colors, image_index, I, K, H, W, pixel_center, near_z, ambient,
+                                   light, accumulate, color, depth, skipped) == 0,
+             "a face index lies outside [0, n)");   // (its scan comes before it touches anything)
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_color(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
+                    const double* d_poses, int P, const int* image_index, int I, const double* K, int H, int W,
+                    double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                    unsigned char* d_color, float* d_depth, int* d_skipped, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_colors && d_poses && K && light && d_color && d_depth && d_skipped, "null argument");
+    raster_check_color(n, F, P, H, W, near_z, image_index, I);
+    bp::render_color(d_poses, P, d_model, n, d_faces, F, d_colors, image_index, I, K, H, W, pixel_center, near_z, ambient, light,
+                     accumulate, d_color, d_depth, d_skipped, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
+                       const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                       unsigned char* color) {
+    BP_TRY
+    BP_CHECK(poses && corners && corner_colors && K && color, "null argument");
+    raster_check_boxes(P, I, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    bp::draw_boxes_host(poses, P, corners, corner_colors, image_index, I, K, H, W, pixel_center, near_z, color);
+    return 0;
+    BP_CATCH
+}
+
+int bp_draw_boxes(const double* d_poses, int P, const double* d_corners, const unsigned char* d_corner_colors,
+                  const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                  unsigned char* d_color, void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_corners && d_corner_colors && K && d_color, "null argument");
+    raster_check_boxes(P, I, H, W, near_z);
+    raster_check_image_index(image_index, P, I);
+    bp::draw_boxes(d_poses, P, d_corners, d_corner_colors, image_index, I, K, H, W, pixel_center, near_z, d_color,
+                   (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,
+                    unsigned char* out) {
+    BP_TRY
+    BP_CHECK(frames && color && depth && out, "null argument");
+    raster_check_overlay(I, H, W, alpha);
+    bp::overlay_host(frames, color, depth, I, H, W, alpha, out);
+    return 0;
+    BP_CATCH
+}
+
+int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, const float* d_depth, int I, int H, int W, int alpha,
+               unsigned char* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_frames && d_color && d_depth && d_out, "null argument");
+    raster_check_overlay(I, H, W, alpha);
+    bp::overlay(d_frames, d_color, d_depth, I, H, W, alpha, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
+                  const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                  const int* d_test_index, double delta, const double* taus, int n_tau, double diameter, double pixel_center,
+                  double near_z, int chunk, double* d_err, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_gt && d_est && K && d_depth_test && d_test_index && taus && d_err && d_counts,
+             "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(T > 0, "T must be positive");
+    BP_CHECK(n_tau >= 1 && n_tau <= bp::VSD_MAX_TAUS, "n_tau must lie in 1 .. 16");
+    BP_CHECK(diameter > 0.0 && depth_scale > 0.0 && chunk >= 0, "diameter and depth_scale must be positive, chunk >= 0");
+    bp::vsd_errors(d_model, n, d_faces, F, d_gt, d_est, P, K, d_depth_test, T, H, W, depth_scale, d_test_index, delta, taus, n_tau,
+                   diameter, pixel_center, near_z, chunk, d_err, d_counts, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_annotate_keypoints_host(const double* poses, int P, const double* kp, int Kp, const double* K, int H, int W,
+                               double pixel_center, double near_z, const float* model_depth, const float* scene_depth, int T,
+                               const int* scene_index, double self_tol, double delta, double* xy, double* z,
+                               unsigned char* flags) {
+    BP_TRY
+    BP_CHECK(poses && kp && K && xy && z && flags, "null argument");
+    annot_check_keypoints(P, H, W, Kp, near_z);
+    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
+    bp::annotate_keypoints_host(poses, P, kp, Kp, K, H, W, pixel_center, near_z, model_depth, scene_depth, scene_index, self_tol,
+                                delta, xy, z, flags);
+    return 0;
+    BP_CATCH
+}
+
+int bp_annotate_keypoints(const double* d_poses, int P, const double* d_kp, int Kp, const double* K, int H, int W,
+                          double pixel_center, double near_z, const float* d_model_depth, const float* d_scene_depth, int T,
+                          const int* d_scene_index, double self_tol, double delta, double* d_xy, double* d_z,
+                          unsigned char* d_flags, void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_kp && K && d_xy && d_z && d_flags, "null argument");
+    annot_check_keypoints(P, H, W, Kp, near_z);
+    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, (hipStream_t)stream);
+    bp::annotate_keypoints(d_poses, P, d_kp, Kp, K, H, W, pixel_center, near_z, d_model_depth, d_scene_depth, d_scene_index,
+                           self_tol, delta, d_xy, d_z, d_flags, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_mask_boxes_host(const float* depth, int P, int H, int W, const double* K, double pixel_center, const float* scene_depth,
+                       int T, const int* scene_index, double delta, int* boxes, int* counts) {
+    BP_TRY
+    BP_CHECK(depth && K && boxes && counts, "null argument");
+    annot_check_image(P, H, W);
+    annot_check_scene(scene_depth, scene_index, scene_index, P, T);
+    bp::mask_boxes_host(depth, P, H, W, K, pixel_center, scene_depth, scene_index, delta, boxes, counts);
+    return 0;
+    BP_CATCH
+}
+
+int bp_mask_boxes(const float* d_depth, int P, int H, int W, const double* K, double pixel_center, const float* d_scene_depth,
+                  int T, const int* d_scene_index, double delta, int* d_boxes, int* d_counts, void* stream) {
+    BP_TRY
+    BP_CHECK(d_depth && K && d_boxes && d_counts, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(P < (1 << 28), "P must be below 2^28");
+    annot_check_scene_device(d_scene_depth, d_scene_index, P, T, (hipStream_t)stream);
+    bp::mask_boxes(d_depth, P, H, W, K, pixel_center, d_scene_depth, d_scene_index, delta, d_boxes, d_counts, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_vertex_boxes_host(const double* poses, int P, const double* vertices, int n, const double* K, int H, int W, int* boxes) {
+    BP_TRY
+    BP_CHECK(poses && vertices && K && boxes, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(n > 0, "n must be positive");
+    bp::vertex_boxes_host(poses, P, vertices, n, K, H, W, boxes);
+    return 0;
+    BP_CATCH
+}
+
+int bp_vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n, const double* K, int H, int W, int* d_boxes,
+                    void* stream) {
+    BP_TRY
+    BP_CHECK(d_poses && d_vertices && K && d_boxes, "null argument");
+    annot_check_image(P, H, W);
+    BP_CHECK(n > 0 && P < (1 << 28), "n must be positive and P below 2^28");
+    bp::vertex_boxes(d_poses, P, d_vertices, n, K, H, W, d_boxes, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
+                        int resW, const float* g, int size, float* out, int* centres, float* set_mask) {
+    BP_TRY
+    BP_CHECK(parts && ul && br && g && out && centres, "null argument");
+    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
+    bp::kpd_targets_host(parts, ul, br, B, Kp, inpH, inpW, resH, resW, g, size, out, centres, set_mask);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
+                   int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream) {
+    BP_TRY
+    BP_CHECK(d_parts && d_ul && d_br && d_g && d_out && d_centres, "null argument");
+    annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
+    bp::kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask,
+                    (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_icp_normal_equations_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                                 const double* K, const uint16_t* depth_test, int T, int H, int W, double depth_scale,
+                                 const int* test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                                 double* out) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && out, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
+    BP_CHECK(bp::icp_normal_equations_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z,
+                                           out) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_refine_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
+                         const uint16_t* depth_test, int T, int H, int W, double depth_scale, const int* test_index,
+                         int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                         double* poses_out, double* stats) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && depth_test && test_index && poses_out && stats, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
+    BP_CHECK(bp::refine_depth_host(poses, P, vertices, n, faces, F, K, depth_test, T, test_index, H, W, prm, near_z, poses_out,
+                                   stats) == 0,
+             "a face index lies outside [0, n)");
+    return 0;
+    BP_CATCH
+}
+
+int bp_icp_normal_equations(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P,
+                            const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale,
+                            const int* d_test_index, double max_dist, double min_cos, double pixel_center, double near_z,
+                            int chunk, double* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_out, "null argument");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(chunk >= 0, "chunk must not be negative");
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, 0, max_dist, min_cos, 0, pixel_center);
+    bp::icp_normal_equations(d_poses, P, d_model, n, d_faces, F, K, d_depth_test, T, d_test_index, H, W, prm, near_z, chunk, d_out,
+                             (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_refine_depth(const double* d_model, int n, const int* d_faces, int F, const double* d_poses, int P, const double* K,
+                    const uint16_t* d_depth_test, int T, int H, int W, double depth_scale, const int* d_test_index,
+                    int iterations, double max_dist, double min_cos, int min_pixels, double pixel_center, double near_z,
+                    int chunk, double* d_poses_out, double* d_stats, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && d_depth_test && d_test_index && d_poses_out && d_stats, "null argument");
+    BP_CHECK(d_poses_out != d_poses, "d_poses_out must not be d_poses: a rejected pose gets its input back");
+    raster_check_sizes(n, F, P, H, W, near_z);
+    BP_CHECK(chunk >= 0, "chunk must not be negative");
+    const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
+    bp::refine_depth(d_poses, P, d_model, n, d_faces, F, K, d_depth_test, T, d_test_index, H, W, prm, near_z, chunk, d_poses_out,
+                     d_stats, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+}  // extern "C"

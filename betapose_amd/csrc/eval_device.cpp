@@ -1,0 +1,264 @@
+// The device drivers of the evaluation tools: what one call of the pose metrics, the rasterisers, VSD, the annotator and
+// the depth refinement enqueues on device pointers -- the chunk-size rule, the workspaces, the launch sequence and the
+// closing synchronize (a driver's workspaces live in a local arena).  Arguments have been checked by the caller
+// (c_api_eval.cpp); the kernels are launched through the launchers of pose_tail.h, raster.h, annotate.h and icp.h.
+#include <algorithm>
+
+#include "annotate.h"
+#include "engine.h"
+#include "icp.h"
+#include "pose_tail.h"
+#include "raster.h"
+
+namespace bp {
+
+constexpr size_t RASTER_WS_BYTES = (size_t)256 << 20;      // what the chunked calls keep their workspaces under
+
+namespace {
+// The renders of one chunk of poses: `slots` z-buffers, posed meshes and skipped counters (zeroed here; nobody reads them)
+struct RasterChunk {
+    size_t HW;
+    uint32_t* zbuf;
+    void* ws;
+    int* skipped;
+    RasterChunk(Arena& a, int n, size_t slots, size_t HW, hipStream_t s)
+        : HW(HW), zbuf((uint32_t*)a.alloc_bytes(slots * HW * sizeof(uint32_t))), ws(a.alloc_bytes(raster_vertex_bytes(n, (int)slots))),
+          skipped((int*)a.alloc_bytes(slots * sizeof(int))) {
+        BP_HIP(hipMemsetAsync(skipped, 0, slots * sizeof(int), s));
+    }
+    // zbuf [(na + nb)][H][W] <- +inf, then poses_a[0 .. na) and poses_b[0 .. nb) drawn into it (launch_raster)
+    void draw(const double* model, int n, const int* faces, int F, const double* poses_a, int na, const double* poses_b, int nb,
+              const double* K, int H, int W, double pixel_center, double near_z, hipStream_t s) {
+        BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)(na + nb) * HW, s));   // +inf
+        launch_raster(model, n, faces, F, poses_a, na, poses_b, nb, K, H, W, pixel_center, near_z, ws, zbuf, skipped, s);
+    }
+};
+}  // namespace
+
+// ------------------------------------------------------------------ pose metrics
+void pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* K, int want,
+                 double* d_out, hipStream_t s) {
+    Arena a;
+    double* partial = (double*)a.alloc_bytes((size_t)P * pose_error_blocks(n) * 3 * sizeof(double));
+    launch_pose_errors(d_model, n, d_gt, d_est, P, K, want, partial, d_out, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // partials live in a local arena
+}
+
+void pose_errors_sym(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* d_sym, int S,
+                     const double* K, int want, double* d_out, hipStream_t s) {
+    Arena a;
+    double* scratch = (double*)a.alloc_bytes(pose_errors_sym_scratch_bytes(n, P, S));
+    launch_pose_errors_sym(d_model, n, d_gt, d_est, P, d_sym, S, K, want, scratch, d_out, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the per-symmetry maxima live in a local arena
+}
+
+// ------------------------------------------------------------------ depth and colour rasterisers
+void render_depth(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F, const double* K, int H,
+                  int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, hipStream_t s) {
+    const size_t HW = (size_t)H * W;
+    size_t chunk = RASTER_WS_BYTES / raster_vertex_bytes(n, 1);
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)P));
+    Arena a;
+    void* ws = a.alloc_bytes(raster_vertex_bytes(n, (int)chunk));
+    BP_HIP(hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)P * HW, s));   // +inf
+    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
+        const int c = (int)std::min(chunk, (size_t)P - p0);
+        launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, c, nullptr, 0, K, H, W, pixel_center, near_z, ws,
+                      (uint32_t*)d_depth + p0 * HW, d_skipped + p0, s);
+    }
+    launch_raster_finish((uint32_t*)d_depth, (size_t)P * HW, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the vertex workspace lives in a local arena
+}
+
+// poses [*p0, return) of the call go to images [i0, i1); *p0 on entry: the first pose not yet consumed
+static int raster_pose_range(const int* image_index, int P, int i1, int p0) {
+    if (!image_index) return std::min(P, i1);
+    int p = p0;
+    while (p < P && image_index[p] < i1) ++p;
+    return p;
+}
+
+void render_color(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F,
+                  const unsigned char* d_colors, const int* image_index, int I, const double* K, int H, int W,
+                  double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                  unsigned char* d_color, float* d_depth, int* d_skipped, hipStream_t s) {
+    const size_t HW = (size_t)H * W;
+    // images in flight: 8 bytes of key per pixel; poses in flight: their vertex workspace; each under RASTER_WS_BYTES
+    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 8), (size_t)I));
+    const size_t pchunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / raster_vertex_bytes(n, 1), (size_t)P));
+    Arena a;
+    unsigned long long* keys = (unsigned long long*)a.alloc_bytes(ichunk * HW * 8);
+    void* ws = a.alloc_bytes(raster_vertex_bytes(n, (int)pchunk));
+    int* d_index = nullptr;
+    if (image_index) {
+        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
+        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
+    const ColorLight lt{ambient, light[0], light[1], light[2]};
+    int p0 = 0;
+    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
+        const int m = (int)std::min(ichunk, (size_t)I - i0);
+        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
+        launch_color_clear(keys, d_depth + i0 * HW, accumulate, (size_t)m * HW, s);
+        for (int q0 = p0; q0 < p1; q0 += (int)pchunk) {
+            const int c = std::min((int)pchunk, p1 - q0);
+            launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, K, pixel_center, near_z, ws, s);
+            launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, K, H, W, pixel_center, near_z, keys,
+                                    d_skipped, s);
+        }
+        launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, K, H, W, pixel_center, near_z, lt,
+                             d_color + i0 * HW * 3, d_depth + i0 * HW, s);
+        p0 = p1;
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the keys and the vertex workspace live in a local arena
+}
+
+void draw_boxes(const double* d_poses, int P, const double* d_corners, const unsigned char* d_corner_colors,
+                const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
+                unsigned char* d_color, hipStream_t s) {
+    const size_t HW = (size_t)H * W;
+    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 4), (size_t)I));
+    Arena a;
+    uint32_t* ids = (uint32_t*)a.alloc_bytes(ichunk * HW * 4);
+    int* d_index = nullptr;
+    if (image_index) {
+        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
+        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    int p0 = 0;
+    for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
+        const int m = (int)std::min(ichunk, (size_t)I - i0);
+        const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
+        if (p1 > p0)
+            launch_draw_boxes(d_poses, p0, p1 - p0, d_corners, d_corner_colors, d_index, (int)i0, m, K, H, W, pixel_center,
+                              near_z, ids, d_color + i0 * HW * 3, s);
+        p0 = p1;
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the id planes live in a local arena
+}
+
+void overlay(const unsigned char* d_frames, const unsigned char* d_color, const float* d_depth, int I, int H, int W, int alpha,
+             unsigned char* d_out, hipStream_t s) {
+    launch_overlay(d_frames, d_color, d_depth, (size_t)I * H * W, alpha, d_out, s);
+    BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ VSD
+void vsd_errors(const double* d_model, int n, const int* d_faces, int F, const double* d_gt, const double* d_est, int P,
+                const double* K, const uint16_t* d_depth_test, int T, int H, int W, double depth_scale, const int* d_test_index,
+                double delta, const double* taus, int n_tau, double diameter, double pixel_center, double near_z, int chunk,
+                double* d_err, int* d_counts, hipStream_t s) {
+    const size_t HW = (size_t)H * W;
+    size_t c = (size_t)chunk;
+    if (c == 0)   // both workspaces (2 c z-buffers, 2 c posed meshes) under RASTER_WS_BYTES
+        c = std::min(RASTER_WS_BYTES / (2 * HW * sizeof(float)), RASTER_WS_BYTES / raster_vertex_bytes(n, 2));
+    c = std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+    VsdTaus tv{};
+    for (int k = 0; k < n_tau; ++k) tv.tau[k] = taus[k];
+    Arena a;
+    RasterChunk r(a, n, 2 * c, HW, s);
+    int* acc = (int*)a.alloc_bytes((size_t)P * VSD_ACC * sizeof(int));
+    BP_HIP(hipMemsetAsync(acc, 0, (size_t)P * VSD_ACC * sizeof(int), s));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        r.draw(d_model, n, d_faces, F, d_gt + p0 * 12, m, d_est + p0 * 12, m, K, H, W, pixel_center, near_z, s);
+        launch_vsd_reduce(r.zbuf, m, d_depth_test, T, d_test_index + p0, H, W, K, pixel_center, depth_scale, delta, tv, n_tau,
+                          diameter, acc + p0 * VSD_ACC, s);
+    }
+    launch_vsd_finish(acc, d_test_index, T, P, n_tau, d_err, d_counts, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders live in a local arena
+}
+
+// ------------------------------------------------------------------ the key-point annotator
+void annotate_keypoints(const double* d_poses, int P, const double* d_kp, int Kp, const double* K, int H, int W,
+                        double pixel_center, double near_z, const float* d_model_depth, const float* d_scene_depth,
+                        const int* d_scene_index, double self_tol, double delta, double* d_xy, double* d_z,
+                        unsigned char* d_flags, hipStream_t s) {
+    launch_annotate_keypoints(d_poses, P, d_kp, Kp, K, H, W, pixel_center, near_z, d_model_depth, d_scene_depth,
+                              d_scene_index, self_tol, delta, d_xy, d_z, d_flags, s);
+    BP_HIP(hipGetLastError());
+}
+
+void mask_boxes(const float* d_depth, int P, int H, int W, const double* K, double pixel_center, const float* d_scene_depth,
+                const int* d_scene_index, double delta, int* d_boxes, int* d_counts, hipStream_t s) {
+    Arena a;
+    int* acc = (int*)a.alloc_bytes((size_t)P * 2 * ANNOT_BOX_INTS * sizeof(int));
+    launch_mask_boxes(d_depth, P, H, W, K, pixel_center, d_scene_depth, d_scene_index, delta, acc, d_boxes, d_counts, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
+}
+
+void vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n, const double* K, int H, int W, int* d_boxes,
+                  hipStream_t s) {
+    Arena a;
+    int* acc = (int*)a.alloc_bytes((size_t)P * ANNOT_BOX_INTS * sizeof(int));
+    launch_vertex_boxes(d_poses, P, d_vertices, n, K, H, W, acc, d_boxes, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the accumulators live in a local arena
+}
+
+void kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
+                 int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, hipStream_t s) {
+    launch_kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask, s);
+    BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ depth refinement (ICP)
+// poses per chunk of the device calls: the z-buffers and the posed meshes of a chunk each stay under RASTER_WS_BYTES
+static size_t icp_chunk(int chunk, int n, int P, size_t HW) {
+    size_t c = (size_t)chunk;
+    if (c == 0) c = std::min(RASTER_WS_BYTES / (HW * sizeof(float)), RASTER_WS_BYTES / raster_vertex_bytes(n, 1));
+    return std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+}
+
+void icp_normal_equations(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F, const double* K,
+                          const uint16_t* d_depth_test, int T, const int* d_test_index, int H, int W, const IcpParams& prm,
+                          double near_z, int chunk, double* d_out, hipStream_t s) {
+    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
+    const int slices = icp_slices(H, W);
+    Arena a;
+    RasterChunk r(a, n, c, HW, s);
+    double* partial = (double*)a.alloc_bytes(c * slices * ICP_ACC * sizeof(double));
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        r.draw(d_model, n, d_faces, F, d_poses + p0 * 12, m, nullptr, 0, K, H, W, prm.c, near_z, s);
+        launch_icp_accumulate(r.zbuf, d_poses + p0 * 12, m, d_depth_test, T, d_test_index + p0, H, W, prm, nullptr, partial, s);
+        launch_icp_sum(partial, d_test_index + p0, T, m, slices, d_out + p0 * ICP_ACC, s);
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
+}
+
+void refine_depth(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F, const double* K,
+                  const uint16_t* d_depth_test, int T, const int* d_test_index, int H, int W, const IcpParams& prm, double near_z,
+                  int chunk, double* d_poses_out, double* d_stats, hipStream_t s) {
+    const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
+    const int slices = icp_slices(H, W);
+    Arena a;
+    RasterChunk r(a, n, c, HW, s);
+    double* partial = (double*)a.alloc_bytes(c * slices * ICP_ACC * sizeof(double));
+    launch_icp_init(d_poses, d_test_index, T, P, d_poses_out, d_stats, s);
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
+        const int m = (int)std::min(c, (size_t)P - p0);
+        double* pose = d_poses_out + p0 * 12;
+        double* stats = d_stats + p0 * ICP_STATS;
+        // the whole loop is enqueued: no host round trip between the iterations
+        for (int k = 0; k <= prm.iterations; ++k) {
+            r.draw(d_model, n, d_faces, F, pose, m, nullptr, 0, K, H, W, prm.c, near_z, s);
+            launch_icp_accumulate(r.zbuf, pose, m, d_depth_test, T, d_test_index + p0, H, W, prm, stats, partial, s);
+            launch_icp_step(partial, m, slices, k, prm, d_poses + p0 * 12, pose, stats, s);
+        }
+    }
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the renders and partial sums live in a local arena
+}
+
+}  // namespace bp

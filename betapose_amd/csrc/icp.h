@@ -1,6 +1,6 @@
 // Depth refinement of estimated poses (projective point-to-plane ICP against the test depth image): the declarations
-// shared by icp_host.cpp, icp.hip and c_api.cpp, so a signature that drifts fails to compile.  Needs no HIP header
-// (icp_host.cpp is plain C++): the stream type is declared as hip_runtime_api.h declares it.
+// shared by icp_host.cpp, icp.hip, eval_device.cpp and c_api_eval.cpp, so a signature that drifts fails to compile.  Needs
+// no HIP header (icp_host.cpp is plain C++): the stream type is declared as hip_runtime_api.h declares it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -44,5 +44,18 @@ void launch_icp_sum(const double* partial, const int* test_index, int T, int P, 
 // accumulation number k (0 .. iterations) of every pose still running: sum, guards, solve, update of poses [P][12] and stats
 void launch_icp_step(const double* partial, int P, int slices, int k, const IcpParams& prm, const double* poses_in,
                      double* poses, double* stats, hipStream_t s);
+
+// ---- eval_device.cpp: the device drivers (arguments checked by the caller): the host twins' arguments on device
+// pointers (K stays host) plus chunk (poses per pass, 0 = as many as keep the workspaces under 256 MB) and the stream.
+// refine_depth enqueues the whole iteration loop of a chunk (render, accumulate, step) without a host round trip; both
+// return when their work is done.
+#pragma GCC visibility push(hidden)     // the library's own: not in its dynamic symbol table
+void icp_normal_equations(const double* poses, int P, const double* model, int n, const int* faces, int F, const double* K,
+                          const uint16_t* depth_test, int T, const int* test_index, int H, int W, const IcpParams& prm,
+                          double near, int chunk, double* out, hipStream_t s);
+void refine_depth(const double* poses, int P, const double* model, int n, const int* faces, int F, const double* K,
+                  const uint16_t* depth_test, int T, const int* test_index, int H, int W, const IcpParams& prm, double near,
+                  int chunk, double* poses_out, double* stats, hipStream_t s);
+#pragma GCC visibility pop
 
 }  // namespace bp

@@ -1,7 +1,8 @@
 // The pose tail's shared declarations: record constants (from include/betapose_hip.h), the launch-argument structs, the
-// host solvers of host_post.cpp and the launchers of the pose units.  Included by c_api.cpp and by every unit that
-// defines one of these functions, so a signature that drifts fails to compile.  Needs no HIP header (host_post.cpp also
-// builds as plain C++): the stream type is declared as hip_runtime_api.h declares it.
+// host solvers of host_post.cpp and the launchers of the pose units.  Included by the units that call them (c_api.cpp
+// through frame_chain.h, c_api_pose.cpp, c_api_eval.cpp, eval_device.cpp) and by every unit that defines one of these
+// functions, so a signature that drifts fails to compile.  Needs no HIP header (host_post.cpp also builds as plain C++):
+// the stream type is declared as hip_runtime_api.h declares it.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -61,6 +62,14 @@ void launch_pose_errors(const double* model, int n, const double* gt, const doub
 size_t pose_errors_sym_scratch_bytes(int n, int P, int S);
 void launch_pose_errors_sym(const double* model, int n, const double* gt, const double* est, int P, const double* sym,
                             int S, const double* K, int want, double* scratch, double* out, hipStream_t s);
+// ---- eval_device.cpp: the two launches above with their scratch brought along (arguments checked by the caller); they
+// return when the work is done
+#pragma GCC visibility push(hidden)     // the library's own: not in its dynamic symbol table
+void pose_errors(const double* model, int n, const double* gt, const double* est, int P, const double* K, int want,
+                 double* out, hipStream_t s);
+void pose_errors_sym(const double* model, int n, const double* gt, const double* est, int P, const double* sym, int S,
+                     const double* K, int want, double* out, hipStream_t s);
+#pragma GCC visibility pop
 // ---- pose_tail.hip
 void launch_solve_pnp_batch(const double* pts3d, int shared_3d, const double* pts2d, int n, int P, const PnpCam& cam,
                             double* Rt, int* status, hipStream_t s);

@@ -1,6 +1,6 @@
-// Depth rasteriser and VSD: the declarations shared by raster_host.cpp, raster.hip, vsd.hip and c_api.cpp, so a signature
-// that drifts fails to compile.  Needs no HIP header (raster_host.cpp is plain C++): the stream type is declared as
-// hip_runtime_api.h declares it.
+// Depth rasteriser and VSD: the declarations shared by raster_host.cpp, raster.hip, vsd.hip, eval_device.cpp and
+// c_api_eval.cpp, so a signature that drifts fails to compile.  Needs no HIP header (raster_host.cpp is plain C++): the
+// stream type is declared as hip_runtime_api.h declares it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -85,5 +85,25 @@ void launch_vsd_reduce(const uint32_t* zbuf, int pairs, const uint16_t* depth_te
                        double diameter, int* acc, hipStream_t s);
 // err [P][n_tau], counts [P][4] from acc [P][VSD_ACC]; a pair whose test_index lies outside [0, T) gets NaN and -1
 void launch_vsd_finish(const int* acc, const int* test_index, int T, int P, int n_tau, double* err, int* counts, hipStream_t s);
+
+// ---- eval_device.cpp: the device drivers, one per device call of include/betapose_hip.h (arguments checked by the
+// caller).  The host twins' arguments on device pointers (image_index, K, light and taus stay host) plus the stream;
+// chunk: poses per pass, 0 = as many as keep the workspaces under 256 MB.  A driver that needs a workspace returns when its work is done; the others only enqueue.
+#pragma GCC visibility push(hidden)     // the library's own: not in its dynamic symbol table
+void render_depth(const double* poses, int P, const double* model, int n, const int* faces, int F, const double* K, int H,
+                  int W, double pixel_center, double near, float* depth, int* skipped, hipStream_t s);
+void render_color(const double* poses, int P, const double* model, int n, const int* faces, int F, const unsigned char* colors,
+                  const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near,
+                  double ambient, const double* light, int accumulate, unsigned char* color, float* depth, int* skipped,
+                  hipStream_t s);
+void draw_boxes(const double* poses, int P, const double* corners, const unsigned char* corner_colors, const int* image_index,
+                int I, const double* K, int H, int W, double pixel_center, double near, unsigned char* color, hipStream_t s);
+void overlay(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,
+             unsigned char* out, hipStream_t s);
+void vsd_errors(const double* model, int n, const int* faces, int F, const double* gt, const double* est, int P, const double* K,
+                const uint16_t* depth_test, int T, int H, int W, double depth_scale, const int* test_index, double delta,
+                const double* taus, int n_tau, double diameter, double pixel_center, double near, int chunk, double* err,
+                int* counts, hipStream_t s);
+#pragma GCC visibility pop
 
 }  // namespace bp

@@ -2,6 +2,7 @@
 fixtures were generated from (tools/make_golden.py)."""
 import functools
 import os
+import re
 
 import numpy as np
 
@@ -30,6 +31,17 @@ def kpd_state_dict():
 @functools.lru_cache(None)
 def frames(n=4):
     return synth.synth_frames(n, FRAME_SEED)
+
+
+@functools.lru_cache(None)
+def header_code():
+    """include/betapose_hip.h with its comments stripped: what the compiler sees of the C ABI."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "betapose_hip.h")).read(), flags=re.S)
+
+
+def header_names():
+    """Every ``bp_*`` function the header declares."""
+    return set(re.findall(r"\b(bp_[a-z0-9_]+)\s*\(", header_code()))
 
 
 def golden(name):

@@ -114,9 +114,7 @@ def test_bn_folding_matches_torch():
 
 def test_library_exports_every_declared_symbol():
     """The C-ABI library loads (no GPU needed) and exports exactly what include/betapose_hip.h declares."""
-    header = open(os.path.join(ROOT, "include", "betapose_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    declared = set(re.findall(r"\b(bp_[a-z0-9_]+)\s*\(", header))
+    declared = helpers.header_names()
     assert len(declared) >= 35
     lib = _lib.lib()
     for name in sorted(declared):
@@ -160,6 +158,25 @@ def test_twin_entry_points_answer_a_null_handle(prefix):
         assert fn(None, *((ctypes.byref(out),) if op == "clone" else args)) == -1, op
         assert lib.bp_last_error() == b"null argument", (op, lib.bp_last_error())
         assert not out.value
+
+
+def test_last_error_is_one_string_for_the_whole_library():
+    """The entry points live in five c_api*.cpp units and bp_last_error() in one of them: whichever unit refuses a call,
+    its text is what bp_last_error() answers.  One entry point per unit, each refusing a null first pointer before any
+    device call.  These five make the check with BP_CHECK, whose text is the message, the failed condition and the
+    place: "null argument (<condition>) @<path>/<unit>:<line>" -- so the message is matched from the start up to the
+    condition, and the place tells that the text is this call's and this unit's."""
+    lib = _lib.lib()
+    for name, unit in (("bp_upload", b"c_api.cpp"), ("bp_conv2d_planes", b"c_api_conv.cpp"), ("bp_solve_pnp", b"c_api_pose.cpp"),
+                       ("bp_render_depth", b"c_api_eval.cpp"), ("bp_png_info", b"c_api_io.cpp")):
+        fn = getattr(lib, name)
+        nulls = [0 if t in (ctypes.c_int, ctypes.c_size_t, ctypes.c_double) else None for t in fn.argtypes]
+        assert nulls[0] is None
+        assert lib.bp_heatmap_argmax(None, 0, 0, 0, 0, None, None) == -1    # leaves another text in bp_last_error()
+        assert lib.bp_last_error().startswith(b"bad argument (")
+        assert fn(*nulls) == -1, name
+        text = lib.bp_last_error()
+        assert text.startswith(b"null argument (") and b"/" + unit + b":" in text, (name, text)
 
 
 def test_product_path_fails_loudly_without_gpu():

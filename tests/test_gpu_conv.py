@@ -677,7 +677,7 @@ def test_conv_halo_full_size_layers(cuda):
 
 # ---- the fp16-skip-connection launch form of every kernel family, alone.  In the engine's 'f16r' mode a convolution launch differs from a
 # plain fp16 launch in two fields: ConvParams::res16 (the skip connection is read from the fp16 plane of the residual tensor, 2 bytes per
-# element) and ConvParams::skip_f32 (the fp32 store is dropped, only the fp16 plane is written).  BP_CONV_F16R=1 (c_api.cpp bp_conv2d_planes,
+# element) and ConvParams::skip_f32 (the fp32 store is dropped, only the fp16 plane is written).  BP_CONV_F16R=1 (c_api_conv.cpp bp_conv2d_planes,
 # read on every call) makes exactly that launch: the residual is rounded to its plane by the hook, and with planes=True the fp32 store goes.
 #
 # The oracle needs no tolerance of its own.  R is an fp32 randn residual (almost no element is an fp16 number), R16 = fp16(R) widened.  Per

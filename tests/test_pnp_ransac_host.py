@@ -184,7 +184,7 @@ def test_flag_parses():
 
 
 def test_new_prototypes_compile_as_c99(tmp_path):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "betapose_hip.h")).read(), flags=re.S)
+    header = helpers.header_code()
     for name in ("bp_pnp_ransac_samples", "bp_pnp_ransac_trials_needed", "bp_pnp_ransac_workspace_bytes",
                  "bp_solve_pnp_ransac_batch", "bp_pipeline_set_pose_ransac", "bp_pose_ransac_workspace_bytes",
                  "bp_pose_from_records_ransac"):

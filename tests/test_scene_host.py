@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import helpers
 from betapose_amd import _lib, cfg as Cfg
 from betapose_amd.darknet import Darknet, check_class_ids
 from betapose_amd.opt import LINEMOD_IDS, build_parser, class_map, id_list, shared_detector_arg
@@ -59,7 +60,7 @@ def test_library_exports_the_scene_entry_points():
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
     syms = subprocess.run([nm, "-D", _lib.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
     exported = set(re.findall(r"\bT (bp_\w+)", syms))
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "betapose_hip.h")).read(), flags=re.S)
+    header = helpers.header_code()
     for name in SYMBOLS:
         assert name in exported, name
         assert re.search(r"\b%s\s*\(" % name, header), name
