@@ -145,6 +145,13 @@ PROTOTYPES = {
                                  vp]),
     "bp_kpd_targets_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp,
                                       vp]),
+    "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
+    "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
+    "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),
+    "bp_farthest_points": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "bp_farthest_points_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_thin_points": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "bp_thin_points_host": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "bp_icp_normal_equations": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp]),
     "bp_icp_normal_equations_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,

@@ -6,6 +6,7 @@
 
 #include "annotate.h"
 #include "c_api_util.h"
+#include "designate.h"
 #include "icp.h"
 #include "pose_tail.h"
 #include "raster.h"
@@ -95,6 +96,27 @@ static bp::IcpParams icp_params(const double* K, int T, double depth_scale, int 
     BP_CHECK(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must lie in [0, 1]");
     BP_CHECK(iterations >= 0 && iterations <= 1000 && min_pixels >= 0, "iterations must lie in 0 .. 1000, min_pixels >= 0");
     return bp::IcpParams{K[0], K[4], K[2], K[5], pixel_center, depth_scale, max_dist, min_cos, min_pixels, iterations};
+}
+
+// ---- the key-point designator (designate.hip / designate_host.cpp)
+static void designate_check_octave(int n, int field, const double* scales, int ns, int k, double min_contrast) {
+    BP_CHECK(n >= 1 && n <= bp::DESIGNATE_MAX_OCTAVE, "n must lie in [1, 131072]");
+    BP_CHECK(field >= 0 && field <= 2, "field must be 0, 1 or 2 (x, y or z)");
+    BP_CHECK(ns >= 4 && ns <= DESIGNATE_MAX_SCALES, "ns must lie in [4, 12]");
+    BP_CHECK(k >= 1 && k <= bp::DESIGNATE_MAX_K, "k must lie in [1, 64]");
+    BP_CHECK(min_contrast >= 0.0, "min_contrast must not be negative");
+    for (int i = 0; i < ns; ++i)
+        BP_CHECK(scales[i] > 0.0 && scales[i] <= 1e150 && (i == 0 || scales[i] >= scales[i - 1]),
+                 "the scales must be positive, finite and ascending");
+}
+static void designate_check_fps(int n, int K, int start) {
+    BP_CHECK(n >= 1 && n <= bp::DESIGNATE_MAX_FPS, "n must lie in [1, 2^20]");
+    BP_CHECK(K >= 1 && K <= n, "K must lie in [1, n]");
+    BP_CHECK(start < n, "start must be below n (negative: the point farthest from the centroid)");
+}
+static void designate_check_thin(int n, int keep) {
+    BP_CHECK(n >= 1 && n <= bp::DESIGNATE_MAX_THIN, "n must lie in [1, 16384]");
+    BP_CHECK(keep >= 1, "keep must be positive");
 }
 
 extern "C" {
@@ -383,6 +405,72 @@ int bp_refine_depth(const double* d_model, int n, const int* d_faces, int F, con
     const bp::IcpParams prm = icp_params(K, T, depth_scale, iterations, max_dist, min_cos, min_pixels, pixel_center);
     bp::refine_depth(d_poses, P, d_model, n, d_faces, F, K, d_depth_test, T, d_test_index, H, W, prm, near_z, chunk, d_poses_out,
                      d_stats, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_voxel_grid_host(const double* points, int n, double leaf, double* out, int* n_out) {
+    BP_TRY
+    BP_CHECK(points && out && n_out, "null argument");
+    BP_CHECK(n >= 1, "n must be positive");
+    BP_CHECK(leaf > 0.0 && leaf <= 1e300, "leaf must be positive and finite");
+    bp::voxel_grid_host(points, n, leaf, out, n_out);
+    return 0;
+    BP_CATCH
+}
+
+int bp_sift_octave_host(const double* points, int n, int field, const double* scales, int ns, int k, double min_contrast,
+                        double* dog, signed char* flags) {
+    BP_TRY
+    BP_CHECK(points && scales && dog && flags, "null argument");
+    designate_check_octave(n, field, scales, ns, k, min_contrast);
+    bp::sift_octave_host(points, n, field, scales, ns, k, min_contrast, dog, flags);
+    return 0;
+    BP_CATCH
+}
+
+int bp_sift_octave(const double* d_points, int n, int field, const double* scales, int ns, int k, double min_contrast,
+                   double* d_dog, signed char* d_flags, void* stream) {
+    BP_TRY
+    BP_CHECK(d_points && scales && d_dog && d_flags, "null argument");
+    designate_check_octave(n, field, scales, ns, k, min_contrast);
+    bp::sift_octave(d_points, n, field, scales, ns, k, min_contrast, d_dog, d_flags, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_farthest_points_host(const double* points, int n, int K, int start, int* idx, double* d2) {
+    BP_TRY
+    BP_CHECK(points && idx && d2, "null argument");
+    designate_check_fps(n, K, start);
+    bp::farthest_points_host(points, n, K, start, idx, d2);
+    return 0;
+    BP_CATCH
+}
+
+int bp_farthest_points(const double* d_points, int n, int K, int start, int* d_idx, double* d_d2, void* stream) {
+    BP_TRY
+    BP_CHECK(d_points && d_idx && d_d2, "null argument");
+    designate_check_fps(n, K, start);
+    bp::farthest_points(d_points, n, K, start, d_idx, d_d2, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_thin_points_host(const double* points, int n, int keep, unsigned char* alive, int* state) {
+    BP_TRY
+    BP_CHECK(points && alive && state, "null argument");
+    designate_check_thin(n, keep);
+    bp::thin_points_host(points, n, keep, alive, state);
+    return 0;
+    BP_CATCH
+}
+
+int bp_thin_points(const double* d_points, int n, int keep, unsigned char* d_alive, int* d_state, void* stream) {
+    BP_TRY
+    BP_CHECK(d_points && d_alive && d_state, "null argument");
+    designate_check_thin(n, keep);
+    bp::thin_points(d_points, n, keep, d_alive, d_state, (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "annotate.h"
+#include "designate.h"
 #include "engine.h"
 #include "icp.h"
 #include "pose_tail.h"
@@ -209,6 +210,31 @@ void kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, in
                  int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, hipStream_t s) {
     launch_kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask, s);
     BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ the key-point designator
+void sift_octave(const double* d_points, int n, int field, const double* scales, int ns, int k, double min_contrast,
+                 double* d_dog, signed char* d_flags, hipStream_t s) {
+    launch_sift_octave(d_points, n, field, scales, ns, k, min_contrast, d_dog, d_flags, s);
+    BP_HIP(hipGetLastError());
+}
+
+void farthest_points(const double* d_points, int n, int K, int start, int* d_idx, double* d_d2, hipStream_t s) {
+    Arena a;
+    double* mind = (double*)a.alloc_bytes((size_t)n * sizeof(double));
+    launch_farthest_points(d_points, n, K, start, mind, d_idx, d_d2, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the minimum distances live in a local arena
+}
+
+void thin_points(const double* d_points, int n, int keep, unsigned char* d_alive, int* d_state, hipStream_t s) {
+    Arena a;
+    double* nn_d = (double*)a.alloc_bytes((size_t)n * sizeof(double));
+    int* nn_j = (int*)a.alloc_bytes((size_t)n * sizeof(int));
+    int* list = (int*)a.alloc_bytes((size_t)n * sizeof(int));
+    launch_thin_points(d_points, n, keep, nn_d, nn_j, list, d_alive, d_state, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));   // the neighbour table lives in a local arena
 }
 
 // ------------------------------------------------------------------ depth refinement (ICP)

@@ -56,6 +56,10 @@
  *   bp_kpd_targets, bp_kpd_targets_host
  *                          generateSampleBox's label half: transformBox +    train_KPD/src/utils/pose.py:113-126
  *                          drawGaussian per part                               train_KPD/src/utils/img.py:61-110
+ *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
+ *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
+ *                          from its published description, never compared with PCL), a farthest-point alternative,
+ *                          and Model3D.refine without its [n][n][3] arrays             utils/model.py:29-46
  *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
  *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
@@ -394,6 +398,40 @@ int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, 
                    int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream);
 int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
                         int resW, const float* g, int size, float* out, int* centres, float* set_mask);
+/* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
+ * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
+ * its _host twin, which needs no GPU.
+ *
+ * bp_voxel_grid_host: the centroid of every occupied cell of a grid of size `leaf` (cell floor(p / leaf) per axis), the
+ * cells in ascending key x + y * dx + z * dx * dy; out [n][3] receives *n_out rows.  When the grid has more than
+ * INT32_MAX cells the cloud is copied through unchanged (PCL's "leaf size is too small").  Host only.
+ *
+ * bp_sift_octave: one octave of the 3-D SIFT detector on the scalar field `field` (0, 1, 2: the x, y or z coordinate).
+ * scales [ns] (host, positive, ascending, 4 <= ns <= 12) are the Gaussian sigmas.  G_i(p) is the mean of the field over
+ * the points q with d2 = |p - q|^2 <= 9 sigma_i^2 under the weights exp(-d2 / (2 sigma_i^2)) (an exponential of the
+ * library's own, within 1e-14 of libm's); d_dog [n][ns-1] = G_{j+1} - G_j.  d_flags [n][ns-3] int8: entry j-1 is -1 / +1
+ * where DoG[p][j] is at least min_contrast in magnitude, strictly below / above DoG[p][j-1] and DoG[p][j+1], and not
+ * above / below any of DoG[q][j-1 .. j+1] over the min(k, n) nearest points q (p among them, 1 <= k <= 64); 0
+ * elsewhere.  All pairs are visited: n <= 131072.  Enqueued on `stream` without synchronising it.
+ *
+ * bp_farthest_points: K <= n <= 2^20 indices d_idx [K], the first `start` (negative: the point farthest from the
+ * centroid), each next one the point with the largest squared distance to those chosen so far; d_d2 [K] is that
+ * distance (for the first: its squared distance from the centroid).  Synchronises `stream`.
+ *
+ * bp_thin_points: Model3D.refine's rounds, n - keep of them (n <= 16384): delete the first point, in row-major pair
+ * order, of the pair with the smallest distance sqrt(d2).  The rounds stop early at the first one whose smallest
+ * distance is not below 100.0, from where the reference deletes a carried position over and over (the caller does
+ * that).  d_alive [n] uint8: 1 for a survivor; d_state [2] int32: the rounds done and the position, among the survivors
+ * before it was deleted, of the last deleted point (0 when none was).  Synchronises `stream`. */
+int bp_voxel_grid_host(const double* points, int n, double leaf, double* out, int* n_out);
+int bp_sift_octave(const double* d_points, int n, int field, const double* scales, int ns, int k, double min_contrast,
+                   double* d_dog, signed char* d_flags, void* stream);
+int bp_sift_octave_host(const double* points, int n, int field, const double* scales, int ns, int k, double min_contrast,
+                        double* dog, signed char* flags);
+int bp_farthest_points(const double* d_points, int n, int K, int start, int* d_idx, double* d_d2, void* stream);
+int bp_farthest_points_host(const double* points, int n, int K, int start, int* idx, double* d2);
+int bp_thin_points(const double* d_points, int n, int keep, unsigned char* d_alive, int* d_state, void* stream);
+int bp_thin_points_host(const double* points, int n, int keep, unsigned char* alive, int* state);
 /* Depth refinement of P estimated poses of one mesh: projective point-to-plane ICP of the mesh's render (as
  * bp_render_depth draws it) against the test depth image d_test_index[p] of d_depth_test [T][H][W] uint16 (depth =
  * raw * depth_scale in pose units, 0 = missing).  Up to `iterations` times: render at the current pose; every pixel
