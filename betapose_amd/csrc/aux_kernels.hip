@@ -1,7 +1,7 @@
 // Small HBM-bound kernels around the convolutions (gfx950): layout changes,
 // max-pool, residual add, nearest upsample, PixelShuffle, SE squeeze/excite,
-// YOLO head decode + objectness arg-max, heat-map arg-max, device-side crop and
-// Pillow-exact bicubic resize.  64-wide wavefront reductions via __shfl_down.
+// heat-map arg-max, device-side crop and Pillow-exact bicubic resize.  64-wide
+// wavefront reductions via __shfl_down.  (The detector's tail is yolo_tail.hip.)
 #include "bp_common.h"
 
 namespace bp {
@@ -21,12 +21,6 @@ __device__ __forceinline__ void store_plane(unsigned short* planes, long long id
         planes[idx + plane_elems] = __builtin_bit_cast(unsigned short, h2);
         planes[idx + 2 * plane_elems] = __builtin_bit_cast(unsigned short, h3);
     }
-}
-
-static inline int grid_for(long long n, int block = 256, int cap = 4096) {
-    BP_CHECK(n < (1ll << 31), "tensor too large for 32-bit indexing");
-    long long g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 // ---------------------------------------------------------------- layout
@@ -280,505 +274,6 @@ void launch_fc(const float* in, const float* w, const float* bias, float* out, i
     BP_CHECK(Cin % 4 == 0 && Cin * 4 <= 64 * 1024, "fc: Cin % 4, Cin <= 16384");
     hipLaunchKernelGGL(fc_kernel, dim3((Cout + FC_PER_BLOCK - 1) / FC_PER_BLOCK, N), dim3(256), (size_t)Cin * 4 * (Cin <= 512 ? 4 : 1), s, in, w,
                        bias, out, Cin, Cout, act, in_parts, in_scale);
-}
-
-// ---------------------------------------------------------------- YOLO head decode (yolo/darknet.py:129-169)
-struct YoloHeads {
-    YoloHead h[4];
-    int n;
-};
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-__global__ void yolo_decode_kernel(YoloHeads hs, int N, int reso, int attrs, int rows, float* __restrict__ pred) {
-    const long long total = (long long)N * rows;
-    // 32-bit index math: every tensor on this path has < 2^31 elements (checked by the launchers), and 64-bit
-    // div/mod costs ~100 instructions on gfx950
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < (int)total; e += gridDim.x * blockDim.x) {
-        const int row = (int)(e % rows);
-        const int n = (int)(e / rows);
-        int hi = 0;
-        for (int k = 1; k < hs.n; ++k)
-            if (row >= hs.h[k].row_off) hi = k;
-        const YoloHead& H = hs.h[hi];
-        const int g = H.g;
-        const int r = row - H.row_off;
-        const int a = r / (g * g);
-        const int cell = r - a * g * g;
-        const int gy = cell / g, gx = cell - gy * g;
-        const float stride = (float)(reso / g);
-        const float* t = H.t + ((long long)n * g * g + cell) * (3 * attrs) + a * attrs;
-        float* o = pred + e * attrs;
-        // anchors are divided by the stride then the box is multiplied back (darknet.py:151,165)
-        o[0] = (sigmoidf_(t[0]) + (float)gx) * stride;
-        o[1] = (sigmoidf_(t[1]) + (float)gy) * stride;
-        o[2] = (expf(t[2]) * (H.aw[a] / stride)) * stride;
-        o[3] = (expf(t[3]) * (H.ah[a] / stride)) * stride;
-        for (int k = 4; k < attrs; ++k) o[k] = sigmoidf_(t[k]);
-    }
-}
-void launch_yolo_decode(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float* pred,
-                        hipStream_t s) {
-    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
-    YoloHeads hs;
-    hs.n = nheads;
-    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
-    hipLaunchKernelGGL(yolo_decode_kernel, dim3(grid_for((long long)N * rows)), dim3(256), 0, s, hs, N, reso, attrs, rows, pred);
-}
-
-// write_results with nms=False (yolo/util.py:118-223): per image the arg-max objectness row (first on
-// ties) among rows with obj > conf whose arg-max class is 0.  One block per image.
-__global__ __launch_bounds__(1024) void yolo_select_kernel(const float* __restrict__ pred, int rows, int attrs,
-                                                            float conf, int num_classes, float* __restrict__ sel, int sel_ld) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    const int n = blockIdx.x;
-    const float* P = pred + (long long)n * rows * attrs;
-    const int ncls = min(num_classes, attrs - 5);
-    float best = -1.f;
-    int bi = 0x7fffffff;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        const float* q = P + (long long)r * attrs;
-        const float obj = q[4];
-        if (!(obj > conf)) continue;
-        // class arg-max over the masked row (first max wins); only class 0 rows are kept
-        int cls = 0;
-        float cm = q[5];
-        for (int k = 1; k < ncls; ++k)
-            if (q[5 + k] > cm) { cm = q[5 + k]; cls = k; }
-        if (cls != 0) continue;
-        if (obj > best || (obj == best && r < bi)) { best = obj; bi = r; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_down(best, off, 64);
-        const int oi = __shfl_down(bi, off, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        float* o = sel + (long long)n * sel_ld;
-        if (best < 0.f) {
-            o[0] = __int_as_float(-1);
-            for (int k = 1; k < 8; ++k) o[k] = 0.f;
-        } else {
-            const float* q = P + (long long)bi * attrs;
-            o[0] = __int_as_float(bi);
-            o[1] = q[0] - q[2] / 2;
-            o[2] = q[1] - q[3] / 2;
-            o[3] = q[0] + q[2] / 2;
-            o[4] = q[1] + q[3] / 2;
-            o[5] = q[4];
-            o[6] = q[5];
-            o[7] = 0.f;
-        }
-    }
-}
-void launch_yolo_select(const float* pred, int N, int rows, int attrs, float conf, int num_classes, float* sel,
-                        hipStream_t s, int sel_ld) {
-    hipLaunchKernelGGL(yolo_select_kernel, dim3(N), dim3(1024), 0, s, pred, rows, attrs, conf, num_classes, sel, sel_ld);
-}
-
-// DetectionLayer.forward + write_results in ONE launch (round 4, node diet): when nobody asks for the [rows][attrs] prediction
-// tensor -- the fused per-frame pipeline reads the select record only -- every thread decodes the objectness and class scores of its
-// rows from the head tensors with the SAME float operations as yolo_decode_kernel, the block reduces with the same first-max rule
-// as yolo_select_kernel, and thread 0 decodes the winner's box.  Identical records by construction (asserted in
-// tests/test_gpu_stages.py against the two-kernel path).
-__global__ __launch_bounds__(1024) void yolo_decode_select_kernel(YoloHeads hs, int reso, int attrs, int rows, float conf, int num_classes,
-                                                                   float* __restrict__ sel, int sel_ld) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    const int n = blockIdx.x;
-    const int ncls = min(num_classes, attrs - 5);
-    auto locate = [&](int row, int* a) -> const float* {
-        int hi = 0;
-        for (int k = 1; k < hs.n; ++k)
-            if (row >= hs.h[k].row_off) hi = k;
-        const YoloHead& H = hs.h[hi];
-        const int g = H.g, r = row - H.row_off;
-        *a = r / (g * g);
-        const int cell = r - *a * g * g;
-        return H.t + ((long long)n * g * g + cell) * (3 * attrs) + *a * attrs;
-    };
-    float best = -1.f;
-    int bi = 0x7fffffff;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        int a;
-        const float* t = locate(r, &a);
-        const float obj = sigmoidf_(t[4]);
-        if (!(obj > conf)) continue;
-        int cls = 0;
-        float cm = sigmoidf_(t[5]);
-        for (int k = 1; k < ncls; ++k) {
-            const float v = sigmoidf_(t[5 + k]);
-            if (v > cm) { cm = v; cls = k; }
-        }
-        if (cls != 0) continue;
-        if (obj > best || (obj == best && r < bi)) { best = obj; bi = r; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_down(best, off, 64);
-        const int oi = __shfl_down(bi, off, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        float* o = sel + (long long)n * sel_ld;
-        if (best < 0.f) {
-            o[0] = __int_as_float(-1);
-            for (int k = 1; k < 8; ++k) o[k] = 0.f;
-        } else {
-            int a, hi = 0;
-            const float* t = locate(bi, &a);
-            for (int k = 1; k < hs.n; ++k)
-                if (bi >= hs.h[k].row_off) hi = k;
-            const YoloHead& H = hs.h[hi];
-            const int g = H.g, r = bi - H.row_off, cell = r - a * g * g;
-            const int gy = cell / g, gx = cell - gy * g;
-            const float stride = (float)(reso / g);
-            const float q0 = (sigmoidf_(t[0]) + (float)gx) * stride;
-            const float q1 = (sigmoidf_(t[1]) + (float)gy) * stride;
-            const float q2 = (expf(t[2]) * (H.aw[a] / stride)) * stride;
-            const float q3 = (expf(t[3]) * (H.ah[a] / stride)) * stride;
-            o[0] = __int_as_float(bi);
-            o[1] = q0 - q2 / 2;
-            o[2] = q1 - q3 / 2;
-            o[3] = q0 + q2 / 2;
-            o[4] = q1 + q3 / 2;
-            o[5] = sigmoidf_(t[4]);
-            o[6] = sigmoidf_(t[5]);
-            o[7] = 0.f;
-        }
-    }
-}
-void launch_yolo_decode_select(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
-                               float* sel, hipStream_t s, int sel_ld) {
-    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
-    YoloHeads hs;
-    hs.n = nheads;
-    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
-    hipLaunchKernelGGL(yolo_decode_select_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, sel, sel_ld);
-}
-
-// ---------------------------------------------------------------- per-class select (shared multi-class detector)
-// write_results(nms=False) with the class filter generalised: the row's arg-max class (first maximum wins) is looked up in
-// a list of up to BP_MAX_SCENE_CLASSES class ids, and the row competes for that list slot only.  ONE pass over the rows: every
-// thread keeps a (objectness, row) pair per slot in registers (constant indices: the slot loops are unrolled), the slots
-// are reduced wave by wave with shuffles and across waves through LDS, and thread k writes slot k's record.  Row sources:
-// the decoded [rows][attrs] tensor (PredRows) or the head tensors (HeadRows), with the float operations of
-// yolo_select_kernel / yolo_decode_select_kernel -- with the list {0} the record is theirs bit for bit.
-struct PredRows {
-    const float* P;   // this image's [rows][attrs]
-    int attrs;
-    __device__ __forceinline__ const float* row(int r) const { return P + (long long)r * attrs; }
-    __device__ __forceinline__ float attr(const float* q, int k) const { return q[k]; }   // k >= 4: objectness, class scores
-    __device__ __forceinline__ void box(int, const float* q, float* b) const { b[0] = q[0]; b[1] = q[1]; b[2] = q[2]; b[3] = q[3]; }
-};
-struct HeadRows {
-    const YoloHeads* hs;
-    int n, attrs, reso;
-    __device__ __forceinline__ int head_of(int r) const {
-        int hi = 0;
-        for (int k = 1; k < hs->n; ++k)
-            if (r >= hs->h[k].row_off) hi = k;
-        return hi;
-    }
-    __device__ __forceinline__ const float* row(int r) const {
-        const YoloHead& H = hs->h[head_of(r)];
-        const int g = H.g, rr = r - H.row_off;
-        const int a = rr / (g * g);
-        const int cell = rr - a * g * g;
-        return H.t + ((long long)n * g * g + cell) * (3 * attrs) + a * attrs;
-    }
-    __device__ __forceinline__ float attr(const float* t, int k) const { return sigmoidf_(t[k]); }
-    __device__ __forceinline__ void box(int r, const float* t, float* b) const {
-        const YoloHead& H = hs->h[head_of(r)];
-        const int g = H.g, rr = r - H.row_off;
-        const int a = rr / (g * g);
-        const int cell = rr - a * g * g;
-        const int gy = cell / g, gx = cell - gy * g;
-        const float stride = (float)(reso / g);
-        b[0] = (sigmoidf_(t[0]) + (float)gx) * stride;
-        b[1] = (sigmoidf_(t[1]) + (float)gy) * stride;
-        b[2] = (expf(t[2]) * (H.aw[a] / stride)) * stride;
-        b[3] = (expf(t[3]) * (H.ah[a] / stride)) * stride;
-    }
-};
-template <class Rows>
-__device__ __forceinline__ void select_classes(const Rows& src, int rows, float conf, int ncls, const YoloClassList& cl,
-                                               float* __restrict__ out, int ld_slot, float (*sv)[16], int (*si)[16]) {
-    constexpr int S = BP_MAX_SCENE_CLASSES;
-    float best[S];
-    int bi[S];
-#pragma unroll
-    for (int k = 0; k < S; ++k) { best[k] = -1.f; bi[k] = 0x7fffffff; }
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        const float* q = src.row(r);
-        const float obj = src.attr(q, 4);
-        if (!(obj > conf)) continue;
-        int cls = 0;
-        float cm = src.attr(q, 5);
-        for (int k = 1; k < ncls; ++k) {
-            const float v = src.attr(q, 5 + k);
-            if (v > cm) { cm = v; cls = k; }
-        }
-#pragma unroll
-        for (int k = 0; k < S; ++k)
-            if (k < cl.n && cl.id[k] == cls && (obj > best[k] || (obj == best[k] && r < bi[k]))) { best[k] = obj; bi[k] = r; }
-    }
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        if (k < cl.n) {   // uniform
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float ov = __shfl_down(best[k], off, 64);
-                const int oi = __shfl_down(bi[k], off, 64);
-                if (ov > best[k] || (ov == best[k] && oi < bi[k])) { best[k] = ov; bi[k] = oi; }
-            }
-            if ((threadIdx.x & 63) == 0) { sv[k][w] = best[k]; si[k][w] = bi[k]; }
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < cl.n) {
-        const int k = threadIdx.x;
-        int id = 0;
-#pragma unroll
-        for (int j = 0; j < S; ++j)
-            if (j == k) id = cl.id[j];
-        float b = sv[k][0];
-        int i = si[k][0];
-        for (int j = 1; j < (int)(blockDim.x >> 6); ++j)
-            if (sv[k][j] > b || (sv[k][j] == b && si[k][j] < i)) { b = sv[k][j]; i = si[k][j]; }
-        float* o = out + (long long)k * ld_slot;
-        if (b < 0.f) {
-            o[0] = __int_as_float(-1);
-            for (int j = 1; j < 8; ++j) o[j] = 0.f;
-        } else {
-            const float* q = src.row(i);
-            float x[4];
-            src.box(i, q, x);
-            o[0] = __int_as_float(i);
-            o[1] = x[0] - x[2] / 2;
-            o[2] = x[1] - x[3] / 2;
-            o[3] = x[0] + x[2] / 2;
-            o[4] = x[1] + x[3] / 2;
-            o[5] = src.attr(q, 4);
-            o[6] = src.attr(q, 5 + id);
-            o[7] = (float)id;
-        }
-    }
-}
-__global__ __launch_bounds__(1024) void yolo_select_classes_kernel(const float* __restrict__ pred, int rows, int attrs, float conf,
-                                                                    int num_classes, YoloClassList cl, float* __restrict__ sel,
-                                                                    int ld_image, int ld_slot) {
-    __shared__ float sv[BP_MAX_SCENE_CLASSES][16];
-    __shared__ int si[BP_MAX_SCENE_CLASSES][16];
-    const PredRows src{pred + (long long)blockIdx.x * rows * attrs, attrs};
-    select_classes(src, rows, conf, min(num_classes, attrs - 5), cl, sel + (long long)blockIdx.x * ld_image, ld_slot, sv, si);
-}
-__global__ __launch_bounds__(1024) void yolo_decode_select_classes_kernel(YoloHeads hs, int reso, int attrs, int rows, float conf,
-                                                                           int num_classes, YoloClassList cl, float* __restrict__ sel,
-                                                                           int ld_image, int ld_slot) {
-    __shared__ float sv[BP_MAX_SCENE_CLASSES][16];
-    __shared__ int si[BP_MAX_SCENE_CLASSES][16];
-    const HeadRows src{&hs, (int)blockIdx.x, attrs, reso};
-    select_classes(src, rows, conf, min(num_classes, attrs - 5), cl, sel + (long long)blockIdx.x * ld_image, ld_slot, sv, si);
-}
-YoloClassList make_class_list(const int* class_ids, int K, int num_classes, int attrs) {
-    BP_CHECK(K >= 1 && K <= BP_MAX_SCENE_CLASSES, "class list: 1 to 16 class ids (BP_MAX_SCENE_CLASSES)");
-    BP_CHECK(class_ids, "class list: null class ids");
-    const int ncls = num_classes < attrs - 5 ? num_classes : attrs - 5;
-    YoloClassList cl{};
-    cl.n = K;
-    for (int k = 0; k < K; ++k) {
-        if (class_ids[k] < 0 || class_ids[k] >= ncls)
-            throw Error("class list: class id " + std::to_string(class_ids[k]) + " is not below the detector's class count " + std::to_string(ncls));
-        for (int j = 0; j < k; ++j)
-            if (class_ids[j] == class_ids[k]) throw Error("class list: duplicate class id " + std::to_string(class_ids[k]));
-        cl.id[k] = class_ids[k];
-    }
-    return cl;
-}
-void launch_yolo_select_classes(const float* pred, int N, int rows, int attrs, float conf, int num_classes, const YoloClassList& cl,
-                                float* sel, hipStream_t s, int ld_image, int ld_slot) {
-    hipLaunchKernelGGL(yolo_select_classes_kernel, dim3(N), dim3(1024), 0, s, pred, rows, attrs, conf, num_classes, cl, sel, ld_image, ld_slot);
-}
-void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
-                                       const YoloClassList& cl, float* sel, hipStream_t s, int ld_image, int ld_slot) {
-    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
-    YoloHeads hs;
-    hs.n = nheads;
-    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
-    hipLaunchKernelGGL(yolo_decode_select_classes_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, cl, sel,
-                       ld_image, ld_slot);
-}
-
-// ---------------------------------------------------------------- select with box NMS (candidate boxes per frame)
-// write_results with its NMS branch live and the final arg-max removed (yolo/util.py:176-196, bbox_iou yolo/bbox.py:51-77):
-// the rows with objectness > conf whose first-max class is class_id, visited by descending objectness (lower row on ties);
-// each visited survivor is kept and removes every later row whose IoU with it is NOT < nms_conf (a NaN IoU removes); stop
-// after C <= BP_MAX_CANDIDATES survivors.  IoU in f32 on corner boxes in detector-input pixels, with the reference's + 1 on
-// widths and heights.  dynamic_write_results' second pass at nms_conf - 0.05 when more than 100 boxes survive is not
-// reproduced: at most 8 survivors are ever kept, so it is moot.
-// One block of 1 024 threads per image: a thread owns rows tid, tid + 1024, ... (at most NMS_RPT; 11 at 10 647 rows), their
-// liveness as a bit mask and their corners in registers.  C rounds of: block arg-max over the live rows (wave shuffles, 16
-// partials through LDS), the winner's box broadcast through LDS, every thread clears the rows that fail the IoU test.  A
-// round without a live row ends the loop, uniformly.  No atomics, nothing uploaded: the launch captures as it is.  No FMA
-// contraction: +, -, x, max / min and one correctly rounded division, bit-identical to an f32 host restatement.
-constexpr int NMS_RPT = 12;   // rows per thread: rows <= 12 288
-__device__ __forceinline__ float nms_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a >= b ? a : b)); }   // torch.max
-__device__ __forceinline__ float nms_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a <= b ? a : b)); }   // torch.min
-// bbox_iou(box1 = the kept box w, box2 = a later row b)
-__device__ __forceinline__ float nms_iou(const float* w, const float* b) {
-#pragma clang fp contract(off)
-    const float ix1 = nms_max(w[0], b[0]), iy1 = nms_max(w[1], b[1]);
-    const float ix2 = nms_min(w[2], b[2]), iy2 = nms_min(w[3], b[3]);
-    const float inter = nms_max(ix2 - ix1 + 1.f, 0.f) * nms_max(iy2 - iy1 + 1.f, 0.f);
-    const float a1 = (w[2] - w[0] + 1.f) * (w[3] - w[1] + 1.f);
-    const float a2 = (b[2] - b[0] + 1.f) * (b[3] - b[1] + 1.f);
-    return inter / (a1 + a2 - inter);
-}
-template <class Rows>
-__device__ __forceinline__ void select_nms(const Rows& src, int rows, float conf, int ncls, int class_id, float nms_conf, int C,
-                                           float* __restrict__ out, int ld_slot, int* __restrict__ count, float* sv, int* si,
-                                           float* sbox) {
-#pragma clang fp contract(off)
-    float bx[NMS_RPT][4], ob[NMS_RPT];
-    unsigned live = 0;
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < NMS_RPT; ++j) {
-        const int r = tid + j * 1024;
-        ob[j] = -1.f;
-        bx[j][0] = bx[j][1] = bx[j][2] = bx[j][3] = 0.f;
-        if (r < rows) {
-            const float* q = src.row(r);
-            const float obj = src.attr(q, 4);
-            if (obj > conf) {
-                int cls = 0;
-                float cm = src.attr(q, 5);
-                for (int k = 1; k < ncls; ++k) {
-                    const float v = src.attr(q, 5 + k);
-                    if (v > cm) { cm = v; cls = k; }
-                }
-                if (cls == class_id) {
-                    float x[4];
-                    src.box(r, q, x);
-                    bx[j][0] = x[0] - x[2] / 2;
-                    bx[j][1] = x[1] - x[3] / 2;
-                    bx[j][2] = x[0] + x[2] / 2;
-                    bx[j][3] = x[1] + x[3] / 2;
-                    ob[j] = obj;
-                    live |= 1u << j;
-                }
-            }
-        }
-    }
-    const int w = tid >> 6;
-    int kept = 0;
-    for (int c = 0; c < C; ++c) {
-        float best = -1.f;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < NMS_RPT; ++j)   // ascending rows: the first maximum stays
-            if (((live >> j) & 1u) && ob[j] > best) { best = ob[j]; bi = tid + j * 1024; }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_down(best, off, 64);
-            const int oi = __shfl_down(bi, off, 64);
-            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { sv[w] = best; si[w] = bi; }
-        __syncthreads();
-        best = sv[0];
-        bi = si[0];
-        for (int k = 1; k < 16; ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        if (best < 0.f) break;   // no live row left: the same on every thread
-        if ((bi & 1023) == tid) {   // the winner's owner: broadcast its box, write its record, retire it
-            const int jw = bi >> 10;
-            float wb[4] = {0.f, 0.f, 0.f, 0.f}, wo = 0.f;
-#pragma unroll
-            for (int j = 0; j < NMS_RPT; ++j)
-                if (j == jw) { wb[0] = bx[j][0]; wb[1] = bx[j][1]; wb[2] = bx[j][2]; wb[3] = bx[j][3]; wo = ob[j]; }
-            sbox[0] = wb[0]; sbox[1] = wb[1]; sbox[2] = wb[2]; sbox[3] = wb[3];
-            float* o = out + (long long)c * ld_slot;
-            o[0] = __int_as_float(bi);
-            o[1] = wb[0]; o[2] = wb[1]; o[3] = wb[2]; o[4] = wb[3];
-            o[5] = wo;
-            o[6] = src.attr(src.row(bi), 5 + class_id);
-            o[7] = (float)class_id;
-            live &= ~(1u << jw);
-        }
-        __syncthreads();   // (also: every thread has read sv / si before the next round rewrites them)
-        const float wb[4] = {sbox[0], sbox[1], sbox[2], sbox[3]};
-#pragma unroll
-        for (int j = 0; j < NMS_RPT; ++j)
-            if ((live >> j) & 1u) {
-                const float iou = nms_iou(wb, bx[j]);
-                if (!(iou < nms_conf)) live &= ~(1u << j);
-            }
-        ++kept;
-        __syncthreads();   // sbox is read before the next winner overwrites it
-    }
-    if (tid < C && tid >= kept) {   // unused slots: the "no detection" record
-        float* o = out + (long long)tid * ld_slot;
-        o[0] = __int_as_float(-1);
-        for (int k = 1; k < 8; ++k) o[k] = 0.f;
-    }
-    if (tid == 0) *count = kept;
-}
-__global__ __launch_bounds__(1024) void yolo_select_nms_kernel(const float* __restrict__ pred, int rows, int attrs, float conf,
-                                                                int num_classes, int class_id, float nms_conf, int C,
-                                                                float* __restrict__ sel, int* __restrict__ count, int ld_image,
-                                                                int ld_slot) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    __shared__ float sbox[4];
-    const PredRows src{pred + (long long)blockIdx.x * rows * attrs, attrs};
-    select_nms(src, rows, conf, min(num_classes, attrs - 5), class_id, nms_conf, C, sel + (long long)blockIdx.x * ld_image, ld_slot,
-               count + blockIdx.x, sv, si, sbox);
-}
-__global__ __launch_bounds__(1024) void yolo_decode_select_nms_kernel(YoloHeads hs, int reso, int attrs, int rows, float conf,
-                                                                       int num_classes, int class_id, float nms_conf, int C,
-                                                                       float* __restrict__ sel, int* __restrict__ count,
-                                                                       int ld_image, int ld_slot) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    __shared__ float sbox[4];
-    const HeadRows src{&hs, (int)blockIdx.x, attrs, reso};
-    select_nms(src, rows, conf, min(num_classes, attrs - 5), class_id, nms_conf, C, sel + (long long)blockIdx.x * ld_image, ld_slot,
-               count + blockIdx.x, sv, si, sbox);
-}
-static void check_select_nms(int rows, int attrs, int num_classes, int class_id, int C) {
-    BP_CHECK(C >= 1 && C <= BP_MAX_CANDIDATES, "select with NMS: 1 to 8 candidates (BP_MAX_CANDIDATES)");
-    BP_CHECK(rows >= 1 && rows <= NMS_RPT * 1024, "select with NMS: at most 12 288 rows per image");
-    const int ncls = num_classes < attrs - 5 ? num_classes : attrs - 5;
-    BP_CHECK(class_id >= 0 && class_id < ncls, "select with NMS: class id is not below the detector's class count");
-}
-void launch_yolo_select_nms(const float* pred, int N, int rows, int attrs, float conf, int num_classes, int class_id, float nms_conf,
-                            int C, float* sel, int* count, hipStream_t s, int ld_image, int ld_slot) {
-    check_select_nms(rows, attrs, num_classes, class_id, C);
-    hipLaunchKernelGGL(yolo_select_nms_kernel, dim3(N), dim3(1024), 0, s, pred, rows, attrs, conf, num_classes, class_id, nms_conf, C,
-                       sel, count, ld_image, ld_slot);
-}
-void launch_yolo_decode_select_nms(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
-                                   int class_id, float nms_conf, int C, float* sel, int* count, hipStream_t s, int ld_image,
-                                   int ld_slot) {
-    BP_CHECK(nheads <= 4, "at most 4 yolo heads");
-    check_select_nms(rows, attrs, num_classes, class_id, C);
-    YoloHeads hs;
-    hs.n = nheads;
-    for (int i = 0; i < nheads; ++i) hs.h[i] = heads[i];
-    hipLaunchKernelGGL(yolo_decode_select_nms_kernel, dim3(N), dim3(1024), 0, s, hs, reso, attrs, rows, conf, num_classes, class_id,
-                       nms_conf, C, sel, count, ld_image, ld_slot);
 }
 
 // ---------------------------------------------------------------- heat-map arg-max (+4 neighbours), eval.py:113-147

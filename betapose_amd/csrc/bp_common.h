@@ -249,6 +249,12 @@ void mega_make_conv_op(const ConvParams& p, int tile, MegaOp* out);        // p 
 void launch_mega(const MegaArgs& a, size_t lds_bytes, hipStream_t s);      // zeroes a.sync, launches 8 * a.nb blocks
 
 // ---- auxiliary kernels (aux_kernels.hip) ----
+// blocks of a grid-stride launch over n elements, which the kernel indexes with 32 bits
+static inline int grid_for(long long n, int block = 256, int cap = 4096) {
+    BP_CHECK(n < (1ll << 31), "tensor too large for 32-bit indexing");
+    long long g = (n + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 void launch_nchw_to_nhwc(const float* in, float* out, int N, int C, int H, int W, hipStream_t s);
 void launch_nhwc_to_nchw(const float* in, int in_ld, float* out, int N, int C, int H, int W, hipStream_t s);
 // planes / plane_elems / np: operand planes of `out` written alongside (ConvParams::out16; null = none)
@@ -274,21 +280,26 @@ struct YoloHead {
     float aw[3], ah[3];  // anchors in pixels
     int row_off;         // first row of this head in the [rows][attrs] output
 };
-// pred: [N][rows][attrs] (DetectionLayer row order); sel: [N][8] floats
-// (idx as int bits, x1,y1,x2,y2,obj,cls_conf,cls_idx); idx = -1 when nothing > conf
-void launch_yolo_decode(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows,
-                        float* pred, hipStream_t s);
+// ---- the detector's tail (yolo_tail.hip) ----
+// Where the rows of a detection come from: the decoded tensor pred [N][rows][attrs] (DetectionLayer row order) when it is
+// set, the head tensors otherwise (decoded on the fly with the same float operations: both give identical records)
+struct YoloRowSource {
+    const float* pred;
+    const YoloHead* heads;
+    int nheads;
+    int reso, attrs, rows;
+    static YoloRowSource tensor(const float* pred, int rows, int attrs) { return {pred, nullptr, 0, 0, attrs, rows}; }
+};
+void launch_yolo_decode(const YoloRowSource& heads, int N, float* pred, hipStream_t s);
+// sel: [N][8] floats (idx as int bits, x1,y1,x2,y2,obj,cls_conf,cls_idx); idx = -1 when nothing > conf: per image the arg-max
+// objectness row (first on ties) among the rows with obj > conf whose arg-max class is 0
 // sel_ld: floats between consecutive images' records (8 dense; the fused pipeline writes straight into its result rows)
-void launch_yolo_select(const float* pred, int N, int rows, int attrs, float conf, int num_classes,
-                        float* sel, hipStream_t s, int sel_ld = 8);
-// both in one launch, for callers that read the select record only (no [rows][attrs] tensor is written): same records
-void launch_yolo_decode_select(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
-                               float* sel, hipStream_t s, int sel_ld = 8);
+void launch_yolo_select(const YoloRowSource& src, int N, float conf, int num_classes, float* sel, hipStream_t s, int sel_ld = 8);
 // Per-class select for a shared multi-class detector: K <= BP_MAX_SCENE_CLASSES class ids travel BY VALUE in the launch
 // arguments (nothing is uploaded, the launch captures into a graph as it is).  A row with objectness > conf is a candidate
 // for the list slot that holds its arg-max class; per slot the arg-max objectness row wins (lower row on ties).
 // sel + n * ld_image + k * ld_slot: the record of image n, slot k -- launch_yolo_select's, with [6] = the winning class's
-// score and [7] = the class id; index -1 and zeros when the class has no row.  Both forms write identical records.
+// score and [7] = the class id; index -1 and zeros when the class has no row.
 #define BP_MAX_SCENE_CLASSES 16
 struct YoloClassList {
     int n;
@@ -296,19 +307,14 @@ struct YoloClassList {
 };
 // checks the list (1..16 ids, distinct, each below min(num_classes, attrs - 5)) and packs it; throws Error otherwise
 YoloClassList make_class_list(const int* class_ids, int K, int num_classes, int attrs);
-void launch_yolo_select_classes(const float* pred, int N, int rows, int attrs, float conf, int num_classes, const YoloClassList& cl,
-                                float* sel, hipStream_t s, int ld_image, int ld_slot);
-void launch_yolo_decode_select_classes(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf,
-                                       int num_classes, const YoloClassList& cl, float* sel, hipStream_t s, int ld_image, int ld_slot);
+void launch_yolo_select_classes(const YoloRowSource& src, int N, float conf, int num_classes, const YoloClassList& cl, float* sel,
+                                hipStream_t s, int ld_image, int ld_slot);
 // Select with box NMS (write_results' NMS branch live, its final arg-max removed): up to C <= BP_MAX_CANDIDATES survivors of
 // class class_id per image, in survivor order, at sel + n * ld_image + c * ld_slot (launch_yolo_select's record, [6] = the class's
 // score, [7] = the class id; unused slots index -1 and zeros); count[n] = survivors.  Parameters by value: the launch captures.
 #define BP_MAX_CANDIDATES 8
-void launch_yolo_select_nms(const float* pred, int N, int rows, int attrs, float conf, int num_classes, int class_id, float nms_conf,
-                            int C, float* sel, int* count, hipStream_t s, int ld_image, int ld_slot);
-void launch_yolo_decode_select_nms(const YoloHead* heads, int nheads, int N, int reso, int attrs, int rows, float conf, int num_classes,
-                                   int class_id, float nms_conf, int C, float* sel, int* count, hipStream_t s, int ld_image,
-                                   int ld_slot);
+void launch_yolo_select_nms(const YoloRowSource& src, int N, float conf, int num_classes, int class_id, float nms_conf, int C,
+                            float* sel, int* count, hipStream_t s, int ld_image, int ld_slot);
 // hm NCHW [N][C][H*W] -> out [N][C][6] = (idx as int bits, max, left, right, up, down)
 // out_ld: floats between consecutive images' [C][6] blocks (0 = dense C*6)
 void launch_heatmap_argmax(const float* hm, int N, int C, int H, int W, float* out, hipStream_t s, int out_ld = 0);

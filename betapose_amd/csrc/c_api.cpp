@@ -363,7 +363,7 @@ int bp_yolo_select(const float* d_pred, int batch, int rows, int attrs, float co
                    void* stream) {
     BP_TRY
     BP_CHECK(d_pred && d_sel && batch >= 1 && rows >= 1 && attrs >= 6, "bad argument");
-    bp::launch_yolo_select(d_pred, batch, rows, attrs, conf, num_classes, d_sel, (hipStream_t)stream);
+    bp::launch_yolo_select(bp::YoloRowSource::tensor(d_pred, rows, attrs), batch, conf, num_classes, d_sel, (hipStream_t)stream);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH
@@ -373,8 +373,8 @@ int bp_yolo_select_nms(const float* d_pred, int batch, int rows, int attrs, floa
                        float nms_conf, int max_candidates, float* d_sel, int* d_counts, void* stream) {
     BP_TRY
     BP_CHECK(d_pred && d_sel && d_counts && batch >= 1 && rows >= 1 && attrs >= 6, "bad argument");
-    bp::launch_yolo_select_nms(d_pred, batch, rows, attrs, conf, num_classes, class_id, nms_conf, max_candidates, d_sel, d_counts,
-                               (hipStream_t)stream, max_candidates * BP_SEL_FLOATS, BP_SEL_FLOATS);
+    bp::launch_yolo_select_nms(bp::YoloRowSource::tensor(d_pred, rows, attrs), batch, conf, num_classes, class_id, nms_conf, max_candidates,
+                               d_sel, d_counts, (hipStream_t)stream, max_candidates * BP_SEL_FLOATS, BP_SEL_FLOATS);
     BP_HIP(hipGetLastError());
     return 0;
     BP_CATCH

@@ -991,7 +991,7 @@ YoloNet::YoloNet(const std::string& cfg_text, const float* stream, size_t n_floa
                 h.ah[a] = (float)an[2 * mask[a] + 1];
             }
             heads_.push_back(h);
-            f32_readers_.push_back(t.p);     // launch_yolo_decode* reads the fp32 head tensor: a convolution that also reads it (a route behind the [yolo] layer) must not cost it its store
+            f32_readers_.push_back(t.p);     // the detector's tail (yolo_tail.hip) reads the fp32 head tensor: a convolution that also reads it (a route behind the [yolo] layer) must not cost it its store
             row_off += 3 * t.H * t.W;
         }
     }
@@ -1001,7 +1001,9 @@ YoloNet::YoloNet(const std::string& cfg_text, const float* stream, size_t n_floa
     finalize();
 }
 
-void YoloNet::run_net(const float* d_img, bool nhwc_input, int batch, hipStream_t s) {
+// input layout + every layer up to the heads; with d_pred the prediction tensor is decoded into it and the rows are read from
+// there, without it nobody reads that tensor (the per-frame chains) and the select takes its rows straight from the heads
+YoloRowSource YoloNet::run_to_rows(const float* d_img, bool nhwc_input, int batch, float* d_pred, hipStream_t s) {
     BP_CHECK(batch >= 1 && batch <= max_batch_, "batch out of range");
     if (nhwc_input) {
         if (d_img != in_nhwc_)
@@ -1011,21 +1013,19 @@ void YoloNet::run_net(const float* d_img, bool nhwc_input, int batch, hipStream_
         launch_nchw_to_nhwc(d_img, in_nhwc_, batch, 3, reso_, reso_, s);
     }
     run_ops(batch, s);
+    // heads hold per-image strides for max_batch_ == layout of batch b (contiguous by image), so decode as is
+    YoloRowSource src{nullptr, heads_.data(), (int)heads_.size(), reso_, attrs_, rows_};
+    if (d_pred) {
+        launch_yolo_decode(src, batch, d_pred, s);
+        src.pred = d_pred;
+    }
+    return src;
 }
 
 void YoloNet::forward(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
                       float* d_sel, hipStream_t s, int sel_ld) {
-    run_net(d_img, nhwc_input, batch, s);
-    // heads hold per-image strides for max_batch_ == layout of batch b (contiguous by image), so decode as is
-    static const bool two_kernels = std::getenv("BP_NO_DECODE_FUSION") != nullptr;   // A/B runs, tests
-    if (d_sel && !d_pred && !two_kernels) {
-        // nobody reads the prediction tensor (the fused per-frame pipeline): decode + select in one launch, same record
-        launch_yolo_decode_select(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, conf, num_classes, d_sel, s, sel_ld);
-    } else {
-        float* pred = d_pred ? d_pred : pred_;
-        launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, pred, s);
-        if (d_sel) launch_yolo_select(pred, batch, rows_, attrs_, conf, num_classes, d_sel, s, sel_ld);
-    }
+    const YoloRowSource src = run_to_rows(d_img, nhwc_input, batch, (d_pred || d_sel) ? d_pred : pred_, s);
+    if (d_sel) launch_yolo_select(src, batch, conf, num_classes, d_sel, s, sel_ld);
     BP_HIP(hipGetLastError());
 }
 
@@ -1033,32 +1033,17 @@ void YoloNet::forward_classes(const float* d_img, bool nhwc_input, int batch, fl
                               const int* class_ids, int K, float* d_sel, hipStream_t s, int ld_image, int ld_slot) {
     const YoloClassList cl = make_class_list(class_ids, K, num_classes, attrs_);
     BP_CHECK(d_sel, "null select buffer");
-    if (ld_image <= 0) ld_image = K * ld_slot;
-    run_net(d_img, nhwc_input, batch, s);
-    if (!d_pred) {
-        // the scene graph: nobody reads the prediction tensor, the K records come straight from the head tensors
-        launch_yolo_decode_select_classes(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, conf, num_classes, cl, d_sel, s,
-                                          ld_image, ld_slot);
-    } else {
-        launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, d_pred, s);
-        launch_yolo_select_classes(d_pred, batch, rows_, attrs_, conf, num_classes, cl, d_sel, s, ld_image, ld_slot);
-    }
+    const YoloRowSource src = run_to_rows(d_img, nhwc_input, batch, d_pred, s);
+    launch_yolo_select_classes(src, batch, conf, num_classes, cl, d_sel, s, ld_image > 0 ? ld_image : K * ld_slot, ld_slot);
     BP_HIP(hipGetLastError());
 }
 
 void YoloNet::forward_nms(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes, int class_id,
                           float nms_conf, int C, float* d_sel, int* d_count, hipStream_t s, int ld_image, int ld_slot) {
     BP_CHECK(d_sel && d_count, "null select buffer");
-    if (ld_image <= 0) ld_image = C * ld_slot;
-    run_net(d_img, nhwc_input, batch, s);
-    if (!d_pred) {
-        // the candidate graph: nobody reads the prediction tensor, the records come straight from the head tensors
-        launch_yolo_decode_select_nms(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, conf, num_classes, class_id, nms_conf,
-                                      C, d_sel, d_count, s, ld_image, ld_slot);
-    } else {
-        launch_yolo_decode(heads_.data(), (int)heads_.size(), batch, reso_, attrs_, rows_, d_pred, s);
-        launch_yolo_select_nms(d_pred, batch, rows_, attrs_, conf, num_classes, class_id, nms_conf, C, d_sel, d_count, s, ld_image, ld_slot);
-    }
+    const YoloRowSource src = run_to_rows(d_img, nhwc_input, batch, d_pred, s);
+    launch_yolo_select_nms(src, batch, conf, num_classes, class_id, nms_conf, C, d_sel, d_count, s, ld_image > 0 ? ld_image : C * ld_slot,
+                           ld_slot);
     BP_HIP(hipGetLastError());
 }
 

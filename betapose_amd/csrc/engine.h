@@ -195,18 +195,19 @@ public:
     void forward(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
                  float* d_sel, hipStream_t s, int sel_ld = 8);
     // the same pass for a multi-class detector shared by K <= BP_MAX_SCENE_CLASSES objects: d_sel + n * ld_image + k * ld_slot
-    // receives the best box whose arg-max class is class_ids[k] (launch_yolo_select_classes; ld_image 0 = K * ld_slot).
+    // receives the best box whose arg-max class is class_ids[k] (yolo_tail.hip launch_yolo_select_classes; ld_image 0 = K * ld_slot).
     // With d_pred the prediction tensor is written too; without it the records are decoded straight from the heads.
     void forward_classes(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes,
                          const int* class_ids, int K, float* d_sel, hipStream_t s, int ld_image = 0, int ld_slot = 8);
     // the same pass with box NMS in the select: up to C <= BP_MAX_CANDIDATES survivors of class class_id per image at
-    // d_sel + n * ld_image + c * ld_slot, their number in d_count[n] (launch_yolo_select_nms; ld_image 0 = C * ld_slot)
+    // d_sel + n * ld_image + c * ld_slot, their number in d_count[n] (yolo_tail.hip launch_yolo_select_nms; ld_image 0 = C * ld_slot)
     void forward_nms(const float* d_img, bool nhwc_input, int batch, float* d_pred, float conf, int num_classes, int class_id,
                      float nms_conf, int C, float* d_sel, int* d_count, hipStream_t s, int ld_image = 0, int ld_slot = 8);
     float* input_nhwc() { return in_nhwc_; }
     float* pred_buffer() { return pred_; }
 private:
-    void run_net(const float* d_img, bool nhwc_input, int batch, hipStream_t s);   // input layout + every layer up to the heads
+    // the step every forward* starts with: the net up to the heads, then where the select reads its rows (d_pred, decoded, or the heads)
+    YoloRowSource run_to_rows(const float* d_img, bool nhwc_input, int batch, float* d_pred, hipStream_t s);
     std::string cfg_text_;
     size_t n_floats_ = 0;
     int reso_, rows_ = 0, attrs_ = 0;

@@ -40,7 +40,7 @@ def check_class_ids(class_ids, n_classes: int, num_classes: int = 80):
     """The class list of one shared detector pass (``forward_select_classes``, ``ScenePipeline``): 1 to
     ``_lib.MAX_SCENE_CLASSES`` distinct ids, each below the class count the select compares over,
     ``min(num_classes, n_classes)`` (``n_classes``: the cfg's).  Returns the ids as a list of ints; raises ``ValueError``
-    otherwise -- the library refuses the same lists (csrc/aux_kernels.hip make_class_list)."""
+    otherwise -- the library refuses the same lists (csrc/yolo_tail.hip make_class_list)."""
     ids = [int(c) for c in class_ids]
     if not 1 <= len(ids) <= _lib.MAX_SCENE_CLASSES:
         raise ValueError("class list: %d class ids, one detector pass selects for 1 to %d" % (len(ids), _lib.MAX_SCENE_CLASSES))

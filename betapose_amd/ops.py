@@ -114,6 +114,20 @@ def crop_candidates(frames_bgr_u8, candidates: int, sel=None, boxes=None, reso: 
     return out, pts
 
 
+def select(pred, confidence: float = 0.01, num_classes: int = 80):
+    """The plain select on an existing prediction tensor (bp_yolo_select): cuda f32 [B,rows,attrs] -> sel f32 [B,8], per
+    image the arg-max objectness row above ``confidence`` whose arg-max class is 0."""
+    import torch
+    _lib.require_gpu()
+    p = pred.contiguous()
+    assert p.dtype == torch.float32 and p.dim() == 3
+    B, rows, attrs = p.shape
+    sel = torch.empty((B, 8), device=p.device, dtype=torch.float32)
+    _lib.check(_lib.lib().bp_yolo_select(p.data_ptr(), B, rows, attrs, float(confidence), int(num_classes), sel.data_ptr(),
+                                         _lib.current_stream()))
+    return sel
+
+
 def select_nms(pred, max_candidates: int, nms_conf: float, class_id: int = 0, confidence: float = 0.01, num_classes: int = 80):
     """Select with box NMS on an existing prediction tensor (bp_yolo_select_nms): cuda f32 [B,rows,attrs] ->
     (sel f32 [B,C,8], counts int32 [B]); see ``Darknet.forward_select_nms``."""

@@ -5,20 +5,14 @@ arg-max class is 0 -- or the int ``0`` when no image has one.  The reduction run
 select kernel on the device-resident prediction tensor."""
 from __future__ import annotations
 
-from . import _lib
+from . import _lib, ops
 from .darknet import sel_to_dets
 
 
 def write_results(prediction, confidence, num_classes, nms=True, nms_conf=0.4):
-    import torch
     _lib.require_gpu()
     pred = prediction if prediction.is_cuda else prediction.cuda()
-    pred = pred.contiguous().float()
-    B, rows, attrs = pred.shape
-    sel = torch.empty((B, 8), device=pred.device, dtype=torch.float32)
-    _lib.check(_lib.lib().bp_yolo_select(pred.data_ptr(), B, rows, attrs, float(confidence), int(num_classes),
-                                         sel.data_ptr(), _lib.current_stream()))
-    return sel_to_dets(sel)
+    return sel_to_dets(ops.select(pred.float(), confidence, num_classes))
 
 
 def dynamic_write_results(prediction, confidence, num_classes, nms=True, nms_conf=0.4):

@@ -1,4 +1,4 @@
-"""Candidate boxes per frame on the GPU: select with box NMS (csrc/aux_kernels.hip) against tests/nms_ref.py, the
+"""Candidate boxes per frame on the GPU: select with box NMS (csrc/yolo_tail.hip) against tests/nms_ref.py, the
 candidate crop, ``CandidatePipeline`` against the stand-alone stages and against ``FramePipeline`` at one candidate, and
 the candidate pose tail (csrc/pose_tail_cands.hip) against ``pipeline.finish_candidate_records``.
 

@@ -1,5 +1,5 @@
 """Shared multi-class detector: one YOLO pass per frame, the per-class select kernel
-(csrc/aux_kernels.hip yolo_select_classes_kernel / yolo_decode_select_classes_kernel), and ``ScenePipeline`` -- every
+(csrc/yolo_tail.hip yolo_select_classes_kernel, from the prediction tensor and from the head tensors), and ``ScenePipeline`` -- every
 object's crop -> key-point net -> arg-max -> pose tail behind that one pass, in one graph.
 
 Inputs: ``helpers.frames``, the 15-class YOLOv3 cfg at 416 with ``synth_yolo_stream(1, blocks)``.  Checked once on the CPU
@@ -144,6 +144,54 @@ def _select_ref(pred, conf, num_classes, class_ids):
             out[k, 7] = np.float32(c)
     out[:, 0] = idx.view(np.float32)
     return out, idx
+
+
+def test_plain_select_on_seeded_tensors_is_the_restatement_bit_for_bit(cuda):
+    """The tensor form of the single select (``ops.select``: the one-slot instantiation of the per-class select with the
+    list [0]) against ``_select_ref(pred, conf, num_classes, [0])``, all eight floats of every image equal as bytes.
+    rows 17 / 1025 / 2535: under one sweep of the block's 1 024 threads, one row past it, several sweeps;
+    (attrs, num_classes) so that min(num_classes, attrs - 5) is 1, 2 (num_classes binds), 80 (attrs binds), 2 of 80 scores.
+    Per trial of three images: [0] nothing above the threshold (one row AT it), [1] an exact three-way tie on the best
+    objectness, the last row among them (the first must win; one of the three also ties its class scores, first maximum
+    = class 0), [2] the top-objectness row has first-max class 1 and the runner-up, of class 0, must win."""
+    from betapose_amd import ops
+    rng = np.random.default_rng(11)
+    f32 = np.float32
+    seen_empty = seen_full = seen_tie = seen_other = 0
+    for trial, (rows, (attrs, nc)) in enumerate((r, an) for r in (17, 1025, 2535) for an in ((6, 80), (8, 2), (85, 80), (85, 2))):
+        ncls = min(nc, attrs - 5)
+        conf = (0.01, 0.5, 0.9)[trial % 3]
+        pred = np.zeros((3, rows, attrs), f32)
+        pred[..., 0:2] = rng.uniform(0, 416, (3, rows, 2))
+        pred[..., 2:4] = rng.uniform(2, 300, (3, rows, 2))
+        pred[..., 4] = rng.uniform(0, 1, (3, rows)) ** 3 * 0.97
+        pred[..., 5:] = rng.uniform(0, 0.9, (3, rows, attrs - 5))
+        pred[0, :, 4] *= f32(conf * 0.5)
+        pred[0, rows // 2, 4] = f32(conf)                        # objectness == conf is not above it
+        tie = np.sort(np.append(rng.choice(rows - 1, 2, replace=False), rows - 1))
+        pred[1, tie, 4] = f32(0.995)
+        pred[1, tie, 5] = f32(0.95)                              # class 0 is their arg-max ...
+        if ncls > 1:
+            pred[1, tie[0], 6] = f32(0.95)                       # ... also where class 1 scores the same
+        top, second = rng.choice(rows, 2, replace=False)
+        pred[2, top, 4], pred[2, second, 4] = f32(0.99), f32(0.98)
+        pred[2, second, 5] = f32(0.95)
+        if ncls > 1:
+            pred[2, top, 6] = f32(0.95)
+        ref = np.stack([_select_ref(pred[b], conf, nc, [0])[0][0] for b in range(3)])
+        idx = ref[:, 0].copy().view(np.int32)
+        print("trial %d rows %d attrs %d num_classes %d conf %.2f -> rows %s" % (trial, rows, attrs, nc, conf, idx.tolist()))
+        assert idx[0] == -1 and (pred[0, :, 4] == f32(conf)).any()
+        assert (pred[1, :, 4] == pred[1, :, 4].max()).sum() == 3 and idx[1] == tie[0] < tie[1] < tie[2]
+        assert idx[2] == (second if ncls > 1 else top) and int(np.argmax(pred[2, :, 4])) == top
+        seen_empty += int((idx < 0).sum())
+        seen_full += int((idx >= 0).sum())
+        seen_tie += 1
+        seen_other += int(ncls > 1)
+        got = ops.select(torch.from_numpy(pred).to(cuda), confidence=conf, num_classes=nc).cpu().numpy()
+        assert got.shape == (3, 8)
+        np.testing.assert_array_equal(_bits(got), _bits(ref), err_msg="trial %d" % trial)
+    assert seen_empty > 0 and seen_full > 0 and seen_tie == 12 and seen_other > 0, "input conditions"
 
 
 @pytest.mark.parametrize("class_ids", [list(range(N_CLASSES)), [7, 0, 12]])

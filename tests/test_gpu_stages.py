@@ -318,7 +318,7 @@ def test_crop_from_dets_reference_signature(cuda):
 
 def test_decode_select_fused_equals_the_two_kernel_path(engines, cuda):
     """Round 4 node diet: DetectionLayer decode + write_results in one launch when nobody reads the prediction tensor
-    (csrc/aux_kernels.hip yolo_decode_select_kernel).  Bit-identical select records to decode -> select, for detections at several
+    (csrc/yolo_tail.hip, the single select from the head rows).  Bit-identical select records to decode -> select, for detections at several
     confidence thresholds and for the no-detection case (yolo/darknet.py:129-169, yolo/util.py:118-223)."""
     det, _ = engines
     x = torch.cat([helpers.yolo_input_from_frame(f) for f in helpers.frames(4)]).to(cuda)
