@@ -200,14 +200,17 @@ def gaussian_table(sigma=1):
     return np.ascontiguousarray(g.astype(np.float32))
 
 
-def kpd_targets(parts, ul, br, in_res=(320, 256), out_res=(80, 64), sigma=1, want_mask=False, device=None):
+def kpd_targets(parts, ul, br, in_res=(320, 256), out_res=(80, 64), sigma=1, want_mask=False, device=None, as_tensor=False):
     """The label half of generateSampleBox ('coco' branch) for ``B`` samples: ``parts`` [B, Kp, 2] float64 image
     coordinates and the windows ``ul``, ``br`` [B, 2] float32 (kpd_windows) give ``(out [B, Kp, resH, resW] float32,
     centres [B, Kp, 2] int32)``, and ``setMask`` (all ones, as the reference returns it) as a third with ``want_mask``.
     A part is drawn iff ``x > 0`` and it lies strictly inside its window; its centre is transformBox's (float32
     arithmetic, round half to even), its patch drawGaussian's clipped copy of gaussian_table(sigma); an undrawn part
-    has centre ``(-1, -1)`` and a zero map.  The maps are bit-equal to the reference's."""
+    has centre ``(-1, -1)`` and a zero map.  The maps are bit-equal to the reference's.  ``as_tensor`` (device path
+    only): the results stay on the device as torch tensors instead of coming back as numpy arrays."""
     from . import _lib
+    if as_tensor and device is None:
+        raise ValueError("as_tensor needs a device")
     parts = np.ascontiguousarray(parts, dtype=np.float64)
     if parts.ndim != 3 or parts.shape[2] != 2:
         raise ValueError("parts must be [B, Kp, 2]")
@@ -238,6 +241,8 @@ def kpd_targets(parts, ul, br, in_res=(320, 256), out_res=(80, 64), sigma=1, wan
                 _lib.check(_lib.lib().bp_kpd_targets(_lib.ptr(d_parts), _lib.ptr(d_ul), _lib.ptr(d_br), B, Kp, inpH, inpW, resH,
                                                      resW, _lib.ptr(d_g), len(g), _lib.ptr(d_out), _lib.ptr(d_centres),
                                                      _lib.ptr(d_mask), torch.cuda.current_stream(dev).cuda_stream))
+                if as_tensor:
+                    return (d_out, d_centres, d_mask) if want_mask else (d_out, d_centres)
                 out, centres = d_out.cpu().numpy(), d_centres.cpu().numpy()
                 mask = d_mask.cpu().numpy() if want_mask else None
     return (out, centres, mask) if want_mask else (out, centres)

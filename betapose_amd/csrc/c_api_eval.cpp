@@ -8,6 +8,7 @@
 #include "c_api_util.h"
 #include "designate.h"
 #include "icp.h"
+#include "kpd_sample.h"
 #include "pose_tail.h"
 #include "raster.h"
 
@@ -86,6 +87,19 @@ static void annot_check_targets(int B, int Kp, int inpH, int inpW, int resH, int
     BP_CHECK(size >= 1 && size % 2 == 1 && size <= 1025, "the Gaussian table needs an odd size of at most 1025");
     // (the kernel indexes rows in groups of four floats: the width counts rounded up to a multiple of 4)
     BP_CHECK((long long)B * Kp * resH * ((resW + 3) / 4 * 4) < (1ll << 31), "the target tensor must hold fewer than 2^31 values");
+}
+
+// ---- KPD training samples (kpd_sample.hip / kpd_sample_host.cpp).  The kernels index rows in groups of four floats: a
+// width counts rounded up to a multiple of 4.
+static void sample_check_inputs(int N, int H, int W, int B, int inpH, int inpW) {
+    BP_CHECK(N > 0 && H > 0 && W > 0 && B > 0 && inpH > 0 && inpW > 0, "N, H, W, B and the input resolution must be positive");
+    check_pixels(H, W);
+    BP_CHECK((long long)B * 3 * inpH * ((inpW + 3) / 4 * 4) < (1ll << 31), "the input tensor must hold fewer than 2^31 values");
+}
+static void sample_check_maps(int B, int C, int H, int W) {
+    BP_CHECK(B > 0 && C > 0 && H > 0 && W > 0, "B, C, H and W must be positive");
+    check_pixels(H, W);
+    BP_CHECK((long long)B * C * H * ((W + 3) / 4 * 4) < (1ll << 31), "the map tensor must hold fewer than 2^31 values");
 }
 
 // what the four refinement calls check alike, and the parameter block they hand on
@@ -344,6 +358,69 @@ int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, 
     annot_check_targets(B, Kp, inpH, inpW, resH, resW, size);
     bp::kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask,
                     (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_inputs_host(const unsigned char* frames, int N, int H, int W, const int* frame_index, const float* ul, const float* br,
+                       const float* gains, const unsigned char* blank, int B, int inpH, int inpW, float* inp) {
+    BP_TRY
+    BP_CHECK(frames && frame_index && ul && br && inp, "null argument");
+    sample_check_inputs(N, H, W, B, inpH, inpW);
+    bp::kpd_inputs_host(frames, N, H, W, frame_index, ul, br, gains, blank, B, inpH, inpW, inp);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const float* d_ul,
+                  const float* d_br, const float* d_gains, const unsigned char* d_blank, int B, int inpH, int inpW, float* d_inp,
+                  void* stream) {
+    BP_TRY
+    BP_CHECK(d_frames && d_frame_index && d_ul && d_br && d_inp, "null argument");
+    sample_check_inputs(N, H, W, B, inpH, inpW);
+    bp::kpd_inputs(d_frames, N, H, W, d_frame_index, d_ul, d_br, d_gains, d_blank, B, inpH, inpW, d_inp, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_augment_host(const float* x, int B, int C, int H, int W, const unsigned char* flip, const double* cs, const int* perm,
+                        float* y) {
+    BP_TRY
+    BP_CHECK(x && flip && cs && y && x != y, "null argument, or x and y are the same tensor");
+    sample_check_maps(B, C, H, W);
+    bp::kpd_augment_host(x, B, C, H, W, flip, cs, perm, y);
+    return 0;
+    BP_CATCH
+}
+
+int bp_kpd_augment(const float* d_x, int B, int C, int H, int W, const unsigned char* d_flip, const double* d_cs,
+                   const int* d_perm, float* d_y, void* stream) {
+    BP_TRY
+    BP_CHECK(d_x && d_flip && d_cs && d_y && d_x != d_y, "null argument, or x and y are the same tensor");
+    sample_check_maps(B, C, H, W);
+    bp::kpd_augment(d_x, B, C, H, W, d_flip, d_cs, d_perm, d_y, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_heatmap_loss_acc_host(const float* out, const float* labels, const float* set_mask, int B, int K, int H, int W,
+                             double* partial, double* loss, float* acc, int* preds, int* gt, float* dists, float* grad) {
+    BP_TRY
+    BP_CHECK(out && labels && partial && loss && acc && preds && gt && dists, "null argument");
+    sample_check_maps(B, K, H, W);
+    bp::heatmap_loss_acc_host(out, labels, set_mask, B, K, H, W, partial, loss, acc, preds, gt, dists, grad);
+    return 0;
+    BP_CATCH
+}
+
+int bp_heatmap_loss_acc(const float* d_out, const float* d_labels, const float* d_set_mask, int B, int K, int H, int W,
+                        double* d_partial, double* d_loss, float* d_acc, int* d_preds, int* d_gt, float* d_dists, float* d_grad,
+                        void* stream) {
+    BP_TRY
+    BP_CHECK(d_out && d_labels && d_partial && d_loss && d_acc && d_preds && d_gt && d_dists, "null argument");
+    sample_check_maps(B, K, H, W);
+    bp::heatmap_loss_acc(d_out, d_labels, d_set_mask, B, K, H, W, d_partial, d_loss, d_acc, d_preds, d_gt, d_dists, d_grad,
+                         (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "annotate.h"
+#include "kpd_sample.h"
 #include "designate.h"
 #include "engine.h"
 #include "icp.h"
@@ -209,6 +210,26 @@ void vertex_boxes(const double* d_poses, int P, const double* d_vertices, int n,
 void kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, int B, int Kp, int inpH, int inpW, int resH,
                  int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, hipStream_t s) {
     launch_kpd_targets(d_parts, d_ul, d_br, B, Kp, inpH, inpW, resH, resW, d_g, size, d_out, d_centres, d_set_mask, s);
+    BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ KPD training samples
+void kpd_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const float* d_ul, const float* d_br,
+                const float* d_gains, const unsigned char* d_blank, int B, int inpH, int inpW, float* d_inp, hipStream_t s) {
+    launch_kpd_inputs(d_frames, N, H, W, d_frame_index, d_ul, d_br, d_gains, d_blank, B, inpH, inpW, d_inp, s);
+    BP_HIP(hipGetLastError());
+}
+
+void kpd_augment(const float* d_x, int B, int C, int H, int W, const unsigned char* d_flip, const double* d_cs, const int* d_perm,
+                 float* d_y, hipStream_t s) {
+    launch_kpd_augment(d_x, B, C, H, W, d_flip, d_cs, d_perm, d_y, s);
+    BP_HIP(hipGetLastError());
+}
+
+void heatmap_loss_acc(const float* d_out, const float* d_labels, const float* d_set_mask, int B, int K, int H, int W,
+                      double* d_partial, double* d_loss, float* d_acc, int* d_preds, int* d_gt, float* d_dists, float* d_grad,
+                      hipStream_t s) {
+    launch_heatmap_loss_acc(d_out, d_labels, d_set_mask, B, K, H, W, d_partial, d_loss, d_acc, d_preds, d_gt, d_dists, d_grad, s);
     BP_HIP(hipGetLastError());
 }
 

@@ -56,6 +56,11 @@
  *   bp_kpd_targets, bp_kpd_targets_host
  *                          generateSampleBox's label half: transformBox +    train_KPD/src/utils/pose.py:113-126
  *                          drawGaussian per part                               train_KPD/src/utils/img.py:61-110
+ *   bp_kpd_inputs, bp_kpd_augment, bp_heatmap_loss_acc (and their _host twins)
+ *                          generateSampleBox's image half and augmentation:     train_KPD/src/utils/pose.py:20-28,107-143
+ *                          cropBox, flip, shuffleLR (torchsample's Rotate is    train_KPD/src/utils/img.py:131-200
+ *                          restated from its published source, never compared); train()'s MSELoss(out * setMask, labels)
+ *                          and heatmapAccuracy                                  train_KPD/src/utils/eval.py:49-108
  *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
  *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
  *                          from its published description, never compared with PCL), a farthest-point alternative,
@@ -398,6 +403,46 @@ int bp_kpd_targets(const double* d_parts, const float* d_ul, const float* d_br, 
                    int resW, const float* d_g, int size, float* d_out, int* d_centres, float* d_set_mask, void* stream);
 int bp_kpd_targets_host(const double* parts, const float* ul, const float* br, int B, int Kp, int inpH, int inpW, int resH,
                         int resW, const float* g, int size, float* out, int* centres, float* set_mask);
+/* KPD training samples (the rest of generateSampleBox, and train()'s criterion and metric).  Each device function is
+ * bit-identical to its _host twin, which needs no GPU, and is enqueued on `stream` without synchronising it.
+ *
+ * bp_kpd_inputs: the network input of B samples.  d_frames [N][H][W][3] uint8 RGB, d_frame_index [B] int32 (an index
+ * outside [0, N) gives a zero sample), windows d_ul, d_br [B][2] f32 as bp_kpd_targets takes them, d_gains [B][3] f32 or
+ * NULL (no multiply), d_blank [B] uint8 or NULL (non-zero: the sample is all zeros, generateSampleBox's jointNum == 0).
+ * A tap of the frame is clamp(u8 / 255 * gain, 0, 1) - mean, mean = (0.406, 0.457, 0.480) for R, G, B, in f32.  The
+ * window's corners are truncated toward zero, (w, h) = br - ul; lenH = max(h, w * inpH / inpW), lenW = lenH * inpW /
+ * inpH; the crop sits in a zero image of PH = max(int(lenH), h) by PW = max(int(lenW), w) at offset
+ * (ceil((PH - h) / 2), ceil((PW - w) / 2)), and that image is resized to d_inp [B][3][inpH][inpW] f32 bilinearly with
+ * align_corners = True (cropBox).  A window without area gives a zero sample.  Every element is written. */
+int bp_kpd_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const float* d_ul,
+                  const float* d_br, const float* d_gains, const unsigned char* d_blank, int B, int inpH, int inpW, float* d_inp,
+                  void* stream);
+int bp_kpd_inputs_host(const unsigned char* frames, int N, int H, int W, const int* frame_index, const float* ul, const float* br,
+                       const float* gains, const unsigned char* blank, int B, int inpH, int inpW, float* inp);
+/* bp_kpd_augment: d_y = the augmented d_x, both [B][C][H][W] f32 and distinct.  d_flip [B] uint8: column j takes column
+ * W - 1 - j, and channel c reads channel d_perm[c] (d_perm [C] int32 or NULL = identity: shuffleLR as a table; an entry
+ * outside [0, C) counts as c).  d_cs [B][2] f64 = (cos, sin) of the sample's rotation angle, formed by the caller;
+ * exactly (1, 0) means no rotation.  Rotation: the source of pixel (row, col) is A (dst - centre) + centre, A = [[cos,
+ * -sin], [sin, cos]], centre = (H / 2 - 0.5, W / 2 - 0.5), in f64; the coordinate is clamped to the map, and the four
+ * taps about its floor are blended in f32.  The taps are read through the flip, so the result is the rotation of the
+ * flipped map.  Every element is written. */
+int bp_kpd_augment(const float* d_x, int B, int C, int H, int W, const unsigned char* d_flip, const double* d_cs,
+                   const int* d_perm, float* d_y, void* stream);
+int bp_kpd_augment_host(const float* x, int B, int C, int H, int W, const unsigned char* flip, const double* cs, const int* perm,
+                        float* y);
+/* bp_heatmap_loss_acc: d_out, d_labels, d_set_mask (or NULL = ones) and d_grad (or NULL), all [B][K][H][W] f32.
+ * *d_loss (f64) = the mean of (out * mask - label)^2, the difference in f32, the squares summed in f64 in a fixed order
+ * (no atomics: the same bits on every run, stream and grid).  d_grad = ((f32)(2 / (B K H W)) * (out * mask - label)) *
+ * mask.  d_preds, d_gt [B][K][2] int32 = the (x, y) of the largest value of out * mask and of the label, the lowest
+ * index among equals (getPreds); d_dists [K][B] f32 = their distance / (H / 10), or -1 unless gt.x > 0 and gt.y > 0
+ * (calc_dists); d_acc [K + 1] f32: [1 + k] the share of channel k's counted samples with dist <= 0.5, -1 when none
+ * counts, [0] the mean of the non-negative ones, 0 when there is none (heatmapAccuracy over every channel).
+ * d_partial [B * K] f64 is scratch. */
+int bp_heatmap_loss_acc(const float* d_out, const float* d_labels, const float* d_set_mask, int B, int K, int H, int W,
+                        double* d_partial, double* d_loss, float* d_acc, int* d_preds, int* d_gt, float* d_dists, float* d_grad,
+                        void* stream);
+int bp_heatmap_loss_acc_host(const float* out, const float* labels, const float* set_mask, int B, int K, int H, int W,
+                             double* partial, double* loss, float* acc, int* preds, int* gt, float* dists, float* grad);
 /* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
  * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
  * its _host twin, which needs no GPU.
