@@ -77,6 +77,12 @@ PROTOTYPES = {
                             C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, c_float_p, vp]),
     "bp_conv2d_planes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, c_float_p, vp]),
+    "bp_conv2d_se": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, c_float_p, vp]),
+    "bp_avgpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, c_int_p, vp]),
+    "bp_fc": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
+    "bp_maxpool3s2p1": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "bp_pixel_shuffle2": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "bp_pipeline_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, C.POINTER(vp)]),
     "bp_pipeline_kernel_count": (C.c_int, [vp]),
     "bp_yolo_profile": (C.c_int, [vp, C.c_int, C.c_int, c_float_p, c_int_p, C.c_int, vp]),

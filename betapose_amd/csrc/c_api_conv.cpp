@@ -19,8 +19,17 @@ int bp_conv2d(const float* d_in, int N, int H, int W, int Cin, const float* h_w,
 int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
                      int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
                      float* d_out, unsigned short* d_out_planes, int iters, float* ms_per_iter, void* stream) {
+    return bp_conv2d_se(d_in, N, H, W, Cin, h_w, h_bias, Cout, k, stride, pad, act, store_mode, d_res, res_after_act, tile, splits,
+                        d_out, d_out_planes, nullptr, nullptr, iters, ms_per_iter, stream);
+}
+
+int bp_conv2d_se(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
+                 int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
+                 float* d_out, unsigned short* d_out_planes, const float* d_res_scale, float* d_pool_out, int iters,
+                 float* ms_per_iter, void* stream) {
     BP_TRY
     BP_CHECK(d_in && h_w && d_out, "null argument");
+    BP_CHECK(!d_res_scale || d_res, "a residual scale needs a residual");
     hipStream_t s = (hipStream_t)stream;
     struct OneConv : bp::Net {
         OneConv() : Net(1) {}
@@ -37,7 +46,7 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
     out.ld = store_mode == bp::ST_PIXSHUF ? Cout / 4 : Cout;
     bp::Tensor res; res.p = const_cast<float*>(d_res); res.ld = Cout; res.C = Cout; res.H = OH; res.W = OW;
     bp::ConvWeights cw; cw.w = h_w; cw.bias = h_bias;
-    net.add_conv("conv", in, out, cw, Cout, k, stride, pad, act, store_mode, d_res ? &res : nullptr, nullptr,
+    net.add_conv("conv", in, out, cw, Cout, k, stride, pad, act, store_mode, d_res ? &res : nullptr, d_res_scale,
                  res_after_act, 1e-5f, OH, OW);
     int t = tile;
     int prec = bp::PREC_F32;
@@ -59,6 +68,12 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
     bp::ConvParams p = net.ops_[0].conv;
     p.N = N; p.M = N * OH * OW;
     if (t < 0) t = bp::TILE_64x64;
+    // the SE average pool in this launch's epilogue (ConvParams::pool_out): under the engine's own precondition, or not at all
+    if (d_pool_out) {
+        BP_CHECK(bp::conv_pool_in_epilogue_ok(p, N, t), "the average pool cannot ride in this launch's epilogue (needs a 64x64 tile, a linear "
+                 "residual-free NHWC layer, Cout % 4 == 0, and one image or OH * OW % 64 == 0)");
+        p.pool_out = d_pool_out;
+    }
     const int np = prec == bp::PREC_F16 ? 1 : 3;
     if (bp::conv_tile_is_pl(t)) {
         // the caller's activations are fp32: their operand planes are made here, as the layer's producer would have
@@ -132,7 +147,7 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
         BP_HIP(hipMemset(p.tickets, 0, (size_t)(2 + 64) * tiles * sizeof(int)));
     }
     bp::HybridTail h;
-    if (sp == 1 && !std::getenv("BP_CONV_SELF_PREFETCH") && bp::conv_hybrid_plan(p, t, bp::conv_slab_floats(t, 8, 256), &h)) {   // (<= 8 slices of <= 256 tail tiles)
+    if (sp == 1 && !p.pool_out && !std::getenv("BP_CONV_SELF_PREFETCH") && bp::conv_hybrid_plan(p, t, bp::conv_slab_floats(t, 8, 256), &h)) {   // (<= 8 slices of <= 256 tail tiles)
         p.partial = net.arena_.alloc(h.slab_floats);
         p.tickets = (int*)net.arena_.alloc_bytes((size_t)h.tiles * sizeof(int));
         BP_HIP(hipMemset(p.tickets, 0, (size_t)h.tiles * sizeof(int)));
@@ -195,6 +210,65 @@ int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const floa
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
     }
+    return 0;
+    BP_CATCH
+}
+
+// ------------------------------------------------------------------ the SE blocks' and the DUC layers' auxiliary kernels, one launch each (tests)
+int bp_avgpool(const float* d_in, int in_ld, int N, int HW, int C, float* d_out, int* parts, void* stream) {
+    BP_TRY
+    BP_CHECK(N >= 1 && HW >= 1 && C >= 1 && in_ld >= C, "bad argument");
+    if (parts) *parts = bp::avgpool_parts(HW);
+    if (!d_out) return 0;          // (the slice count alone: the caller sizes d_out [N][parts][C] with it)
+    BP_CHECK(d_in, "null argument");
+    bp::launch_avgpool(d_in, in_ld, d_out, N, HW, C, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+    BP_CATCH
+}
+
+int bp_fc(const float* d_in, const float* h_w, const float* h_bias, int N, int Cin, int Cout, int act, int in_parts, float in_scale,
+          float* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_in && h_w && d_out && N >= 1 && Cin >= 4 && Cout >= 1 && in_parts >= 1, "bad argument");
+    BP_CHECK(act == 0 || act == 2 || act == 3, "fc: act 0 linear / 2 relu / 3 sigmoid");
+    hipStream_t s = (hipStream_t)stream;
+    struct DevBuf {
+        float* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } w, b;
+    BP_HIP(hipMalloc((void**)&w.p, (size_t)Cout * Cin * sizeof(float)));
+    BP_HIP(hipMalloc((void**)&b.p, (size_t)Cout * sizeof(float)));
+    BP_HIP(hipMemcpy(w.p, h_w, (size_t)Cout * Cin * sizeof(float), hipMemcpyHostToDevice));
+    if (h_bias) BP_HIP(hipMemcpy(b.p, h_bias, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
+    else BP_HIP(hipMemset(b.p, 0, (size_t)Cout * sizeof(float)));
+    bp::launch_fc(d_in, w.p, b.p, d_out, N, Cin, Cout, act, in_parts, in_scale, s);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize(s));
+    return 0;
+    BP_CATCH
+}
+
+int bp_maxpool3s2p1(const float* d_in, int N, int H, int W, int C, float* d_out, unsigned short* d_out_planes, int np, void* stream) {
+    BP_TRY
+    BP_CHECK(d_in && d_out && N >= 1 && H >= 1 && W >= 1 && C >= 4, "bad argument");
+    BP_CHECK(d_out_planes ? (np == 1 || np == 3) : np == 0, "output planes: np 1 (fp16) or 3 (bf16x3) with a plane buffer, 0 without");
+    const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;      // as the engine sizes the layer
+    bp::launch_maxpool3s2p1(d_in, d_out, N, H, W, C, OH, OW, (hipStream_t)stream, d_out_planes, (long long)N * OH * OW * C, np);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+    BP_CATCH
+}
+
+int bp_pixel_shuffle2(const float* d_in, int N, int H, int W, int C, float* d_out, unsigned short* d_out_planes, int np, void* stream) {
+    BP_TRY
+    BP_CHECK(d_in && d_out && N >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "bad argument");
+    BP_CHECK(d_out_planes ? (np == 1 || np == 3) : np == 0, "output planes: np 1 (fp16) or 3 (bf16x3) with a plane buffer, 0 without");
+    bp::launch_pixel_shuffle2(d_in, d_out, N, H, W, C, (hipStream_t)stream, d_out_planes, (long long)N * H * W * C, np);
+    BP_HIP(hipGetLastError());
+    BP_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
     BP_CATCH
 }

@@ -600,6 +600,12 @@ bool conv_home_layout(int tile, int splits) {
     return splits > 1 && splits <= 64 && xcc_base() >= 0 && (tile == TILE_64x64_BD || (conv_tile_is_pl(tile) && !conv_tile_is_plh(tile)));
 }
 
+bool conv_pool_in_epilogue_ok(const ConvParams& c, int batch, int tile) {
+    if (conv_tile_bm(tile) != 64 || conv_tile_bn(tile) != 64) return false;
+    if (c.store_mode != ST_NHWC || c.res || c.res_scale || c.act != ACT_LINEAR || (c.out_ld & 3) || (c.Cout & 3)) return false;
+    return batch == 1 || (c.OH * c.OW) % 64 == 0;
+}
+
 // p's launch carries the prefetch blocks for `next` (launched as nl), when next's work blocks of residue x read the N-tiles
 // n == x (mod min(N-tiles, 8)) -- the xcd_home layout, or the plain one-slice grid of the 64x64 filters-direct kernel -- from a filter
 // image that is contiguous per (N-tile, K-slice) pair

@@ -26,6 +26,9 @@ inline size_t conv_slab_floats(int tile, int slices, int tiles) { return (size_t
 struct HybridTail { int full = 0, splits = 0, cps = 0, tiles = 0; size_t slab_floats = 0; };
 bool conv_hybrid_plan(const ConvParams& p, int tile, size_t partial_floats, HybridTail* h);
 bool conv_home_layout(int tile, int splits);   // the launch keeps all K slices of a tile on one XCD
+// the SE average pool can ride in this launch's epilogue (ConvParams::pool_out): a 64x64 tile with the staged vector epilogue of a linear,
+// residual-free NHWC layer, whose 64-row slabs never span two images of the batch
+bool conv_pool_in_epilogue_ok(const ConvParams& c, int batch, int tile);
 // p's launch carries the prefetch blocks for the filters of `next`, which runs as `nl`
 void conv_prefetch_of(ConvParams& p, const ConvParams& next, const ConvLaunch& nl);
 

@@ -521,10 +521,7 @@ int xcc_base() {
 // staged vector epilogue, when a tile never spans two images.  BP_NO_POOL_FUSION=1: the separate kernel (A/B, tests).
 bool Net::pool_in_epilogue(const Op& conv, int batch, int tile) const {
     static const bool off = std::getenv("BP_NO_POOL_FUSION") != nullptr;
-    const ConvParams& c = conv.conv;
-    if (off || !conv.pool_out || conv_tile_bm(tile) != 64 || conv_tile_bn(tile) != 64) return false;
-    if (c.store_mode != ST_NHWC || c.res || c.res_scale || c.act != ACT_LINEAR || (c.out_ld & 3) || (c.Cout & 3)) return false;
-    return batch == 1 || (c.OH * c.OW) % 64 == 0;
+    return !off && conv.pool_out && conv_pool_in_epilogue_ok(conv.conv, batch, tile);
 }
 
 // the launch descriptor of convolution `op` at this batch size under the current plan: tile, K slices, workspaces, epilogue extras.

@@ -26,7 +26,7 @@ for _n, _i in (("kg1", 7), ("kg2", 8), ("kg4", 9), ("rd4", 10), ("rd8", 11)):
 
 def conv2d_nhwc(x, weight, bias=None, stride: int = 1, pad: int = 0, act: str = "linear", store: str = "nhwc",
                 res=None, res_after_act: bool = False, tile: str = "auto", splits: int = 0, iters: int = 0,
-                planes: bool = False, out=None):
+                planes: bool = False, out=None, res_scale=None, pool=False):
     """One fused convolution.  ``x``: cuda f32 [N,H,W,Cin] (NHWC); ``weight``: host
     numpy/torch [Cout,Cin,k,k]; returns the output tensor laid out per ``store`` and,
     when ``iters`` > 0, also the measured ms per launch.  ``planes``: also return the operand planes the epilogue
@@ -38,7 +38,13 @@ def conv2d_nhwc(x, weight, bias=None, stride: int = 1, pad: int = 0, act: str = 
     Environment, read by the library on every call: ``BP_CONV_F16R=1`` makes an ``*_f16`` launch as the engine's ``f16r``
     plan makes it -- ``res`` is rounded to its fp16 plane and the kernel reads the skip connection from that plane
     (ConvParams::res16), and with ``planes=True`` the fp32 store is dropped (ConvParams::skip_f32): only the returned plane
-    is written, the fp32 tensor keeps whatever it held (unspecified, unless the caller passed ``out``)."""
+    is written, the fp32 tensor keeps whatever it held (unspecified, unless the caller passed ``out``).
+
+    ``res_scale``: cuda f32 [N, Cout], the SE gate of the skip connection -- ``res`` is multiplied by it per image and channel
+    (ConvParams::res_scale; needs ``res``).  ``pool``: the launch's epilogue also writes the sums of conv + bias over every 64-row
+    slab (ConvParams::pool_out) into a cuda f32 buffer [ceil(N*OH*OW / 64), Cout], returned behind the planes; ``True`` allocates
+    it, a caller's tensor (contiguous f32, at least that many elements; pre-filled, it shows what the launch wrote) is used and
+    returned as it is.  The library refuses the launch forms whose epilogue cannot carry the pool."""
     import torch
     _lib.require_gpu()
     w = np.ascontiguousarray(weight.detach().cpu().numpy() if hasattr(weight, "detach") else weight, dtype=np.float32)
@@ -66,13 +72,116 @@ def conv2d_nhwc(x, weight, bias=None, stride: int = 1, pad: int = 0, act: str = 
     if planes:
         assert store != "nchw", "NCHW outputs (the heat-maps) have no operand planes"
         pl = torch.zeros((1 if TILE[tile] < _B3 else 3,) + tuple(out.shape), device=x.device, dtype=torch.int16)
-    _lib.check(_lib.lib().bp_conv2d_planes(x.data_ptr(), N, H, W, Cin, w.ctypes.data, b.ctypes.data if b is not None else None,
-                                           Cout, k, stride, pad, ACT[act], STORE[store],
-                                           res.contiguous().data_ptr() if res is not None else None, int(res_after_act),
-                                           TILE[tile], int(splits), out.data_ptr(), pl.data_ptr() if planes else None,
-                                           int(iters), C.byref(ms), _lib.current_stream()))
-    ret = (out,) + ((pl,) if planes else ()) + ((ms.value,) if iters > 0 else ())
+    rs = None
+    if res_scale is not None:
+        if not (tuple(res_scale.shape) == (N, Cout) and res_scale.dtype == torch.float32 and res_scale.device == x.device):
+            raise ValueError("res_scale must be a float32 tensor of shape %s on %s" % ((N, Cout), x.device))
+        rs = res_scale.contiguous()
+    pb = None
+    if pool is not False and pool is not None:
+        slabs = (N * OH * OW + 63) // 64
+        if pool is True:
+            pb = torch.empty((slabs, Cout), device=x.device, dtype=torch.float32)
+        else:
+            pb = pool
+            if not (pb.dtype == torch.float32 and pb.device == x.device and pb.is_contiguous() and pb.numel() >= slabs * Cout):
+                raise ValueError("pool must be a contiguous float32 tensor of at least %d elements on %s" % (slabs * Cout, x.device))
+    r = res.contiguous() if res is not None else None
+    _lib.check(_lib.lib().bp_conv2d_se(x.data_ptr(), N, H, W, Cin, w.ctypes.data, b.ctypes.data if b is not None else None,
+                                       Cout, k, stride, pad, ACT[act], STORE[store],
+                                       r.data_ptr() if r is not None else None, int(res_after_act),
+                                       TILE[tile], int(splits), out.data_ptr(), pl.data_ptr() if planes else None,
+                                       rs.data_ptr() if rs is not None else None, pb.data_ptr() if pb is not None else None,
+                                       int(iters), C.byref(ms), _lib.current_stream()))
+    ret = (out,) + ((pl,) if planes else ()) + ((pb,) if pb is not None else ()) + ((ms.value,) if iters > 0 else ())
     return ret if len(ret) > 1 else out
+
+
+FC_ACT = {"linear": 0, "relu": 2, "sigmoid": 3}
+
+
+def avgpool_parts(x, channels: Optional[int] = None, col0: int = 0, out=None):
+    """The SE blocks' global average pool as slice sums (bp_avgpool, avgpool_partial_kernel).  ``x``: cuda f32 [N, HW, ld] (or
+    [N, H, W, ld]) whose rows are contiguous; columns ``col0`` .. ``col0 + channels`` of a row are pooled (default: all, ld == C) --
+    a view into a wider tensor is passed as the wide tensor plus the view's columns.  Returns (sums [N, P, C], P): the sums of P pixel
+    slices of ceil(HW / P) pixels each; the mean is sums.sum(1) / HW.  ``out``: a caller's contiguous cuda f32 tensor of that shape to
+    write into (pre-filled, it shows what the launch wrote)."""
+    import torch
+    _lib.require_gpu()
+    assert x.dtype == torch.float32 and x.dim() in (3, 4)
+    x = x.contiguous()
+    N, ld = x.shape[0], x.shape[-1]
+    HW = x.numel() // (N * ld)
+    Cc = ld - col0 if channels is None else int(channels)
+    assert 0 <= col0 and Cc >= 1 and col0 + Cc <= ld
+    parts = C.c_int(0)
+    _lib.check(_lib.lib().bp_avgpool(None, ld, N, HW, Cc, None, C.byref(parts), _lib.current_stream()))
+    if out is None:
+        out = torch.empty((N, parts.value, Cc), device=x.device, dtype=torch.float32)
+    elif not (tuple(out.shape) == (N, parts.value, Cc) and out.dtype == torch.float32 and out.device == x.device and out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % ((N, parts.value, Cc), x.device))
+    _lib.check(_lib.lib().bp_avgpool(x.data_ptr() + 4 * col0, ld, N, HW, Cc, out.data_ptr(), C.byref(parts), _lib.current_stream()))
+    return out, parts.value
+
+
+def fc(x, weight, bias=None, act: str = "linear", in_scale: float = 1.0):
+    """The SE blocks' fully connected layer (bp_fc, fc_kernel): act(bias + weight @ v).  ``x``: cuda f32 [N, Cin] (v = x), or
+    [N, in_parts, Cin] slice sums (v = in_scale * x.sum(1)); ``weight``: host numpy/torch [Cout, Cin], Cin % 4 == 0; ``act``
+    'linear' / 'relu' / 'sigmoid'.  Returns cuda f32 [N, Cout]."""
+    import torch
+    _lib.require_gpu()
+    w = np.ascontiguousarray(weight.detach().cpu().numpy() if hasattr(weight, "detach") else weight, dtype=np.float32)
+    b = None
+    if bias is not None:
+        b = np.ascontiguousarray(bias.detach().cpu().numpy() if hasattr(bias, "detach") else bias, dtype=np.float32)
+    assert x.dtype == torch.float32 and x.dim() in (2, 3)
+    x = x.contiguous()
+    N, Cin = x.shape[0], x.shape[-1]
+    parts = x.shape[1] if x.dim() == 3 else 1
+    Cout = w.shape[0]
+    assert w.shape == (Cout, Cin) and (b is None or b.shape == (Cout,))
+    out = torch.empty((N, Cout), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().bp_fc(x.data_ptr(), w.ctypes.data, b.ctypes.data if b is not None else None, N, Cin, Cout, FC_ACT[act],
+                                int(parts), float(in_scale), out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def _aux_planes(out, planes):
+    import torch
+    if not planes:
+        return None, 0
+    npl = {"f16": 1, "b3": 3}[planes]
+    return torch.zeros((npl,) + tuple(out.shape), device=out.device, dtype=torch.int16), npl
+
+
+def maxpool3s2p1(x, planes: Optional[str] = None):
+    """MaxPool 3x3 / stride 2 / pad 1 (bp_maxpool3s2p1): cuda f32 NHWC [N, H, W, C], C % 4 == 0 -> [N, (H-1)//2+1, (W-1)//2+1, C].
+    ``planes`` 'f16' / 'b3': also return the operand planes the kernel writes for the next layer (int16 [np, *out.shape])."""
+    import torch
+    _lib.require_gpu()
+    assert x.dtype == torch.float32 and x.dim() == 4
+    x = x.contiguous()
+    N, H, W, Cc = x.shape
+    out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc), device=x.device, dtype=torch.float32)
+    pl, npl = _aux_planes(out, planes)
+    _lib.check(_lib.lib().bp_maxpool3s2p1(x.data_ptr(), N, H, W, Cc, out.data_ptr(), pl.data_ptr() if pl is not None else None, npl,
+                                          _lib.current_stream()))
+    return (out, pl) if pl is not None else out
+
+
+def pixel_shuffle2(x, planes: Optional[str] = None):
+    """PixelShuffle(2) (bp_pixel_shuffle2): cuda f32 NHWC [N, H, W, C], C % 4 == 0 -> [N, 2H, 2W, C/4] with torch's channel order
+    (out[c, 2h+i, 2w+j] = in[4c + 2i + j, h, w]).  ``planes``: as ``maxpool3s2p1``."""
+    import torch
+    _lib.require_gpu()
+    assert x.dtype == torch.float32 and x.dim() == 4
+    x = x.contiguous()
+    N, H, W, Cc = x.shape
+    out = torch.empty((N, 2 * H, 2 * W, Cc // 4), device=x.device, dtype=torch.float32)
+    pl, npl = _aux_planes(out, planes)
+    _lib.check(_lib.lib().bp_pixel_shuffle2(x.data_ptr(), N, H, W, Cc, out.data_ptr(), pl.data_ptr() if pl is not None else None, npl,
+                                            _lib.current_stream()))
+    return (out, pl) if pl is not None else out
 
 
 def crop(frames_bgr_u8, sel=None, boxes=None, reso: int = 416, oh: int = 320, ow: int = 256, nchw: bool = True):

@@ -71,8 +71,8 @@
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
  *                          (+ init/detect_image/detect_mat/dispose: include/yolo_v2_class_compat.h)
- *   bp_*_set_precision, bp_*_set_policy, bp_stream_create_masked, bp_probe_placement, bp_conv2d, bp_*_tap_*,
- *   bp_*_profile, bp_*_op_stats: no reference counterpart (tuning, measurement and test hooks)
+ *   bp_*_set_precision, bp_*_set_policy, bp_stream_create_masked, bp_probe_placement, bp_conv2d*, bp_avgpool, bp_fc,
+ *   bp_maxpool3s2p1, bp_pixel_shuffle2, bp_*_tap_*, bp_*_profile, bp_*_op_stats: no reference counterpart (tuning, measurement and test hooks)
  *
  * Weight streams.  "YOLO stream" = payload of a Darknet .weights file after its
  * header (train_YOLO/src/parser.c:1148-1174): per [convolutional] block in cfg order
@@ -526,6 +526,29 @@ int bp_conv2d(const float* d_in, int N, int H, int W, int Cin, const float* h_w,
 int bp_conv2d_planes(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
                      int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
                      float* d_out, unsigned short* d_out_planes, int iters, float* ms_per_iter, void* stream);
+/* ... and the wider form both forward to, with the launch forms of the SE blocks:
+ * d_res_scale  device [N][Cout] f32 or NULL: the skip connection multiplied by a gate per image and channel (needs d_res);
+ * d_pool_out   device [ceil(M / 64)][Cout] f32 or NULL, M = N OH OW: the launch's epilogue also writes the column sums of
+ *              conv + bias over every 64-row slab (the global average pool as slice sums).  Only under the engine's own
+ *              precondition -- a 64x64 tile, NHWC store, no residual, linear activation, Cout % 4 == 0, and N == 1 or
+ *              OH OW % 64 == 0 -- otherwise the call fails and nothing is launched. */
+int bp_conv2d_se(const float* d_in, int N, int H, int W, int Cin, const float* h_w, const float* h_bias, int Cout, int k,
+                 int stride, int pad, int act, int store_mode, const float* d_res, int res_after_act, int tile, int splits,
+                 float* d_out, unsigned short* d_out_planes, const float* d_res_scale, float* d_pool_out, int iters,
+                 float* ms_per_iter, void* stream);
+/* The auxiliary kernels of the SE blocks and the DUC layers, one launch each (unit tests); every call waits for its launch.
+ * bp_avgpool: d_in NHWC view [N][HW][C] with row stride in_ld >= C -> d_out [N][*parts][C], the SUMS of *parts pixel slices
+ *   of ceil(HW / *parts) pixels each (empty slices 0); d_out NULL: only *parts is returned.
+ * bp_fc: d_out[b][o] = act(h_bias[o] + sum_i h_w[o][i] x[b][i]), act 0 linear / 2 relu / 3 sigmoid, x = d_in [N][Cin]
+ *   (in_parts == 1) or in_scale * sum_p d_in[b][p][i] (d_in [N][in_parts][Cin]); Cin % 4 == 0; h_w host [Cout][Cin].
+ * bp_maxpool3s2p1: NHWC [N][H][W][C] -> [N][(H-1)/2+1][(W-1)/2+1][C], 3x3 / stride 2 / pad 1, C % 4 == 0.
+ * bp_pixel_shuffle2: NHWC [N][H][W][C] -> [N][2H][2W][C/4], out[c, 2h+i, 2w+j] = in[4c + 2i + j, h, w].
+ *   d_out_planes: NULL (np 0), or [np][output elements] u16 operand planes of the output (np 1 fp16 / 3 bf16x3). */
+int bp_avgpool(const float* d_in, int in_ld, int N, int HW, int C, float* d_out, int* parts, void* stream);
+int bp_fc(const float* d_in, const float* h_w, const float* h_bias, int N, int Cin, int Cout, int act, int in_parts, float in_scale,
+          float* d_out, void* stream);
+int bp_maxpool3s2p1(const float* d_in, int N, int H, int W, int C, float* d_out, unsigned short* d_out_planes, int np, void* stream);
+int bp_pixel_shuffle2(const float* d_in, int N, int H, int W, int C, float* d_out, unsigned short* d_out_planes, int np, void* stream);
 
 /* ---- whole frame on device: resize -> detector -> select -> crop -> KPD -> arg-max, optionally as one hipGraph ---- */
 /* d_frames [batch][H][W][3] u8 BGR, d_results [batch][BP_RESULT_FLOATS], d_hm [batch][50][80][64]: caller-owned

@@ -694,8 +694,9 @@ def test_conv_halo_full_size_layers(cuda):
 # behind it -- the look-ahead NL is min(nl, 2) with nl >= 2 required, MS / NG / the grid do not depend on it -- and the two K halves' partial
 # sums are added as own + partner's, one commutative fp32 add per element, whatever the plan.  No row is relaxed.
 #
-# NOT covered here (the hook cannot make these launches): res16 together with the SE channel scale (ConvParams::res_scale -- the hook never
-# sets it), and the fp16 form of conv_fused.hip (no single-launch hook).
+# Covered elsewhere: res16 together with the SE channel scale (ConvParams::res_scale, which bp_conv2d_se sets) -- tests/test_gpu_se_block.py
+# test_res_scale / test_res_scale_s1, oracle 3, on every f16 tile that takes a scaled skip connection.
+# NOT covered (no single-launch hook): the fp16 form of conv_fused.hip.
 F16R_SENTINEL = 0x7FC5A5A5      # a NaN with a payload: no kernel produces these bits
 
 
