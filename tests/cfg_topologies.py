@@ -10,8 +10,10 @@ topologies around them: a route of a route, a layer in two concats, view offsets
 concat members, a head tensor that is also a convolution's input, one head and four heads, and 1x1 -> 3x3 -> 1x1 groups
 that the conv -> conv fusion (conv_fused.hip) may or may not take.
 
-Every case runs at ``RESO`` = 64, the smallest resolution the engine takes: maps are 32, 16 or 8 wide.  Weights and
-inputs are seeded (betapose_amd/synth.py); nothing is read from a fixture.
+A case carries its resolution (``reso(name)``).  It is ``RESO`` = 64 unless the case says otherwise, the smallest the engine
+takes: maps are 32, 16 or 8 wide.  The ``partial_*`` cases run at 160 and 96, where the maps behind strides 8 and 16 are 20, 10,
+12 and 6 wide: no multiple of the fused block kernel's 8 x 8 output patch, which both default networks only ever run on maps
+that are one.  Weights and inputs are seeded (betapose_amd/synth.py); nothing is read from a fixture.
 
 Shared by tests/test_cfg_topologies_host.py (CPU) and tests/test_gpu_cfg_topologies.py (also from its child processes).
 """
@@ -73,12 +75,13 @@ def _cfg(*layers):
     return "\n".join(layers)
 
 
-def _expect(ops, grids, classes=1, shapes=None, absent=(), planes=(), fp32=()):
-    """ops: engine op names that must be in the plan; absent: op names that must NOT be (the layer is a view written in place, or
+def _expect(ops, grids, classes=1, shapes=None, absent=(), planes=(), fp32=(), reso=RESO, fuse=None):
+    """reso: the input resolution the case runs at; fuse: for the cases of the fused block kernel, what must run as one launch (FUSE_* below);
+    ops: engine op names that must be in the plan; absent: op names that must NOT be (the layer is a view written in place, or
     lives in a convolution's epilogue); planes / fp32: convolutions that must / must not run on an operand-plane kernel in the plane
     modes; grids: the heads' grid sizes in cfg order; shapes: layer index -> (C, H) of the layers the case is about."""
     return {"ops": list(ops), "absent": list(absent), "planes": list(planes), "fp32": list(fp32), "heads": len(grids),
-            "grids": list(grids), "classes": classes, "shapes": dict(shapes or {})}
+            "grids": list(grids), "classes": classes, "shapes": dict(shapes or {}), "reso": reso, "fuse": fuse}
 
 
 # name -> (cfg text, expect).  The layer index is written in front of every line.
@@ -248,6 +251,57 @@ CASES = {
     ), _expect([], [16], shapes={10: (64, 32), 11: (128, 32)}, absent=["shortcut10", "concat11"],
                planes=["conv1", "conv2", "conv3", "conv5", "conv8", "conv12"])),
 }
+
+# ---- the fused block kernel (conv_fused.hip) on maps that are no multiple of its 8 x 8 patch.  Two cfgs (a case has at most 16 layers), each
+# at 160 (maps 20 and 10 wide: full and partial patches in one launch, partial widths 4 and 2) and at 96 (12 wide: 4 patches, three of them
+# partial; 6 wide: one patch, partial in both directions).  The template form <mid channels / 32, trailing 1x1, Cin / 32> stands behind each
+# group.  At the default threshold of 48 blocks none of them fuses at batch 1 or 2; the tests that run them fused set BP_FUSE_MIN_BLOCKS=1.
+# Each cfg holds one unfused shortcut of a layer onto itself: the identity between taps that every run is checked for.
+_PARTIAL_S8 = _cfg(
+    conv(32, 3, 2),         # 0
+    conv(64, 3, 2),         # 1
+    conv(64, 3, 2),         # 2   stride 8
+    conv(32, 1, 1),         # 3
+    conv(64, 3, 1),         # 4   pair 64 -> 32 -> 64                                  <1, false, 2>
+    shortcut(-3),           # 5   = 4 + 2, in conv 4's epilogue (added after the activation)
+    conv(64, 1, 1),         # 6
+    conv(64, 3, 1),         # 7
+    conv(128, 1, 1),        # 8   trio, CoutPad of the trailing 1x1 = 128               <2, true, 2>
+    conv(64, 1, 1),         # 9
+    conv(128, 3, 1),        # 10  pair 128 -> 64 -> 128: two N tiles per patch          <2, false, 4>
+    shortcut(-3),           # 11  = 10 + 8, in conv 10's epilogue
+    shortcut(-1),           # 12  = 11 + 11, unfused
+    head(1),                # 13
+    yolo(1),                # 14
+)
+_PARTIAL_S16 = _cfg(
+    conv(32, 3, 2),         # 0
+    conv(64, 3, 2),         # 1
+    conv(64, 3, 2),         # 2
+    conv(256, 3, 2),        # 3   stride 16
+    conv(64, 1, 1),         # 4
+    conv(64, 3, 1),         # 5
+    conv(256, 1, 1),        # 6   the whole bottleneck shape                           <2, true, 8>
+    shortcut(-4),           # 7   = 6 + 3, in conv 6's epilogue
+    shortcut(-1),           # 8   = 7 + 7, unfused
+    conv(64, 1, 1),         # 9
+    conv(80, 3, 1),         # 10  pair 256 -> 64 -> 80: Cout no multiple of 64          <2, false, 8>
+    head(1),                # 11  a 1x1 behind the pair, but from 80 channels: it cannot be the block's third member
+    yolo(1),                # 12
+)
+# What runs as one launch under BP_FUSE_MIN_BLOCKS=1, by mode: the layer indices of each group's members.  bf16x3 takes every group.  The fp16 modes leave the 128 -> 64 -> 128 pair to the plane kernels (conv_fused.hip fused_form, the `g1 == 4` line) unless
+# BP_FUSE_F16_ALL is set ("f16+all").
+FUSE_S8 = {"bf16x3": [(3, 4), (6, 7, 8), (9, 10)], "f16": [(3, 4), (6, 7, 8)], "f16r": [(3, 4), (6, 7, 8)],
+           "f16+all": [(3, 4), (6, 7, 8), (9, 10)]}
+FUSE_S16 = {"bf16x3": [(4, 5, 6), (9, 10)], "f16": [(4, 5, 6), (9, 10)], "f16r": [(4, 5, 6), (9, 10)]}
+for _r in (160, 96):
+    CASES["partial_s8_%d" % _r] = (_PARTIAL_S8, _expect(
+        ["shortcut12"], [_r // 8], shapes={2: (64, _r // 8), 5: (64, _r // 8), 8: (128, _r // 8), 11: (128, _r // 8), 12: (128, _r // 8)},
+        absent=["shortcut5", "shortcut11"], reso=_r, fuse=FUSE_S8))
+    CASES["partial_s16_%d" % _r] = (_PARTIAL_S16, _expect(
+        ["shortcut8"], [_r // 16], shapes={3: (256, _r // 16), 7: (256, _r // 16), 8: (256, _r // 16), 10: (80, _r // 16)},
+        absent=["shortcut7"], reso=_r, fuse=FUSE_S16))
+PARTIAL_CASES = tuple(sorted(n for n in CASES if CASES[n][1]["fuse"]))
 SELECT_CASES = ("heads_1", "heads_4")
 
 
@@ -262,17 +316,21 @@ def stream(name):
     return synth.synth_yolo_stream(WEIGHT_SEED, blocks(name))
 
 
-def rand_input(seed, batch=2):
-    return torch.rand(batch, 3, RESO, RESO, generator=torch.Generator().manual_seed(seed))
+def reso(name):
+    return CASES[name][1]["reso"]
+
+
+def rand_input(seed, batch=2, reso=RESO):
+    return torch.rand(batch, 3, reso, reso, generator=torch.Generator().manual_seed(seed))
 
 
 @functools.lru_cache(None)
 def oracle(name, seed=INPUT_SEED, batch=2):
-    """(input [batch,3,64,64], oracle rows [batch, rows, attrs], {layer index: NCHW output}) -- computed once per case and
+    """(input [batch,3,reso,reso], oracle rows [batch, rows, attrs], {layer index: NCHW output}) -- computed once per case and
     shared; callers must not write to them."""
-    x = rand_input(seed, batch)
+    x = rand_input(seed, batch, reso(name))
     keep = {}
-    rows = yolo_ref.darknet_forward(blocks(name), W.split_darknet_stream(blocks(name), stream(name)), x, reso=RESO, keep=keep)
+    rows = yolo_ref.darknet_forward(blocks(name), W.split_darknet_stream(blocks(name), stream(name)), x, reso=reso(name), keep=keep)
     return x, rows, keep
 
 
@@ -317,7 +375,7 @@ def write_cfg(name, directory):
 
 def make_net(name, directory, precision, max_batch=3):
     from betapose_amd.darknet import Darknet
-    net = Darknet(write_cfg(name, directory), reso=RESO, max_batch=max_batch).load_stream(stream(name)).cuda().eval()
+    net = Darknet(write_cfg(name, directory), reso=reso(name), max_batch=max_batch).load_stream(stream(name)).cuda().eval()
     net.set_precision(precision)
     return net
 
@@ -327,7 +385,7 @@ def run_case(net, name, seed=INPUT_SEED):
     store holds another input's values, not this one's from an earlier call.  The taps are read last layer first: reading a
     tap may rebuild its tensor (Net::tap_copy), which must not repair what a later layer has already read."""
     x = oracle(name, seed)[0].cuda()
-    net(rand_input(DECOY_SEED, net.max_batch).cuda())
+    net(rand_input(DECOY_SEED, net.max_batch, reso(name)).cuda())
     out = {"ops": [n for n, _ in net.op_names()], "rows": net.rows, "attrs": net.attrs}
     out["rows1"] = [net(x[b:b + 1]).cpu()[0] for b in range(x.shape[0])]
     out["rows2"] = net(x).cpu()
@@ -337,6 +395,7 @@ def run_case(net, name, seed=INPUT_SEED):
     for i in reversed(range(len(taps))):
         out["taps"][taps[i][0]] = net.tap(i, batch=x.shape[0]).cpu()
     out["tiles"] = op_tiles(net, x.shape[0])
+    out["fused_launches"] = [net.fused_launches(b) for b in (1, 2)]
     return out
 
 
@@ -419,6 +478,119 @@ def identities(name, ops, taps):
         if not torch.equal(taps[str(i)], want):
             bad.append("%s %d: max |d| %.3e" % (t, i, float((taps[str(i)] - want).abs().max())))
     return n, bad
+
+
+# ---------------------------------------------------------------- the fused block kernel on partial patches (PARTIAL_CASES)
+FUSED_REL = {"bf16x3": 3e-5, "f16": 1e-2, "f16r": 1e-2}     # tests/test_gpu_fused.py, fused against unfused: |d| <= rel * max(1, scale)
+
+
+def fuse_plan_misses(name, key, tiles, launches):
+    """What of the case's fusion plan ``CASES[name][1]["fuse"][key]`` does not hold in ``tiles`` (op_tiles) and the engine's count of
+    fused launches: a group that is to fuse reports TILE_NONE for every member but the last and TILE_FUSED for that one; no other
+    convolution reports either -- a group that stays unfused, and the head behind the 80-channel pair, which cannot be a third member."""
+    expect, bad = CASES[name][1]["fuse"][key], []
+    for g in expect:
+        got, want = tuple(tiles["conv%d" % i] for i in g), (TILE_NONE,) * (len(g) - 1) + (TILE_FUSED,)
+        if got != want:
+            bad.append("group %s reports tiles %s, not one fused launch %s" % (g, got, want))
+    members = {i for g in expect for i in g}
+    bad += ["%s is not in a group that may fuse but reports tile %d" % (c, t) for c, t in sorted(tiles.items())
+            if c.startswith("conv") and int(c[4:]) not in members and t in (TILE_NONE, TILE_FUSED)]
+    if launches != len(expect):
+        bad.append("%d fused launches, not %d" % (launches, len(expect)))
+    return bad
+
+
+def evidence_taps(name, tiles, tap_names):
+    """The taps a fused launch stored: those of the convolutions that report TILE_FUSED (named by the shortcut behind the convolution where
+    that lives in its epilogue).  A tensor that exists only inside a block is rebuilt for its tap by the unfused launches (Net::tap_copy):
+    it says nothing about the fused kernel."""
+    bl, out = blocks(name), []
+    for c, t in tiles.items():
+        if c.startswith("conv") and t == TILE_FUSED:
+            i = int(c[4:])
+            folded = bl[i + 1]["type"] == "shortcut" and str(i) not in tap_names
+            out.append(str(i + 1) if folded else str(i))
+    return sorted(out, key=int)
+
+
+def where_off(d, bar):
+    """Where |d| ([batch, C, H, W]) is over ``bar`` on a map cut into 8 x 8 patches from its top left corner.  Per region -- the pixels of
+    full patches, the columns of the partial patches at the right edge, the rows of those at the bottom edge -- the maximum and how many pixels
+    are over the bar; then the pixel columns over the bar above the bottom strip and the pixel rows over the bar left of the right strip (a
+    mask wrong by one pixel shows as a single column or row there)."""
+    px = torch.nan_to_num(d, nan=float("inf")).amax(dim=(0, 1))
+    hf, wf = 8 * (px.shape[0] // 8), 8 * (px.shape[1] // 8)
+    over = px > bar
+    yl, xl = hf or px.shape[0], wf or px.shape[1]      # (a map of one partial patch: every row, every column)
+
+    def region(what, t, o):
+        return "%s max %.3e, %d of %d pixels over the bar" % (what, float(t.max()) if t.numel() else 0.0, int(o.sum()), o.numel())
+    return "; ".join((region("full-patch pixels (y < %d, x < %d)" % (hf, wf), px[:hf, :wf], over[:hf, :wf]),
+                      region("partial column strip (x >= %d)" % wf, px[:, wf:], over[:, wf:]),
+                      region("partial row strip (y >= %d)" % hf, px[hf:, :], over[hf:, :]),
+                      "columns over the bar at y < %d: %s" % (yl, torch.nonzero(over[:yl].any(0)).flatten().tolist()),
+                      "rows over the bar at x < %d: %s" % (xl, torch.nonzero(over[:, :xl].any(1)).flatten().tolist())))
+
+
+def run_batch(net, x):
+    """(rows, {tap name: NCHW tensor}) of one call; the taps are read last layer first (see run_case)."""
+    rows = net(x.cuda()).cpu()
+    names = net.taps()
+    return rows, {names[i][0]: net.tap(i, batch=x.shape[0]).cpu() for i in reversed(range(len(names)))}
+
+
+def fused_vs_plain(precision, rf, rp, picked):
+    """``rf``, ``rp``: run_batch of the fused engine and of its set_fusion(False) twin on one input.  Rows at the mode's bars, every tap at
+    FUSED_REL of its scale.  -> (worst |d| / max(1, scale) over the ``picked`` taps, [what misses]); a picked tap that was not compared
+    is a miss."""
+    worst, first, bad, rel = 0.0, [], [], FUSED_REL[precision]
+    if rows_close(rf[0], rp[0], precision) is not None:
+        bad.append("rows: " + rows_close(rf[0], rp[0], precision))
+    compared = set()
+    for k, t in rf[1].items():
+        ref = rp[1][k]
+        d, scale = (t - ref).abs(), max(1.0, float(ref.abs().max()))
+        if k in picked:
+            compared.add(k)
+            worst = max(worst, float(d.max()) / scale)
+        if not (float(d.max()) <= rel * scale and bool(torch.isfinite(t).all())):
+            (bad if k not in picked else first).append("layer %s%s: max |d| %.3e over %.3e (scale %.2f): %s" % (k, " (stored by a fused launch)" if k in picked else "", float(d.max()), rel * scale, scale, where_off(d, rel * scale)))
+    first += ["tap %s was stored by a fused launch and was not compared" % k for k in picked if k not in compared]
+    return worst, first[::-1] + bad         # (the fused launches' own taps first, in layer order)
+
+
+def fused_partial_case(name, directory, precision, key, check):
+    """One PARTIAL_CASES case in one mode under BP_FUSE_MIN_BLOCKS=1 (set by the caller's process): the plan is the case's
+    ``fuse[key]`` at batch 1, 2 and 3; fused against unfused at batch 1 (either image), 2 and 3 (the oracle holds two images: the third is
+    another seed's) with the taps the fused launches stored named first in a miss; then the fused engine and its unfused twin both meet
+    ``check`` (the oracle's rows and layers, the identities, the repeat)."""
+    fused, plain = make_net(name, directory, precision), make_net(name, directory, precision)
+    plain.set_fusion(False)
+    picked = None
+    for b in (1, 2, 3):
+        assert plain.fused_launches(b) == 0
+        tiles = op_tiles(fused, b)
+        bad = fuse_plan_misses(name, key, tiles, fused.fused_launches(b))
+        assert not bad, (name, key, b, bad, tiles)
+        taps = evidence_taps(name, tiles, [t[0] for t in fused.taps()])
+        assert picked in (None, taps) and len(taps) == len(CASES[name][1]["fuse"][key])
+        picked = taps
+    # fused against unfused first: both plans read the same input, so a wrong border pixel is not diluted by the layers in front, and the
+    # message says where it is
+    x = oracle(name)[0]
+    x3 = torch.cat((x, rand_input(INPUT_SEED + 1, 1, reso(name))))
+    fused(rand_input(DECOY_SEED, fused.max_batch, reso(name)).cuda())
+    for b, xb in ((1, x[:1]), (1, x[1:]), (2, x), (3, x3)):
+        worst, bad = fused_vs_plain(precision, run_batch(fused, xb), run_batch(plain, xb), picked)
+        print("fused against unfused %s %s batch %d taps %s: worst |d| / max(1, scale) %.2e" % (name, key, b, ",".join(picked), worst))
+        for m in bad:
+            print("MISS %s %s batch %d: %s" % (name, key, b, m))
+        assert not bad, (name, key, b, bad[0])
+    rf, rp = run_case(fused, name), run_case(plain, name)
+    assert set(picked) <= set(rf["taps"]), (picked, sorted(rf["taps"]))       # (check compares every tap of the run with the oracle's layer)
+    check(name, precision, rf)
+    check(name, precision, rp)
 
 
 def selected_index(sel):

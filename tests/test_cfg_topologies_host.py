@@ -11,9 +11,9 @@ from betapose_amd import weights as W
 NAMES = sorted(T.CASES)
 
 
-def _trace(blocks):
+def _trace(blocks, reso):
     """(C, H) per layer from the cfg alone (yolo/darknet.py:223-317 semantics), independent of the oracle's arithmetic."""
-    out, c, h = [], 3, T.RESO
+    out, c, h = [], 3, reso
     for i, b in enumerate(blocks):
         t = b["type"]
         if t == "convolutional":
@@ -38,7 +38,10 @@ def _trace(blocks):
 
 def test_the_case_table_is_complete():
     assert set(NAMES) == {"fallback_ops", "head_shared_96", "odd_channels_concat", "offset_mod4", "copy_concat_64", "heads_1", "heads_4",
-                          "up_after_route", "shortcut_after_upsample", "fusable_trios"}
+                          "up_after_route", "shortcut_after_upsample", "fusable_trios",
+                          "partial_s8_160", "partial_s8_96", "partial_s16_160", "partial_s16_96"}
+    assert {n: T.reso(n) for n in NAMES if T.reso(n) != T.RESO} == {"partial_s8_160": 160, "partial_s8_96": 96, "partial_s16_160": 160, "partial_s16_96": 96}
+    assert set(T.PARTIAL_CASES) == {n for n in NAMES if n.startswith("partial_")}
     assert set(T.SELECT_CASES) <= set(NAMES)
 
 
@@ -62,9 +65,9 @@ def test_case_parses_and_its_stream_fits(name):
 def test_oracle_runs_the_case(name):
     blocks, expect = T.blocks(name), T.CASES[name][1]
     x, rows, keep = T.oracle(name)
-    assert x.shape == (2, 3, T.RESO, T.RESO) and float(x.min()) >= 0.0 and float(x.max()) < 1.0
+    assert x.shape == (2, 3, T.reso(name), T.reso(name)) and float(x.min()) >= 0.0 and float(x.max()) < 1.0
     assert rows.shape == (2, 3 * sum(g * g for g in expect["grids"]), 5 + expect["classes"])
-    shapes = _trace(blocks)
+    shapes = _trace(blocks, T.reso(name))
     assert sorted(keep) == list(range(len(blocks)))
     for i, (c, h) in enumerate(shapes):
         assert keep[i].shape == (2, c, h, h), (name, i)

@@ -53,6 +53,8 @@ def test_plan_is_what_the_case_claims(run):
     if precision not in T.PLANE_MODES:       # (f32, and bf16x3 on fp32 activations: no operand planes anywhere)
         assert not [c for c, t in r["tiles"].items() if t in T.PLANE_TILES]
     assert r["rows"] == 3 * sum(g * g for g in expect["grids"]) and r["attrs"] == 5 + expect["classes"]
+    if expect["fuse"]:       # (below the planner's threshold of 48 blocks at batch 1 and 2: this run is the unfused kernels on 20-, 12-, 10- and 6-wide maps)
+        assert r["fused_launches"] == [0, 0]
     # every layer that is not an alias, or a convolution living in its successor's epilogue, has a tap named by its index
     root = T.roots(name)
     assert set(r["taps"]) <= {str(i) for i in range(len(root)) if root[i] == i}
@@ -190,3 +192,40 @@ print("FUSION-OK")
 '''
     r = _child(code, {"BP_FUSE_MIN_BLOCKS": "1"})
     assert r.returncode == 0 and "FUSION-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+def _misses(r):
+    """The child's "MISS" lines (cfg_topologies.fused_partial_case): which taps miss fused against unfused and at which pixels, the fused
+    launches' own taps first."""
+    return "\n".join(line for line in r.stdout.splitlines() if line.startswith("MISS"))[:6000] + "\n"
+
+
+@pytest.mark.parametrize("name", T.PARTIAL_CASES)
+def test_fused_blocks_on_partial_patches(cuda, name):
+    """The fused block kernel (conv_fused.hip) on 20-, 12-, 10- and 6-wide maps, where patches hang over the right and the bottom edge: the
+    halo's zeroing of intermediate pixels outside the image on interior patch positions, the pixel mask of the epilogue, ``TX = (W + 7) >> 3``.
+    ``BP_FUSE_MIN_BLOCKS=1`` lets every group fuse at every batch size.  In bf16x3, f16 and f16r (cfg_topologies.fused_partial_case): the
+    plan from ``op_tiles`` is the case's ``fuse`` table (a run that stayed unfused fails here); the fused engine and its ``set_fusion(False)``
+    twin meet the oracle at the bars of every other case; fused against unfused at batch 1, 2 and 3 at the bars of tests/test_gpu_fused.py
+    on the taps the fused launches themselves stored, with the pixel rows and columns that miss in the message.
+    Forms: s8 <1,false,2> with the skip after the activation, <2,true,2> with CoutPad 128, <2,false,4> with two N tiles (bf16x3 only: fp16
+    leaves it to the plane kernels); s16 <2,true,8> with a skip connection, <2,false,8> with Cout = 80 and the head refused as third member."""
+    code = r'''
+name = %r
+for precision in ("bf16x3", "f16", "f16r"):
+    T.fused_partial_case(name, tmp, precision, precision, check)
+print("PARTIAL-OK")
+''' % name
+    r = _child(code, {"BP_FUSE_MIN_BLOCKS": "1"})
+    assert r.returncode == 0 and "PARTIAL-OK" in r.stdout, _misses(r) + r.stdout[-2000:] + r.stderr[-3000:]
+
+
+def test_fused_f16_pair_with_two_n_tiles_on_partial_patches(cuda):
+    """``BP_FUSE_F16_ALL=1``: the fp16 <2,false,4> form (128 -> 64 -> 128, two N tiles per patch), compiled into every build and planned by
+    none without the switch, on the 20-wide map; the same checks."""
+    code = r'''
+T.fused_partial_case("partial_s8_160", tmp, "f16", "f16+all", check)
+print("F16-ALL-OK")
+'''
+    r = _child(code, {"BP_FUSE_MIN_BLOCKS": "1", "BP_FUSE_F16_ALL": "1"})
+    assert r.returncode == 0 and "F16-ALL-OK" in r.stdout, _misses(r) + r.stdout[-2000:] + r.stderr[-3000:]
