@@ -2,7 +2,10 @@
 
 ``normal_equations_np`` and ``refine_np`` are written from the definition's text (the docstring of
 metrics.refine_poses_depth), not from csrc/icp_math.inc: whole-image array expressions, numpy's pairwise sums and
-numpy.linalg.solve.  Only the renders come from the project (metrics.render_depth on the host, tested on its own)."""
+numpy.linalg.solve.  Only the renders come from the project (metrics.render_depth on the host, tested on its own).
+
+The restatement, the scenes and the helpers take the image ``size`` (default raster_common.SIZE, the camera is
+raster_common.camera(size)); a scene dict carries its ``size`` and ``K``, which ``equations`` and ``refine`` pass on."""
 import functools
 
 import numpy as np
@@ -24,6 +27,7 @@ P_SCENE = 4
 # which the condition number of A, below 2e3 on every pose of these scenes, turns into at most ~ 2e3 * 2e-13 = 4e-10 of a
 # step; the steps shrink geometrically, so the issue's 1e-9 holds with room (measured: 4e-15).
 POSE_TOL = 1e-9
+COND_MAX = 2e3                                  # the condition number that derivation assumes (condition_numbers below)
 
 
 def rodrigues(w):
@@ -34,12 +38,13 @@ def rodrigues(w):
     return np.eye(3) + np.sin(th) * k + (1 - np.cos(th)) * (k @ k)
 
 
-def pixel_terms(depth, test, pose, max_dist, min_cos, c=0.0):
+def pixel_terms(depth, test, pose, max_dist, min_cos, c=0.0, size=rc.SIZE):
     """Everything the definition says about the pixels of one render [H, W] (0 = nothing drawn) and one test depth image
     in pose units (0 = missing): dict of the boolean mask ``take`` [H, W], ``J`` [H, W, 6], ``r`` [H, W], and the two
     threshold quantities ``cos`` and ``dist`` with the mask ``cand`` of the pixels they were decided on."""
     z = np.asarray(depth, dtype=np.float64)
     zt = np.asarray(test, dtype=np.float64)
+    (H, W), K = size, rc.camera(size)
     ys, xs = np.mgrid[0:H, 0:W]
     d = np.stack([(xs + c - K[0, 2]) / K[0, 0], (ys + c - K[1, 2]) / K[1, 1], np.ones((H, W))], axis=-1)
     q = z[..., None] * d
@@ -65,9 +70,9 @@ def pixel_terms(depth, test, pose, max_dist, min_cos, c=0.0):
     return {"take": take, "J": J, "r": r, "cos": cos, "dist": dist, "cand": cand}
 
 
-def accumulate_np(depth, test, pose, max_dist, min_cos, c=0.0):
+def accumulate_np(depth, test, pose, max_dist, min_cos, c=0.0, size=rc.SIZE):
     """[29] = A's upper triangle row by row, b, N, E of one render against one test image."""
-    t = pixel_terms(depth, test, pose, max_dist, min_cos, c)
+    t = pixel_terms(depth, test, pose, max_dist, min_cos, c, size)
     J, r = t["J"][t["take"]], t["r"][t["take"]]
     out = np.zeros(ACC)
     k = 0
@@ -82,16 +87,16 @@ def accumulate_np(depth, test, pose, max_dist, min_cos, c=0.0):
     return out
 
 
-def render(pose, v, f, c=0.0, near=0.01):
-    return metrics.render_depth(np.asarray(pose)[None, :3], v, f, K, (H, W), None, c, near)[0][0]
+def render(pose, v, f, c=0.0, near=0.01, size=rc.SIZE):
+    return metrics.render_depth(np.asarray(pose)[None, :3], v, f, rc.camera(size), size, None, c, near)[0][0]
 
 
-def normal_equations_np(poses, v, f, test_u16, index, depth_scale, max_dist, min_cos, c=0.0):
+def normal_equations_np(poses, v, f, test_u16, index, depth_scale, max_dist, min_cos, c=0.0, size=rc.SIZE):
     out = np.zeros((len(poses), ACC))
     for p, pose in enumerate(poses):
         if 0 <= index[p] < len(test_u16):
-            out[p] = accumulate_np(render(pose, v, f, c), test_u16[index[p]].astype(np.float64) * depth_scale, pose, max_dist,
-                                   min_cos, c)
+            out[p] = accumulate_np(render(pose, v, f, c, size=size), test_u16[index[p]].astype(np.float64) * depth_scale, pose,
+                                   max_dist, min_cos, c, size)
     return out
 
 
@@ -106,7 +111,8 @@ def unpack(acc):
     return A, acc[21:27].copy(), int(acc[27]), float(acc[28])
 
 
-def refine_np(poses, v, f, test_u16, index, depth_scale, iterations=8, max_dist=0.02, min_cos=0.25, min_pixels=32, c=0.0):
+def refine_np(poses, v, f, test_u16, index, depth_scale, iterations=8, max_dist=0.02, min_cos=0.25, min_pixels=32, c=0.0,
+              size=rc.SIZE):
     """(poses_out [P, 3, 4], stats [P, 6]) by the definition."""
     poses = np.asarray(poses, dtype=np.float64)[:, :3, :4]
     out, stats = poses.copy(), np.zeros((len(poses), 6))
@@ -118,10 +124,10 @@ def refine_np(poses, v, f, test_u16, index, depth_scale, iterations=8, max_dist=
         pose, status, done = poses[p].copy(), OK, 0
 
         def measure():
-            _, _, N, E = unpack(accumulate_np(render(pose, v, f, c), test, pose, max_dist, min_cos, c))
+            _, _, N, E = unpack(accumulate_np(render(pose, v, f, c, size=size), test, pose, max_dist, min_cos, c, size))
             return N, (np.sqrt(E / N) if N > 0 else 0.0)
         for k in range(iterations):
-            A, b, N, E = unpack(accumulate_np(render(pose, v, f, c), test, pose, max_dist, min_cos, c))
+            A, b, N, E = unpack(accumulate_np(render(pose, v, f, c, size=size), test, pose, max_dist, min_cos, c, size))
             if k == 0:
                 stats[p, 0], stats[p, 1] = N, (np.sqrt(E / N) if N > 0 else 0.0)
             if N < min_pixels:
@@ -172,7 +178,7 @@ def box_face_cosines(pose):
     return -((BOX_NORMALS @ R.T) * c).sum(-1) / np.linalg.norm(c, axis=-1)
 
 
-def ground_truth(name):
+def ground_truth(name, size=rc.SIZE):
     """The scene's P_SCENE ground-truth poses: raster_common.poses_for(name), and for the box those of its first 32 that
     show THREE faces at more than BOX_MIN_FACE_COS each.  Point-to-plane residuals constrain a pose only along the
     normals they see: with one or two faces of a cube inside min_cos the translation along the hidden normals (and the
@@ -180,8 +186,8 @@ def ground_truth(name):
     asked to approach the ground truth (test_icp_host.test_box_sliding_poses keeps two such poses and checks what does
     hold there)."""
     if name != "box":
-        return rc.poses_for(name, P_SCENE)
-    cand = rc.poses_for("box", 32)
+        return rc.poses_for(name, P_SCENE, size)
+    cand = rc.poses_for("box", 32, size)
     keep = [p for p in cand if (box_face_cosines(p) > BOX_MIN_FACE_COS).sum() == 3]
     assert len(keep) >= P_SCENE
     return np.stack(keep[:P_SCENE])
@@ -195,16 +201,16 @@ def box_sliding_ground_truth():
 
 
 @functools.lru_cache(maxsize=None)
-def scene(name, rot_deg=ROT_DEG, trans_fract=TRANS_FRACT, sliding=False):
+def scene(name, rot_deg=ROT_DEG, trans_fract=TRANS_FRACT, sliding=False, size=rc.SIZE):
     """dict of one mesh's refinement scene: ground truth = ground_truth(name) (``sliding``: box_sliding_ground_truth);
     test image p is the host render at ground truth p, quantised to uint16 with a quantum of 5e-5 diameters (every depth
-    of the pose range stays under 65 535 counts); start pose p is ground truth p perturbed.  Computed once per session,
-    read-only."""
+    of the pose range stays under 65 535 counts); start pose p is ground truth p perturbed.  ``size`` is the image's and
+    fixes the camera (raster_common.camera); the dict carries both.  Computed once per session, read-only."""
     v, f = rc.MESHES[name]()
     d = rc.diameter(v)
-    gt = box_sliding_ground_truth() if sliding else ground_truth(name)
+    gt = box_sliding_ground_truth() if sliding else ground_truth(name, size)
     depth_scale = 5e-5 * d
-    depth = metrics.render_depth(gt, v, f, K, (H, W))[0].astype(np.float64)
+    depth = metrics.render_depth(gt, v, f, rc.camera(size), size)[0].astype(np.float64)
     counts = np.round(depth / depth_scale)
     assert counts.max() < 65535
     test = counts.astype(np.uint16)
@@ -214,24 +220,24 @@ def scene(name, rot_deg=ROT_DEG, trans_fract=TRANS_FRACT, sliding=False):
     for a in (v, f, gt, test, start, index):
         a.setflags(write=False)
     return {"v": v, "f": f, "d": d, "gt": gt, "start": start, "test": test, "index": index, "depth_scale": depth_scale,
-            "max_dist": MAX_DIST_FRACT * d, "min_cos": 0.25}
+            "max_dist": MAX_DIST_FRACT * d, "min_cos": 0.25, "size": tuple(size), "K": rc.camera(size)}
 
 
 @functools.lru_cache(maxsize=None)
-def refined_np(name):
+def refined_np(name, size=rc.SIZE):
     """refine_np of a scene with the default iterations and min_pixels, once per session."""
-    s = scene(name)
+    s = scene(name, size=size)
     out, stats = refine_np(s["start"], s["v"], s["f"], s["test"], s["index"], s["depth_scale"], max_dist=s["max_dist"],
-                           min_cos=s["min_cos"])
+                           min_cos=s["min_cos"], size=size)
     out.setflags(write=False)
     stats.setflags(write=False)
     return out, stats
 
 
 @functools.lru_cache(maxsize=None)
-def refined_host(name):
-    s = scene(name)
-    out, stats = metrics.refine_poses_depth(s["start"], s["v"], s["f"], K, s["test"], s["index"], s["depth_scale"],
+def refined_host(name, size=rc.SIZE):
+    s = scene(name, size=size)
+    out, stats = metrics.refine_poses_depth(s["start"], s["v"], s["f"], s["K"], s["test"], s["index"], s["depth_scale"],
                                             max_dist=s["max_dist"], min_cos=s["min_cos"])
     out.setflags(write=False)
     stats.setflags(write=False)
@@ -247,12 +253,58 @@ def threshold_margin(poses, s, c=0.0):
     threshold: the tests' precondition is that it exceeds 1e-9, so no decision hangs on the last bits."""
     worst = np.inf
     for p, pose in enumerate(poses):
-        t = pixel_terms(render(pose, s["v"], s["f"], c), s["test"][s["index"][p]].astype(np.float64) * s["depth_scale"], pose,
-                        s["max_dist"], s["min_cos"], c)
+        t = pixel_terms(render(pose, s["v"], s["f"], c, size=s["size"]),
+                        s["test"][s["index"][p]].astype(np.float64) * s["depth_scale"], pose, s["max_dist"], s["min_cos"], c,
+                        s["size"])
         if t["cand"].any():
             worst = min(worst, np.abs(t["cos"][t["cand"]] - s["min_cos"]).min(),
                         np.abs(t["dist"][t["cand"]] - s["max_dist"]).min())
     return worst
+
+
+def condition_numbers(acc):
+    """The 2-norm condition number of A of every row of normal equations [P, 29]."""
+    return np.array([np.linalg.cond(unpack(a)[0]) for a in acc])
+
+
+def many_scene():
+    """raster_common.MANY_CYCLE poses of the box on the MANY_SIZE image, each with the render of its own ground truth as
+    test image and a perturbed start: the scene the many-poses test cycles through."""
+    size = rc.MANY_SIZE
+    v, f = rc.box()
+    d = rc.diameter(v)
+    gt = rc.many_poses()
+    depth_scale = 5e-5 * d
+    test = np.round(metrics.render_depth(gt, v, f, rc.camera(size), size)[0].astype(np.float64) / depth_scale).astype(np.uint16)
+    rng = np.random.default_rng(141)
+    start = np.stack([perturb(gt[p], rng, d, ROT_DEG, TRANS_FRACT) for p in range(len(gt))])
+    return {"v": v, "f": f, "d": d, "gt": gt, "start": start, "test": test, "index": np.arange(len(gt), dtype=np.int32),
+            "depth_scale": depth_scale, "max_dist": MAX_DIST_FRACT * d, "min_cos": 0.25, "size": size, "K": rc.camera(size)}
+
+
+def closeup_scene(size):
+    """The frame-filling cube of raster_common.edge_cases as an accumulation scene: the test image is the render at that
+    pose, the two start poses are it perturbed.  The random-pose scenes keep their objects round the middle of the
+    image, so their accepted pixels end before the last rows; here they lie in every row but the border's, and so in
+    every 2 048-pixel slice of the device's accumulation, the ragged last one included (take_per_slice shows it)."""
+    v, f, gt, _ = rc.edge_cases(size)["box_closeup"]
+    d = rc.diameter(v)
+    depth_scale = 5e-5 * d
+    counts = np.round(metrics.render_depth(gt[None], v, f, rc.camera(size), size)[0].astype(np.float64) / depth_scale)
+    assert counts.max() < 65535
+    rng = np.random.default_rng(151)
+    start = np.stack([perturb(gt, rng, d, ROT_DEG, TRANS_FRACT) for _ in range(2)])
+    return {"v": v, "f": f, "d": d, "gt": np.stack([gt, gt]), "start": start, "test": counts.astype(np.uint16),
+            "index": np.zeros(2, np.int32), "depth_scale": depth_scale, "max_dist": MAX_DIST_FRACT * d, "min_cos": 0.25,
+            "size": tuple(size), "K": rc.camera(size)}
+
+
+def take_per_slice(pose, p, s, c=0.0, pixels=2048):
+    """The numpy restatement's count of accepted pixels of pose ``p`` of scene ``s``, by slice of ``pixels`` flat
+    pixel indices (icp.hip ICP_PIX: one block of icp_accumulate_kernel each)."""
+    take = pixel_terms(render(pose, s["v"], s["f"], c, size=s["size"]), s["test"][s["index"][p]].astype(np.float64) * s["depth_scale"],
+                       pose, s["max_dist"], s["min_cos"], c, s["size"])["take"].reshape(-1)
+    return np.add.reduceat(take.astype(np.int64), np.arange(0, take.size, pixels))
 
 
 def entry_bounds(acc):
@@ -272,6 +324,18 @@ def entry_bounds(acc):
     return out
 
 
+def worst_bound_ratio(got, want):
+    """The largest |got - want| / entry_bounds(want) over every entry with a bound: what the tests print before
+    assert_equations_close asks for <= 1."""
+    worst = 0.0
+    for g, w in zip(np.asarray(got), np.asarray(want)):
+        bound = entry_bounds(w)
+        on = bound > 0
+        if on.any():
+            worst = max(worst, float((np.abs(g - w)[on] / bound[on]).max()))
+    return worst
+
+
 def assert_equations_close(got, want):
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape
@@ -285,12 +349,12 @@ def assert_equations_close(got, want):
 # ---------------------------------------------------------------- what both test files call and the guard scenes
 
 def equations(s, poses, device=None, **kw):
-    return metrics.icp_normal_equations(poses, s["v"], s["f"], K, s["test"], s["index"], s["depth_scale"], s["max_dist"],
+    return metrics.icp_normal_equations(poses, s["v"], s["f"], s["K"], s["test"], s["index"], s["depth_scale"], s["max_dist"],
                                         s["min_cos"], device=device, **kw)
 
 
 def refine(s, poses, test=None, index=None, device=None, **kw):
-    return metrics.refine_poses_depth(poses, s["v"], s["f"], K, s["test"] if test is None else test,
+    return metrics.refine_poses_depth(poses, s["v"], s["f"], s["K"], s["test"] if test is None else test,
                                       s["index"] if index is None else index, s["depth_scale"], max_dist=s["max_dist"],
                                       min_cos=s["min_cos"], device=device, **kw)
 
@@ -299,7 +363,7 @@ def guard_cases(s):
     """name -> (test images, index, expected status): situations in which the pose must come back bit for bit."""
     far = np.array(s["gt"])
     far[:, 2, 3] += s["d"]                     # one diameter deeper: every |z_t - z_r| exceeds max_dist = 0.2 diameters
-    far_depth = metrics.render_depth(far, s["v"], s["f"], K, (H, W))[0].astype(np.float64)
+    far_depth = metrics.render_depth(far, s["v"], s["f"], s["K"], s["size"])[0].astype(np.float64)
     far_test = np.round(far_depth / s["depth_scale"]).astype(np.uint16)
     return {"all_zero": (np.zeros_like(s["test"]), s["index"], TOO_FEW),
             "no_image": (s["test"], np.full(len(s["index"]), -1, np.int32), NO_IMAGE),

@@ -1,10 +1,38 @@
-"""Meshes, poses, the independent ray caster and the edge cases shared by test_raster_host.py and test_gpu_raster.py."""
+"""Meshes, poses, the independent ray caster and the edge cases shared by test_raster_host.py and test_gpu_raster.py.
+
+Everything that depends on the camera takes ``size=(H, W)``; the camera of a size is ``camera(size)``.  ``SIZES`` are the
+image shapes the raster, VSD, ICP and colour tests run at, and what each opens in the kernels:
+  (48, 64)   3 072 px, the shape of every test before the sizes: W is the wave width and divides the 256-thread block (a
+             lane keeps one column, ``i / W`` is a shift), one VSD slice (vsd.hip VSD_PIX = 4 096), two whole ICP slices
+             (icp.hip ICP_PIX = 2 048).
+  (75, 113)  8 475 px: W is an odd prime above the wave width, so a lane's column changes from pixel to pixel, the border
+             test falls on other lanes in every row and ``i / W`` is a division; three VSD slices (4 096 + 4 096 + 283,
+             the first boundary inside row 36 at x = 28) and five ICP slices (4 x 2 048 + 283).
+  (129, 67)  8 643 px: H > W, W three past a wave; three VSD and five ICP slices, the last of 451 pixels.
+A size opens a slice only for a scene that puts pixels there.  The random poses keep their objects round the middle of
+the image, so the last slice of either kind stays empty in them: the VSD rectangles of test_gpu_raster.py and the
+frame-filling icp_common.closeup_scene are what feed it.
+``MANY`` poses on a ``MANY_SIZE`` image are two more than a grid has columns (65 535): the ``q += gridDim.y`` loops over
+poses and pairs iterate twice, and MANY * 256 elements are more than the 65 535 blocks of raster_finish_kernel hold."""
 import functools
 
 import numpy as np
 
-H, W = 48, 64
-K = np.array([[60.0, 0.0, 31.5], [0.0, 60.0, 23.5], [0.0, 0.0, 1.0]])
+SIZE = (48, 64)
+SIZES = [(48, 64), (75, 113), (129, 67)]
+MANY, MANY_SIZE, MANY_CYCLE = 65538, (16, 16), 7
+
+
+def camera(size=SIZE):
+    """The camera matrix of an image size: f = 60 px at 48 x 64 and in proportion to the tighter side elsewhere, the
+    principal point in the middle of the image."""
+    H, W = size
+    f = 60 * min(W / 64, H / 48)
+    return np.array([[f, 0.0, (W - 1) / 2], [0.0, f, (H - 1) / 2], [0.0, 0.0, 1.0]])
+
+
+H, W = SIZE
+K = camera(SIZE)
 
 
 def rand_rot(rng):
@@ -74,9 +102,10 @@ def diameter(v):
     return float(np.sqrt(((v[:, None, :] - v[None, :, :]) ** 2).sum(axis=2)).max())
 
 
-def poses_for(name, count=4):
+def poses_for(name, count=4, size=SIZE):
     """Seeded random rotations at RANGES[name] diameters: the object spans 23 .. 33 px of the 64 x 48 image (the torus
-    35 .. 46 px, partly cut by the border), a few pixels off the principal point."""
+    35 .. 46 px, partly cut by the border), a few pixels off the principal point.  The poses are the same at every
+    ``size``; the camera's focal length grows with it, so the object fills the same share of the tighter side."""
     v, _ = MESHES[name]()
     d = diameter(v)
     rng = np.random.default_rng(SEEDS[name])
@@ -92,8 +121,9 @@ def camera_vertices(pose, v):
     return v @ pose[:3, :3].T + pose[:3, 3]
 
 
-def ray_cast(pose, v, f, c):
+def ray_cast(pose, v, f, c, size=SIZE):
     """Nearest hit of every pixel's ray with every triangle (Moller-Trumbore, numpy f64): depth z [H, W], 0 = no hit."""
+    (H, W), K = size, camera(size)
     X = camera_vertices(pose, v)
     ys, xs = np.mgrid[0:H, 0:W]
     d = np.stack([(xs + c - K[0, 2]) / K[0, 0], (ys + c - K[1, 2]) / K[1, 1], np.ones((H, W))], axis=-1).reshape(-1, 1, 3)
@@ -107,13 +137,14 @@ def ray_cast(pose, v, f, c):
         qv = np.cross(tv, e1)
         w = (d * qv).sum(-1) * inv
         t = (e2 * qv).sum(-1) * inv
-    hit = (np.abs(det) > 0) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t > 0)
+        hit = (np.abs(det) > 0) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t > 0)    # (det == 0: inf - inf, and no hit)
     t = np.where(hit, t, np.inf).min(axis=1)      # d has z = 1, so t is the depth
     return np.where(np.isfinite(t), t, 0.0).reshape(H, W)
 
 
-def ambiguous(pose, v, f, c, tol=2.0 ** -7):
+def ambiguous(pose, v, f, c, tol=2.0 ** -7, size=SIZE):
     """Pixels whose centre lies within ``tol`` px of a projected triangle edge (f64, unsnapped)."""
+    (H, W), K = size, camera(size)
     X = camera_vertices(pose, v)
     uv = np.stack([K[0, 0] * X[:, 0] / X[:, 2] + K[0, 2] - c, K[1, 1] * X[:, 1] / X[:, 2] + K[1, 2] - c], axis=1)
     a = np.concatenate([uv[f[:, 0]], uv[f[:, 1]], uv[f[:, 2]]])[None]
@@ -127,8 +158,9 @@ def ambiguous(pose, v, f, c, tol=2.0 ** -7):
     return (dist.min(axis=1) < tol).reshape(H, W)
 
 
-def edge_cases():
+def edge_cases(size=SIZE):
     """name -> (vertices, faces, pose [3, 4], near): the situations beyond the random poses."""
+    K = camera(size)
     bv, bf = box()
     sv, sf = icosphere()
     rot = rand_rot(np.random.default_rng(5))
@@ -136,29 +168,97 @@ def edge_cases():
     cases = {}
     # 12 triangles, each box far above the cooperative threshold: nearly the whole frame is covered
     cases["box_closeup"] = (bv, bf, np.hstack([tilt, [[0.02], [-0.01], [0.95]]]), 0.01)
-    cases["half_outside"] = (sv, sf, np.hstack([rot, [[-31.5 * 4.0 / 60.0], [0.3], [4.0]]]), 0.01)
+    cases["half_outside"] = (sv, sf, np.hstack([rot, [[-K[0, 2] * 4.0 / K[0, 0]], [0.3], [4.0]]]), 0.01)   # centre at x = 0
     cases["outside"] = (sv, sf, np.hstack([rot, [[40.0], [0.0], [4.0]]]), 0.01)
     # the cube straddles the camera plane: triangles with a vertex behind `near` are dropped and counted
     cases["behind_near"] = (bv, bf, np.hstack([rot, [[0.1], [0.05], [0.3]]]), 0.01)
     return cases
 
 
+def pixel_quad(corners, depths, size=SIZE, c=0.0):
+    """(vertices [4, 3], faces [2, 3]) of the quad whose corners project to the pixel coordinates ``corners`` (four
+    (u, v) in pixel-index coordinates, in order round the quad) at the camera-space depths ``depths``, drawn at the
+    identity pose and split along the diagonal from corner 0 to corner 2."""
+    K = camera(size)
+    v = np.array([[(u + c - K[0, 2]) / K[0, 0] * z, (w + c - K[1, 2]) / K[1, 1] * z, z] for (u, w), z in zip(corners, depths)])
+    return v, np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+
+
+def pixel_rect(x0, y0, x1, y1, z=2.0, size=SIZE):
+    """The fronto-parallel rectangle that covers exactly the pixels x0 .. x1 - 1 by y0 .. y1 - 1 (top-left rule)."""
+    return pixel_quad([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], [z] * 4, size)
+
+
+# The large-coordinate quad: every vertex projects between 10 000 and 16 000 px from the origin on both axes (snapped:
+# up to 2^22 in 1/256 px), so an edge function multiplies differences of up to 2^23 and reaches about 2^44 -- far beyond
+# 32 bits -- while the quad covers the whole 113 x 75 image and its diagonal from corner 0 to corner 2 crosses it from
+# (0, 14.6) to (59.4, 74): both triangles own a part of the image, and a wrong high half of a product moves the diagonal.
+# The depths differ, so the two planes do too.
+BIG_QUAD_CORNERS = [(-12000.0, -11990.0), (15000.0, -13000.0), (14000.0, 14020.0), (-15000.0, 12000.0)]
+BIG_QUAD_DEPTHS = [2.0, 2.5, 3.0, 2.25]
+BIG_QUAD_SIZE = (75, 113)
+
+
+def big_quad(out_of_range=False):
+    """The large-coordinate quad; ``out_of_range``: corner 2, which both triangles share, moved to u = 16 390 px, just
+    past the +-16 384 px that rs_project accepts."""
+    corners = list(BIG_QUAD_CORNERS)
+    if out_of_range:
+        corners[2] = (16390.0, corners[2][1])
+    return pixel_quad(corners, BIG_QUAD_DEPTHS, BIG_QUAD_SIZE)
+
+
+def many_poses(count=MANY_CYCLE):
+    """``count`` seeded poses of the box that fill a good part of the MANY_SIZE image (the box spans 7 .. 12 of its 16
+    pixels), for the tests that cycle through them MANY times."""
+    rng = np.random.default_rng(41)
+    out = np.tile(np.eye(4)[:3], (count, 1, 1))
+    for p in range(count):
+        out[p, :, :3] = rand_rot(rng)
+        out[p, :, 3] = [rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15), rng.uniform(1.9, 2.4)]
+    return out
+
+
 @functools.lru_cache(maxsize=None)
-def host_render(name, c):
+def host_render(name, c, size=SIZE):
     """(depth [P, H, W], skipped [P]) of the four random poses of a mesh on the host, computed once per session."""
     from betapose_amd import metrics
     v, f = MESHES[name]()
-    depth, skipped = metrics.render_depth(poses_for(name), v, f, K, (H, W), None, c)
+    depth, skipped = metrics.render_depth(poses_for(name, size=size), v, f, camera(size), size, None, c)
     depth.setflags(write=False)
     skipped.setflags(write=False)
     return depth, skipped
 
 
-def vsd_scene(seed=21):
+def vsd_margin(gt, est, v, f, test, index, d, size=SIZE, depth_scale=0.001):
+    """The smallest distance of any pixel of these pairs from a decision of the VSD definition, from the host's
+    intermediates: |dist - dist_test - delta| on the rendered pixels of either render and |rel - tau| on the
+    intersection.  The parity tests' precondition is that it exceeds 1e-9, so a last-bit difference in a distance could
+    not move a count."""
+    from betapose_amd import metrics
+    K = camera(size)
+    dg = metrics.render_depth(gt, v, f, K, size)[0]
+    de = metrics.render_depth(est, v, f, K, size)[0]
+    worst = np.inf
+    for p in range(len(gt)):
+        m = metrics.vsd_masks(test[index[p]].astype(np.float64) * depth_scale, dg[p], de[p], K, metrics.BOP_VSD_DELTA)
+        for name in ("dist_gt", "dist_est"):
+            on = m[name] > 0
+            if on.any():
+                worst = min(worst, np.abs((m[name] - m["dist_test"])[on] - metrics.BOP_VSD_DELTA).min())
+        if m["inter"].any():
+            rel = np.abs(m["dist_gt"] - m["dist_est"])[m["inter"]] / d
+            worst = min(worst, np.abs(rel[:, None] - np.asarray(metrics.BOP_VSD_TAUS)[None]).min())
+    return worst
+
+
+def vsd_scene(seed=21, size=SIZE):
     """The VSD parity scene: the torus and the icosphere are scored in one mesh (the icosphere beside the torus), P = 5
     pairs over T = 2 test images.  The estimates are off by 0 .. 10 % of the diameter; a test image is the render of its
-    first pair's ground truth with an occluder plane over the left part and a band of zeros (missing depth)."""
+    first pair's ground truth with an occluder plane over the left part and a band of zeros (missing depth), both placed
+    in proportion to the image."""
     from betapose_amd import metrics
+    (H, W), K = size, camera(size)
     tv, tf = torus()
     sv, sf = icosphere()
     v = np.concatenate([tv, sv * 0.6 + [0.0, 0.0, 1.2]])
@@ -188,7 +288,8 @@ def vsd_scene(seed=21):
         p = int(np.argmax(index == t))
         depth = metrics.render_depth(gt[p:p + 1], v, f, K, (H, W))[0][0].astype(np.float64)
         scene = np.where(depth > 0, depth, 0.6)                       # a back wall behind the object
-        scene[:, :26 + 4 * t] = np.minimum(scene[:, :26 + 4 * t], float(gt[p, 2, 3]) - 0.08)   # the occluder plane
-        scene[20 + 3 * t:23 + 3 * t, :] = 0.0                         # missing depth
+        edge, top = (26 + 4 * t) * W // 64, (20 + 3 * t) * H // 48
+        scene[:, :edge] = np.minimum(scene[:, :edge], float(gt[p, 2, 3]) - 0.08)   # the occluder plane
+        scene[top:top + 3 * H // 48, :] = 0.0                          # missing depth
         test[t] = np.round(scene * 1000.0).astype(np.uint16)
     return v, f, gt, est, test, index, d

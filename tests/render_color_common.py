@@ -1,7 +1,8 @@
 """What test_render_color_host.py and test_gpu_render_color.py share: seeded vertex colours, an independent numpy f64
 colour ray caster (Moller-Trumbore nearest hit with its face and barycentrics, then the shading formula of DESIGN.md 3.5
 written out in numpy), the scenes of every test, and ``CASES``: name -> function(device) -> tuple of arrays, the calls the
-GPU test repeats on the device and compares byte for byte with the host's."""
+GPU test repeats on the device and compares byte for byte with the host's.  The cases of ``SIZE_FREE`` also take an image
+size, function(device, size) (default raster_common.SIZE; the camera is raster_common.camera(size))."""
 import functools
 
 import numpy as np
@@ -17,8 +18,9 @@ def colors_for(n, seed=11):
     return np.random.default_rng(seed).integers(0, 256, size=(n, 3), dtype=np.uint8)
 
 
-def ray_cast_color(pose, v, f, colors, c, ambient, light):
+def ray_cast_color(pose, v, f, colors, c, ambient, light, size=rc.SIZE):
     """(color [H, W, 3] float64 before rounding is applied as floor(x + 0.5) clipped to 255, hit [H, W] bool)."""
+    (H, W), K = size, rc.camera(size)
     X = rc.camera_vertices(pose, v)
     ys, xs = np.mgrid[0:H, 0:W]
     d = np.stack([(xs + c - K[0, 2]) / K[0, 0], (ys + c - K[1, 2]) / K[1, 1], np.ones((H, W))], axis=-1).reshape(-1, 1, 3)
@@ -117,19 +119,19 @@ BOX_POSES = {
 
 
 def _mesh_case(name, c):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
         v, f = rc.MESHES[name]()
-        return metrics.render_color(rc.poses_for(name), v, f, colors_for(len(v)), K, (H, W), device, pixel_center=c,
-                                    light=LIGHTS[1])
+        return metrics.render_color(rc.poses_for(name, size=size), v, f, colors_for(len(v)), rc.camera(size), size, device,
+                                    pixel_center=c, light=LIGHTS[1])
     return run
 
 
 def _edge_case(name):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
-        v, f, pose, near = rc.edge_cases()[name]
-        return metrics.render_color(pose[None], v, f, colors_for(len(v)), K, (H, W), device, near=near)
+        v, f, pose, near = rc.edge_cases(size)[name]
+        return metrics.render_color(pose[None], v, f, colors_for(len(v)), rc.camera(size), size, device, near=near)
     return run
 
 
@@ -142,43 +144,44 @@ def _quad_case(ambient, cam):
 
 
 def _tie_case(order, poses=1):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
         v, f, col = coincident(order)
-        return metrics.render_color(np.repeat(EYE, poses, axis=0), v, f, col, K, (H, W), device,
+        return metrics.render_color(np.repeat(EYE, poses, axis=0), v, f, col, rc.camera(size), size, device,
                                     image_index=np.zeros(poses, np.int32), images=1, ambient=1.0)
     return run
 
 
 def _index_case(index, images):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
         v, f = rc.torus()
-        return metrics.render_color(rc.poses_for("torus")[:2], v, f, colors_for(len(v)), K, (H, W), device,
+        return metrics.render_color(rc.poses_for("torus", size=size)[:2], v, f, colors_for(len(v)), rc.camera(size), size, device,
                                     image_index=index, images=images)
     return run
 
 
-def _accumulate_case(device):
+def _accumulate_case(device, size=rc.SIZE):
     from betapose_amd import metrics
     (sv, sf, sc, ps), (bv, bf, bc, pb), _ = two_mesh_scene()
-    first = metrics.render_color(ps[None], sv, sf, sc, K, (H, W), device)
-    second = metrics.render_color(pb[None], bv, bf, bc, K, (H, W), device, into=first[:2])
+    first = metrics.render_color(ps[None], sv, sf, sc, rc.camera(size), size, device)
+    second = metrics.render_color(pb[None], bv, bf, bc, rc.camera(size), size, device, into=first[:2])
     return first + second
 
 
 def _boxes_case(names):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
         poses = np.concatenate([BOX_POSES[n] for n in names])
         index = np.minimum(np.arange(len(poses)) // 2, 1).astype(np.int32) if len(poses) > 1 else None
         images = 2 if len(poses) > 1 else 1
-        base = np.full((images, H, W, 3), 9, np.uint8)
-        return (metrics.draw_boxes(base, poses, unit_box_corners(), K, None, device, index, near=0.5),)
+        base = np.full((images,) + tuple(size) + (3,), 9, np.uint8)
+        return (metrics.draw_boxes(base, poses, unit_box_corners(), rc.camera(size), None, device, index, near=0.5),)
     return run
 
 
-def overlay_inputs():
+def overlay_inputs(size=rc.SIZE):
+    H, W = size
     rng = np.random.default_rng(17)
     frames = rng.integers(0, 256, size=(2, H, W, 3), dtype=np.uint8)
     color = rng.integers(0, 256, size=(2, H, W, 3), dtype=np.uint8)
@@ -187,9 +190,9 @@ def overlay_inputs():
 
 
 def _overlay_case(alpha):
-    def run(device):
+    def run(device, size=rc.SIZE):
         from betapose_amd import metrics
-        return (metrics.overlay(*overlay_inputs(), alpha=alpha, device=device),)
+        return (metrics.overlay(*overlay_inputs(size), alpha=alpha, device=device),)
     return run
 
 
@@ -215,10 +218,14 @@ for _alpha in (0, 128, 256):
     CASES["overlay-%d" % _alpha] = _overlay_case(_alpha)
 
 
+# the cases that take an image size: all but the quads, whose expectations are written in pixel coordinates
+SIZE_FREE = sorted(n for n in CASES if not n.startswith("quad-"))
+
+
 @functools.lru_cache(maxsize=None)
-def host(name):
+def host(name, size=rc.SIZE):
     """The host twin's result of a case, computed once per session and read-only."""
-    out = CASES[name](None)
+    out = CASES[name](None) if tuple(size) == rc.SIZE else CASES[name](None, size)
     for a in out:
         a.setflags(write=False)
     return out

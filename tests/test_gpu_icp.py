@@ -1,7 +1,22 @@
 """bp_icp_normal_equations and bp_refine_depth (csrc/icp.hip) against their host twins on the scenes of test_icp_host.py:
 the normal equations within the rounding of an f64 sum and bit-identical between calls; the refined poses with the same
 statuses, step counts and pixel counts; identical bits between two calls, chunk sizes and streams; the guards, the
-argument checks, metrics.refine_poses_depth(device=...) and the harness flag."""
+argument checks, metrics.refine_poses_depth(device=...) and the harness flag.
+
+Image sizes (raster_common.SIZES) and what each opens in icp_accumulate_kernel (ICP_PIX = 2 048 pixels per block):
+  48 x 64     every test that names no size.  Two whole slices; W divides the block, so a lane keeps one column and the
+              border test falls on the same lanes in every row.
+  75 x 113    five slices, 4 x 2 048 + 283; W is an odd prime, so a lane's column changes with every pixel and ``i / W`` is
+              a division; ``partial[(p * gridDim.x + blockIdx.x) * 29 + k]`` and icp_sum_slices run over five slices
+              (chunks of 1 and 3 poses move a pose's rows).
+  129 x 67    five slices, the last of 451 pixels; H > W.
+              In the random-pose scenes the object ends before the last rows: at 75 x 113 their last slice adds nothing,
+              at 129 x 67 only two slices add anything.  test_normal_equations_parity_in_every_slice fills the frame and
+              has accepted pixels in every slice at both sizes: 167 of the 283 at 75 x 113 (the 27 second pixels of a
+              lane there lie in the border row, which never counts), up to 340 of the 451 at 129 x 67, among them second
+              pixels of a lane.
+  16 x 16     with 65 538 poses, two more than a grid has columns: the pose loops of the raster kernels and of
+              icp_accumulate_kernel iterate again."""
 import os
 import subprocess
 import sys
@@ -12,6 +27,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import icp_common as ic  # noqa: E402
+import raster_common as rc  # noqa: E402
 from icp_common import diverged_scene, equations, guard_cases, refine, singular_scene  # noqa: E402
 
 H, W, K = ic.H, ic.W, ic.K
@@ -53,9 +69,13 @@ def assert_refined_like_host(got, want):
 
 @pytest.mark.parametrize("name", ["torus", "box"])
 def test_refine_parity_repeat_chunks_and_stream(name):
+    check_refine_parity_repeat_chunks_and_stream(name, rc.SIZE)
+
+
+def check_refine_parity_repeat_chunks_and_stream(name, size):
     import torch
-    s = ic.scene(name)
-    want = ic.refined_host(name)
+    s = ic.scene(name, size=size)
+    want = ic.refined_host(name, size)
     first = refine(s, s["start"], device="cuda")
     assert_refined_like_host(first, want)
     for p in range(len(first[0])):
@@ -116,6 +136,90 @@ def test_diverged_singular_and_mixed_statuses():
     assert np.array_equal(stats[:, 5], [ic.OK, ic.NO_IMAGE, ic.OK, ic.NO_IMAGE])
     assert np.array_equal(bits(got[[1, 3]]), bits(s["start"][[1, 3]]))
     assert np.abs(got[[0, 2]] - ic.refined_host("box")[0][[0, 2]]).max() <= ic.POSE_TOL
+
+
+# ---------------------------------------------------------------- the other image sizes, many poses
+
+def size_id(size):
+    return "%dx%d" % tuple(size)
+
+
+@pytest.mark.parametrize("c", [0.0, 0.5])
+@pytest.mark.parametrize("name", ["torus", "box"])
+@pytest.mark.parametrize("size", rc.SIZES[1:], ids=size_id)
+def test_normal_equations_parity_and_repeat_at_size(size, name, c):
+    """Five slices per pose, the last ragged, on rows that are no multiple of the block (raster_common.SIZES): within
+    the rounding of an f64 sum of the host twin, the same bits between calls and between chunks of 1 and 3 poses (the
+    stride of ``partial`` between poses), and N exactly the count of the numpy restatement's mask."""
+    s = ic.scene(name, size=size)
+    assert ic.threshold_margin(s["start"], s, c) > 1e-9
+    want = equations(s, s["start"], pixel_center=c)
+    got = equations(s, s["start"], device="cuda", pixel_center=c)
+    print(size, name, c, "N", got[:, 27], "worst |device - host| / bound", ic.worst_bound_ratio(got, want))
+    ic.assert_equations_close(got, want)
+    assert np.array_equal(bits(equations(s, s["start"], device="cuda", pixel_center=c)), bits(got))
+    assert np.array_equal(bits(equations(s, s["start"], device="cuda", pixel_center=c, chunk=1)), bits(got))
+    assert np.array_equal(bits(equations(s, s["start"], device="cuda", pixel_center=c, chunk=3)), bits(got))
+    for p, pose in enumerate(s["start"]):
+        take = ic.pixel_terms(ic.render(pose, s["v"], s["f"], c, size=size), s["test"][p].astype(np.float64) * s["depth_scale"],
+                              pose, s["max_dist"], s["min_cos"], c, size)["take"]
+        assert got[p, 27] == take.sum() and take.sum() >= 200
+
+
+@pytest.mark.parametrize("c", [0.0, 0.5])
+@pytest.mark.parametrize("size", rc.SIZES[1:], ids=size_id)
+def test_normal_equations_parity_in_every_slice(size, c):
+    """The objects of the random-pose scenes end before the last rows, so the last of their five slices adds nothing.
+    icp_common.closeup_scene fills the frame: precondition, from the numpy restatement, every slice of 2 048 pixels
+    holds accepted pixels, the ragged last one too, and at 129 x 67 also beyond its first 256 (the second pixel of a
+    lane; at 75 x 113 those 27 pixels lie in the border row H - 1, which never counts).  Then the usual bars: the host
+    twin within the rounding of an f64 sum, N exactly numpy's, the same bits between calls and chunk sizes."""
+    s = ic.closeup_scene(size)
+    assert ic.threshold_margin(s["start"], s, c) > 1e-9
+    per_slice = np.stack([ic.take_per_slice(pose, p, s, c) for p, pose in enumerate(s["start"])])
+    assert per_slice.shape == (2, 5) and per_slice.min() > 0, per_slice
+    if size == (129, 67):
+        assert ic.take_per_slice(s["start"][1], 1, s, c, pixels=256)[33:].sum() > 0     # flat index >= 4 * 2 048 + 256
+    want = equations(s, s["start"], pixel_center=c)
+    got = equations(s, s["start"], device="cuda", pixel_center=c)
+    ic.assert_equations_close(got, want)
+    assert np.array_equal(got[:, 27], per_slice.sum(axis=1))
+    assert np.array_equal(bits(equations(s, s["start"], device="cuda", pixel_center=c)), bits(got))
+    assert np.array_equal(bits(equations(s, s["start"], device="cuda", pixel_center=c, chunk=1)), bits(got))
+
+
+def test_refine_parity_repeat_chunks_and_stream_at_75x113():
+    s = ic.scene("torus", size=(75, 113))
+    assert ic.threshold_margin(s["start"], s) > 1e-9
+    assert ic.condition_numbers(equations(s, s["start"])).max() < ic.COND_MAX       # what POSE_TOL's derivation assumes
+    check_refine_parity_repeat_chunks_and_stream("torus", (75, 113))
+
+
+def test_guard_returns_the_input_at_75x113():
+    """The guard whose pixels are all looked at and all refused: test images one diameter too deep."""
+    s = ic.scene("torus", size=(75, 113))
+    test, index, status = guard_cases(s)["far"]
+    assert test.shape == s["test"].shape and test.max() > 0
+    got, stats = refine(s, s["start"], test, index, device="cuda")
+    assert np.array_equal(bits(got), bits(s["start"]))
+    assert np.all(stats[:, 5] == status) and np.all(stats[:, 4] == 0) and np.all(stats[:, [0, 2]] == 0)
+
+
+def test_normal_equations_more_poses_than_a_grid_has_columns():
+    """65 538 poses on a 16 x 16 image, cycling through 7 (icp_common.many_scene): the pose loops of the raster kernels
+    and of icp_accumulate_kernel take a second iteration.  The 7 poses alone are held to the host twin; row p of the
+    long call equals row p % 7 of that device result bit for bit."""
+    s = ic.many_scene()
+    assert ic.threshold_margin(s["start"], s) > 1e-9
+    seven = equations(s, s["start"], device="cuda")
+    ic.assert_equations_close(seven, equations(s, s["start"]))
+    assert seven[:, 27].min() >= 32 and len({r.tobytes() for r in seven}) == len(seven)
+    cycle = np.arange(rc.MANY) % len(seven)
+    many = equations(dict(s, index=s["index"][cycle]), s["start"][cycle], device="cuda")
+    whole = rc.MANY // len(seven) * len(seven)
+    assert np.array_equal(bits(many[:whole]).reshape(-1, len(seven), ic.ACC),
+                          np.broadcast_to(bits(seven), (whole // len(seven),) + seven.shape))
+    assert np.array_equal(bits(many[whole:]), bits(seven[:rc.MANY - whole]))
 
 
 def test_refine_rejects_bad_arguments():

@@ -1,6 +1,20 @@
 """bp_render_depth (csrc/raster.hip) and bp_vsd_errors (csrc/vsd.hip) against their host twins: the depth images as uint32
 bit patterns with the skipped counts -- every mesh, pose and edge case of test_raster_host.py, several poses in one call,
-repeated calls and a second stream -- the VSD errors and counts exactly, for every chunk size, and the argument checks."""
+repeated calls and a second stream -- the VSD errors and counts exactly, for every chunk size, and the argument checks.
+
+Image sizes (raster_common.SIZES) and what each opens:
+  48 x 64     every test that names no size.  3 072 px: one slice of vsd_reduce_kernel (VSD_PIX = 4 096), W = the wave width.
+  75 x 113    8 475 px, W an odd prime: ``i / W`` is a division; three VSD slices, 4 096 + 4 096 + 283, so ``i0`` is not 0,
+              the last ``i1`` is ragged and a pair's counters take three atomicAdds; the first slice boundary lies inside
+              row 36.  The cooperative-wave path of raster_tri_kernel walks boxes whose width is no multiple of 64.
+  129 x 67    8 643 px, H > W, W three past a wave: three VSD slices, the last of 451 pixels.
+              The parity scene renders nothing in the last slice at either size; the rectangles of
+              test_vsd_counts_known_by_construction do, one of them in the 451-pixel tail.
+  16 x 16     with 65 538 poses or pairs, two more than a grid has columns: the ``q += gridDim.y`` loops of
+              raster_transform_kernel and raster_tri_kernel and the pair loop of vsd_reduce_kernel iterate again, and
+              raster_finish_kernel strides (16 777 728 elements against 65 535 blocks of 256).
+test_vsd_counts_known_by_construction checks the slices against counts that follow from geometry alone;
+test_render_large_coordinates runs edge functions of about 2^44 and the +-16 384 px range test."""
 import numpy as np
 import pytest
 
@@ -25,7 +39,7 @@ def device_render(poses, v, f, c=0.0, near=0.01, stream=None, size=(H, W)):
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
     _lib.check(_lib.lib().bp_render_depth(_lib.ptr(d_model), len(v), _lib.ptr(d_faces), len(f), _lib.ptr(d_poses), len(poses),
-                                          _lib.ptr(np.ascontiguousarray(K).reshape(9)), size[0], size[1], c, near,
+                                          _lib.ptr(np.ascontiguousarray(rc.camera(size)).reshape(9)), size[0], size[1], c, near,
                                           _lib.ptr(d_depth), _lib.ptr(d_skipped), s.cuda_stream))
     return d_depth.cpu().numpy(), d_skipped.cpu().numpy()
 
@@ -98,13 +112,95 @@ def test_render_bad_face_index_is_skipped_and_counted():
     assert np.array_equal(depth.view(np.uint32), metrics.render_depth(pose, v, f[keep], K, (H, W))[0].view(np.uint32))
 
 
+# ---------------------------------------------------------------- the other image sizes, large coordinates, many poses
+
+NEW_SIZES = rc.SIZES[1:]
+
+
+def size_id(size):
+    return "%dx%d" % tuple(size)
+
+
+@pytest.mark.parametrize("c", [0.0, 0.5])
+@pytest.mark.parametrize("name", ["icosphere", "torus", "box"])
+@pytest.mark.parametrize("size", NEW_SIZES, ids=size_id)
+def test_render_parity_random_poses_at_size(size, name, c):
+    v, f = rc.MESHES[name]()
+    want = rc.host_render(name, c, size)
+    assert (want[0] > 0).any(axis=(1, 2)).all()
+    assert_same_image(device_render(rc.poses_for(name, size=size), v, f, c, size=size), want)
+
+
+@pytest.mark.parametrize("case", ["box_closeup", "half_outside", "outside", "behind_near"])
+@pytest.mark.parametrize("size", NEW_SIZES, ids=size_id)
+def test_render_parity_edge_cases_at_size(size, case):
+    from betapose_amd import metrics
+    v, f, pose, near = rc.edge_cases(size)[case]
+    want = metrics.render_depth(pose[None], v, f, rc.camera(size), size, near=near)
+    assert_same_image(device_render(pose[None], v, f, near=near, size=size), want)
+    assert_same_image(metrics.render_depth(pose[None], v, f, rc.camera(size), size, device="cuda", near=near), want)
+    if case == "behind_near":
+        assert want[1][0] > 0
+    if case == "box_closeup":                   # the cooperative-wave path, on rows that are no multiple of the wave
+        assert (want[0] > 0).mean() > 0.9
+
+
+@pytest.mark.parametrize("out_of_range", [False, True])
+def test_render_large_coordinates(out_of_range):
+    """raster_common.big_quad on the 113 x 75 image: edge products of about 2^44 (test_raster_host holds the host twin
+    to the ray caster there), and one vertex past the +-16 384 px range: two triangles skipped, nothing drawn."""
+    from betapose_amd import metrics
+    size = rc.BIG_QUAD_SIZE
+    v, f = rc.big_quad(out_of_range)
+    pose = np.eye(4)[None, :3]
+    want = metrics.render_depth(pose, v, f, rc.camera(size), size)
+    assert_same_image(device_render(pose, v, f, size=size), want)
+    if out_of_range:
+        assert want[1][0] == 2 and not want[0].any()
+    else:
+        assert want[1][0] == 0 and (want[0] > 0).all()
+
+
+def cycled(a, count=rc.MANY):
+    """``count`` rows that cycle through the rows of ``a``."""
+    return np.ascontiguousarray(np.asarray(a)[np.arange(count) % len(a)])
+
+
+def assert_rows_cycle(got, want):
+    """Row p of ``got`` equals row p % len(want) of ``want``, bit for bit."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if got.dtype.kind == "f":
+        got, want = got.view("u%d" % got.itemsize), want.view("u%d" % want.itemsize)
+    n, whole = len(want), len(got) // len(want) * len(want)
+    assert np.array_equal(got[:whole].reshape((whole // n, n) + got.shape[1:]), np.broadcast_to(want, (whole // n,) + want.shape))
+    assert np.array_equal(got[whole:], want[:len(got) - whole])
+
+
+def test_render_more_poses_than_a_grid_has_columns():
+    """65 538 poses of the box on a 16 x 16 image, cycling through 7: the ``q += gridDim.y`` loops of
+    raster_transform_kernel and raster_tri_kernel take a second iteration for the last three poses, and the 16 777 728
+    elements are more than raster_finish_kernel's 65 535 blocks of 256 hold, so its loop strides.  Image p and
+    skipped[p] equal the host's of pose p % 7 bit for bit; every image was pre-filled with a sentinel."""
+    from betapose_amd import metrics
+    size = rc.MANY_SIZE
+    v, f = rc.box()
+    poses = rc.many_poses()
+    want = metrics.render_depth(poses, v, f, rc.camera(size), size)
+    assert (want[0] > 0).sum(axis=(1, 2)).min() > 50 and len({w.tobytes() for w in want[0]}) == rc.MANY_CYCLE
+    assert rc.MANY > 65535 and rc.MANY * size[0] * size[1] > 65535 * 256
+    depth, skipped = device_render(cycled(poses), v, f, size=size)
+    assert_rows_cycle(depth, want[0])
+    assert_rows_cycle(skipped, want[1])
+
+
 # ---------------------------------------------------------------- VSD
 
-def device_vsd(v, f, gt, est, test, index, d, chunk=0, taus=None, stream=None):
+def device_vsd(v, f, gt, est, test, index, d, chunk=0, taus=None, stream=None, size=(H, W), depth_scale=0.001):
     import torch
     from betapose_amd import _lib, metrics
     taus = np.ascontiguousarray(metrics.BOP_VSD_TAUS if taus is None else taus, np.float64)
     P = len(gt)
+    assert test.shape[1:] == tuple(size) and len(est) == P and len(index) == P      # what the kernel will index
     d_model = torch.from_numpy(np.ascontiguousarray(v, np.float64)).cuda()
     d_faces = torch.from_numpy(np.ascontiguousarray(f, np.int32)).cuda()
     d_gt = torch.from_numpy(np.ascontiguousarray(gt[:, :3, :4]).reshape(P, 12)).cuda()
@@ -117,45 +213,104 @@ def device_vsd(v, f, gt, est, test, index, d, chunk=0, taus=None, stream=None):
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
     _lib.check(_lib.lib().bp_vsd_errors(_lib.ptr(d_model), len(v), _lib.ptr(d_faces), len(f), _lib.ptr(d_gt), _lib.ptr(d_est), P,
-                                        _lib.ptr(np.ascontiguousarray(K).reshape(9)), _lib.ptr(d_test), test.shape[0], H, W,
-                                        0.001, _lib.ptr(d_idx), metrics.BOP_VSD_DELTA, _lib.ptr(taus), len(taus), d, 0.0, 0.01,
-                                        chunk, _lib.ptr(d_err), _lib.ptr(d_counts), s.cuda_stream))
+                                        _lib.ptr(np.ascontiguousarray(rc.camera(size)).reshape(9)), _lib.ptr(d_test),
+                                        test.shape[0], size[0], size[1], depth_scale, _lib.ptr(d_idx), metrics.BOP_VSD_DELTA,
+                                        _lib.ptr(taus), len(taus), d, 0.0, 0.01, chunk, _lib.ptr(d_err), _lib.ptr(d_counts), s.cuda_stream))
     return d_err.cpu().numpy(), d_counts.cpu().numpy()
 
 
 def test_vsd_parity_and_chunks():
+    check_vsd_parity_and_chunks((H, W))
+
+
+def check_vsd_parity_and_chunks(size):
     import torch
     from betapose_amd import metrics
-    v, f, gt, est, test, index, d = rc.vsd_scene()
+    (H, W), K = size, rc.camera(size)
+    v, f, gt, est, test, index, d = rc.vsd_scene(size=size)
     # precondition, from the host's intermediates: no pixel sits within 1e-9 of a threshold, so a last-bit difference in
     # a distance could not move a count
-    dg = metrics.render_depth(gt, v, f, K, (H, W))[0]
-    de = metrics.render_depth(est, v, f, K, (H, W))[0]
-    for p in range(len(gt)):
-        m = metrics.vsd_masks(test[index[p]].astype(np.float64) * 0.001, dg[p], de[p], K, metrics.BOP_VSD_DELTA)
-        on = m["dist_gt"] > 0
-        assert np.abs((m["dist_gt"] - m["dist_test"])[on] - metrics.BOP_VSD_DELTA).min() > 1e-9
-        on = m["dist_est"] > 0
-        assert np.abs((m["dist_est"] - m["dist_test"])[on] - metrics.BOP_VSD_DELTA).min() > 1e-9
-        rel = np.abs(m["dist_gt"] - m["dist_est"])[m["inter"]] / d
-        assert np.abs(rel[:, None] - np.asarray(metrics.BOP_VSD_TAUS)[None]).min() > 1e-9
+    assert rc.vsd_margin(gt, est, v, f, test, index, d, size) > 1e-9
     want_err, want_counts = metrics.pose_errors_vsd(gt, est, v, f, K, test, index, d)
     assert len(np.unique(want_err)) > 10                 # the scene separates the pairs and the taus
     for chunk in (1, 2, 0):
-        err, counts = device_vsd(v, f, gt, est, test, index, d, chunk)
+        err, counts = device_vsd(v, f, gt, est, test, index, d, chunk, size=size)
         assert np.array_equal(counts, want_counts), chunk
         assert np.array_equal(err, want_err), chunk
-    err, counts = device_vsd(v, f, gt, est, test, index, d, 2, stream=torch.cuda.Stream())
+    err, counts = device_vsd(v, f, gt, est, test, index, d, 2, stream=torch.cuda.Stream(), size=size)
     assert np.array_equal(counts, want_counts) and np.array_equal(err, want_err)
     err, counts = metrics.pose_errors_vsd(gt, est, v, f, K, test, index, d, device="cuda", chunk=3)
     assert np.array_equal(counts, want_counts) and np.array_equal(err, want_err)
     # a test index the caller got wrong is reported, not read
     bad = index.copy()
     bad[2] = 2
-    err, counts = device_vsd(v, f, gt, est, test, bad, d)
+    err, counts = device_vsd(v, f, gt, est, test, bad, d, size=size)
     assert np.isnan(err[2]).all() and (counts[2] == -1).all()
     keep = [0, 1, 3, 4]
     assert np.array_equal(err[keep], want_err[keep]) and np.array_equal(counts[keep], want_counts[keep])
+
+
+@pytest.mark.parametrize("size", NEW_SIZES, ids=size_id)
+def test_vsd_parity_and_chunks_at_size(size):
+    """Three pixel slices per pair, the last ragged (raster_common.SIZES): the same scene, chunks, stream and wrapper."""
+    check_vsd_parity_and_chunks(size)
+
+
+# name -> (size, (x0, y0, x1, y1)): rectangles of pixels x0 .. x1 - 1 by y0 .. y1 - 1, by the slices of 4 096 pixels they
+# lie in.  At 75 x 113 pixel 4 096 is (28, 36) and pixel 8 192 is (56, 72); at 129 x 67 pixel 8 192 is (18, 122)
+VSD_RECTS = {"last_slice": ((75, 113), (5, 73, 108, 75)),        # rows 73 .. 74: the ragged slice of 283 pixels alone
+             "first_boundary": ((75, 113), (10, 35, 60, 38)),    # rows 35 .. 37 across pixel 4 096
+             "all_slices": ((75, 113), (5, 30, 100, 75)),        # rows 30 .. 74: pixels in all three
+             "last_slice_129x67": ((129, 67), (3, 123, 64, 129))}   # rows 123 .. 128: the ragged slice of 451 pixels alone
+
+
+@pytest.mark.parametrize("rect", sorted(VSD_RECTS))
+def test_vsd_counts_known_by_construction(rect):
+    """Counts that follow from the geometry alone, not from numpy or the host twin: a pixel-aligned rectangle at depth
+    2 m, ground truth = estimate, against an empty test image and against the surface itself.  Every count is the
+    rectangle's area and every error 0.  With the estimate one pixel column to the right, intersection and union are
+    (w - 1) h and (w + 1) h and every error is 2 h / ((w + 1) h), the equal distances adding nothing."""
+    from betapose_amd import metrics
+    size, (x0, y0, x1, y1) = VSD_RECTS[rect]
+    w, h = x1 - x0, y1 - y0
+    first, last = y0 * size[1] + x0, (y1 - 1) * size[1] + x1 - 1
+    assert 0 <= x0 < x1 < size[1] and 0 <= y0 < y1 <= size[0]
+    assert {"last_slice": first >= 8192, "first_boundary": first < 4096 <= last < 8192,
+            "all_slices": first < 4096 and last >= 8192, "last_slice_129x67": first >= 8192 and last >= 8192 + 256}[rect]
+    z = 2.0
+    v, f = rc.pixel_rect(x0, y0, x1, y1, z, size)
+    test = np.zeros((2,) + size, np.uint16)
+    test[1, y0:y1, x0:x1] = 2000                   # z in millimetres
+    index = np.array([0, 1], np.int32)
+    gt = np.tile(np.eye(4)[:3], (2, 1, 1))
+    err, counts = device_vsd(v, f, gt, gt, test, index, 0.1, size=size)
+    assert np.array_equal(counts, np.full((2, 4), w * h))
+    assert np.array_equal(err, np.zeros((2, len(metrics.BOP_VSD_TAUS))))
+    est = gt.copy()
+    est[:, 0, 3] = z / rc.camera(size)[0, 0]       # one pixel at depth z
+    err, counts = device_vsd(v, f, gt, est, test, index, 0.1, size=size)
+    assert np.array_equal(counts, np.tile([w * h, w * h, (w - 1) * h, (w + 1) * h], (2, 1)))
+    assert np.array_equal(err, np.full((2, len(metrics.BOP_VSD_TAUS)), (2 * h) / ((w + 1) * h)))
+
+
+def test_vsd_more_pairs_than_a_grid_has_columns():
+    """65 538 pairs on a 16 x 16 image over two test images, chunk = 0 (one chunk: 131 076 renders in one raster launch,
+    65 538 pairs in one reduction), cycling through 7 pairs: the pose loops of the raster kernels and the pair loop of
+    vsd_reduce_kernel iterate up to three times.  Row p equals row p % 7 of the host's 7 pairs exactly."""
+    import icp_common as ic
+    from betapose_amd import metrics
+    s = ic.many_scene()
+    size = s["size"]
+    gt, est, test = s["gt"], s["start"], s["test"][:2]
+    index = np.array([0, 1, 0, 1, 1, 0, 1], np.int32)
+    assert rc.vsd_margin(gt, est, s["v"], s["f"], test, index, s["d"], size, s["depth_scale"]) > 1e-9
+    want_err, want_counts = metrics.pose_errors_vsd(gt, est, s["v"], s["f"], s["K"], test, index, s["d"], s["depth_scale"])
+    assert len({r.tobytes() for r in want_counts}) == rc.MANY_CYCLE and (want_counts[:, 0] > 50).all()
+    assert (want_counts[:, 3] > 0).all() and len(np.unique(want_err)) > 10
+    err, counts = device_vsd(s["v"], s["f"], cycled(gt), cycled(est), test, cycled(index), s["d"], 0, size=size,
+                             depth_scale=s["depth_scale"])
+    assert_rows_cycle(counts, want_counts)
+    assert_rows_cycle(err, want_err)
 
 
 def test_argument_checks():

@@ -1,6 +1,11 @@
 """bp_render_color, bp_draw_boxes and bp_overlay (csrc/raster_color.hip) against their host twins, byte for byte: the
 colour bytes, the depth bits and the skipped counts of every case of test_render_color_host.py (render_color_common.CASES),
-bad face indices, pre-filled outputs, a second stream and the Renderer on a device.  64 x 48 images, a few launches each."""
+bad face indices, pre-filled outputs, a second stream and the Renderer on a device.  A few launches each.
+
+Image sizes (raster_common.SIZES): 48 x 64 wherever no size is named (W = the wave width); 75 x 113 for every case that
+takes a size (W an odd prime above the wave width: the per-pixel kernels' ``i / W`` is a division, a lane changes its column
+with every pixel, and the cooperative-wave visibility path walks boxes whose width is no multiple of 64); 129 x 67 once
+(H > W, W three past a wave)."""
 import numpy as np
 import pytest
 
@@ -28,6 +33,28 @@ def test_parity_with_the_host_twin(name):
         assert (want[1] > 0).mean() > 0.9
     if name == "edge-behind_near":
         assert want[2][0] > 0
+
+
+@pytest.mark.parametrize("name", cc.SIZE_FREE)
+def test_parity_with_the_host_twin_at_75x113(name):
+    """Every case that takes an image size on a 113 x 75 image: rows of an odd prime length above the wave width, where
+    a lane of the per-pixel kernels changes its column with every pixel (raster_common.SIZES)."""
+    size = (75, 113)
+    want = cc.host(name, size)
+    assert want[0].shape[1:3] == size
+    assert_same(cc.CASES[name]("cuda", size), want)
+    if name == "edge-box_closeup":
+        assert (want[1] > 0).mean() > 0.9
+    if name == "edge-behind_near":
+        assert want[2][0] > 0
+
+
+def test_parity_with_the_host_twin_at_129x67():
+    """An image higher than wide, W three past a wave: the torus' four poses, shaded."""
+    size = (129, 67)
+    want = cc.host("mesh-torus-0.0", size)
+    assert want[0].shape == (4, 129, 67, 3) and (want[1] > 0).any(axis=(1, 2)).all()
+    assert_same(cc.CASES["mesh-torus-0.0"]("cuda", size), want)
 
 
 def device_render_color(poses, v, f, colors, index=None, images=None, accumulate=0, stream=None, near=0.01):

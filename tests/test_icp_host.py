@@ -58,6 +58,56 @@ def test_refinement_halves_add(name):
     assert np.all(stats[:, 3] < stats[:, 1])
 
 
+SIZE = (75, 113)      # five slices of the device's accumulation, the last ragged (raster_common.SIZES); here: N three times as large
+
+
+@pytest.mark.parametrize("c", [0.0, 0.5])
+def test_normal_equations_match_the_definition_at_75x113(c):
+    s = ic.scene("torus", size=SIZE)
+    assert s["test"].shape[1:] == SIZE
+    assert ic.threshold_margin(s["start"], s, c) > 1e-9
+    want = ic.normal_equations_np(s["start"], s["v"], s["f"], s["test"], s["index"], s["depth_scale"], s["max_dist"],
+                                  s["min_cos"], c, SIZE)
+    assert want[:, 27].min() >= 200
+    cond = ic.condition_numbers(want)
+    assert cond.max() < ic.COND_MAX, cond           # what POSE_TOL's derivation assumes
+    got = equations(s, s["start"], pixel_center=c)
+    print("N", want[:, 27], "cond(A)", cond, "worst |host - numpy| / bound", ic.worst_bound_ratio(got, want))
+    ic.assert_equations_close(got, want)             # (entry 27, N, exactly)
+
+
+@pytest.mark.parametrize("size", [(75, 113), (129, 67)], ids=["75x113", "129x67"])
+def test_normal_equations_match_the_definition_on_a_filled_frame(size):
+    """icp_common.closeup_scene: accepted pixels in every row but the border's (the scene the device test uses to feed
+    every slice of its accumulation), about 8 000 terms per sum."""
+    s = ic.closeup_scene(size)
+    assert ic.threshold_margin(s["start"], s) > 1e-9
+    assert np.stack([ic.take_per_slice(pose, p, s) for p, pose in enumerate(s["start"])]).min() > 0
+    want = ic.normal_equations_np(s["start"], s["v"], s["f"], s["test"], s["index"], s["depth_scale"], s["max_dist"],
+                                  s["min_cos"], 0.0, size)
+    assert want[:, 27].min() >= 7000
+    ic.assert_equations_close(equations(s, s["start"]), want)
+
+
+def test_refinement_at_75x113():
+    """test_refinement_halves_add for the torus on the larger image: the same assertions and bars, after their
+    preconditions (every start pose's threshold margin and cond(A) below COND_MAX)."""
+    s = ic.scene("torus", size=SIZE)
+    assert ic.threshold_margin(s["start"], s) > 1e-9
+    assert ic.condition_numbers(equations(s, s["start"])).max() < ic.COND_MAX
+    want, want_stats = ic.refined_np("torus", SIZE)
+    got, stats = ic.refined_host("torus", SIZE)
+    for p in range(len(got)):
+        before, after = ic.add(s["start"][p], s["gt"][p], s["v"]), ic.add(got[p], s["gt"][p], s["v"])
+        assert after < 0.5 * before, (p, before, after)
+    assert np.array_equal(stats[:, [0, 2, 4, 5]], want_stats[:, [0, 2, 4, 5]])
+    assert np.all(stats[:, 5] == ic.OK) and np.all(stats[:, 4] == 8)
+    print("N_first", stats[:, 0], "worst |host - numpy| of a pose entry", np.abs(got - want).max())
+    assert np.abs(got - want).max() <= ic.POSE_TOL
+    assert np.allclose(stats[:, [1, 3]], want_stats[:, [1, 3]], rtol=1e-6, atol=0)
+    assert np.all(stats[:, 3] < stats[:, 1])
+
+
 def test_box_sliding_poses():
     """Two cube poses that show fewer than three faces inside min_cos: the residual still falls (or the pose is given
     back), and the host twin still follows the definition; nothing is claimed about the distance to the ground truth."""

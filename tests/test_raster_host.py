@@ -14,11 +14,11 @@ from betapose_amd import metrics
 H, W, K = rc.H, rc.W, rc.K
 
 
-def check_against_ray_caster(depth, pose, v, f, c, min_compared=150):
+def check_against_ray_caster(depth, pose, v, f, c, min_compared=150, size=rc.SIZE):
     """Coverage identical and depth equal to 1e-6 relative on every pixel that is not within 2^-7 px of a projected edge;
     at most 5 % of the covered pixels may be ambiguous and at least ``min_compared`` covered pixels must be compared."""
-    ref = rc.ray_cast(pose, v, f, c)
-    amb = rc.ambiguous(pose, v, f, c)
+    ref = rc.ray_cast(pose, v, f, c, size)
+    amb = rc.ambiguous(pose, v, f, c, size=size)
     covered = (ref > 0) | (depth > 0)
     clear = ~amb
     assert np.array_equal((depth > 0) & clear, (ref > 0) & clear)
@@ -78,6 +78,87 @@ def test_vertices_behind_near_are_skipped_and_counted():
     assert np.isfinite(depth).all() and (depth >= 0).all()
     drawn = depth[depth > 0]
     assert len(drawn) and drawn.min() >= near and drawn.max() <= X[:, 2].max()
+
+
+# ---------------------------------------------------------------- the other image sizes (raster_common.SIZES)
+
+NEW_SIZES = rc.SIZES[1:]
+
+
+def size_id(size):
+    return "%dx%d" % tuple(size)
+
+
+@pytest.mark.parametrize("c", [0.0, 0.5])
+@pytest.mark.parametrize("name", ["icosphere", "torus", "box"])
+@pytest.mark.parametrize("size", NEW_SIZES, ids=size_id)
+def test_host_render_matches_ray_caster_at_size(size, name, c):
+    """test_host_render_matches_ray_caster on an image whose width is no multiple of anything and on one higher than
+    wide, with the same bars."""
+    v, f = rc.MESHES[name]()
+    poses = rc.poses_for(name, size=size)
+    depth, skipped = rc.host_render(name, c, size)
+    assert depth.shape == (4,) + tuple(size) and depth.dtype == np.float32 and not skipped.any()
+    for p in range(4):
+        check_against_ray_caster(depth[p], poses[p], v, f, c, size=size)
+
+
+@pytest.mark.parametrize("case,min_compared", [("box_closeup", 150), ("half_outside", 100), ("behind_near", 0)])
+@pytest.mark.parametrize("size", NEW_SIZES, ids=size_id)
+def test_edge_cases_at_size(size, case, min_compared):
+    """The close-up, the object half outside and the cube across the camera plane at the other sizes: what the tests
+    above assert of each at 48 x 64, the first two against the ray caster."""
+    H, W = size
+    v, f, pose, near = rc.edge_cases(size)[case]
+    depth, skipped = metrics.render_depth(pose[None], v, f, rc.camera(size), size, near=near)
+    if case == "behind_near":
+        X = rc.camera_vertices(pose, v)
+        behind = (X[f][:, :, 2] < near).any(axis=1)
+        assert 0 < behind.sum() < len(f) and skipped[0] == behind.sum()
+        assert np.isfinite(depth).all() and (depth >= 0).all()
+        drawn = depth[depth > 0]
+        assert len(drawn) and drawn.min() >= near and drawn.max() <= X[:, 2].max()
+        return
+    assert skipped[0] == 0
+    if case == "box_closeup":
+        assert (depth[0] > 0).mean() > 0.9
+    else:
+        assert (depth[0][:, 0] > 0).any() and not (depth[0][:, W // 2:] > 0).any()
+    check_against_ray_caster(depth[0], pose, v, f, 0.0, min_compared, size)
+
+
+def test_large_coordinates_need_64_bit_edge_functions():
+    """raster_common.big_quad: vertices 10 000 .. 16 000 px from the origin, edge products of about 2^44, the diagonal
+    across the 113 x 75 image.  Coverage and depth against the ray caster with the usual bars; both triangles own pixels."""
+    size = rc.BIG_QUAD_SIZE
+    v, f = rc.big_quad()
+    uv = v[:, :2] / v[:, 2:] * rc.camera(size)[0, 0] + rc.camera(size)[[0, 1], 2]
+    assert np.abs(uv).min() >= 10000 and np.abs(uv).max() <= 16000
+    snapped = np.rint(uv * 256).astype(np.int64)
+    worst = max(abs(int((b - a)[0]) * int((c - a)[1])) for a in snapped for b in snapped for c in snapped)
+    assert worst > 2 ** 43                      # what an edge function multiplies here does not fit in 32 (or 40) bits
+    pose = np.eye(4)[:3]
+    depth, skipped = metrics.render_depth(pose[None], v, f, rc.camera(size), size)
+    assert skipped[0] == 0 and (depth[0] > 0).all()
+    check_against_ray_caster(depth[0], pose, v, f, 0.0, size=size)
+    for tri in f:                               # each triangle alone draws its side of the diagonal
+        one = metrics.render_depth(pose[None], v, tri[None], rc.camera(size), size)[0][0] > 0
+        assert 1000 < one.sum() < one.size - 1000
+
+
+def test_vertex_past_the_projection_range_skips_its_triangles():
+    """The same quad with the shared corner 2 at u = 16 390 px, past RS_MAX_UV = 16 384: both triangles are skipped and
+    counted, nothing is drawn; at u = 16 380 px they are drawn."""
+    size = rc.BIG_QUAD_SIZE
+    v, f = rc.big_quad(out_of_range=True)
+    pose = np.eye(4)[None, :3]
+    depth, skipped = metrics.render_depth(pose, v, f, rc.camera(size), size)
+    assert skipped[0] == 2 and not depth.any()
+    corners = list(rc.BIG_QUAD_CORNERS)
+    corners[2] = (16380.0, corners[2][1])
+    v, f = rc.pixel_quad(corners, rc.BIG_QUAD_DEPTHS, size)
+    depth, skipped = metrics.render_depth(pose, v, f, rc.camera(size), size)
+    assert skipped[0] == 0 and (depth[0] > 0).all()
 
 
 @pytest.mark.parametrize("faces", [[[0, 1, 2], [0, 2, 3]], [[0, 2, 1], [0, 3, 2]], [[0, 1, 3], [1, 2, 3]], [[3, 1, 0], [1, 3, 2]]])

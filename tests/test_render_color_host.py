@@ -253,6 +253,92 @@ def test_overlay_is_the_integer_blend(alpha):
         assert np.array_equal(out, frames)
 
 
+# ---------------------------------------------------------------- 8b. every size-free case on a 113 x 75 image
+SIZE = (75, 113)      # W an odd prime above the wave width (raster_common.SIZES)
+
+
+def check_shading(name, c, color, depth, size):
+    """test_shading_matches_numpy_ray_caster's comparison and bars for the four poses of one mesh."""
+    v, f = rc.MESHES[name]()
+    col = cc.colors_for(len(v))
+    poses = rc.poses_for(name, size=size)
+    for p in range(4):
+        ref, hit = cc.ray_cast_color(poses[p], v, f, col, c, 0.5, cc.LIGHTS[1], size)
+        clear = ~rc.ambiguous(poses[p], v, f, c, size=size)
+        covered = hit | (depth[p] > 0)
+        assert np.array_equal((depth[p] > 0) & clear, hit & clear)
+        both = hit & clear
+        assert (covered & ~clear).sum() <= 0.05 * covered.sum() and both.sum() >= 150
+        diff = np.abs(color[p][both].astype(np.float64) - ref[both])
+        print(name, c, p, "compared", int(both.sum()), "max diff", diff.max(), "pixels off by one", int((diff > 0).any(1).sum()))
+        assert diff.max() <= 1 and ref[both].std() > 10
+
+
+@pytest.mark.parametrize("name", cc.SIZE_FREE)
+def test_size_free_cases_at_75x113(name):
+    """What sections 1 .. 8 assert of a case at 64 x 48, at 113 x 75: the depth and skipped counts are render_depth's,
+    the shading the numpy ray caster's, the tie, image_index and accumulation rules, the integer blend; the boxes stay
+    inside their image and show where they showed."""
+    H, W = SIZE
+    K = rc.camera(SIZE)
+    out = cc.host(name, SIZE)
+    kind, _, rest = name.partition("-")
+    if kind == "mesh":
+        mesh, c = rest.rsplit("-", 1)
+        color, depth, skipped = out
+        want, want_skipped = rc.host_render(mesh, float(c), SIZE)
+        assert color.shape == (4, H, W, 3) and np.array_equal(depth.view(np.uint32), want.view(np.uint32))
+        assert np.array_equal(skipped, want_skipped) and not color[depth == 0].any()
+        check_shading(mesh, float(c), color, depth, SIZE)
+    elif kind == "edge":
+        v, f, pose, near = rc.edge_cases(SIZE)[rest]
+        color, depth, skipped = out
+        want, want_skipped = metrics.render_depth(pose[None], v, f, K, SIZE, near=near)
+        assert np.array_equal(depth.view(np.uint32), want.view(np.uint32)) and np.array_equal(skipped, want_skipped)
+        assert not color[depth == 0].any() and color.any() == (rest != "outside")
+    elif kind == "tie":
+        color, depth, skipped = out
+        drawn = depth[0] > 0
+        first = cc.BLUE if rest == "blue-red" else cc.RED
+        assert drawn.sum() > 300 and np.all(color[0][drawn] == first) and len(skipped) == (2 if rest == "two-poses" else 1)
+        assert np.array_equal(depth, cc.host("tie-red-blue", SIZE)[1])
+    elif kind == "index":
+        single, sdepth, sskipped = cc.host("index-01", SIZE)
+        assert np.array_equal(out[2], sskipped)
+        a_inf, b_inf = (np.where(d > 0, d, np.inf) for d in sdepth.astype(np.float64))
+        first = a_inf <= b_inf
+        if rest == "00":
+            assert np.array_equal(out[1][0].view(np.uint32), np.where(first, sdepth[0], sdepth[1]).view(np.uint32))
+            assert np.array_equal(out[0][0], np.where(first[..., None], single[0], single[1]))
+        else:
+            v, f = rc.torus()
+            for p in range(2):
+                c1, d1, _ = metrics.render_color(rc.poses_for("torus", size=SIZE)[p:p + 1], v, f, cc.colors_for(len(v)), K, SIZE)
+                assert np.array_equal(c1[0], single[p]) and np.array_equal(d1[0], sdepth[p])
+            assert (np.isfinite(a_inf) & np.isfinite(b_inf) & first).any() and (np.isfinite(a_inf) & np.isfinite(b_inf) & ~first).any()
+    elif kind == "accumulate":
+        (sv, sf, sc, ps), (bv, bf, bc, pb), (v, f) = cc.two_mesh_scene()
+        c1, d1, k1, c2, d2, k2 = out
+        alone = metrics.render_color(pb[None], bv, bf, bc, K, SIZE)
+        overlap = (d1[0] > 0) & (alone[1][0] > 0)
+        assert overlap.sum() > 20 and not np.any(d1[0][overlap] == alone[1][0][overlap])    # no fragment ties in depth
+        assert (alone[1][0] > 0).sum() > overlap.sum()                                    # and the box shows beside it
+        want = metrics.render_color(ps[None], v, f, np.concatenate([sc, bc]), K, SIZE)
+        assert np.array_equal(c2, want[0]) and np.array_equal(d2.view(np.uint32), want[1].view(np.uint32))
+        assert not np.array_equal(c2, c1)
+    elif kind == "boxes":
+        drawn = (out[0] != 9).any(axis=-1)
+        assert out[0].shape[1:] == (H, W, 3) and drawn.any() == (rest != "nothing")
+        if rest == "frontal":                       # 4 edges of 37.5 px, 4 of 26.8, 4 of 5.4: 279 less the shared corners
+            assert 200 < drawn.sum() < 320
+    else:
+        assert kind == "overlay"
+        frames, color, depth = cc.overlay_inputs(SIZE)
+        alpha = int(rest)
+        want = (alpha * color.astype(np.int64) + (256 - alpha) * frames.astype(np.int64) + 128) >> 8
+        assert np.array_equal(out[0], np.where((depth > 0)[..., None], want, frames).astype(np.uint8))
+
+
 # ---------------------------------------------------------------- 9. the Renderer mirror
 class _Model:
     def __init__(self, v, f, col_u8):
