@@ -157,6 +157,17 @@ PROTOTYPES = {
     "bp_kpd_augment_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "bp_heatmap_loss_acc": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "bp_heatmap_loss_acc_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "bp_yolo_loss_partials": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bp_yolo_inputs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_yolo_inputs_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bp_yolo_truth": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                vp]),
+    "bp_yolo_truth_host": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
+                                     vp]),
+    "bp_yolo_loss": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp,
+                               C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "bp_yolo_loss_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
+                                    vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
     "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
     "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),

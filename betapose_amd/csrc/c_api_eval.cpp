@@ -11,6 +11,7 @@
 #include "kpd_sample.h"
 #include "pose_tail.h"
 #include "raster.h"
+#include "yolo_train.h"
 
 static void check_pixels(int H, int W) { BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24"); }
 
@@ -100,6 +101,41 @@ static void sample_check_maps(int B, int C, int H, int W) {
     BP_CHECK(B > 0 && C > 0 && H > 0 && W > 0, "B, C, H and W must be positive");
     check_pixels(H, W);
     BP_CHECK((long long)B * C * H * ((W + 3) / 4 * 4) < (1ll << 31), "the map tensor must hold fewer than 2^31 values");
+}
+
+// ---- detector training (yolo_train.hip / yolo_train_host.cpp)
+static void yolo_check_inputs(int N, int H, int W, int B, int net_h, int net_w) {
+    BP_CHECK(N > 0 && H > 0 && W > 0 && B > 0, "N, H, W and B must be positive");
+    BP_CHECK(net_h >= 2 && net_w >= 2, "net_h and net_w must be at least 2");
+    check_pixels(H, W);
+    BP_CHECK((long long)B * 3 * net_h * ((net_w + 3) / 4 * 4) < (1ll << 31), "the input tensor must hold fewer than 2^31 values");
+}
+// crop [B][4] (host copy): the resize needs two source columns and rows; the bounds keep every index an int
+static void yolo_check_crop(const int* crop, int B) {
+    for (int b = 0; b < B; ++b) {
+        const int* c = crop + (size_t)b * 4;
+        BP_CHECK(c[2] >= 2 && c[3] >= 2, "swidth and sheight must be at least 2");
+        BP_CHECK(c[0] > -(1 << 24) && c[0] < (1 << 24) && c[1] > -(1 << 24) && c[1] < (1 << 24) && c[2] < (1 << 24) &&
+                     c[3] < (1 << 24), "pleft, ptop, swidth and sheight must lie below 2^24 in magnitude");
+    }
+}
+static void yolo_check_truth(int M, int B, int classes, int max_boxes, int net_w, int net_h) {
+    BP_CHECK(M >= 0 && B > 0 && classes > 0 && max_boxes > 0 && net_w > 0 && net_h > 0,
+             "B, classes, max_boxes, net_w and net_h must be positive, M not negative");
+    BP_CHECK((long long)B * max_boxes * 5 < (1ll << 31), "the truth tensor must hold fewer than 2^31 values");
+}
+static void yolo_check_loss(int B, int n, int classes, int h, int w, int net_w, int net_h, int total, int max_boxes, int channels,
+                            int focal_loss) {
+    BP_CHECK(focal_loss == 0, "focal_loss is not supported");
+    BP_CHECK(B > 0 && n > 0 && classes > 0 && h > 0 && w > 0 && net_w > 0 && net_h > 0 && total > 0 && max_boxes > 0,
+             "B, n, classes, h, w, net_w, net_h, total and max_boxes must be positive");
+    BP_CHECK(n <= total && classes <= (1 << 16), "n must not exceed total, classes not 65536");
+    BP_CHECK(channels == n * (5 + classes), "the head's channel count must be n * (5 + classes)");
+    check_pixels(h, w);
+    BP_CHECK((long long)B * n * (5 + classes) * h * w < (1ll << 31), "the head's output must hold fewer than 2^31 values");
+}
+static void yolo_check_mask(const int* mask, int n, int total) {
+    for (int i = 0; i < n; ++i) BP_CHECK(mask[i] >= 0 && mask[i] < total, "a mask entry lies outside [0, total)");
 }
 
 // what the four refinement calls check alike, and the parameter block they hand on
@@ -421,6 +457,94 @@ int bp_heatmap_loss_acc(const float* d_out, const float* d_labels, const float* 
     sample_check_maps(B, K, H, W);
     bp::heatmap_loss_acc(d_out, d_labels, d_set_mask, B, K, H, W, d_partial, d_loss, d_acc, d_preds, d_gt, d_dists, d_grad,
                          (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+size_t bp_yolo_loss_partials(int B, int n, int classes, int h, int w) {
+    if (B <= 0 || n <= 0 || classes <= 0 || h <= 0 || w <= 0) return 0;
+    return bp::yolo_loss_partials(B, n, classes, h, w);
+}
+
+int bp_yolo_inputs_host(const unsigned char* frames, int N, int H, int W, const int* frame_index, const int* crop,
+                        const unsigned char* flip, const float* hsv, int B, int net_h, int net_w, float* out) {
+    BP_TRY
+    BP_CHECK(frames && frame_index && crop && flip && out, "null argument");
+    yolo_check_inputs(N, H, W, B, net_h, net_w);
+    yolo_check_crop(crop, B);
+    bp::yolo_inputs_host(frames, N, H, W, frame_index, crop, flip, hsv, B, net_h, net_w, out);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const int* d_crop,
+                   const unsigned char* d_flip, const float* d_hsv, int B, int net_h, int net_w, float* d_out, void* stream) {
+    BP_TRY
+    BP_CHECK(d_frames && d_frame_index && d_crop && d_flip && d_out, "null argument");
+    yolo_check_inputs(N, H, W, B, net_h, net_w);
+    // the crop is read back to be checked before any kernel uses it
+    std::vector<int> crop((size_t)B * 4);
+    BP_HIP(hipMemcpyAsync(crop.data(), d_crop, crop.size() * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    BP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    yolo_check_crop(crop.data(), B);
+    bp::yolo_inputs(d_frames, N, H, W, d_frame_index, d_crop, d_flip, d_hsv, B, net_h, net_w, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_truth_host(const float* labels, int M, const int* first, const int* swap, const float* geom, const unsigned char* flip,
+                       int B, int classes, int max_boxes, int net_w, int net_h, int small_object, int* order, float* truth,
+                       int* kept) {
+    BP_TRY
+    BP_CHECK(first && geom && flip && truth && kept && (M == 0 || (labels && swap && order)), "null argument");
+    yolo_check_truth(M, B, classes, max_boxes, net_w, net_h);
+    BP_CHECK(first[0] >= 0 && first[B] <= M, "first must lie within [0, M]");
+    for (int b = 0; b < B; ++b) BP_CHECK(first[b] <= first[b + 1], "first must be non-decreasing");
+    bp::yolo_truth_host(labels, M, first, swap, geom, flip, B, classes, max_boxes, net_w, net_h, small_object, order, truth, kept);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_truth(const float* d_labels, int M, const int* d_first, const int* d_swap, const float* d_geom,
+                  const unsigned char* d_flip, int B, int classes, int max_boxes, int net_w, int net_h, int small_object,
+                  int* d_order, float* d_truth, int* d_kept, void* stream) {
+    BP_TRY
+    BP_CHECK(d_first && d_geom && d_flip && d_truth && d_kept && (M == 0 || (d_labels && d_swap && d_order)), "null argument");
+    yolo_check_truth(M, B, classes, max_boxes, net_w, net_h);
+    bp::yolo_truth(d_labels, M, d_first, d_swap, d_geom, d_flip, B, classes, max_boxes, net_w, net_h, small_object, d_order,
+                   d_truth, d_kept, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_loss_host(const float* x, int B, int channels, int n, int classes, int h, int w, int net_w, int net_h,
+                      const float* anchors, int total, const int* mask, const float* truth, int max_boxes, float ignore_thresh,
+                      float truth_thresh, int focal_loss, float* act, float* delta, double* cost, double* stats, double* partial) {
+    BP_TRY
+    BP_CHECK(x && anchors && mask && truth && delta && cost && stats && partial && x != delta, "null argument, or x and delta are the same tensor");
+    yolo_check_loss(B, n, classes, h, w, net_w, net_h, total, max_boxes, channels, focal_loss);
+    yolo_check_mask(mask, n, total);
+    bp::yolo_loss_host(x, B, n, classes, h, w, net_w, net_h, anchors, total, mask, truth, max_boxes, ignore_thresh, truth_thresh,
+                       act, delta, cost, stats, partial);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_loss(const float* d_x, int B, int channels, int n, int classes, int h, int w, int net_w, int net_h,
+                 const float* d_anchors, int total, const int* d_mask, const float* d_truth, int max_boxes, float ignore_thresh,
+                 float truth_thresh, int focal_loss, float* d_act, float* d_delta, double* d_cost, double* d_stats,
+                 double* d_partial, void* stream) {
+    BP_TRY
+    BP_CHECK(d_x && d_anchors && d_mask && d_truth && d_delta && d_cost && d_stats && d_partial && d_x != d_delta,
+             "null argument, or x and delta are the same tensor");
+    yolo_check_loss(B, n, classes, h, w, net_w, net_h, total, max_boxes, channels, focal_loss);
+    // the mask indexes the anchors: it is read back to be checked before any kernel uses it
+    std::vector<int> mask(n);
+    BP_HIP(hipMemcpyAsync(mask.data(), d_mask, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    BP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    yolo_check_mask(mask.data(), n, total);
+    bp::yolo_loss(d_x, B, n, classes, h, w, net_w, net_h, d_anchors, total, d_mask, d_truth, max_boxes, ignore_thresh,
+                  truth_thresh, d_act, d_delta, d_cost, d_stats, d_partial, (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

@@ -11,6 +11,7 @@
 #include "icp.h"
 #include "pose_tail.h"
 #include "raster.h"
+#include "yolo_train.h"
 
 namespace bp {
 
@@ -230,6 +231,29 @@ void heatmap_loss_acc(const float* d_out, const float* d_labels, const float* d_
                       double* d_partial, double* d_loss, float* d_acc, int* d_preds, int* d_gt, float* d_dists, float* d_grad,
                       hipStream_t s) {
     launch_heatmap_loss_acc(d_out, d_labels, d_set_mask, B, K, H, W, d_partial, d_loss, d_acc, d_preds, d_gt, d_dists, d_grad, s);
+    BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ detector training
+void yolo_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const int* d_crop,
+                 const unsigned char* d_flip, const float* d_hsv, int B, int net_h, int net_w, float* d_out, hipStream_t s) {
+    launch_yolo_inputs(d_frames, N, H, W, d_frame_index, d_crop, d_flip, d_hsv, B, net_h, net_w, d_out, s);
+    BP_HIP(hipGetLastError());
+}
+
+void yolo_truth(const float* d_labels, int M, const int* d_first, const int* d_swap, const float* d_geom,
+                const unsigned char* d_flip, int B, int classes, int max_boxes, int net_w, int net_h, int small_object,
+                int* d_order, float* d_truth, int* d_kept, hipStream_t s) {
+    launch_yolo_truth(d_labels, M, d_first, d_swap, d_geom, d_flip, B, classes, max_boxes, net_w, net_h, small_object, d_order,
+                      d_truth, d_kept, s);
+    BP_HIP(hipGetLastError());
+}
+
+void yolo_loss(const float* d_x, int B, int n, int classes, int h, int w, int net_w, int net_h, const float* d_anchors, int total,
+               const int* d_mask, const float* d_truth, int max_boxes, float ignore_thresh, float truth_thresh, float* d_act,
+               float* d_delta, double* d_cost, double* d_stats, double* d_partial, hipStream_t s) {
+    launch_yolo_loss(d_x, B, n, classes, h, w, net_w, net_h, d_anchors, total, d_mask, d_truth, max_boxes, ignore_thresh,
+                     truth_thresh, d_act, d_delta, d_cost, d_stats, d_partial, s);
     BP_HIP(hipGetLastError());
 }
 

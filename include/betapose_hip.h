@@ -61,6 +61,9 @@
  *                          cropBox, flip, shuffleLR (torchsample's Rotate is    train_KPD/src/utils/img.py:131-200
  *                          restated from its published source, never compared); train()'s MSELoss(out * setMask, labels)
  *                          and heatmapAccuracy                                  train_KPD/src/utils/eval.py:49-108
+ *   bp_yolo_inputs, bp_yolo_truth, bp_yolo_loss (and their _host twins)
+ *                          load_data_detection (no OpenCV), fill_truth_detection,  train_YOLO/src/data.c:189-225,303-392,811-859
+ *                          forward_yolo_layer with train = 1                       train_YOLO/src/yolo_layer.c:166-282
  *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
  *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
  *                          from its published description, never compared with PCL), a farthest-point alternative,
@@ -443,6 +446,49 @@ int bp_heatmap_loss_acc(const float* d_out, const float* d_labels, const float* 
                         void* stream);
 int bp_heatmap_loss_acc_host(const float* out, const float* labels, const float* set_mask, int B, int K, int H, int W,
                              double* partial, double* loss, float* acc, int* preds, int* gt, float* dists, float* grad);
+/* Detector training: Darknet's detection data path and its [yolo] layer's training forward.  Each
+ * device function is bit-identical to its _host twin, which needs no GPU.
+ *
+ * bp_yolo_inputs: d_out [B][3][net_h][net_w] f32 = one sample of load_data_detection per row of the batch, without its
+ * random draws: frame d_frame_index[b] of d_frames [N][H][W][3] uint8 RGB as u8 / 255 (an index outside [0, N) gives a
+ * zero sample), crop_image by d_crop [B][4] int32 = (pleft, ptop, swidth, sheight) with positions clamped into the frame,
+ * resize_image's two-pass bilinear to (net_w, net_h), flip_image where d_flip [B] uint8 is set, distort_image by
+ * d_hsv [B][3] f32 = (dhue, dsat, dexp) or NULL for no distortion.  swidth, sheight, net_w or net_h below 2 is an
+ * error (the device call reads d_crop back to check it).  Every element is written. */
+int bp_yolo_inputs(const unsigned char* d_frames, int N, int H, int W, const int* d_frame_index, const int* d_crop,
+                   const unsigned char* d_flip, const float* d_hsv, int B, int net_h, int net_w, float* d_out, void* stream);
+int bp_yolo_inputs_host(const unsigned char* frames, int N, int H, int W, const int* frame_index, const int* crop,
+                        const unsigned char* flip, const float* hsv, int B, int net_h, int net_w, float* out);
+/* bp_yolo_truth: fill_truth_detection with correct_boxes.  d_labels [M][5] f32 = (id, x, y, w, h) as parsed from the
+ * label files, sample b owning rows d_first[b] .. d_first[b + 1] (d_first [B + 1] int32; the host call rejects a list
+ * that decreases or leaves [0, M], the kernel clamps it); d_swap [M] int32 = the index randomize_boxes draws at each
+ * step, within the sample's slice (one outside it swaps nothing); d_geom [B][4] f32 = (dx, dy, sx, sy) as
+ * load_data_detection passes them; d_order [M] int32 is scratch.  d_truth [B][max_boxes][5] f32 = (x, y, w, h, id),
+ * zero past the d_kept[b] rows kept.  The list is cut to max_boxes before the filter, as in the reference.
+ * small_object changes no output there and none here. */
+int bp_yolo_truth(const float* d_labels, int M, const int* d_first, const int* d_swap, const float* d_geom,
+                  const unsigned char* d_flip, int B, int classes, int max_boxes, int net_w, int net_h, int small_object,
+                  int* d_order, float* d_truth, int* d_kept, void* stream);
+int bp_yolo_truth_host(const float* labels, int M, const int* first, const int* swap, const float* geom, const unsigned char* flip,
+                       int B, int classes, int max_boxes, int net_w, int net_h, int small_object, int* order, float* truth,
+                       int* kept);
+/* bp_yolo_loss: forward_yolo_layer with train = 1 for one head.  d_x [B][channels][h][w] f32 is the raw head output,
+ * channels = n * (5 + classes) (anything else is an error, as is focal_loss != 0); d_anchors [total][2] f32, d_mask [n]
+ * int32 with values in [0, total) (read back and checked); d_truth [B][max_boxes][5] f32.  d_act (or NULL) = l.output,
+ * d_delta = l.delta, both shaped as d_x and distinct from it; *d_cost (f64) = the sum of delta^2, in f64 in a fixed
+ * order; d_stats [7] f64 = the sums of IoU, class, obj and any-obj, the recall .5 and .75 counts and the count that the
+ * reference's log line divides.  exp, log and the logistic are computed in f64 without a math library.  A truth row
+ * with a negative id, or whose cell lies outside the grid (x or y of exactly 1), is passed over; the reference indexes
+ * outside its arrays there.  d_partial [bp_yolo_loss_partials(B, n, classes, h, w)] f64 is scratch.  No atomics: the
+ * same bits on every run and stream. */
+size_t bp_yolo_loss_partials(int B, int n, int classes, int h, int w);
+int bp_yolo_loss(const float* d_x, int B, int channels, int n, int classes, int h, int w, int net_w, int net_h,
+                 const float* d_anchors, int total, const int* d_mask, const float* d_truth, int max_boxes, float ignore_thresh,
+                 float truth_thresh, int focal_loss, float* d_act, float* d_delta, double* d_cost, double* d_stats,
+                 double* d_partial, void* stream);
+int bp_yolo_loss_host(const float* x, int B, int channels, int n, int classes, int h, int w, int net_w, int net_h,
+                      const float* anchors, int total, const int* mask, const float* truth, int max_boxes, float ignore_thresh,
+                      float truth_thresh, int focal_loss, float* act, float* delta, double* cost, double* stats, double* partial);
 /* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
  * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
  * its _host twin, which needs no GPU.
