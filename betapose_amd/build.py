@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbetapose_hip.so")
 SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_fused.hip", "conv_pl.hip", "conv_s1.hip", "conv_p3.hip", "aux_kernels.hip", "yolo_tail.hip", "pose_metrics.hip", "pose_metrics_sym.hip", "raster.hip", "raster_color.hip", "vsd.hip", "icp.hip", "annotate.hip", "kpd_sample.hip", "yolo_train.hip", "designate.hip", "pose_tail.hip", "pose_tail_cands.hip", "pose_tail_inst.hip", "pnp_ransac.hip", "engine.cpp", "conv_plan.cpp", "host_post.cpp", "raster_host.cpp", "raster_color_host.cpp", "icp_host.cpp", "annotate_host.cpp", "kpd_sample_host.cpp", "yolo_train_host.cpp", "designate_host.cpp", "frame_io.cpp", "jpeg_bmp.cpp", "c_api.cpp", "c_api_conv.cpp", "c_api_pose.cpp", "c_api_eval.cpp", "c_api_io.cpp", "eval_device.cpp", "darknet_compat.cpp"]
-HEADERS = ["bp_common.h", "c_api_util.h", "engine.h", "conv_plan.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "raster_color_math.inc", "icp.h", "icp_math.inc", "annotate.h", "annotate_math.inc", "kpd_sample.h", "kpd_sample_math.inc", "yolo_train.h", "yolo_train_math.inc", "designate.h", "designate_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
+HEADERS = ["bp_common.h", "c_api_util.h", "engine.h", "conv_plan.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "raster_walk.inc", "raster_color_math.inc", "icp.h", "icp_math.inc", "annotate.h", "annotate_math.inc", "kpd_sample.h", "kpd_sample_math.inc", "yolo_train.h", "yolo_train_math.inc", "designate.h", "designate_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
            os.path.join("..", "..", "include", "yolo_v2_class_compat.h")]
 # measured-and-superseded kernels (round-1/2 experiments) live in csrc/experimental/ and are compiled only into
 # libbetapose_hip_exp.so (--experimental); the product library has no input under that directory

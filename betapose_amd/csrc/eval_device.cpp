@@ -18,6 +18,20 @@ namespace bp {
 constexpr size_t RASTER_WS_BYTES = (size_t)256 << 20;      // what the chunked calls keep their workspaces under
 
 namespace {
+// The chunk-size rule: items per pass of `count` items whose workspace takes bytes_per_item each -- as many as keep it
+// under RASTER_WS_BYTES (or `asked`, a caller's own chunk, where that is not 0), at least 1, at most count
+size_t chunk_items(size_t bytes_per_item, size_t count, size_t asked = 0) {
+    return std::max<size_t>(1, std::min(asked ? asked : RASTER_WS_BYTES / bytes_per_item, count));
+}
+
+// the call's image_index [P] on the device, NULL for NULL (pose p -> image p)
+int* upload_image_index(Arena& a, const int* image_index, int P, hipStream_t s) {
+    if (!image_index) return nullptr;
+    int* d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
+    BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    return d_index;
+}
+
 // The renders of one chunk of poses: `slots` z-buffers, posed meshes and skipped counters (zeroed here; nobody reads them)
 struct RasterChunk {
     size_t HW;
@@ -31,9 +45,9 @@ struct RasterChunk {
     }
     // zbuf [(na + nb)][H][W] <- +inf, then poses_a[0 .. na) and poses_b[0 .. nb) drawn into it (launch_raster)
     void draw(const double* model, int n, const int* faces, int F, const double* poses_a, int na, const double* poses_b, int nb,
-              const double* K, int H, int W, double pixel_center, double near_z, hipStream_t s) {
+              const RsCam& cam, int H, int W, hipStream_t s) {
         BP_HIP(hipMemsetD32Async((hipDeviceptr_t)zbuf, 0x7f800000, (size_t)(na + nb) * HW, s));   // +inf
-        launch_raster(model, n, faces, F, poses_a, na, poses_b, nb, K, H, W, pixel_center, near_z, ws, zbuf, skipped, s);
+        launch_raster(model, n, faces, F, poses_a, na, poses_b, nb, cam, H, W, ws, zbuf, skipped, s);
     }
 };
 }  // namespace
@@ -61,16 +75,16 @@ void pose_errors_sym(const double* d_model, int n, const double* d_gt, const dou
 void render_depth(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F, const double* K, int H,
                   int W, double pixel_center, double near_z, float* d_depth, int* d_skipped, hipStream_t s) {
     const size_t HW = (size_t)H * W;
-    size_t chunk = RASTER_WS_BYTES / raster_vertex_bytes(n, 1);
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)P));
+    const size_t chunk = chunk_items(raster_vertex_bytes(n, 1), (size_t)P);
+    const RsCam cam = raster_cam(K, pixel_center, near_z);
     Arena a;
     void* ws = a.alloc_bytes(raster_vertex_bytes(n, (int)chunk));
     BP_HIP(hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)P * HW, s));   // +inf
     BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
     for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
         const int c = (int)std::min(chunk, (size_t)P - p0);
-        launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, c, nullptr, 0, K, H, W, pixel_center, near_z, ws,
-                      (uint32_t*)d_depth + p0 * HW, d_skipped + p0, s);
+        launch_raster(d_model, n, d_faces, F, d_poses + p0 * 12, c, nullptr, 0, cam, H, W, ws, (uint32_t*)d_depth + p0 * HW,
+                      d_skipped + p0, s);
     }
     launch_raster_finish((uint32_t*)d_depth, (size_t)P * HW, s);
     BP_HIP(hipGetLastError());
@@ -91,16 +105,12 @@ void render_color(const double* d_poses, int P, const double* d_model, int n, co
                   unsigned char* d_color, float* d_depth, int* d_skipped, hipStream_t s) {
     const size_t HW = (size_t)H * W;
     // images in flight: 8 bytes of key per pixel; poses in flight: their vertex workspace; each under RASTER_WS_BYTES
-    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 8), (size_t)I));
-    const size_t pchunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / raster_vertex_bytes(n, 1), (size_t)P));
+    const size_t ichunk = chunk_items(HW * 8, (size_t)I), pchunk = chunk_items(raster_vertex_bytes(n, 1), (size_t)P);
+    const RsCam cam = raster_cam(K, pixel_center, near_z);
     Arena a;
     unsigned long long* keys = (unsigned long long*)a.alloc_bytes(ichunk * HW * 8);
     void* ws = a.alloc_bytes(raster_vertex_bytes(n, (int)pchunk));
-    int* d_index = nullptr;
-    if (image_index) {
-        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
-        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    int* d_index = upload_image_index(a, image_index, P, s);
     BP_HIP(hipMemsetAsync(d_skipped, 0, (size_t)P * sizeof(int), s));
     const ColorLight lt{ambient, light[0], light[1], light[2]};
     int p0 = 0;
@@ -110,12 +120,11 @@ void render_color(const double* d_poses, int P, const double* d_model, int n, co
         launch_color_clear(keys, d_depth + i0 * HW, accumulate, (size_t)m * HW, s);
         for (int q0 = p0; q0 < p1; q0 += (int)pchunk) {
             const int c = std::min((int)pchunk, p1 - q0);
-            launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, K, pixel_center, near_z, ws, s);
-            launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, K, H, W, pixel_center, near_z, keys,
-                                    d_skipped, s);
+            launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, nullptr, 0, cam, ws, s);
+            launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, cam, H, W, keys, d_skipped, s);
         }
-        launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, K, H, W, pixel_center, near_z, lt,
-                             d_color + i0 * HW * 3, d_depth + i0 * HW, s);
+        launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, cam, H, W, lt, d_color + i0 * HW * 3,
+                             d_depth + i0 * HW, s);
         p0 = p1;
     }
     BP_HIP(hipGetLastError());
@@ -126,21 +135,18 @@ void draw_boxes(const double* d_poses, int P, const double* d_corners, const uns
                 const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near_z,
                 unsigned char* d_color, hipStream_t s) {
     const size_t HW = (size_t)H * W;
-    const size_t ichunk = std::max<size_t>(1, std::min<size_t>(RASTER_WS_BYTES / (HW * 4), (size_t)I));
+    const size_t ichunk = chunk_items(HW * 4, (size_t)I);
+    const RsCam cam = raster_cam(K, pixel_center, near_z);
     Arena a;
     uint32_t* ids = (uint32_t*)a.alloc_bytes(ichunk * HW * 4);
-    int* d_index = nullptr;
-    if (image_index) {
-        d_index = (int*)a.alloc_bytes((size_t)P * sizeof(int));
-        BP_HIP(hipMemcpyAsync(d_index, image_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    int* d_index = upload_image_index(a, image_index, P, s);
     int p0 = 0;
     for (size_t i0 = 0; i0 < (size_t)I; i0 += ichunk) {
         const int m = (int)std::min(ichunk, (size_t)I - i0);
         const int p1 = raster_pose_range(image_index, P, (int)i0 + m, p0);
         if (p1 > p0)
-            launch_draw_boxes(d_poses, p0, p1 - p0, d_corners, d_corner_colors, d_index, (int)i0, m, K, H, W, pixel_center,
-                              near_z, ids, d_color + i0 * HW * 3, s);
+            launch_draw_boxes(d_poses, p0, p1 - p0, d_corners, d_corner_colors, d_index, (int)i0, m, cam, H, W, ids,
+                              d_color + i0 * HW * 3, s);
         p0 = p1;
     }
     BP_HIP(hipGetLastError());
@@ -159,10 +165,10 @@ void vsd_errors(const double* d_model, int n, const int* d_faces, int F, const d
                 double delta, const double* taus, int n_tau, double diameter, double pixel_center, double near_z, int chunk,
                 double* d_err, int* d_counts, hipStream_t s) {
     const size_t HW = (size_t)H * W;
-    size_t c = (size_t)chunk;
-    if (c == 0)   // both workspaces (2 c z-buffers, 2 c posed meshes) under RASTER_WS_BYTES
-        c = std::min(RASTER_WS_BYTES / (2 * HW * sizeof(float)), RASTER_WS_BYTES / raster_vertex_bytes(n, 2));
-    c = std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+    // without a chunk of the caller's, both workspaces (2 c z-buffers, 2 c posed meshes) stay under RASTER_WS_BYTES:
+    // the larger of the two per-pair sizes decides (the smaller of the two quotients, taken before the clamp)
+    const size_t c = chunk_items(std::max(2 * HW * sizeof(float), raster_vertex_bytes(n, 2)), (size_t)P, (size_t)chunk);
+    const RsCam cam = raster_cam(K, pixel_center, near_z);
     VsdTaus tv{};
     for (int k = 0; k < n_tau; ++k) tv.tau[k] = taus[k];
     Arena a;
@@ -171,7 +177,7 @@ void vsd_errors(const double* d_model, int n, const int* d_faces, int F, const d
     BP_HIP(hipMemsetAsync(acc, 0, (size_t)P * VSD_ACC * sizeof(int), s));
     for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
         const int m = (int)std::min(c, (size_t)P - p0);
-        r.draw(d_model, n, d_faces, F, d_gt + p0 * 12, m, d_est + p0 * 12, m, K, H, W, pixel_center, near_z, s);
+        r.draw(d_model, n, d_faces, F, d_gt + p0 * 12, m, d_est + p0 * 12, m, cam, H, W, s);
         launch_vsd_reduce(r.zbuf, m, d_depth_test, T, d_test_index + p0, H, W, K, pixel_center, depth_scale, delta, tv, n_tau,
                           diameter, acc + p0 * VSD_ACC, s);
     }
@@ -283,11 +289,10 @@ void thin_points(const double* d_points, int n, int keep, unsigned char* d_alive
 }
 
 // ------------------------------------------------------------------ depth refinement (ICP)
-// poses per chunk of the device calls: the z-buffers and the posed meshes of a chunk each stay under RASTER_WS_BYTES
+// poses per chunk of the device calls: without a chunk of the caller's, the z-buffers and the posed meshes of a chunk
+// each stay under RASTER_WS_BYTES (the larger of the two per-pose sizes decides)
 static size_t icp_chunk(int chunk, int n, int P, size_t HW) {
-    size_t c = (size_t)chunk;
-    if (c == 0) c = std::min(RASTER_WS_BYTES / (HW * sizeof(float)), RASTER_WS_BYTES / raster_vertex_bytes(n, 1));
-    return std::max<size_t>(1, std::min<size_t>(c, (size_t)P));
+    return chunk_items(std::max(HW * sizeof(float), raster_vertex_bytes(n, 1)), (size_t)P, (size_t)chunk);
 }
 
 void icp_normal_equations(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F, const double* K,
@@ -295,12 +300,13 @@ void icp_normal_equations(const double* d_poses, int P, const double* d_model, i
                           double near_z, int chunk, double* d_out, hipStream_t s) {
     const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
     const int slices = icp_slices(H, W);
+    const RsCam cam = raster_cam(K, prm.c, near_z);
     Arena a;
     RasterChunk r(a, n, c, HW, s);
     double* partial = (double*)a.alloc_bytes(c * slices * ICP_ACC * sizeof(double));
     for (size_t p0 = 0; p0 < (size_t)P; p0 += c) {
         const int m = (int)std::min(c, (size_t)P - p0);
-        r.draw(d_model, n, d_faces, F, d_poses + p0 * 12, m, nullptr, 0, K, H, W, prm.c, near_z, s);
+        r.draw(d_model, n, d_faces, F, d_poses + p0 * 12, m, nullptr, 0, cam, H, W, s);
         launch_icp_accumulate(r.zbuf, d_poses + p0 * 12, m, d_depth_test, T, d_test_index + p0, H, W, prm, nullptr, partial, s);
         launch_icp_sum(partial, d_test_index + p0, T, m, slices, d_out + p0 * ICP_ACC, s);
     }
@@ -313,6 +319,7 @@ void refine_depth(const double* d_poses, int P, const double* d_model, int n, co
                   int chunk, double* d_poses_out, double* d_stats, hipStream_t s) {
     const size_t HW = (size_t)H * W, c = icp_chunk(chunk, n, P, HW);
     const int slices = icp_slices(H, W);
+    const RsCam cam = raster_cam(K, prm.c, near_z);
     Arena a;
     RasterChunk r(a, n, c, HW, s);
     double* partial = (double*)a.alloc_bytes(c * slices * ICP_ACC * sizeof(double));
@@ -323,7 +330,7 @@ void refine_depth(const double* d_poses, int P, const double* d_model, int n, co
         double* stats = d_stats + p0 * ICP_STATS;
         // the whole loop is enqueued: no host round trip between the iterations
         for (int k = 0; k <= prm.iterations; ++k) {
-            r.draw(d_model, n, d_faces, F, pose, m, nullptr, 0, K, H, W, prm.c, near_z, s);
+            r.draw(d_model, n, d_faces, F, pose, m, nullptr, 0, cam, H, W, s);
             launch_icp_accumulate(r.zbuf, pose, m, d_depth_test, T, d_test_index + p0, H, W, prm, stats, partial, s);
             launch_icp_step(partial, m, slices, k, prm, d_poses + p0 * 12, pose, stats, s);
         }

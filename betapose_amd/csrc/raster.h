@@ -1,6 +1,8 @@
-// Depth rasteriser and VSD: the declarations shared by raster_host.cpp, raster.hip, vsd.hip, eval_device.cpp and
-// c_api_eval.cpp, so a signature that drifts fails to compile.  Needs no HIP header (raster_host.cpp is plain C++): the
-// stream type is declared as hip_runtime_api.h declares it.
+// Depth and colour rasterisers and VSD: the declarations shared by raster_host.cpp, raster.hip, raster_color_host.cpp,
+// raster_color.hip, vsd.hip, eval_device.cpp and c_api_eval.cpp, so a signature that drifts fails to compile.  Needs no HIP
+// header (the host twins are plain C++): the stream type is declared as hip_runtime_api.h declares it.  The loop over a
+// pose's triangles and their pixels belongs to none of those files: it is raster_walk.inc, which the four raster units
+// include.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -16,6 +18,16 @@ struct VsdTaus {
     double tau[VSD_MAX_TAUS];
 };
 
+// the rasterisers' camera (raster_math.inc), built here and nowhere else
+struct RsCam {
+    double fx, fy, cx, cy;
+    double c;       // pixel_center
+    double near;    // vertices with z < near make their triangles skipped
+};
+inline RsCam raster_cam(const double* K, double pixel_center, double near) {      // K 3x3 row-major
+    return RsCam{K[0], K[4], K[2], K[5], pixel_center, near};
+}
+
 // ---- raster_host.cpp: the host twin of launch_render_depth.  poses [P][12], vertices [n][3], faces [F][3], K 3x3, all
 // host; depth [P][H][W] (0 where nothing was drawn), skipped [P].  Returns -1 for a face index outside [0, n), else 0.
 int render_depth_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F, const double* K,
@@ -27,14 +39,13 @@ size_t raster_vertex_bytes(int n, int poses);
 // Draws poses_a[0 .. na) and then poses_b[0 .. nb) (poses_b may be NULL with nb == 0) into zbuf [(na + nb)][H][W], f32
 // bit patterns that the caller has cleared to +inf, and ADDS the skipped triangles of each to skipped [(na + nb)].
 void launch_raster(const double* model, int n, const int* faces, int F, const double* poses_a, int na, const double* poses_b,
-                   int nb, const double* K, int H, int W, double pixel_center, double near, void* vertex_ws, uint32_t* zbuf,
-                   int* skipped, hipStream_t s);
+                   int nb, const RsCam& cam, int H, int W, void* vertex_ws, uint32_t* zbuf, int* skipped, hipStream_t s);
 // +inf -> 0 over `count` values, in place: the z-buffer becomes the public depth image
 void launch_raster_finish(uint32_t* zbuf, size_t count, hipStream_t s);
-// launch_raster's first half alone, for the colour renderer: the camera-space xyz and the snapped uv of `poses` poses
-// into vertex_ws (raster_vertex_bytes(n, poses): xyz [poses][n][3] f64, then uv [poses][n][2] i32)
-void launch_raster_transform(const double* model, int n, const double* poses, int count, const double* K, double pixel_center,
-                             double near, void* vertex_ws, hipStream_t s);
+// launch_raster's first half, which the colour renderer launches alone: the camera-space xyz and the snapped uv of the
+// na + nb poses into vertex_ws (raster_vertex_bytes(n, na + nb): xyz [na + nb][n][3] f64, then uv [na + nb][n][2] i32)
+void launch_raster_transform(const double* model, int n, const double* poses_a, int na, const double* poses_b, int nb,
+                             const RsCam& cam, void* vertex_ws, hipStream_t s);
 
 // ---- raster_color_host.cpp: the host twins of the colour renderer (raster_color.hip), all pointers host.  colors
 // [n][3] u8, image_index [P] or NULL (pose p -> image p), light [3]; color [I][H][W][3] u8, depth [I][H][W] f32.
@@ -62,18 +73,17 @@ void launch_color_clear(unsigned long long* keys, const float* depth, int accumu
 // image img0 of the call; d_image_index [P] of the call or NULL; fragment ids are (call's pose slot) * F + face.  ADDS the
 // skipped triangles to skipped[q0 ..].
 void launch_color_visibility(const int* faces, int F, int n, const void* vertex_ws, int q0, int count,
-                             const int* d_image_index, int img0, const double* K, int H, int W, double pixel_center,
-                             double near, unsigned long long* keys, int* skipped, hipStream_t s);
+                             const int* d_image_index, int img0, const RsCam& cam, int H, int W, unsigned long long* keys,
+                             int* skipped, hipStream_t s);
 // colour and depth of `images` images from their keys: the winner shaded from model, faces, colors and the call's poses
 void launch_color_resolve(const unsigned long long* keys, int images, const double* model, const int* faces, int F,
-                          const unsigned char* colors, const double* poses, const double* K, int H, int W,
-                          double pixel_center, double near, const ColorLight& light, unsigned char* color, float* depth,
-                          hipStream_t s);
+                          const unsigned char* colors, const double* poses, const RsCam& cam, int H, int W,
+                          const ColorLight& light, unsigned char* color, float* depth, hipStream_t s);
 // the 12 box edges of poses [q0, q0 + count) of the call over color, whose first image is image img0 of the call; ids
 // [images][H][W] u32 is scratch that the call clears itself
 void launch_draw_boxes(const double* poses, int q0, int count, const double* corners, const unsigned char* corner_colors,
-                       const int* d_image_index, int img0, int images, const double* K, int H, int W, double pixel_center,
-                       double near, uint32_t* ids, unsigned char* color, hipStream_t s);
+                       const int* d_image_index, int img0, int images, const RsCam& cam, int H, int W, uint32_t* ids,
+                       unsigned char* color, hipStream_t s);
 void launch_overlay(const unsigned char* frames, const unsigned char* color, const float* depth, size_t pixels, int alpha,
                     unsigned char* out, hipStream_t s);
 

@@ -3,10 +3,9 @@
 // raster_math.inc + raster_color_math.inc, the text the host twin (raster_color_host.cpp) compiles too; here is who
 // loops over what:
 //   1. color_clear_kernel, one lane per pixel: the empty key, or the kept key of a pixel an earlier call drew.
-//   2. raster.hip's transform (launch_raster_transform), then color_visibility_kernel, one lane per (pose, triangle)
-//      with raster_tri_kernel's split: a lane walks a small clamped bounding box alone, a box of more than RS_COOP_AREA
-//      pixels is left for the wave (__ballot, __shfl, 64 pixels at a time).  Every covered pixel takes ONE 64-bit
-//      atomicMin of (depth bits << 32 | pose slot * F + face) on global memory.
+//   2. raster.hip's transform (launch_raster_transform), then color_visibility_kernel, one lane per (pose, triangle):
+//      rs_walk (raster_walk.inc, the walk raster_tri_kernel and the host twins run too) with the key buffer as its sink.
+//      Every covered pixel takes ONE 64-bit atomicMin of (depth bits << 32 | pose slot * F + face) on global memory.
 //   3. color_resolve_kernel, one lane per pixel, no atomics: decodes the key and shades the winner from the model, the
 //      faces and the pose (never from the per-chunk vertex workspace), keeps an accumulated pixel, or writes background.
 //   4. box_mark_kernel, one lane per (pose, edge): an integer DDA over major-axis positions clamped to the image, each
@@ -25,6 +24,8 @@ namespace bp {
 namespace {
 
 #include "raster_math.inc"
+#define RS_WALK_DEVICE      // the kernels' walk too, not only the host's
+#include "raster_walk.inc"
 #include "raster_color_math.inc"
 
 constexpr int RC_THREADS = 256;
@@ -46,10 +47,13 @@ __global__ __launch_bounds__(RC_THREADS) void color_clear_kernel(unsigned long l
     }
 }
 
-__device__ __forceinline__ void rc_draw(const RsCam& cam, const RsTri& t, int x, int y, int W, uint32_t id,
-                                        unsigned long long* __restrict__ kb) {
-    if (rs_covers(t, x, y)) atomicMin(&kb[(size_t)y * W + x], rc_key(rs_depth_bits(cam, t, x, y), id));
-}
+struct KeySink {       // smaller key wins: nearest, then the lowest pose slot, then the lowest face
+    unsigned long long* __restrict__ kb;
+    uint32_t id0;       // fragment id of the pose slot's face 0
+    __device__ __forceinline__ void operator()(size_t at, uint32_t bits, int face) const {
+        atomicMin(&kb[at], rc_key(bits, id0 + (uint32_t)face));
+    }
+};
 
 __global__ __launch_bounds__(RC_THREADS) void color_visibility_kernel(const int* __restrict__ faces, int F, int n,
                                                                       const double* __restrict__ xyz, const int* __restrict__ uv,
@@ -57,76 +61,12 @@ __global__ __launch_bounds__(RC_THREADS) void color_visibility_kernel(const int*
                                                                       int img0, RsCam cam, int H, int W,
                                                                       unsigned long long* __restrict__ keys,
                                                                       int* __restrict__ skipped) {
-    const int f = blockIdx.x * RC_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    int ia = -1, ib = -1, ic = -1;
-    if (f < F) {
-        ia = faces[(size_t)f * 3 + 0];
-        ib = faces[(size_t)f * 3 + 1];
-        ic = faces[(size_t)f * 3 + 2];
-    }
-    const bool in_range = (unsigned)ia < (unsigned)n && (unsigned)ib < (unsigned)n && (unsigned)ic < (unsigned)n;
-    for (int qc = blockIdx.y; qc < poses; qc += gridDim.y) {   // (uniform over the block: the ballots below see whole waves)
+    const RsFace face = rs_face(faces, F, blockIdx.x * RC_THREADS + threadIdx.x);
+    for (int qc = blockIdx.y; qc < poses; qc += gridDim.y) {   // (uniform over the block: the walk's ballots see whole waves)
         const int q = q0 + qc;                                 // the call's pose slot
-        const double* X = xyz + (size_t)qc * n * 3;
-        const int* S = uv + (size_t)qc * n * 2;
         const int image = (image_index ? image_index[q] : q) - img0;    // in range: the host chose the chunk by it
-        unsigned long long* kb = keys + (size_t)image * H * W;
-        const uint32_t id = (uint32_t)((unsigned long long)q * F + f);
-        RsTri t = {};
-        int have = 0, skip = 0;
-        if (f < F) {
-            if (!in_range) {
-                skip = 1;
-            } else {
-                const int ax = S[(size_t)ia * 2], ay = S[(size_t)ia * 2 + 1];
-                const int bx = S[(size_t)ib * 2], by = S[(size_t)ib * 2 + 1];
-                const int cx = S[(size_t)ic * 2], cy = S[(size_t)ic * 2 + 1];
-                if (ax == RS_INVALID || bx == RS_INVALID || cx == RS_INVALID) {
-                    skip = 1;
-                } else {
-                    double A[3], B[3], C[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        A[k] = X[(size_t)ia * 3 + k];
-                        B[k] = X[(size_t)ib * 3 + k];
-                        C[k] = X[(size_t)ic * 3 + k];
-                    }
-                    have = rs_setup(A, B, C, ax, ay, bx, by, cx, cy, H, W, &t);
-                }
-            }
-        }
-        const unsigned long long sk = __ballot(skip);
-        if (lane == 0 && sk) atomicAdd(&skipped[q], (int)__popcll(sk));
-
-        int big = 0;
-        if (have) {
-            const int w = t.bx1 - t.bx0 + 1, h = t.by1 - t.by0 + 1;   // w * h <= H * W <= 2^24
-            if (w * h > RS_COOP_AREA) {
-                big = 1;
-            } else {
-                for (int y = t.by0; y <= t.by1; ++y)
-                    for (int x = t.bx0; x <= t.bx1; ++x) rc_draw(cam, t, x, y, W, id, kb);
-            }
-        }
-        // the wave takes its big triangles one after the other, 64 pixels of the box at a time
-        unsigned long long todo = __ballot(big);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            RsTri u;
-            u.x0 = __shfl(t.x0, src, 64); u.y0 = __shfl(t.y0, src, 64);
-            u.x1 = __shfl(t.x1, src, 64); u.y1 = __shfl(t.y1, src, 64);
-            u.x2 = __shfl(t.x2, src, 64); u.y2 = __shfl(t.y2, src, 64);
-            u.bx0 = __shfl(t.bx0, src, 64); u.by0 = __shfl(t.by0, src, 64);
-            u.bx1 = __shfl(t.bx1, src, 64); u.by1 = __shfl(t.by1, src, 64);
-            u.nx = __shfl(t.nx, src, 64); u.ny = __shfl(t.ny, src, 64);
-            u.nz = __shfl(t.nz, src, 64); u.nd = __shfl(t.nd, src, 64);
-            u.zmin = __shfl(t.zmin, src, 64); u.zmax = __shfl(t.zmax, src, 64);
-            const uint32_t uid = id - (uint32_t)lane + (uint32_t)src;      // the source lane's face
-            const int w = u.bx1 - u.bx0 + 1, cnt = w * (u.by1 - u.by0 + 1);
-            for (int k = lane; k < cnt; k += 64) rc_draw(cam, u, u.bx0 + k % w, u.by0 + k / w, W, uid, kb);
-        }
+        rs_walk(cam, face, F, n, xyz + (size_t)qc * n * 3, uv + (size_t)qc * n * 2, H, W, skipped + q,
+                KeySink{keys + (size_t)image * H * W, (uint32_t)((unsigned long long)q * F)});
     }
 }
 
@@ -235,9 +175,8 @@ void launch_color_clear(unsigned long long* keys, const float* depth, int accumu
 }
 
 void launch_color_visibility(const int* faces, int F, int n, const void* vertex_ws, int q0, int count,
-                             const int* d_image_index, int img0, const double* K, int H, int W, double pixel_center,
-                             double near, unsigned long long* keys, int* skipped, hipStream_t s) {
-    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+                             const int* d_image_index, int img0, const RsCam& cam, int H, int W, unsigned long long* keys,
+                             int* skipped, hipStream_t s) {
     const double* xyz = (const double*)vertex_ws;
     const int* uv = (const int*)(xyz + (size_t)count * n * 3);
     const int gy = count < 65535 ? count : 65535;
@@ -246,19 +185,16 @@ void launch_color_visibility(const int* faces, int F, int n, const void* vertex_
 }
 
 void launch_color_resolve(const unsigned long long* keys, int images, const double* model, const int* faces, int F,
-                          const unsigned char* colors, const double* poses, const double* K, int H, int W,
-                          double pixel_center, double near, const ColorLight& light, unsigned char* color, float* depth,
-                          hipStream_t s) {
-    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+                          const unsigned char* colors, const double* poses, const RsCam& cam, int H, int W,
+                          const ColorLight& light, unsigned char* color, float* depth, hipStream_t s) {
     const size_t count = (size_t)images * H * W;
     hipLaunchKernelGGL(color_resolve_kernel, dim3(rc_blocks(count)), dim3(RC_THREADS), 0, s, keys, count, model, faces, F,
                        colors, poses, cam, light, H, W, color, depth);
 }
 
 void launch_draw_boxes(const double* poses, int q0, int count, const double* corners, const unsigned char* corner_colors,
-                       const int* d_image_index, int img0, int images, const double* K, int H, int W, double pixel_center,
-                       double near, uint32_t* ids, unsigned char* color, hipStream_t s) {
-    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+                       const int* d_image_index, int img0, int images, const RsCam& cam, int H, int W, uint32_t* ids,
+                       unsigned char* color, hipStream_t s) {
     const size_t pixels = (size_t)images * H * W;
     BP_HIP(hipMemsetAsync(ids, 0, pixels * sizeof(uint32_t), s));
     if (count > 0)

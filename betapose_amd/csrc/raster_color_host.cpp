@@ -1,6 +1,7 @@
 // Host twin of the colour renderer (include/betapose_hip.h bp_render_color_host, bp_draw_boxes_host, bp_overlay_host):
-// plain loops over poses, triangles, edges and pixels around the arithmetic of raster_math.inc and
-// raster_color_math.inc, the text raster_color.hip compiles too.  Visibility is a minimum over 64-bit keys and the box
+// plain loops over poses, edges and pixels around the arithmetic of raster_math.inc and raster_color_math.inc, the text
+// raster_color.hip compiles too; the loop over a pose's triangles and their pixels is rs_walk_host (raster_walk.inc, the
+// depth rasteriser's too) with the key buffer as its sink.  Visibility is a minimum over 64-bit keys and the box
 // overlap rule a maximum over 32-bit ids, neither of which depends on the order of its operands, so these images and the
 // kernels' are equal byte for byte.
 #include <algorithm>
@@ -17,6 +18,7 @@ namespace bp {
 
 namespace {
 #include "raster_math.inc"
+#include "raster_walk.inc"
 #include "raster_color_math.inc"
 }  // namespace
 
@@ -26,7 +28,7 @@ int render_color_host(const double* poses, int P, const double* vertices, int n,
                       unsigned char* color, float* depth, int* skipped) {
     for (int i = 0; i < F * 3; ++i)
         if (faces[i] < 0 || faces[i] >= n) return -1;
-    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+    const RsCam cam = raster_cam(K, pixel_center, near);
     const ColorLight lt{ambient, light[0], light[1], light[2]};
     const size_t HW = (size_t)H * W;
     std::vector<double> X((size_t)n * 3);
@@ -39,33 +41,12 @@ int render_color_host(const double* poses, int P, const double* vertices, int n,
             if (depth[i] > 0.0f) keys[i] = rc_key(bits, RC_KEEP);
         }
     for (int q = 0; q < P; ++q) {
-        const double* pose = poses + (size_t)q * 12;
         unsigned long long* kb = keys.data() + (size_t)(image_index ? image_index[q] : q) * HW;
-        for (int i = 0; i < n; ++i) {
-            rs_transform(pose, vertices[i * 3 + 0], vertices[i * 3 + 1], vertices[i * 3 + 2], &X[(size_t)i * 3]);
-            rs_project(cam, &X[(size_t)i * 3], &S[(size_t)i * 2], &S[(size_t)i * 2 + 1]);
-        }
-        int skip = 0;
-        for (int f = 0; f < F; ++f) {
-            const int a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-            if (S[a * 2] == RS_INVALID || S[b * 2] == RS_INVALID || S[c * 2] == RS_INVALID) {
-                ++skip;
-                continue;
-            }
-            RsTri t;
-            if (!rs_setup(&X[(size_t)a * 3], &X[(size_t)b * 3], &X[(size_t)c * 3], S[a * 2], S[a * 2 + 1], S[b * 2],
-                          S[b * 2 + 1], S[c * 2], S[c * 2 + 1], H, W, &t))
-                continue;
-            const uint32_t id = (uint32_t)((unsigned long long)q * F + f);
-            for (int y = t.by0; y <= t.by1; ++y)
-                for (int x = t.bx0; x <= t.bx1; ++x) {
-                    if (!rs_covers(t, x, y)) continue;
-                    const unsigned long long key = rc_key(rs_depth_bits(cam, t, x, y), id);
-                    unsigned long long& dst = kb[(size_t)y * W + x];
-                    if (key < dst) dst = key;
-                }
-        }
-        skipped[q] = skip;
+        skipped[q] = rs_walk_host(cam, poses + (size_t)q * 12, vertices, n, faces, F, H, W, X.data(), S.data(),
+                                  [&](size_t at, uint32_t bits, int f) {    // smaller key wins
+                                      const unsigned long long key = rc_key(bits, (uint32_t)((unsigned long long)q * F + f));
+                                      if (key < kb[at]) kb[at] = key;
+                                  });
     }
     // resolve: shade the winner of every pixel from the model, the faces and the pose alone
     for (int i = 0; i < I; ++i)
@@ -98,7 +79,7 @@ int render_color_host(const double* poses, int P, const double* vertices, int n,
 void draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
                      const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near,
                      unsigned char* color) {
-    const RsCam cam{K[0], K[4], K[2], K[5], pixel_center, near};
+    const RsCam cam = raster_cam(K, pixel_center, near);
     const size_t HW = (size_t)H * W;
     std::vector<uint32_t> ids((size_t)I * HW, 0u);
     for (int q = 0; q < P; ++q) {

@@ -1,10 +1,10 @@
 // The depth rasteriser's arithmetic of O(1) size, ONE source for the host renderer (raster_host.cpp render_depth_host) and
 // the device kernels (raster.hip): the camera transform of a vertex, its projection and snapping, the set-up of a
 // triangle, the coverage test of a pixel and the depth at a covered pixel.  Host and device compile this text and do the
-// same f64 / integer operations in the same order, without FMA contraction, so their images agree bit for bit; only who
-// loops over poses, triangles and pixels differs per side.
-// Plain C++17, no HIP header.  Included inside `namespace bp { namespace {` after <cmath> and <cstdint>, in a unit that
-// has `#pragma clang fp contract(off)` in force.
+// same f64 / integer operations in the same order, without FMA contraction, so their images agree bit for bit; who loops
+// over a pose's triangles and their pixels is raster_walk.inc, one source too.
+// Plain C++17, no HIP header.  Included inside `namespace bp { namespace {` after <cmath>, <cstdint> and raster.h (the
+// camera, RsCam, is raster.h's: the launchers take it), in a unit that has `#pragma clang fp contract(off)` in force.
 //
 // Conventions (DESIGN.md §3.5): the centre of pixel (x, y) lies at image coordinates (x + c, y + c), c = pixel_center.
 // Projected vertices are snapped to 1/256 px in PIXEL-INDEX coordinates (u - c, v - c), so that the centre of pixel x is
@@ -24,12 +24,6 @@ constexpr double RS_MAX_UV = 16384.0;           // |u|, |v| beyond 2^14 px: the 
 constexpr int RS_INVALID = INT32_MIN;           // snapped x of a vertex that fails the near / range test
 constexpr uint32_t RS_EMPTY = 0x7f800000u;      // +inf: the z-buffer's cleared value
 constexpr int RS_COOP_AREA = 256;               // bounding boxes above this many pixels are rasterised by the whole wave
-
-struct RsCam {
-    double fx, fy, cx, cy;
-    double c;       // pixel_center
-    double near;    // vertices with z < near make their triangles skipped
-};
 
 // vertex of the posed mesh in the camera frame: X = R x + t, pose = [R|t] row-major 3x4
 BP_HD void rs_transform(const double* pose, double x, double y, double z, double* X) {
