@@ -168,6 +168,19 @@ PROTOTYPES = {
                                C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
     "bp_yolo_loss_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
                                     vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
+    "bp_yolo_map_max_dets": (C.c_int, []),
+    "bp_yolo_detections_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bp_detector_map_reduce_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "bp_yolo_detections": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                     C.c_int, vp, vp, vp, vp]),
+    "bp_yolo_detections_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_float, C.c_int, vp, vp]),
+    "bp_detector_map_match": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_float, C.c_int, C.c_int,
+                                        C.c_int, vp, vp, vp, vp, vp, vp]),
+    "bp_detector_map_match_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_float, C.c_int,
+                                             C.c_int, C.c_int, vp, vp, vp, vp]),
+    "bp_detector_map_reduce": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
+    "bp_detector_map_reduce_host": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
     "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
     "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
     "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),

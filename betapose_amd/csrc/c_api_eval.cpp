@@ -11,6 +11,7 @@
 #include "kpd_sample.h"
 #include "pose_tail.h"
 #include "raster.h"
+#include "yolo_map.h"
 #include "yolo_train.h"
 
 static void check_pixels(int H, int W) { BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24"); }
@@ -136,6 +137,42 @@ static void yolo_check_loss(int B, int n, int classes, int h, int w, int net_w, 
 }
 static void yolo_check_mask(const int* mask, int n, int total) {
     for (int i = 0; i < n; ++i) BP_CHECK(mask[i] >= 0 && mask[i] < total, "a mask entry lies outside [0, total)");
+}
+
+// ---- detector validation (yolo_map.hip / yolo_map_host.cpp)
+static void map_check_detections(int B, int rows, int attrs, const int* heads, int nheads, int net_w, int net_h, int classes,
+                                 float thresh, int max_dets, bool device) {
+    BP_CHECK(B > 0 && rows > 0 && net_w > 0 && net_h > 0 && classes > 0 && max_dets > 0,
+             "B, rows, net_w, net_h, classes and max_dets must be positive");
+    BP_CHECK(classes <= (1 << 12) && attrs == 5 + classes, "attrs must be 5 + classes, classes at most 4096");
+    BP_CHECK(thresh >= 0.0f, "thresh must not be negative");
+    BP_CHECK(!device || max_dets <= bp::yolo_map_max_dets(), "max_dets exceeds the device's cap");
+    BP_CHECK(nheads > 0 && nheads <= bp::yolo_map_max_heads(), "between 1 and 8 heads");
+    long long at = 0;
+    for (int h = 0; h < nheads; ++h) {
+        const int* q = heads + h * 4;
+        BP_CHECK(q[1] > 0 && q[2] > 0 && q[3] > 0 && q[2] <= (1 << 12) && q[3] <= (1 << 12) && q[1] <= (1 << 6),
+                 "a head needs positive anchors, gh and gw");
+        BP_CHECK(q[0] == at, "the heads must follow each other from row 0");
+        at += (long long)q[1] * q[2] * q[3];
+        BP_CHECK(at <= rows, "the heads hold more rows than pred");
+    }
+    BP_CHECK(at == rows, "the heads must cover every row of pred");
+    BP_CHECK((long long)B * rows * attrs < (1ll << 31), "pred must hold fewer than 2^31 values");
+    BP_CHECK((long long)B * max_dets * (6 + classes) < (1ll << 31), "the detection rows must hold fewer than 2^31 values");
+}
+static void map_check_match(int B, int max_dets, int classes, int M, int rec_stride, int truth_base, int image_base) {
+    BP_CHECK(B > 0 && max_dets > 0 && classes > 0 && classes <= (1 << 12) && M >= 0 && rec_stride > 0,
+             "B, max_dets, classes and rec_stride must be positive, M not negative");
+    BP_CHECK((long long)max_dets * classes * 6 < (1ll << 31) && (long long)B * max_dets * (6 + classes) < (1ll << 31) &&
+                 (long long)B * rec_stride * 6 < (1ll << 31), "the detection rows and records must hold fewer than 2^31 values");
+    BP_CHECK(truth_base >= 0 && image_base >= 0 && (long long)truth_base + M < (1ll << 31) && (long long)image_base + B < (1ll << 31),
+             "truth_base and image_base must stay below 2^31");
+}
+static void map_check_reduce(int D, int classes, int truths, int N) {
+    BP_CHECK(D >= 0 && D <= (1 << 26) && classes > 0 && classes <= (1 << 12) && truths >= 0 && N >= 0,
+             "D within [0, 2^26], classes positive, truths and N not negative");
+    BP_CHECK((long long)classes * (D > 0 ? D : 1) * 2 < (1ll << 40), "the PR arrays are too large");
 }
 
 // what the four refinement calls check alike, and the parameter block they hand on
@@ -545,6 +582,90 @@ int bp_yolo_loss(const float* d_x, int B, int channels, int n, int classes, int 
     yolo_check_mask(mask.data(), n, total);
     bp::yolo_loss(d_x, B, n, classes, h, w, net_w, net_h, d_anchors, total, d_mask, d_truth, max_boxes, ignore_thresh,
                   truth_thresh, d_act, d_delta, d_cost, d_stats, d_partial, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_map_max_dets(void) { return bp::yolo_map_max_dets(); }
+
+size_t bp_yolo_detections_scratch(int B, int max_dets, int classes) {
+    if (B <= 0 || max_dets <= 0 || classes <= 0) return 0;
+    return bp::yolo_detections_scratch(B, max_dets, classes);
+}
+
+size_t bp_detector_map_reduce_scratch(int D, int truths) {
+    if (D < 0 || D > (1 << 26) || truths < 0) return 0;
+    return bp::map_reduce_scratch(D, truths);
+}
+
+int bp_yolo_detections_host(const float* pred, int B, int rows, int attrs, const int* heads, int nheads, int net_w, int net_h,
+                            int classes, float thresh, float nms, int max_dets, float* dets, int* count) {
+    BP_TRY
+    BP_CHECK(pred && heads && dets && count, "null argument");
+    map_check_detections(B, rows, attrs, heads, nheads, net_w, net_h, classes, thresh, max_dets, false);
+    bp::yolo_detections_host(pred, B, rows, heads, nheads, net_w, net_h, classes, thresh, nms, max_dets, dets, count);
+    return 0;
+    BP_CATCH
+}
+
+int bp_yolo_detections(const float* d_pred, int B, int rows, int attrs, const int* heads, int nheads, int net_w, int net_h,
+                       int classes, float thresh, float nms, int max_dets, float* d_dets, int* d_count, void* d_scratch,
+                       void* stream) {
+    BP_TRY
+    BP_CHECK(d_pred && heads && d_dets && d_count && d_scratch, "null argument");
+    map_check_detections(B, rows, attrs, heads, nheads, net_w, net_h, classes, thresh, max_dets, true);
+    bp::yolo_detections(d_pred, B, rows, heads, nheads, net_w, net_h, classes, thresh, nms, max_dets, d_dets, d_count, d_scratch,
+                        (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_detector_map_match_host(const float* dets, const int* count, int B, int max_dets, int classes, const float* labels, int M,
+                               const int* first, float iou_thresh, float thresh_calc, int truth_base, int image_base,
+                               int rec_stride, float* rec, int* rec_count, int* truth_classes_count, double* img_stats) {
+    BP_TRY
+    BP_CHECK(dets && count && first && rec && rec_count && truth_classes_count && img_stats && (M == 0 || labels), "null argument");
+    map_check_match(B, max_dets, classes, M, rec_stride, truth_base, image_base);
+    BP_CHECK(first[0] >= 0 && first[B] <= M, "first must lie within [0, M]");
+    for (int b = 0; b < B; ++b) BP_CHECK(first[b] <= first[b + 1], "first must be non-decreasing");
+    bp::map_match_host(dets, count, B, max_dets, classes, labels, M, first, iou_thresh, thresh_calc, truth_base, image_base,
+                       rec_stride, rec, rec_count, truth_classes_count, img_stats);
+    return 0;
+    BP_CATCH
+}
+
+int bp_detector_map_match(const float* d_dets, const int* d_count, int B, int max_dets, int classes, const float* d_labels, int M,
+                          const int* d_first, float iou_thresh, float thresh_calc, int truth_base, int image_base, int rec_stride,
+                          float* d_rec, int* d_rec_count, int* d_truth_classes_count, double* d_img_stats, int* d_claim,
+                          void* stream) {
+    BP_TRY
+    BP_CHECK(d_dets && d_count && d_first && d_rec && d_rec_count && d_truth_classes_count && d_img_stats && d_claim &&
+                 (M == 0 || d_labels), "null argument");
+    map_check_match(B, max_dets, classes, M, rec_stride, truth_base, image_base);
+    bp::map_match(d_dets, d_count, B, max_dets, classes, d_labels, M, d_first, iou_thresh, thresh_calc, truth_base, image_base,
+                  rec_stride, d_rec, d_rec_count, d_truth_classes_count, d_img_stats, d_claim, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_detector_map_reduce_host(const float* rec, int D, const int* truth_classes_count, int classes, int truths,
+                                const double* img_stats, int N, double* ap, double* stats, double* pr) {
+    BP_TRY
+    BP_CHECK(truth_classes_count && ap && stats && (D == 0 || rec) && (N == 0 || img_stats), "null argument");
+    map_check_reduce(D, classes, truths, N);
+    bp::map_reduce_host(rec, D, truth_classes_count, classes, truths, img_stats, N, ap, stats, pr);
+    return 0;
+    BP_CATCH
+}
+
+int bp_detector_map_reduce(const float* d_rec, int D, const int* d_truth_classes_count, int classes, int truths,
+                           const double* d_img_stats, int N, double* d_ap, double* d_stats, double* d_pr, void* d_scratch,
+                           void* stream) {
+    BP_TRY
+    BP_CHECK(d_truth_classes_count && d_ap && d_stats && d_scratch && (D == 0 || d_rec) && (N == 0 || d_img_stats), "null argument");
+    map_check_reduce(D, classes, truths, N);
+    bp::map_reduce(d_rec, D, d_truth_classes_count, classes, truths, d_img_stats, N, d_ap, d_stats, d_pr, d_scratch,
+                   (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

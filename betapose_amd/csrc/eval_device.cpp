@@ -11,6 +11,7 @@
 #include "icp.h"
 #include "pose_tail.h"
 #include "raster.h"
+#include "yolo_map.h"
 #include "yolo_train.h"
 
 namespace bp {
@@ -260,6 +261,27 @@ void yolo_loss(const float* d_x, int B, int n, int classes, int h, int w, int ne
                float* d_delta, double* d_cost, double* d_stats, double* d_partial, hipStream_t s) {
     launch_yolo_loss(d_x, B, n, classes, h, w, net_w, net_h, d_anchors, total, d_mask, d_truth, max_boxes, ignore_thresh,
                      truth_thresh, d_act, d_delta, d_cost, d_stats, d_partial, s);
+    BP_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ detector validation
+void yolo_detections(const float* d_pred, int B, int rows, const int* heads, int nheads, int net_w, int net_h, int classes,
+                     float thresh, float nms, int max_dets, float* d_dets, int* d_count, void* d_scratch, hipStream_t s) {
+    launch_yolo_detections(d_pred, B, rows, heads, nheads, net_w, net_h, classes, thresh, nms, max_dets, d_dets, d_count, d_scratch, s);
+    BP_HIP(hipGetLastError());
+}
+
+void map_match(const float* d_dets, const int* d_count, int B, int max_dets, int classes, const float* d_labels, int M,
+               const int* d_first, float iou_thresh, float thresh_calc, int truth_base, int image_base, int rec_stride, float* d_rec,
+               int* d_rec_count, int* d_truth_classes_count, double* d_img_stats, int* d_claim, hipStream_t s) {
+    launch_map_match(d_dets, d_count, B, max_dets, classes, d_labels, M, d_first, iou_thresh, thresh_calc, truth_base, image_base,
+                     rec_stride, d_rec, d_rec_count, d_truth_classes_count, d_img_stats, d_claim, s);
+    BP_HIP(hipGetLastError());
+}
+
+void map_reduce(const float* d_rec, int D, const int* d_truth_classes_count, int classes, int truths, const double* d_img_stats,
+                int N, double* d_ap, double* d_stats, double* d_pr, void* d_scratch, hipStream_t s) {
+    launch_map_reduce(d_rec, D, d_truth_classes_count, classes, truths, d_img_stats, N, d_ap, d_stats, d_pr, d_scratch, s);
     BP_HIP(hipGetLastError());
 }
 

@@ -64,6 +64,9 @@
  *   bp_yolo_inputs, bp_yolo_truth, bp_yolo_loss (and their _host twins)
  *                          load_data_detection (no OpenCV), fill_truth_detection,  train_YOLO/src/data.c:189-225,303-392,811-859
  *                          forward_yolo_layer with train = 1                       train_YOLO/src/yolo_layer.c:166-282
+ *   bp_yolo_detections, bp_detector_map_match, bp_detector_map_reduce (and their _host twins)
+ *                          get_network_boxes + do_nms_sort,                        train_YOLO/src/yolo_layer.c:365-392, box.c:331-363
+ *                          validate_detector_map (`./darknet detector map`)       train_YOLO/src/detector.c:556-888
  *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
  *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
  *                          from its published description, never compared with PCL), a farthest-point alternative,
@@ -489,6 +492,58 @@ int bp_yolo_loss(const float* d_x, int B, int channels, int n, int classes, int 
 int bp_yolo_loss_host(const float* x, int B, int channels, int n, int classes, int h, int w, int net_w, int net_h,
                       const float* anchors, int total, const int* mask, const float* truth, int max_boxes, float ignore_thresh,
                       float truth_thresh, int focal_loss, float* act, float* delta, double* cost, double* stats, double* partial);
+/* Detector validation: Darknet's `detector map`.  Each device function is bit-identical to its _host
+ * twin, which needs no GPU.  Integers inside float32 rows travel as their bits.
+ *
+ * bp_yolo_detections: get_network_boxes(net, 1, 1, thresh, 0, 0, 0, &n, 0) followed by do_nms_sort(dets, n, classes, nms)
+ * for every image of d_pred [B][rows][attrs] f32, the decoded tensor bp_yolo_forward writes (attrs = 5 + classes, boxes in
+ * detector-input pixels, rows ordered head, anchor, gy, gx).  heads [nheads][4] int32 = (first row, anchors, gh, gw) is a
+ * HOST array in both calls; the heads follow each other from row 0 and cover every row.  A row with objectness > thresh
+ * (thresh >= 0) is a candidate: box / (net_w, net_h), prob[k] = objectness * cls[k], 0 unless > thresh; its candidate
+ * index counts head, cell, anchor as Darknet does.  For each class the candidates are sorted by prob[k] descending,
+ * stably over the order the previous class left (initially the candidate index), and every entry with prob[k] != 0
+ * zeroes prob[k] of every later entry whose box_iou with it is > nms.  nms <= 0 skips this.  d_dets [B][max_dets][6 +
+ * classes] f32 = (x, y, w, h, objectness, candidate index, prob[classes]) in the order the last class's sort left, zero
+ * past the count; d_count [B] int32 = the true number of candidates.  An image with d_count[b] > max_dets has a zero
+ * block: it is reported, never cut.  max_dets <= bp_yolo_map_max_dets() (4096) on the device, any on the host.
+ * d_scratch holds bp_yolo_detections_scratch(B, max_dets, classes) bytes. */
+int bp_yolo_map_max_dets(void);
+size_t bp_yolo_detections_scratch(int B, int max_dets, int classes);
+int bp_yolo_detections(const float* d_pred, int B, int rows, int attrs, const int* heads, int nheads, int net_w, int net_h,
+                       int classes, float thresh, float nms, int max_dets, float* d_dets, int* d_count, void* d_scratch,
+                       void* stream);
+int bp_yolo_detections_host(const float* pred, int B, int rows, int attrs, const int* heads, int nheads, int net_w, int net_h,
+                            int classes, float thresh, float nms, int max_dets, float* dets, int* count);
+/* bp_detector_map_match: detector.c:665-756 for a batch.  d_dets, d_count as above (an image whose count exceeds max_dets
+ * gives no record); d_labels [M][5] f32 = (id, x, y, w, h) with d_first [B + 1] int32 as bp_yolo_truth takes them.  For
+ * every detection and class with prob > 0, in that order, a record of 6 words: (p, image_base + b, class, truth, max_iou,
+ * position within the image); truth = truth_base + the index in d_labels of the same-class label with the greatest
+ * box_iou > iou_thresh (the first on ties), or -1.  d_rec [B][rec_stride][6] f32, zero past the count; d_rec_count [B] =
+ * the true number (records past rec_stride are dropped, also from the statistics: size it from d_count).
+ * d_truth_classes_count [classes] int32 is ADDED to, one per label whose id is a whole number in [0, classes) (any other
+ * label is passed over).  d_img_stats [B][3] f64 = (tp, fp, iou_sum) over the records with p > thresh_calc as the
+ * reference counts them: a true positive has a truth that no earlier record of the image claims, whatever that
+ * record's prob or class; all else is a false positive.  d_claim [M + 1] int32 is scratch. */
+int bp_detector_map_match(const float* d_dets, const int* d_count, int B, int max_dets, int classes, const float* d_labels, int M,
+                          const int* d_first, float iou_thresh, float thresh_calc, int truth_base, int image_base, int rec_stride,
+                          float* d_rec, int* d_rec_count, int* d_truth_classes_count, double* d_img_stats, int* d_claim,
+                          void* stream);
+int bp_detector_map_match_host(const float* dets, const int* count, int B, int max_dets, int classes, const float* labels, int M,
+                               const int* first, float iou_thresh, float thresh_calc, int truth_base, int image_base,
+                               int rec_stride, float* rec, int* rec_count, int* truth_classes_count, double* img_stats);
+/* bp_detector_map_reduce: detector.c:774-876 over the run's D records, d_rec [D][6] in any order.  Ranks: p descending,
+ * then image, position (and index) ascending.  A record is a true positive when it is the first in rank order to claim
+ * its truth (< truths = unique_truth_count), a later claimant counts as neither, a record without a truth is a false
+ * positive of its class.  d_ap [classes] f64 = the 11-point AP (recall >= point * 0.1 in double); d_stats [8] f64 = mAP,
+ * then precision, recall and F1 in float32 as the reference forms them (NaN where it divides 0 by 0), average IoU, TP, FP
+ * and FN at thresh_calc from d_img_stats [N][3] added in index order; d_pr (or NULL) [classes][D][2] f64 = (precision,
+ * recall) of every rank.  d_scratch holds bp_detector_map_reduce_scratch(D, truths) bytes. */
+size_t bp_detector_map_reduce_scratch(int D, int truths);
+int bp_detector_map_reduce(const float* d_rec, int D, const int* d_truth_classes_count, int classes, int truths,
+                           const double* d_img_stats, int N, double* d_ap, double* d_stats, double* d_pr, void* d_scratch,
+                           void* stream);
+int bp_detector_map_reduce_host(const float* rec, int D, const int* truth_classes_count, int classes, int truths,
+                                const double* img_stats, int N, double* ap, double* stats, double* pr);
 /* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
  * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
  * its _host twin, which needs no GPU.
