@@ -181,6 +181,16 @@ PROTOTYPES = {
                                              C.c_int, C.c_int, vp, vp, vp, vp]),
     "bp_detector_map_reduce": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
     "bp_detector_map_reduce_host": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "bp_train_conv_scratch": (C.c_size_t, [C.c_int] * 7),
+    "bp_train_update_chunk": (C.c_int, []),
+    "bp_train_conv": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp, vp]),
+    "bp_train_conv_host": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp]),
+    "bp_train_bn_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [C.c_int] * 3 + [vp]),
+    "bp_train_bn_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [C.c_int] * 3),
+    "bp_train_bn_backward": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp] * 3 + [C.c_int] * 2 + [vp]),
+    "bp_train_bn_backward_host": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp] * 3 + [C.c_int] * 2),
+    "bp_train_update": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
+    "bp_train_update_host": (C.c_int, [vp, C.c_int, C.c_float, C.c_float, C.c_float]),
     "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
     "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
     "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),

@@ -67,6 +67,9 @@
  *   bp_yolo_detections, bp_detector_map_match, bp_detector_map_reduce (and their _host twins)
  *                          get_network_boxes + do_nms_sort,                        train_YOLO/src/yolo_layer.c:365-392, box.c:331-363
  *                          validate_detector_map (`./darknet detector map`)       train_YOLO/src/detector.c:556-888
+ *   bp_train_conv, bp_train_bn_forward, bp_train_bn_backward, bp_train_update (and their _host twins)
+ *                          train_network_datum's CPU path: forward / backward /     train_YOLO/src/network.c:193-292,
+ *                          update of convolutional layers with batch norm          convolutional_layer.c:674-925, batchnorm_layer.c:65-163
  *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
  *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
  *                          from its published description, never compared with PCL), a farthest-point alternative,
@@ -544,6 +547,47 @@ int bp_detector_map_reduce(const float* d_rec, int D, const int* d_truth_classes
                            void* stream);
 int bp_detector_map_reduce_host(const float* rec, int D, const int* truth_classes_count, int classes, int truths,
                                 const double* img_stats, int N, double* ap, double* stats, double* pr);
+/* One Darknet training iteration: train_network_datum's CPU path for convolutional layers, in four
+ * calls that betapose_amd/darknet_train.py strings together.  Tensors are f32 [N][C][H][W], filters [K][C][size][size];
+ * size is 1 or 3, stride 1 or 2, padding size / 2.  Each device function is meant to be bit-identical to its _host twin,
+ * which needs no GPU.  No floating-point atomics.
+ *
+ * bp_train_conv: one implicit GEMM on the fp32 matrix pipe in one of three roles.  role 0: y [N][K][OH][OW] = the raw
+ * convolution of x [N][C][H][W] with w (every element written); role 1: w, here the filter UPDATES, += delta (y) x
+ * im2col(x), summed over (n, oy, ox) ascending in slices of 2048 added in order, through d_scratch
+ * [bp_train_conv_scratch()] floats; role 2: x, here the INPUT's delta, += w^T delta (y).  An element is one fmaf chain
+ * over k = (ky, kx, channel) ascending.
+ * bp_train_bn_forward: x [N][C][S] the raw convolution.  bn and train: mean, var [C] (f64 sums in a fixed order, the
+ * variance over N * S - 1, so N * S = 1 is an error), rolling = .9 rolling + .1 batch, x_norm and out = leaky(x_norm *
+ * scale + bias); bn and not train: the rolling pair normalises; not bn: out = act(x + bias), the other pointers may be
+ * NULL.  leaky 0 is the linear activation.
+ * bp_train_bn_backward: delta [N][C][S] (of out) becomes the delta of the raw convolution: the activation's gradient
+ * keyed on out, bias_updates += sum, and with bn scale_updates += sum(delta x_norm), the scaling, mean_delta,
+ * variance_delta and normalize_delta as Darknet forms them.  stat [2][C] is scratch.
+ * bp_train_update: update_convolutional_layer for every tensor of a table of (parameter, update, count, kind) rows of
+ * four 64-bit words, on the side that runs it; kind 1 (filters): u += decay_term * p first; then p += rate_over_batch *
+ * u; u *= momentum, each a rounded f32 step.  blocks = the sum over the rows of ceil(count / bp_train_update_chunk()). */
+size_t bp_train_conv_scratch(int N, int C, int H, int W, int K, int size, int stride);
+int bp_train_update_chunk(void);
+int bp_train_conv(int role, float* d_x, float* d_w, float* d_y, int N, int C, int H, int W, int K, int size, int stride,
+                  float* d_scratch, void* stream);
+int bp_train_conv_host(int role, float* x, float* w, float* y, int N, int C, int H, int W, int K, int size, int stride,
+                       float* scratch);
+int bp_train_bn_forward(const float* d_x, int N, int C, int S, const float* d_scales, const float* d_biases,
+                        float* d_rolling_mean, float* d_rolling_var, float* d_mean, float* d_var, float* d_x_norm, float* d_out,
+                        int bn, int leaky, int train, void* stream);
+int bp_train_bn_forward_host(const float* x, int N, int C, int S, const float* scales, const float* biases, float* rolling_mean,
+                             float* rolling_var, float* mean, float* var, float* x_norm, float* out, int bn, int leaky,
+                             int train);
+int bp_train_bn_backward(const float* d_out, float* d_delta, const float* d_x, const float* d_x_norm, const float* d_mean,
+                         const float* d_var, const float* d_scales, int N, int C, int S, float* d_bias_updates,
+                         float* d_scale_updates, float* d_stat, int bn, int leaky, void* stream);
+int bp_train_bn_backward_host(const float* out, float* delta, const float* x, const float* x_norm, const float* mean,
+                              const float* var, const float* scales, int N, int C, int S, float* bias_updates,
+                              float* scale_updates, float* stat, int bn, int leaky);
+int bp_train_update(const void* d_table, int tensors, int blocks, float rate_over_batch, float decay_term, float momentum,
+                    void* stream);
+int bp_train_update_host(const void* table, int tensors, float rate_over_batch, float decay_term, float momentum);
 /* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
  * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
  * its _host twin, which needs no GPU.
