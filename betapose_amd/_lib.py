@@ -191,6 +191,32 @@ PROTOTYPES = {
     "bp_train_bn_backward_host": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp] * 3 + [C.c_int] * 2),
     "bp_train_update": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
     "bp_train_update_host": (C.c_int, [vp, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "bp_kpd_train_conv_scratch": (C.c_size_t, [C.c_int] * 7),
+    "bp_kpd_train_update_chunk": (C.c_int, []),
+    "bp_kpd_train_conv": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp, vp]),
+    "bp_kpd_train_conv_host": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp]),
+    "bp_kpd_train_bn_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] * 3 + [vp]),
+    "bp_kpd_train_bn_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] * 3),
+    "bp_kpd_train_bn_backward": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp] * 2 + [C.c_int] * 2 + [vp]),
+    "bp_kpd_train_bn_backward_host": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp] * 2 + [C.c_int] * 2),
+    "bp_kpd_train_tail_forward": (C.c_int, [vp] * 4 + [C.c_int] * 3 + [vp]),
+    "bp_kpd_train_tail_forward_host": (C.c_int, [vp] * 4 + [C.c_int] * 3),
+    "bp_kpd_train_tail_backward": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp]),
+    "bp_kpd_train_tail_backward_host": (C.c_int, [vp] * 7 + [C.c_int] * 3),
+    "bp_kpd_train_pool_forward": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "bp_kpd_train_pool_forward_host": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "bp_kpd_train_pool_backward": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "bp_kpd_train_pool_backward_host": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+    "bp_kpd_train_sigmoid_forward": (C.c_int, [vp, vp, C.c_longlong, vp]),
+    "bp_kpd_train_sigmoid_forward_host": (C.c_int, [vp, vp, C.c_longlong]),
+    "bp_kpd_train_sigmoid_backward": (C.c_int, [vp, vp, C.c_longlong, vp]),
+    "bp_kpd_train_sigmoid_backward_host": (C.c_int, [vp, vp, C.c_longlong]),
+    "bp_kpd_train_maxpool_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "bp_kpd_train_maxpool_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_kpd_train_maxpool_backward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_kpd_train_maxpool_backward_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bp_kpd_train_rmsprop": (C.c_int, [vp, C.c_int, C.c_int] + [C.c_double] * 5 + [vp]),
+    "bp_kpd_train_rmsprop_host": (C.c_int, [vp, C.c_int] + [C.c_double] * 5),
     "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
     "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
     "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),

@@ -9,16 +9,7 @@
 
 static void train_check_conv(int role, const void* x, const void* w, const void* y, int N, int C, int H, int W, int K, int size,
                              int stride, const void* scratch) {
-    BP_CHECK(role >= 0 && role <= 2, "role must be 0 (forward), 1 (filter gradient) or 2 (input gradient)");
-    BP_CHECK(x && w && y && (role != 1 || scratch), "null argument");
-    BP_CHECK(N > 0 && C > 0 && H > 0 && W > 0 && K > 0, "N, C, H, W and K must be positive");
-    BP_CHECK(size == 1 || size == 3, "size must be 1 or 3");
-    BP_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
-    const long long OH = (H + 2 * (size / 2) - size) / stride + 1, OW = (W + 2 * (size / 2) - size) / stride + 1;
-    const long long lim = 1ll << 31;
-    BP_CHECK((long long)N * C * H * W < lim && (long long)N * K * OH * OW < lim && (long long)K * C * size * size < lim,
-             "a tensor of 2^31 elements or more");
-    BP_CHECK((long long)(K > C ? K : C) <= 64ll * 65535 && (long long)N * OH * OW <= 2048ll * 65535, "shape too large for one launch");
+    bp_check_train_conv(role, x, w, y, N, C, H, W, K, size, stride, scratch, false);
 }
 
 static void train_check_bn(int N, int C, int S, int bn, int train) {
@@ -41,7 +32,7 @@ static long long train_check_table(const bp::TrainTensor* t, int tensors) {
 extern "C" {
 
 size_t bp_train_conv_scratch(int N, int C, int H, int W, int K, int size, int stride) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || (size != 1 && size != 3) || (stride != 1 && stride != 2)) return 0;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || !bp_train_conv_size_ok(size, false) || (stride != 1 && stride != 2)) return 0;
     return bp::train_conv_scratch(N, C, H, W, K, size, stride);
 }
 

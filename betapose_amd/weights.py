@@ -118,8 +118,11 @@ def split_darknet_stream(blocks, flat: np.ndarray) -> List[dict]:
 FASTPOSE_STAGES = ((64, 3, 1), (128, 4, 2), (256, 23, 2), (512, 3, 2))  # planes, blocks, stride
 
 
-def fastpose_modules(n_classes: int = 50) -> List[dict]:
-    """Ordered module list (state-dict order) of FastPose.
+def fastpose_modules(n_classes: int = 50, stages=FASTPOSE_STAGES, stem: int = 64) -> List[dict]:
+    """Ordered module list (state-dict order) of FastPose.  ``stem`` (the 7 x 7 convolution's filters) and ``stages``
+    (``(planes, blocks, stride)`` each) default to the reference's net; with ``last = 4 * planes[-1]`` the tail is pixel
+    shuffle, DUC(``last / 4`` -> ``last / 2``), DUC(``last / 8`` -> ``last / 4``) and ``conv_out`` from ``last / 16``
+    channels, so ``last`` must be a multiple of 16.
 
     Entries: ``{"kind": "conv", "name", "cin", "cout", "k", "stride", "pad",
     "bn": bn_name|None, "bias": bool}`` or ``{"kind": "linear", "name", "cin",
@@ -131,13 +134,16 @@ def fastpose_modules(n_classes: int = 50) -> List[dict]:
         mods.append({"kind": "conv", "name": name, "cin": cin, "cout": cout, "k": k,
                      "stride": stride, "pad": pad, "bn": bn, "bias": bias})
 
-    conv("preact.conv1", 3, 64, 7, 2, 3, bn="preact.bn1")
-    inplanes = 64
-    for li, (planes, nblocks, stride) in enumerate(FASTPOSE_STAGES, start=1):
+    last = 4 * int(stages[-1][0])
+    if last % 16:
+        raise ValueError("4 * planes of the last stage is %d: the two DUCs and conv_out need a multiple of 16" % last)
+    conv("preact.conv1", 3, stem, 7, 2, 3, bn="preact.bn1")
+    inplanes = stem
+    for li, (planes, nblocks, stride) in enumerate(stages, start=1):
         for bi in range(nblocks):
             p = "preact.layer%d.%d" % (li, bi)
             s = stride if bi == 0 else 1
-            first = bi == 0  # make_layer: first block always has a downsample here
+            first = bi == 0 and (s != 1 or inplanes != planes * 4)  # make_layer: a downsample (and SE) where the shape changes
             conv(p + ".conv1", inplanes, planes, 1, 1, 0, bn=p + ".bn1")
             conv(p + ".conv2", planes, planes, 3, s, 1, bn=p + ".bn2")
             conv(p + ".conv3", planes, planes * 4, 1, 1, 0, bn=p + ".bn3")
@@ -146,9 +152,9 @@ def fastpose_modules(n_classes: int = 50) -> List[dict]:
                 mods.append({"kind": "linear", "name": p + ".se.fc.2", "cin": planes * 4, "cout": planes * 4})
                 conv(p + ".downsample.0", inplanes, planes * 4, 1, s, 0, bn=p + ".downsample.1")
             inplanes = planes * 4
-    conv("duc1.conv", 512, 1024, 3, 1, 1, bn="duc1.bn")
-    conv("duc2.conv", 256, 512, 3, 1, 1, bn="duc2.bn")
-    conv("conv_out", 128, n_classes, 3, 1, 1, bn=None, bias=True)
+    conv("duc1.conv", last // 4, last // 2, 3, 1, 1, bn="duc1.bn")
+    conv("duc2.conv", last // 8, last // 4, 3, 1, 1, bn="duc2.bn")
+    conv("conv_out", last // 16, n_classes, 3, 1, 1, bn=None, bias=True)
     return mods
 
 

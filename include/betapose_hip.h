@@ -70,6 +70,10 @@
  *   bp_train_conv, bp_train_bn_forward, bp_train_bn_backward, bp_train_update (and their _host twins)
  *                          train_network_datum's CPU path: forward / backward /     train_YOLO/src/network.c:193-292,
  *                          update of convolutional layers with batch norm          convolutional_layer.c:674-925, batchnorm_layer.c:65-163
+ *   bp_kpd_train_conv, bp_kpd_train_bn_forward / _backward, bp_kpd_train_tail_forward / _backward,
+ *   bp_kpd_train_pool_*, bp_kpd_train_sigmoid_*, bp_kpd_train_maxpool_*, bp_kpd_train_rmsprop (and their _host twins)
+ *                          train() / valid() for FastPose_SE under RMSprop            train_KPD/src/train.py:19-109,
+ *                          (PyTorch's batch norm, bottleneck tail, SE gate)           models/layers/SE_Resnet.py, SE_module.py, DUC.py
  *   bp_sift_octave, bp_farthest_points, bp_thin_points (and their _host twins), bp_voxel_grid_host
  *                          pcl::SIFTKeypoint as extract_sift sets it up (restated     1_keypoint_designator/main.cpp:41-73
  *                          from its published description, never compared with PCL), a farthest-point alternative,
@@ -588,6 +592,67 @@ int bp_train_bn_backward_host(const float* out, float* delta, const float* x, co
 int bp_train_update(const void* d_table, int tensors, int blocks, float rate_over_batch, float decay_term, float momentum,
                     void* stream);
 int bp_train_update_host(const void* table, int tensors, float rate_over_batch, float decay_term, float momentum);
+/* One training iteration of the key-point detector (train_KPD/src/train.py train() / valid() for FastPose_SE), DESIGN.md
+ * 3.14.  float32 [N][C][S] activations and gradients (the loss's gradient, torch's sign).  Each device function is meant
+ * to be bit-identical to its _host twin, which needs no GPU.  No floating-point atomics.  On the device a tensor whose S
+ * is a multiple of 4 must be 16-byte aligned.
+ *
+ * bp_kpd_train_conv: bp_train_conv's core, unchanged, admitting size 7 too (padding size / 2: the 7 x 7 / 2 stem); a
+ * Linear is size 1 on a 1 x 1 map with N the batch.  Gradients are added to their buffers.
+ * bp_kpd_train_bn_forward: torch's BatchNorm2d.  bn and train: mean [C] and invstd [C] = 1 / sqrt(var + 1e-5) from f64
+ * sums in a fixed order (biased variance; N * S = 1 is an error), running = .9 running + .1 batch (the variance
+ * unbiased), out = relu?(((x - mean) * invstd) * w + b); bn and not train: the running pair normalises; not bn: out =
+ * relu?(x + b), the other pointers may be NULL.
+ * bp_kpd_train_bn_backward: d (of out) becomes the gradient of x in place: m = relu ? d * (out > 0) : d, grad_b += sum(m),
+ * grad_w += sum(m * (x - mean)) * invstd, d = (m - sum / n - (x - mean) * dotp * invstd^2 / n) * invstd * w; not bn: d = m.
+ * bp_kpd_train_tail_forward: out = relu(y * s[n][c] + res), s NULL in a block without SE.  _backward: m = dout * (out > 0),
+ * dres += m, dy = m * s, ds [N][C] = sum_S m * y.
+ * bp_kpd_train_pool_forward: pool [rows] = the f64 sum of each row of S values, times 1 / S.  _backward: dy += dpool / S.
+ * bp_kpd_train_sigmoid_forward: s = 1 / (1 + exp(-x)) with the library's own exp.  _backward: g = g * (1 - s) * s in place.
+ * bp_kpd_train_maxpool_forward: 3 x 3, stride 2, padding 1 (-inf) over [planes][H][W]; arg [planes][OH][OW] int32 holds
+ * iy * W + ix of the window's first maximum in scan order.  _backward: dx (written) gathers the outputs that chose it.
+ * bp_kpd_train_rmsprop: torch.optim.RMSprop (not centred) for every tensor of a table of (parameter, gradient, square_avg,
+ * momentum buffer, count) rows of five 64-bit words, on the side that runs it, in torch's single-tensor order with the
+ * roundings of torch's CPU kernels (g + wd p, v + ((1 - alpha) g) g and p - lr b are fused multiply-adds).  blocks = the sum over the rows of ceil(count / bp_kpd_train_update_chunk()). */
+size_t bp_kpd_train_conv_scratch(int N, int C, int H, int W, int K, int size, int stride);
+int bp_kpd_train_update_chunk(void);
+int bp_kpd_train_conv(int role, float* d_x, float* d_w, float* d_y, int N, int C, int H, int W, int K, int size, int stride,
+                      float* d_scratch, void* stream);
+int bp_kpd_train_conv_host(int role, float* x, float* w, float* y, int N, int C, int H, int W, int K, int size, int stride,
+                           float* scratch);
+int bp_kpd_train_bn_forward(const float* d_x, int N, int C, int S, const float* d_w, const float* d_b, float* d_running_mean,
+                            float* d_running_var, float* d_mean, float* d_invstd, float* d_out, int bn, int relu, int train,
+                            void* stream);
+int bp_kpd_train_bn_forward_host(const float* x, int N, int C, int S, const float* w, const float* b, float* running_mean,
+                                 float* running_var, float* mean, float* invstd, float* out, int bn, int relu, int train);
+int bp_kpd_train_bn_backward(const float* d_out, float* d_d, const float* d_x, const float* d_mean, const float* d_invstd,
+                             const float* d_w, int N, int C, int S, float* d_grad_w, float* d_grad_b, int bn, int relu,
+                             void* stream);
+int bp_kpd_train_bn_backward_host(const float* out, float* d, const float* x, const float* mean, const float* invstd, const float* w,
+                                  int N, int C, int S, float* grad_w, float* grad_b, int bn, int relu);
+int bp_kpd_train_tail_forward(const float* d_y, const float* d_s, const float* d_res, float* d_out, int N, int C, int S,
+                              void* stream);
+int bp_kpd_train_tail_forward_host(const float* y, const float* s, const float* res, float* out, int N, int C, int S);
+int bp_kpd_train_tail_backward(const float* d_out, const float* d_dout, const float* d_y, const float* d_s, float* d_dres,
+                               float* d_dy, float* d_ds, int N, int C, int S, void* stream);
+int bp_kpd_train_tail_backward_host(const float* out, const float* dout, const float* y, const float* s, float* dres, float* dy,
+                                    float* ds, int N, int C, int S);
+int bp_kpd_train_pool_forward(const float* d_y, int rows, int S, float* d_pool, void* stream);
+int bp_kpd_train_pool_forward_host(const float* y, int rows, int S, float* pool);
+int bp_kpd_train_pool_backward(const float* d_dpool, float* d_dy, int rows, int S, void* stream);
+int bp_kpd_train_pool_backward_host(const float* dpool, float* dy, int rows, int S);
+int bp_kpd_train_sigmoid_forward(const float* d_x, float* d_s, long long n, void* stream);
+int bp_kpd_train_sigmoid_forward_host(const float* x, float* s, long long n);
+int bp_kpd_train_sigmoid_backward(const float* d_s, float* d_g, long long n, void* stream);
+int bp_kpd_train_sigmoid_backward_host(const float* s, float* g, long long n);
+int bp_kpd_train_maxpool_forward(const float* d_x, int planes, int H, int W, float* d_out, int* d_arg, void* stream);
+int bp_kpd_train_maxpool_forward_host(const float* x, int planes, int H, int W, float* out, int* arg);
+int bp_kpd_train_maxpool_backward(const float* d_dout, const int* d_arg, int planes, int H, int W, float* d_dx, void* stream);
+int bp_kpd_train_maxpool_backward_host(const float* dout, const int* arg, int planes, int H, int W, float* dx);
+int bp_kpd_train_rmsprop(const void* d_table, int tensors, int blocks, double lr, double alpha, double eps, double weight_decay,
+                         double momentum, void* stream);
+int bp_kpd_train_rmsprop_host(const void* table, int tensors, double lr, double alpha, double eps, double weight_decay,
+                              double momentum);
 /* Key-point designation (stage 1 of the reference).  All geometry is float64, points are [n][3], every sum runs in
  * ascending index order and every choice among equals goes to the lower index; each device function is bit-identical to
  * its _host twin, which needs no GPU.
