@@ -17,7 +17,10 @@ static std::vector<float> fill(size_t n, unsigned seed) {
 
 int main() {
     double sum = 0.0;
-    const int shapes[4][7] = {{3, 3, 9, 11, 18, 3, 1}, {1, 5, 13, 13, 7, 3, 2}, {2, 9, 7, 6, 4, 1, 2}, {3, 3, 27, 27, 5, 3, 1}};
+    // the last two: c512_k1024 and k2049 of tests/darknet_train_common.py (16 block rows with chains of 4608 and 9216
+    // terms; a second reduction slice of one value)
+    const int shapes[6][7] = {{3, 3, 9, 11, 18, 3, 1}, {1, 5, 13, 13, 7, 3, 2}, {2, 9, 7, 6, 4, 1, 2}, {3, 3, 27, 27, 5, 3, 1},
+                              {2, 512, 2, 2, 1024, 3, 1}, {3, 4, 1, 683, 5, 1, 1}};
     for (const auto& s : shapes) {
         const int N = s[0], C = s[1], H = s[2], W = s[3], K = s[4], size = s[5], stride = s[6], pad = size / 2;
         const int OH = (H + 2 * pad - size) / stride + 1, OW = (W + 2 * pad - size) / stride + 1;
