@@ -273,6 +273,14 @@ PROTOTYPES = {
     "bp_loader_next": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(vp)]),
     "bp_loader_release": (C.c_int, [vp, C.c_longlong]),
     "bp_upload": (C.c_int, [vp, vp, C.c_size_t, vp]),
+    "bp_synth_background": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, vp, vp]),
+    "bp_synth_background_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, vp]),
+    "bp_synth_windows": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_synth_windows_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bp_synth_compose": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint, C.c_uint, vp, vp]),
+    "bp_synth_compose_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint, C.c_uint, vp]),
+    "bp_synth_sensor_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp, vp]),
+    "bp_synth_sensor_depth_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp]),
 }
 
 RESULT_FLOATS = 316

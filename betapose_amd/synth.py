@@ -6,6 +6,9 @@ is stable across numpy versions, so the same arrays are regenerated on the GPU
 box, in the oracle tools and in the tests.  The distributions are chosen so
 activations stay O(1) through 75 / 104 conv layers (residual branches are
 damped) and the detector's objectness / the heat-map maxima are not saturated.
+
+The second half of the module is the training-scene synthesiser: rendered, occluded and composited
+frames with a sensor's depth and their ground truth, from a mesh alone (``synthesize_scenes``, ``write_scene_tree``).
 """
 from __future__ import annotations
 
@@ -191,3 +194,536 @@ def write_sixd_tree(base: str, seq: int, gt_by_frame: Dict[int, list], models_mm
         yaml.safe_dump(gt, f)
     with open(os.path.join(sdir, "info.yml"), "w") as f:
         yaml.safe_dump(info, f)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Training-scene synthesiser: frames, sensor depth and ground truth of a mesh, from nothing but the mesh.
+# The four per-pixel stages run in libbetapose_hip (csrc/synth.hip, host twins csrc/synth_host.cpp, byte-identical); the
+# geometry -- poses and occluder placement -- is numpy float64 here, and the glue draws each scene's numbers from
+# generators seeded by (seed, purpose, scene number), so a scene does not depend on how the scenes are chunked.
+# Frames are [I, H, W, 3] uint8 in BGR, as cv2.imread and FrameLoader give them; the files of a tree are RGB PNGs.
+COMPOSE_PARAMS = 9        # csrc/synth.h SY_PARAMS: feather, r, gain[3] (Q8), offset[3], sigma (Q8)
+SENSOR_PARAMS = 3         # SY_DEPTH_PARAMS: noise_k, edge_counts, hole_p
+WINDOW_INTS = 6           # SY_WINDOW: bank image, x0, y0, w, h, flip
+NOISE_VARIANCE = 65535    # of the noise value: 12 uniform bytes, 12 (256^2 - 1) / 12
+
+
+def _images_size(size):
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError("size = (H, W) must be positive")
+    return H, W
+
+
+def _table(params, I, cols, name):
+    t = np.ascontiguousarray(params, dtype=np.int32)
+    if t.shape != (I, cols):
+        raise ValueError("%s must be [%d, %d] int32" % (name, I, cols))
+    return t
+
+
+def _torch_device(device):
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    return torch, torch.device(device)
+
+
+def _upload(torch, dev, a):
+    """A host array on the device (torch warns when it wraps a read-only array: such a one is copied first)."""
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+
+
+def compose_params(images, feather=1, blur=0, gain=(256, 256, 256), offset=(0, 0, 0), sigma=0):
+    """The ``params`` table of ``compose`` with the same row for every image: [images, 9] int32.  The defaults are the
+    neutral camera (the paste alone) except for the feather; ``feather=0`` makes compose equal metrics.overlay."""
+    row = [int(feather), int(blur)] + [int(g) for g in gain] + [int(o) for o in offset] + [int(sigma)]
+    return np.tile(np.array(row, np.int32), (int(images), 1))
+
+
+def sensor_params(images, noise_k=0, edge_counts=0, hole_p=0):
+    """The ``params`` table of ``sensor_depth`` with the same row for every image: [images, 3] int32."""
+    return np.tile(np.array([int(noise_k), int(edge_counts), int(hole_p)], np.int32), (int(images), 1))
+
+
+def procedural_background(images, size, seed, first_image=0, device=None):
+    """``images`` computed backgrounds [I, H, W, 3] uint8, scenes ``first_image`` .. of ``seed``: four octaves of lattice
+    value noise (cells of 64, 32, 16 and 8 pixels, bilinear in fixed point) over a base colour, the weights, the colour
+    and the contrast drawn per scene.  ``device=None``: the host twin; a torch device: the kernel."""
+    from . import _lib
+    H, W = _images_size(size)
+    I = int(images)
+    if I == 0:
+        return np.zeros((0, H, W, 3), np.uint8)
+    if device is None:
+        out = np.empty((I, H, W, 3), np.uint8)
+        _lib.check(_lib.lib().bp_synth_background_host(I, H, W, int(seed), int(first_image), _lib.ptr(out)))
+        return out
+    torch, dev = _torch_device(device)
+    with torch.cuda.device(dev):
+        d_out = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().bp_synth_background(I, H, W, int(seed), int(first_image), _lib.ptr(d_out),
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy()
+
+
+def background_windows(bank, windows, size, device=None):
+    """Backgrounds [I, H, W, 3] uint8 cut from a bank of photographs [Nb, Hb, Wb, 3] uint8: row i of ``windows``
+    [I, 6] int32 = (bank image, x0, y0, w, h, flip) names a window inside its photograph, which is resampled to
+    ``size`` bilinearly in fixed point with the pixel centres aligned, mirrored left to right when ``flip``."""
+    from . import _lib
+    H, W = _images_size(size)
+    bank = np.ascontiguousarray(bank, dtype=np.uint8)
+    if bank.ndim != 4 or bank.shape[3] != 3:
+        raise ValueError("bank must be [Nb, Hb, Wb, 3]")
+    windows = np.ascontiguousarray(windows, dtype=np.int32)
+    if windows.ndim != 2 or windows.shape[1] != WINDOW_INTS:
+        raise ValueError("windows must be [I, 6]: bank image, x0, y0, w, h, flip")
+    I, (Nb, Hb, Wb) = len(windows), bank.shape[:3]
+    if I == 0:
+        return np.zeros((0, H, W, 3), np.uint8)
+    if device is None:
+        out = np.empty((I, H, W, 3), np.uint8)
+        _lib.check(_lib.lib().bp_synth_windows_host(_lib.ptr(bank), Nb, Hb, Wb, _lib.ptr(windows), I, H, W, _lib.ptr(out)))
+        return out
+    torch, dev = _torch_device(device)
+    with torch.cuda.device(dev):
+        d_bank = _upload(torch, dev, bank)
+        d_out = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().bp_synth_windows(_lib.ptr(d_bank), Nb, Hb, Wb, _lib.ptr(windows), I, H, W, _lib.ptr(d_out),
+                                               torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy()
+
+
+def compose(background, color, depth, params, seed, first_image=0, device=None):
+    """Training frames [I, H, W, 3] uint8: the render (``color``, ``depth`` of metrics.render_color) over ``background``
+    through a camera model.  Per pixel and channel, in this order: paste with an inside feather -- where the centre has a
+    fragment ``(a F + (9 - a) B + 4) // 9`` with ``a`` the pixels of the 3 x 3 neighbourhood (clamped to the image) with
+    depth > 0, else B; feather off: a = 9 --, the separable binomial blur of radius r (rows, then columns, edges
+    clamped, each pass rounded half up), ``((gain v + 128) >> 8) + offset``, the noise value (12 summed bytes of the
+    random source minus 1530) times sigma / 2^16 rounded half up, clamp.  ``params`` [I, 9] int32 = (feather, r, gain x3
+    in Q8, offset x3, sigma in Q8), see compose_params.  Image i is scene ``first_image + i`` of the random source."""
+    from . import _lib
+    background = np.ascontiguousarray(background, dtype=np.uint8)
+    color = np.ascontiguousarray(color, dtype=np.uint8)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if background.ndim != 4 or background.shape[3] != 3 or color.shape != background.shape or depth.shape != background.shape[:3]:
+        raise ValueError("background and color must be [I, H, W, 3], depth [I, H, W]")
+    I, H, W = depth.shape
+    params = _table(params, I, COMPOSE_PARAMS, "params")
+    if I == 0:
+        return background.copy()
+    if device is None:
+        out = np.empty_like(background)
+        _lib.check(_lib.lib().bp_synth_compose_host(_lib.ptr(background), _lib.ptr(color), _lib.ptr(depth), I, H, W,
+                                                    _lib.ptr(params), int(seed), int(first_image), _lib.ptr(out)))
+        return out
+    torch, dev = _torch_device(device)
+    with torch.cuda.device(dev):
+        d_bg, d_color, d_depth = (_upload(torch, dev, a) for a in (background, color, depth))
+        d_out = torch.empty_like(d_bg)
+        _lib.check(_lib.lib().bp_synth_compose(_lib.ptr(d_bg), _lib.ptr(d_color), _lib.ptr(d_depth), I, H, W, _lib.ptr(params),
+                                               int(seed), int(first_image), _lib.ptr(d_out),
+                                               torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy()
+
+
+def sensor_depth(depth, depth_scale, params, seed, first_image=0, device=None):
+    """A depth sensor's image [I, H, W] uint16 of the scene depth [I, H, W] float32 (metres): counts of ``depth_scale``
+    metres, rounded half up, 0 where there is nothing, at most 65 535; plus noise of sigma ``noise_k count^2 / 2^28``
+    counts; a pixel whose 3 x 3 neighbourhood (clamped, background included) spans more than ``edge_counts`` counts
+    becomes 0 with probability ``hole_p / 256``.  ``params`` [I, 3] int32 = (noise_k, edge_counts, hole_p)."""
+    from . import _lib
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if depth.ndim != 3:
+        raise ValueError("depth must be [I, H, W]")
+    I, H, W = depth.shape
+    params = _table(params, I, SENSOR_PARAMS, "params")
+    if I == 0:
+        return np.zeros((0, H, W), np.uint16)
+    if device is None:
+        out = np.empty((I, H, W), np.uint16)
+        _lib.check(_lib.lib().bp_synth_sensor_depth_host(_lib.ptr(depth), I, H, W, float(depth_scale), _lib.ptr(params),
+                                                         int(seed), int(first_image), _lib.ptr(out)))
+        return out
+    torch, dev = _torch_device(device)
+    with torch.cuda.device(dev):
+        d_depth = _upload(torch, dev, depth)
+        d_out = torch.empty((I, H, W), dtype=torch.int16, device=dev)      # (the bits; the kernel writes uint16)
+        _lib.check(_lib.lib().bp_synth_sensor_depth(_lib.ptr(d_depth), I, H, W, float(depth_scale), _lib.ptr(params), int(seed),
+                                                    int(first_image), _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
+        return d_out.cpu().numpy().view(np.uint16)
+
+
+# ---- geometry on the host
+_POSE_DRAWS, _OCCLUDER_DRAWS, _CAMERA_DRAWS, _WINDOW_DRAWS = 0, 1, 2, 3      # the second word of a generator's seed
+
+
+def _scene_rng(seed, purpose, scene, stream=0):
+    return np.random.Generator(np.random.PCG64([int(seed), int(purpose), int(scene), int(stream)]))
+
+
+def _unit(v):
+    return v / np.linalg.norm(v)
+
+
+def _look_at(direction):
+    """R0 with ``R0 @ direction = (0, 0, -1)``: the camera (x right, y down, z forward) sits along ``direction`` from the
+    object and looks at it, the object's z axis pointing up in the image; at the poles its x axis takes that part."""
+    z = -direction
+    up = np.array([0.0, 0.0, 1.0]) if abs(direction[2]) < 0.999 else np.array([1.0, 0.0, 0.0])
+    x = _unit(np.cross(z, up))
+    y = np.cross(z, x)
+    return np.stack([x, y, z])
+
+
+def _rotation_between_z_and(ray):
+    """The smallest rotation Q with ``Q @ (0, 0, 1) = ray`` (unit, z > 0)."""
+    v = np.cross([0.0, 0.0, 1.0], ray)
+    c = ray[2]
+    V = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return np.eye(3) + V + V @ V / (1.0 + c)
+
+
+def _orthonormal(R):
+    """The nearest rotation: products of rotations drift by a few ulp, the renderer does not care, the contract does."""
+    u, _, vt = np.linalg.svd(R)
+    return u @ vt
+
+
+def sample_poses(n, K, size, radius, seed, elevation=(10.0, 80.0), distance=None, inplane=(-30.0, 30.0), margin=None,
+                 first_scene=0):
+    """``n`` model-to-camera poses [n, 3, 4] float64 of an object of ``radius`` round its origin.  Per scene: the
+    direction from the object to the camera is uniform in area over the band ``elevation`` (degrees above the object's
+    xy plane; sin(elevation) uniform, azimuth uniform), the camera looks along it with the object's z axis up and is
+    rolled by an angle of ``inplane`` (degrees); the object's centre lies at ``distance`` (lo, hi; default 4 .. 8 radii)
+    from the camera, on the ray of a pixel drawn uniformly at least ``margin`` pixels inside the image (default: the
+    projected radius at the nearest distance, so the whole object is in view where the image allows).  Elevation and
+    distance stay exactly what was drawn: the roll and the shift turn the camera about its own centre.  Scene
+    ``first_scene + i`` has its own generator, seeded by (seed, scene)."""
+    H, W = _images_size(size)
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    lo, hi = (4.0 * radius, 8.0 * radius) if distance is None else (float(distance[0]), float(distance[1]))
+    if not radius > 0 or not lo > radius or hi < lo:
+        raise ValueError("distance = (lo, hi) needs radius < lo <= hi")
+    if margin is None:
+        margin = min(K[0, 0], K[1, 1]) * radius / lo
+    m = min(float(margin), (min(H, W) - 1) / 2.0)
+    if m < 0:
+        raise ValueError("margin must not be negative")
+    s_lo, s_hi = np.sin(np.radians(elevation[0])), np.sin(np.radians(elevation[1]))
+    poses = np.zeros((int(n), 3, 4))
+    for i in range(int(n)):
+        rng = _scene_rng(seed, _POSE_DRAWS, first_scene + i)
+        s = rng.uniform(s_lo, s_hi)
+        az = rng.uniform(0.0, 2.0 * np.pi)
+        roll = np.radians(rng.uniform(inplane[0], inplane[1]))
+        dist = rng.uniform(lo, hi)
+        u, v = rng.uniform(m, W - 1 - m), rng.uniform(m, H - 1 - m)
+        c = np.sqrt(max(0.0, 1.0 - s * s))
+        direction = np.array([c * np.cos(az), c * np.sin(az), s])
+        ray = _unit(np.array([(u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], 1.0]))
+        Rz = np.array([[np.cos(roll), -np.sin(roll), 0.0], [np.sin(roll), np.cos(roll), 0.0], [0.0, 0.0, 1.0]])
+        poses[i, :, :3] = _orthonormal(_rotation_between_z_and(ray) @ Rz @ _look_at(direction))
+        poses[i, :, 3] = dist * ray
+    return poses
+
+
+def place_occluders(target_poses, radii, K, size, seed, count, depth_fraction=(0.4, 0.8), lateral=1.0, first_scene=0, stream=0):
+    """Poses [n, count, 3, 4] of ``count`` occluders per scene in front of the targets at ``target_poses`` [n, 3, 4]:
+    a uniformly random rotation, the centre on the segment from the camera to the target's centre at a fraction of
+    ``depth_fraction`` of the target's distance, moved perpendicular to that segment by up to ``lateral`` times the
+    target's radius ``radii`` (uniform in area).  ``stream`` selects another set of draws for the same scenes (what
+    synthesize_scenes uses for a redraw).  ``K`` and ``size`` are accepted for symmetry with sample_poses: the placement
+    is along the target's ray and needs neither."""
+    tp = np.asarray(target_poses, dtype=np.float64).reshape(-1, *np.shape(target_poses)[-2:])[:, :3, :4]
+    radius = float(np.asarray(radii, dtype=np.float64).reshape(-1)[0])
+    out = np.zeros((len(tp), int(count), 3, 4))
+    for i in range(len(tp)):
+        rng = _scene_rng(seed, _OCCLUDER_DRAWS, first_scene + i, stream)
+        t = tp[i, :, 3]
+        ray = _unit(t)
+        e1 = _unit(np.cross(ray, [1.0, 0.0, 0.0] if abs(ray[0]) < 0.9 else [0.0, 1.0, 0.0]))
+        e2 = np.cross(ray, e1)
+        for j in range(int(count)):
+            q = _unit(rng.normal(size=4))
+            w, x, y, z = q
+            out[i, j, :, :3] = _orthonormal(np.array(
+                [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                 [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                 [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]))
+            f = rng.uniform(depth_fraction[0], depth_fraction[1])
+            rho, phi = lateral * radius * np.sqrt(rng.uniform(0.0, 1.0)), rng.uniform(0.0, 2.0 * np.pi)
+            out[i, j, :, 3] = f * t + rho * (np.cos(phi) * e1 + np.sin(phi) * e2)
+    return out
+
+
+def _runs(indices):
+    """Consecutive runs [a, b) of a sorted list of scene indices."""
+    runs = []
+    for i in indices:
+        if runs and runs[-1][1] == i:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return runs
+
+
+def _mesh3(mesh):
+    """(vertices f64 [n, 3], faces int32 [F, 3], colours uint8 [n, 3] in BGR); a mesh without colours is mid grey."""
+    v = np.ascontiguousarray(mesh[0], dtype=np.float64).reshape(-1, 3)
+    f = np.ascontiguousarray(mesh[1], dtype=np.int32).reshape(-1, 3)
+    c = np.full((len(v), 3), 128, np.uint8) if len(mesh) < 3 or mesh[2] is None else np.ascontiguousarray(mesh[2], np.uint8)
+    return v, f, c
+
+
+DEFAULT_CAMERA = dict(feather=1, blur=(0, 2), gain=(224, 288), offset=(-12, 12), sigma=(0, 768))
+DEFAULT_SENSOR = dict(noise_k=512, edge_counts=30, hole_p=128)
+
+
+def draw_camera(n, seed, camera=None, first_scene=0):
+    """compose's table [n, 9] with each scene's blur radius, gains, offsets and sigma drawn uniformly from the integer
+    ranges of ``camera`` (DEFAULT_CAMERA; a plain number fixes a value)."""
+    cam = dict(DEFAULT_CAMERA, **(camera or {}))
+    rng_of = lambda i: _scene_rng(seed, _CAMERA_DRAWS, first_scene + i)
+    pick = lambda rng, r: int(r) if np.isscalar(r) else int(rng.integers(int(r[0]), int(r[1]) + 1))
+    rows = []
+    for i in range(int(n)):
+        rng = rng_of(i)
+        rows.append([pick(rng, cam["feather"]), pick(rng, cam["blur"])] + [pick(rng, cam["gain"]) for _ in range(3)] +
+                    [pick(rng, cam["offset"]) for _ in range(3)] + [pick(rng, cam["sigma"])])
+    return np.array(rows, np.int32).reshape(int(n), COMPOSE_PARAMS)
+
+
+def draw_windows(n, bank_shape, size, seed, first_scene=0):
+    """background_windows' table [n, 6]: per scene a photograph of the bank, the largest window of the output's aspect
+    ratio scaled by a factor of 0.5 .. 1, placed uniformly, flipped with probability 1/2."""
+    Nb, Hb, Wb = (int(v) for v in bank_shape[:3])
+    H, W = _images_size(size)
+    rows = []
+    for i in range(int(n)):
+        rng = _scene_rng(seed, _WINDOW_DRAWS, first_scene + i)
+        k = min(Wb / W, Hb / H) * rng.uniform(0.5, 1.0)
+        w, h = max(1, min(Wb, int(W * k))), max(1, min(Hb, int(H * k)))
+        rows.append([int(rng.integers(Nb)), int(rng.integers(Wb - w + 1)), int(rng.integers(Hb - h + 1)), w, h, int(rng.integers(2))])
+    return np.array(rows, np.int32).reshape(int(n), WINDOW_INTS)
+
+
+def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=None, elevation=(10.0, 80.0), distance=None,
+                      inplane=(-30.0, 30.0), margin=None, depth_fraction=(0.4, 0.8), lateral=1.0, min_visib=0.3,
+                      max_redraws=4, backgrounds=None, camera=None, sensor=None, depth_scale=0.001, first_scene=0,
+                      ambient=0.5, light=(0.0, 0.0, 0.0), device=None):
+    """``n`` training scenes of the mesh ``target`` = (vertices, faces[, colours RGB uint8]) in metres, partly hidden
+    by one instance of each mesh of ``occluders``: a dict of arrays with one row per scene --
+
+      ``frames`` [n, H, W, 3] uint8 BGR, ``depth`` [n, H, W] uint16 (counts of ``depth_scale`` metres),
+      ``obj_ids`` [1 + occluders] (the target first; default 1, 2, ...), ``poses`` [n, objects, 3, 4] and ``t_mm``
+      [n, objects, 3] (the translation in millimetres: ``poses[..., 3]`` IS ``t_mm * 0.001``, what a SIXD reader
+      computes from the written file), ``present`` [n, objects] bool, ``box_full`` [n, objects, 4] (xmin, xmax, ymin,
+      ymax of each object rendered alone, -1 where it covers no pixel), the target's ``box_visible`` [n, 4] and
+      ``visib_fract`` [n] against the sensor depth (annotate.mask_boxes), ``redraws`` [n] and ``params`` (compose's table).
+
+    The target is rendered at sample_poses' poses, the occluders at place_occluders' ``into`` the same images, the
+    backgrounds are procedural (or windows of the bank ``backgrounds`` [Nb, Hb, Wb, 3] BGR), compose and sensor_depth
+    make the frames and the depth images.  A scene whose ``visib_fract`` is below ``min_visib`` has its occluders drawn
+    again from the next stream, at most ``max_redraws`` times; after that it keeps none (``present`` False).  Everything
+    is a function of (seed, scene number): ``first_scene`` shifts the scene numbers, so chunks concatenate to the whole.
+    ``device=None``: the host twins throughout; a torch device: the kernels, with the same bytes."""
+    from . import annotate as A, metrics
+    H, W = _images_size(size)
+    n = int(n)
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    tv, tf, tc = _mesh3(target)
+    occ = [_mesh3(m) for m in occluders]
+    ids = np.arange(1, 2 + len(occ)) if obj_ids is None else np.asarray(obj_ids, dtype=np.int64).reshape(-1)
+    if len(ids) != 1 + len(occ):
+        raise ValueError("obj_ids names the target and every occluder")
+    if radius is None:
+        radius = float(np.linalg.norm(tv, axis=1).max())
+    sens = dict(DEFAULT_SENSOR, **(sensor or {}))
+    sens_row = sensor_params(1, sens["noise_k"], sens["edge_counts"], sens["hole_p"])
+    bgr = lambda c: np.ascontiguousarray(c[:, ::-1])
+
+    def millimetres(p):                      # translations as the tree stores them; metres are derived from those
+        t_mm = p[..., 3] * 1000.0
+        p = p.copy()
+        p[..., 3] = t_mm * 0.001
+        return p, t_mm
+
+    tposes, t_mm_t = millimetres(sample_poses(n, K, (H, W), radius, seed, elevation, distance, inplane, margin, first_scene))
+    color_t, depth_t, _ = metrics.render_color(tposes, tv, tf, bgr(tc), K, (H, W), device, ambient=ambient, light=light)
+    md = metrics.render_depth(tposes, tv, tf, K, (H, W), device)[0]
+
+    def sensed(depth, scenes):               # sensor depth of the listed scenes (sorted), run by run of scene numbers
+        out = np.empty((len(scenes), H, W), np.uint16)
+        at = 0
+        for a, b in _runs(scenes):
+            out[at:at + b - a] = sensor_depth(depth[at:at + b - a], depth_scale, np.tile(sens_row, (b - a, 1)), seed,
+                                              first_scene + a, device)
+            at += b - a
+        return out
+
+    def visibility(scenes, u16):
+        boxes, counts = A.mask_boxes(md[scenes], K, A.scene_depth_from_u16(u16, depth_scale), device=device)
+        return boxes, counts[:, 1] / np.maximum(counts[:, 0], 1)
+
+    color, depth = color_t.copy(), depth_t.copy()
+    oposes, t_mm_o = np.zeros((n, len(occ), 3, 4)), np.zeros((n, len(occ), 3))
+    present = np.ones((n, 1 + len(occ)), bool)
+    redraws = np.zeros(n, np.int32)
+    pending = list(range(n)) if occ else []
+    for attempt in range(int(max_redraws) + 1):
+        if not pending:
+            break
+        p, t_mm = millimetres(np.concatenate([place_occluders(tposes[s:s + 1], radius, K, (H, W), seed, len(occ), depth_fraction,
+                                                              lateral, first_scene + s, attempt) for s in pending]))
+        c, d = color_t[pending], depth_t[pending]
+        for j, (ov, of, oc) in enumerate(occ):
+            c, d, _ = metrics.render_color(p[:, j], ov, of, bgr(oc), K, (H, W), device, ambient=ambient, light=light, into=(c, d))
+        _, vf = visibility(pending, sensed(d, pending))
+        keep = vf >= min_visib
+        for k, s in enumerate(pending):
+            if keep[k]:
+                color[s], depth[s], oposes[s], t_mm_o[s] = c[k], d[k], p[k], t_mm[k]
+            else:
+                redraws[s] += 1
+        pending = [s for k, s in enumerate(pending) if not keep[k]]
+    for s in pending:                        # no placement passed: the scene keeps no occluder
+        present[s, 1:] = False
+    u16 = sensed(depth, list(range(n)))
+    boxes, vf = visibility(list(range(n)), u16) if n else (np.zeros((0, 2, 4), np.int32), np.zeros(0))
+    box_full = np.full((n, 1 + len(occ), 4), -1, np.int32)
+    box_full[:, 0] = boxes[:, 0]
+    for j, (ov, of, _) in enumerate(occ):
+        rows = np.flatnonzero(present[:, 1 + j])
+        if len(rows):
+            alone = metrics.render_depth(oposes[rows, j], ov, of, K, (H, W), device)[0]
+            box_full[rows, 1 + j] = A.mask_boxes(alone, K, device=device)[0][:, 0]
+    if backgrounds is None:
+        bg = procedural_background(n, (H, W), seed, first_scene, device)
+    else:
+        bank = np.asarray(backgrounds, dtype=np.uint8)
+        bg = background_windows(bank, draw_windows(n, bank.shape, (H, W), seed, first_scene), (H, W), device)
+    params = draw_camera(n, seed, camera, first_scene)
+    frames = compose(bg, color, depth, params, seed, first_scene, device)
+    return dict(frames=frames, depth=u16, obj_ids=ids, poses=np.concatenate([tposes[:, None], oposes], axis=1),
+                t_mm=np.concatenate([t_mm_t[:, None], t_mm_o], axis=1), present=present, box_full=box_full,
+                box_visible=boxes[:, 1].copy(), visib_fract=vf, redraws=redraws, params=params)
+
+
+# ---- files
+def _write_mesh_ply(path, vertices, faces, colors=None):
+    """ASCII PLY with float64 coordinates written by repr (they read back to the same bits), optional uint8 RGB."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    with open(path, "w") as out:
+        out.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n" % len(v))
+        if colors is not None:
+            out.write("property uchar red\nproperty uchar green\nproperty uchar blue\n")
+        out.write("element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f))
+        for i in range(len(v)):
+            row = " ".join(repr(float(x)) for x in v[i])
+            out.write(row + (" %d %d %d\n" % tuple(int(x) for x in colors[i]) if colors is not None else "\n"))
+        for a, b, c in f:
+            out.write("3 %d %d %d\n" % (a, b, c))
+
+
+def write_png(path, array):
+    """An [H, W, 3] uint8 RGB or [H, W] uint16 array as a PNG file (Pillow, as evaluate.py's --save_img)."""
+    from PIL import Image
+    a = np.ascontiguousarray(array)
+    if not ((a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8) or (a.ndim == 2 and a.dtype == np.uint16)):
+        raise ValueError("write_png takes [H, W, 3] uint8 or [H, W] uint16")
+    Image.fromarray(a).save(path, format="PNG")
+
+
+def write_scene_tree(base, seq, scenes, meshes, K, depth_scale=0.001, first_frame=0):
+    """Write ``scenes`` (synthesize_scenes) as sequence ``seq`` of the SIXD tree ``base``, the layout sixd.load_sixd and
+    annotate.py read: ``camera.yml`` (fx, fy, cx, cy, depth_scale in millimetres per count, width, height),
+    ``models/models_info.yml`` (diameters, millimetres), ``models/obj_XX.ply``, ``test/SS/rgb/NNNN.png`` (RGB),
+    ``test/SS/depth/NNNN.png`` (16 bit), ``test/SS/gt.yml`` -- per frame the objects present, the target first, with
+    ``cam_R_m2c``, ``cam_t_m2c`` = the scenes' ``t_mm`` (millimetres; a reader's metres, t_mm * 0.001, are the scenes'
+    poses bit for bit) and ``obj_bb`` = (xmin, ymin, xmax - xmin, ymax - ymin) of the full box -- and ``test/SS/info.yml``
+    (cam_K, depth_scale).  ``meshes`` = {obj_id: (vertices in MILLIMETRES, faces[, colours RGB])}, the units of a SIXD
+    model file; the scenes were rendered from those vertices times 0.001.  Floats are written by repr.  ``first_frame``
+    > 0 appends a later chunk of scenes to the sequence's ``gt.yml`` and ``info.yml``.  This is the
+    writer of synthesised trees; ``write_sixd_tree`` above stays the writer of the ground-truth fixtures."""
+    import os
+    import yaml
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    n, H, W = scenes["depth"].shape
+    sdir = os.path.join(base, "test", "%02d" % int(seq))
+    for d in (os.path.join(base, "models"), os.path.join(sdir, "rgb"), os.path.join(sdir, "depth")):
+        os.makedirs(d, exist_ok=True)
+    with open(os.path.join(base, "camera.yml"), "w") as f:
+        yaml.safe_dump({"fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
+                        "depth_scale": float(depth_scale) * 1000.0, "width": W, "height": H}, f)
+    info_models = {}
+    for oid, mesh in sorted(meshes.items()):
+        v = np.asarray(mesh[0], dtype=np.float64).reshape(-1, 3)
+        hull = v if len(v) <= 2048 else v[np.unique(np.concatenate([v.argmin(0), v.argmax(0), np.arange(0, len(v), len(v) // 2048 + 1)]))]
+        diam = float(np.sqrt(((hull[:, None] - hull[None]) ** 2).sum(-1)).max())
+        info_models[int(oid)] = {"diameter": diam}
+        _write_mesh_ply(os.path.join(base, "models", "obj_%02d.ply" % int(oid)), v, mesh[1], mesh[2] if len(mesh) > 2 else None)
+    with open(os.path.join(base, "models", "models_info.yml"), "w") as f:
+        yaml.safe_dump(info_models, f)
+    gt, info = {}, {}
+    if int(first_frame) > 0:                 # a later chunk of the sequence: keep the frames already listed
+        with open(os.path.join(sdir, "gt.yml")) as f:
+            gt = yaml.safe_load(f)
+        with open(os.path.join(sdir, "info.yml")) as f:
+            info = yaml.safe_load(f)
+    for i in range(n):
+        nr = int(first_frame) + i
+        write_png(os.path.join(sdir, "rgb", "%04d.png" % nr), scenes["frames"][i][..., ::-1])
+        write_png(os.path.join(sdir, "depth", "%04d.png" % nr), scenes["depth"][i])
+        rows = []
+        for j, oid in enumerate(scenes["obj_ids"]):
+            if not scenes["present"][i, j]:
+                continue
+            xmin, xmax, ymin, ymax = (int(v) for v in scenes["box_full"][i, j])
+            rows.append({"obj_id": int(oid), "cam_R_m2c": [float(v) for v in scenes["poses"][i, j, :, :3].reshape(9)],
+                         "cam_t_m2c": [float(v) for v in scenes["t_mm"][i, j]],
+                         "obj_bb": [xmin, ymin, xmax - xmin, ymax - ymin]})
+        gt[nr] = rows
+        info[nr] = {"cam_K": [float(v) for v in K.reshape(9)], "depth_scale": float(depth_scale) * 1000.0}
+    with open(os.path.join(sdir, "gt.yml"), "w") as f:
+        yaml.safe_dump(gt, f)
+    with open(os.path.join(sdir, "info.yml"), "w") as f:
+        yaml.safe_dump(info, f)
+
+
+def export_training_set(tree, annotations, out, seq=None):
+    """Lay the frames of sequence ``seq`` of the tree ``tree`` (default: its only sequence) out as the two training
+    loaders expect, from the annotator's output ``annotations`` (annotate.write_annotations):
+      ``out/kpd/%012d.png``                      every annotated frame in one folder, KPDSampleLoader's ``img_folder``;
+      ``out/detector/NNNN.png`` + ``NNNN.txt``   image and Darknet label side by side, and ``out/detector/train.txt`` /
+                                                 ``eval.txt``, the ``train=`` / ``valid=`` lists of YoloSampleLoader.
+    Returns the two lists' paths.  Files are copied byte for byte."""
+    import os
+    import shutil
+    test = os.path.join(tree, "test")
+    if seq is None:
+        seqs = sorted(d for d in os.listdir(test) if os.path.isdir(os.path.join(test, d)))
+        if len(seqs) != 1:
+            raise ValueError("%s holds %d sequences: name one with seq=" % (test, len(seqs)))
+        seq = int(seqs[0])
+    rgb = os.path.join(test, "%02d" % int(seq), "rgb")
+    kpd, det = os.path.join(out, "kpd"), os.path.join(out, "detector")
+    os.makedirs(kpd, exist_ok=True)
+    os.makedirs(det, exist_ok=True)
+    lists = {}
+    for split in ("train", "eval"):
+        with open(os.path.join(annotations, "%s.txt" % split)) as f:
+            frames = [int(ln.strip()[:-len(".png")]) for ln in f if ln.strip()]
+        paths = []
+        for nr in frames:
+            src = os.path.join(rgb, "%04d.png" % nr)
+            shutil.copyfile(src, os.path.join(kpd, "%012d.png" % nr))
+            shutil.copyfile(src, os.path.join(det, "%04d.png" % nr))
+            shutil.copyfile(os.path.join(annotations, "labels", "%04d.txt" % nr), os.path.join(det, "%04d.txt" % nr))
+            paths.append(os.path.join(det, "%04d.png" % nr))
+        lists[split] = os.path.join(det, "%s.txt" % split)
+        with open(lists[split], "w") as f:
+            f.write("".join(p + "\n" for p in paths))
+    return lists

@@ -80,6 +80,8 @@
  *                          and Model3D.refine without its [n][n][3] arrays             utils/model.py:29-46
  *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
  *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
+ *   bp_synth_background, bp_synth_windows, bp_synth_compose, bp_synth_sensor_depth (and their _host twins)
+ *                          no reference counterpart: training frames and sensor depth synthesised from renders
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
  *   bp_darknet_*           Detector(cfg, weights, gpu) / Detector::detect    train_YOLO/src/yolo_v2_class.cpp:95-317
@@ -986,6 +988,41 @@ int bp_loader_next(bp_loader* l, long long* index, const unsigned char** bgr);
 int bp_loader_release(bp_loader* l, long long index);
 /* asynchronous host -> device copy on `stream` (h_src should be a loader slot or other pinned memory) */
 int bp_upload(void* d_dst, const void* h_src, size_t bytes, void* stream);
+
+/* ---- training-scene synthesiser (no reference counterpart) ----
+ * Images are [I][H][W][3] uint8, H, W <= 32768 and H W <= 2^24.  Image i of a call is scene `first_image` + i of the
+ * random source, a 32-bit mix keyed by (seed, stream, scene, pixel, channel): a scene's bytes do not depend on how the
+ * scenes are split over calls.  All per-pixel arithmetic is integer or fixed point; every _host twin works on host
+ * memory and gives the same bytes.  The per-image tables (`windows`, `params`) are HOST memory in both forms.  The
+ * device forms are enqueued on `stream` and do not synchronise it. */
+/* Procedural backgrounds: four octaves of lattice value noise (cells of 64, 32, 16, 8 px, bilinear in Q8) weighted,
+ * scaled and added to a base colour, all drawn per scene. */
+int bp_synth_background(int I, int H, int W, unsigned seed, unsigned first_image, unsigned char* d_out, void* stream);
+int bp_synth_background_host(int I, int H, int W, unsigned seed, unsigned first_image, unsigned char* out);
+/* Windows of a photograph bank d_bank [Nb][Hb][Wb][3] resampled to H x W, bilinear in fixed point, pixel centres
+ * aligned; windows [I][6] int32 = (bank image, x0, y0, w, h, flip), each window inside its image. */
+int bp_synth_windows(const unsigned char* d_bank, int Nb, int Hb, int Wb, const int* windows, int I, int H, int W,
+                     unsigned char* d_out, void* stream);
+int bp_synth_windows_host(const unsigned char* bank, int Nb, int Hb, int Wb, const int* windows, int I, int H, int W,
+                          unsigned char* out);
+/* The composite of a render (d_color, d_depth of bp_render_color) over a background through a camera model, per pixel
+ * and channel: paste with an inside feather ((a F + (9 - a) B + 4) / 9, a = pixels with depth > 0 in the 3 x 3
+ * neighbourhood clamped to the image; B where the centre has none), separable binomial blur of radius r (rows, then
+ * columns, clamped edges, each pass rounded half up), gain (Q8) and offset, noise (Irwin-Hall of 12 bytes, times a Q8
+ * sigma), clamp.  params [I][9] int32 = (feather 0/1, r 0..2, gain[3] 0..4096, offset[3] -255..255, sigma 0..16384).
+ * The output must not be an input. */
+int bp_synth_compose(const unsigned char* d_background, const unsigned char* d_color, const float* d_depth, int I, int H, int W,
+                     const int* params, unsigned seed, unsigned first_image, unsigned char* d_out, void* stream);
+int bp_synth_compose_host(const unsigned char* background, const unsigned char* color, const float* depth, int I, int H, int W,
+                          const int* params, unsigned seed, unsigned first_image, unsigned char* out);
+/* A depth sensor's image of a scene depth [I][H][W] f32 in metres: uint16 counts = depth / depth_scale rounded half up
+ * (0 stays 0, at most 65 535), plus noise of sigma noise_k count^2 / 2^28 counts, and set to 0 with probability
+ * hole_p / 256 where the counts of the 3 x 3 neighbourhood (clamped) span more than edge_counts.
+ * params [I][3] int32 = (noise_k 0..65535, edge_counts >= 0, hole_p 0..256). */
+int bp_synth_sensor_depth(const float* d_depth, int I, int H, int W, double depth_scale, const int* params, unsigned seed,
+                          unsigned first_image, uint16_t* d_out, void* stream);
+int bp_synth_sensor_depth_host(const float* depth, int I, int H, int W, double depth_scale, const int* params, unsigned seed,
+                               unsigned first_image, uint16_t* out);
 
 #ifdef __cplusplus
 }
