@@ -29,7 +29,9 @@ from betapose_amd import annotate as A, metrics, sixd, synth  # noqa: E402
 def build_parser():
     p = argparse.ArgumentParser(description="Keypoint Annotation")
     p.add_argument("--expID", default="default", type=str, help="Experiment ID")
-    p.add_argument("--obj_id", default=1, type=int, help="Object ID to annotate.")
+    p.add_argument("--obj_id", default=1, type=int,
+                   help="Object ID to annotate. Its sequence may hold other objects too (synthesize.py --models --seq N): only "
+                        "the rows of this object are annotated.")
     p.add_argument("--total_kp_number", default=50, type=int, help="Total number of keypoints to annotate.")
     p.add_argument("--train_split", default=180, type=int, help="Select this number to train and others to test.")
     p.add_argument("--output_base", default="./kp_dataset/", type=str, help="Output base address.")

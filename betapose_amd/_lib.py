@@ -281,6 +281,8 @@ PROTOTYPES = {
     "bp_synth_compose_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint, C.c_uint, vp]),
     "bp_synth_sensor_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp, vp]),
     "bp_synth_sensor_depth_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp]),
+    "bp_synth_instances": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "bp_synth_instances_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
 }
 
 RESULT_FLOATS = 316

@@ -340,6 +340,85 @@ def darknet_label(bbox_xyxy, image_size=(480, 640)):
     return "0 %f %f %f %f" % ((x1 + w / 2) / image_size[1], (y1 + h / 2) / image_size[0], w / image_size[1], h / image_size[0])
 
 
+def darknet_labels_multi(gt_rows, class_of, image_size=(480, 640), box="full"):
+    """The label lines of train_YOLO/scripts/gt_multi_object.py for one frame's ``gt.yml`` rows: one ``"%d %f %f %f %f"``
+    line (class, box centre and size as fractions of the image) per row whose ``obj_id`` is a key of ``class_of``
+    ({obj_id: class}), in row order.  ``box="full"`` reads ``obj_bb`` (x, y, w, h) -- with ``class_of = {i: i - 1}`` these
+    are the reference's lines --, ``box="visible"`` reads ``obj_bb_visib`` (synth.write_scene_tree's) and raises where a
+    row has none."""
+    if box not in ("full", "visible"):
+        raise ValueError("box must be 'full' or 'visible'")
+    key = "obj_bb" if box == "full" else "obj_bb_visib"
+    height, width = image_size
+    lines = []
+    for row in gt_rows:
+        oid = int(row["obj_id"])
+        if oid not in class_of:
+            continue
+        if key not in row:
+            raise ValueError("a gt.yml row of object %d has no %s" % (oid, key))
+        bbox = list(row[key])
+        bbox[0] = (bbox[0] + bbox[2] / 2) / width
+        bbox[1] = (bbox[1] + bbox[3] / 2) / height
+        bbox[2] = bbox[2] / width
+        bbox[3] = bbox[3] / height
+        lines.append("%d %f %f %f %f" % (int(class_of[oid]), bbox[0], bbox[1], bbox[2], bbox[3]))
+    return lines
+
+
+def write_multi_labels(bench_or_tree, seq, outdir, class_of, train_split, seed=0, box="full", image_size=None):
+    """Detector labels of EVERY object of a sequence: ``outdir/labels/NNNN.txt`` with darknet_labels_multi's lines for
+    each frame (an empty file where none of ``class_of``'s objects is in the frame), a seeded random split of
+    ``train_split`` frames for training and the rest for evaluation as ``train.txt`` / ``eval.txt`` (frame file names,
+    as write_annotations), ``obj.names`` (``obj_XX`` per class, in class order) and ``obj.data`` with ``classes``,
+    ``train``, ``valid``, ``names`` and ``backup``, the keys train_detector.py and detector_map.py read.
+    ``bench_or_tree``: a SIXD tree's path, whose ``test/SS/gt.yml`` is read row by row (what ``box="visible"`` needs), or
+    a sixd.load_sixd benchmark (full boxes only; ``seq`` is then unused).  ``image_size`` defaults to the tree's
+    ``camera.yml`` (480 x 640 without one).  Returns ``{'train': [...], 'eval': [...]}``, the frame numbers."""
+    import yaml
+    class_of = {int(k): int(v) for k, v in class_of.items()}
+    classes = sorted(set(class_of.values()))
+    if classes != list(range(len(classes))) or len(classes) != len(class_of):
+        raise ValueError("class_of must map the objects one to one onto classes 0 .. n - 1")
+    if isinstance(bench_or_tree, (str, os.PathLike)):
+        tree = os.fspath(bench_or_tree)
+        with open(os.path.join(tree, "test", "%02d" % int(seq), "gt.yml")) as f:
+            rows_of = {int(nr): rows for nr, rows in yaml.safe_load(f).items()}
+        if image_size is None and os.path.exists(os.path.join(tree, "camera.yml")):
+            with open(os.path.join(tree, "camera.yml")) as f:
+                cam = yaml.safe_load(f)
+            image_size = (int(cam.get("height", 480)), int(cam.get("width", 640)))
+    else:
+        rows_of = {int(fr.nr): [{"obj_id": int(o), "obj_bb": list(bb)} for o, _, bb in fr.gt] for fr in bench_or_tree.frames}
+    image_size = (480, 640) if image_size is None else image_size
+    frames = sorted(rows_of)
+    N = len(frames)
+    if not 0 <= int(train_split) <= N:
+        raise ValueError("train_split must lie in 0 .. %d" % N)
+    os.makedirs(os.path.join(outdir, "labels"), exist_ok=True)
+    for nr in frames:
+        with open(os.path.join(outdir, "labels", "%04d.txt" % nr), "w") as f:
+            f.write("".join(ln + "\n" for ln in darknet_labels_multi(rows_of[nr], class_of, image_size, box)))
+    chosen = set(np.random.default_rng(seed).choice(N, int(train_split), replace=False).tolist()) if N else set()
+    split = {"train": [nr for i, nr in enumerate(frames) if i in chosen], "eval": [nr for i, nr in enumerate(frames) if i not in chosen]}
+    for t, nrs in split.items():
+        with open(os.path.join(outdir, "%s.txt" % t), "w") as f:
+            f.write("".join("%04d.png\n" % nr for nr in nrs))
+    write_detector_data(outdir, class_of)
+    return split
+
+
+def write_detector_data(folder, class_of):
+    """``obj.names`` and ``obj.data`` of the detector set in ``folder`` (its ``train.txt`` / ``eval.txt``)."""
+    by_class = sorted((c, o) for o, c in class_of.items())
+    with open(os.path.join(folder, "obj.names"), "w") as f:
+        f.write("".join("obj_%02d\n" % o for _, o in by_class))
+    with open(os.path.join(folder, "obj.data"), "w") as f:
+        f.write("classes = %d\ntrain = %s\nvalid = %s\nnames = %s\nbackup = %s\n" % (
+            len(by_class), os.path.join(folder, "train.txt"), os.path.join(folder, "eval.txt"), os.path.join(folder, "obj.names"),
+            os.path.join(folder, "backup")))
+
+
 def write_annotations(outdir, ann, train_split, seed=0, image_size=(480, 640)):
     """Write ``ann`` (annotate_sequence) in the reference's layout under ``outdir``: ``kp_label/<i>.npy`` [Kp, 2] and
     ``bbox/<i>.npy`` [4] per annotated frame (``i`` counts the annotations from 0, the reference's output_counter), a

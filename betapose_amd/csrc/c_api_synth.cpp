@@ -45,6 +45,13 @@ static void synth_check_sensor(const int* params, int I, double depth_scale) {
     }
 }
 
+static void synth_check_instances(int J, int I, int H, int W) {
+    BP_CHECK(I > 0 && H > 0 && W > 0, "I, H and W must be positive");
+    BP_CHECK(J >= 1 && J <= bp::SY_INST_MAX, "J must lie in 1 .. 32");
+    BP_CHECK((long long)H * W <= (1ll << 24), "H * W must not exceed 2^24");
+    BP_CHECK((long long)I * J < (1ll << 28), "I * J must be below 2^28");
+}
+
 extern "C" {
 
 int bp_synth_background_host(int I, int H, int W, unsigned seed, unsigned first_image, unsigned char* out) {
@@ -128,6 +135,27 @@ int bp_synth_sensor_depth(const float* d_depth, int I, int H, int W, double dept
     synth_check_images(I, H, W);
     synth_check_sensor(params, I, depth_scale);
     bp::launch_synth_sensor_depth(d_depth, I, H, W, depth_scale, params, seed, first_image, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_synth_instances_host(const float* alone, int J, int I, int H, int W, const unsigned char* present, unsigned char* ids,
+                            float* depth, int* stats) {
+    BP_TRY
+    BP_CHECK(alone && present && ids && depth && stats, "null argument");
+    synth_check_instances(J, I, H, W);
+    bp::synth_instances_host(alone, J, I, H, W, present, ids, depth, stats);
+    return 0;
+    BP_CATCH
+}
+
+int bp_synth_instances(const float* d_alone, int J, int I, int H, int W, const unsigned char* d_present, unsigned char* d_ids,
+                       float* d_depth, int* d_stats, void* stream) {
+    BP_TRY
+    BP_CHECK(d_alone && d_present && d_ids && d_depth && d_stats, "null argument");
+    BP_CHECK(d_depth != d_alone, "the output must not be an input: a plane is read again after the depth is written");
+    synth_check_instances(J, I, H, W);
+    bp::launch_synth_instances(d_alone, J, I, H, W, d_present, d_ids, d_depth, d_stats, (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

@@ -8,7 +8,8 @@ activations stay O(1) through 75 / 104 conv layers (residual branches are
 damped) and the detector's objectness / the heat-map maxima are not saturated.
 
 The second half of the module is the training-scene synthesiser: rendered, occluded and composited
-frames with a sensor's depth and their ground truth, from a mesh alone (``synthesize_scenes``, ``write_scene_tree``).
+frames with a sensor's depth and their ground truth, from a mesh alone (``synthesize_scenes``, ``write_scene_tree``),
+and scenes of several targets with their instance masks (``instance_masks``, ``synthesize_multi``).
 """
 from __future__ import annotations
 
@@ -392,7 +393,7 @@ def _orthonormal(R):
 
 
 def sample_poses(n, K, size, radius, seed, elevation=(10.0, 80.0), distance=None, inplane=(-30.0, 30.0), margin=None,
-                 first_scene=0):
+                 first_scene=0, stream=0):
     """``n`` model-to-camera poses [n, 3, 4] float64 of an object of ``radius`` round its origin.  Per scene: the
     direction from the object to the camera is uniform in area over the band ``elevation`` (degrees above the object's
     xy plane; sin(elevation) uniform, azimuth uniform), the camera looks along it with the object's z axis up and is
@@ -400,7 +401,8 @@ def sample_poses(n, K, size, radius, seed, elevation=(10.0, 80.0), distance=None
     from the camera, on the ray of a pixel drawn uniformly at least ``margin`` pixels inside the image (default: the
     projected radius at the nearest distance, so the whole object is in view where the image allows).  Elevation and
     distance stay exactly what was drawn: the roll and the shift turn the camera about its own centre.  Scene
-    ``first_scene + i`` has its own generator, seeded by (seed, scene)."""
+    ``first_scene + i`` has its own generator, seeded by (seed, scene, stream): ``stream`` selects another set of draws
+    for the same scenes (synthesize_multi gives object j stream j); stream 0 is the draws this function always made."""
     H, W = _images_size(size)
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
     lo, hi = (4.0 * radius, 8.0 * radius) if distance is None else (float(distance[0]), float(distance[1]))
@@ -414,7 +416,7 @@ def sample_poses(n, K, size, radius, seed, elevation=(10.0, 80.0), distance=None
     s_lo, s_hi = np.sin(np.radians(elevation[0])), np.sin(np.radians(elevation[1]))
     poses = np.zeros((int(n), 3, 4))
     for i in range(int(n)):
-        rng = _scene_rng(seed, _POSE_DRAWS, first_scene + i)
+        rng = _scene_rng(seed, _POSE_DRAWS, first_scene + i, stream)
         s = rng.uniform(s_lo, s_hi)
         az = rng.uniform(0.0, 2.0 * np.pi)
         roll = np.radians(rng.uniform(inplane[0], inplane[1]))
@@ -611,6 +613,143 @@ def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=
                 box_visible=boxes[:, 1].copy(), visib_fract=vf, redraws=redraws, params=params)
 
 
+# ---- scenes of several targets
+INSTANCE_STATS = 10       # csrc/synth.h SY_INST_STATS: px_all, px_visib, full box, visible box
+MAX_INSTANCES = 32        # SY_INST_MAX
+MULTI_STACK_FLOATS = 1 << 24      # synthesize_multi's bound on its stack of lone renders
+
+
+def instance_masks(alone, present=None, device=None):
+    """Who owns each pixel of ``I`` scenes of ``J`` objects: ``(ids [I, H, W] uint8, depth [I, H, W] float32, stats
+    [I, J, 10] int32)`` from ``alone`` [J, I, H, W] float32 -- ``alone[j, i]`` is object j's depth image rendered alone in
+    scene i (metrics.render_depth's, 0 where nothing was drawn; the renders stack in this order) -- and ``present``
+    [I, J] (default: all).  Per pixel, among the present objects with a depth > 0 the smallest depth wins, among depths
+    of exactly the same float32 bits the HIGHEST j: metrics.render_color(into=...)'s rule when the objects are drawn in
+    ascending j.  ``ids`` = 1 + the winner (0: nothing), ``depth`` its depth (0).  ``stats[i, j]`` = (px_all, px_visib,
+    full xmin, xmax, ymin, ymax, visible xmin, xmax, ymin, ymax): the pixels with ``alone[j, i] > 0`` and those with
+    ``ids == j + 1``, boxes inclusive in get_bbox_from_mask order and -1 four times when their count is 0.  An object
+    that is not present keeps its full count and box.  ``J <= 32``, ``H W <= 2^24``.  ``device=None``: the host twin; a
+    torch device: csrc/synth_inst.hip, with the same bytes."""
+    from . import _lib
+    alone = np.ascontiguousarray(alone)
+    if alone.dtype != np.float32 or alone.ndim != 4:
+        raise ValueError("alone must be a float32 array [J, I, H, W]")
+    J, I, H, W = alone.shape
+    pres = np.ones((I, J), np.uint8) if present is None else np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+    if pres.shape != (I, J):
+        raise ValueError("present must be [%d, %d]" % (I, J))
+    if I == 0:
+        return np.zeros((0, H, W), np.uint8), np.zeros((0, H, W), np.float32), np.zeros((0, J, INSTANCE_STATS), np.int32)
+    if device is None:
+        ids, depth = np.empty((I, H, W), np.uint8), np.empty((I, H, W), np.float32)
+        stats = np.empty((I, J, INSTANCE_STATS), np.int32)
+        _lib.check(_lib.lib().bp_synth_instances_host(_lib.ptr(alone), J, I, H, W, _lib.ptr(pres), _lib.ptr(ids), _lib.ptr(depth),
+                                                      _lib.ptr(stats)))
+        return ids, depth, stats
+    torch, dev = _torch_device(device)
+    with torch.cuda.device(dev):
+        d_alone, d_pres = _upload(torch, dev, alone), _upload(torch, dev, pres)
+        d_ids = torch.empty((I, H, W), dtype=torch.uint8, device=dev)
+        d_depth = torch.empty((I, H, W), dtype=torch.float32, device=dev)
+        d_stats = torch.empty((I, J, INSTANCE_STATS), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().bp_synth_instances(_lib.ptr(d_alone), J, I, H, W, _lib.ptr(d_pres), _lib.ptr(d_ids), _lib.ptr(d_depth),
+                                                 _lib.ptr(d_stats), torch.cuda.current_stream(dev).cuda_stream))
+        return d_ids.cpu().numpy(), d_depth.cpu().numpy(), d_stats.cpu().numpy()
+
+
+def below_visibility(stats, min_visib):
+    """synthesize_multi's removal rule on instance_masks' ``stats`` [..., 10]: True where an object covers no pixel
+    or owns fewer than ``min_visib`` of the pixels it covers (float64)."""
+    px_all, px_visib = stats[..., 0].astype(np.float64), stats[..., 1].astype(np.float64)
+    return (stats[..., 0] == 0) | (px_visib < float(min_visib) * px_all)
+
+
+def synthesize_multi(meshes, K, size, n, seed, obj_ids=None, min_visib=0.3, elevation=(10.0, 80.0), distance=None,
+                     inplane=(-30.0, 30.0), backgrounds=None, camera=None, sensor=None, depth_scale=0.001, first_scene=0,
+                     ambient=0.5, light=(0.0, 0.0, 0.0), device=None):
+    """``n`` training scenes of the ``J`` meshes ``meshes`` = [(vertices, faces[, colours RGB uint8]), ...] in metres,
+    EVERY one of them a target: synthesize_scenes' dict with one row per scene and per-object shapes --
+
+      ``frames`` [n, H, W, 3] uint8 BGR, ``depth`` [n, H, W] uint16, ``obj_ids`` [J] (default 1, 2, ...), ``poses``
+      [n, J, 3, 4], ``t_mm`` [n, J, 3], ``present`` [n, J] bool, ``box_full``, ``box_visible`` [n, J, 4] (xmin, xmax, ymin,
+      ymax; -1 when empty), ``visib_fract`` [n, J] = ``px_visib / max(px_all, 1)``, ``px_all``, ``px_visib`` [n, J],
+      ``ids`` [n, H, W] uint8 (1 + the index j of the object that owns the pixel, 0 background), ``redraws`` [n] (zeros:
+      nothing is drawn again here) and ``params``.
+
+    Object j's poses are ``sample_poses(..., radius=its own, stream=j)`` through synthesize_scenes' millimetre round
+    trip; each object is rendered alone (render_depth) and instance_masks says who owns each pixel.  Visibility is the
+    renderer's own: an object's ``px_visib`` are the pixels it owns, out of the ``px_all`` it covers when alone.  The
+    removal rule: an object with ``px_all == 0`` or ``px_visib < min_visib * px_all`` (float64) is dropped from its
+    scene, all such objects in ONE round, and instance_masks runs once more with what is left.  Removing objects can only
+    uncover the others -- a pixel's owner either stays or was removed -- so every survivor keeps at least the pixels, and
+    so the fraction, it had: the survivors pass the rule again and one round is a fixed point.  A dropped object keeps
+    its pose and ``box_full`` and has ``present`` False, ``px_visib`` 0 and ``box_visible`` -1.  Colour is
+    render_color(into=...) over the present objects in ascending j, whose depth is instance_masks' bit for bit;
+    backgrounds, compose and sensor_depth are synthesize_scenes'.  The scenes are processed in chunks of
+    ``max(1, 2^24 // (J H W))``: the stack of lone renders never holds more than 2^24 floats (64 MB; one scene where a
+    single one is larger), the bound annotate_sequence puts on its depth stack.  Everything is a function of (seed, scene
+    number): chunks -- these and the caller's own, through ``first_scene`` -- concatenate to the whole.  ``device=None``:
+    the host twins throughout; a torch device: the kernels, with the same bytes."""
+    from . import metrics
+    H, W = _images_size(size)
+    n = int(n)
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    ms = [_mesh3(m) for m in meshes]
+    J = len(ms)
+    if not 1 <= J <= MAX_INSTANCES:
+        raise ValueError("synthesize_multi takes 1 .. %d meshes" % MAX_INSTANCES)
+    oids = np.arange(1, 1 + J) if obj_ids is None else np.asarray(obj_ids, dtype=np.int64).reshape(-1)
+    if len(oids) != J or len(set(oids.tolist())) != J:
+        raise ValueError("obj_ids names every mesh once")
+    radii = [float(np.linalg.norm(v, axis=1).max()) for v, _, _ in ms]
+    sens = dict(DEFAULT_SENSOR, **(sensor or {}))
+    sens_row = sensor_params(1, sens["noise_k"], sens["edge_counts"], sens["hole_p"])
+    bank = None if backgrounds is None else np.asarray(backgrounds, dtype=np.uint8)
+    out = dict(frames=np.zeros((n, H, W, 3), np.uint8), depth=np.zeros((n, H, W), np.uint16), poses=np.zeros((n, J, 3, 4)),
+               t_mm=np.zeros((n, J, 3)), present=np.zeros((n, J), bool), box_full=np.zeros((n, J, 4), np.int32),
+               box_visible=np.zeros((n, J, 4), np.int32), visib_fract=np.zeros((n, J)), px_all=np.zeros((n, J), np.int32),
+               px_visib=np.zeros((n, J), np.int32), ids=np.zeros((n, H, W), np.uint8), redraws=np.zeros(n, np.int32),
+               params=np.zeros((n, COMPOSE_PARAMS), np.int32))
+    step = max(1, MULTI_STACK_FLOATS // (J * H * W))
+    for a in range(0, n, step):
+        c = min(step, n - a)
+        first = first_scene + a
+        poses, alone = np.zeros((c, J, 3, 4)), np.zeros((J, c, H, W), np.float32)
+        for j, (v, f, _) in enumerate(ms):
+            p = sample_poses(c, K, (H, W), radii[j], seed, elevation, distance, inplane, None, first, stream=j)
+            out["t_mm"][a:a + c, j] = p[..., 3] * 1000.0         # translations as the tree stores them; metres derive from those
+            p[..., 3] = out["t_mm"][a:a + c, j] * 0.001
+            poses[:, j] = p
+            alone[j] = metrics.render_depth(p, v, f, K, (H, W), device)[0]
+        ids, depth, stats = instance_masks(alone, None, device)
+        present = ~below_visibility(stats, min_visib)
+        if not present.all():
+            ids, depth, stats = instance_masks(alone, present, device)
+        color, zbuf = np.zeros((c, H, W, 3), np.uint8), np.zeros((c, H, W), np.float32)
+        for j, (v, f, col) in enumerate(ms):
+            rows = np.flatnonzero(present[:, j])
+            if len(rows):
+                color, zbuf, _ = metrics.render_color(poses[rows, j], v, f, np.ascontiguousarray(col[:, ::-1]), K, (H, W), device,
+                                                      image_index=rows.astype(np.int32), images=c, ambient=ambient, light=light,
+                                                      into=(color, zbuf))
+        if not np.array_equal(zbuf.view(np.int32), depth.view(np.int32)):
+            raise RuntimeError("the colour chain's depth differs from instance_masks': the tie rule is broken")
+        if bank is None:
+            bg = procedural_background(c, (H, W), seed, first, device)
+        else:
+            bg = background_windows(bank, draw_windows(c, bank.shape, (H, W), seed, first), (H, W), device)
+        params = draw_camera(c, seed, camera, first)
+        s = slice(a, a + c)
+        out["frames"][s] = compose(bg, color, depth, params, seed, first, device)
+        out["depth"][s] = sensor_depth(depth, depth_scale, np.tile(sens_row, (c, 1)), seed, first, device)
+        out["poses"][s], out["present"][s], out["ids"][s], out["params"][s] = poses, present, ids, params
+        out["px_all"][s], out["px_visib"][s] = stats[..., 0], stats[..., 1]
+        out["box_full"][s], out["box_visible"][s] = stats[..., 2:6], stats[..., 6:10]
+        out["visib_fract"][s] = stats[..., 1] / np.maximum(stats[..., 0], 1)
+    out["obj_ids"] = oids
+    return out
+
+
 # ---- files
 def _write_mesh_ply(path, vertices, faces, colors=None):
     """ASCII PLY with float64 coordinates written by repr (they read back to the same bits), optional uint8 RGB."""
@@ -629,11 +768,12 @@ def _write_mesh_ply(path, vertices, faces, colors=None):
 
 
 def write_png(path, array):
-    """An [H, W, 3] uint8 RGB or [H, W] uint16 array as a PNG file (Pillow, as evaluate.py's --save_img)."""
+    """An [H, W, 3] uint8 RGB, [H, W] uint16 or [H, W] uint8 (greyscale) array as a PNG file (Pillow, as evaluate.py's
+    --save_img)."""
     from PIL import Image
     a = np.ascontiguousarray(array)
-    if not ((a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8) or (a.ndim == 2 and a.dtype == np.uint16)):
-        raise ValueError("write_png takes [H, W, 3] uint8 or [H, W] uint16")
+    if not ((a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8) or (a.ndim == 2 and a.dtype in (np.uint16, np.uint8))):
+        raise ValueError("write_png takes [H, W, 3] uint8, [H, W] uint16 or [H, W] uint8")
     Image.fromarray(a).save(path, format="PNG")
 
 
@@ -647,13 +787,24 @@ def write_scene_tree(base, seq, scenes, meshes, K, depth_scale=0.001, first_fram
     (cam_K, depth_scale).  ``meshes`` = {obj_id: (vertices in MILLIMETRES, faces[, colours RGB])}, the units of a SIXD
     model file; the scenes were rendered from those vertices times 0.001.  Floats are written by repr.  ``first_frame``
     > 0 appends a later chunk of scenes to the sequence's ``gt.yml`` and ``info.yml``.  This is the
-    writer of synthesised trees; ``write_sixd_tree`` above stays the writer of the ground-truth fixtures."""
+    writer of synthesised trees; ``write_sixd_tree`` above stays the writer of the ground-truth fixtures.
+    Scenes with ``ids`` (synthesize_multi) also get ``test/SS/mask/NNNN.png``, 8-bit greyscale with the owner's obj_id
+    per pixel and 0 for the background (so the ids must be below 256), and every ``gt.yml`` row also carries
+    ``obj_bb_visib`` (the visible box, as ``obj_bb``; -1 x4 stays -1, -1, 0, 0), ``visib_fract``, ``px_count_all`` and
+    ``px_count_visib``; scenes without ``ids`` write exactly the files above."""
     import os
     import yaml
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
     n, H, W = scenes["depth"].shape
     sdir = os.path.join(base, "test", "%02d" % int(seq))
-    for d in (os.path.join(base, "models"), os.path.join(sdir, "rgb"), os.path.join(sdir, "depth")):
+    multi = "ids" in scenes
+    if multi:
+        owner = np.concatenate([[0], np.asarray(scenes["obj_ids"], dtype=np.int64)])
+        if owner.min() < 0 or owner.max() > 255:
+            raise ValueError("an instance mask holds obj_ids 1 .. 255")
+        owner = owner.astype(np.uint8)
+    for d in (os.path.join(base, "models"), os.path.join(sdir, "rgb"), os.path.join(sdir, "depth")) + \
+            ((os.path.join(sdir, "mask"),) if multi else ()):
         os.makedirs(d, exist_ok=True)
     with open(os.path.join(base, "camera.yml"), "w") as f:
         yaml.safe_dump({"fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
@@ -677,6 +828,8 @@ def write_scene_tree(base, seq, scenes, meshes, K, depth_scale=0.001, first_fram
         nr = int(first_frame) + i
         write_png(os.path.join(sdir, "rgb", "%04d.png" % nr), scenes["frames"][i][..., ::-1])
         write_png(os.path.join(sdir, "depth", "%04d.png" % nr), scenes["depth"][i])
+        if multi:
+            write_png(os.path.join(sdir, "mask", "%04d.png" % nr), owner[scenes["ids"][i]])
         rows = []
         for j, oid in enumerate(scenes["obj_ids"]):
             if not scenes["present"][i, j]:
@@ -685,6 +838,10 @@ def write_scene_tree(base, seq, scenes, meshes, K, depth_scale=0.001, first_fram
             rows.append({"obj_id": int(oid), "cam_R_m2c": [float(v) for v in scenes["poses"][i, j, :, :3].reshape(9)],
                          "cam_t_m2c": [float(v) for v in scenes["t_mm"][i, j]],
                          "obj_bb": [xmin, ymin, xmax - xmin, ymax - ymin]})
+            if multi:
+                xmin, xmax, ymin, ymax = (int(v) for v in scenes["box_visible"][i, j])
+                rows[-1].update(obj_bb_visib=[xmin, ymin, xmax - xmin, ymax - ymin], visib_fract=float(scenes["visib_fract"][i, j]),
+                                px_count_all=int(scenes["px_all"][i, j]), px_count_visib=int(scenes["px_visib"][i, j]))
         gt[nr] = rows
         info[nr] = {"cam_K": [float(v) for v in K.reshape(9)], "depth_scale": float(depth_scale) * 1000.0}
     with open(os.path.join(sdir, "gt.yml"), "w") as f:
@@ -726,4 +883,34 @@ def export_training_set(tree, annotations, out, seq=None):
         lists[split] = os.path.join(det, "%s.txt" % split)
         with open(lists[split], "w") as f:
             f.write("".join(p + "\n" for p in paths))
+    return lists
+
+
+def export_detector_set(tree, seq, labels_dir, out):
+    """Lay the frames of sequence ``seq`` of the tree ``tree`` and the labels of every object (``labels_dir``:
+    annotate.write_multi_labels) side by side as YoloSampleLoader expects, as export_training_set does for one class:
+    ``out/NNNN.png`` + ``NNNN.txt``, ``out/train.txt`` / ``eval.txt`` (the images' paths), ``out/obj.names`` and
+    ``out/obj.data`` whose ``train`` / ``valid`` / ``names`` / ``backup`` point into ``out``.  Returns the two lists' paths
+    and the ``.data`` file's: ``{'train', 'eval', 'data'}``.  Images and labels are copied byte for byte."""
+    import os
+    import shutil
+    from . import annotate as A
+    rgb = os.path.join(tree, "test", "%02d" % int(seq), "rgb")
+    os.makedirs(out, exist_ok=True)
+    lists = {}
+    for split in ("train", "eval"):
+        with open(os.path.join(labels_dir, "%s.txt" % split)) as f:
+            frames = [int(ln.strip()[:-len(".png")]) for ln in f if ln.strip()]
+        paths = []
+        for nr in frames:
+            shutil.copyfile(os.path.join(rgb, "%04d.png" % nr), os.path.join(out, "%04d.png" % nr))
+            shutil.copyfile(os.path.join(labels_dir, "labels", "%04d.txt" % nr), os.path.join(out, "%04d.txt" % nr))
+            paths.append(os.path.join(out, "%04d.png" % nr))
+        lists[split] = os.path.join(out, "%s.txt" % split)
+        with open(lists[split], "w") as f:
+            f.write("".join(p + "\n" for p in paths))
+    with open(os.path.join(labels_dir, "obj.names")) as f:
+        objects = [int(ln.strip()[len("obj_"):]) for ln in f if ln.strip()]
+    A.write_detector_data(out, {o: c for c, o in enumerate(objects)})
+    lists["data"] = os.path.join(out, "obj.data")
     return lists

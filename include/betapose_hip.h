@@ -80,7 +80,7 @@
  *                          and Model3D.refine without its [n][n][3] arrays             utils/model.py:29-46
  *   bp_refine_depth, bp_refine_depth_host, bp_icp_normal_equations, bp_icp_normal_equations_host
  *                          no reference counterpart: projective point-to-plane ICP of a pose against the test depth image
- *   bp_synth_background, bp_synth_windows, bp_synth_compose, bp_synth_sensor_depth (and their _host twins)
+ *   bp_synth_background, bp_synth_windows, bp_synth_compose, bp_synth_sensor_depth, bp_synth_instances (and their _host twins)
  *                          no reference counterpart: training frames and sensor depth synthesised from renders
  *   bp_png_*, bp_loader_*  cv2.imread on ImageLoader's thread (PNG frames)   dataloader.py:150-179
  *   bp_upload              the H2D of a frame (img.cuda())                    dataloader.py:339
@@ -1023,6 +1023,21 @@ int bp_synth_sensor_depth(const float* d_depth, int I, int H, int W, double dept
                           unsigned first_image, uint16_t* d_out, void* stream);
 int bp_synth_sensor_depth_host(const float* depth, int I, int H, int W, double depth_scale, const int* params, unsigned seed,
                                unsigned first_image, uint16_t* out);
+/* Instance ownership of scenes of J objects.  alone [J][I][H][W] f32: alone[j][i] is object j's depth
+ * image rendered alone in scene i (bp_render_depth's, 0 where nothing was drawn).  Per pixel, among the objects with
+ * present[i][j] != 0 and a depth > 0 the smallest depth wins, and among depths of exactly the same float32 bits the
+ * HIGHEST j: bp_render_color's accumulation rule when the objects are drawn in ascending j.  ids [I][H][W] uint8 =
+ * 1 + the winner (0: nothing drawn), depth [I][H][W] f32 = its depth (0).  stats [I][J][10] int32 = (px_all, px_visib,
+ * full xmin, xmax, ymin, ymax, visible xmin, xmax, ymin, ymax): px_all counts the pixels with alone[j][i] > 0, px_visib
+ * those with ids == j + 1; the boxes are inclusive and -1 four times when their count is 0.  An object that is not
+ * present keeps its full count and box; its visible count is 0.  1 <= J <= 32, H W <= 2^24, I J < 2^28.  Integer
+ * arithmetic after one float comparison per (pixel, object): host and device give the same bytes.  The device form
+ * accumulates in d_stats itself (no workspace), is enqueued on `stream` and does not synchronise it; every byte of the
+ * three outputs is written; d_depth must not be d_alone. */
+int bp_synth_instances(const float* d_alone, int J, int I, int H, int W, const unsigned char* d_present, unsigned char* d_ids,
+                       float* d_depth, int* d_stats, void* stream);
+int bp_synth_instances_host(const float* alone, int J, int I, int H, int W, const unsigned char* present, unsigned char* ids,
+                            float* depth, int* stats);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,8 @@
     python synthesize.py --model obj_01.ply [--occluders a.ply,b.ply] --obj_id N --frames N --out TREE/
                          [--size 480x640] [--camera fx,fy,cx,cy] [--backgrounds DIR] [--min_visib .3] [--seed 0]
                          [--device cuda:0] [--training_set DIR]
+    python synthesize.py --models a.ply,b.ply,... --obj_ids 1,5,6 --frames N --out TREE/ [--seq N] [--class_map 1:0,5:1,6:2]
+                         [--label_box full|visible] [--detector_set DIR] [--train_split N] [the options above]
 
 The model (and the occluders) are SIXD model files: millimetres, per-vertex colours where they have them.  The object is
 rendered at seeded random poses, partly hidden by one instance of every occluder, pasted over a procedural background
@@ -13,6 +15,13 @@ sensor's images as sequence ``obj_id`` of the tree ``--out`` -- the tree ``annot
 ``kpmodels/obj_XX.ply`` is designate.py's to write.  --training_set also lays the frames out for train_kpd.py and
 train_detector.py; it needs the annotator's output directory ``<training_set>/annot/<obj_id %02d>`` to exist.
 Without --device everything runs on the host twins; no GPU is needed, and the files are the same bytes either way.
+
+--models makes scenes of SEVERAL targets instead (synth.py synthesize_multi): every mesh is placed on its
+own, an object that shows less than --min_visib of itself is left out of its scene, and sequence --seq (default: the
+first of --obj_ids) of the tree gets every remaining object's row in ``gt.yml`` -- with its visible box, fraction and
+pixel counts -- and an instance mask ``mask/NNNN.png``.  --detector_set also writes the shared detector's training set:
+one Darknet line per object and frame (class = --class_map, default the position in --obj_ids; box = --label_box), the
+images beside them, ``train.txt`` / ``eval.txt`` and the ``obj.data`` train_detector.py and detector_map.py take.
 """
 from __future__ import annotations
 
@@ -32,7 +41,14 @@ CHUNK = 64      # scenes synthesised and written at a time
 
 def build_parser():
     p = argparse.ArgumentParser(description="Training-scene synthesiser")
-    p.add_argument("--model", required=True, type=str, help="the object's mesh (.ply, millimetres)")
+    p.add_argument("--model", default=None, type=str, help="the object's mesh (.ply, millimetres)")
+    p.add_argument("--models", default=None, type=str, help="comma-separated meshes, every one a target (instead of --model)")
+    p.add_argument("--obj_ids", default=None, type=str, help="with --models: comma-separated object ids, one per mesh")
+    p.add_argument("--seq", default=None, type=int, help="with --models: the sequence to write (default: the first object id)")
+    p.add_argument("--class_map", default=None, type=str, help="with --detector_set: obj_id:class,... (default: position in --obj_ids)")
+    p.add_argument("--label_box", default="full", choices=("full", "visible"), help="with --detector_set: which box a label holds")
+    p.add_argument("--detector_set", default=None, type=str, help="with --models: also write the shared detector's training set here")
+    p.add_argument("--train_split", default=None, type=int, help="with --detector_set: frames for training (default: nine in ten)")
     p.add_argument("--occluders", default="", type=str, help="comma-separated meshes that may hide the object")
     p.add_argument("--obj_id", default=1, type=int, help="object id (and sequence number) in the tree")
     p.add_argument("--frames", default=200, type=int, help="number of scenes")
@@ -72,10 +88,51 @@ def load_bank(folder):
     return np.stack(images)
 
 
+def main_multi(args, K, size):
+    """--models: scenes of several targets, their tree and (--detector_set) the shared detector's training set."""
+    from betapose_amd import annotate as A
+    paths = [p for p in args.models.split(",") if p]
+    if not args.obj_ids:
+        raise SystemExit("--models needs --obj_ids, one id per mesh")
+    ids = [int(v) for v in args.obj_ids.split(",") if v]
+    if len(ids) != len(paths) or len(set(ids)) != len(ids):
+        raise SystemExit("--obj_ids must name each of the %d meshes of --models once" % len(paths))
+    seq = ids[0] if args.seq is None else args.seq
+    meshes = {oid: metrics.load_ply_colored_mesh(p) for oid, p in zip(ids, paths)}         # millimetres
+    metres = [(meshes[oid][0] * 0.001, meshes[oid][1], meshes[oid][2]) for oid in ids]
+    bank = load_bank(args.backgrounds) if args.backgrounds else None
+    kept = np.zeros(len(ids), np.int64)
+    fract = []
+    for first in range(0, args.frames, CHUNK):
+        n = min(CHUNK, args.frames - first)
+        scenes = synth.synthesize_multi(metres, K, size, n, args.seed, obj_ids=ids, min_visib=args.min_visib, backgrounds=bank,
+                                        first_scene=first, device=args.device)
+        synth.write_scene_tree(args.out, seq, scenes, meshes, K, 0.001, first_frame=first)
+        kept += scenes["present"].sum(axis=0)
+        fract += scenes["visib_fract"][scenes["present"]].tolist()
+    print("synthesised %d scenes of objects %s into sequence %02d of %s: %s kept, mean visib_fract %.3f"
+          % (args.frames, ",".join("%02d" % i for i in ids), seq, args.out,
+             " ".join("%02d:%d" % (i, k) for i, k in zip(ids, kept)), float(np.mean(fract)) if fract else 0.0))
+    if args.detector_set:
+        class_of = {oid: c for c, oid in enumerate(ids)}
+        if args.class_map:
+            class_of = {int(a): int(b) for a, b in (pair.split(":") for pair in args.class_map.split(",") if pair)}
+        split = args.frames - args.frames // 10 if args.train_split is None else args.train_split
+        annot = os.path.join(args.detector_set, "annot")
+        A.write_multi_labels(args.out, seq, annot, class_of, split, args.seed, args.label_box, size)
+        lists = synth.export_detector_set(args.out, seq, annot, args.detector_set)
+        print("detector set of %d classes: %s" % (len(class_of), lists["data"]))
+    return 0
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if (args.model is None) == (args.models is None):
+        raise SystemExit("give exactly one of --model (one target and its occluders) and --models (several targets)")
     H, W = (int(v) for v in args.size.lower().split("x"))
     K = camera_matrix(args.camera, (H, W))
+    if args.models is not None:
+        return main_multi(args, K, (H, W))
     paths = [args.model] + [p for p in args.occluders.split(",") if p]
     ids = [args.obj_id] + [i for i in range(1, len(paths) + 1) if i != args.obj_id][:len(paths) - 1]
     meshes = {oid: metrics.load_ply_colored_mesh(p) for oid, p in zip(ids, paths)}         # millimetres
