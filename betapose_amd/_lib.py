@@ -133,6 +133,15 @@ PROTOTYPES = {
                                   C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, vp]),
     "bp_render_color_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp]),
+    "bp_texture_mips_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bp_texture_mips": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_texture_mips_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bp_render_color_textured": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
+                                           C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, C.c_int, vp,
+                                           vp, vp, vp]),
+    "bp_render_color_textured_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+                                                vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp,
+                                                C.c_int, vp, vp, vp]),
     "bp_draw_boxes": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]),
     "bp_draw_boxes_host": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
     "bp_overlay": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),

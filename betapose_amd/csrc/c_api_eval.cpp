@@ -43,6 +43,13 @@ static void raster_check_color(int n, int F, int P, int H, int W, double near_z,
     BP_CHECK((unsigned long long)P * (unsigned long long)F <= bp::COLOR_MAX_IDS, "P * F must not exceed 2^32 - 2");
 }
 
+// what the texture calls check alike: the size limit, and `levels` against the size
+static void raster_check_texture(int Wt, int Ht, int levels) {
+    BP_CHECK(Wt > 0 && Ht > 0, "Wt and Ht must be positive");
+    BP_CHECK(Wt <= bp::texture_max_size() && Ht <= bp::texture_max_size(), "a texture must not exceed 8192 x 8192");
+    BP_CHECK(levels >= 1 && levels <= bp::texture_full_levels(Wt, Ht), "levels must lie in 1 .. 1 + ceil(log2(max(Wt, Ht)))");
+}
+
 static void raster_check_boxes(int P, int I, int H, int W, double near_z) {
     BP_CHECK(P > 0 && I > 0 && H > 0 && W > 0, "P, I, H and W must be positive");
     check_pixels(H, W);
@@ -276,6 +283,69 @@ int bp_render_color(const double* d_model, int n, const int* d_faces, int F, con
     raster_check_color(n, F, P, H, W, near_z, image_index, I);
     bp::render_color(d_poses, P, d_model, n, d_faces, F, d_colors, image_index, I, K, H, W, pixel_center, near_z, ambient, light,
                      accumulate, d_color, d_depth, d_skipped, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+size_t bp_texture_mips_bytes(int Wt, int Ht, int levels) {
+    if (Wt <= 0 || Ht <= 0 || Wt > bp::texture_max_size() || Ht > bp::texture_max_size() || levels < 1 ||
+        levels > bp::texture_full_levels(Wt, Ht))
+        return 0;
+    return bp::texture_mips_texels(Wt, Ht, levels) * sizeof(uint32_t);
+}
+
+int bp_texture_mips_host(const unsigned char* texture, int Wt, int Ht, int levels, uint32_t* mips) {
+    BP_TRY
+    BP_CHECK(texture && mips, "null argument");
+    raster_check_texture(Wt, Ht, levels);
+    bp::texture_mips_host(texture, Wt, Ht, levels, mips);
+    return 0;
+    BP_CATCH
+}
+
+int bp_texture_mips(const unsigned char* d_texture, int Wt, int Ht, int levels, uint32_t* d_mips, void* stream) {
+    BP_TRY
+    BP_CHECK(d_texture && d_mips, "null argument");
+    raster_check_texture(Wt, Ht, levels);
+    bp::launch_texture_mips(d_texture, Wt, Ht, levels, d_mips, (hipStream_t)stream);
+    BP_HIP(hipGetLastError());
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_color_textured_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                                  const unsigned char* colors, const double* uv, const uint32_t* mips, int Wt, int Ht,
+                                  int levels, const int* image_index, int I, const double* K, int H, int W,
+                                  double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                                  unsigned char* color, float* depth, int* skipped) {
+    BP_TRY
+    BP_CHECK(poses && vertices && faces && K && light && color && depth && skipped, "null argument");
+    BP_CHECK(uv ? mips != nullptr : colors != nullptr, "null argument: uv needs the pyramid, no uv needs colors");
+    raster_check_color(n, F, P, H, W, near_z, image_index, I);
+    if (uv) raster_check_texture(Wt, Ht, levels);
+    const bp::ColorTexture tex{uv, mips, Wt, Ht, levels};
+    const int rc = uv ? bp::render_color_textured_host(poses, P, vertices, n, faces, F, tex, image_index, I, K, H, W, pixel_center,
+                                                       near_z, ambient, light, accumulate, color, depth, skipped)
+                      : bp::render_color_host(poses, P, vertices, n, faces, F, colors, image_index, I, K, H, W, pixel_center,
+                                              near_z, ambient, light, accumulate, color, depth, skipped);
+    BP_CHECK(rc == 0, "a face index lies outside [0, n)");   // (the scan comes before anything is touched)
+    return 0;
+    BP_CATCH
+}
+
+int bp_render_color_textured(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
+                             const double* d_uv, const uint32_t* d_mips, int Wt, int Ht, int levels, const double* d_poses,
+                             int P, const int* image_index, int I, const double* K, int H, int W, double pixel_center,
+                             double near_z, double ambient, const double* light, int accumulate, unsigned char* d_color,
+                             float* d_depth, int* d_skipped, void* stream) {
+    BP_TRY
+    BP_CHECK(d_model && d_faces && d_poses && K && light && d_color && d_depth && d_skipped, "null argument");
+    BP_CHECK(d_uv ? d_mips != nullptr : d_colors != nullptr, "null argument: uv needs the pyramid, no uv needs colors");
+    raster_check_color(n, F, P, H, W, near_z, image_index, I);
+    if (d_uv) raster_check_texture(Wt, Ht, levels);
+    const bp::ColorTexture tex{d_uv, d_mips, Wt, Ht, levels};
+    bp::render_color(d_poses, P, d_model, n, d_faces, F, d_colors, image_index, I, K, H, W, pixel_center, near_z, ambient, light,
+                     accumulate, d_color, d_depth, d_skipped, (hipStream_t)stream, d_uv ? &tex : nullptr);
     return 0;
     BP_CATCH
 }

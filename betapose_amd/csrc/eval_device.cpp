@@ -103,7 +103,7 @@ static int raster_pose_range(const int* image_index, int P, int i1, int p0) {
 void render_color(const double* d_poses, int P, const double* d_model, int n, const int* d_faces, int F,
                   const unsigned char* d_colors, const int* image_index, int I, const double* K, int H, int W,
                   double pixel_center, double near_z, double ambient, const double* light, int accumulate,
-                  unsigned char* d_color, float* d_depth, int* d_skipped, hipStream_t s) {
+                  unsigned char* d_color, float* d_depth, int* d_skipped, hipStream_t s, const ColorTexture* tex) {
     const size_t HW = (size_t)H * W;
     // images in flight: 8 bytes of key per pixel; poses in flight: their vertex workspace; each under RASTER_WS_BYTES
     const size_t ichunk = chunk_items(HW * 8, (size_t)I), pchunk = chunk_items(raster_vertex_bytes(n, 1), (size_t)P);
@@ -124,8 +124,12 @@ void render_color(const double* d_poses, int P, const double* d_model, int n, co
             launch_raster_transform(d_model, n, d_poses + (size_t)q0 * 12, c, nullptr, 0, cam, ws, s);
             launch_color_visibility(d_faces, F, n, ws, q0, c, d_index, (int)i0, cam, H, W, keys, d_skipped, s);
         }
-        launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, cam, H, W, lt, d_color + i0 * HW * 3,
-                             d_depth + i0 * HW, s);
+        if (tex)
+            launch_color_resolve_tex(keys, m, d_model, d_faces, F, *tex, d_poses, cam, H, W, lt, d_color + i0 * HW * 3,
+                                     d_depth + i0 * HW, s);
+        else
+            launch_color_resolve(keys, m, d_model, d_faces, F, d_colors, d_poses, cam, H, W, lt, d_color + i0 * HW * 3,
+                                 d_depth + i0 * HW, s);
         p0 = p1;
     }
     BP_HIP(hipGetLastError());

@@ -1,5 +1,5 @@
 // Depth and colour rasterisers and VSD: the declarations shared by raster_host.cpp, raster.hip, raster_color_host.cpp,
-// raster_color.hip, vsd.hip, eval_device.cpp and c_api_eval.cpp, so a signature that drifts fails to compile.  Needs no HIP
+// raster_color.hip, raster_texture_host.cpp, raster_texture.hip, vsd.hip, eval_device.cpp and c_api_eval.cpp, so a signature that drifts fails to compile.  Needs no HIP
 // header (the host twins are plain C++): the stream type is declared as hip_runtime_api.h declares it.  The loop over a
 // pose's triangles and their pixels belongs to none of those files: it is raster_walk.inc, which the four raster units
 // include.
@@ -54,6 +54,11 @@ int render_color_host(const double* poses, int P, const double* vertices, int n,
                       const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
                       double pixel_center, double near, double ambient, const double* light, int accumulate,
                       unsigned char* color, float* depth, int* skipped);
+// render_color_host's first half, which the textured twin runs too: keys [I][H][W] <- the z-test of every pose (with
+// `accumulate` over the kept keys of depth [I][H][W]), skipped [P].  The face indices have been checked.
+void color_visibility_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                           const int* image_index, int I, const RsCam& cam, int H, int W, int accumulate, const float* depth,
+                           unsigned long long* keys, int* skipped);
 void draw_boxes_host(const double* poses, int P, const double* corners, const unsigned char* corner_colors,
                      const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near,
                      unsigned char* color);
@@ -87,6 +92,29 @@ void launch_draw_boxes(const double* poses, int q0, int count, const double* cor
 void launch_overlay(const unsigned char* frames, const unsigned char* color, const float* depth, size_t pixels, int alpha,
                     unsigned char* out, hipStream_t s);
 
+// ---- raster_texture_host.cpp / raster_texture.hip: a texture in the place of the vertex colours
+struct ColorTexture {
+    const double* uv;        // [F][3][2]: (u, v) of every face corner, v upwards
+    const uint32_t* mips;    // the packed pyramid of a Wt x Ht image, one dword a texel
+    int Wt, Ht;
+    int levels;              // levels the resolve may read, 1 .. texture_full_levels (1: the image alone)
+};
+int texture_max_size();                                     // Wt, Ht above this are refused
+int texture_full_levels(int Wt, int Ht);                    // 1 + ceil(log2(max(Wt, Ht)))
+size_t texture_mips_texels(int Wt, int Ht, int levels);     // dwords of the first `levels` levels
+// mips <- the first `levels` levels of image [Ht][Wt][3] u8
+void texture_mips_host(const unsigned char* image, int Wt, int Ht, int levels, uint32_t* mips);
+void launch_texture_mips(const unsigned char* image, int Wt, int Ht, int levels, uint32_t* mips, hipStream_t s);
+// render_color_host with the textured resolve
+int render_color_textured_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                               const ColorTexture& tex, const int* image_index, int I, const double* K, int H, int W,
+                               double pixel_center, double near, double ambient, const double* light, int accumulate,
+                               unsigned char* color, float* depth, int* skipped);
+// launch_color_resolve with the textured fragment
+void launch_color_resolve_tex(const unsigned long long* keys, int images, const double* model, const int* faces, int F,
+                              const ColorTexture& tex, const double* poses, const RsCam& cam, int H, int W,
+                              const ColorLight& light, unsigned char* color, float* depth, hipStream_t s);
+
 // ---- vsd.hip
 // acc [pairs][VSD_ACC] (zeroed by the caller) += the counts of pairs [0, pairs): zbuf holds the ground-truth renders
 // [pairs][H][W] followed by the estimates' [pairs][H][W] (cleared value +inf = nothing drawn)
@@ -102,10 +130,11 @@ void launch_vsd_finish(const int* acc, const int* test_index, int T, int P, int 
 #pragma GCC visibility push(hidden)     // the library's own: not in its dynamic symbol table
 void render_depth(const double* poses, int P, const double* model, int n, const int* faces, int F, const double* K, int H,
                   int W, double pixel_center, double near, float* depth, int* skipped, hipStream_t s);
+// (tex: NULL shades from colors, otherwise from the texture and colors is not read)
 void render_color(const double* poses, int P, const double* model, int n, const int* faces, int F, const unsigned char* colors,
                   const int* image_index, int I, const double* K, int H, int W, double pixel_center, double near,
                   double ambient, const double* light, int accumulate, unsigned char* color, float* depth, int* skipped,
-                  hipStream_t s);
+                  hipStream_t s, const ColorTexture* tex = nullptr);
 void draw_boxes(const double* poses, int P, const double* corners, const unsigned char* corner_colors, const int* image_index,
                 int I, const double* K, int H, int W, double pixel_center, double near, unsigned char* color, hipStream_t s);
 void overlay(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W, int alpha,

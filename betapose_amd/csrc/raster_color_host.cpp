@@ -22,6 +22,29 @@ namespace {
 #include "raster_color_math.inc"
 }  // namespace
 
+void color_visibility_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                           const int* image_index, int I, const RsCam& cam, int H, int W, int accumulate, const float* depth,
+                           unsigned long long* keys, int* skipped) {
+    const size_t HW = (size_t)H * W;
+    std::vector<double> X((size_t)n * 3);
+    std::vector<int> S((size_t)n * 2);
+    std::fill(keys, keys + (size_t)I * HW, RC_EMPTY_KEY);
+    if (accumulate)
+        for (size_t i = 0; i < (size_t)I * HW; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, &depth[i], 4);
+            if (depth[i] > 0.0f) keys[i] = rc_key(bits, RC_KEEP);
+        }
+    for (int q = 0; q < P; ++q) {
+        unsigned long long* kb = keys + (size_t)(image_index ? image_index[q] : q) * HW;
+        skipped[q] = rs_walk_host(cam, poses + (size_t)q * 12, vertices, n, faces, F, H, W, X.data(), S.data(),
+                                  [&](size_t at, uint32_t bits, int f) {    // smaller key wins
+                                      const unsigned long long key = rc_key(bits, (uint32_t)((unsigned long long)q * F + f));
+                                      if (key < kb[at]) kb[at] = key;
+                                  });
+    }
+}
+
 int render_color_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
                       const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
                       double pixel_center, double near, double ambient, const double* light, int accumulate,
@@ -31,23 +54,8 @@ int render_color_host(const double* poses, int P, const double* vertices, int n,
     const RsCam cam = raster_cam(K, pixel_center, near);
     const ColorLight lt{ambient, light[0], light[1], light[2]};
     const size_t HW = (size_t)H * W;
-    std::vector<double> X((size_t)n * 3);
-    std::vector<int> S((size_t)n * 2);
-    std::vector<unsigned long long> keys((size_t)I * HW, RC_EMPTY_KEY);
-    if (accumulate)
-        for (size_t i = 0; i < (size_t)I * HW; ++i) {
-            uint32_t bits;
-            std::memcpy(&bits, &depth[i], 4);
-            if (depth[i] > 0.0f) keys[i] = rc_key(bits, RC_KEEP);
-        }
-    for (int q = 0; q < P; ++q) {
-        unsigned long long* kb = keys.data() + (size_t)(image_index ? image_index[q] : q) * HW;
-        skipped[q] = rs_walk_host(cam, poses + (size_t)q * 12, vertices, n, faces, F, H, W, X.data(), S.data(),
-                                  [&](size_t at, uint32_t bits, int f) {    // smaller key wins
-                                      const unsigned long long key = rc_key(bits, (uint32_t)((unsigned long long)q * F + f));
-                                      if (key < kb[at]) kb[at] = key;
-                                  });
-    }
+    std::vector<unsigned long long> keys((size_t)I * HW);
+    color_visibility_host(poses, P, vertices, n, faces, F, image_index, I, cam, H, W, accumulate, depth, keys.data(), skipped);
     // resolve: shade the winner of every pixel from the model, the faces and the pose alone
     for (int i = 0; i < I; ++i)
         for (int y = 0; y < H; ++y)

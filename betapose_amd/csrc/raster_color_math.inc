@@ -1,5 +1,6 @@
 // The colour renderer's arithmetic of O(1) size, ONE source for the host twin (raster_color_host.cpp) and the device
-// kernels (raster_color.hip): the 64-bit z-test key, the shading of a winning fragment, the set-up, stepping and colour of
+// kernels (raster_color.hip): the 64-bit z-test key, the shading of a winning fragment (its geometry is the textured
+// resolve's too, raster_texture_math.inc), the set-up, stepping and colour of
 // one edge of a 3-D bounding box and the blend of a rendered pixel over a frame.  Host and device compile this text and do
 // the same f64 / integer operations in the same order, without FMA contraction, so their images agree byte for byte.
 // Plain C++17, f64 and integers only.  Included right after raster_math.inc (it uses RsCam, rs_transform and the integer
@@ -27,12 +28,21 @@ BP_HD double rc_sub_area(const double* P, const double* Q, const double* X, doub
     return (cx * nx + cy * ny) + cz * nz;
 }
 
-// Colour of the fragment of pixel (x, y) on the triangle with camera-space vertices A, B, C IN THE FACE'S OWN ORDER and
-// vertex colours ca, cb, cc [3] u8: perspective-correct interpolation at the point X where the pixel's ray meets the
-// triangle's plane (the same clamped f64 depth rs_depth_bits rounds to f32), times the two-sided diffuse + ambient
-// weight of the reference's fragment shader, light_w = min(ambient + 0.5 max(L . N, 0), 1).
-BP_HD void rc_shade(const RsCam& cam, const double* A, const double* B, const double* C, const unsigned char* ca,
-                    const unsigned char* cb, const unsigned char* cc, int x, int y, const ColorLight& lt, unsigned char* out) {
+// What the two resolves (vertex colours: rc_shade; texture: raster_texture_math.inc tx_shade) share of a fragment: the
+// plane n . X = nd of the triangle with n.n = nn, the clamped perspective-correct weights of its three vertices at the
+// point where the pixel's ray meets the plane, and the light weight.
+struct RcFrag {
+    double nx, ny, nz, nd, nn;
+    double wa, wb, wc;
+    double light_w;
+};
+
+// The fragment of pixel (x, y) on the triangle with camera-space vertices A, B, C IN THE FACE'S OWN ORDER:
+// perspective-correct weights at the point X where the pixel's ray meets the triangle's plane (the same clamped f64
+// depth rs_depth_bits rounds to f32) and the two-sided diffuse + ambient weight of the reference's fragment shader,
+// light_w = min(ambient + 0.5 max(L . N, 0), 1).
+BP_HD void rc_fragment(const RsCam& cam, const double* A, const double* B, const double* C, int x, int y, const ColorLight& lt,
+                       RcFrag* g) {
     // the plane and the depth exactly as rs_setup / rs_depth_bits compute them
     const double e1x = B[0] - A[0], e1y = B[1] - A[1], e1z = B[2] - A[2];
     const double e2x = C[0] - A[0], e2y = C[1] - A[1], e2z = C[2] - A[2];
@@ -80,12 +90,24 @@ BP_HD void rc_shade(const RsCam& cam, const double* A, const double* B, const do
     if (!(diffuse > 0.0)) diffuse = 0.0;
     double light_w = lt.ambient + 0.5 * diffuse;
     if (light_w > 1.0) light_w = 1.0;
+    g->nx = nx; g->ny = ny; g->nz = nz; g->nd = nd; g->nn = nn;
+    g->wa = wa; g->wb = wb; g->wc = wc;
+    g->light_w = light_w;
+}
+
+// a channel of the image from its unlit value `base` (0 .. 255) and the light weight
+BP_HD unsigned char rc_lit(double light_w, double base) {
+    const double v = floor(light_w * base + 0.5);
+    return (unsigned char)(v >= 255.0 ? 255 : (v > 0.0 ? (int)v : 0));
+}
+
+// Colour of that fragment from the vertex colours ca, cb, cc [3] u8: their mix by the fragment's weights, lit.
+BP_HD void rc_shade(const RsCam& cam, const double* A, const double* B, const double* C, const unsigned char* ca,
+                    const unsigned char* cb, const unsigned char* cc, int x, int y, const ColorLight& lt, unsigned char* out) {
+    RcFrag g;
+    rc_fragment(cam, A, B, C, x, y, lt, &g);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double base = (wa * (double)ca[k] + wb * (double)cb[k]) + wc * (double)cc[k];
-        const double v = floor(light_w * base + 0.5);
-        out[k] = (unsigned char)(v >= 255.0 ? 255 : (v > 0.0 ? (int)v : 0));
-    }
+    for (int k = 0; k < 3; ++k) out[k] = rc_lit(g.light_w, (g.wa * (double)ca[k] + g.wb * (double)cb[k]) + g.wc * (double)cc[k]);
 }
 
 // ---- 3-D bounding boxes: the 12 edges of the reference's Model3D._compute_bbox between its 8 corners

@@ -322,17 +322,98 @@ def load_ply_mesh(path: str):
     ``load_ply_vertices`` reads them (same formats, same units: the file's own, nothing is scaled) and the
     ``vertex_indices`` / ``vertex_index`` list of its face element.  A polygon of more than three vertices is
     fan-triangulated about its first vertex, (v0, v1, v2), (v0, v2, v3), ...; one of fewer than three is dropped."""
-    return _read_ply_mesh(path)[:2]
+    return _read_ply_mesh(path)[0][:2]
 
 
 def load_ply_colored_mesh(path: str):
     """``(vertices [n, 3] float64, faces [F, 3] int32, colors [n, 3] uint8 RGB)``: ``load_ply_mesh`` plus the ``red``,
     ``green``, ``blue`` properties of the vertex element (ASCII and both binary byte orders; float colours in [0, 1]
     are scaled to 0 .. 255).  A file without them gives 128 everywhere, the reference's 0.5 grey (utils/model.py)."""
-    vertices, faces, colors = _read_ply_mesh(path)
+    vertices, faces, colors = _read_ply_mesh(path)[0]
     if colors is None:
         colors = np.full((len(vertices), 3), 128, np.uint8)
     return vertices, faces, colors
+
+
+def load_ply_textured_mesh(path: str):
+    """``(vertices, faces, colors, uv, texture_file)``: ``load_ply_colored_mesh`` plus the mesh's texture coordinates and
+    the image they refer to.  ``uv`` [F, 3, 2] float64 holds one (u, v) per face corner (v upwards: v = 1 is the image's
+    top row), or is None when the file has none.  Two layouts are read, in ASCII and both binary byte orders: scalar
+    vertex properties ``texture_u`` / ``texture_v`` (also ``u`` / ``v`` and ``s`` / ``t``), copied to the corners of every
+    face, and a face ``property list uchar float texcoord`` of 2 k floats for a k-gon, which fan triangulation carries
+    along exactly as it carries the indices (and which survives seams); where a file has both, the face list wins.
+    ``texture_file`` is the path named by the first ``comment TextureFile NAME``, resolved against the PLY's folder, or
+    None."""
+    (vertices, faces, colors), uv, texture_file = _read_ply_mesh(path)
+    if colors is None:
+        colors = np.full((len(vertices), 3), 128, np.uint8)
+    return vertices, faces, colors, uv, texture_file
+
+
+TEXTURE_MAX_SIZE = 8192       # csrc/raster_texture_math.inc TX_MAX_SIZE
+
+
+def load_texture(path: str) -> np.ndarray:
+    """A PNG file as a texture [Ht, Wt, 3] uint8 RGB, row 0 the top of the image (the project's own decoder,
+    frame_loader.decode_png: grey, RGB and RGBA at 8 bits; alpha is dropped)."""
+    from . import frame_loader
+    with open(path, "rb") as f:
+        data = f.read()
+    return np.ascontiguousarray(frame_loader.decode_png(data)[:, :, ::-1])
+
+
+def texture_levels(Wt, Ht):
+    """Levels of the full pyramid of a Wt x Ht image: 1 + ceil(log2(max(Wt, Ht)))."""
+    levels, w, h = 1, int(Wt), int(Ht)
+    while w > 1 or h > 1:
+        w, h, levels = (w + 1) >> 1, (h + 1) >> 1, levels + 1
+    return levels
+
+
+class TextureMips:
+    """A packed mip pyramid (``texture_mips``): ``data`` uint32 [texels] (numpy on the host, a torch tensor on a
+    device), level 0 = the Wt x Ht image, one dword a texel with channel k in byte k, the levels one after the other."""
+
+    def __init__(self, data, Wt, Ht, levels, device):
+        self.data, self.Wt, self.Ht, self.levels, self.device = data, int(Wt), int(Ht), int(levels), device
+
+    def level(self, l):
+        """Level ``l`` as a uint8 array [h, w, 3] (a copy, on the host)."""
+        w, h, at = self.Wt, self.Ht, 0
+        for _ in range(int(l)):
+            at, w, h = at + w * h, (w + 1) >> 1, (h + 1) >> 1
+        d = self.data if isinstance(self.data, np.ndarray) else self.data.cpu().numpy()
+        return np.ascontiguousarray(d.view(np.uint32)[at:at + w * h].view(np.uint8).reshape(h, w, 4)[:, :, :3])
+
+
+def texture_mips(texture, device=None):
+    """The mip pyramid of ``texture`` [Ht, Wt, 3] uint8 as render_color takes it (a ``TextureMips``): level l + 1 has
+    ceil(w / 2) x ceil(h / 2) texels, each ``(a + b + c + d + 2) >> 2`` per channel of its 2 x 2 block (the partner
+    index clamped where a dimension is odd), down to 1 x 1.  ``device=None``: built by the host twin,
+    for the host renderer; a torch device: by bp_texture_mips, resident there.  The two hold the same bytes."""
+    from . import _lib
+    tex = np.ascontiguousarray(texture)
+    if tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] != 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
+        raise ValueError("a texture is a uint8 array [Ht, Wt, 3]")
+    Ht, Wt = tex.shape[:2]
+    if Wt > TEXTURE_MAX_SIZE or Ht > TEXTURE_MAX_SIZE:
+        raise ValueError("a texture must not exceed %d x %d (got %d x %d)" % (TEXTURE_MAX_SIZE, TEXTURE_MAX_SIZE, Wt, Ht))
+    levels = texture_levels(Wt, Ht)
+    texels = _lib.lib().bp_texture_mips_bytes(Wt, Ht, levels) // 4
+    if device is None:
+        data = np.empty(texels, np.uint32)
+        _lib.check(_lib.lib().bp_texture_mips_host(_lib.ptr(tex), Wt, Ht, levels, _lib.ptr(data)))
+        return TextureMips(data, Wt, Ht, levels, None)
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_tex = torch.from_numpy(tex).to(dev)
+        data = torch.empty(texels, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.lib().bp_texture_mips(_lib.ptr(d_tex), Wt, Ht, levels, _lib.ptr(data), stream.cuda_stream))
+        stream.synchronize()       # d_tex is released on return
+    return TextureMips(data, Wt, Ht, levels, dev)
 
 
 def _ply_colors(cols, kinds):
@@ -344,8 +425,12 @@ def _ply_colors(cols, kinds):
     return np.ascontiguousarray(np.stack(out, axis=1))
 
 
+_PLY_UV_NAMES = (("texture_u", "texture_v"), ("u", "v"), ("s", "t"))
+
+
 def _read_ply_mesh(path: str):
-    """(vertices, faces, colors or None) of a .ply file; load_ply_mesh and load_ply_colored_mesh."""
+    """((vertices, faces, colors or None), uv [F, 3, 2] or None, texture file or None) of a .ply file; load_ply_mesh,
+    load_ply_colored_mesh and load_ply_textured_mesh."""
     with open(path, "rb") as f:
         head = b""
         while not head.rstrip().endswith(b"end_header"):
@@ -357,10 +442,13 @@ def _read_ply_mesh(path: str):
         if not lines or lines[0] != "ply":
             raise ValueError("%s: not a PLY file" % path)
         fmt, elems = None, []                   # elems: [name, count, [(property name, type) | (name, count type, item type)]]
+        texture_file = None
         for ln in lines[1:]:
             tok = ln.split()
             if tok[0] == "format":
                 fmt = tok[1]
+            elif tok[0] == "comment" and len(tok) >= 3 and tok[1] == "TextureFile" and texture_file is None:
+                texture_file = os.path.join(os.path.dirname(os.path.abspath(path)), ln.split(None, 2)[2])
             elif tok[0] == "element":
                 elems.append([tok[1], int(tok[2]), []])
             elif tok[0] == "property" and elems:
@@ -373,18 +461,22 @@ def _read_ply_mesh(path: str):
             raise ValueError("%s: unknown PLY format %s" % (path, fmt))
         end = ">" if fmt == "binary_big_endian" else "<"
         vertices, faces, colors = None, None, None
+        vertex_uv, corner_uv = None, None           # [n, 2] of the vertex element, [F, 3, 2] of the face element's texcoord
         rgb = ("red", "green", "blue")
         for name, count, props in elems:
             has_list = any(len(p_) == 3 for p_ in props)
             names = [p_[0] for p_ in props]
+            uvn = None
             if name == "vertex":
                 if has_list or not all(a in names for a in ("x", "y", "z")):
                     raise ValueError("%s: the vertex element needs scalar x, y, z" % path)
-            want = None
+                uvn = next((pair for pair in _PLY_UV_NAMES if pair[0] in names and pair[1] in names), None)
+            want, want_tc = None, None
             if name == "face":
                 want = next((i for i, p_ in enumerate(props) if len(p_) == 3 and p_[0] in ("vertex_indices", "vertex_index")), None)
                 if want is None:
                     raise ValueError("%s: face element without a vertex_indices list" % path)
+                want_tc = next((i for i, p_ in enumerate(props) if len(p_) == 3 and p_[0] == "texcoord"), None)
             rows = []
             if fmt != "ascii" and not has_list:
                 dt = np.dtype([(nm, end + t) for nm, t in props])
@@ -396,6 +488,8 @@ def _read_ply_mesh(path: str):
                     vertices = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float64)
                     if all(a in names for a in rgb):
                         colors = _ply_colors([v[a] for a in rgb], [dict(props)[a] for a in rgb])
+                    if uvn:
+                        vertex_uv = np.stack([v[uvn[0]], v[uvn[1]]], axis=1).astype(np.float64)
                 continue
             for _ in range(count):
                 vals = []
@@ -432,15 +526,31 @@ def _read_ply_mesh(path: str):
                 if all(a in names for a in rgb):
                     cx = [names.index(a) for a in rgb]
                     colors = _ply_colors([[r[i][0] for r in rows] for i in cx], [props[i][1] for i in cx])
+                if uvn:
+                    ux, vx = names.index(uvn[0]), names.index(uvn[1])
+                    vertex_uv = np.array([[r[ux][0], r[vx][0]] for r in rows], dtype=np.float64).reshape(count, 2)
             elif name == "face":
-                tris = []
+                tris, corners = [], []
                 for r in rows:
                     poly = [int(i) for i in r[want]]
                     tris.extend((poly[0], poly[k], poly[k + 1]) for k in range(1, len(poly) - 1))
+                    if want_tc is not None and len(poly) >= 3:
+                        tc = r[want_tc]
+                        if len(tc) != 2 * len(poly):
+                            raise ValueError("%s: a texcoord list of %d values on a face of %d vertices" % (path, len(tc), len(poly)))
+                        at = lambda k: (float(tc[2 * k]), float(tc[2 * k + 1]))
+                        corners.extend((at(0), at(k), at(k + 1)) for k in range(1, len(poly) - 1))
                 faces = np.array(tris, dtype=np.int32).reshape(-1, 3)
+                if want_tc is not None:
+                    corner_uv = np.array(corners, dtype=np.float64).reshape(-1, 3, 2)
         if vertices is None or faces is None:
             raise ValueError("%s: needs a vertex and a face element" % path)
-        return vertices, faces, colors
+        uv = corner_uv
+        if uv is None and vertex_uv is not None:
+            if len(faces) and (faces.min() < 0 or faces.max() >= len(vertex_uv)):
+                raise ValueError("%s: a face index lies outside [0, %d)" % (path, len(vertex_uv)))
+            uv = np.ascontiguousarray(vertex_uv[faces])
+        return (vertices, faces, colors), uv, texture_file
 
 
 BOP_VSD_TAUS = tuple(0.05 * k for k in range(1, 11))        # misalignment tolerances, fractions of the object diameter
@@ -514,7 +624,7 @@ def _image_index(image_index, images, P):
 
 
 def render_color(poses, vertices, faces, colors, K, size, device=None, image_index=None, images=None, pixel_center=0.0,
-                 near=0.01, ambient=0.5, light=(0.0, 0.0, 0.0), into=None):
+                 near=0.01, ambient=0.5, light=(0.0, 0.0, 0.0), into=None, uv=None, texture=None, mip=True):
     """Shaded colour images of a triangle mesh with per-vertex colours: ``(color [I, H, W, 3] uint8, depth [I, H, W]
     float32, skipped [P] int32)``.  Geometry, coverage and depth are ``render_depth``'s; ``colors`` [n, 3] uint8 come
     back in the channel order they were given in.  ``image_index`` [P] (non-decreasing, values in [0, ``images``)) draws
@@ -525,10 +635,22 @@ def render_color(poses, vertices, faces, colors, K, size, device=None, image_ind
     colour 0, depth 0.  ``into=(color, depth)``: accumulate over an earlier result (of any mesh); the arrays are not
     modified, the updated copies are returned.  An earlier pixel gives way to a nearer fragment and also to one of
     EXACTLY its depth (same float32 bits): the later call wins such a tie.  ``device=None``: the host twin; a torch device: bp_render_color on it.
-    The two are byte-identical."""
+    The two are byte-identical.
+    ``texture`` (a [Ht, Wt, 3] uint8 image, or its pyramid from ``texture_mips`` built for the same ``device``) with
+    ``uv`` [F, 3, 2] (load_ply_textured_mesh) takes the place of the vertex colours, which are then not read (``colors``
+    may be None): the fragment's (u, v) is the corner coordinates mixed by the same weights, the level comes from the
+    footprint of one pixel step in level-0 texels (comparisons against powers of four; ``mip=False``: level 0 whatever
+    the footprint), the sample is one level's bilinear mix in 8-bit fixed point with wrap mode repeat, and it is lit
+    and rounded as a mixed vertex colour is.  Texels come back in the channel order given.  ``into=``
+    works across textured and vertex-coloured calls in either order.  Without ``texture`` the call is what it was."""
     from . import _lib
     poses = _poses34(poses)
     vertices, faces = _mesh_args(vertices, faces)
+    if texture is not None:
+        return _render_color_textured(poses, vertices, faces, colors, K, size, device, image_index, images, pixel_center, near,
+                                      ambient, light, into, uv, texture, mip)
+    if uv is not None:
+        raise ValueError("uv without a texture")
     colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
     if len(colors) != len(vertices):
         raise ValueError("colors needs one row per vertex")
@@ -569,6 +691,64 @@ def render_color(poses, vertices, faces, colors, K, size, device=None, image_ind
                                               float(pixel_center), float(near), float(ambient), _lib.ptr(lt), acc,
                                               _lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_skipped),
                                               torch.cuda.current_stream(dev).cuda_stream))
+        return d_color.cpu().numpy(), d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+
+
+def _render_color_textured(poses, vertices, faces, colors, K, size, device, image_index, images, pixel_center, near, ambient,
+                           light, into, uv, texture, mip):
+    """render_color's textured branch (poses, vertices and faces already in their call form)."""
+    from . import _lib
+    if uv is None:
+        raise ValueError("a texture needs uv [F, 3, 2]")
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.shape != (len(faces), 3, 2):
+        raise ValueError("uv must have the shape [F, 3, 2] = [%d, 3, 2], got %s" % (len(faces), list(uv.shape)))
+    mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, device)
+    on_device = not isinstance(mips.data, np.ndarray)
+    if on_device != (device is not None):
+        raise ValueError("the pyramid was built for %s, the call is for %s: build it with texture_mips(texture, device)" %
+                         (("device %s" % mips.device) if on_device else "the host", device if device is not None else "the host"))
+    levels = mips.levels if mip else 1
+    H, W = int(size[0]), int(size[1])
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
+    P = len(poses)
+    index, I = _image_index(image_index, images, P)
+    if into is not None:
+        color = np.array(into[0], dtype=np.uint8, order="C")
+        depth = np.array(into[1], dtype=np.float32, order="C")
+        I = len(depth) if images is None else I
+        if color.shape != (I, H, W, 3) or depth.shape != (I, H, W):
+            raise ValueError("into=(color, depth) must have the shapes [I, H, W, 3] and [I, H, W]")
+    else:
+        color, depth = np.zeros((I, H, W, 3), np.uint8), np.zeros((I, H, W), np.float32)
+    if P == 0:
+        return color, depth, np.zeros(0, np.int32)
+    acc = int(into is not None)
+    if device is None:
+        skipped = np.empty(P, np.int32)
+        _lib.check(_lib.lib().bp_render_color_textured_host(
+            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), None, _lib.ptr(uv),
+            _lib.ptr(mips.data), mips.Wt, mips.Ht, levels, _lib.ptr(index), I, _lib.ptr(Kf), H, W, float(pixel_center),
+            float(near), float(ambient), _lib.ptr(lt), acc, _lib.ptr(color), _lib.ptr(depth), _lib.ptr(skipped)))
+        return color, depth, skipped
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    if mips.data.device != dev and not (dev.index is None and mips.data.device.type == dev.type):
+        raise ValueError("the pyramid lives on %s, the call is for %s" % (mips.data.device, dev))
+    with torch.cuda.device(mips.data.device):
+        dev = mips.data.device
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_uv = torch.from_numpy(uv).to(dev)
+        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
+        d_color, d_depth = torch.from_numpy(color).to(dev), torch.from_numpy(depth).to(dev)
+        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().bp_render_color_textured(
+            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), None, _lib.ptr(d_uv), _lib.ptr(mips.data), mips.Wt,
+            mips.Ht, levels, _lib.ptr(d_poses), P, _lib.ptr(index), I, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
+            float(ambient), _lib.ptr(lt), acc, _lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_skipped),
+            torch.cuda.current_stream(dev).cuda_stream))
         return d_color.cpu().numpy(), d_depth.cpu().numpy(), d_skipped.cpu().numpy()
 
 

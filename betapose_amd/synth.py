@@ -479,6 +479,29 @@ def _mesh3(mesh):
     return v, f, c
 
 
+def _mesh_texture(mesh, device):
+    """render_color's texture arguments of a mesh tuple: {} for (vertices, faces[, colours]) and for a longer tuple
+    without uv or texture; for (vertices, faces, colours, uv, texture) ``uv`` [F, 3, 2] and the pyramid of ``texture``
+    [Ht, Wt, 3] uint8 RGB, swapped to BGR as the colours are and built ONCE, for ``device``."""
+    if len(mesh) < 5 or mesh[3] is None or mesh[4] is None:
+        return {}
+    from . import metrics
+    if isinstance(mesh[4], metrics.TextureMips):     # textured_mesh's: swapped and built already
+        return dict(uv=np.ascontiguousarray(mesh[3], dtype=np.float64), texture=mesh[4])
+    tex = np.asarray(mesh[4])
+    if tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] != 3:
+        raise ValueError("a mesh's texture is a uint8 image [Ht, Wt, 3] (RGB)")
+    return dict(uv=np.ascontiguousarray(mesh[3], dtype=np.float64),
+                texture=metrics.texture_mips(np.ascontiguousarray(tex[:, :, ::-1]), device))
+
+
+def textured_mesh(mesh, device=None):
+    """``mesh`` with its texture image replaced by the pyramid _mesh_texture would build from it, for ``device``: what a
+    caller that synthesises chunk after chunk (synthesize.py) hands over, so that the pyramid is built once."""
+    tex = _mesh_texture(mesh, device)
+    return tuple(mesh) if not tex else tuple(mesh[:3]) + (tex["uv"], tex["texture"])
+
+
 DEFAULT_CAMERA = dict(feather=1, blur=(0, 2), gain=(224, 288), offset=(-12, 12), sigma=(0, 768))
 DEFAULT_SENSOR = dict(noise_k=512, edge_counts=30, hole_p=128)
 
@@ -516,7 +539,10 @@ def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=
                       max_redraws=4, backgrounds=None, camera=None, sensor=None, depth_scale=0.001, first_scene=0,
                       ambient=0.5, light=(0.0, 0.0, 0.0), device=None):
     """``n`` training scenes of the mesh ``target`` = (vertices, faces[, colours RGB uint8]) in metres, partly hidden
-    by one instance of each mesh of ``occluders``: a dict of arrays with one row per scene --
+    by one instance of each mesh of ``occluders``: a dict of arrays with one row per scene.  A mesh may also be
+    (vertices, faces, colours, uv, texture) with ``uv`` [F, 3, 2] and ``texture`` [Ht, Wt, 3] uint8 RGB
+    (metrics.load_ply_textured_mesh, load_texture): it is rendered textured (render_color's ``uv``, ``texture``; the
+    pyramid is built once per mesh); only the frames' colours change with it --
 
       ``frames`` [n, H, W, 3] uint8 BGR, ``depth`` [n, H, W] uint16 (counts of ``depth_scale`` metres),
       ``obj_ids`` [1 + occluders] (the target first; default 1, 2, ...), ``poses`` [n, objects, 3, 4] and ``t_mm``
@@ -537,6 +563,7 @@ def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
     tv, tf, tc = _mesh3(target)
     occ = [_mesh3(m) for m in occluders]
+    ttex, otex = _mesh_texture(target, device), [_mesh_texture(m, device) for m in occluders]
     ids = np.arange(1, 2 + len(occ)) if obj_ids is None else np.asarray(obj_ids, dtype=np.int64).reshape(-1)
     if len(ids) != 1 + len(occ):
         raise ValueError("obj_ids names the target and every occluder")
@@ -553,7 +580,7 @@ def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=
         return p, t_mm
 
     tposes, t_mm_t = millimetres(sample_poses(n, K, (H, W), radius, seed, elevation, distance, inplane, margin, first_scene))
-    color_t, depth_t, _ = metrics.render_color(tposes, tv, tf, bgr(tc), K, (H, W), device, ambient=ambient, light=light)
+    color_t, depth_t, _ = metrics.render_color(tposes, tv, tf, bgr(tc), K, (H, W), device, ambient=ambient, light=light, **ttex)
     md = metrics.render_depth(tposes, tv, tf, K, (H, W), device)[0]
 
     def sensed(depth, scenes):               # sensor depth of the listed scenes (sorted), run by run of scene numbers
@@ -581,7 +608,8 @@ def synthesize_scenes(target, occluders, K, size, n, seed, obj_ids=None, radius=
                                                               lateral, first_scene + s, attempt) for s in pending]))
         c, d = color_t[pending], depth_t[pending]
         for j, (ov, of, oc) in enumerate(occ):
-            c, d, _ = metrics.render_color(p[:, j], ov, of, bgr(oc), K, (H, W), device, ambient=ambient, light=light, into=(c, d))
+            c, d, _ = metrics.render_color(p[:, j], ov, of, bgr(oc), K, (H, W), device, ambient=ambient, light=light, into=(c, d),
+                                           **otex[j])
         _, vf = visibility(pending, sensed(d, pending))
         keep = vf >= min_visib
         for k, s in enumerate(pending):
@@ -667,7 +695,8 @@ def below_visibility(stats, min_visib):
 def synthesize_multi(meshes, K, size, n, seed, obj_ids=None, min_visib=0.3, elevation=(10.0, 80.0), distance=None,
                      inplane=(-30.0, 30.0), backgrounds=None, camera=None, sensor=None, depth_scale=0.001, first_scene=0,
                      ambient=0.5, light=(0.0, 0.0, 0.0), device=None):
-    """``n`` training scenes of the ``J`` meshes ``meshes`` = [(vertices, faces[, colours RGB uint8]), ...] in metres,
+    """``n`` training scenes of the ``J`` meshes ``meshes`` = [(vertices, faces[, colours RGB uint8]), ...] in metres
+    (or (vertices, faces, colours, uv, texture), as synthesize_scenes takes them),
     EVERY one of them a target: synthesize_scenes' dict with one row per scene and per-object shapes --
 
       ``frames`` [n, H, W, 3] uint8 BGR, ``depth`` [n, H, W] uint16, ``obj_ids`` [J] (default 1, 2, ...), ``poses``
@@ -695,6 +724,7 @@ def synthesize_multi(meshes, K, size, n, seed, obj_ids=None, min_visib=0.3, elev
     n = int(n)
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
     ms = [_mesh3(m) for m in meshes]
+    texs = [_mesh_texture(m, device) for m in meshes]
     J = len(ms)
     if not 1 <= J <= MAX_INSTANCES:
         raise ValueError("synthesize_multi takes 1 .. %d meshes" % MAX_INSTANCES)
@@ -731,7 +761,7 @@ def synthesize_multi(meshes, K, size, n, seed, obj_ids=None, min_visib=0.3, elev
             if len(rows):
                 color, zbuf, _ = metrics.render_color(poses[rows, j], v, f, np.ascontiguousarray(col[:, ::-1]), K, (H, W), device,
                                                       image_index=rows.astype(np.int32), images=c, ambient=ambient, light=light,
-                                                      into=(color, zbuf))
+                                                      into=(color, zbuf), **texs[j])
         if not np.array_equal(zbuf.view(np.int32), depth.view(np.int32)):
             raise RuntimeError("the colour chain's depth differs from instance_masks': the tie rule is broken")
         if bank is None:

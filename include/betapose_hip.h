@@ -44,7 +44,7 @@
  *   bp_pose_errors_sym     no reference counterpart: the BOP errors MSSD and MSPD over an object's symmetry set
  *   bp_render_depth, bp_render_depth_host
  *                          Renderer.render's depth image (OpenGL through vispy)   utils/renderer.py
- *   bp_render_color, bp_draw_boxes, bp_overlay (and their _host twins)
+ *   bp_render_color, bp_render_color_textured, bp_texture_mips, bp_draw_boxes, bp_overlay (and their _host twins)
  *                          Renderer.draw_model / draw_boundingbox / finish and      utils/renderer.py:137-181
  *                          draw_detections_3D's paste over the frame                utils/utils.py:269-301
  *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
@@ -338,6 +338,40 @@ int bp_render_color_host(const double* poses, int P, const double* vertices, int
                          const unsigned char* colors, const int* image_index, int I, const double* K, int H, int W,
                          double pixel_center, double near_z, double ambient, const double* light, int accumulate,
                          unsigned char* color, float* depth, int* skipped);
+/* A texture in the place of the vertex colours.  The pyramid: level 0 is the image [Ht][Wt][3] uint8
+ * (row 0 the top), level l + 1 has ceil(w / 2) x ceil(h / 2) texels, each (a + b + c + d + 2) >> 2 per channel of its
+ * 2 x 2 block with the partner index clamped where a dimension is odd, down to 1 x 1: 1 + ceil(log2(max(Wt, Ht)))
+ * levels, of which a call builds or reads the first `levels`.  A texel is one dword, channel k in byte k; the levels
+ * follow each other.  Wt, Ht <= 8192.  bp_texture_mips_bytes: the bytes of the first `levels` levels, 0 for sizes or
+ * levels out of range.  bp_texture_mips is enqueued on `stream` and does not synchronise it; bp_texture_mips_host is the
+ * same on host memory, byte-identical. */
+size_t bp_texture_mips_bytes(int Wt, int Ht, int levels);
+int bp_texture_mips(const unsigned char* d_texture, int Wt, int Ht, int levels, uint32_t* d_mips, void* stream);
+int bp_texture_mips_host(const unsigned char* texture, int Wt, int Ht, int levels, uint32_t* mips);
+/* bp_render_color with a texture: every argument of bp_render_color means what it means there, and visibility, depth,
+ * the weights wa, wb, wc and light_w of the winning fragment are its own.  d_uv [F][3][2] f64: (u, v) of every face
+ * corner, v upwards (v = 1 is the image's top row); d_mips, Wt, Ht: a pyramid of bp_texture_mips, of which the first
+ * `levels` levels are read (1: the image alone, no mip-mapping).  The fragment's (u, v) is the corner coordinates mixed
+ * by wa, wb, wc.  Its level: with (u, v) taken by unclamped barycentrics where the rays of pixels (x, y), (x + 1, y) and
+ * (x, y + 1) meet the face's plane, rx and ry are the squared lengths of the two differences of (u Wt, v Ht), and
+ * level = the number of l < levels - 1 with rx > 4^l or ry > 4^l (a comparison with a NaN is false).  The sample: a
+ * coordinate that is NaN becomes 0, its magnitude is limited to 2^30, it wraps as u - floor(u); s = u w - 0.5,
+ * t = (1 - v) h - 0.5 in the level's size; floor(256 s), floor(256 t) give the texel and an 8-bit fraction per axis; the
+ * four taps are wrapped modulo the level's size before they are loaded; a channel is ((c00 (256 - fx) + c10 fx)
+ * (256 - fy) + (c01 (256 - fx) + c11 fx) fy + 32768) >> 16 and takes the place of the mixed vertex colour:
+ * min(255, floor(light_w c + 0.5)).  d_uv == NULL: d_colors is used and the call is bp_render_color; otherwise d_colors
+ * is not read and may be NULL.  Accumulation works across the two kinds of call in either order.  The _host twin is the
+ * same on host memory, byte-identical.  bp_render_color_textured synchronises `stream`. */
+int bp_render_color_textured(const double* d_model, int n, const int* d_faces, int F, const unsigned char* d_colors,
+                             const double* d_uv, const uint32_t* d_mips, int Wt, int Ht, int levels, const double* d_poses,
+                             int P, const int* image_index, int I, const double* K, int H, int W, double pixel_center,
+                             double near_z, double ambient, const double* light, int accumulate, unsigned char* d_color,
+                             float* d_depth, int* d_skipped, void* stream);
+int bp_render_color_textured_host(const double* poses, int P, const double* vertices, int n, const int* faces, int F,
+                                  const unsigned char* colors, const double* uv, const uint32_t* mips, int Wt, int Ht,
+                                  int levels, const int* image_index, int I, const double* K, int H, int W,
+                                  double pixel_center, double near_z, double ambient, const double* light, int accumulate,
+                                  unsigned char* color, float* depth, int* skipped);
 /* The 12 edges of a 3-D bounding box at P poses, drawn one pixel wide over d_color [I][H][W][3] uint8 without a depth
  * test (Renderer.draw_boundingbox, utils/renderer.py).  d_corners [8][3] f64 object frame in the order of
  * Model3D._compute_bbox (x outermost, then z, then y, min before max), d_corner_colors [8][3] uint8; image_index, I,

@@ -3,11 +3,13 @@
 
     python synthesize.py --model obj_01.ply [--occluders a.ply,b.ply] --obj_id N --frames N --out TREE/
                          [--size 480x640] [--camera fx,fy,cx,cy] [--backgrounds DIR] [--min_visib .3] [--seed 0]
-                         [--device cuda:0] [--training_set DIR]
+                         [--device cuda:0] [--training_set DIR] [--no_texture]
     python synthesize.py --models a.ply,b.ply,... --obj_ids 1,5,6 --frames N --out TREE/ [--seq N] [--class_map 1:0,5:1,6:2]
                          [--label_box full|visible] [--detector_set DIR] [--train_split N] [the options above]
 
-The model (and the occluders) are SIXD model files: millimetres, per-vertex colours where they have them.  The object is
+The model (and the occluders) are SIXD model files: millimetres, per-vertex colours where they have them.  A file with
+texture coordinates (``texture_u`` / ``texture_v`` per vertex or a face ``texcoord`` list) and a ``comment TextureFile
+NAME`` is rendered with that PNG, found beside the PLY; --no_texture ignores it.  The object is
 rendered at seeded random poses, partly hidden by one instance of every occluder, pasted over a procedural background
 (or windows of the PNG photographs under --backgrounds) through a camera model, and written with a simulated depth
 sensor's images as sequence ``obj_id`` of the tree ``--out`` -- the tree ``annotate.py --sixd_base TREE --visibility
@@ -59,6 +61,7 @@ def build_parser():
     p.add_argument("--min_visib", default=0.3, type=float, help="smallest visible fraction of the object")
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--device", default=None, type=str, help="torch device of the kernels (default: the host twins)")
+    p.add_argument("--no_texture", action="store_true", help="ignore a mesh's TextureFile: vertex colours only")
     p.add_argument("--training_set", default=None, type=str, help="also export the loaders' layout from <DIR>/annot/<obj_id>")
     return p
 
@@ -88,6 +91,22 @@ def load_bank(folder):
     return np.stack(images)
 
 
+def load_meshes(ids, paths, args):
+    """({obj_id: (vertices, faces, colours)} in millimetres as the tree stores them, the meshes in metres as the
+    synthesiser takes them: with uv and the texture's pyramid where the PLY names a texture and --no_texture is off)."""
+    meshes, metres = {}, []
+    for oid, path in zip(ids, paths):
+        v, f, c, uv, texture_file = metrics.load_ply_textured_mesh(path)
+        meshes[oid] = (v, f, c)
+        mesh = (v * 0.001, f, c)
+        if texture_file is not None and uv is not None and not args.no_texture:
+            if not os.path.isfile(texture_file):
+                raise SystemExit("%s names the texture %s, which does not exist (--no_texture renders without it)" % (path, texture_file))
+            mesh = synth.textured_mesh(mesh + (uv, metrics.load_texture(texture_file)), args.device)
+        metres.append(mesh)
+    return meshes, metres
+
+
 def main_multi(args, K, size):
     """--models: scenes of several targets, their tree and (--detector_set) the shared detector's training set."""
     from betapose_amd import annotate as A
@@ -98,8 +117,7 @@ def main_multi(args, K, size):
     if len(ids) != len(paths) or len(set(ids)) != len(ids):
         raise SystemExit("--obj_ids must name each of the %d meshes of --models once" % len(paths))
     seq = ids[0] if args.seq is None else args.seq
-    meshes = {oid: metrics.load_ply_colored_mesh(p) for oid, p in zip(ids, paths)}         # millimetres
-    metres = [(meshes[oid][0] * 0.001, meshes[oid][1], meshes[oid][2]) for oid in ids]
+    meshes, metres = load_meshes(ids, paths, args)
     bank = load_bank(args.backgrounds) if args.backgrounds else None
     kept = np.zeros(len(ids), np.int64)
     fract = []
@@ -135,8 +153,7 @@ def main(argv=None):
         return main_multi(args, K, (H, W))
     paths = [args.model] + [p for p in args.occluders.split(",") if p]
     ids = [args.obj_id] + [i for i in range(1, len(paths) + 1) if i != args.obj_id][:len(paths) - 1]
-    meshes = {oid: metrics.load_ply_colored_mesh(p) for oid, p in zip(ids, paths)}         # millimetres
-    metres = [(meshes[oid][0] * 0.001, meshes[oid][1], meshes[oid][2]) for oid in ids]
+    meshes, metres = load_meshes(ids, paths, args)
     bank = load_bank(args.backgrounds) if args.backgrounds else None
     redraws = dropped = 0
     fract = []
