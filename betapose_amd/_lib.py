@@ -148,6 +148,10 @@ PROTOTYPES = {
     "bp_overlay_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                 C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "bp_image_gradients": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "bp_image_gradients_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "bp_gradient_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "bp_gradient_scores_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "bp_annotate_keypoints": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, C.c_int,
                                         vp, C.c_double, C.c_double, vp, vp, vp, vp]),
     "bp_annotate_keypoints_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp,

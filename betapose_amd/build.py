@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbetapose_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_fused.hip", "conv_pl.hip", "conv_s1.hip", "conv_p3.hip", "aux_kernels.hip", "yolo_tail.hip", "pose_metrics.hip", "pose_metrics_sym.hip", "raster.hip", "raster_color.hip", "raster_texture.hip", "vsd.hip", "icp.hip", "annotate.hip", "kpd_sample.hip", "yolo_train.hip", "yolo_map.hip", "darknet_train.hip", "kpd_train.hip", "designate.hip", "synth.hip", "synth_inst.hip", "pose_tail.hip", "pose_tail_cands.hip", "pose_tail_inst.hip", "pnp_ransac.hip", "engine.cpp", "conv_plan.cpp", "host_post.cpp", "raster_host.cpp", "raster_color_host.cpp", "raster_texture_host.cpp", "icp_host.cpp", "annotate_host.cpp", "kpd_sample_host.cpp", "yolo_train_host.cpp", "yolo_map_host.cpp", "darknet_train_host.cpp", "kpd_train_host.cpp", "designate_host.cpp", "synth_host.cpp", "synth_inst_host.cpp", "frame_io.cpp", "jpeg_bmp.cpp", "c_api.cpp", "c_api_conv.cpp", "c_api_pose.cpp", "c_api_eval.cpp", "c_api_train.cpp", "c_api_kpd_train.cpp", "c_api_synth.cpp", "c_api_io.cpp", "eval_device.cpp", "darknet_compat.cpp"]
-HEADERS = ["bp_common.h", "c_api_util.h", "engine.h", "conv_plan.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "raster_walk.inc", "raster_color_math.inc", "raster_texture_math.inc", "icp.h", "icp_math.inc", "annotate.h", "annotate_math.inc", "kpd_sample.h", "kpd_sample_math.inc", "yolo_train.h", "yolo_train_math.inc", "yolo_map.h", "yolo_map_math.inc", "darknet_train.h", "darknet_train_math.inc", "kpd_train.h", "kpd_train_math.inc", "designate.h", "designate_math.inc", "synth.h", "synth_math.inc", "synth_inst_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
+SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_fused.hip", "conv_pl.hip", "conv_s1.hip", "conv_p3.hip", "aux_kernels.hip", "yolo_tail.hip", "pose_metrics.hip", "pose_metrics_sym.hip", "raster.hip", "raster_color.hip", "raster_texture.hip", "vsd.hip", "verify.hip", "icp.hip", "annotate.hip", "kpd_sample.hip", "yolo_train.hip", "yolo_map.hip", "darknet_train.hip", "kpd_train.hip", "designate.hip", "synth.hip", "synth_inst.hip", "pose_tail.hip", "pose_tail_cands.hip", "pose_tail_inst.hip", "pnp_ransac.hip", "engine.cpp", "conv_plan.cpp", "host_post.cpp", "raster_host.cpp", "raster_color_host.cpp", "raster_texture_host.cpp", "verify_host.cpp", "icp_host.cpp", "annotate_host.cpp", "kpd_sample_host.cpp", "yolo_train_host.cpp", "yolo_map_host.cpp", "darknet_train_host.cpp", "kpd_train_host.cpp", "designate_host.cpp", "synth_host.cpp", "synth_inst_host.cpp", "frame_io.cpp", "jpeg_bmp.cpp", "c_api.cpp", "c_api_conv.cpp", "c_api_pose.cpp", "c_api_eval.cpp", "c_api_train.cpp", "c_api_kpd_train.cpp", "c_api_synth.cpp", "c_api_io.cpp", "eval_device.cpp", "darknet_compat.cpp"]
+HEADERS = ["bp_common.h", "c_api_util.h", "engine.h", "conv_plan.h", "frame_chain.h", "frame_io.h", "conv_tail.inc", "pnp_wave.inc", "pnp_math.inc", "pose_decode.inc", "pose_tail.h", "raster.h", "raster_math.inc", "raster_walk.inc", "raster_color_math.inc", "raster_texture_math.inc", "verify.h", "verify_math.inc", "icp.h", "icp_math.inc", "annotate.h", "annotate_math.inc", "kpd_sample.h", "kpd_sample_math.inc", "yolo_train.h", "yolo_train_math.inc", "yolo_map.h", "yolo_map_math.inc", "darknet_train.h", "darknet_train_math.inc", "kpd_train.h", "kpd_train_math.inc", "designate.h", "designate_math.inc", "synth.h", "synth_math.inc", "synth_inst_math.inc", "conv_dev.h", os.path.join("..", "..", "include", "betapose_hip.h"),
            os.path.join("..", "..", "include", "yolo_v2_class_compat.h")]
 # measured-and-superseded kernels (round-1/2 experiments) live in csrc/experimental/ and are compiled only into
 # libbetapose_hip_exp.so (--experimental); the product library has no input under that directory
@@ -25,9 +25,9 @@ ARCH = "gfx950"
 LAST_ACTION = None      # "compiled" | "reused": what the last build() of the product library did (__graft_entry__.build prints it)
 # Host launch stubs every HIP object must export.  hipcc has been seen to drop a kernel's host stub SILENTLY (the object
 # links, the launch then fails at run time) -- DESIGN.md §3.1d -- so the build counts them.
-MIN_STUBS = {"conv_s1.hip": 1, "conv_p3.hip": 39, "conv_igemm.hip": 14, "conv_halo.hip": 13, "conv_fused.hip": 12, "conv_pl.hip": 12, "aux_kernels.hip": 16, "yolo_tail.hip": 7, "pose_metrics.hip": 2, "pose_metrics_sym.hip": 4, "raster.hip": 3, "raster_color.hip": 6, "raster_texture.hip": 3, "vsd.hip": 2, "icp.hip": 4, "annotate.hip": 7, "kpd_sample.hip": 4, "yolo_train.hip": 6, "yolo_map.hip": 9, "darknet_train.hip": 5, "kpd_train.hip": 17, "designate.hip": 5, "synth.hip": 4, "synth_inst.hip": 4, "pose_tail.hip": 3, "pose_tail_cands.hip": 1, "pose_tail_inst.hip": 1, "pnp_ransac.hip": 2}
+MIN_STUBS = {"conv_s1.hip": 1, "conv_p3.hip": 39, "conv_igemm.hip": 14, "conv_halo.hip": 13, "conv_fused.hip": 12, "conv_pl.hip": 12, "aux_kernels.hip": 16, "yolo_tail.hip": 7, "pose_metrics.hip": 2, "pose_metrics_sym.hip": 4, "raster.hip": 3, "raster_color.hip": 6, "raster_texture.hip": 3, "vsd.hip": 2, "verify.hip": 6, "icp.hip": 4, "annotate.hip": 7, "kpd_sample.hip": 4, "yolo_train.hip": 6, "yolo_map.hip": 9, "darknet_train.hip": 5, "kpd_train.hip": 17, "designate.hip": 5, "synth.hip": 4, "synth_inst.hip": 4, "pose_tail.hip": 3, "pose_tail_cands.hip": 1, "pose_tail_inst.hip": 1, "pnp_ransac.hip": 2}
 MIN_STUBS_EXP = {"conv_s1.hip": 1, "conv_p3.hip": 39, "experimental/kernels_unity.hip": 26, "conv_fused.hip": 12, "conv_pl.hip": 12, "experimental/conv_w64.hip": 8,
-                 "experimental/conv_kg.hip": 3, "experimental/conv_rd.hip": 2, "aux_kernels.hip": 19, "yolo_tail.hip": 7, "pose_metrics.hip": 2, "pose_metrics_sym.hip": 4, "raster.hip": 3, "raster_color.hip": 6, "raster_texture.hip": 3, "vsd.hip": 2, "icp.hip": 4, "annotate.hip": 7, "kpd_sample.hip": 4, "yolo_train.hip": 6, "yolo_map.hip": 9, "darknet_train.hip": 5, "kpd_train.hip": 17, "designate.hip": 5, "synth.hip": 4, "synth_inst.hip": 4, "pose_tail.hip": 3, "pose_tail_cands.hip": 1, "pose_tail_inst.hip": 1, "pnp_ransac.hip": 2}
+                 "experimental/conv_kg.hip": 3, "experimental/conv_rd.hip": 2, "aux_kernels.hip": 19, "yolo_tail.hip": 7, "pose_metrics.hip": 2, "pose_metrics_sym.hip": 4, "raster.hip": 3, "raster_color.hip": 6, "raster_texture.hip": 3, "vsd.hip": 2, "verify.hip": 6, "icp.hip": 4, "annotate.hip": 7, "kpd_sample.hip": 4, "yolo_train.hip": 6, "yolo_map.hip": 9, "darknet_train.hip": 5, "kpd_train.hip": 17, "designate.hip": 5, "synth.hip": 4, "synth_inst.hip": 4, "pose_tail.hip": 3, "pose_tail_cands.hip": 1, "pose_tail_inst.hip": 1, "pnp_ransac.hip": 2}
 
 
 def hipcc() -> str:

@@ -11,6 +11,7 @@
 #include "kpd_sample.h"
 #include "pose_tail.h"
 #include "raster.h"
+#include "verify.h"
 #include "yolo_map.h"
 #include "yolo_train.h"
 
@@ -213,6 +214,17 @@ static void designate_check_thin(int n, int keep) {
     BP_CHECK(keep >= 1, "keep must be positive");
 }
 
+// ---- pose verification (verify.hip / verify_host.cpp)
+static void verify_check_image(int H, int W, int red_channel) {
+    BP_CHECK(H >= 3 && W >= 3, "H and W must be at least 3 (the reflect-101 border of a 5-tap stencil)");
+    check_pixels(H, W);
+    BP_CHECK(red_channel == 0 || red_channel == 2, "red_channel must be 0 or 2");
+}
+static void verify_check_scores(int P, int T, int H, int W, int red_channel) {
+    BP_CHECK(P >= 0 && T > 0, "P must not be negative, T must be positive");
+    verify_check_image(H, W, red_channel);
+}
+
 extern "C" {
 
 int bp_pose_errors(const double* d_model, int n, const double* d_gt, const double* d_est, int P, const double* K, int want,
@@ -391,6 +403,53 @@ int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, cons
     BP_CHECK(d_frames && d_color && d_depth && d_out, "null argument");
     raster_check_overlay(I, H, W, alpha);
     bp::overlay(d_frames, d_color, d_depth, I, H, W, alpha, d_out, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_image_gradients_host(const unsigned char* images, int I, int H, int W, int red_channel, int min_sq, float* grad,
+                            float* mag) {
+    BP_TRY
+    BP_CHECK(I >= 0, "I must not be negative");
+    verify_check_image(H, W, red_channel);
+    if (I == 0) return 0;
+    BP_CHECK(images && grad, "null argument");
+    bp::image_gradients_host(images, I, H, W, red_channel, min_sq, grad, mag);
+    return 0;
+    BP_CATCH
+}
+
+int bp_image_gradients(const unsigned char* d_images, int I, int H, int W, int red_channel, int min_sq, float* d_grad,
+                       float* d_mag, void* stream) {
+    BP_TRY
+    BP_CHECK(I >= 0, "I must not be negative");
+    verify_check_image(H, W, red_channel);
+    if (I == 0) return 0;
+    BP_CHECK(d_images && d_grad, "null argument");
+    bp::launch_image_gradients(d_images, I, H, W, red_channel, min_sq, d_grad, d_mag, (hipStream_t)stream);
+    return 0;
+    BP_CATCH
+}
+
+int bp_gradient_scores_host(const unsigned char* renders, const float* scene_grad, const int* frame_index, int P, int T, int H,
+                            int W, int red_channel, int render_min_sq, uint64_t* sum, int* count, double* score) {
+    BP_TRY
+    verify_check_scores(P, T, H, W, red_channel);
+    if (P == 0) return 0;
+    BP_CHECK(renders && scene_grad && frame_index && sum && count && score, "null argument");
+    bp::gradient_scores_host(renders, scene_grad, frame_index, P, T, H, W, red_channel, render_min_sq, sum, count, score);
+    return 0;
+    BP_CATCH
+}
+
+int bp_gradient_scores(const unsigned char* d_renders, const float* d_scene_grad, const int* d_frame_index, int P, int T, int H,
+                       int W, int red_channel, int render_min_sq, uint64_t* d_sum, int* d_count, double* d_score, void* stream) {
+    BP_TRY
+    verify_check_scores(P, T, H, W, red_channel);
+    if (P == 0) return 0;
+    BP_CHECK(d_renders && d_scene_grad && d_frame_index && d_sum && d_count && d_score, "null argument");
+    bp::launch_gradient_scores(d_renders, d_scene_grad, d_frame_index, P, T, H, W, red_channel, render_min_sq,
+                               (unsigned long long*)d_sum, d_count, d_score, (hipStream_t)stream);
     return 0;
     BP_CATCH
 }

@@ -938,6 +938,218 @@ def pose_errors_vsd(gt_poses, est_poses, vertices, faces, K, depth_test_u16, tes
         return d_err.cpu().numpy(), d_counts.cpu().numpy()
 
 
+# ---- pose verification by gradient agreement (csrc/verify.hip, verify_host.cpp)
+VERIFY_SCENE_MIN_SQ = 25             # the reference's `mags < 5` on an 8-bit image: masked iff gx^2 + gy^2 <= 24
+VERIFY_RENDER_MIN_SQ = 1624975       # ... on a render that is float in [0, 1]: masked iff m2 < (4.999 * 255)^2 = 1624974.8
+VERIFY_STACK_BYTES = 256 << 20       # what verify_poses keeps a chunk's render stack (colour and depth) under
+
+
+def _verify_images(images, what):
+    images = np.ascontiguousarray(images)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise ValueError("%s must be a uint8 array [N, H, W, 3]" % what)
+    if images.shape[1] < 3 or images.shape[2] < 3:
+        raise ValueError("%s: H and W must be at least 3" % what)
+    return images if images.flags.writeable else images.copy()          # (torch.from_numpy wants a writable array)
+
+
+def _red(red_channel):
+    if red_channel not in (0, 2):
+        raise ValueError("red_channel must be 0 or 2")
+    return int(red_channel)
+
+
+def image_gradients(images, red_channel=0, min_sq=VERIFY_SCENE_MIN_SQ, device=None):
+    """Unit Sobel gradients of ``images`` [I, H, W, 3] uint8: ``(grads [I, H, W, 2] float32, mags [I, H, W] float32)``,
+    the reference's ``compute_grads_and_mags`` (utils/utils.py:576-585) for a stack of images.  Gray is
+    ``(4899 R + 9617 G + 1868 B + 8192) >> 14`` with byte ``red_channel`` (0 or 2) as R; the Sobel is ``ksize=5`` with a
+    reflect-101 border; a pixel is kept iff ``gx^2 + gy^2 >= min_sq`` (integers), its magnitude is
+    ``sqrt(gx^2 + gy^2) + 0.001`` and its gradient (gx, gy) over that; a masked pixel is all 0.
+    ``device=None``: the host twin; a torch device: bp_image_gradients on it.  The two are byte-identical."""
+    from . import _lib
+    images = _verify_images(images, "images")
+    I, H, W = images.shape[:3]
+    red = _red(red_channel)
+    if device is None:
+        grads, mags = np.zeros((I, H, W, 2), np.float32), np.zeros((I, H, W), np.float32)
+        _lib.check(_lib.lib().bp_image_gradients_host(_lib.ptr(images), I, H, W, red, int(min_sq), _lib.ptr(grads), _lib.ptr(mags)))
+        return grads, mags
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        d_images = torch.from_numpy(images).to(dev)
+        d_grads = torch.empty((I, H, W, 2), dtype=torch.float32, device=dev)
+        d_mags = torch.empty((I, H, W), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().bp_image_gradients(_lib.ptr(d_images), I, H, W, red, int(min_sq), _lib.ptr(d_grads), _lib.ptr(d_mags),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        return d_grads.cpu().numpy(), d_mags.cpu().numpy()
+
+
+def gradient_scores(renders, frames_or_grads, frame_index, red_channel=0, render_min_sq=VERIFY_RENDER_MIN_SQ,
+                    scene_min_sq=VERIFY_SCENE_MIN_SQ, device=None):
+    """The verification score of P renders: ``(scores [P] float64, sums [P] uint64, counts [P] int32)``.  ``renders``
+    [P, H, W, 3] uint8 (render_color's images); ``frames_or_grads`` either the frames [T, H, W, 3] uint8, whose gradients
+    are taken first (image_gradients, ``scene_min_sq``), or those gradients [T, H, W, 2] float32; render p is compared
+    with frame ``frame_index[p]``.  Over the render's kept pixels (``render_min_sq``) ``sums`` adds
+    ``lrint(|g_render . g_scene| 2^24)`` of the unit gradients, ``counts`` is their number and ``scores = sums / 2^24 /
+    (counts + 1)``: the reference's ``dot / (sum + 1)`` (utils/utils.py:602-604).  A frame index outside [0, T) gives
+    score NaN, sum 0 and count -1.  ``device`` as image_gradients; the integer sum makes host and device byte-identical
+    and the device's result the same from run to run."""
+    from . import _lib
+    renders = _verify_images(renders, "renders")
+    P, H, W = renders.shape[:3]
+    red = _red(red_channel)
+    idx = np.ascontiguousarray(frame_index, dtype=np.int32).reshape(-1)
+    if len(idx) != P:
+        raise ValueError("frame_index needs one entry per render")
+    scene = np.ascontiguousarray(frames_or_grads)
+    is_frames = scene.dtype == np.uint8
+    if is_frames:
+        scene = _verify_images(scene, "frames")
+    elif scene.dtype != np.float32 or scene.ndim != 4 or scene.shape[3] != 2:
+        raise ValueError("frames_or_grads must be uint8 [T, H, W, 3] or float32 [T, H, W, 2]")
+    if scene.shape[1:3] != (H, W):
+        raise ValueError("renders are %d x %d, the frames %d x %d" % (H, W, scene.shape[1], scene.shape[2]))
+    T = len(scene)
+    if T < 1:
+        raise ValueError("at least one frame")
+    scores, sums, counts = np.zeros(P, np.float64), np.zeros(P, np.uint64), np.zeros(P, np.int32)
+    if P == 0:
+        return scores, sums, counts
+    if device is None:
+        grads = image_gradients(scene, red, scene_min_sq)[0] if is_frames else scene
+        _lib.check(_lib.lib().bp_gradient_scores_host(_lib.ptr(renders), _lib.ptr(grads), _lib.ptr(idx), P, T, H, W, red,
+                                                      int(render_min_sq), _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(scores)))
+        return scores, sums, counts
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        d_grads = _device_scene_grads(scene, is_frames, red, scene_min_sq, dev)
+        d_renders, d_idx = torch.from_numpy(renders).to(dev), torch.from_numpy(idx).to(dev)
+        d_sums = torch.empty(P, dtype=torch.int64, device=dev)             # (the bits; the kernel writes uint64)
+        d_counts = torch.empty(P, dtype=torch.int32, device=dev)
+        d_scores = torch.empty(P, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().bp_gradient_scores(_lib.ptr(d_renders), _lib.ptr(d_grads), _lib.ptr(d_idx), P, T, H, W, red,
+                                                 int(render_min_sq), _lib.ptr(d_sums), _lib.ptr(d_counts), _lib.ptr(d_scores), s))
+        return d_scores.cpu().numpy(), d_sums.cpu().numpy().view(np.uint64), d_counts.cpu().numpy()
+
+
+def _device_scene_grads(scene, is_frames, red, scene_min_sq, dev):
+    """The scene's gradients [T, H, W, 2] as a tensor on ``dev`` (inside ``torch.cuda.device(dev)``)."""
+    import torch
+    from . import _lib
+    if not is_frames:
+        return torch.from_numpy(scene).to(dev)
+    T, H, W = scene.shape[:3]
+    d_frames = torch.from_numpy(scene).to(dev)
+    d_grads = torch.empty((T, H, W, 2), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().bp_image_gradients(_lib.ptr(d_frames), T, H, W, red, int(scene_min_sq), _lib.ptr(d_grads), None,
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return d_grads
+
+
+def verify_chunk(H, W, P, chunk=0):
+    """Poses per pass of verify_poses: ``chunk``, or for 0 as many as keep the render stack (3 bytes of colour and 4 of
+    depth per pixel) under 256 MB; at least 1, at most P (bp_vsd_errors' convention)."""
+    return max(1, min(int(chunk) if chunk else VERIFY_STACK_BYTES // (H * W * 7), max(P, 1)))
+
+
+def verify_poses(poses, vertices, faces, colors, K, frames, frame_index, device=None, pixel_center=0.0, near=0.01,
+                 ambient=0.5, light=(0.0, 0.0, 0.0), uv=None, texture=None, chunk=0, red_channel=0,
+                 render_min_sq=VERIFY_RENDER_MIN_SQ, scene_min_sq=VERIFY_SCENE_MIN_SQ):
+    """Scores P pose hypotheses of one mesh against the frames they belong to: ``(scores [P] float64, sums [P] uint64,
+    counts [P] int32, skipped [P] int32)``.  Every pose is rendered into an image of its own (render_color with
+    ``colors``, or with ``uv`` and ``texture`` textured; ``pixel_center``, ``near``, ``ambient``, ``light`` are its) and
+    scored against frame ``frame_index[p]`` of ``frames`` [T, H, W, 3] uint8 as gradient_scores does; the highest score
+    is the pose whose rendered edges agree best with the frame's (the reference's verify_6D_poses).  The colours, the
+    texture and the frames share one channel order; ``red_channel`` says which byte is red.  ``chunk`` poses are
+    rendered and scored at a time (verify_chunk); the results do not depend on it.  ``device=None``: the host twins; a
+    torch device: frames, mesh and poses are uploaded once, each chunk is rendered (bp_render_color[_textured]) and
+    scored (bp_gradient_scores) on it, and only the four result rows come back.  Byte-identical either way."""
+    from . import _lib
+    poses = _poses34(poses)
+    vertices, faces = _mesh_args(vertices, faces)
+    frames = _verify_images(frames, "frames")
+    T, H, W = frames.shape[:3]
+    red = _red(red_channel)
+    P = len(poses)
+    idx = np.ascontiguousarray(frame_index, dtype=np.int32).reshape(-1)
+    if len(idx) != P:
+        raise ValueError("frame_index needs one entry per pose")
+    if T < 1:
+        raise ValueError("at least one frame")
+    if (uv is None) != (texture is None):
+        raise ValueError("uv and texture are given together")
+    scores, sums, counts = np.zeros(P, np.float64), np.zeros(P, np.uint64), np.zeros(P, np.int32)
+    skipped = np.zeros(P, np.int32)
+    if P == 0:
+        return scores, sums, counts, skipped
+    step = verify_chunk(H, W, P, chunk)
+    if device is None:
+        grads = image_gradients(frames, red, scene_min_sq)[0]
+        for s in range(0, P, step):
+            color, _, skipped[s:s + step] = render_color(poses[s:s + step], vertices, faces, colors, K, (H, W), None,
+                                                         pixel_center=pixel_center, near=near, ambient=ambient, light=light,
+                                                         uv=uv, texture=texture)
+            scores[s:s + step], sums[s:s + step], counts[s:s + step] = gradient_scores(
+                color, grads, idx[s:s + step], red, render_min_sq)
+        return scores, sums, counts, skipped
+    import torch
+    _lib.require_gpu()
+    dev = torch.device(device)
+    L = _lib.lib()
+    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
+    mips = None
+    if texture is not None:
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        if uv.shape != (len(faces), 3, 2):
+            raise ValueError("uv must have the shape [F, 3, 2] = [%d, 3, 2], got %s" % (len(faces), list(uv.shape)))
+        mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, dev)
+        if isinstance(mips.data, np.ndarray):
+            raise ValueError("the pyramid was built for the host, the call is for %s" % (dev,))
+        dev = mips.data.device
+    else:
+        colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+        if len(colors) != len(vertices):
+            raise ValueError("colors needs one row per vertex")
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        d_grads = _device_scene_grads(frames, True, red, scene_min_sq, dev)
+        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
+        d_colors = torch.from_numpy(colors).to(dev) if mips is None else None
+        d_uv = torch.from_numpy(uv).to(dev) if mips is not None else None
+        d_poses, d_idx = torch.from_numpy(poses.reshape(P, 12)).to(dev), torch.from_numpy(idx).to(dev)
+        d_color = torch.empty((step, H, W, 3), dtype=torch.uint8, device=dev)
+        d_depth = torch.empty((step, H, W), dtype=torch.float32, device=dev)
+        d_sums = torch.empty(P, dtype=torch.int64, device=dev)             # (the bits; the kernel writes uint64)
+        d_counts = torch.empty(P, dtype=torch.int32, device=dev)
+        d_scores = torch.empty(P, dtype=torch.float64, device=dev)
+        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
+        for s in range(0, P, step):
+            n = min(step, P - s)
+            d_color[:n].zero_()
+            d_depth[:n].zero_()
+            if mips is None:
+                _lib.check(L.bp_render_color(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_colors),
+                                             _lib.ptr(d_poses[s:s + n]), n, None, n, _lib.ptr(Kf), H, W, float(pixel_center),
+                                             float(near), float(ambient), _lib.ptr(lt), 0, _lib.ptr(d_color), _lib.ptr(d_depth),
+                                             _lib.ptr(d_skipped[s:s + n]), st))
+            else:
+                _lib.check(L.bp_render_color_textured(
+                    _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), None, _lib.ptr(d_uv), _lib.ptr(mips.data),
+                    mips.Wt, mips.Ht, mips.levels, _lib.ptr(d_poses[s:s + n]), n, None, n, _lib.ptr(Kf), H, W,
+                    float(pixel_center), float(near), float(ambient), _lib.ptr(lt), 0, _lib.ptr(d_color), _lib.ptr(d_depth),
+                    _lib.ptr(d_skipped[s:s + n]), st))
+            _lib.check(L.bp_gradient_scores(_lib.ptr(d_color), _lib.ptr(d_grads), _lib.ptr(d_idx[s:s + n]), n, T, H, W, red,
+                                            int(render_min_sq), _lib.ptr(d_sums[s:s + n]), _lib.ptr(d_counts[s:s + n]),
+                                            _lib.ptr(d_scores[s:s + n]), st))
+        return (d_scores.cpu().numpy(), d_sums.cpu().numpy().view(np.uint64), d_counts.cpu().numpy(), d_skipped.cpu().numpy())
+
+
 ICP_ACC = 29                                                # csrc/icp.h ICP_ACC
 ICP_STATUS = ("OK", "TOO_FEW", "SINGULAR", "DIVERGED", "REJECTED", "NO_IMAGE")   # stats[:, 5] (csrc/icp_math.inc)
 

@@ -82,6 +82,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help='--candidates C: a pose for EVERY merged pose pPose-NMS leaves, not result[0] alone -- each JSON entry '
                         'carries its own cam_R / cam_t and the scoring matches ground-truth entries to instances by box IoU '
                         '(DESIGN.md 3.7).  Alone or with --device_pnp (one more launch at the end of the frame graph)')
+    p.add_argument('--verify', nargs='?', default=None, const='device', choices=['device', 'host'],
+                   help='--candidates C --all_instances: choose the frame\'s pose among its instance poses by looking at the '
+                        'image -- every solved instance is rendered with the object\'s coloured mesh and scored by the agreement '
+                        'of its unit Sobel gradients with the frame\'s (the reference\'s verify_6D_poses; DESIGN.md 3.18), on the '
+                        'run\'s GPU (or with "host" by the byte-identical host twin).  The best becomes cam_R / cam_t before '
+                        '--refine_depth and before scoring, which then takes the frame pose as it is (no ground-truth box '
+                        'picks an instance); one more line gives the frames scored and the choices changed.  Default: off')
     p.add_argument('--fused', default=False, action='store_true', help='one hipGraph per frame instead of stage threads')
     p.add_argument('--device_pnp', default=False, action='store_true',
                    help='--fused: key-point decode, pPose-NMS, pruning and PnP on each rank\'s GPU at the end of the frame '

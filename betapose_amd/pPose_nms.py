@@ -69,6 +69,8 @@ def results_to_json_list(all_results, for_eval=False):
             if len(cam_R) > 0:
                 r["cam_R"] = np.array(cam_R).reshape((9, 1))[:, 0].tolist()
                 r["cam_t"] = np.array(cam_t).reshape((3, 1))[:, 0].tolist()
+            if instances is not None and "verify_score" in instances[j]:    # --verify (renderer.verify_results)
+                r["verify_score"] = float(instances[j]["verify_score"])
             kp, sc = _np(human["keypoints"]), _np(human["kp_score"]).reshape(-1)
             flat = []
             for k in range(sc.shape[0]):

@@ -163,6 +163,85 @@ def frame_poses(frame, all_instances=False):
     return [_pose44(frame["cam_R"], frame["cam_t"])]
 
 
+def _image_u8(image):
+    """A frame as uint8 [H, W, 3]: uint8 as it is, floats in [0, 1] rounded to nearest."""
+    image = np.asarray(image)
+    return np.ascontiguousarray(image if image.dtype == np.uint8 else metrics.colors_u8(image))
+
+
+def verify_6D_poses(detections, model_map, cam, image, device=None):
+    """Signature and behaviour of the reference's function of this name (utils/utils.py:558-610): ``detections`` is a
+    list of ``[class index, confidence, l, t, r, b, pose0, ..., poseN]`` for one ``image`` ([H, W, 3], BGR as the
+    reference reads frames: uint8, or floats in [0, 1]); every pose of a detection is rendered with the model
+    ``model_map["%02d" % (class index + 1)]`` and scored by the agreement of its unit Sobel gradients with the image's
+    (metrics.verify_poses with the reference's thresholds and this module's ``Renderer`` pixel centre, ambient weight
+    and light); returned is the list of ``det[:6] + [best pose]``, the first pose on a tie as ``np.argmax``.  The gray
+    conversion treats byte 2 as red for the image and for the render, as the reference's ``COLOR_BGR2GRAY`` does to both.
+    ``device``: None for the host twin, a torch device for the GPU; the choice is the same.  DESIGN.md 3.18 lists where
+    the score departs from the reference's."""
+    frame = _image_u8(image)[None]
+    filtered = []
+    for det in detections:
+        model = model_map["%02d" % (int(det[0]) + 1)]
+        poses = [_pose34(T) for T in det[6:]]
+        new_det = list(det[:6])
+        if poses:
+            scores = metrics.verify_poses(np.stack(poses), model.vertices, model.indices, metrics.colors_u8(model.colors),
+                                          cam, frame, np.zeros(len(poses), np.int32), device,
+                                          pixel_center=Renderer.pixel_center, red_channel=2)[0]
+            new_det.append(det[6 + int(np.argmax(scores))])
+        filtered.append(new_det)
+    return filtered
+
+
+def verify_results(final_result, model, frame_dir, cam, device=None, batch=8):
+    """--verify: for every frame dict of ``final_result`` whose ``"instances"`` list has at least two solved entries,
+    those poses are rendered with ``model`` (RGB colours) and scored against the frame ``<frame_dir>/<imgname>``
+    (metrics.verify_poses, pixel centre 0).  Every solved instance gets its score as ``"verify_score"``; the pose with
+    the highest score (the first on a tie) becomes the frame's ``cam_R`` / ``cam_t`` and the pose it replaces is kept
+    under ``"pose_unverified"`` = ``{"cam_R", "cam_t"}``.  Frames with fewer solved instances are left untouched.
+    Frames are read and scored ``batch`` at a time on ``device`` (None: the host twin; same choice, same bytes).
+    Returns ``(frames scored, choices changed)``."""
+    import os
+    from PIL import Image
+    todo = []
+    for f in final_result:
+        solved = [k for k, s in enumerate(f.get("instances", ())) if int(s["status"]) == 0 and len(s["cam_R"]) > 0]
+        if len(solved) >= 2:
+            todo.append((f, solved))
+    changed = 0
+    colors = metrics.colors_u8(model.colors)
+    for b0 in range(0, len(todo), batch):
+        part = todo[b0:b0 + batch]
+        frames = [np.asarray(Image.open(os.path.join(frame_dir, os.path.basename(f["imgname"]))).convert("RGB")) for f, _ in part]
+        groups = [list(range(len(part)))] if len({fr.shape for fr in frames}) == 1 else [[i] for i in range(len(part))]
+        for slots in groups:
+            poses, index = [], []
+            for k, i in enumerate(slots):
+                f, solved = part[i]
+                for j in solved:
+                    poses.append(_pose44(f["instances"][j]["cam_R"], f["instances"][j]["cam_t"]))
+                    index.append(k)
+            scores = metrics.verify_poses(np.stack(poses), model.vertices, model.indices, colors, cam,
+                                          np.stack([frames[i] for i in slots]), np.array(index, np.int32), device)[0]
+            at = 0
+            for i in slots:
+                f, solved = part[i]
+                sc = scores[at:at + len(solved)]
+                at += len(solved)
+                for j, v in zip(solved, sc):
+                    f["instances"][j]["verify_score"] = float(v)
+                best = f["instances"][solved[int(np.argmax(sc))]]
+                old_R, old_t = np.asarray(f["cam_R"], dtype=np.float64), np.asarray(f["cam_t"], dtype=np.float64)
+                new_R = np.asarray(best["cam_R"], dtype=np.float64).reshape(old_R.shape if old_R.size == 9 else (3, 3))
+                new_t = np.asarray(best["cam_t"], dtype=np.float64).reshape(old_t.shape if old_t.size == 3 else (3, 1))
+                f["pose_unverified"] = {"cam_R": f["cam_R"], "cam_t": f["cam_t"]}
+                if old_R.size != 9 or not (np.array_equal(new_R, old_R) and np.array_equal(new_t, old_t)):
+                    changed += 1
+                f["cam_R"], f["cam_t"] = new_R, new_t
+    return len(todo), changed
+
+
 class BoxModel:
     """A grey box around ``points`` as a renderer model: what --save_img draws where there is no mesh file (--synthetic)."""
 

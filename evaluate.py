@@ -134,6 +134,16 @@ def save_images(args, obj_id, final_result, gt_frames, kp3d, cam_K, device):
     print("Saved %d images to %s (%.1f frames/sec)" % (n, os.path.join(args.outputpath, "vis"), n / max(time.time() - t0, 1e-9)))
 
 
+def verify_frame_poses(args, obj_id, final_result, gt_frames, kp3d, cam_K, device):
+    """--verify: renderer.verify_results with the mesh --save_img draws (without a dataset: a grey box), on ``device`` or
+    with ``--verify host`` by the host twin; prints the counts."""
+    from betapose_amd import renderer
+    model = render_model(None if gt_frames is None else args.sixd_base, obj_id, kp3d)
+    scored, changed = renderer.verify_results(final_result, model, args.inputpath, cam_K,
+                                              None if args.verify == "host" else device)
+    print("Pose verification for seq %02d: %d frames scored, %d choices changed" % (obj_id, scored, changed))
+
+
 def synthetic_depth_inputs(final_result, kp3d, cam_K, size, device):
     """--synthetic --vsd / --refine_depth: a closed loop that only shows the path runs.  The mesh is the bounding box of
     the synthetic key points, the ground truth is each frame's own estimated pose and its depth image is rendered from
@@ -178,6 +188,8 @@ def print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, size, device, vsd=Tru
 
 def main():
     args = parse_args()
+    if args.verify and not (int(args.candidates) and args.all_instances):      # (before anything needs the GPU)
+        raise SystemExit("--verify needs --candidates C --all_instances: it chooses among the instance poses of a frame")
     import torch
     from betapose_amd import _lib
     from betapose_amd.darknet import Darknet
@@ -336,7 +348,10 @@ def main():
     if rank == 0:
         print('===========================> Finish Model Running: %d frames, %d with a pose, %.2f s' % (
             len(im_names), sum(len(f['result']) > 0 for f in final_result), time.time() - t0))
+        if args.verify:     # before the JSON, the refinement and every error: they see the verified frame pose
+            verify_frame_poses(args, obj_id, final_result, gt_frames, kp3d, cam_K, torch.device("cuda", local))
         write_json(final_result, args.outputpath)
+        match = args.all_instances and not args.verify      # --verify: no ground-truth box takes part in the choice
         if gt_frames is not None:
             sym = obj_id in id_list(args.symmetric_ids)
             depth_inputs, m_ref = None, None
@@ -346,10 +361,10 @@ def main():
             if args.refine_depth is not None:   # before any error: the lines below are those of the refined poses
                 m_ref = refine_scored_poses(obj_id, final_result, gt_frames, model_vertices, depth_inputs, diameter,
                                             torch.device("cuda", local), args.refine_depth,
-                                            match_instances=args.all_instances)
+                                            match_instances=match)
             m = metrics.evaluate_results(final_result, gt_frames, model_vertices, metric_cam, diameter, pixel_thresh,
                                          symmetric=sym, device=torch.device("cuda", local) if sym else None,
-                                         match_instances=args.all_instances)
+                                         match_instances=match)
             print("Mean add accuracy for seq %02d is: %.3f" % (obj_id, m["mean_add"]))
             if sym:
                 print("Mean add-s accuracy for seq %02d is: %.3f" % (obj_id, m["mean_adds"]))
@@ -357,13 +372,13 @@ def main():
             print("Mean IoU for seq %02d is: %.3f" % (obj_id, m["mean_iou"]))
             if args.bop_metrics:
                 print_bop_metrics(args.sixd_base, obj_id, final_result, gt_frames, model_vertices, metric_cam, diameter,
-                                  torch.device("cuda", local), match_instances=args.all_instances)
+                                  torch.device("cuda", local), match_instances=match)
             if args.vsd and m_ref is not None:      # the refinement pass has scored the refined poses already
                 print("Mean vsd recall for seq %02d is: %.3f" % (obj_id, m_ref["ar_vsd"]))
             elif args.vsd:
                 print_vsd_metrics(args.sixd_base, obj_id, 2 if args.occlusion else None, final_result, gt_frames,
                                   model_vertices, metric_cam, diameter, torch.device("cuda", local),
-                                  match_instances=args.all_instances, depth_inputs=depth_inputs)
+                                  match_instances=match, depth_inputs=depth_inputs)
         elif (args.vsd or args.refine_depth is not None) and args.synthetic:
             print_synthetic_vsd(obj_id, final_result, kp3d, cam_K, synth_size, torch.device("cuda", local), vsd=args.vsd,
                                 refine_iterations=args.refine_depth)

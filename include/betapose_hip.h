@@ -47,6 +47,9 @@
  *   bp_render_color, bp_render_color_textured, bp_texture_mips, bp_draw_boxes, bp_overlay (and their _host twins)
  *                          Renderer.draw_model / draw_boundingbox / finish and      utils/renderer.py:137-181
  *                          draw_detections_3D's paste over the frame                utils/utils.py:269-301
+ *   bp_image_gradients, bp_gradient_scores (and their _host twins)
+ *                          verify_6D_poses: compute_grads_and_mags and the score     utils/utils.py:558-610
+ *                          sum |g_ren . g_scene| / (count(ren_mags > 0) + 1) of every rendered pose hypothesis
  *   bp_vsd_errors          no reference counterpart: the BOP error VSD over those renders and the test depth image
  *   bp_annotate_keypoints, bp_vertex_boxes (and their _host twins)
  *                          sinobj.apply_pose / project_all / project_kp     2_keypoint_annotator/annotate_keypoint.py:108-175
@@ -394,6 +397,36 @@ int bp_overlay(const unsigned char* d_frames, const unsigned char* d_color, cons
                int alpha, unsigned char* d_out, void* stream);
 int bp_overlay_host(const unsigned char* frames, const unsigned char* color, const float* depth, int I, int H, int W,
                     int alpha, unsigned char* out);
+/* Pose verification by gradient agreement (the reference's verify_6D_poses).  All arithmetic up to the
+ * unit vectors is integer, and the sum is integer, so host and device give the same bytes.
+ *   gray   of a uint8 pixel: (4899 R + 9617 G + 1868 B + 8192) >> 14; byte red_channel (0 or 2) is R, byte 1 is G
+ *   Sobel  ksize 5, separable, d = [-1, -2, 0, 2, 1], s = [1, 4, 6, 4, 1]: gx = s along y then d along x, gy = d along y
+ *          then s along x (correlation); border reflect-101 (-1 -> 1, -2 -> 2, W -> W - 2, W + 1 -> W - 3), so H, W >= 3.
+ *          |g| <= 12240 and m2 = gx^2 + gy^2 <= 299 635 200 fits an int32
+ *   mask   a pixel is kept iff m2 >= min_sq.  The reference's `sqrt(m2) + 0.001 < 5` masks an 8-bit image's pixel iff
+ *          m2 <= 24: min_sq = 25; applied to a render that is float in [0, 1] it masks iff m2 < (4.999 * 255)^2 =
+ *          1 624 974.8 in 8-bit units: min_sq = 1 624 975
+ *   unit   of a kept pixel: mag = sqrtf((float)m2) + 0.001f, nx = (float)gx / mag, ny = (float)gy / mag, square root and
+ *          quotients correctly rounded to f32; a masked pixel has nx = ny = 0 and magnitude 0
+ *   term   t = fabsf(rnx * snx + rny * sny) (two products, one sum, no contraction), q = (uint32) lrintf(t * 2^24), and 0
+ *          where t is NaN or above 2 (a scene gradient that is no unit vector)
+ * bp_image_gradients: d_images [I][H][W][3] uint8 -> d_grad [I][H][W][2] f32 = (nx, ny) and, unless NULL, d_mag [I][H][W]
+ * f32.  I = 0 is a no-op.
+ * bp_gradient_scores: P renders d_renders [P][H][W][3] uint8 against the gradients d_scene_grad [T][H][W][2] of the frames
+ * (bp_image_gradients' output), render p against frame d_frame_index[p].  Per render, in one fused kernel whose render
+ * gradients never reach memory: d_sum[p] (uint64) = the sum of q over the render's kept pixels, d_count[p] = the number
+ * of kept render pixels, d_score[p] (f64) = sum / 2^24 / (count + 1).  The rows are zeroed by the call and accumulated
+ * with integer atomics: no workspace, and the same bytes from run to run.  A pose whose frame index lies outside
+ * [0, T) gets score NaN, sum 0 and count -1.  P = 0 is a no-op.
+ * Both are enqueued on `stream` and do not synchronise it. */
+int bp_image_gradients(const unsigned char* d_images, int I, int H, int W, int red_channel, int min_sq, float* d_grad,
+                       float* d_mag, void* stream);
+int bp_image_gradients_host(const unsigned char* images, int I, int H, int W, int red_channel, int min_sq, float* grad,
+                            float* mag);
+int bp_gradient_scores(const unsigned char* d_renders, const float* d_scene_grad, const int* d_frame_index, int P, int T, int H,
+                       int W, int red_channel, int render_min_sq, uint64_t* d_sum, int* d_count, double* d_score, void* stream);
+int bp_gradient_scores_host(const unsigned char* renders, const float* scene_grad, const int* frame_index, int P, int T, int H,
+                            int W, int red_channel, int render_min_sq, uint64_t* sum, int* count, double* score);
 /* BOP's Visible Surface Discrepancy (step cost, normalised by the diameter, visibility mode bop19) of P pose pairs of
  * one mesh: both poses of a pair are rendered as bp_render_depth does and compared with the test depth image
  * d_test_index[p] of d_depth_test [T][H][W] uint16 (depth = raw * depth_scale in pose units, 0 = missing).  taus: host,

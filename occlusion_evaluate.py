@@ -42,6 +42,8 @@ def main():
     args = parse_args()
     if not args.obj_ids:
         return evaluate.main()          # the reference's own protocol: one object per run (--candidates works there)
+    if args.verify and not (int(args.candidates) and args.all_instances):
+        raise SystemExit("--verify needs --candidates C --all_instances: it chooses among the instance poses of a frame")
     if args.all_instances and not int(args.candidates):
         raise SystemExit("--all_instances needs --candidates C: the instances are the merged poses of a frame's candidate boxes")
     if int(args.candidates):
