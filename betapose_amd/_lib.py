@@ -8,295 +8,60 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BP_LIB: an alternative build of the same library (tools only: `python -m betapose_amd.build --experimental` makes
 # libbetapose_hip_exp.so with the measured-and-rejected kernels and the timing ablations compiled in)
 LIB_PATH = os.environ.get("BP_LIB") or os.path.join(_HERE, "libbetapose_hip.so")
+HEADER_PATH = os.path.join(_HERE, "csrc", "..", "..", "include", "betapose_hip.h")      # build.py HEADERS
 _lock = threading.Lock()
 _lib = None
 
-c_float_p = C.POINTER(C.c_float)
-c_double_p = C.POINTER(C.c_double)
-c_int_p = C.POINTER(C.c_int)
-vp = C.c_void_p
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "unsigned int": C.c_uint, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
 
-# name -> (restype, argtypes); every symbol include/betapose_hip.h declares
-PROTOTYPES = {
-    "bp_last_error": (C.c_char_p, []),
-    "bp_version": (C.c_int, []),
-    "bp_device_count": (C.c_int, []),
-    "bp_device_name": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
-    "bp_yolo_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-    "bp_yolo_create_from_memory": (C.c_int, [C.c_char_p, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-    "bp_yolo_clone": (C.c_int, [vp, C.POINTER(vp)]),
-    "bp_kpd_clone": (C.c_int, [vp, C.POINTER(vp)]),
-    "bp_yolo_destroy": (None, [vp]),
-    "bp_yolo_rows": (C.c_int, [vp]),
-    "bp_yolo_attrs": (C.c_int, [vp]),
-    "bp_yolo_forward": (C.c_int, [vp, vp, C.c_int, vp, vp]),
-    "bp_yolo_forward_select": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
-    "bp_yolo_forward_select_classes": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp]),
-    "bp_yolo_select": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]),
-    "bp_yolo_tap_count": (C.c_int, [vp]),
-    "bp_yolo_tap_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, c_int_p, c_int_p, c_int_p]),
-    "bp_yolo_tap_copy": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
-    "bp_kpd_create": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-    "bp_kpd_destroy": (None, [vp]),
-    "bp_kpd_forward": (C.c_int, [vp, vp, C.c_int, vp, vp]),
-    "bp_kpd_forward_argmax": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
-    "bp_kpd_launch_count": (C.c_int, [vp, C.c_int]),
-    "bp_kpd_tap_count": (C.c_int, [vp]),
-    "bp_kpd_tap_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, c_int_p, c_int_p, c_int_p]),
-    "bp_kpd_tap_copy": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
-    "bp_yolo_set_policy": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bp_kpd_set_policy": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bp_yolo_set_precision": (C.c_int, [vp, C.c_int]),
-    "bp_kpd_set_precision": (C.c_int, [vp, C.c_int]),
-    "bp_calibrate_ticks": (C.c_int, [C.c_longlong, c_float_p, vp]),
-    "bp_yolo_set_prefetch": (C.c_int, [vp, C.c_int]),
-    "bp_kpd_set_prefetch": (C.c_int, [vp, C.c_int]),
-    "bp_yolo_set_fusion": (C.c_int, [vp, C.c_int]),
-    "bp_kpd_set_fusion": (C.c_int, [vp, C.c_int]),
-    "bp_yolo_fused_launches": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
-    "bp_kpd_fused_launches": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
-    "bp_yolo_xcd_errors": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
-    "bp_kpd_xcd_errors": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
-    "bp_yolo_set_stamps": (C.c_int, [vp, vp, C.c_int]),
-    "bp_kpd_set_stamps": (C.c_int, [vp, vp, C.c_int]),
-    "bp_yolo_op_name": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
-    "bp_kpd_op_name": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
-    "bp_yolo_op_stats": (C.c_int, [vp, c_double_p, c_double_p, C.c_int]),
-    "bp_kpd_op_stats": (C.c_int, [vp, c_double_p, c_double_p, C.c_int]),
-    "bp_yolo_device_bytes": (C.c_size_t, [vp]),
-    "bp_kpd_device_bytes": (C.c_size_t, [vp]),
-    "bp_crop": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
-    "bp_resize_bicubic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_conv2d": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                            C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, c_float_p, vp]),
-    "bp_conv2d_planes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, c_float_p, vp]),
-    "bp_conv2d_se": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                               C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, c_float_p, vp]),
-    "bp_avgpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, c_int_p, vp]),
-    "bp_fc": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
-    "bp_maxpool3s2p1": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
-    "bp_pixel_shuffle2": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
-    "bp_pipeline_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, C.POINTER(vp)]),
-    "bp_pipeline_kernel_count": (C.c_int, [vp]),
-    "bp_yolo_profile": (C.c_int, [vp, C.c_int, C.c_int, c_float_p, c_int_p, C.c_int, vp]),
-    "bp_kpd_profile": (C.c_int, [vp, C.c_int, C.c_int, c_float_p, c_int_p, C.c_int, vp]),
-    "bp_pipeline_destroy": (None, [vp]),
-    "bp_pipeline_frames": (vp, [vp]),
-    "bp_pipeline_results": (vp, [vp]),
-    "bp_pipeline_heatmaps": (vp, [vp]),
-    "bp_pipeline_set_fixed_box": (C.c_int, [vp, vp]),
-    "bp_pipeline_run": (C.c_int, [vp, C.c_int, vp]),
-    "bp_pipeline_prepare": (C.c_int, [vp]),
-    "bp_pipeline_latency_faults": (C.c_int, [vp]),
-    "bp_scene_create": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.POINTER(vp)]),
-    "bp_scene_destroy": (None, [vp]),
-    "bp_scene_results": (vp, [vp]),
-    "bp_scene_poses": (vp, [vp]),
-    "bp_scene_set_pose_solver": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
-    "bp_scene_set_pose_ransac": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_double]),
-    "bp_scene_prepare": (C.c_int, [vp]),
-    "bp_scene_run": (C.c_int, [vp, C.c_int, vp]),
-    "bp_scene_kernel_count": (C.c_int, [vp]),
-    "bp_yolo_select_nms": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
-    "bp_yolo_forward_select_nms": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp]),
-    "bp_crop_candidates": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
-    "bp_cands_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, vp, vp, C.POINTER(vp)]),
-    "bp_cands_destroy": (None, [vp]),
-    "bp_cands_results": (vp, [vp]),
-    "bp_cands_counts": (vp, [vp]),
-    "bp_cands_prepare": (C.c_int, [vp]),
-    "bp_cands_run": (C.c_int, [vp, C.c_int, vp]),
-    "bp_cands_kernel_count": (C.c_int, [vp]),
-    "bp_cands_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
-    "bp_cands_pose": (vp, [vp]),
-    "bp_cands_merged": (vp, [vp]),
-    "bp_cands_info": (vp, [vp]),
-    "bp_pose_from_candidate_records": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
-    "bp_cands_set_instance_poses": (C.c_int, [vp, C.c_int, vp]),
-    "bp_cands_instance_poses": (vp, [vp]),
-    "bp_pose_instances_from_merged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
-    "bp_heatmap_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_pose_errors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
-    "bp_pose_errors_sym": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
-    "bp_render_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp,
-                                  vp]),
-    "bp_render_depth_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp,
-                                       vp]),
-    "bp_render_color": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double,
-                                  C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, vp]),
-    "bp_render_color_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
-                                       C.c_double, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp]),
-    "bp_texture_mips_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "bp_texture_mips": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_texture_mips_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_render_color_textured": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
-                                           C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, C.c_int, vp,
-                                           vp, vp, vp]),
-    "bp_render_color_textured_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int,
-                                                vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp,
-                                                C.c_int, vp, vp, vp]),
-    "bp_draw_boxes": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]),
-    "bp_draw_boxes_host": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
-    "bp_overlay": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_overlay_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_vsd_errors": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
-                                C.c_double, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
-    "bp_image_gradients": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_image_gradients_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_gradient_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
-    "bp_gradient_scores_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_annotate_keypoints": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, C.c_int,
-                                        vp, C.c_double, C.c_double, vp, vp, vp, vp]),
-    "bp_annotate_keypoints_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp,
-                                             C.c_int, vp, C.c_double, C.c_double, vp, vp, vp]),
-    "bp_mask_boxes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, vp, C.c_double, vp, vp, vp]),
-    "bp_mask_boxes_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, vp, C.c_double, vp, vp]),
-    "bp_vertex_boxes": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
-    "bp_vertex_boxes_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
-    "bp_kpd_targets": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp,
-                                 vp]),
-    "bp_kpd_targets_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp,
-                                      vp]),
-    "bp_kpd_inputs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_kpd_inputs_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_kpd_augment": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
-    "bp_kpd_augment_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
-    "bp_heatmap_loss_acc": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "bp_heatmap_loss_acc_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
-    "bp_yolo_loss_partials": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bp_yolo_inputs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_yolo_inputs_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_yolo_truth": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
-                                vp]),
-    "bp_yolo_truth_host": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
-                                     vp]),
-    "bp_yolo_loss": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp,
-                               C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
-    "bp_yolo_loss_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
-                                    vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
-    "bp_yolo_map_max_dets": (C.c_int, []),
-    "bp_yolo_detections_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "bp_detector_map_reduce_scratch": (C.c_size_t, [C.c_int, C.c_int]),
-    "bp_yolo_detections": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                     C.c_int, vp, vp, vp, vp]),
-    "bp_yolo_detections_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                          C.c_float, C.c_int, vp, vp]),
-    "bp_detector_map_match": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_float, C.c_int, C.c_int,
-                                        C.c_int, vp, vp, vp, vp, vp, vp]),
-    "bp_detector_map_match_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_float, C.c_int,
-                                             C.c_int, C.c_int, vp, vp, vp, vp]),
-    "bp_detector_map_reduce": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
-    "bp_detector_map_reduce_host": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
-    "bp_train_conv_scratch": (C.c_size_t, [C.c_int] * 7),
-    "bp_train_update_chunk": (C.c_int, []),
-    "bp_train_conv": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp, vp]),
-    "bp_train_conv_host": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp]),
-    "bp_train_bn_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [C.c_int] * 3 + [vp]),
-    "bp_train_bn_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [C.c_int] * 3),
-    "bp_train_bn_backward": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp] * 3 + [C.c_int] * 2 + [vp]),
-    "bp_train_bn_backward_host": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp] * 3 + [C.c_int] * 2),
-    "bp_train_update": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
-    "bp_train_update_host": (C.c_int, [vp, C.c_int, C.c_float, C.c_float, C.c_float]),
-    "bp_kpd_train_conv_scratch": (C.c_size_t, [C.c_int] * 7),
-    "bp_kpd_train_update_chunk": (C.c_int, []),
-    "bp_kpd_train_conv": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp, vp]),
-    "bp_kpd_train_conv_host": (C.c_int, [C.c_int, vp, vp, vp] + [C.c_int] * 7 + [vp]),
-    "bp_kpd_train_bn_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] * 3 + [vp]),
-    "bp_kpd_train_bn_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] * 3),
-    "bp_kpd_train_bn_backward": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp] * 2 + [C.c_int] * 2 + [vp]),
-    "bp_kpd_train_bn_backward_host": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp] * 2 + [C.c_int] * 2),
-    "bp_kpd_train_tail_forward": (C.c_int, [vp] * 4 + [C.c_int] * 3 + [vp]),
-    "bp_kpd_train_tail_forward_host": (C.c_int, [vp] * 4 + [C.c_int] * 3),
-    "bp_kpd_train_tail_backward": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp]),
-    "bp_kpd_train_tail_backward_host": (C.c_int, [vp] * 7 + [C.c_int] * 3),
-    "bp_kpd_train_pool_forward": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
-    "bp_kpd_train_pool_forward_host": (C.c_int, [vp, C.c_int, C.c_int, vp]),
-    "bp_kpd_train_pool_backward": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
-    "bp_kpd_train_pool_backward_host": (C.c_int, [vp, vp, C.c_int, C.c_int]),
-    "bp_kpd_train_sigmoid_forward": (C.c_int, [vp, vp, C.c_longlong, vp]),
-    "bp_kpd_train_sigmoid_forward_host": (C.c_int, [vp, vp, C.c_longlong]),
-    "bp_kpd_train_sigmoid_backward": (C.c_int, [vp, vp, C.c_longlong, vp]),
-    "bp_kpd_train_sigmoid_backward_host": (C.c_int, [vp, vp, C.c_longlong]),
-    "bp_kpd_train_maxpool_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_kpd_train_maxpool_forward_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_kpd_train_maxpool_backward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_kpd_train_maxpool_backward_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_kpd_train_rmsprop": (C.c_int, [vp, C.c_int, C.c_int] + [C.c_double] * 5 + [vp]),
-    "bp_kpd_train_rmsprop_host": (C.c_int, [vp, C.c_int] + [C.c_double] * 5),
-    "bp_voxel_grid_host": (C.c_int, [vp, C.c_int, C.c_double, vp, c_int_p]),
-    "bp_sift_octave": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
-    "bp_sift_octave_host": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),
-    "bp_farthest_points": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_farthest_points_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_thin_points": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
-    "bp_thin_points_host": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
-    "bp_icp_normal_equations": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
-                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp]),
-    "bp_icp_normal_equations_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,
-                                               C.c_double, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
-    "bp_refine_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
-                                  C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp]),
-    "bp_refine_depth_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp,
-                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, vp, vp]),
-    "bp_pipeline_set_pose_solver": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
-    "bp_pipeline_poses": (vp, [vp]),
-    "bp_pose_from_records": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
-    "bp_solve_pnp_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
-    "bp_pnp_ransac_samples": (C.c_int, [C.c_int, C.c_int, vp]),
-    "bp_pnp_ransac_trials_needed": (C.c_int, [C.c_int, C.c_double, vp]),
-    "bp_pnp_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "bp_solve_pnp_ransac_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp,
-                                            vp, C.c_size_t, vp]),
-    "bp_pipeline_set_pose_ransac": (C.c_int, [vp, C.c_double, C.c_int, C.c_double]),
-    "bp_pose_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "bp_pose_from_records_ransac": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp,
-                                              C.c_size_t, vp]),
-    "bp_solve_pnp": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
-    "bp_solve_pnp_status": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
-    "bp_solve_pnp_refined": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
-    "bp_solve_pnp_ransac": (C.c_int, [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
-    "bp_pose_nms": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
-    "bp_darknet_last_error": (C.c_char_p, []),
-    "bp_darknet_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]),
-    "bp_darknet_destroy": (None, [vp]),
-    "bp_darknet_width": (C.c_int, [vp]),
-    "bp_darknet_height": (C.c_int, [vp]),
-    "bp_darknet_classes": (C.c_int, [vp]),
-    "bp_darknet_detect_rgb": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int]),
-    "bp_darknet_detect_png": (C.c_int, [vp, vp, C.c_size_t, C.c_float, C.c_float, vp, C.c_int]),
-    "bp_darknet_detect_image": (C.c_int, [vp, vp, C.c_size_t, C.c_float, C.c_float, vp, C.c_int]),
-    "bp_image_decode_rgb": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "bp_darknet_detect_file": (C.c_int, [vp, C.c_char_p, C.c_float, C.c_float, vp, C.c_int]),
-    "bp_yolo_create_darknet": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-    "bp_stream_create_masked": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
-    "bp_stream_destroy": (C.c_int, [vp]),
-    "bp_probe_placement": (C.c_int, [C.c_int, vp, vp, vp]),
-    "bp_png_info": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "bp_png_decode_bgr": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "bp_loader_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.POINTER(vp)]),
-    "bp_loader_destroy": (None, [vp]),
-    "bp_loader_next": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(vp)]),
-    "bp_loader_release": (C.c_int, [vp, C.c_longlong]),
-    "bp_upload": (C.c_int, [vp, vp, C.c_size_t, vp]),
-    "bp_synth_background": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, vp, vp]),
-    "bp_synth_background_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, vp]),
-    "bp_synth_windows": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
-    "bp_synth_windows_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
-    "bp_synth_compose": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint, C.c_uint, vp, vp]),
-    "bp_synth_compose_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint, C.c_uint, vp]),
-    "bp_synth_sensor_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp, vp]),
-    "bp_synth_sensor_depth_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_uint, C.c_uint, vp]),
-    "bp_synth_instances": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
-    "bp_synth_instances_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
-}
+
+def _ctype(text, decl, is_return=False):
+    """The ctypes type of one parameter (its name, if any, included in ``text``) or of a return type."""
+    tok = [t for t in re.findall(r"\w+|\*|\S", text) if t != "const"]
+    if any(t != "*" and not re.fullmatch(r"\w+", t) for t in tok):      # ( ) [ ] ... : function pointers, arrays, variadics
+        raise ValueError("cannot map '%s' in the declaration: %s" % (text.strip(), decl))
+    if "*" in tok:      # char* is a C string, every other pointer (pointer to pointer included) an address
+        return C.c_char_p if tok[:tok.index("*")] == ["char"] and tok.count("*") == 1 else C.c_void_p
+    if is_return and tok == ["void"]:
+        return None
+    for name in (tok, tok[:-1] if not is_return else None):                 # without and with the parameter's name
+        if name and " ".join(name) in _SCALARS:
+            return _SCALARS[" ".join(name)]
+    raise ValueError("unknown type '%s' in the declaration: %s" % (text.strip(), decl))
+
+
+def parse_prototypes(header_text):
+    """name -> (restype, argtypes) of every function ``header_text`` declares.  Scalars map by name, ``char*`` to
+    c_char_p and every other pointer to c_void_p; a declaration that cannot be mapped raises ValueError naming it."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    code = re.sub(r"^[ \t]*#.*$", " ", code, flags=re.M).replace('extern "C" {', " ")
+    code = re.sub(r"\{[^{}]*\}", " ", code).replace("}", " ")               # struct bodies; the closing brace of extern "C"
+    protos = {}
+    for decl in (" ".join(s.split()) for s in code.split(";")):
+        if not decl or decl.startswith("typedef "):
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\((.*)\)", decl)
+        if not m:
+            raise ValueError("not a function declaration: %s" % decl)
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        protos[name] = (_ctype(ret, decl, True), [_ctype(p, decl) for p in params])
+    return protos
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_prototypes(_f.read())      # every symbol include/betapose_hip.h declares
 
 RESULT_FLOATS = 316
 POSE_DOUBLES = 166          # include/betapose_hip.h BP_POSE_DOUBLES
@@ -364,3 +129,67 @@ def ptr(t) -> int:
 def current_stream() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+_BITS = {"uint16": "int16", "uint32": "int32", "uint64": "int64"}       # torch holds these as the signed type of their size
+
+
+class Side:
+    """Where a host/device pair ``bp_X_host`` / ``bp_X`` runs and where its buffers live: the host (``device=None``,
+    numpy arrays) or a torch device (tensors).  A wrapper takes its buffers from ``put`` / ``empty`` / ``zeros``, states
+    its argument list once in ``call`` and reads the results back with ``get``."""
+
+    def __init__(self, device=None):
+        self.torch = self.dev = None
+        if device is not None:
+            import torch
+            require_gpu()
+            self.torch, self.dev = torch, torch.device(device)
+
+    def _dtype(self, dtype):
+        name = np.dtype(dtype).name
+        return getattr(self.torch, _BITS.get(name, name))
+
+    def put(self, a, dtype=None, copy=False):
+        """``a`` (array, tensor or None) on this side: a contiguous numpy array on the host (``copy``: one of its own),
+        a tensor on the device.  A tensor that already lives there is taken as it is; an unsigned array goes up as the
+        bits of the signed type of its size."""
+        if a is None:
+            return None
+        if self.dev is None:
+            if hasattr(a, "data_ptr"):
+                a = a.detach().cpu().numpy()
+            return np.array(a, dtype, order="C") if copy else np.ascontiguousarray(a, dtype)
+        if hasattr(a, "data_ptr"):
+            return (a.to(self.dev) if dtype is None else a.to(self.dev, self._dtype(dtype))).contiguous()
+        a = np.ascontiguousarray(a, dtype)
+        if a.dtype.name in _BITS:
+            a = a.view(_BITS[a.dtype.name])
+        return self.torch.from_numpy(a if a.flags.writeable else a.copy()).to(self.dev)     # (torch warns on a read-only array)
+
+    def empty(self, shape, dtype=np.float32):
+        if self.dev is None:
+            return np.empty(shape, dtype)
+        return self.torch.empty(shape, dtype=self._dtype(dtype), device=self.dev)
+
+    def zeros(self, shape, dtype=np.float32):
+        if self.dev is None:
+            return np.zeros(shape, dtype)
+        return self.torch.zeros(shape, dtype=self._dtype(dtype), device=self.dev)
+
+    def get(self, a, dtype=None, copy=False):
+        """The buffer ``a`` of this side as a numpy array: itself on the host (``copy``: a copy), read back from the
+        device.  ``dtype`` names the unsigned type whose bits a device buffer holds."""
+        a = (a.copy() if copy else a) if self.dev is None else a.cpu().numpy()
+        return a if dtype is None else a.view(dtype)
+
+    def call(self, name, *args):
+        """``name + "_host"`` on the host, ``name`` on the device's current stream.  An argument with a ``shape`` (or
+        None) becomes its pointer, anything else (scalars, the ``ptr`` of an array that stays on the host in both calls)
+        passes through."""
+        args = [ptr(a) if (a is None or hasattr(a, "shape")) else a for a in args]
+        if self.dev is None:
+            check(getattr(lib(), name + "_host")(*args))
+        else:
+            with self.torch.cuda.device(self.dev):
+                check(getattr(lib(), name)(*args, self.torch.cuda.current_stream(self.dev).cuda_stream))

@@ -60,15 +60,6 @@ def _depth_stack(depth, H=None, W=None, P=None, name="depth"):
     return d
 
 
-def _on_device(device):
-    """(torch, torch.device) of a device call; raises without a GPU."""
-    import torch
-    from . import _lib
-    _lib.require_gpu()
-    dev = torch.device(device)
-    return torch, dev
-
-
 def scene_depth_from_u16(frames_u16, depth_scale):
     """Test depth images [T, H, W] uint16 -> float32 in pose units, ``raw.astype(float64) * depth_scale`` cast to
     float32: the one conversion both the host and the device path of this module read (0 stays 0 = missing)."""
@@ -101,27 +92,13 @@ def project_keypoints(poses, kp3d, K, size, model_depth=None, scene_depth=None, 
         raise ValueError("near must be positive")
     md = None if model_depth is None else _depth_stack(model_depth, H, W, P, "model_depth")
     scene, idx, T = _scene_args(scene_depth, scene_index, P, H, W)
-    xy, z, flags = np.empty((P, Kp, 2), np.float64), np.empty((P, Kp), np.float64), np.empty((P, Kp), np.uint8)
     if P == 0:
-        return xy, z, flags
-    tail = (float(self_tol), float(delta))
-    if device is None:
-        _lib.check(_lib.lib().bp_annotate_keypoints_host(
-            _lib.ptr(poses), P, _lib.ptr(kp), Kp, _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(md),
-            _lib.ptr(scene), T, _lib.ptr(idx), *tail, _lib.ptr(xy), _lib.ptr(z), _lib.ptr(flags)))
-        return xy, z, flags
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-        d_poses, d_kp, d_md, d_scene, d_idx = up(poses.reshape(P, 12)), up(kp), up(md), up(scene), up(idx)
-        d_xy = torch.empty((P, Kp, 2), dtype=torch.float64, device=dev)
-        d_z = torch.empty((P, Kp), dtype=torch.float64, device=dev)
-        d_flags = torch.empty((P, Kp), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().bp_annotate_keypoints(
-            _lib.ptr(d_poses), P, _lib.ptr(d_kp), Kp, _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(d_md),
-            _lib.ptr(d_scene), T, _lib.ptr(d_idx), *tail, _lib.ptr(d_xy), _lib.ptr(d_z), _lib.ptr(d_flags),
-            torch.cuda.current_stream(dev).cuda_stream))
-        return d_xy.cpu().numpy(), d_z.cpu().numpy(), d_flags.cpu().numpy()
+        return np.empty((P, Kp, 2), np.float64), np.empty((P, Kp), np.float64), np.empty((P, Kp), np.uint8)
+    side = _lib.Side(device)
+    xy, z, flags = side.empty((P, Kp, 2), np.float64), side.empty((P, Kp), np.float64), side.empty((P, Kp), np.uint8)
+    side.call("bp_annotate_keypoints", side.put(poses), P, side.put(kp), Kp, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
+              side.put(md), side.put(scene), T, side.put(idx), float(self_tol), float(delta), xy, z, flags)
+    return side.get(xy), side.get(z), side.get(flags)
 
 
 def mask_boxes(depth, K, scene_depth=None, scene_index=None, delta=BOP_VSD_DELTA, pixel_center=0.0, device=None):
@@ -137,23 +114,13 @@ def mask_boxes(depth, K, scene_depth=None, scene_index=None, delta=BOP_VSD_DELTA
     _size((H, W))
     Kf = _K9(K)
     scene, idx, T = _scene_args(scene_depth, scene_index, P, H, W)
-    boxes, counts = np.empty((P, 2, 4), np.int32), np.empty((P, 2), np.int32)
     if P == 0:
-        return boxes, counts
-    if device is None:
-        _lib.check(_lib.lib().bp_mask_boxes_host(_lib.ptr(d), P, H, W, _lib.ptr(Kf), float(pixel_center), _lib.ptr(scene), T,
-                                                 _lib.ptr(idx), float(delta), _lib.ptr(boxes), _lib.ptr(counts)))
-        return boxes, counts
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-        d_depth, d_scene, d_idx = up(d), up(scene), up(idx)
-        d_boxes = torch.empty((P, 2, 4), dtype=torch.int32, device=dev)
-        d_counts = torch.empty((P, 2), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_mask_boxes(_lib.ptr(d_depth), P, H, W, _lib.ptr(Kf), float(pixel_center), _lib.ptr(d_scene), T,
-                                            _lib.ptr(d_idx), float(delta), _lib.ptr(d_boxes), _lib.ptr(d_counts),
-                                            torch.cuda.current_stream(dev).cuda_stream))
-        return d_boxes.cpu().numpy(), d_counts.cpu().numpy()
+        return np.empty((P, 2, 4), np.int32), np.empty((P, 2), np.int32)
+    side = _lib.Side(device)
+    boxes, counts = side.empty((P, 2, 4), np.int32), side.empty((P, 2), np.int32)
+    side.call("bp_mask_boxes", side.put(d), P, H, W, _lib.ptr(Kf), float(pixel_center), side.put(scene), T, side.put(idx),
+              float(delta), boxes, counts)
+    return side.get(boxes), side.get(counts)
 
 
 def vertex_boxes(poses, vertices, K, size, device=None):
@@ -169,19 +136,12 @@ def vertex_boxes(poses, vertices, K, size, device=None):
     P = len(poses)
     if len(v) < 1:
         raise ValueError("at least one vertex")
-    boxes = np.empty((P, 4), np.int32)
     if P == 0:
-        return boxes
-    if device is None:
-        _lib.check(_lib.lib().bp_vertex_boxes_host(_lib.ptr(poses), P, _lib.ptr(v), len(v), _lib.ptr(Kf), H, W, _lib.ptr(boxes)))
-        return boxes
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_poses, d_v = torch.from_numpy(poses.reshape(P, 12)).to(dev), torch.from_numpy(v).to(dev)
-        d_boxes = torch.empty((P, 4), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_vertex_boxes(_lib.ptr(d_poses), P, _lib.ptr(d_v), len(v), _lib.ptr(Kf), H, W, _lib.ptr(d_boxes),
-                                              torch.cuda.current_stream(dev).cuda_stream))
-        return d_boxes.cpu().numpy()
+        return np.empty((P, 4), np.int32)
+    side = _lib.Side(device)
+    boxes = side.empty((P, 4), np.int32)
+    side.call("bp_vertex_boxes", side.put(poses), P, side.put(v), len(v), _lib.ptr(Kf), H, W, boxes)
+    return side.get(boxes)
 
 
 def gaussian_table(sigma=1):
@@ -225,26 +185,16 @@ def kpd_targets(parts, ul, br, in_res=(320, 256), out_res=(80, 64), sigma=1, wan
     if B * Kp * resH * ((resW + 3) // 4 * 4) >= 1 << 31:
         raise ValueError("the target tensor must hold fewer than 2^31 values")
     g = gaussian_table(sigma)
-    out, centres = np.empty((B, Kp, resH, resW), np.float32), np.empty((B, Kp, 2), np.int32)
-    mask = np.empty((B, Kp, resH, resW), np.float32) if want_mask else None
-    if B:
-        if device is None:
-            _lib.check(_lib.lib().bp_kpd_targets_host(_lib.ptr(parts), _lib.ptr(ul), _lib.ptr(br), B, Kp, inpH, inpW, resH, resW,
-                                                      _lib.ptr(g), len(g), _lib.ptr(out), _lib.ptr(centres), _lib.ptr(mask)))
-        else:
-            torch, dev = _on_device(device)
-            with torch.cuda.device(dev):
-                d_parts, d_ul, d_br, d_g = (torch.from_numpy(a).to(dev) for a in (parts, ul, br, g))
-                d_out = torch.empty((B, Kp, resH, resW), dtype=torch.float32, device=dev)
-                d_centres = torch.empty((B, Kp, 2), dtype=torch.int32, device=dev)
-                d_mask = torch.empty_like(d_out) if want_mask else None
-                _lib.check(_lib.lib().bp_kpd_targets(_lib.ptr(d_parts), _lib.ptr(d_ul), _lib.ptr(d_br), B, Kp, inpH, inpW, resH,
-                                                     resW, _lib.ptr(d_g), len(g), _lib.ptr(d_out), _lib.ptr(d_centres),
-                                                     _lib.ptr(d_mask), torch.cuda.current_stream(dev).cuda_stream))
-                if as_tensor:
-                    return (d_out, d_centres, d_mask) if want_mask else (d_out, d_centres)
-                out, centres = d_out.cpu().numpy(), d_centres.cpu().numpy()
-                mask = d_mask.cpu().numpy() if want_mask else None
+    if not B:
+        out, centres = np.empty((B, Kp, resH, resW), np.float32), np.empty((B, Kp, 2), np.int32)
+        return (out, centres, np.empty((B, Kp, resH, resW), np.float32)) if want_mask else (out, centres)
+    side = _lib.Side(device)
+    out, centres = side.empty((B, Kp, resH, resW), np.float32), side.empty((B, Kp, 2), np.int32)
+    mask = side.empty((B, Kp, resH, resW), np.float32) if want_mask else None
+    side.call("bp_kpd_targets", side.put(parts), side.put(ul), side.put(br), B, Kp, inpH, inpW, resH, resW, side.put(g), len(g),
+              out, centres, mask)
+    if not as_tensor:
+        out, centres, mask = side.get(out), side.get(centres), side.get(mask) if want_mask else None
     return (out, centres, mask) if want_mask else (out, centres)
 
 

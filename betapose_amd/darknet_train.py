@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from . import cfg as C, weights as W
-from .yolo_train import _loss_device, yolo_head_params, yolo_loss
+from .yolo_train import _loss_call, yolo_head_params, yolo_loss
 
 f32 = np.float32
 POLICIES = ("constant", "steps", "step", "exp", "poly")
@@ -178,11 +178,8 @@ class TrainableDarknet:
         self.convs = [l for l in self.layers if l["type"] == "convolutional"]
         self.heads = [l for l in self.layers if l["type"] == "yolo"]
         self.seen = 0
-        self.torch = None
-        self.dev = None
-        if device is not None:
-            from .annotate import _on_device
-            self.torch, self.dev = _on_device(device)
+        self.side = _lib.Side(device)
+        self.torch, self.dev = self.side.torch, self.side.dev
         flat = None
         if weights is not None:
             _, seen, flat = W.read_darknet_weights(weights)
@@ -212,26 +209,17 @@ class TrainableDarknet:
 
     # ------------------------------------------------------------------------------------------- arrays on either side
     def _put(self, a):
-        return a.copy() if self.dev is None else self.torch.from_numpy(a).to(self.dev)
+        return self.side.put(a, f32, copy=True)      # (the net owns and updates its parameters)
 
     def _zeros(self, shape):
-        return np.zeros(shape, f32) if self.dev is None else self.torch.zeros(shape, dtype=self.torch.float32, device=self.dev)
+        return self.side.zeros(tuple(shape), f32)
 
     def _get(self, a):
-        return a.copy() if self.dev is None else a.cpu().numpy()
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
+        return self.side.get(a, copy=True)
 
     def _call(self, name, *args):
         """the host twin, or the device function on the current stream"""
-        L, p = self._L, self._L.ptr
-        args = [p(a) if (a is None or hasattr(a, "shape")) else a for a in args]
-        if self.dev is None:
-            L.check(getattr(L.lib(), name + "_host")(*args))
-        else:
-            with self.torch.cuda.device(self.dev):
-                L.check(getattr(L.lib(), name)(*args, self._stream()))
+        self.side.call(name, *args)
 
     def _table(self):
         """the update's table: (parameter, update, count, kind) per tensor, on the side that runs it"""
@@ -353,13 +341,11 @@ class TrainableDarknet:
         """update_network: one launch over every parameter tensor"""
         ub = self.net["batch"] * self.net["subdivisions"]
         a, dk = f32(self.current_rate() / f32(ub)), f32(-self.net["decay"] * f32(ub))
+        rates = (float(a), float(dk), float(self.net["momentum"]))
         if self.dev is None:
-            self._L.check(self._L.lib().bp_train_update_host(self._tab.ctypes.data, self._ntab, float(a), float(dk),
-                                                             float(self.net["momentum"])))
+            self.side.call("bp_train_update", self._tab, self._ntab, *rates)
         else:
-            with self.torch.cuda.device(self.dev):
-                self._L.check(self._L.lib().bp_train_update(self._tab.data_ptr(), self._ntab, self._blocks, float(a), float(dk),
-                                                            float(self.net["momentum"]), self._stream()))
+            self.side.call("bp_train_update", self._tab, self._ntab, self._blocks, *rates)
 
     def loss(self, heads, truth):
         """the heads' yolo_loss: (per-head deltas, per-head costs as float64 -- device tensors [1] on a device)"""
@@ -371,8 +357,8 @@ class TrainableDarknet:
                 c, _, d, _ = yolo_loss(x, truth, size, h["anchors"], h["mask"], h["classes"], h["ignore_thresh"], h["truth_thresh"],
                                        want_act=False)
             else:
-                r = _loss_device(self.torch, self.dev, x, truth, size, h["anchors"], h["mask"], h["classes"], h["ignore_thresh"],
-                                 h["truth_thresh"], 0, False)
+                r = _loss_call(self.side, x, truth, size, h["anchors"], h["mask"], h["classes"], h["ignore_thresh"],
+                               h["truth_thresh"], 0, False)
                 c, d = r["cost"], r["delta"]
             deltas.append(d), costs.append(c)
         return deltas, costs

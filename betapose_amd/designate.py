@@ -27,19 +27,6 @@ def _points(points, name="points"):
     return p
 
 
-def _on_device(device):
-    """(torch, torch.device) of a device call; raises without a GPU."""
-    import torch
-    from . import _lib
-    _lib.require_gpu()
-    return torch, torch.device(device)
-
-
-def _up(torch, a, dev):
-    """A host array on the device (a read-only array is copied first: torch refuses to wrap one)."""
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-
-
 def voxel_grid(points, leaf):
     """Centroids of the occupied cells of a grid of size ``leaf`` (cell ``floor(p / leaf)`` per axis), in ascending
     cell-key order, each summed in input order.  A grid of more than INT32_MAX cells returns the cloud unchanged
@@ -63,19 +50,10 @@ def sift_octave(points, field, scales, k=25, min_contrast=0.2, device=None):
     n, ns = len(p), len(sc)
     if ns < 4:
         raise ValueError("at least 4 scales")
-    dog, flags = np.empty((n, ns - 1), np.float64), np.empty((n, ns - 3), np.int8)
-    args = (int(field), _lib.ptr(sc), ns, int(k), float(min_contrast))
-    if device is None:
-        _lib.check(_lib.lib().bp_sift_octave_host(_lib.ptr(p), n, *args, _lib.ptr(dog), _lib.ptr(flags)))
-        return dog, flags
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_p = _up(torch, p, dev)
-        d_dog = torch.empty((n, ns - 1), dtype=torch.float64, device=dev)
-        d_flags = torch.empty((n, ns - 3), dtype=torch.int8, device=dev)
-        _lib.check(_lib.lib().bp_sift_octave(_lib.ptr(d_p), n, *args, _lib.ptr(d_dog), _lib.ptr(d_flags),
-                                             torch.cuda.current_stream(dev).cuda_stream))
-        return d_dog.cpu().numpy(), d_flags.cpu().numpy()
+    side = _lib.Side(device)
+    dog, flags = side.empty((n, ns - 1), np.float64), side.empty((n, ns - 3), np.int8)
+    side.call("bp_sift_octave", side.put(p), n, int(field), _lib.ptr(sc), ns, int(k), float(min_contrast), dog, flags)
+    return side.get(dog), side.get(flags)
 
 
 def octave_scales(min_scale, octave, n_scales_per_octave):
@@ -122,18 +100,10 @@ def farthest_points(points, K, start=None, device=None):
     st = -1 if start is None else int(start)
     if start is not None and not 0 <= st < n:
         raise ValueError("start must lie in [0, n)")
-    idx, d2 = np.empty(max(K, 0), np.int32), np.empty(max(K, 0), np.float64)
-    if device is None:
-        _lib.check(_lib.lib().bp_farthest_points_host(_lib.ptr(p), n, K, st, _lib.ptr(idx), _lib.ptr(d2)))
-        return idx, d2
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_p = _up(torch, p, dev)
-        d_idx = torch.empty(max(K, 1), dtype=torch.int32, device=dev)
-        d_d2 = torch.empty(max(K, 1), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().bp_farthest_points(_lib.ptr(d_p), n, K, st, _lib.ptr(d_idx), _lib.ptr(d_d2),
-                                                 torch.cuda.current_stream(dev).cuda_stream))
-        return d_idx.cpu().numpy(), d_d2.cpu().numpy()
+    side = _lib.Side(device)
+    idx, d2 = side.empty(max(K, 1), np.int32), side.empty(max(K, 1), np.float64)       # (K < 1 raises in the library)
+    side.call("bp_farthest_points", side.put(p), n, K, st, idx, d2)
+    return side.get(idx), side.get(d2)
 
 
 def thin_tail(survivors, rounds_left, position):
@@ -155,19 +125,10 @@ def thin_points(points, keep, device=None):
     from . import _lib
     p = _points(points)
     n, keep = len(p), int(keep)
-    alive, state = np.empty(n, np.uint8), np.zeros(2, np.int32)
-    if device is None:
-        _lib.check(_lib.lib().bp_thin_points_host(_lib.ptr(p), n, keep, _lib.ptr(alive), _lib.ptr(state)))
-    else:
-        torch, dev = _on_device(device)
-        with torch.cuda.device(dev):
-            d_p = _up(torch, p, dev)
-            d_alive = torch.empty(n, dtype=torch.uint8, device=dev)
-            d_state = torch.empty(2, dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().bp_thin_points(_lib.ptr(d_p), n, keep, _lib.ptr(d_alive), _lib.ptr(d_state),
-                                                 torch.cuda.current_stream(dev).cuda_stream))
-            alive, state = d_alive.cpu().numpy(), d_state.cpu().numpy()
-    survivors = np.flatnonzero(alive)
+    side = _lib.Side(device)
+    alive, state = side.empty(n, np.uint8), side.zeros(2, np.int32)
+    side.call("bp_thin_points", side.put(p), n, keep, alive, state)
+    survivors, state = np.flatnonzero(side.get(alive)), side.get(state)
     return thin_tail(survivors, max(0, n - keep) - int(state[0]), int(state[1]))
 
 

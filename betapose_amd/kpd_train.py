@@ -47,10 +47,8 @@ class TrainableFastPose:
         self.hyper = dict(lr=float(LR), momentum=float(momentum), wd=float(weightDecay), alpha=OPT_DEFAULTS["alpha"],
                           eps=OPT_DEFAULTS["eps"])
         self.flip_pairs = tuple(flip_pairs)
-        self.torch = self.dev = None
-        if device is not None:
-            from .annotate import _on_device
-            self.torch, self.dev = _on_device(device)
+        self.side = _lib.Side(device)
+        self.torch, self.dev = self.side.torch, self.side.dev
         rng = np.random.default_rng(seed)
         self.P, self.G, self.nbt, self.trainable = {}, {}, {}, []
         self.by_name = {}
@@ -83,16 +81,13 @@ class TrainableFastPose:
 
     # ------------------------------------------------------------------------------------------- arrays on either side
     def _put(self, a):
-        a = np.ascontiguousarray(a, f32)
-        return a.copy() if self.dev is None else self.torch.from_numpy(a).to(self.dev)
+        return self.side.put(a, f32, copy=True)      # (the net owns and updates its parameters)
 
     def _zeros(self, shape, dtype=f32):
-        if self.dev is None:
-            return np.zeros(shape, dtype)
-        return self.torch.zeros(tuple(shape), dtype=self.torch.float32 if dtype == f32 else self.torch.int32, device=self.dev)
+        return self.side.zeros(tuple(shape), dtype)
 
     def _get(self, a):
-        return a.copy() if self.dev is None else a.cpu().numpy()
+        return self.side.get(a, copy=True)
 
     def _buf(self, key, shape, dtype=f32):
         b = self._bufs.get(key)
@@ -102,13 +97,7 @@ class TrainableFastPose:
 
     def _call(self, name, *args):
         """the host twin, or the device function on the current stream"""
-        L, p = self._L, self._L.ptr
-        args = [p(a) if (a is None or hasattr(a, "shape")) else a for a in args]
-        if self.dev is None:
-            L.check(getattr(L.lib(), name + "_host")(*args))
-        else:
-            with self.torch.cuda.device(self.dev):
-                L.check(getattr(L.lib(), name)(*args, self.torch.cuda.current_stream(self.dev).cuda_stream))
+        self.side.call(name, *args)
 
     def _table(self):
         """the optimiser's table: (parameter, gradient, square_avg, momentum buffer, count) per tensor, on its side"""
@@ -289,7 +278,7 @@ class TrainableFastPose:
         if self.dev is None:
             loss, acc, _, _, _, grad = T.heatmap_loss_accuracy(out, labels, set_mask, want_grad=want_grad)
             return loss, float(acc[0]), grad
-        r = T._loss_device(self.torch, self.dev, out, labels, set_mask, want_grad)
+        r = T._loss_call(self.side, out, labels, set_mask, want_grad)
         return r["loss"], r["acc"][:1], r["grad"]
 
     def _read(self, loss, acc):

@@ -72,20 +72,13 @@ def pose_errors(gt_poses, est_poses, model, cam, device=None, want=WANT_ADD | WA
             if want & WANT_2D:
                 out[p, 2] = projection_error_2d(g, e, model, cam)
         return out[:, 0], out[:, 1], out[:, 2]
-    import torch
     from . import _lib
-    _lib.require_gpu()
-    dev = torch.device(device)
+    side = _lib.Side(device)
     K = np.ascontiguousarray(cam, dtype=np.float64).reshape(9) if want & WANT_2D else None
-    with torch.cuda.device(dev):
-        d_model = torch.from_numpy(model).to(dev)
-        d_gt = torch.from_numpy(np.ascontiguousarray(gt.reshape(P, 12))).to(dev)
-        d_est = torch.from_numpy(np.ascontiguousarray(est.reshape(P, 12))).to(dev)
-        d_out = torch.from_numpy(out).to(dev)
-        _lib.check(_lib.lib().bp_pose_errors(_lib.ptr(d_model), len(model), _lib.ptr(d_gt), _lib.ptr(d_est), P,
-                                             _lib.ptr(K), int(want), _lib.ptr(d_out),
-                                             torch.cuda.current_stream(dev).cuda_stream))
-        out = d_out.cpu().numpy()
+    d_out = side.put(out)
+    side.call("bp_pose_errors", side.put(model), len(model), side.put(gt.reshape(P, 12)), side.put(est.reshape(P, 12)), P,
+              _lib.ptr(K), int(want), d_out)
+    out = side.get(d_out)
     return out[:, 0], out[:, 1], out[:, 2]
 
 
@@ -215,21 +208,13 @@ def pose_errors_sym(gt_poses, est_poses, model, cam, syms, device=None, want=WAN
             if want & WANT_MSPD:
                 out[p, 1] = mspd_err(gt[p], est[p], model, cam, sym)
         return out[:, 0], out[:, 1]
-    import torch
     from . import _lib
-    _lib.require_gpu()
-    dev = torch.device(device)
+    side = _lib.Side(device)
     K = np.ascontiguousarray(cam, dtype=np.float64).reshape(9) if want & WANT_MSPD else None
-    with torch.cuda.device(dev):
-        d_model = torch.from_numpy(model).to(dev)
-        d_gt = torch.from_numpy(np.ascontiguousarray(gt.reshape(P, 12))).to(dev)
-        d_est = torch.from_numpy(np.ascontiguousarray(est.reshape(P, 12))).to(dev)
-        d_sym = torch.from_numpy(sym.reshape(len(sym), 12)).to(dev)
-        d_out = torch.from_numpy(out).to(dev)
-        _lib.check(_lib.lib().bp_pose_errors_sym(_lib.ptr(d_model), len(model), _lib.ptr(d_gt), _lib.ptr(d_est), P,
-                                                 _lib.ptr(d_sym), len(sym), _lib.ptr(K), int(want), _lib.ptr(d_out),
-                                                 torch.cuda.current_stream(dev).cuda_stream))
-        out = d_out.cpu().numpy()
+    d_out = side.put(out)
+    side.call("bp_pose_errors_sym", side.put(model), len(model), side.put(gt.reshape(P, 12)), side.put(est.reshape(P, 12)), P,
+              side.put(sym), len(sym), _lib.ptr(K), int(want), d_out)
+    out = side.get(d_out)
     return out[:, 0], out[:, 1]
 
 
@@ -400,20 +385,12 @@ def texture_mips(texture, device=None):
         raise ValueError("a texture must not exceed %d x %d (got %d x %d)" % (TEXTURE_MAX_SIZE, TEXTURE_MAX_SIZE, Wt, Ht))
     levels = texture_levels(Wt, Ht)
     texels = _lib.lib().bp_texture_mips_bytes(Wt, Ht, levels) // 4
-    if device is None:
-        data = np.empty(texels, np.uint32)
-        _lib.check(_lib.lib().bp_texture_mips_host(_lib.ptr(tex), Wt, Ht, levels, _lib.ptr(data)))
-        return TextureMips(data, Wt, Ht, levels, None)
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_tex = torch.from_numpy(tex).to(dev)
-        data = torch.empty(texels, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _lib.check(_lib.lib().bp_texture_mips(_lib.ptr(d_tex), Wt, Ht, levels, _lib.ptr(data), stream.cuda_stream))
-        stream.synchronize()       # d_tex is released on return
-    return TextureMips(data, Wt, Ht, levels, dev)
+    side = _lib.Side(device)
+    data = side.empty(texels, np.uint32)
+    side.call("bp_texture_mips", side.put(tex), Wt, Ht, levels, data)
+    if side.dev is not None:
+        side.torch.cuda.current_stream(side.dev).synchronize()       # the uploaded texture is released on return
+    return TextureMips(data, Wt, Ht, levels, side.dev)
 
 
 def _ply_colors(cols, kinds):
@@ -592,25 +569,15 @@ def render_depth(poses, vertices, faces, K, size, device=None, pixel_center=0.0,
     P = len(poses)
     if P == 0:
         return np.zeros((0, H, W), np.float32), np.zeros(0, np.int32)
+    side = _lib.Side(device)
+    d_poses, mesh = side.put(poses), (side.put(vertices), len(vertices), side.put(faces), len(faces))
+    depth, skipped = side.empty((P, H, W), np.float32), side.empty(P, np.int32)
+    rest = (_lib.ptr(Kf), H, W, float(pixel_center), float(near), depth, skipped)
     if device is None:
-        depth, skipped = np.empty((P, H, W), np.float32), np.empty(P, np.int32)
-        _lib.check(_lib.lib().bp_render_depth_host(_lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces),
-                                                   len(faces), _lib.ptr(Kf), H, W, float(pixel_center), float(near),
-                                                   _lib.ptr(depth), _lib.ptr(skipped)))
-        return depth, skipped
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_depth = torch.empty((P, H, W), dtype=torch.float32, device=dev)
-        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_render_depth(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces),
-                                              _lib.ptr(d_poses), P, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
-                                              _lib.ptr(d_depth), _lib.ptr(d_skipped),
-                                              torch.cuda.current_stream(dev).cuda_stream))
-        return d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+        side.call("bp_render_depth", d_poses, P, *mesh, *rest)
+    else:
+        side.call("bp_render_depth", *mesh, d_poses, P, *rest)
+    return side.get(depth), side.get(skipped)
 
 
 def _image_index(image_index, images, P):
@@ -646,14 +613,24 @@ def render_color(poses, vertices, faces, colors, K, size, device=None, image_ind
     from . import _lib
     poses = _poses34(poses)
     vertices, faces = _mesh_args(vertices, faces)
+    mips = None
     if texture is not None:
-        return _render_color_textured(poses, vertices, faces, colors, K, size, device, image_index, images, pixel_center, near,
-                                      ambient, light, into, uv, texture, mip)
-    if uv is not None:
+        if uv is None:
+            raise ValueError("a texture needs uv [F, 3, 2]")
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        if uv.shape != (len(faces), 3, 2):
+            raise ValueError("uv must have the shape [F, 3, 2] = [%d, 3, 2], got %s" % (len(faces), list(uv.shape)))
+        mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, device)
+        on_device = not isinstance(mips.data, np.ndarray)
+        if on_device != (device is not None):
+            raise ValueError("the pyramid was built for %s, the call is for %s: build it with texture_mips(texture, device)" %
+                             (("device %s" % mips.device) if on_device else "the host", device if device is not None else "the host"))
+    elif uv is not None:
         raise ValueError("uv without a texture")
-    colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
-    if len(colors) != len(vertices):
-        raise ValueError("colors needs one row per vertex")
+    else:
+        colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+        if len(colors) != len(vertices):
+            raise ValueError("colors needs one row per vertex")
     H, W = int(size[0]), int(size[1])
     Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
     lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
@@ -669,87 +646,24 @@ def render_color(poses, vertices, faces, colors, K, size, device=None, image_ind
         color, depth = np.zeros((I, H, W, 3), np.uint8), np.zeros((I, H, W), np.float32)
     if P == 0:
         return color, depth, np.zeros(0, np.int32)
-    acc = int(into is not None)
+    side = _lib.Side(device)
+    if mips is not None and device is not None:
+        if mips.data.device != side.dev and not (side.dev.index is None and mips.data.device.type == side.dev.type):
+            raise ValueError("the pyramid lives on %s, the call is for %s" % (mips.data.device, side.dev))
+        side.dev = mips.data.device
+    d_poses, mesh = side.put(poses), (side.put(vertices), len(vertices), side.put(faces), len(faces))
+    if mips is None:
+        name, paint = "bp_render_color", (side.put(colors),)
+    else:       # (the vertex colours are not read)
+        name, paint = "bp_render_color_textured", (None, side.put(uv), mips.data, mips.Wt, mips.Ht, mips.levels if mip else 1)
+    d_color, d_depth, skipped = side.put(color), side.put(depth), side.empty(P, np.int32)
+    rest = (_lib.ptr(index), I, _lib.ptr(Kf), H, W, float(pixel_center), float(near), float(ambient), _lib.ptr(lt),
+            int(into is not None), d_color, d_depth, skipped)
     if device is None:
-        skipped = np.empty(P, np.int32)
-        _lib.check(_lib.lib().bp_render_color_host(_lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces),
-                                                   len(faces), _lib.ptr(colors), _lib.ptr(index), I, _lib.ptr(Kf), H, W,
-                                                   float(pixel_center), float(near), float(ambient), _lib.ptr(lt), acc,
-                                                   _lib.ptr(color), _lib.ptr(depth), _lib.ptr(skipped)))
-        return color, depth, skipped
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_colors = torch.from_numpy(colors).to(dev)
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_color, d_depth = torch.from_numpy(color).to(dev), torch.from_numpy(depth).to(dev)
-        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_render_color(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces),
-                                              _lib.ptr(d_colors), _lib.ptr(d_poses), P, _lib.ptr(index), I, _lib.ptr(Kf), H, W,
-                                              float(pixel_center), float(near), float(ambient), _lib.ptr(lt), acc,
-                                              _lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_skipped),
-                                              torch.cuda.current_stream(dev).cuda_stream))
-        return d_color.cpu().numpy(), d_depth.cpu().numpy(), d_skipped.cpu().numpy()
-
-
-def _render_color_textured(poses, vertices, faces, colors, K, size, device, image_index, images, pixel_center, near, ambient,
-                           light, into, uv, texture, mip):
-    """render_color's textured branch (poses, vertices and faces already in their call form)."""
-    from . import _lib
-    if uv is None:
-        raise ValueError("a texture needs uv [F, 3, 2]")
-    uv = np.ascontiguousarray(uv, dtype=np.float64)
-    if uv.shape != (len(faces), 3, 2):
-        raise ValueError("uv must have the shape [F, 3, 2] = [%d, 3, 2], got %s" % (len(faces), list(uv.shape)))
-    mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, device)
-    on_device = not isinstance(mips.data, np.ndarray)
-    if on_device != (device is not None):
-        raise ValueError("the pyramid was built for %s, the call is for %s: build it with texture_mips(texture, device)" %
-                         (("device %s" % mips.device) if on_device else "the host", device if device is not None else "the host"))
-    levels = mips.levels if mip else 1
-    H, W = int(size[0]), int(size[1])
-    Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
-    lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
-    P = len(poses)
-    index, I = _image_index(image_index, images, P)
-    if into is not None:
-        color = np.array(into[0], dtype=np.uint8, order="C")
-        depth = np.array(into[1], dtype=np.float32, order="C")
-        I = len(depth) if images is None else I
-        if color.shape != (I, H, W, 3) or depth.shape != (I, H, W):
-            raise ValueError("into=(color, depth) must have the shapes [I, H, W, 3] and [I, H, W]")
+        side.call(name, d_poses, P, *mesh, *paint, *rest)
     else:
-        color, depth = np.zeros((I, H, W, 3), np.uint8), np.zeros((I, H, W), np.float32)
-    if P == 0:
-        return color, depth, np.zeros(0, np.int32)
-    acc = int(into is not None)
-    if device is None:
-        skipped = np.empty(P, np.int32)
-        _lib.check(_lib.lib().bp_render_color_textured_host(
-            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), None, _lib.ptr(uv),
-            _lib.ptr(mips.data), mips.Wt, mips.Ht, levels, _lib.ptr(index), I, _lib.ptr(Kf), H, W, float(pixel_center),
-            float(near), float(ambient), _lib.ptr(lt), acc, _lib.ptr(color), _lib.ptr(depth), _lib.ptr(skipped)))
-        return color, depth, skipped
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    if mips.data.device != dev and not (dev.index is None and mips.data.device.type == dev.type):
-        raise ValueError("the pyramid lives on %s, the call is for %s" % (mips.data.device, dev))
-    with torch.cuda.device(mips.data.device):
-        dev = mips.data.device
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_uv = torch.from_numpy(uv).to(dev)
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_color, d_depth = torch.from_numpy(color).to(dev), torch.from_numpy(depth).to(dev)
-        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_render_color_textured(
-            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), None, _lib.ptr(d_uv), _lib.ptr(mips.data), mips.Wt,
-            mips.Ht, levels, _lib.ptr(d_poses), P, _lib.ptr(index), I, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
-            float(ambient), _lib.ptr(lt), acc, _lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_skipped),
-            torch.cuda.current_stream(dev).cuda_stream))
-        return d_color.cpu().numpy(), d_depth.cpu().numpy(), d_skipped.cpu().numpy()
+        side.call(name, *mesh, *paint, d_poses, P, *rest)
+    return side.get(d_color), side.get(d_depth), side.get(skipped)
 
 
 # Model3D._compute_bbox of the reference (utils/model.py:50-72): the corners of the axis-aligned box, x outermost, then
@@ -788,21 +702,11 @@ def draw_boxes(color, poses, corners, K, corner_colors=None, device=None, image_
     if P == 0:
         return color
     index, _ = _image_index(image_index, I, P)
-    if device is None:
-        _lib.check(_lib.lib().bp_draw_boxes_host(_lib.ptr(poses), P, _lib.ptr(corners), _lib.ptr(cc), _lib.ptr(index), I,
-                                                 _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(color)))
-        return color
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_corners, d_cc = torch.from_numpy(corners).to(dev), torch.from_numpy(cc).to(dev)
-        d_color = torch.from_numpy(color).to(dev)
-        _lib.check(_lib.lib().bp_draw_boxes(_lib.ptr(d_poses), P, _lib.ptr(d_corners), _lib.ptr(d_cc), _lib.ptr(index), I,
-                                            _lib.ptr(Kf), H, W, float(pixel_center), float(near), _lib.ptr(d_color),
-                                            torch.cuda.current_stream(dev).cuda_stream))
-        return d_color.cpu().numpy()
+    side = _lib.Side(device)
+    d_color = side.put(color)
+    side.call("bp_draw_boxes", side.put(poses), P, side.put(corners), side.put(cc), _lib.ptr(index), I, _lib.ptr(Kf), H, W,
+              float(pixel_center), float(near), d_color)
+    return side.get(d_color)
 
 
 def overlay(frames, color, depth, alpha=128, device=None):
@@ -817,21 +721,10 @@ def overlay(frames, color, depth, alpha=128, device=None):
     I, H, W = depth.shape
     if I == 0:
         return frames.copy()
-    if device is None:
-        out = np.empty_like(frames)
-        _lib.check(_lib.lib().bp_overlay_host(_lib.ptr(frames), _lib.ptr(color), _lib.ptr(depth), I, H, W, int(alpha),
-                                              _lib.ptr(out)))
-        return out
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_frames, d_color = torch.from_numpy(frames).to(dev), torch.from_numpy(color).to(dev)
-        d_depth = torch.from_numpy(depth).to(dev)
-        d_out = torch.empty_like(d_frames)
-        _lib.check(_lib.lib().bp_overlay(_lib.ptr(d_frames), _lib.ptr(d_color), _lib.ptr(d_depth), I, H, W, int(alpha),
-                                         _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy()
+    side = _lib.Side(device)
+    out = side.empty(frames.shape, np.uint8)
+    side.call("bp_overlay", side.put(frames), side.put(color), side.put(depth), I, H, W, int(alpha), out)
+    return side.get(out)
 
 
 def vsd_masks(depth_test, depth_gt, depth_est, K, delta, pixel_center=0.0):
@@ -918,24 +811,14 @@ def pose_errors_vsd(gt_poses, est_poses, vertices, faces, K, depth_test_u16, tes
                 m = vsd_masks(test, dg[j], de[j], K, delta, pixel_center)
                 counts[p] = (int((dg[j] > 0).sum()), int(m["visib_gt"].sum()), int(m["inter"].sum()), int(m["union"].sum()))
         return err, counts
-    import torch
     from . import _lib
-    _lib.require_gpu()
-    dev = torch.device(device)
+    side = _lib.Side(device)
     Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
-    with torch.cuda.device(dev):
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_gt, d_est = torch.from_numpy(gt.reshape(P, 12)).to(dev), torch.from_numpy(est.reshape(P, 12)).to(dev)
-        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
-        d_idx = torch.from_numpy(idx).to(dev)
-        d_err = torch.empty((P, len(taus)), dtype=torch.float64, device=dev)
-        d_counts = torch.empty((P, 4), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_vsd_errors(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_gt),
-                                            _lib.ptr(d_est), P, _lib.ptr(Kf), _lib.ptr(d_test), T, H, W, float(depth_scale),
-                                            _lib.ptr(d_idx), float(delta), _lib.ptr(taus), len(taus), float(diameter),
-                                            float(pixel_center), float(near), int(chunk), _lib.ptr(d_err), _lib.ptr(d_counts),
-                                            torch.cuda.current_stream(dev).cuda_stream))
-        return d_err.cpu().numpy(), d_counts.cpu().numpy()
+    d_err, d_counts = side.empty((P, len(taus)), np.float64), side.empty((P, 4), np.int32)
+    side.call("bp_vsd_errors", side.put(vertices), len(vertices), side.put(faces), len(faces), side.put(gt), side.put(est), P,
+              _lib.ptr(Kf), side.put(dtest), T, H, W, float(depth_scale), side.put(idx), float(delta), _lib.ptr(taus), len(taus),
+              float(diameter), float(pixel_center), float(near), int(chunk), d_err, d_counts)
+    return side.get(d_err), side.get(d_counts)
 
 
 # ---- pose verification by gradient agreement (csrc/verify.hip, verify_host.cpp)
@@ -970,20 +853,10 @@ def image_gradients(images, red_channel=0, min_sq=VERIFY_SCENE_MIN_SQ, device=No
     images = _verify_images(images, "images")
     I, H, W = images.shape[:3]
     red = _red(red_channel)
-    if device is None:
-        grads, mags = np.zeros((I, H, W, 2), np.float32), np.zeros((I, H, W), np.float32)
-        _lib.check(_lib.lib().bp_image_gradients_host(_lib.ptr(images), I, H, W, red, int(min_sq), _lib.ptr(grads), _lib.ptr(mags)))
-        return grads, mags
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_images = torch.from_numpy(images).to(dev)
-        d_grads = torch.empty((I, H, W, 2), dtype=torch.float32, device=dev)
-        d_mags = torch.empty((I, H, W), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().bp_image_gradients(_lib.ptr(d_images), I, H, W, red, int(min_sq), _lib.ptr(d_grads), _lib.ptr(d_mags),
-                                                 torch.cuda.current_stream(dev).cuda_stream))
-        return d_grads.cpu().numpy(), d_mags.cpu().numpy()
+    side = _lib.Side(device)
+    grads, mags = side.zeros((I, H, W, 2), np.float32), side.zeros((I, H, W), np.float32)
+    side.call("bp_image_gradients", side.put(images), I, H, W, red, int(min_sq), grads, mags)
+    return side.get(grads), side.get(mags)
 
 
 def gradient_scores(renders, frames_or_grads, frame_index, red_channel=0, render_min_sq=VERIFY_RENDER_MIN_SQ,
@@ -1017,38 +890,22 @@ def gradient_scores(renders, frames_or_grads, frame_index, red_channel=0, render
     scores, sums, counts = np.zeros(P, np.float64), np.zeros(P, np.uint64), np.zeros(P, np.int32)
     if P == 0:
         return scores, sums, counts
-    if device is None:
-        grads = image_gradients(scene, red, scene_min_sq)[0] if is_frames else scene
-        _lib.check(_lib.lib().bp_gradient_scores_host(_lib.ptr(renders), _lib.ptr(grads), _lib.ptr(idx), P, T, H, W, red,
-                                                      int(render_min_sq), _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(scores)))
-        return scores, sums, counts
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        s = torch.cuda.current_stream(dev).cuda_stream
-        d_grads = _device_scene_grads(scene, is_frames, red, scene_min_sq, dev)
-        d_renders, d_idx = torch.from_numpy(renders).to(dev), torch.from_numpy(idx).to(dev)
-        d_sums = torch.empty(P, dtype=torch.int64, device=dev)             # (the bits; the kernel writes uint64)
-        d_counts = torch.empty(P, dtype=torch.int32, device=dev)
-        d_scores = torch.empty(P, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().bp_gradient_scores(_lib.ptr(d_renders), _lib.ptr(d_grads), _lib.ptr(d_idx), P, T, H, W, red,
-                                                 int(render_min_sq), _lib.ptr(d_sums), _lib.ptr(d_counts), _lib.ptr(d_scores), s))
-        return d_scores.cpu().numpy(), d_sums.cpu().numpy().view(np.uint64), d_counts.cpu().numpy()
+    side = _lib.Side(device)
+    d_grads = _scene_grads(side, scene, is_frames, red, scene_min_sq)
+    d_scores, d_sums, d_counts = side.put(scores), side.put(sums), side.put(counts)
+    side.call("bp_gradient_scores", side.put(renders), d_grads, side.put(idx), P, T, H, W, red, int(render_min_sq), d_sums,
+              d_counts, d_scores)
+    return side.get(d_scores), side.get(d_sums, np.uint64), side.get(d_counts)
 
 
-def _device_scene_grads(scene, is_frames, red, scene_min_sq, dev):
-    """The scene's gradients [T, H, W, 2] as a tensor on ``dev`` (inside ``torch.cuda.device(dev)``)."""
-    import torch
-    from . import _lib
+def _scene_grads(side, scene, is_frames, red, scene_min_sq):
+    """The scene's gradients [T, H, W, 2] as a buffer of ``side``: taken from the frames there, or the given ones put there."""
     if not is_frames:
-        return torch.from_numpy(scene).to(dev)
+        return side.put(scene)
     T, H, W = scene.shape[:3]
-    d_frames = torch.from_numpy(scene).to(dev)
-    d_grads = torch.empty((T, H, W, 2), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().bp_image_gradients(_lib.ptr(d_frames), T, H, W, red, int(scene_min_sq), _lib.ptr(d_grads), None,
-                                             torch.cuda.current_stream(dev).cuda_stream))
-    return d_grads
+    grads = side.zeros((T, H, W, 2), np.float32)
+    side.call("bp_image_gradients", side.put(scene), T, H, W, red, int(scene_min_sq), grads, None)
+    return grads
 
 
 def verify_chunk(H, W, P, chunk=0):
@@ -1097,57 +954,38 @@ def verify_poses(poses, vertices, faces, colors, K, frames, frame_index, device=
             scores[s:s + step], sums[s:s + step], counts[s:s + step] = gradient_scores(
                 color, grads, idx[s:s + step], red, render_min_sq)
         return scores, sums, counts, skipped
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    L = _lib.lib()
+    side = _lib.Side(device)
     Kf = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
     lt = np.ascontiguousarray(light, dtype=np.float64).reshape(3)
-    mips = None
     if texture is not None:
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         if uv.shape != (len(faces), 3, 2):
             raise ValueError("uv must have the shape [F, 3, 2] = [%d, 3, 2], got %s" % (len(faces), list(uv.shape)))
-        mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, dev)
+        mips = texture if isinstance(texture, TextureMips) else texture_mips(texture, side.dev)
         if isinstance(mips.data, np.ndarray):
-            raise ValueError("the pyramid was built for the host, the call is for %s" % (dev,))
-        dev = mips.data.device
+            raise ValueError("the pyramid was built for the host, the call is for %s" % (side.dev,))
+        side.dev = mips.data.device
+        name, paint = "bp_render_color_textured", (None, side.put(uv), mips.data, mips.Wt, mips.Ht, mips.levels)
     else:
         colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
         if len(colors) != len(vertices):
             raise ValueError("colors needs one row per vertex")
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        d_grads = _device_scene_grads(frames, True, red, scene_min_sq, dev)
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_colors = torch.from_numpy(colors).to(dev) if mips is None else None
-        d_uv = torch.from_numpy(uv).to(dev) if mips is not None else None
-        d_poses, d_idx = torch.from_numpy(poses.reshape(P, 12)).to(dev), torch.from_numpy(idx).to(dev)
-        d_color = torch.empty((step, H, W, 3), dtype=torch.uint8, device=dev)
-        d_depth = torch.empty((step, H, W), dtype=torch.float32, device=dev)
-        d_sums = torch.empty(P, dtype=torch.int64, device=dev)             # (the bits; the kernel writes uint64)
-        d_counts = torch.empty(P, dtype=torch.int32, device=dev)
-        d_scores = torch.empty(P, dtype=torch.float64, device=dev)
-        d_skipped = torch.empty(P, dtype=torch.int32, device=dev)
-        for s in range(0, P, step):
-            n = min(step, P - s)
-            d_color[:n].zero_()
-            d_depth[:n].zero_()
-            if mips is None:
-                _lib.check(L.bp_render_color(_lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_colors),
-                                             _lib.ptr(d_poses[s:s + n]), n, None, n, _lib.ptr(Kf), H, W, float(pixel_center),
-                                             float(near), float(ambient), _lib.ptr(lt), 0, _lib.ptr(d_color), _lib.ptr(d_depth),
-                                             _lib.ptr(d_skipped[s:s + n]), st))
-            else:
-                _lib.check(L.bp_render_color_textured(
-                    _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), None, _lib.ptr(d_uv), _lib.ptr(mips.data),
-                    mips.Wt, mips.Ht, mips.levels, _lib.ptr(d_poses[s:s + n]), n, None, n, _lib.ptr(Kf), H, W,
-                    float(pixel_center), float(near), float(ambient), _lib.ptr(lt), 0, _lib.ptr(d_color), _lib.ptr(d_depth),
-                    _lib.ptr(d_skipped[s:s + n]), st))
-            _lib.check(L.bp_gradient_scores(_lib.ptr(d_color), _lib.ptr(d_grads), _lib.ptr(d_idx[s:s + n]), n, T, H, W, red,
-                                            int(render_min_sq), _lib.ptr(d_sums[s:s + n]), _lib.ptr(d_counts[s:s + n]),
-                                            _lib.ptr(d_scores[s:s + n]), st))
-        return (d_scores.cpu().numpy(), d_sums.cpu().numpy().view(np.uint64), d_counts.cpu().numpy(), d_skipped.cpu().numpy())
+        name, paint = "bp_render_color", (side.put(colors),)
+    d_grads = _scene_grads(side, frames, True, red, scene_min_sq)
+    mesh = (side.put(vertices), len(vertices), side.put(faces), len(faces))
+    d_poses, d_idx = side.put(poses.reshape(P, 12)), side.put(idx)
+    d_color, d_depth = side.empty((step, H, W, 3), np.uint8), side.empty((step, H, W), np.float32)
+    d_sums, d_counts = side.empty(P, np.uint64), side.empty(P, np.int32)
+    d_scores, d_skipped = side.empty(P, np.float64), side.empty(P, np.int32)
+    for s in range(0, P, step):
+        n = min(step, P - s)
+        d_color[:n].zero_()
+        d_depth[:n].zero_()
+        side.call(name, *mesh, *paint, d_poses[s:s + n], n, None, n, _lib.ptr(Kf), H, W, float(pixel_center), float(near),
+                  float(ambient), _lib.ptr(lt), 0, d_color, d_depth, d_skipped[s:s + n])
+        side.call("bp_gradient_scores", d_color, d_grads, d_idx[s:s + n], n, T, H, W, red, int(render_min_sq), d_sums[s:s + n],
+                  d_counts[s:s + n], d_scores[s:s + n])
+    return side.get(d_scores), side.get(d_sums, np.uint64), side.get(d_counts), side.get(d_skipped)
 
 
 ICP_ACC = 29                                                # csrc/icp.h ICP_ACC
@@ -1179,26 +1017,16 @@ def icp_normal_equations(poses, vertices, faces, K, depth_test_u16, test_index, 
     out = np.zeros((P, ICP_ACC), np.float64)
     if P == 0:
         return out
+    side = _lib.Side(device)
+    d_poses, mesh = side.put(poses), (side.put(vertices), len(vertices), side.put(faces), len(faces))
+    d_out = side.put(out)
+    scan = (_lib.ptr(Kf), side.put(dtest), T, H, W, float(depth_scale), side.put(idx), float(max_dist), float(min_cos),
+            float(pixel_center), float(near))
     if device is None:
-        _lib.check(_lib.lib().bp_icp_normal_equations_host(
-            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), _lib.ptr(Kf), _lib.ptr(dtest),
-            T, H, W, float(depth_scale), _lib.ptr(idx), float(max_dist), float(min_cos), float(pixel_center), float(near),
-            _lib.ptr(out)))
-        return out
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
-        d_idx = torch.from_numpy(idx).to(dev)
-        d_out = torch.empty((P, ICP_ACC), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().bp_icp_normal_equations(
-            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_poses), P, _lib.ptr(Kf),
-            _lib.ptr(d_test), T, H, W, float(depth_scale), _lib.ptr(d_idx), float(max_dist), float(min_cos),
-            float(pixel_center), float(near), int(chunk or 0), _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy()
+        side.call("bp_icp_normal_equations", d_poses, P, *mesh, *scan, d_out)
+    else:
+        side.call("bp_icp_normal_equations", *mesh, d_poses, P, *scan, int(chunk or 0), d_out)
+    return side.get(d_out)
 
 
 def refine_poses_depth(poses, vertices, faces, K, depth_test_u16, test_index, depth_scale=0.001, iterations=8,
@@ -1236,28 +1064,16 @@ def refine_poses_depth(poses, vertices, faces, K, depth_test_u16, test_index, de
     out, stats = poses.copy(), np.zeros((P, 6), np.float64)
     if P == 0:
         return out, stats
+    side = _lib.Side(device)
+    d_poses, mesh = side.put(poses), (side.put(vertices), len(vertices), side.put(faces), len(faces))
+    d_out, d_stats = side.put(out), side.put(stats)
+    scan = (_lib.ptr(Kf), side.put(dtest), T, H, W, float(depth_scale), side.put(idx), int(iterations), float(max_dist),
+            float(min_cos), int(min_pixels), float(pixel_center), float(near))
     if device is None:
-        _lib.check(_lib.lib().bp_refine_depth_host(
-            _lib.ptr(poses), P, _lib.ptr(vertices), len(vertices), _lib.ptr(faces), len(faces), _lib.ptr(Kf), _lib.ptr(dtest),
-            T, H, W, float(depth_scale), _lib.ptr(idx), int(iterations), float(max_dist), float(min_cos), int(min_pixels),
-            float(pixel_center), float(near), _lib.ptr(out), _lib.ptr(stats)))
-        return out, stats
-    import torch
-    _lib.require_gpu()
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        d_model, d_faces = torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev)
-        d_poses = torch.from_numpy(poses.reshape(P, 12)).to(dev)
-        d_test = torch.from_numpy(dtest.view(np.int16)).to(dev)           # (the bits; the kernel reads uint16)
-        d_idx = torch.from_numpy(idx).to(dev)
-        d_out = torch.empty((P, 12), dtype=torch.float64, device=dev)
-        d_stats = torch.empty((P, 6), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().bp_refine_depth(
-            _lib.ptr(d_model), len(vertices), _lib.ptr(d_faces), len(faces), _lib.ptr(d_poses), P, _lib.ptr(Kf),
-            _lib.ptr(d_test), T, H, W, float(depth_scale), _lib.ptr(d_idx), int(iterations), float(max_dist), float(min_cos),
-            int(min_pixels), float(pixel_center), float(near), int(chunk or 0), _lib.ptr(d_out), _lib.ptr(d_stats),
-            torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy().reshape(P, 3, 4), d_stats.cpu().numpy()
+        side.call("bp_refine_depth", d_poses, P, *mesh, *scan, d_out, d_stats)
+    else:
+        side.call("bp_refine_depth", *mesh, d_poses, P, *scan, int(chunk or 0), d_out, d_stats)
+    return side.get(d_out).reshape(P, 3, 4), side.get(d_stats)
 
 
 def refine_keypoints(vertices: np.ndarray, keep: int) -> np.ndarray:

@@ -223,18 +223,6 @@ def _table(params, I, cols, name):
     return t
 
 
-def _torch_device(device):
-    import torch
-    from . import _lib
-    _lib.require_gpu()
-    return torch, torch.device(device)
-
-
-def _upload(torch, dev, a):
-    """A host array on the device (torch warns when it wraps a read-only array: such a one is copied first)."""
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-
-
 def compose_params(images, feather=1, blur=0, gain=(256, 256, 256), offset=(0, 0, 0), sigma=0):
     """The ``params`` table of ``compose`` with the same row for every image: [images, 9] int32.  The defaults are the
     neutral camera (the paste alone) except for the feather; ``feather=0`` makes compose equal metrics.overlay."""
@@ -256,16 +244,10 @@ def procedural_background(images, size, seed, first_image=0, device=None):
     I = int(images)
     if I == 0:
         return np.zeros((0, H, W, 3), np.uint8)
-    if device is None:
-        out = np.empty((I, H, W, 3), np.uint8)
-        _lib.check(_lib.lib().bp_synth_background_host(I, H, W, int(seed), int(first_image), _lib.ptr(out)))
-        return out
-    torch, dev = _torch_device(device)
-    with torch.cuda.device(dev):
-        d_out = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().bp_synth_background(I, H, W, int(seed), int(first_image), _lib.ptr(d_out),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy()
+    side = _lib.Side(device)
+    out = side.empty((I, H, W, 3), np.uint8)
+    side.call("bp_synth_background", I, H, W, int(seed), int(first_image), out)
+    return side.get(out)
 
 
 def background_windows(bank, windows, size, device=None):
@@ -283,17 +265,10 @@ def background_windows(bank, windows, size, device=None):
     I, (Nb, Hb, Wb) = len(windows), bank.shape[:3]
     if I == 0:
         return np.zeros((0, H, W, 3), np.uint8)
-    if device is None:
-        out = np.empty((I, H, W, 3), np.uint8)
-        _lib.check(_lib.lib().bp_synth_windows_host(_lib.ptr(bank), Nb, Hb, Wb, _lib.ptr(windows), I, H, W, _lib.ptr(out)))
-        return out
-    torch, dev = _torch_device(device)
-    with torch.cuda.device(dev):
-        d_bank = _upload(torch, dev, bank)
-        d_out = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().bp_synth_windows(_lib.ptr(d_bank), Nb, Hb, Wb, _lib.ptr(windows), I, H, W, _lib.ptr(d_out),
-                                               torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy()
+    side = _lib.Side(device)
+    out = side.empty((I, H, W, 3), np.uint8)
+    side.call("bp_synth_windows", side.put(bank), Nb, Hb, Wb, _lib.ptr(windows), I, H, W, out)
+    return side.get(out)
 
 
 def compose(background, color, depth, params, seed, first_image=0, device=None):
@@ -314,19 +289,11 @@ def compose(background, color, depth, params, seed, first_image=0, device=None):
     params = _table(params, I, COMPOSE_PARAMS, "params")
     if I == 0:
         return background.copy()
-    if device is None:
-        out = np.empty_like(background)
-        _lib.check(_lib.lib().bp_synth_compose_host(_lib.ptr(background), _lib.ptr(color), _lib.ptr(depth), I, H, W,
-                                                    _lib.ptr(params), int(seed), int(first_image), _lib.ptr(out)))
-        return out
-    torch, dev = _torch_device(device)
-    with torch.cuda.device(dev):
-        d_bg, d_color, d_depth = (_upload(torch, dev, a) for a in (background, color, depth))
-        d_out = torch.empty_like(d_bg)
-        _lib.check(_lib.lib().bp_synth_compose(_lib.ptr(d_bg), _lib.ptr(d_color), _lib.ptr(d_depth), I, H, W, _lib.ptr(params),
-                                               int(seed), int(first_image), _lib.ptr(d_out),
-                                               torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy()
+    side = _lib.Side(device)
+    out = side.empty(background.shape, np.uint8)
+    side.call("bp_synth_compose", side.put(background), side.put(color), side.put(depth), I, H, W, _lib.ptr(params), int(seed),
+              int(first_image), out)
+    return side.get(out)
 
 
 def sensor_depth(depth, depth_scale, params, seed, first_image=0, device=None):
@@ -342,18 +309,11 @@ def sensor_depth(depth, depth_scale, params, seed, first_image=0, device=None):
     params = _table(params, I, SENSOR_PARAMS, "params")
     if I == 0:
         return np.zeros((0, H, W), np.uint16)
-    if device is None:
-        out = np.empty((I, H, W), np.uint16)
-        _lib.check(_lib.lib().bp_synth_sensor_depth_host(_lib.ptr(depth), I, H, W, float(depth_scale), _lib.ptr(params),
-                                                         int(seed), int(first_image), _lib.ptr(out)))
-        return out
-    torch, dev = _torch_device(device)
-    with torch.cuda.device(dev):
-        d_depth = _upload(torch, dev, depth)
-        d_out = torch.empty((I, H, W), dtype=torch.int16, device=dev)      # (the bits; the kernel writes uint16)
-        _lib.check(_lib.lib().bp_synth_sensor_depth(_lib.ptr(d_depth), I, H, W, float(depth_scale), _lib.ptr(params), int(seed),
-                                                    int(first_image), _lib.ptr(d_out), torch.cuda.current_stream(dev).cuda_stream))
-        return d_out.cpu().numpy().view(np.uint16)
+    side = _lib.Side(device)
+    out = side.empty((I, H, W), np.uint16)
+    side.call("bp_synth_sensor_depth", side.put(depth), I, H, W, float(depth_scale), _lib.ptr(params), int(seed),
+              int(first_image), out)
+    return side.get(out, np.uint16)
 
 
 # ---- geometry on the host
@@ -668,21 +628,11 @@ def instance_masks(alone, present=None, device=None):
         raise ValueError("present must be [%d, %d]" % (I, J))
     if I == 0:
         return np.zeros((0, H, W), np.uint8), np.zeros((0, H, W), np.float32), np.zeros((0, J, INSTANCE_STATS), np.int32)
-    if device is None:
-        ids, depth = np.empty((I, H, W), np.uint8), np.empty((I, H, W), np.float32)
-        stats = np.empty((I, J, INSTANCE_STATS), np.int32)
-        _lib.check(_lib.lib().bp_synth_instances_host(_lib.ptr(alone), J, I, H, W, _lib.ptr(pres), _lib.ptr(ids), _lib.ptr(depth),
-                                                      _lib.ptr(stats)))
-        return ids, depth, stats
-    torch, dev = _torch_device(device)
-    with torch.cuda.device(dev):
-        d_alone, d_pres = _upload(torch, dev, alone), _upload(torch, dev, pres)
-        d_ids = torch.empty((I, H, W), dtype=torch.uint8, device=dev)
-        d_depth = torch.empty((I, H, W), dtype=torch.float32, device=dev)
-        d_stats = torch.empty((I, J, INSTANCE_STATS), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_synth_instances(_lib.ptr(d_alone), J, I, H, W, _lib.ptr(d_pres), _lib.ptr(d_ids), _lib.ptr(d_depth),
-                                                 _lib.ptr(d_stats), torch.cuda.current_stream(dev).cuda_stream))
-        return d_ids.cpu().numpy(), d_depth.cpu().numpy(), d_stats.cpu().numpy()
+    side = _lib.Side(device)
+    ids, depth = side.empty((I, H, W), np.uint8), side.empty((I, H, W), np.float32)
+    stats = side.empty((I, J, INSTANCE_STATS), np.int32)
+    side.call("bp_synth_instances", side.put(alone), J, I, H, W, side.put(pres), ids, depth, stats)
+    return side.get(ids), side.get(depth), side.get(stats)
 
 
 def below_visibility(stats, min_visib):

@@ -14,36 +14,16 @@ import os
 
 import numpy as np
 
-from .annotate import _on_device, kpd_targets, kpd_windows
+from . import _lib
+from .annotate import kpd_targets, kpd_windows
 
 MEAN_RGB = (0.406, 0.457, 0.480)
-
-
-def _is_tensor(a):
-    return hasattr(a, "data_ptr")
-
-
-def _host(a, dtype):
-    """A contiguous numpy array of ``dtype`` from an array or a tensor (or None)."""
-    if a is None:
-        return None
-    if _is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, dtype=dtype)
-
-
-def _dev(torch, dev, a, dtype):
-    """A contiguous tensor of ``dtype`` on ``dev`` from an array or a tensor (or None)."""
-    if a is None:
-        return None
-    if not _is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a, dtype=getattr(np, str(dtype).split(".")[-1])))
-    return a.to(device=dev, dtype=dtype).contiguous()
+_np = _lib.Side().put       # (an array, a tensor or None, dtype) -> a contiguous numpy array
 
 
 def _windows(ul, br, B):
-    ul = _host(ul, np.float32).reshape(-1, 2)
-    br = _host(br, np.float32).reshape(-1, 2)
+    ul = _np(ul, np.float32).reshape(-1, 2)
+    br = _np(br, np.float32).reshape(-1, 2)
     if len(ul) != B or len(br) != B:
         raise ValueError("ul and br need one row per sample")
     if not (np.isfinite(ul).all() and np.isfinite(br).all()):
@@ -61,8 +41,7 @@ def kpd_inputs(frames, frame_index, ul, br, gains=None, blank=None, in_res=(320,
     im_to_torch skips it for an image whose maximum is 0 or 1); the window is cropBox's: corners truncated toward zero,
     padded with zeros to the input's aspect ratio about its centre (ceil before, floor after), resized bilinearly with
     ``align_corners=True``."""
-    from . import _lib
-    idx = np.ascontiguousarray(_host(frame_index, np.int32)).reshape(-1)
+    idx = np.ascontiguousarray(_np(frame_index, np.int32)).reshape(-1)
     B = len(idx)
     ul, br = _windows(ul, br, B)
     if frames.ndim != 4 or frames.shape[3] != 3 or (frames.dtype != np.uint8 and str(frames.dtype) != "torch.uint8"):
@@ -73,27 +52,16 @@ def kpd_inputs(frames, frame_index, ul, br, gains=None, blank=None, in_res=(320,
     inpH, inpW = int(in_res[0]), int(in_res[1])
     if min(inpH, inpW) < 1:
         raise ValueError("the input resolution must be positive")
-    gains = None if gains is None else _host(gains, np.float32).reshape(-1, 3)
-    blank = None if blank is None else _host(blank, np.uint8).reshape(-1)
+    gains = None if gains is None else _np(gains, np.float32).reshape(-1, 3)
+    blank = None if blank is None else _np(blank, np.uint8).reshape(-1)
     if (gains is not None and len(gains) != B) or (blank is not None and len(blank) != B):
         raise ValueError("gains and blank need one row per sample")
-    if device is None:
-        fr = _host(frames, np.uint8)
-        inp = np.empty((B, 3, inpH, inpW), np.float32)
-        if B:
-            _lib.check(_lib.lib().bp_kpd_inputs_host(_lib.ptr(fr), N, H, W, _lib.ptr(idx), _lib.ptr(ul), _lib.ptr(br),
-                                                     _lib.ptr(gains), _lib.ptr(blank), B, inpH, inpW, _lib.ptr(inp)))
-        return inp
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_fr = _dev(torch, dev, frames, torch.uint8)
-        d = [_dev(torch, dev, a, t) for a, t in ((idx, torch.int32), (ul, torch.float32), (br, torch.float32),
-                                                 (gains, torch.float32), (blank, torch.uint8))]
-        inp = torch.empty((B, 3, inpH, inpW), dtype=torch.float32, device=dev)
-        if B:
-            _lib.check(_lib.lib().bp_kpd_inputs(_lib.ptr(d_fr), N, H, W, *(_lib.ptr(a) for a in d), B, inpH, inpW, _lib.ptr(inp),
-                                                torch.cuda.current_stream(dev).cuda_stream))
-        return inp
+    side = _lib.Side(device)
+    inp = side.empty((B, 3, inpH, inpW), np.float32)
+    if B:
+        side.call("bp_kpd_inputs", side.put(frames, np.uint8), N, H, W, side.put(idx), side.put(ul), side.put(br), side.put(gains),
+                  side.put(blank), B, inpH, inpW, inp)
+    return inp
 
 
 def channel_table(C, flip_pairs=()):
@@ -126,31 +94,20 @@ def augment_maps(x, flip, angle_deg, flip_pairs=(), device=None):
     ``A = [[cos, -sin], [sin, cos]]`` on (row, col) and centre ``(H/2 - 0.5, W/2 - 0.5)`` in float64, bilinear taps with
     the coordinate clamped to the map (edge replication), blended in float32.  A sample with ``flip = 0`` and
     ``angle = 0`` is copied."""
-    from . import _lib
     if x.ndim != 4:
         raise ValueError("x must be [B, C, H, W]")
     B, C, H, W = (int(v) for v in x.shape)
-    flip = _host(flip, np.uint8).reshape(-1)
-    cs = rotation_terms(_host(angle_deg, np.float64))
+    flip = _np(flip, np.uint8).reshape(-1)
+    cs = rotation_terms(_np(angle_deg, np.float64))
     if len(flip) != B or len(cs) != B:
         raise ValueError("flip and angle_deg need one entry per sample")
     perm = channel_table(C, flip_pairs) if len(flip_pairs) else None
-    if device is None:
-        xh = _host(x, np.float32)
-        y = np.empty_like(xh)
-        if xh.size:
-            _lib.check(_lib.lib().bp_kpd_augment_host(_lib.ptr(xh), B, C, H, W, _lib.ptr(flip), _lib.ptr(cs), _lib.ptr(perm),
-                                                      _lib.ptr(y)))
-        return y
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_x = _dev(torch, dev, x, torch.float32)
-        d_flip, d_cs, d_perm = _dev(torch, dev, flip, torch.uint8), _dev(torch, dev, cs, torch.float64), _dev(torch, dev, perm, torch.int32)
-        y = torch.empty_like(d_x)
-        if d_x.numel():
-            _lib.check(_lib.lib().bp_kpd_augment(_lib.ptr(d_x), B, C, H, W, _lib.ptr(d_flip), _lib.ptr(d_cs), _lib.ptr(d_perm),
-                                                 _lib.ptr(y), torch.cuda.current_stream(dev).cuda_stream))
-        return y
+    side = _lib.Side(device)
+    d_x = side.put(x, np.float32)
+    y = side.empty(tuple(d_x.shape), np.float32)
+    if B * C * H * W:
+        side.call("bp_kpd_augment", d_x, B, C, H, W, side.put(flip), side.put(cs), side.put(perm), y)
+    return y
 
 
 def _loss_shapes(out, labels, set_mask):
@@ -162,22 +119,17 @@ def _loss_shapes(out, labels, set_mask):
     return B, K, H, W
 
 
-def _loss_device(torch, dev, out, labels, set_mask, want_grad):
-    """The device call on device tensors: a dict of device tensors (``loss`` [1] float64)."""
-    from . import _lib
+def _loss_call(side, out, labels, set_mask, want_grad):
+    """bp_heatmap_loss_acc on ``side``: a dict of its buffers (``loss`` [1] float64)."""
     B, K, H, W = _loss_shapes(out, labels, set_mask)
-    with torch.cuda.device(dev):
-        d_out, d_lab, d_mask = (_dev(torch, dev, a, torch.float32) for a in (out, labels, set_mask))
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        r = {"loss": new((1,), torch.float64), "acc": new((K + 1,), torch.float32), "preds": new((B, K, 2), torch.int32),
-             "gt": new((B, K, 2), torch.int32), "dists": new((K, B), torch.float32),
-             "grad": torch.empty_like(d_out) if want_grad else None}
-        partial = new((B * K,), torch.float64)
-        _lib.check(_lib.lib().bp_heatmap_loss_acc(_lib.ptr(d_out), _lib.ptr(d_lab), _lib.ptr(d_mask), B, K, H, W, _lib.ptr(partial),
-                                                  _lib.ptr(r["loss"]), _lib.ptr(r["acc"]), _lib.ptr(r["preds"]), _lib.ptr(r["gt"]),
-                                                  _lib.ptr(r["dists"]), _lib.ptr(r["grad"]),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
-        return r
+    d_out, d_lab, d_mask = (side.put(a, np.float32) for a in (out, labels, set_mask))
+    r = {"loss": side.empty(1, np.float64), "acc": side.empty(K + 1, np.float32), "preds": side.empty((B, K, 2), np.int32),
+         "gt": side.empty((B, K, 2), np.int32), "dists": side.empty((K, B), np.float32),
+         "grad": side.empty((B, K, H, W), np.float32) if want_grad else None}
+    partial = side.empty(B * K, np.float64)
+    side.call("bp_heatmap_loss_acc", d_out, d_lab, d_mask, B, K, H, W, partial, r["loss"], r["acc"], r["preds"], r["gt"],
+              r["dists"], r["grad"])
+    return r
 
 
 def heatmap_loss_accuracy(out, labels, set_mask=None, want_grad=False, device=None):
@@ -191,22 +143,11 @@ def heatmap_loss_accuracy(out, labels, set_mask=None, want_grad=False, device=No
     among equal maxima; ``dists`` [K, B] float32 calc_dists with ``norm = H / 10``, -1 unless ``gt.x > 0 and gt.y > 0``;
     ``grad`` [B, K, H, W] float32 = ``((float32)(2 / N) * (out * mask - labels)) * mask`` with ``want_grad``, else None
     (a tensor on ``device``; everything else is returned on the host)."""
-    from . import _lib
-    B, K, H, W = _loss_shapes(out, labels, set_mask)
-    if device is None:
-        o, l, m = (_host(a, np.float32) for a in (out, labels, set_mask))
-        loss, acc = np.empty(1, np.float64), np.empty(K + 1, np.float32)
-        preds, gt, dists = np.empty((B, K, 2), np.int32), np.empty((B, K, 2), np.int32), np.empty((K, B), np.float32)
-        grad = np.empty((B, K, H, W), np.float32) if want_grad else None
-        partial = np.empty(B * K, np.float64)
-        _lib.check(_lib.lib().bp_heatmap_loss_acc_host(_lib.ptr(o), _lib.ptr(l), _lib.ptr(m), B, K, H, W, _lib.ptr(partial),
-                                                       _lib.ptr(loss), _lib.ptr(acc), _lib.ptr(preds), _lib.ptr(gt),
-                                                       _lib.ptr(dists), _lib.ptr(grad)))
-        return float(loss[0]), acc, preds, gt, dists, grad
-    torch, dev = _on_device(device)
-    r = _loss_device(torch, dev, out, labels, set_mask, want_grad)
-    return (float(r["loss"].cpu()[0]), r["acc"].cpu().numpy(), r["preds"].cpu().numpy(), r["gt"].cpu().numpy(),
-            r["dists"].cpu().numpy(), r["grad"])
+    _loss_shapes(out, labels, set_mask)
+    side = _lib.Side(device)
+    r = _loss_call(side, out, labels, set_mask, want_grad)
+    return (float(side.get(r["loss"])[0]), side.get(r["acc"]), side.get(r["preds"]), side.get(r["gt"]), side.get(r["dists"]),
+            r["grad"])
 
 
 def _heatmap_mse_class():
@@ -221,7 +162,7 @@ def _heatmap_mse_class():
 
         @staticmethod
         def forward(ctx, out, labels, set_mask=None):
-            r = _loss_device(torch, out.device, out.detach(), labels.detach(), None if set_mask is None else set_mask.detach(), True)
+            r = _loss_call(_lib.Side(out.device), out.detach(), labels.detach(), None if set_mask is None else set_mask.detach(), True)
             ctx.save_for_backward(r["grad"])
             HeatmapMSE.last = {k: r[k] for k in ("acc", "preds", "gt", "dists")}
             return r["loss"][0].to(torch.float32)

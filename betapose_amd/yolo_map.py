@@ -11,17 +11,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .annotate import _on_device
-from .train_data import _dev, _host
+from .train_data import _np
 
 STAT_NAMES = ("mAP", "precision", "recall", "f1", "avg_iou", "tp", "fp", "fn")
 REC = 6     # words of a record: p, image, class, truth, max_iou, position within the image
-
-
-def _stream(torch, dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def heads_table(shapes):
     """The head table of yolo_detections from ``shapes`` = [(anchors, gh, gw), ...] in the order of the cfg's ``[yolo]``
     blocks: int32 [nheads, 4] = (first row, anchors, gh, gw)."""
@@ -67,13 +60,13 @@ def max_dets_cap():
     return int(_lib.lib().bp_yolo_map_max_dets())
 
 
-def _detections_host(pred, heads, net_size, classes, thresh, nms, max_dets):
+def _detections(side, pred, heads, net_size, classes, thresh, nms, max_dets):
     from . import _lib
-    B, rows, attrs = pred.shape
-    dets = np.empty((B, max_dets, 6 + classes), np.float32)
-    count = np.empty(B, np.int32)
-    _lib.check(_lib.lib().bp_yolo_detections_host(_lib.ptr(pred), B, rows, attrs, _lib.ptr(heads), len(heads), int(net_size[1]),
-                                                  int(net_size[0]), classes, thresh, nms, max_dets, _lib.ptr(dets), _lib.ptr(count)))
+    B, rows, attrs = (int(v) for v in pred.shape)
+    dets, count = side.empty((B, max_dets, 6 + classes), np.float32), side.empty(B, np.int32)
+    scratch = [] if side.dev is None else [side.empty(max(int(_lib.lib().bp_yolo_detections_scratch(B, max_dets, classes)), 4) // 4)]
+    side.call("bp_yolo_detections", side.put(pred, np.float32), B, rows, attrs, _lib.ptr(heads), len(heads), int(net_size[1]),
+              int(net_size[0]), classes, thresh, nms, max_dets, dets, count, *scratch)
     return dets, count
 
 
@@ -90,29 +83,12 @@ def yolo_detections(pred, heads, net_size, classes, thresh=.005, nms=.45, max_de
     heads = np.ascontiguousarray(heads, np.int32).reshape(-1, 4)
     if pred.ndim != 3 or int(pred.shape[2]) != 5 + classes:
         raise ValueError("pred must be [B, rows, 5 + classes]")
-    B, rows, attrs = (int(v) for v in pred.shape)
-    if device is None:
-        p = _host(pred, np.float32)
-        dets, count = _detections_host(p, heads, net_size, classes, thresh, nms, max_dets)
-        over = np.nonzero(count > max_dets)[0]
-    else:
-        torch, dev = _on_device(device)
-        with torch.cuda.device(dev):
-            d_p = _dev(torch, dev, pred, torch.float32)
-            dets = torch.empty((B, max_dets, 6 + classes), dtype=torch.float32, device=dev)
-            count = torch.empty((B,), dtype=torch.int32, device=dev)
-            scratch = torch.empty((max(int(_lib.lib().bp_yolo_detections_scratch(B, max_dets, classes)), 4) // 4,),
-                                  dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().bp_yolo_detections(_lib.ptr(d_p), B, rows, attrs, _lib.ptr(heads), len(heads), int(net_size[1]),
-                                                     int(net_size[0]), classes, thresh, nms, max_dets, _lib.ptr(dets),
-                                                     _lib.ptr(count), _lib.ptr(scratch), _stream(torch, dev)))
-            c = count.cpu().numpy()
-        over = np.nonzero(c > max_dets)[0]
-        p = None
+    rows = int(pred.shape[1])
+    side = _lib.Side(device)
+    dets, count = _detections(side, pred, heads, net_size, classes, thresh, nms, max_dets)
     overflow = {}
-    for b in over:
-        one = _host(pred[int(b):int(b) + 1], np.float32)
-        d, c1 = _detections_host(one, heads, net_size, classes, thresh, nms, rows)
+    for b in np.nonzero(side.get(count) > max_dets)[0]:
+        d, c1 = _detections(_lib.Side(), pred[int(b):int(b) + 1], heads, net_size, classes, thresh, nms, rows)
         overflow[int(b)] = d[0, :int(c1[0])].copy()
     return dets, count, overflow
 
@@ -125,43 +101,26 @@ def map_match(dets, count, labels, first, classes, iou_thresh=.5, thresh_calc=.2
     ``truth_classes_count`` [classes] int32 (the one passed in, added to) and ``img_stats`` [B, 3] float64 = (tp, fp,
     iou_sum) at ``thresh_calc``.  ``rec_stride`` defaults to what the largest image needs."""
     from . import _lib
-    labels = _host(labels, np.float32).reshape(-1, 5)
-    first = _host(first, np.int32).reshape(-1)
+    labels = _np(labels, np.float32).reshape(-1, 5)
+    first = _np(first, np.int32).reshape(-1)
     M, B, max_dets = len(labels), len(first) - 1, int(dets.shape[1])
     if dets.ndim != 3 or int(dets.shape[0]) != B or int(dets.shape[2]) != 6 + classes:
         raise ValueError("dets must be [B, max_dets, 6 + classes] and first hold B + 1 entries")
     if first[0] < 0 or first[-1] > M or (np.diff(first) < 0).any():
         raise ValueError("first must be non-decreasing within [0, M]")
-    if device is None:
-        d, c = _host(dets, np.float32), _host(count, np.int32)
-        if rec_stride is None:
-            rec_stride = max(int(np.where(c > max_dets, 0, c).max(initial=0)) * classes, 1)
-        tcc = np.zeros(classes, np.int32) if truth_classes_count is None else truth_classes_count
-        r = dict(rec=np.empty((B, rec_stride, REC), np.float32), rec_count=np.empty(B, np.int32), truth_classes_count=tcc,
-                 img_stats=np.empty((B, 3), np.float64))
-        _lib.check(_lib.lib().bp_detector_map_match_host(_lib.ptr(d), _lib.ptr(c), B, max_dets, classes, _lib.ptr(labels), M,
-                                                         _lib.ptr(first), iou_thresh, thresh_calc, truth_base, image_base,
-                                                         rec_stride, _lib.ptr(r["rec"]), _lib.ptr(r["rec_count"]), _lib.ptr(tcc),
-                                                         _lib.ptr(r["img_stats"])))
-        return r
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d, c = _dev(torch, dev, dets, torch.float32), _dev(torch, dev, count, torch.int32)
-        if rec_stride is None:
-            ch = c.cpu().numpy()
-            rec_stride = max(int(np.where(ch > max_dets, 0, ch).max(initial=0)) * classes, 1)
-        d_l = _dev(torch, dev, labels if M else np.zeros((1, 5), np.float32), torch.float32)
-        d_f = _dev(torch, dev, first, torch.int32)
-        tcc = torch.zeros((classes,), dtype=torch.int32, device=dev) if truth_classes_count is None else truth_classes_count
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        r = dict(rec=new((B, rec_stride, REC), torch.float32), rec_count=new((B,), torch.int32), truth_classes_count=tcc,
-                 img_stats=new((B, 3), torch.float64))
-        claim = new((M + 1,), torch.int32)
-        _lib.check(_lib.lib().bp_detector_map_match(_lib.ptr(d), _lib.ptr(c), B, max_dets, classes, _lib.ptr(d_l), M, _lib.ptr(d_f),
-                                                    iou_thresh, thresh_calc, truth_base, image_base, rec_stride, _lib.ptr(r["rec"]),
-                                                    _lib.ptr(r["rec_count"]), _lib.ptr(tcc), _lib.ptr(r["img_stats"]),
-                                                    _lib.ptr(claim), _stream(torch, dev)))
-        return r
+    side = _lib.Side(device)
+    d, c = side.put(dets, np.float32), side.put(count, np.int32)
+    if rec_stride is None:
+        ch = side.get(c)
+        rec_stride = max(int(np.where(ch > max_dets, 0, ch).max(initial=0)) * classes, 1)
+    tcc = side.zeros(classes, np.int32) if truth_classes_count is None else truth_classes_count
+    r = dict(rec=side.empty((B, rec_stride, REC), np.float32), rec_count=side.empty(B, np.int32), truth_classes_count=tcc,
+             img_stats=side.empty((B, 3), np.float64))
+    claim = [] if side.dev is None else [side.empty(M + 1, np.int32)]
+    side.call("bp_detector_map_match", d, c, B, max_dets, classes, side.put(labels if M else np.zeros((1, 5), np.float32)), M,
+              side.put(first), iou_thresh, thresh_calc, truth_base, image_base, rec_stride, r["rec"], r["rec_count"], tcc,
+              r["img_stats"], *claim)
+    return r
 
 
 def map_reduce(rec, truth_classes_count, truths, img_stats, classes, want_pr=False, device=None):
@@ -170,28 +129,14 @@ def map_reduce(rec, truth_classes_count, truths, img_stats, classes, want_pr=Fal
     ``img_stats`` [N, 3] the images' (tp, fp, iou_sum) in index order."""
     from . import _lib
     D, N = int(rec.shape[0]), int(img_stats.shape[0])
-    if device is None:
-        rc, tcc, st = _host(rec, np.float32).reshape(-1, REC), _host(truth_classes_count, np.int32), _host(img_stats, np.float64)
-        r = dict(ap=np.empty(classes, np.float64), stats=np.empty(8, np.float64),
-                 pr=np.empty((classes, D, 2), np.float64) if want_pr else None)
-        _lib.check(_lib.lib().bp_detector_map_reduce_host(_lib.ptr(rc) if D else None, D, _lib.ptr(tcc), classes, int(truths),
-                                                          _lib.ptr(st) if N else None, N, _lib.ptr(r["ap"]), _lib.ptr(r["stats"]),
-                                                          _lib.ptr(r["pr"]) if want_pr and D else None))
-        return r
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        rc = _dev(torch, dev, rec, torch.float32) if D else None
-        tcc = _dev(torch, dev, truth_classes_count, torch.int32)
-        st = _dev(torch, dev, img_stats, torch.float64) if N else None
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        r = dict(ap=new((classes,), torch.float64), stats=new((8,), torch.float64),
-                 pr=new((classes, D, 2), torch.float64) if want_pr else None)
-        scratch = new((max(int(_lib.lib().bp_detector_map_reduce_scratch(D, int(truths))), 8) // 8 + 1,), torch.int64)
-        _lib.check(_lib.lib().bp_detector_map_reduce(_lib.ptr(rc), D, _lib.ptr(tcc), classes, int(truths), _lib.ptr(st), N,
-                                                     _lib.ptr(r["ap"]), _lib.ptr(r["stats"]),
-                                                     _lib.ptr(r["pr"]) if want_pr and D else None, _lib.ptr(scratch),
-                                                     _stream(torch, dev)))
-        return r
+    side = _lib.Side(device)
+    r = dict(ap=side.empty(classes, np.float64), stats=side.empty(8, np.float64),
+             pr=side.empty((classes, D, 2), np.float64) if want_pr else None)
+    scratch = [] if side.dev is None else [side.empty(max(int(_lib.lib().bp_detector_map_reduce_scratch(D, int(truths))), 8) // 8 + 1,
+                                                      np.int64)]
+    side.call("bp_detector_map_reduce", side.put(rec, np.float32) if D else None, D, side.put(truth_classes_count, np.int32), classes,
+              int(truths), side.put(img_stats, np.float64) if N else None, N, r["ap"], r["stats"], r["pr"] if D else None, *scratch)
+    return r
 
 
 class DetectorMap:
@@ -222,8 +167,8 @@ class DetectorMap:
         calls); a list that is walked in another order names both, and gives the same result."""
         classes, dev = self.classes, self.device
         tb = self.truths if truth_base is None else int(truth_base)
-        labels = _host(labels, np.float32).reshape(-1, 5)
-        first = _host(first, np.int32).reshape(-1)
+        labels = _np(labels, np.float32).reshape(-1, 5)
+        first = _np(first, np.int32).reshape(-1)
         B = len(first) - 1
         base = self.images if image_base is None else int(image_base)
         dets, count, over = yolo_detections(pred, self.heads, self.net_size, classes, self.thresh, self.nms, self.max_dets, dev)
@@ -261,12 +206,12 @@ class DetectorMap:
         st = self._cat([c[2] for c in chunks], 3, np.float64)
         tcc = self.tcc if self.tcc is not None else np.zeros(self.classes, np.int32)
         r = map_reduce(rec, tcc, self.truths, st, self.classes, want_pr, self.device)
-        ap, stats = (_host(r[k], np.float64) for k in ("ap", "stats"))
+        ap, stats = (_np(r[k], np.float64) for k in ("ap", "stats"))
         out = dict(zip(STAT_NAMES, stats.tolist()))
         for k in ("tp", "fp", "fn"):
             out[k] = int(out[k])
         out.update(ap=ap, detections_count=int(rec.shape[0]), unique_truth_count=int(self.truths),
-                   truth_classes_count=_host(tcc, np.int32).copy(), overflow_images=sorted(self.overflow), thresh_calc=self.thresh_calc,
+                   truth_classes_count=_np(tcc, np.int32).copy(), overflow_images=sorted(self.overflow), thresh_calc=self.thresh_calc,
                    pr=r["pr"])
         return out
 

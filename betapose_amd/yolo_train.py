@@ -13,16 +13,9 @@ import os
 
 import numpy as np
 
-from .annotate import _on_device
-from .train_data import _dev, _host, save_npz  # noqa: F401  (save_npz is part of this module's surface)
+from .train_data import _np, save_npz  # noqa: F401  (save_npz is part of this module's surface)
 
 STAT_NAMES = ("iou", "class", "obj", "anyobj", "recall50", "recall75", "count")
-
-
-def _stream(torch, dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 # ------------------------------------------------------------------------------------------------ inputs
 def yolo_inputs(frames, frame_index, crop, flip, hsv=None, net_size=(416, 416), device=None, out=None):
     """One sample of load_data_detection per row, without its random draws: ``out`` [B, 3, net_h, net_w] float32, a numpy
@@ -31,34 +24,24 @@ def yolo_inputs(frames, frame_index, crop, flip, hsv=None, net_size=(416, 416), 
     [B, 4] int32 = (pleft, ptop, swidth, sheight), ``flip`` [B], ``hsv`` [B, 3] float32 = (dhue, dsat, dexp) or None
     for no distortion, ``net_size`` = (net_h, net_w).  ``out`` may name the tensor (device) to write."""
     from . import _lib
-    idx = _host(frame_index, np.int32).reshape(-1)
+    idx = _np(frame_index, np.int32).reshape(-1)
     B = len(idx)
-    crop = _host(crop, np.int32).reshape(-1, 4)
-    flip = _host(flip, np.uint8).reshape(-1)
-    hsv = None if hsv is None else _host(hsv, np.float32).reshape(-1, 3)
+    crop = _np(crop, np.int32).reshape(-1, 4)
+    flip = _np(flip, np.uint8).reshape(-1)
+    hsv = None if hsv is None else _np(hsv, np.float32).reshape(-1, 3)
     if len(crop) != B or len(flip) != B or (hsv is not None and len(hsv) != B):
         raise ValueError("crop, flip and hsv need one row per sample")
     if frames.ndim != 4 or frames.shape[3] != 3 or (frames.dtype != np.uint8 and str(frames.dtype) != "torch.uint8"):
         raise ValueError("frames must be uint8 [N, H, W, 3]")
     N, H, W = (int(v) for v in frames.shape[:3])
     net_h, net_w = int(net_size[0]), int(net_size[1])
-    if device is None:
-        fr = _host(frames, np.uint8)
-        res = np.empty((B, 3, net_h, net_w), np.float32)
-        _lib.check(_lib.lib().bp_yolo_inputs_host(_lib.ptr(fr), N, H, W, _lib.ptr(idx), _lib.ptr(crop), _lib.ptr(flip),
-                                                  _lib.ptr(hsv), B, net_h, net_w, _lib.ptr(res)))
-        return res
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        d_fr = _dev(torch, dev, frames, torch.uint8)
-        d = [_dev(torch, dev, a, t) for a, t in ((idx, torch.int32), (crop, torch.int32), (flip, torch.uint8),
-                                                 (hsv, torch.float32))]
-        res = torch.empty((B, 3, net_h, net_w), dtype=torch.float32, device=dev) if out is None else out
-        if tuple(res.shape) != (B, 3, net_h, net_w) or res.dtype != torch.float32:
-            raise ValueError("out must be float32 [B, 3, net_h, net_w]")
-        _lib.check(_lib.lib().bp_yolo_inputs(_lib.ptr(d_fr), N, H, W, *(_lib.ptr(a) for a in d), B, net_h, net_w, _lib.ptr(res),
-                                             _stream(torch, dev)))
-        return res
+    side = _lib.Side(device)
+    res = side.empty((B, 3, net_h, net_w), np.float32) if device is None or out is None else out
+    if res is out and (tuple(res.shape) != (B, 3, net_h, net_w) or res.dtype != side.torch.float32):
+        raise ValueError("out must be float32 [B, 3, net_h, net_w]")
+    side.call("bp_yolo_inputs", side.put(frames, np.uint8), N, H, W, side.put(idx), side.put(crop), side.put(flip), side.put(hsv),
+              B, net_h, net_w, res)
+    return res
 
 
 # ------------------------------------------------------------------------------------------------ truth rows
@@ -69,37 +52,25 @@ def yolo_truth(labels, first, swap, geom, flip, classes=1, max_boxes=90, net_siz
     [B, 4] float32 = (dx, dy, sx, sy) as load_data_detection passes them, ``flip`` [B].  A truth row is (x, y, w, h,
     id); the rows past ``kept[b]`` are zero.  The list is cut to ``max_boxes`` before the filter, as in the reference."""
     from . import _lib
-    labels = _host(labels, np.float32).reshape(-1, 5)
+    labels = _np(labels, np.float32).reshape(-1, 5)
     M = len(labels)
-    first = _host(first, np.int32).reshape(-1)
+    first = _np(first, np.int32).reshape(-1)
     B = len(first) - 1
-    swap = _host(swap, np.int32).reshape(-1)
-    geom = _host(geom, np.float32).reshape(-1, 4)
-    flip = _host(flip, np.uint8).reshape(-1)
+    swap = _np(swap, np.int32).reshape(-1)
+    geom = _np(geom, np.float32).reshape(-1, 4)
+    flip = _np(flip, np.uint8).reshape(-1)
     if B < 1 or len(swap) != M or len(geom) != B or len(flip) != B:
         raise ValueError("first needs B + 1 entries, swap one per label, geom and flip one row per sample")
     net_h, net_w = int(net_size[0]), int(net_size[1])
-    if device is None:
-        order = np.empty(max(M, 1), np.int32)
-        truth, kept = np.empty((B, max_boxes, 5), np.float32), np.empty(B, np.int32)
-        _lib.check(_lib.lib().bp_yolo_truth_host(_lib.ptr(labels), M, _lib.ptr(first), _lib.ptr(swap), _lib.ptr(geom),
-                                                 _lib.ptr(flip), B, classes, max_boxes, net_w, net_h, small_object, _lib.ptr(order),
-                                                 _lib.ptr(truth), _lib.ptr(kept)))
-        return truth, kept
-    if first[0] < 0 or first[-1] > M or (np.diff(first) < 0).any():
+    if device is not None and (first[0] < 0 or first[-1] > M or (np.diff(first) < 0).any()):
         raise ValueError("first must be non-decreasing within [0, M]")
-    torch, dev = _on_device(device)
-    with torch.cuda.device(dev):
-        pad = lambda a, shape: a if M else np.zeros(shape, a.dtype)   # (an empty tensor has no address)
-        d = [_dev(torch, dev, a, t) for a, t in ((pad(labels, (1, 5)), torch.float32), (first, torch.int32),
-                                                 (pad(swap, (1,)), torch.int32), (geom, torch.float32), (flip, torch.uint8))]
-        order = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
-        truth = torch.empty((B, max_boxes, 5), dtype=torch.float32, device=dev)
-        kept = torch.empty((B,), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().bp_yolo_truth(_lib.ptr(d[0]), M, _lib.ptr(d[1]), _lib.ptr(d[2]), _lib.ptr(d[3]), _lib.ptr(d[4]), B,
-                                            classes, max_boxes, net_w, net_h, small_object, _lib.ptr(order), _lib.ptr(truth),
-                                            _lib.ptr(kept), _stream(torch, dev)))
-        return truth, kept
+    side = _lib.Side(device)
+    pad = lambda a, shape: a if M else np.zeros(shape, a.dtype)   # (an empty tensor has no address)
+    order = side.empty(max(M, 1), np.int32)
+    truth, kept = side.empty((B, max_boxes, 5), np.float32), side.empty(B, np.int32)
+    side.call("bp_yolo_truth", side.put(pad(labels, (1, 5))), M, side.put(first), side.put(pad(swap, (1,))), side.put(geom),
+              side.put(flip), B, classes, max_boxes, net_w, net_h, small_object, order, truth, kept)
+    return truth, kept
 
 
 # ------------------------------------------------------------------------------------------------ loss
@@ -110,24 +81,21 @@ def _loss_shapes(x, truth, mask, anchors, classes):
     return B, C, h, w, int(truth.shape[1]), len(mask), len(anchors)
 
 
-def _loss_device(torch, dev, x, truth, net_size, anchors, mask, classes, ignore_thresh, truth_thresh, focal_loss, want_act):
-    """The device call on device tensors: a dict of device tensors (``cost`` [1], ``stats`` [7] float64)."""
+def _loss_call(side, x, truth, net_size, anchors, mask, classes, ignore_thresh, truth_thresh, focal_loss, want_act):
+    """bp_yolo_loss on ``side``: a dict of its buffers (``cost`` [1], ``stats`` [7] float64)."""
     from . import _lib
-    anchors = _host(anchors, np.float32).reshape(-1, 2)
-    mask = _host(mask, np.int32).reshape(-1)
+    anchors = _np(anchors, np.float32).reshape(-1, 2)
+    mask = _np(mask, np.int32).reshape(-1)
     B, C, h, w, max_boxes, n, total = _loss_shapes(x, truth, mask, anchors, classes)
-    with torch.cuda.device(dev):
-        d_x, d_t = _dev(torch, dev, x, torch.float32), _dev(torch, dev, truth, torch.float32)
-        d_a, d_m = _dev(torch, dev, anchors, torch.float32), _dev(torch, dev, mask, torch.int32)
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        r = {"cost": new((1,), torch.float64), "stats": new((7,), torch.float64), "delta": torch.empty_like(d_x),
-             "act": torch.empty_like(d_x) if want_act else None}
-        partial = new((max(int(_lib.lib().bp_yolo_loss_partials(B, n, classes, h, w)), 1),), torch.float64)
-        _lib.check(_lib.lib().bp_yolo_loss(_lib.ptr(d_x), B, C, n, classes, h, w, int(net_size[1]), int(net_size[0]), _lib.ptr(d_a),
-                                           total, _lib.ptr(d_m), _lib.ptr(d_t), max_boxes, ignore_thresh, truth_thresh,
-                                           int(focal_loss), _lib.ptr(r["act"]), _lib.ptr(r["delta"]), _lib.ptr(r["cost"]),
-                                           _lib.ptr(r["stats"]), _lib.ptr(partial), _stream(torch, dev)))
-        return r
+    d_x, d_t = side.put(x, np.float32), side.put(truth, np.float32)
+    shape = tuple(d_x.shape)
+    r = {"cost": side.empty(1, np.float64), "stats": side.empty(7, np.float64), "delta": side.empty(shape, np.float32),
+         "act": side.empty(shape, np.float32) if want_act else None}
+    partial = side.empty(max(int(_lib.lib().bp_yolo_loss_partials(B, n, classes, h, w)), 1), np.float64)
+    side.call("bp_yolo_loss", d_x, B, C, n, classes, h, w, int(net_size[1]), int(net_size[0]), side.put(anchors), total,
+              side.put(mask), d_t, max_boxes, ignore_thresh, truth_thresh, int(focal_loss), r["act"], r["delta"], r["cost"],
+              r["stats"], partial)
+    return r
 
 
 def yolo_loss(x, truth, net_size, anchors, mask, classes=1, ignore_thresh=0.7, truth_thresh=1.0, focal_loss=0, want_act=True,
@@ -140,23 +108,9 @@ def yolo_loss(x, truth, net_size, anchors, mask, classes=1, ignore_thresh=0.7, t
     on ``device``, arrays otherwise; ``act`` None without ``want_act``).  ``delta`` is the descent direction Darknet
     adds in backward_yolo_layer, not a derivative."""
     from . import _lib
-    if device is None:
-        xs, t = _host(x, np.float32), _host(truth, np.float32)
-        anchors = _host(anchors, np.float32).reshape(-1, 2)
-        mask = _host(mask, np.int32).reshape(-1)
-        B, C, h, w, max_boxes, n, total = _loss_shapes(xs, t, mask, anchors, classes)
-        cost, stats = np.empty(1, np.float64), np.empty(7, np.float64)
-        delta = np.empty_like(xs)
-        act = np.empty_like(xs) if want_act else None
-        partial = np.empty(max(int(_lib.lib().bp_yolo_loss_partials(B, n, classes, h, w)), 1), np.float64)
-        _lib.check(_lib.lib().bp_yolo_loss_host(_lib.ptr(xs), B, C, n, classes, h, w, int(net_size[1]), int(net_size[0]),
-                                                _lib.ptr(anchors), total, _lib.ptr(mask), _lib.ptr(t), max_boxes, ignore_thresh,
-                                                truth_thresh, int(focal_loss), _lib.ptr(act), _lib.ptr(delta), _lib.ptr(cost),
-                                                _lib.ptr(stats), _lib.ptr(partial)))
-        return float(cost[0]), dict(zip(STAT_NAMES, stats.tolist())), delta, act
-    torch, dev = _on_device(device)
-    r = _loss_device(torch, dev, x, truth, net_size, anchors, mask, classes, ignore_thresh, truth_thresh, focal_loss, want_act)
-    return float(r["cost"].cpu()[0]), dict(zip(STAT_NAMES, r["stats"].cpu().tolist())), r["delta"], r["act"]
+    side = _lib.Side(device)
+    r = _loss_call(side, x, truth, net_size, anchors, mask, classes, ignore_thresh, truth_thresh, focal_loss, want_act)
+    return float(side.get(r["cost"])[0]), dict(zip(STAT_NAMES, side.get(r["stats"]).tolist())), r["delta"], r["act"]
 
 
 def region_line(stats, cells, index=0):
@@ -183,8 +137,9 @@ def _yolo_loss_class():
         @staticmethod
         def forward(ctx, x, truth, net_size, anchors, mask, classes=1, ignore_thresh=0.7, truth_thresh=1.0):
             if x.is_cuda:
-                r = _loss_device(torch, x.device, x.detach(), truth.detach(), net_size, anchors, mask, classes, ignore_thresh,
-                                 truth_thresh, 0, False)
+                from . import _lib
+                r = _loss_call(_lib.Side(x.device), x.detach(), truth.detach(), net_size, anchors, mask, classes, ignore_thresh,
+                               truth_thresh, 0, False)
                 cost, delta, stats = r["cost"][0].to(torch.float32), r["delta"], r["stats"]
             else:
                 c, st, d, _ = yolo_loss(x.detach(), truth.detach(), net_size, anchors, mask, classes, ignore_thresh, truth_thresh,
